@@ -17,9 +17,15 @@ switches off (library options gemm_splitk = 0, attn_streamk = 0), to bf16 noise 
 every receive buffer has been re-used; a transport that fails moves ALL ranks one rung down the ladder
 p2p (coarse receive buffers) -> p2p-fine (fine-grained) -> torch.distributed, and the line says which rung ran.
 
-Prints ONE JSON line (rank 0).  Extra objects: ``roofline`` for the dominant kernel BY TIME (the GEMM kernel: half of
-the step; measured live with HIP events on the launch stream), ``attn_roofline`` for the joint attention beside it, and
-``cpu_baseline`` (the CPU oracle timed on this box's host cores, rank 0, N = 1).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (``value``,
+``ms_per_step``, ...).  ``--full`` adds what is measured or checked beside it: the board calibration, ``roofline`` for
+the dominant kernel BY TIME (the GEMM kernel: half of the step; measured live with HIP events on the launch stream in a
+second pass), ``attn_roofline`` for the joint attention beside it, the fp8-weights and large-q/k-gain variants,
+``cpu_baseline`` (the CPU oracle timed on this box's host cores, rank 0, N = 1), and for N > 1 the CFG pair (N >= 4) and
+the P2P exchange probe.  The ``--no-*`` switches leave single pieces of that out.
+
+``--dump-outputs DIR`` writes what the last timed step returned (the noise prediction) as ``DIR/noise_pred.npy`` in fp32;
+weights and inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -170,6 +176,23 @@ def pmc_traffic(world, *kernels):
     return None
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """``arrays`` (name -> tensor) as ``directory/<name>.npy`` in fp32.  Above DUMP_BYTES in all, each array is replaced by
+    the same seeded sample of its flattened elements (sorted indices from a fixed generator) in every run."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() > share:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, f"{name}.npy"), a.numpy())
+
+
 def self_launch(n):
     """One rank per GPU through ``python -m torch.distributed.run`` (the command shape the driver itself uses), rendezvous
     on 127.0.0.1 and a free port; every argument of this invocation is passed on.  Returns the child's exit code."""
@@ -213,7 +236,20 @@ def main():
     ap.add_argument("--no-qk-gain-variant", action="store_true", help="skip the extra large-q/k-gain measurement beside the headline")
     ap.add_argument("--fp8-weights", action="store_true",
                     help="BASELINE config 5's weight format: e4m3 operands in the DiT Linears (not the headline, which is bf16)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what stands beside the headline: board calibration, per-kernel event pass and "
+                         "rooflines, fp8-weights and large-q/k-gain variants, CPU baseline, N >= 4 CFG pair, P2P exchange probe")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's output as DIR/noise_pred.npy (fp32; a seeded sample above 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.cpu_baseline_config0 and not args.full:
+        ap.error("--cpu-baseline-config0 is part of --full")
+    if not args.full:
+        # a plain run does only what its headline figure needs
+        args.no_calibration = args.no_kernel_timers = args.no_fp8_variant = args.no_qk_gain_variant = True
+        args.no_cpu_baseline = args.no_cfg_pair_variant = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as a CHILD process (this process has
@@ -386,7 +422,7 @@ def main():
         if not noise_ok:
             raise SystemExit(f"the sharded step in its default mode is not within bf16 summation noise of the unsharded step: {validation}")
         del ref_strict
-        if getattr(model, "_seq_p2p", None) is not None:
+        if args.full and getattr(model, "_seq_p2p", None) is not None:
             # what the push kernel does to the links of THIS node: one all-to-all of the packed q|k|v exchange's size, every
             # rank's figure (diagnostic, outside the timed region)
             probe = model._seq_p2p.exchange_probe(mbytes_per_peer=max(1, 40 // model._seq_p2p.world))
@@ -435,6 +471,8 @@ def main():
         dt, out = timed_region()
     # (a P2P wait that gave up poisons the step's output with NaN; check_gemm_workspace below raises on the same condition)
     assert torch.isfinite(out.float()).all(), "non-finite output after the timed steps"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"noise_pred": out})      # before any later pass re-uses the engine's buffers
     if dist is not None:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -1,6 +1,6 @@
 """The bench.py contract (one JSON line; metric / config of BASELINE.json; roofline and cpu_baseline objects) checked on the
 committed output of the end-of-round run (profiles/r6_final_bench.json = stdout of ``python bench.py --steps 20 --warmup 5``
-on an MI355X) and on the script's command line, without a GPU."""
+on an MI355X, what ``--full`` prints now) and on the script's command line, without a GPU."""
 import json
 import os
 import subprocess
@@ -87,8 +87,29 @@ def test_committed_rehearsal_lines_of_the_n_gpu_path_carry_their_own_reference()
 def test_bench_command_line_parses_without_a_gpu():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in out.stdout
+    # the extras beside the headline are measured only with --full; zero timed steps is refused
+    for bad in (["--cpu-baseline-config0"], ["--steps", "0"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *bad], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and "error" in r.stderr, bad
+
+
+def test_dumped_outputs_are_fp32_and_a_fixed_sample_above_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: the step's output in fp32 as it is; above the size limit the same seeded sample of it in every run."""
+    import numpy as np
+    import torch
+    import bench
+    t = torch.randn(2, 3, 16, 6, 9, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "a"), {"noise_pred": t})
+    a = np.load(tmp_path / "a" / "noise_pred.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, t.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"noise_pred": t})
+    b, c = (np.load(tmp_path / d / "noise_pred.npy") for d in ("b", "c"))
+    assert b.shape == (100,) and b.dtype == np.float32 and np.array_equal(b, c)
+    assert np.isin(b, t.float().numpy().ravel()).all()
 
 
 def test_bench_starts_its_own_ranks_when_no_launcher_did():

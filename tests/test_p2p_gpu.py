@@ -191,7 +191,7 @@ def test_bench_two_ranks_validates_against_the_unsharded_step_and_walks_the_ladd
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--layers", "2", "--steps", "1", "--warmup", "1",
-            "--no-cpu-baseline", "--no-fp8-variant", "--no-kernel-timers"]
+            "--full", "--no-cpu-baseline", "--no-fp8-variant", "--no-kernel-timers"]
     for fake, want in (("", "p2p"), ("1", "torch")):
         env = dict(os.environ, BYA_BENCH_SHARE_GPU="1", BYA_BENCH_FAKE_MISMATCH=fake, HSA_ENABLE_IPC_MODE_LEGACY="0")
         env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)

@@ -7,7 +7,7 @@ R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
 out = {}
 for rnd in range(2):
     for tag, env in (("branchfree", {}), *([("side_build", {"BYA_HIP_LIB": os.environ["QKN_AB_SIDE_LIB"]})] if os.environ.get("QKN_AB_SIDE_LIB") else []), ("two_launches", {"BYA_QKN_EPILOGUE": "0"})):
-        r = subprocess.run([sys.executable, R + "/bench.py", "--no-cpu-baseline", "--no-fp8-variant", "--no-qk-gain-variant", "--steps", "6", "--warmup", "2"],
+        r = subprocess.run([sys.executable, R + "/bench.py", "--full", "--no-cpu-baseline", "--no-fp8-variant", "--no-qk-gain-variant", "--steps", "6", "--warmup", "2"],
                            env=dict(os.environ, **env), capture_output=True, text=True)
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         out.setdefault(tag, []).append((round(d["ms_per_step"], 2), d["kernel_ms_per_step"]["bya_gemm_bf16"], d["kernel_ms_per_step"].get("bya_qknorm_rope")))

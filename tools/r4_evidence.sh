@@ -2,7 +2,9 @@
 TAG=${1:-r4_e}
 export TMPDIR=/tmp
 R=$PWD
-python bench.py --steps 10 --warmup 3 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
+OUT=${OUT:-out}                 # folder of the bench lines below
+mkdir -p "$OUT"
+python bench.py --full --steps 10 --warmup 3 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 cd /tmp
 timeout 900 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/${TAG}_prof --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timers --no-fp8-variant > $R/gpurun_out/${TAG}_prof.log 2>&1
 cd $R

@@ -6,6 +6,8 @@
 #   D  bench.py --gpus 2 / 4 / 8 at full depth with the ranks on this one GPU (rehearsal of the N > 1 path)  ~15 min
 export TMPDIR=/tmp
 R=$PWD
+OUT=${OUT:-out}                 # folder of the bench lines below
+mkdir -p "$OUT"
 mkdir -p gpurun_out
 PARTS="${*:-A B C D}"
 for P in $PARTS; do
@@ -13,7 +15,7 @@ case $P in
 A)
   python -m pytest tests -q -m gpu --durations=25 > gpurun_out/r6_final_pytest_gpu.txt 2>&1
   python __graft_entry__.py --smoke > gpurun_out/r6_final_smoke.txt 2>&1
-  python bench.py --steps 20 --warmup 5 > gpurun_out/r6_final_bench.json 2> gpurun_out/r6_final_bench.err
+  python bench.py --full --steps 20 --warmup 5 > "$OUT/r6_final_bench.json" 2> "$OUT/r6_final_bench.err"
   ;;
 B)
   cd /tmp
@@ -40,7 +42,7 @@ C)
   ;;
 D)
   for N in 2 4 8; do
-    BYA_BENCH_SHARE_GPU=1 timeout 1200 python bench.py --gpus $N --steps 3 --warmup 2 --no-cpu-baseline --no-fp8-variant --no-qk-gain-variant > gpurun_out/r6_final_bench_${N}_ranks_on_one_gpu_42_layers.json 2> gpurun_out/r6_final_bench_${N}_ranks.err
+    BYA_BENCH_SHARE_GPU=1 timeout 1200 python bench.py --full --gpus $N --steps 3 --warmup 2 --no-cpu-baseline --no-fp8-variant --no-qk-gain-variant > "$OUT/r6_final_bench_${N}_ranks_on_one_gpu_42_layers.json" 2> "$OUT/r6_final_bench_${N}_ranks.err"
   done
   ;;
 esac
