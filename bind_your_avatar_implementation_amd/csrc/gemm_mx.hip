@@ -1,0 +1,297 @@
+// MX (OCP Microscaling) "NT" GEMM on the block-scaled CDNA4 matrix instruction, and the block quantiser that feeds it:
+//     C[m,n] = epi( sum_k A[m,k] * W[n,k] ),   A, W = e8m0 scale per 32 consecutive k  x  e4m3 / e2m3 elements
+// Format and storage: include/bya.h, "MX weights".  The four big Linears of a DiT block (attn1.to_q|k|v, attn1.to_out,
+// ff.net.0.proj, ff.net.2 -- models/transformer.py:241-260) when the engine is built with MX weights
+// (enable_mx_weights).  No reference counterpart; parity is against the CPU restatement on the same bytes
+// (tests/test_mx_gpu.py).
+//
+// v_mfma_scale_f32_16x16x128_f8f6f4: 128 k per instruction; the scale VGPR of lane l carries the scale of row l & 15 for
+// K-block l >> 4 of the step (byte selected by op_sel; the kernel shifts the lane's byte into position 0).  Which k a lane's
+// operand VGPRs hold depends on the element width -- measured with one-hot W and a distinct scale per block
+// (tests/test_mx_gpu.py, operand-map test on exact data):
+//   - e2m3: six VGPRs = the 24 bytes of block l >> 4, element i at bits 6i.. (runs at the fp4 rate, twice the e4m3 rate);
+//   - e4m3: VGPRs 0-3 hold k = 16 (l >> 4) .. +15, VGPRs 4-7 hold k = 64 + 16 (l >> 4) .. +15 -- the instruction's 32-k
+//     block b is then bytes 16 b .. 16 b + 15 of the first and of the second 64-k half of lanes 32 (b / 2) ..., so a lane
+//     filled with one contiguous 32-byte block (the layout of gemm_fp8_kernel.h, correct there only because its scales are
+//     all 2^0) gets the wrong scale on half its bytes.  The kernel reads 16-byte chunks g and 4 + g of the K-tile for lane
+//     group g: the instruction's block b is then exactly k = 32 b .. 32 b + 31 of the tile, as stored.
+//
+// The kernel is the 128 x 128 tile of gemm_fp8_kernel.h (4 waves of 64 x 64, two-stage LDS ring fed by global_load_lds,
+// group-M tile order) with real block scales, and for big e2m3 launches the same loop on 256 x 256 tiles (8 waves of
+// 64 x 128):
+//   - a K-tile is 128 elements = 128 bytes (e4m3: the XOR-swizzled image of the fp8 kernel) or 96 bytes (e2m3: rows stored
+//     back to back with chunk pairs swapped on every other group of 8 rows, 16 bytes per lane and DMA instruction, the
+//     lane's block read as three 8-byte pieces);
+//   - the 4 scale bytes of a row for one K-tile are one dword; the block's 256 rows' dwords ride in the same LDS stage
+//     (one 4-byte global_load_lds per wave), so their wait is the ring's own vmcnt(0).
+#include "gemm_common.h"
+#include "mx_common.h"
+#include "options.h"
+
+namespace {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int MX_BK = 128;                 // elements per K-tile (one MFMA step)
+constexpr int MX_GROUP_M = 8;              // row-tiles per group of the tile order (as the fp8 kernel)
+__host__ __device__ constexpr int mx_tile_row_bytes(int fmt) { return fmt == MX_E4M3 ? 128 : 96; }
+// e2m3 launches of >= 200 256 x 256 tiles run on 256 x 256 tiles (8 waves, one workgroup per CU, half the L2 -> LDS bytes
+// per FLOP of the 128 x 128 tile: 572 vs 699 us at q|k|v, 706 vs 978 us at ff.net.2), everything else on 128 x 128 tiles.
+// The ring is two stages deep; three (a counted wait keeping the next K-tile's DMA in flight across the barrier) measured
+// no faster, so DMA latency is not the bound.  Side builds flip both (tools/mx_gemm_ablate.py).
+#ifndef BYA_MX_E2M3_STAGES
+#define BYA_MX_E2M3_STAGES 2
+#endif
+static_assert(BYA_MX_E2M3_STAGES == 2 || BYA_MX_E2M3_STAGES == 3, "e2m3 ring: two or three stages");
+#ifndef BYA_MX_E2M3_BIG_TILE
+#define BYA_MX_E2M3_BIG_TILE 1
+#endif
+__host__ __device__ constexpr int mx_stages(int fmt) { return fmt == MX_E4M3 ? 2 : BYA_MX_E2M3_STAGES; }
+
+// ROWS x RB bytes of one K-tile into LDS, 1 KiB per wave-instruction.
+template <int FMT, int ROWS, int NWAVES>
+__device__ __forceinline__ void stage_mx(const uint8_t* __restrict__ src, int ld, int row0, int row_max, int kb0,
+                                         char* lds_tile, int wave, int lane) {
+    if constexpr (FMT == MX_E4M3) {
+        // 8 rows per instruction; 16-byte chunk c of row r lands at chunk c ^ ((r >> 1) & 7)
+        constexpr int PER_WAVE = ROWS / NWAVES;
+#pragma unroll
+        for (int q = 0; q < PER_WAVE / 8; ++q) {
+            const int rbase = wave * PER_WAVE + q * 8;
+            const int rl = rbase + (lane >> 3);
+            const int chunk = (lane & 7) ^ ((rl >> 1) & 7);
+            int gr = row0 + rl;
+            gr = gr < row_max ? gr : row_max;
+            const uint8_t* g = src + (long long)gr * ld + kb0 + chunk * 16;
+            __builtin_amdgcn_global_load_lds(GLOBAL_PTR(g), LDS_PTR(lds_tile + rbase * 128), 16, 0, 0);
+        }
+    } else {
+        // 96-byte rows back to back: byte t of the tile is row t / 96, offset t % 96 (a multiple of 16).  16-byte chunk c of
+        // row r lands at chunk c ^ ((r >> 3) & 1) (pairs 0|1, 2|3, 4|5 stay in the row): rows r and r + 8, 768 bytes apart, hit
+        // the same banks unswizzled -- a 2-way conflict on every fragment read
+        constexpr int RB = 96, INSTR = ROWS * RB / 1024, PER_WAVE = INSTR / NWAVES;
+        static_assert(INSTR % NWAVES == 0, "tile must split evenly over the waves");
+#pragma unroll
+        for (int q = 0; q < PER_WAVE; ++q) {
+            const int qi = wave * PER_WAVE + q;
+            const int t = qi * 1024 + lane * 16;
+            const int rl = t / RB, off = t - rl * RB;
+            int gr = row0 + rl;
+            gr = gr < row_max ? gr : row_max;
+            const uint8_t* g = src + (long long)gr * ld + kb0 + (off ^ (((rl >> 3) & 1) << 4));
+            __builtin_amdgcn_global_load_lds(GLOBAL_PTR(g), LDS_PTR(lds_tile + qi * 1024), 16, 0, 0);
+        }
+    }
+}
+
+// lane group g's operand of one row (e4m3: k = 16 g .. +15 and 64 + 16 g .. +15; e2m3: block g = k = 32 g .. 32 g + 31)
+template <int FMT>
+__device__ __forceinline__ i32x8 lds_frag_mx(const char* tile, int row, int g) {
+    if constexpr (FMT == MX_E4M3) {
+        const int sw = (row >> 1) & 7;
+        const i32x4 lo = *reinterpret_cast<const i32x4*>(tile + row * 128 + ((g ^ sw) << 4));
+        const i32x4 hi = *reinterpret_cast<const i32x4*>(tile + row * 128 + (((4 + g) ^ sw) << 4));
+        return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    } else {
+        const char* r = tile + row * 96;
+        const int x = ((row >> 3) & 1) << 4, o = g * 24;                    // (the staging's chunk swizzle)
+        const i32x2 p0 = *reinterpret_cast<const i32x2*>(r + (o ^ x));
+        const i32x2 p1 = *reinterpret_cast<const i32x2*>(r + ((o + 8) ^ x));
+        const i32x2 p2 = *reinterpret_cast<const i32x2*>(r + ((o + 16) ^ x));
+        return i32x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], 0, 0};
+    }
+}
+
+template <int FMT, int BM, int BN, int WAVES_M, int WAVES_N>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_kernel(GemmArgs p, const uint8_t* __restrict__ sa,
+                                                                         const uint8_t* __restrict__ sw, int GM) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NWAVES = WAVES_M * WAVES_N, RB = mx_tile_row_bytes(FMT);
+    constexpr int TILE_A = BM * RB, TILE_W = BN * RB, SCALES = (BM + BN) * 4, STAGE = TILE_A + TILE_W + SCALES;
+    static_assert(BM + BN == 64 * WAVES_M * WAVES_N, "one scale row per lane of the block");
+    constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, MI = WM / 16, NI = WN / 16;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+    const int nwg = tiles_m * tiles_n;
+    const int id = xcd_remap(blockIdx.x, nwg);
+    const int per_group = GM * tiles_n;
+    const int group = id / per_group, first_m = group * GM;
+    const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
+    const int in_g = id - group * per_group;
+    const int tm = first_m + in_g % gsz, tn = in_g / gsz;
+    const int m0 = tm * BM, n0 = tn * BN;
+    const int z = blockIdx.z;
+
+    const uint8_t* A = reinterpret_cast<const uint8_t*>(p.A) + (long long)z * p.a_bs;
+    const uint8_t* W = reinterpret_cast<const uint8_t*>(p.W);
+    const int nk = p.K / MX_BK, ks = p.K / 32;          // K-tiles; scale bytes per row
+
+    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    // The K-tile's 4 scale bytes of every A and W row travel through the LDS ring with the codes: one 4-byte DMA per lane
+    // (lane t of the block: A row t, or W row t - BM), clamped like the staged rows.  (Eight scattered dword loads per wave and
+    // K-tile straight into registers doubled the kernel's time: DESIGN.md section 11.)
+    const uint8_t* srow;
+    {
+        const bool is_a = tid < BM;
+        const int r = is_a ? m0 + tid : n0 + tid - BM, rmax = is_a ? p.M - 1 : p.N - 1;
+        srow = is_a ? sa + ((long long)z * p.M + (r < rmax ? r : rmax)) * ks : sw + (long long)(r < rmax ? r : rmax) * ks;
+    }
+    auto stage = [&](int kt, int buf) {
+        char* base = smem + buf * STAGE;
+        stage_mx<FMT, BM, NWAVES>(A, p.lda, m0, p.M - 1, kt * RB, base, wave, lane);
+        stage_mx<FMT, BN, NWAVES>(W, p.ldw, n0, p.N - 1, kt * RB, base + TILE_A, wave, lane);
+        __builtin_amdgcn_global_load_lds(GLOBAL_PTR(srow + 4 * kt), LDS_PTR(base + TILE_A + TILE_W + wave * 256), 4, 0, 0);
+    };
+
+    f32x4 acc[NI][MI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < MI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int sh = 8 * fq;                               // this lane's block within the K-tile -> its scale byte
+    // Ring of NST stages.  Two deep (e4m3): every K-tile waits for all its loads, then one barrier.  Three deep (e2m3): the
+    // wait is counted -- the loads of the next K-tile stay in flight across the barrier (a raw s_barrier: __syncthreads
+    // would make hipcc drain them), so a K-tile's DMA has two K-tiles of compute to land in instead of none.
+    constexpr int NST = mx_stages(FMT);
+    constexpr int VM_STAGE = (FMT == MX_E4M3 ? (BM + BN) / NWAVES / 8 : (BM + BN) * RB / 1024 / NWAVES) + 1;  // DMAs per wave
+    for (int s0 = 0; s0 < NST - 1 && s0 < nk; ++s0) stage(s0, s0);
+    for (int kt = 0; kt < nk; ++kt) {
+        if constexpr (NST == 2) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        } else {
+            if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(VM_STAGE) : "memory");   // K-tile kt landed
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();               // ... for every wave, and every wave is done with stage (kt - 1) % NST
+        }
+        if (kt + NST - 1 < nk) stage(kt + NST - 1, (kt + NST - 1) % NST);
+        const char* ta = smem + (kt % NST) * STAGE;
+        const char* tw = ta + TILE_A;
+        const uint32_t* ts = reinterpret_cast<const uint32_t*>(tw + TILE_W);
+        int xa[MI], xw[NI];
+#pragma unroll
+        for (int j = 0; j < MI; ++j) xa[j] = (int)(ts[wm * WM + j * 16 + fr] >> sh);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) xw[i] = (int)(ts[BM + wn * WN + i * 16 + fr] >> sh);
+        i32x8 fa[MI], fw[NI];
+#pragma unroll
+        for (int j = 0; j < MI; ++j) fa[j] = lds_frag_mx<FMT>(ta, wm * WM + j * 16 + fr, fq);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) fw[i] = lds_frag_mx<FMT>(tw, wn * WN + i * 16 + fr, fq);
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+            for (int j = 0; j < MI; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[i], fa[j], acc[i][j], FMT, FMT,
+                                                                             0, xw[i], 0, xa[j]);
+    }
+
+    // Lane holds C[m][n4 .. n4+3], m = m_base + 16 j, n4 = n_base + 16 i (W fragment = the instruction's A operand)
+    const int m_base = m0 + wm * WM + fr, n_base = n0 + wn * WN + fq * 4;
+    auto run = [&](auto act_tag) {
+        epilogue_block<decltype(act_tag)::value, NI, MI, (NI * MI > 16 ? 1 : NI)>(p, z, m_base, n_base, acc);
+    };
+    dispatch_act_big(p.act, run);
+}
+
+template <int FMT, int BM, int BN, int WAVES_M, int WAVES_N>
+int launch_mx(const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, int batch, hipStream_t s) {
+    const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
+    dim3 grid(tiles_m * tiles_n, 1, batch);
+    const size_t lds = (size_t)mx_stages(FMT) * (BM + BN) * (mx_tile_row_bytes(FMT) + 4);
+    static std::atomic<unsigned long long> attr_done{0};
+    auto kern = gemm_mx_kernel<FMT, BM, BN, WAVES_M, WAVES_N>;
+    if (bya_allow_big_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
+    BYA_LAUNCH(kern, grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a, sa, sw, MX_GROUP_M);
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+// ---- standalone quantiser: one lane per 8 consecutive elements (one 16-byte load), a lane quad per block.
+template <int FMT>
+__global__ __launch_bounds__(256) void quantize_mx_kernel(const bf16_t* __restrict__ x, uint8_t* __restrict__ q,
+                                                          uint8_t* __restrict__ scales, long long M, int K, long long ldx) {
+    const long long per_row = K / 8, total = M * per_row;
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool ok = gid < total;                       // (total % 4 == 0: a quad is all in or all out)
+    const long long row = ok ? gid / per_row : 0;
+    const int c = ok ? (int)(gid - row * per_row) : 0;
+    float v[8];
+    if (ok) unpack8(*reinterpret_cast<const u32x4*>(x + row * ldx + c * 8), v);
+    else
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = 0.f;
+    float amax = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[e]));
+    amax = quad_amax(amax);
+    if (!ok) return;
+    const long long row_bytes = (long long)K / 32 * mx_block_bytes(FMT);
+    const int part = c & 3, blk = c >> 2;
+    uint8_t* dst = q + row * row_bytes + (long long)blk * mx_block_bytes(FMT) + part * (mx_block_bytes(FMT) / 4);
+    const uint32_t sb = mx_quant8<FMT>(v, amax, dst);
+    if (part == 0) scales[row * (K / 32) + blk] = (uint8_t)sb;
+}
+
+}  // namespace
+
+extern "C" int bya_quantize_mx(const void* x, void* codes, void* scales, int32_t M, int32_t K, int64_t ldx, int32_t fmt,
+                               hipStream_t stream) {
+    if (!x || !codes || !scales || M <= 0 || K <= 0 || K % 128) return BYA_ERR_SHAPE;
+    if (fmt != MX_E4M3 && fmt != MX_E2M3) return BYA_ERR_SHAPE;
+    if (ldx < K || ldx % 8 || ((uintptr_t)x & 15) || ((uintptr_t)codes & 7)) return BYA_ERR_ALIGN;
+    const long long total = (long long)M * (K / 8);
+    dim3 grid((unsigned)((total + 255) / 256));
+    if (fmt == MX_E4M3)
+        BYA_LAUNCH(quantize_mx_kernel<MX_E4M3>, grid, dim3(256), 0, stream, (const bf16_t*)x, (uint8_t*)codes,
+                   (uint8_t*)scales, (long long)M, K, (long long)ldx);
+    else
+        BYA_LAUNCH(quantize_mx_kernel<MX_E2M3>, grid, dim3(256), 0, stream, (const bf16_t*)x, (uint8_t*)codes,
+                   (uint8_t*)scales, (long long)M, K, (long long)ldx);
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+extern "C" int bya_gemm_mx(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                           void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
+                           int32_t fmt, hipStream_t stream) {
+    if (!A || !W || !a_scales || !w_scales || !C || !d) return BYA_ERR_SHAPE;
+    if (fmt != MX_E4M3 && fmt != MX_E2M3) return BYA_ERR_SHAPE;
+    if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return BYA_ERR_SHAPE;
+    if (d->K % MX_BK != 0 || d->N % 4 != 0) return BYA_ERR_SHAPE;
+    if ((long long)d->batch * d->M * (d->K / 32) >= (1LL << 31) || (long long)d->N * (d->K / 32) >= (1LL << 31))
+        return BYA_ERR_SHAPE;
+    const int row_bytes = d->K / 32 * mx_block_bytes(fmt);
+    if (d->lda < row_bytes || d->ldw < row_bytes) return BYA_ERR_SHAPE;
+    if (d->lda % 16 || d->ldw % 16 || d->ldc % 4 || (res && d->ldres % 4) || d->a_batch_stride % 16) return BYA_ERR_ALIGN;
+    if (((uintptr_t)A | (uintptr_t)W) & 15) return BYA_ERR_ALIGN;
+    if (((uintptr_t)a_scales | (uintptr_t)w_scales) & 3) return BYA_ERR_ALIGN;
+    if (((uintptr_t)C | (uintptr_t)res | (uintptr_t)bias | (uintptr_t)gate0 | (uintptr_t)gate1) & 7) return BYA_ERR_ALIGN;
+    if (!act_on_big_tiles(d->act)) return BYA_ERR_UNSUPPORTED;            // none / GELU(tanh): the DiT Linears
+    if (d->n_split < 0 || (d->n_split > 0 && (d->n_split % 4 || d->c_split_stride % 4 || res))) return BYA_ERR_SHAPE;
+    GemmArgs a;
+    a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C;
+    a.res = (const bf16_t*)res; a.gate0 = (const bf16_t*)gate0; a.gate1 = (const bf16_t*)(gate1 ? gate1 : gate0);
+    a.M = d->M; a.N = d->N; a.K = d->K;
+    a.lda = d->lda; a.ldw = d->ldw; a.ldc = d->ldc; a.ldres = d->ldres;
+    a.a_bs = d->a_batch_stride; a.c_bs = d->c_batch_stride; a.res_bs = d->res_batch_stride;
+    a.gate_bs = d->gate_batch_stride; a.gate_split = d->gate_split; a.act = d->act; a.leaky = 0.01f;
+    a.n_split = d->n_split; a.c_split_stride = d->c_split_stride;
+    a.bias_rowscale = d->bias_rowscale; a.alpha = d->alpha == 0.0f ? 1.0f : d->alpha;
+    a.ws_counters = nullptr; a.ws_slabs = nullptr;
+    const uint8_t* sa = (const uint8_t*)a_scales;
+    const uint8_t* sw = (const uint8_t*)w_scales;
+    const long long ks = d->K / 32;
+    const long long tiles256 = (long long)((d->M + 255) / 256) * ((d->N + 255) / 256) * d->batch;
+    const bool big = BYA_MX_E2M3_BIG_TILE && tiles256 >= 200;          // (about a round of 256 CUs, or more)
+    return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
+        if (fmt == MX_E4M3) return launch_mx<MX_E4M3, 128, 128, 2, 2>(piece, sa + row0 * ks, sw, batch, stream);
+        if (big) return launch_mx<MX_E2M3, 256, 256, 4, 2>(piece, sa + row0 * ks, sw, batch, stream);
+        return launch_mx<MX_E2M3, 128, 128, 2, 2>(piece, sa + row0 * ks, sw, batch, stream);
+    });
+}

@@ -8,6 +8,7 @@
 // (models/audio_model.py:249), diffusers Attention.norm_q/norm_k + apply_rotary_emb (transformer.py:204-208).
 #include "bya_common.h"
 #include "qknorm_math.h"
+#include "mx_common.h"
 #include "../../include/bya.h"
 #include <stdlib.h>
 #include "options.h"
@@ -23,6 +24,8 @@ struct LnArgs {
     // fp8 output (bya_layernorm_fp8): y is then a byte matrix (ldy / y_bs in bytes) and q_scale[z * rows_per_batch + row]
     // receives the row's scale
     float* q_scale;
+    // MX output (bya_layernorm_mx): y is then a code matrix (ldy / y_bs in bytes), mx_scales[(z * rows_per_batch + row) * D / 32 + b]
+    uint8_t* mx_scales;
 };
 
 template <int VEC>
@@ -36,8 +39,9 @@ __device__ __forceinline__ void load_vec(const bf16_t* p, float* f) {
 }
 
 // D = 64 * VEC * NV ; each lane owns NV vectors of VEC contiguous elements, vector v at column (v*64 + lane)*VEC
-template <int VEC, int NV, bool Q8 = false>
+template <int VEC, int NV, bool Q8 = false, int MXF = -1>
 __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
+    static_assert(MXF < 0 || (VEC == 8 && !Q8), "MX output: 8-element vectors (a lane quad per 32-block)");
     constexpr int D = 64 * VEC * NV;
     const int lane = threadIdx.x & 63;
     const long long row_lin = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -46,7 +50,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
     const int z = (int)(row_lin / p.rows_per_batch);
     const long long row = row_lin - (long long)z * p.rows_per_batch;
     const bf16_t* x = p.x + z * p.x_bs + row * p.ldx;
-    bf16_t* y = Q8 ? nullptr : p.y + z * p.y_bs + row * p.ldy;
+    bf16_t* y = (Q8 || MXF >= 0) ? nullptr : p.y + z * p.y_bs + row * p.ldy;
 
     float v[NV][VEC];
     float sum = 0.f;
@@ -103,7 +107,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
                 for (int e = 0; e < VEC; ++e) o[e] = o[e] * (1.0f + sc[e]) + sh[e];
             }
         }
-        if constexpr (Q8) {
+        if constexpr (Q8 || MXF >= 0) {
             // keep the result -- rounded to bf16 exactly as the bf16 kernel would store it -- for the row maximum
 #pragma unroll
             for (int e = 0; e < VEC; e += 2) {
@@ -144,6 +148,22 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
             } else {
                 *reinterpret_cast<uint32_t*>(q + col) = w[0];
             }
+        }
+    }
+    if constexpr (MXF >= 0) {
+        // bya_quantize_mx of the row this wave just normalised: vector i of lane l is part l & 3 of block 16 i + l / 4
+        uint8_t* q = reinterpret_cast<uint8_t*>(p.y) + z * p.y_bs + row * p.ldy;
+        uint8_t* sc = p.mx_scales + (z * p.rows_per_batch + row) * (D / 32);
+        constexpr int PART = mx_block_bytes(MXF) / 4;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            float amax = 0.f;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) amax = fmaxf(amax, fabsf(v[i][e]));
+            amax = quad_amax(amax);
+            const int blk = i * 16 + (lane >> 2);
+            const uint32_t sb = mx_quant8<MXF>(v[i], amax, q + blk * mx_block_bytes(MXF) + (lane & 3) * PART);
+            if ((lane & 3) == 0) sc[blk] = (uint8_t)sb;
         }
     }
 }
@@ -234,11 +254,11 @@ int launch_ln_adaln_rows(const LnArgs& a, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 
-template <int VEC, int NV, bool Q8 = false>
+template <int VEC, int NV, bool Q8 = false, int MXF = -1>
 int launch_ln(const LnArgs& a, hipStream_t s) {
     const long long total = a.rows_per_batch * a.batch;
     dim3 grid((unsigned)((total + 3) / 4));
-    BYA_LAUNCH((layernorm_kernel<VEC, NV, Q8>), grid, dim3(256), 0, s, a);
+    BYA_LAUNCH((layernorm_kernel<VEC, NV, Q8, MXF>), grid, dim3(256), 0, s, a);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 
@@ -340,7 +360,7 @@ extern "C" int bya_layernorm(const void* x, void* y, const void* w, const void* 
     a.shift0 = (const bf16_t*)shift0; a.scale0 = (const bf16_t*)scale0;
     a.shift1 = (const bf16_t*)(shift1 ? shift1 : shift0); a.scale1 = (const bf16_t*)(scale1 ? scale1 : scale0);
     a.rows_per_batch = rows_per_batch; a.ldx = ldx; a.ldy = ldy; a.x_bs = x_batch_stride; a.y_bs = y_batch_stride;
-    a.mod_bs = mod_batch_stride; a.split = split; a.batch = batch; a.eps = eps; a.q_scale = nullptr;
+    a.mod_bs = mod_batch_stride; a.split = split; a.batch = batch; a.eps = eps; a.q_scale = nullptr; a.mx_scales = nullptr;
     switch (D) {
         case 512: return launch_ln<8, 1>(a, stream);
         case 768: return launch_ln<4, 3>(a, stream);
@@ -369,9 +389,31 @@ extern "C" int bya_layernorm_fp8(const void* x, void* q, float* q_scale, const v
     a.shift0 = (const bf16_t*)shift0; a.scale0 = (const bf16_t*)scale0;
     a.shift1 = (const bf16_t*)(shift1 ? shift1 : shift0); a.scale1 = (const bf16_t*)(scale1 ? scale1 : scale0);
     a.rows_per_batch = rows_per_batch; a.ldx = ldx; a.ldy = ldq; a.x_bs = x_batch_stride; a.y_bs = q_batch_stride;
-    a.mod_bs = mod_batch_stride; a.split = split; a.batch = batch; a.eps = eps; a.q_scale = q_scale;
+    a.mod_bs = mod_batch_stride; a.split = split; a.batch = batch; a.eps = eps; a.q_scale = q_scale; a.mx_scales = nullptr;
     if (D != 3072) return BYA_ERR_UNSUPPORTED;          // the DiT width: the only LayerNorm in front of an fp8 Linear
     return launch_ln<8, 6, true>(a, stream);
+}
+
+extern "C" int bya_layernorm_mx(const void* x, void* q, void* q_scales, const void* w, const void* b, const void* shift0,
+                                const void* scale0, const void* shift1, const void* scale1, int64_t rows_per_batch,
+                                int32_t batch, int32_t D, int64_t ldx, int64_t ldq, int64_t x_batch_stride,
+                                int64_t q_batch_stride, int64_t mod_batch_stride, int64_t split, float eps, int32_t fmt,
+                                hipStream_t stream) {
+    if (!x || !q || !q_scales || rows_per_batch <= 0 || batch <= 0) return BYA_ERR_SHAPE;
+    if (fmt != MX_E4M3 && fmt != MX_E2M3) return BYA_ERR_SHAPE;
+    if ((shift0 == nullptr) != (scale0 == nullptr)) return BYA_ERR_SHAPE;
+    if (((uintptr_t)x & 15) || ((uintptr_t)q & 7)) return BYA_ERR_ALIGN;
+    if ((ldx | ldq | x_batch_stride | q_batch_stride) % 8) return BYA_ERR_ALIGN;
+    if (D != 3072) return BYA_ERR_UNSUPPORTED;          // the DiT width: the only LayerNorm in front of an MX Linear
+    if (ldq < (int64_t)D / 32 * mx_block_bytes(fmt)) return BYA_ERR_SHAPE;
+    LnArgs a;
+    a.x = (const bf16_t*)x; a.y = (bf16_t*)q; a.w = (const bf16_t*)w; a.b = (const bf16_t*)b;
+    a.shift0 = (const bf16_t*)shift0; a.scale0 = (const bf16_t*)scale0;
+    a.shift1 = (const bf16_t*)(shift1 ? shift1 : shift0); a.scale1 = (const bf16_t*)(scale1 ? scale1 : scale0);
+    a.rows_per_batch = rows_per_batch; a.ldx = ldx; a.ldy = ldq; a.x_bs = x_batch_stride; a.y_bs = q_batch_stride;
+    a.mod_bs = mod_batch_stride; a.split = split; a.batch = batch; a.eps = eps; a.q_scale = nullptr;
+    a.mx_scales = (uint8_t*)q_scales;
+    return fmt == MX_E4M3 ? launch_ln<8, 6, false, MX_E4M3>(a, stream) : launch_ln<8, 6, false, MX_E2M3>(a, stream);
 }
 
 extern "C" int bya_qknorm_rope(void* q, void* k, const void* qw, const void* qb, const void* kw, const void* kb,

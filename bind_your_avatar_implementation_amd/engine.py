@@ -91,6 +91,14 @@ class DenoiseEngine:
         # pack time, per-row activation scales on the fly; fp32 accumulation, bf16 everywhere else)
         self.fp8_weights = bool(getattr(model, "_fp8_weights", False)) or os.environ.get("BYA_FP8_WEIGHTS") == "1"
         self.fuse_ln_quant = os.environ.get("BYA_FP8_FUSED_LN", "1") != "0"     # AdaLN LayerNorm writes e4m3 directly
+        # MX weights (enable_mx_weights; API only): the selected Linears on OCP MX operands ("mxfp6" / "mxfp8", 32-element
+        # blocks with e8m0 scales, quantised by the instruction's own block scales -- include/bya.h, "MX weights")
+        self.mx_fmt = getattr(model, "_mx_weights", None)
+        if self.mx_fmt is not None:
+            ops.mx_fmt_code(self.mx_fmt)
+            if self.fp8_weights:
+                raise ValueError("fp8 weights (enable_fp8_weights / BYA_FP8_WEIGHTS) and MX weights (enable_mx_weights) "
+                                 "are both requested: enable one of them")
         # the remaining A/B switches of the step, read ONCE here (round 4 looked them up in os.environ on every step / call)
         self.side_stream_conditioning = os.environ.get("BYA_INVARIANTS_SIDE_STREAM", "1") != "0"
         self.sp_allgather = os.environ.get("BYA_SP_ALLGATHER", "0") == "1"       # exchange A as a K/V all-gather (A/B)
@@ -180,6 +188,14 @@ class DenoiseEngine:
         self.qkv_b = [cat([b.attn1.to_q.bias, b.attn1.to_k.bias, b.attn1.to_v.bias]).contiguous()
                       for b in m.transformer_blocks]
         self.w8 = None
+        blocks = m.transformer_blocks
+        source = {"qkv": lambda: self.qkv_w,
+                  "out": lambda: [b.attn1.to_out[0].weight for b in blocks],
+                  "ff1": lambda: [b.ff.net[0].proj.weight for b in blocks],
+                  "ff2": lambda: [b.ff.net[2].weight for b in blocks],
+                  # ... and the two 3072-wide query projections that sit directly behind a LayerNorm of the video rows
+                  "pq": lambda: [pc.to_q.weight for pc in m.perceiver_cross_attention] if m.is_train_face else None,
+                  "aq": lambda: [al["attn"].to_q.weight for al in m.audio_model.layers] if m.is_train_audio else None}
         if self.fp8_weights:
             # which Linears run in e4m3 (enable_fp8_weights(linears=...) / BYA_FP8_LINEARS; "all" = every kind): the rest stays bf16
             keep = getattr(m, "_fp8_linears", None) or os.environ.get("BYA_FP8_LINEARS") or FP8_DEFAULT
@@ -187,19 +203,24 @@ class DenoiseEngine:
             unknown = keep - set(FP8_LINEARS)
             if unknown:
                 raise ValueError(f"fp8 linears {sorted(unknown)}: expected a subset of {FP8_LINEARS}")
-            blocks = m.transformer_blocks
-            source = {"qkv": lambda: self.qkv_w,
-                      "out": lambda: [b.attn1.to_out[0].weight for b in blocks],
-                      "ff1": lambda: [b.ff.net[0].proj.weight for b in blocks],
-                      "ff2": lambda: [b.ff.net[2].weight for b in blocks],
-                      # ... and the two 3072-wide query projections that sit directly behind a LayerNorm of the video rows
-                      "pq": lambda: [pc.to_q.weight for pc in m.perceiver_cross_attention] if m.is_train_face else None,
-                      "aq": lambda: [al["attn"].to_q.weight for al in m.audio_model.layers] if m.is_train_audio else None}
             self.w8 = {}
             for k in FP8_LINEARS:
                 ws = source[k]() if k in keep else None
                 if ws is not None:
                     self.w8[k] = [ops.quantize_rows_fp8(w) for w in ws]
+        self.wmx = None
+        if self.mx_fmt is not None:
+            # the same vocabulary and default as the fp8 mode (enable_mx_weights(linears=...); "all" = every kind)
+            keep = getattr(m, "_mx_linears", None) or FP8_DEFAULT
+            keep = set(FP8_LINEARS if keep == "all" else keep.split(",")) if isinstance(keep, str) else set(keep)
+            unknown = keep - set(FP8_LINEARS)
+            if unknown:
+                raise ValueError(f"MX linears {sorted(unknown)}: expected a subset of {FP8_LINEARS}")
+            self.wmx = {}
+            for k in FP8_LINEARS:
+                ws = source[k]() if k in keep else None
+                if ws is not None:
+                    self.wmx[k] = [ops.quantize_mx(w.contiguous(), self.mx_fmt) for w in ws]
         pe = getattr(m.patch_embed, "pos_embedding", None)
         use_pe = (not self.cfg.use_rotary_positional_embeddings) or self.cfg.use_learned_positional_embeddings
         self.pos_embedding = pe[0] if (pe is not None and use_pe) else None
@@ -293,7 +314,7 @@ class DenoiseEngine:
         """Block ``i``'s packed q|k|v projection + q/k LayerNorm + RoPE (models/transformer.py:200-209, 241-245): ONE launch
         with the norm in the GEMM's epilogue where the library takes it (bf16 weights, no statistics wanted), else the
         projection and ``bya_qknorm_rope`` on its output -- the same bits either way."""
-        fused = self.qkn_epilogue and stats is None and (self.w8 is None or "qkv" not in self.w8) and xq is None
+        fused = self.qkn_epilogue and stats is None and not self._quantised("qkv") and xq is None
         if fused and ops.gemm_qkv_norm_rope(xn, self.qkv_w[i], out, self.qkv_b[i], split, at.norm_q.weight, at.norm_q.bias,
                                             at.norm_k.weight, at.norm_k.bias, cos, sin, text_rows, eps=at.norm_q.eps,
                                             k_scale=self.k_scale):
@@ -306,6 +327,12 @@ class DenoiseEngine:
         """One of the four big Linears of DiT block ``i`` (models/transformer.py:241-260): the bf16 GEMM, or -- when the
         engine holds fp8 weights -- row-quantise the activations (unless the producer already did: ``quantised``) and run
         the e4m3 GEMM with the same epilogue."""
+        if self.wmx is not None and which in self.wmx:
+            if quantised is None:
+                quantised = ops.quantize_mx(a, self.mx_fmt, *self._amx(a.shape))
+            codes, sa = quantised
+            wc, sw = self.wmx[which][i]
+            return ops.gemm_mx(codes, sa.view(*a.shape[:-1], -1), wc, sw, out, self.mx_fmt, **kw)
         if self.w8 is None or which not in self.w8:
             return ops.gemm(a, w, out, **kw)
         if quantised is None:
@@ -317,11 +344,31 @@ class DenoiseEngine:
     def _ln_linear(self, which, i, x, xn, norm, w, out, **kw):
         """LayerNorm(x) -> Linear for the perceiver / audio query projections (models/router.py:246-253,
         models/audio_model.py:247-253): two launches in bf16; with fp8 weights the LayerNorm emits e4m3 directly."""
-        if self.w8 is not None and which in self.w8 and self.fuse_ln_quant:
-            xq = ops.layernorm_fp8(x, *self._a8(xn.shape), norm.weight, norm.bias, eps=norm.eps)
+        if self._quantised(which) and self.fuse_ln_quant:
+            xq = self._layernorm_quant(which, x, xn.shape, norm.weight, norm.bias, eps=norm.eps)
             return self._dit_linear(which, i, xn, w, out, quantised=xq, **kw)
         ops.layernorm(x, xn, norm.weight, norm.bias, eps=norm.eps)
         return self._dit_linear(which, i, xn, w, out, **kw)
+
+    def _quantised(self, which):
+        """Whether Linear kind ``which`` runs on quantised operands (fp8 or MX weights)."""
+        return (self.w8 is not None and which in self.w8) or (self.wmx is not None and which in self.wmx)
+
+    def _layernorm_quant(self, which, x, shape, weight, bias, **kw):
+        """LayerNorm whose output feeds the quantised Linear ``which`` alone: emitted in that Linear's operand format."""
+        if self.wmx is not None and which in self.wmx:
+            return ops.layernorm_mx(x, *self._amx(shape), self.mx_fmt, weight, bias, **kw)
+        return ops.layernorm_fp8(x, *self._a8(shape), weight, bias, **kw)
+
+    def _amx(self, shape):
+        """Workspace for the MX codes and block scales of one activation matrix."""
+        key = ("amx", self.mx_fmt, tuple(shape))
+        hold = self._ws.get(key)
+        if hold is None:
+            hold = self._ws[key] = (torch.empty(*shape[:-1], ops.mx_code_bytes(shape[-1], self.mx_fmt), dtype=torch.uint8,
+                                                device=self.dev),
+                                    torch.empty(*shape[:-1], shape[-1] // 32, dtype=torch.uint8, device=self.dev))
+        return hold
 
     def _a8(self, shape):
         """Workspace for the e4m3 copy of one activation matrix and its row scales."""
@@ -671,9 +718,9 @@ class DenoiseEngine:
                 ln_kw = dict(eps=nz.norm.eps, shift0=mo[:, 3 * D:], scale0=mo[:, 4 * D:], shift1=mo, scale1=mo[:, D:],
                              split=Tt_loc, mod_batch_stride=mbs)
                 xq = None
-                if self.w8 is not None and ("qkv", "ff1")[half] in self.w8 and self.fuse_ln_quant:
-                    # the AdaLN output feeds exactly one Linear (q|k|v, or the MLP's first): emit it in e4m3 directly
-                    xq = ops.layernorm_fp8(x, *self._a8(xn.shape), nz.norm.weight, nz.norm.bias, **ln_kw)
+                if self._quantised(("qkv", "ff1")[half]) and self.fuse_ln_quant:
+                    # the AdaLN output feeds exactly one Linear (q|k|v, or the MLP's first): emit it in e4m3 / MX directly
+                    xq = self._layernorm_quant(("qkv", "ff1")[half], x, xn.shape, nz.norm.weight, nz.norm.bias, **ln_kw)
                 else:
                     ops.layernorm(x, xn, nz.norm.weight, nz.norm.bias, **ln_kw)
                 if half == 0:
@@ -695,7 +742,7 @@ class DenoiseEngine:
                             # (device bound: this rank's rows give its partial maxima for ALL heads; the tables travel with
                             # the q|k|v exchange and the attention takes the maximum over the ranks' tables for its heads)
                             sb, st = self._attn_bound(i, H, slots=max(1, 64 // W))
-                            if (self.sp_overlap_v and st is None and xq is None and (self.w8 is None or "qkv" not in self.w8)
+                            if (self.sp_overlap_v and st is None and xq is None and not self._quantised("qkv")
                                     and S_loc >= self.SP_OVERLAP_V_MIN_ROWS):
                                 # (r6) v FIRST: v needs no norm -- its projection is a launch of its own, its column blocks travel
                                 # on the side stream while the q | k projection (with the norm in its epilogue) runs; only the

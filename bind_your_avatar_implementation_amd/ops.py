@@ -494,6 +494,84 @@ def gemm_fp8(a8, a_scale, w8, w_scale, out, bias=None, res=None, gate0=None, gat
     return out
 
 
+
+# OCP MX element formats (include/bya.h, "MX weights"): name -> the matrix instruction's format code, element bits
+MX_FORMATS = {"mxfp8": 0, "mxfp6": 2}
+MX_BITS = {"mxfp8": 8, "mxfp6": 6}
+
+
+def mx_fmt_code(fmt):
+    if fmt not in MX_FORMATS:
+        raise ValueError(f"MX format {fmt!r}: expected one of {sorted(MX_FORMATS)}")
+    return MX_FORMATS[fmt]
+
+
+def mx_code_bytes(K, fmt):
+    """Bytes of one row of K MX codes (no padding)."""
+    return K * MX_BITS[fmt] // 8
+
+
+def quantize_mx(x, fmt="mxfp6", codes=None, scales=None):
+    """OCP MX block quantisation of a bf16 matrix [(B,) M, K] -> (uint8 codes [.., M, K * bits / 8], uint8 e8m0 scales
+    [.., M, K / 32])."""
+    lib = _hip.load()
+    code = mx_fmt_code(fmt)
+    b, M, K, bs, ldx = _mat(x, "x")
+    if b > 1 and bs != M * ldx:
+        raise ValueError("quantize_mx: batch entries must be evenly stacked rows")
+    lead = tuple(x.shape[:-1])
+    if codes is None:
+        codes = torch.empty(*lead, mx_code_bytes(K, fmt), dtype=torch.uint8, device=x.device)
+    if scales is None:
+        scales = torch.empty(*lead, K // 32, dtype=torch.uint8, device=x.device)
+    assert codes.dtype == torch.uint8 and codes.is_contiguous() and codes.numel() == b * M * mx_code_bytes(K, fmt)
+    assert scales.dtype == torch.uint8 and scales.is_contiguous() and scales.numel() == b * M * (K // 32)
+    tok = _begin("bya_quantize_mx")
+    check(lib.bya_quantize_mx(_p(x), _p(codes), _p(scales), b * M, K, ldx, code, _stream()), "bya_quantize_mx")
+    _end(tok)
+    return codes, scales
+
+
+def gemm_mx(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, res=None, gate0=None, gate1=None,
+            gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0):
+    """out = res + gate * act(A @ W.T + bias) with both operands in MX form (``quantize_mx``); K is read off the scales."""
+    lib = _hip.load()
+    code = mx_fmt_code(fmt)
+    if a_scales.dim() == 2:
+        ab, (M, KS) = 1, a_scales.shape
+    else:
+        ab, M, KS = a_scales.shape
+    K = KS * 32
+    ob, Mo, N, c_bs, ldc = _mat(out, "out")
+    if split is not None:
+        N = w_codes.shape[0]
+    rb_ = mx_code_bytes(K, fmt)
+    assert a_codes.dtype == w_codes.dtype == a_scales.dtype == w_scales.dtype == torch.uint8
+    assert a_codes.is_contiguous() and w_codes.is_contiguous() and a_scales.is_contiguous() and w_scales.is_contiguous()
+    assert a_codes.numel() == ab * M * rb_ and w_codes.shape == (N, rb_) and w_scales.shape == (N, KS)
+    assert (ab, M) == (ob, Mo)
+    d = GemmDesc()
+    d.M, d.N, d.K, d.batch = M, N, K, ab
+    d.lda, d.ldw, d.ldc = rb_, rb_, ldc
+    d.a_batch_stride, d.c_batch_stride = M * rb_, c_bs
+    d.ldres, d.res_batch_stride = 0, 0
+    if res is not None:
+        rb, Mr, Nr, r_bs, ldres = _mat(res, "res")
+        if (Mr, Nr) != (M, N) or rb not in (1, ab):
+            raise ValueError("res shape mismatch")
+        d.ldres, d.res_batch_stride = ldres, (r_bs if rb == ab else 0)
+    d.gate_batch_stride, d.gate_split, d.act = gate_batch_stride, gate_split, ACT[act]
+    d.n_split, d.c_split_stride = (0, 0) if split is None else split
+    d.bias_rowscale, d.alpha = None, float(alpha)
+    name = "bya_gemm_mx"
+    if _SHAPE_LABELS:
+        name += f":{fmt}:{ab}x{M}x{N}x{K}:{act or 'none'}{'+gate' if gate0 is not None else ''}{'+res' if res is not None else ''}"
+    tok = _begin(name, 2.0 * ab * M * N * K)
+    check(lib.bya_gemm_mx(_p(a_codes), _p(a_scales), _p(w_codes), _p(w_scales), _p(bias), _p(out), _p(res), _p(gate0),
+                          _p(gate1), ctypes.byref(d), code, _stream()), "bya_gemm_mx")
+    _end(tok)
+    return out
+
 def linear_small_m(x, w, bias, out, silu_in=False, act_out=None):
     """out[M<=8, N] = f(x) @ w.T + bias (weight-streaming kernel)."""
     lib = _hip.load()
@@ -548,6 +626,23 @@ def layernorm_fp8(x, q, q_scale, weight=None, bias=None, eps=1e-5, shift0=None, 
     _end(tok)
     return q, q_scale
 
+
+
+def layernorm_mx(x, codes, scales, fmt="mxfp6", weight=None, bias=None, eps=1e-5, shift0=None, scale0=None, shift1=None,
+                 scale1=None, split=0, mod_batch_stride=0):
+    """``layernorm`` + ``quantize_mx`` of its bf16-rounded output in one pass (same bytes, no bf16 round trip)."""
+    lib = _hip.load()
+    code = mx_fmt_code(fmt)
+    xb, rows, D, x_bs, ldx = _mat(x, "x")
+    rb_ = mx_code_bytes(D, fmt)
+    assert codes.dtype == torch.uint8 and codes.is_contiguous() and codes.numel() == xb * rows * rb_
+    assert scales.dtype == torch.uint8 and scales.is_contiguous() and scales.numel() == xb * rows * (D // 32)
+    tok = _begin("bya_layernorm_mx")
+    check(lib.bya_layernorm_mx(_p(x), _p(codes), _p(scales), _p(weight), _p(bias), _p(shift0), _p(scale0), _p(shift1),
+                               _p(scale1), rows, xb, D, ldx, rb_, x_bs, rows * rb_, mod_batch_stride, split, float(eps),
+                               code, _stream()), "bya_layernorm_mx")
+    _end(tok)
+    return codes, scales
 
 def qknorm_rope(q, k, qw, qb, kw, kb, cos, sin, heads, text_rows, eps=1e-6, k_scale=1.0, stats=None):
     """In place on q, k [B, S, heads*64]; q or k may be None (only the other one is processed).  ``stats``: fp32

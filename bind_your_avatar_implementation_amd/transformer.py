@@ -380,6 +380,22 @@ class BindyouravatarTransformer3DModel(nn.Module):
         self.invalidate_engine()
         return self
 
+    def enable_mx_weights(self, fmt: str = "mxfp6", enabled: bool = True, linears=None):
+        """Run the selected Linears on OCP MX operands: 32-element blocks along K with one e8m0 scale each, applied by
+        gfx950's block-scaled matrix instruction (include/bya.h, "MX weights").  ``fmt``: "mxfp6" (e2m3 elements, the
+        instruction's fastest dense rate) or "mxfp8" (e4m3 elements, the more accurate).  Weights are quantised when the
+        engine packs them, activations per block on the fly (by the AdaLN LayerNorm itself where it feeds the Linear).
+        ``linears``: as for enable_fp8_weights (a subset of engine.FP8_LINEARS or "all"; default engine.FP8_DEFAULT).
+        Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference counterpart (the
+        reference is bf16/fp16 only); returns self."""
+        from .ops import MX_FORMATS
+        if fmt not in MX_FORMATS:
+            raise ValueError(f"MX format {fmt!r}: expected one of {sorted(MX_FORMATS)}")
+        self._mx_weights = fmt if enabled else None
+        self._mx_linears = (linears if isinstance(linears, str) else tuple(linears)) if linears else None
+        self.invalidate_engine()
+        return self
+
     def invalidate_engine(self):
         """Drop packed weights / workspaces / captured graphs (call after changing parameters in place)."""
         self._engine = None

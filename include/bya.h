@@ -184,6 +184,48 @@ int bya_layernorm_fp8(const void* x, void* q, float* q_scale, const void* w, con
                       int64_t mod_batch_stride, int64_t split, float eps, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * MX weights (OCP Microscaling; no reference counterpart: the reference runs bf16/fp16 only).  Elements in blocks of 32
+ * consecutive values along K, each block with one e8m0 scale byte:  x[m, 32 b + i] ~= 2^(scale[m,b] - 127) * elem(code).
+ * Element formats, numbered as the matrix instruction's cbsz / blgp fields:
+ *   BYA_MX_E4M3 = 0: OCP e4m3fn, emax_elem = 8, largest finite 448, 32 bytes per block (element i = byte i);
+ *   BYA_MX_E2M3 = 2: OCP e2m3 (1 sign, 2 exponent bits of bias 1, 3 mantissa bits, no inf / NaN), emax_elem = 2,
+ *                    largest finite 7.5, 24 bytes per block: element i at bits 6i .. 6i+5 of the block's 192-bit
+ *                    little-endian string (least significant bit first: the order v_mfma_scale_f32_16x16x128_f8f6f4
+ *                    reads from its six operand VGPRs, checked on exact data).
+ *   Storage is the plain row-major order in both formats; the GEMM kernel arranges the operand VGPRs per format
+ *   (csrc/gemm_mx.hip: for e4m3 the instruction's 32-k block spans two 16-byte pieces of different lanes).
+ *
+ * Scale of block b of row m (amax = max |x| over the block, taken on the bf16 values):
+ *   E = floor(log2 amax) - emax_elem, clamped to [-127, 127]; stored byte E + 127.
+ *   An all-zero block (+0 or -0 values only) stores the byte 127 and all-zero codes.
+ * Element code:  q = RNE(x * 2^-E) (one round-to-nearest-even from the exact product), saturated to +-largest finite;
+ *   the sign of x is kept (a negative value that rounds to zero gives -0).
+ * Storage: codes uint8 [rows, K * bits / 8] row-major (row stride K * bits / 8, no padding), scales uint8 [rows, K / 32].
+ *   Weights use the same layout with rows = output channels.  K % 128 == 0.
+ *
+ * bya_quantize_mx:  bf16 x [M, K] (row stride ldx, elements) -> codes, scales.  ldx % 8 == 0, x 16-byte aligned.
+ * bya_layernorm_mx: bya_layernorm (same arguments, same arithmetic as bya_layernorm_fp8) followed by bya_quantize_mx of each
+ *   bf16-rounded output row, in one pass -- byte for byte the two launches.  codes [batch][rows][D * bits / 8] (row stride
+ *   ldq, batch stride q_batch_stride, bytes; both % 8 == 0), scales [batch * rows_per_batch, D / 32].  D = 3072 only.
+ * bya_gemm_mx:  C[z][m,n] = res + gate * alpha * act( sum_k A[z][m,k] * W[n,k] + rowscale*bias[n] ) with A and W in MX form
+ *   on v_mfma_scale_f32_16x16x128_f8f6f4, the block scales applied by the instruction (fp32 accumulation).  Same
+ *   descriptor and epilogue as bya_gemm_bf16; lda / ldw / a_batch_stride count BYTES of codes; a_scales is
+ *   [batch * M, K / 32], w_scales [N, K / 32] (dense).  Both operands use the same element format.
+ *   Requirements: K % 128 == 0, N % 4 == 0, lda / ldw % 16 == 0, A / W 16-byte aligned, a_scales / w_scales 4-byte aligned,
+ *   batch * M * K / 32 < 2^31; act in {NONE, GELU_TANH(_IEEE)}.
+ * --------------------------------------------------------------------------------------------- */
+enum { BYA_MX_E4M3 = 0, BYA_MX_E2M3 = 2 };
+int bya_quantize_mx(const void* x, void* codes, void* scales, int32_t M, int32_t K, int64_t ldx, int32_t fmt,
+                    hipStream_t stream);
+int bya_layernorm_mx(const void* x, void* q, void* q_scales, const void* w, const void* b, const void* shift0,
+                     const void* scale0, const void* shift1, const void* scale1, int64_t rows_per_batch, int32_t batch,
+                     int32_t D, int64_t ldx, int64_t ldq, int64_t x_batch_stride, int64_t q_batch_stride,
+                     int64_t mod_batch_stride, int64_t split, float eps, int32_t fmt, hipStream_t stream);
+int bya_gemm_mx(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, void* C,
+                const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* desc, int32_t fmt,
+                hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Small-M linear (M <= 8 rows):  out[m,n] = sum_k f(x[m,k]) * W[n,k] + bias[n],  f = identity or SiLU.
  * HBM-bound weight stream.  Replaces TimestepEmbedding.linear_1/2, CogVideoXLayerNormZero.linear
  * (models/transformer.py:198,212 -- all 2*num_layers of them in ONE launch over packed weights) and
