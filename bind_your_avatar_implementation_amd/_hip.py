@@ -22,6 +22,10 @@ class GemmDesc(_c.Structure):
                 ("n_split", _i32), ("c_split_stride", _i64), ("bias_rowscale", _vp), ("alpha", _f32)]
 
 
+class GemmPlan(_c.Structure):
+    _fields_ = [("path", _i32), ("m0", _i32), ("tail", _i32), ("split_k", _i32), ("row_chunks", _i32)]
+
+
 class QkNormDesc(_c.Structure):
     _fields_ = [("qw", _vp), ("qb", _vp), ("kw", _vp), ("kb", _vp), ("cos", _vp), ("sin", _vp),
                 ("text_rows", _i32), ("width", _i32), ("eps", _f32), ("k_scale", _f32)]
@@ -57,17 +61,21 @@ SIGNATURES = {
     "bya_gemm_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _vp],
     "bya_gemm_skinny_bf16": [_vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _vp],
     "bya_gemm_qkv_norm_rope": [_vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _vp],
+    "bya_gemm_bf16_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(GemmPlan)],
+    "bya_gemm_qkv_norm_rope_plan": [_vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _c.POINTER(GemmPlan)],
     "bya_set_gemm_workspace": [_vp, _i64],
     "bya_gemm_workspace_bytes": [_c.POINTER(_i64)],
     "bya_gemm_workspace_status": [_c.POINTER(_i32), _vp],
     "bya_quantize_rows_fp8": [_vp, _vp, _vp, _i32, _i32, _i64, _i64, _vp],
     "bya_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _vp],
+    "bya_gemm_fp8_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(GemmPlan)],
     "bya_layernorm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
                           _f32, _vp],
     "bya_quantize_mx": [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp],
     "bya_layernorm_mx": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
                          _f32, _i32, _vp],
     "bya_gemm_mx": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _i32, _vp],
+    "bya_gemm_mx_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _i32, _c.POINTER(GemmPlan)],
     "bya_linear_small_m": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "bya_timestep_features": [_vp, _vp, _i32, _i32, _i32, _f32, _vp],
     "bya_layernorm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -128,6 +136,9 @@ ENV_OPTIONS = {
     "BYA_FP8_KERNEL": ("fp8_kernel", lambda v: 1 if v.startswith("1") else 0),
     "BYA_P2P_GROUPS": ("p2p_groups", int),
 }
+
+# BYA_GEMM_PATH_* of include/bya.h: the kernels of a GEMM launch (bya_gemm_plan.path / .tail)
+GEMM_PATHS = {0: "t128x64", 1: "t128x128", 2: "t256x128", 3: "t256x256", 4: "p256", 5: "p128", 6: "p128s", 7: "w8_256"}
 
 ERRORS = {-1: "BYA_ERR_SHAPE", -2: "BYA_ERR_ALIGN", -3: "BYA_ERR_LAUNCH", -4: "BYA_ERR_UNSUPPORTED"}
 

@@ -311,18 +311,20 @@ inline bool v4_eligible(const GemmArgs& a) {
 // ... and the 128 x 256 persistent kernel (gemm_v5.hip) needs four K-tiles for its three-stage ring to run across tiles
 inline bool p128_eligible(const GemmArgs& a) { return v4_eligible(a) && a.K >= 4 * BK && a.conv_cpg_log2 < 0 && bya_opt(BYA_OPT_GEMM_VARIANT) == 0; }
 
-int launch256(const GemmArgs& a, int batch, hipStream_t s) {
+// Kernel choice for the 256x256 tile shapes.  Default: the persistent one-wave-per-SIMD kernel (gemm_v4.hip) whenever
+// its 16-byte epilogue accesses are aligned and K has at least three K-tiles, else the 8-wave kernel below.
+// BYA_GEMM_VARIANT (read per call so one process can A/B them, tools/gemm_probe.py): "w8" = this file's 8-wave
+// kernel (the fallback), anything else = gemm_v4.hip.
+inline int path256(const GemmArgs& a) {
+    return v4_eligible(a) && bya_opt(BYA_OPT_GEMM_VARIANT) != 1 ? BYA_GEMM_PATH_P256 : BYA_GEMM_PATH_W8_256;
+}
+
+int launch_w8_256(const GemmArgs& a, int batch, hipStream_t s) {
     const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
     dim3 grid(tiles_m * tiles_n, 1, batch);
     const size_t lds = 2 * 512 * BK * 2;
     static std::atomic<unsigned long long> attr_done{0};
     if (bya_allow_big_lds(reinterpret_cast<const void*>(gemm256_kernel), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-    // Kernel choice for the 256x256 tile shapes.  Default: the persistent one-wave-per-SIMD kernel (gemm_v4.hip) whenever
-    // its 16-byte epilogue accesses are aligned and K has at least three K-tiles, else the 8-wave kernel below.
-    // BYA_GEMM_VARIANT (read per call so one process can A/B them, tools/gemm_probe.py): "w8" = this file's 8-wave
-    // kernel (the fallback), anything else = gemm_v4.hip.
-    const bool v4_ok = v4_eligible(a);
-    if (v4_ok && bya_opt(BYA_OPT_GEMM_VARIANT) != 1) return bya_launch_gemm256p(&a, batch, s);
     BYA_LAUNCH(gemm256_kernel, grid, dim3(512), lds, s, a);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
@@ -465,10 +467,11 @@ extern "C" int bya_gemm_workspace_bytes(int64_t* bytes) {
 
 namespace {
 int dispatch_gemm(const GemmArgs& a, int nbatch, hipStream_t stream);
-}  // namespace
+void plan_gemm(const GemmArgs& a, int nbatch, bya_gemm_plan* p);
 
-extern "C" int bya_gemm_bf16(const void* A, const void* W, const void* bias, void* C, const void* res,
-                             const void* gate0, const void* gate1, const bya_gemm_desc* d, hipStream_t stream) {
+// bya_gemm_bf16's arguments -> GemmArgs (with the current device's split-K workspace); BYA_OK or the error that rejects them
+int bf16_args(const void* A, const void* W, const void* bias, const void* C, const void* res, const void* gate0,
+              const void* gate1, const bya_gemm_desc* d, GemmArgs* out) {
     if (!A || !W || !C || !d) return BYA_ERR_SHAPE;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return BYA_ERR_SHAPE;
     if (d->K % BK != 0 || d->N % 4 != 0) return BYA_ERR_SHAPE;
@@ -476,7 +479,7 @@ extern "C" int bya_gemm_bf16(const void* A, const void* W, const void* bias, voi
     if (((uintptr_t)A | (uintptr_t)W) & 15) return BYA_ERR_ALIGN;
     if (((uintptr_t)C | (uintptr_t)res | (uintptr_t)bias | (uintptr_t)gate0 | (uintptr_t)gate1) & 7) return BYA_ERR_ALIGN;
     if (d->act < 0 || d->act > 6) return BYA_ERR_UNSUPPORTED;
-    GemmArgs a;
+    GemmArgs& a = *out;
     a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C;
     a.res = (const bf16_t*)res; a.gate0 = (const bf16_t*)gate0; a.gate1 = (const bf16_t*)(gate1 ? gate1 : gate0);
     a.M = d->M; a.N = d->N; a.K = d->K;
@@ -490,16 +493,12 @@ extern "C" int bya_gemm_bf16(const void* A, const void* W, const void* bias, voi
     a.ws_counters = reinterpret_cast<unsigned*>(ws);
     a.ws_slabs = ws ? reinterpret_cast<float*>(ws + GEMM_WS_COUNTER_BYTES) : nullptr;
     if (d->n_split < 0 || (d->n_split > 0 && (d->n_split % 4 || d->c_split_stride % 4 || res))) return BYA_ERR_SHAPE;
-    return gemm_row_chunks(a, d->batch, 2, [&](const GemmArgs& piece, int batch, long long) {
-        return dispatch_gemm(piece, batch, stream);
-    });
+    return BYA_OK;
 }
 
-// The packed q|k|v projection with the q/k LayerNorm(64) + RoPE (+ the k pre-scale) in its epilogue: one launch, q and k
-// written once (include/bya.h).  Only the persistent one-wave-per-SIMD kernel has that epilogue: anything it does not take
-// is BYA_ERR_UNSUPPORTED and the caller keeps bya_gemm_bf16 + bya_qknorm_rope.
-extern "C" int bya_gemm_qkv_norm_rope(const void* A, const void* W, const void* bias, void* C, const bya_gemm_desc* d,
-                                      const bya_qknorm_desc* n, hipStream_t stream) {
+// bya_gemm_qkv_norm_rope's arguments -> GemmArgs; BYA_ERR_UNSUPPORTED: not this kernel's shape (the caller keeps two launches)
+int qkn_args(const void* A, const void* W, const void* bias, const void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n,
+             GemmArgs* out) {
     if (!A || !W || !C || !d || !n) return BYA_ERR_SHAPE;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0 || d->K % BK != 0) return BYA_ERR_SHAPE;
     if (!n->qw || !n->qb || !n->kw || !n->kb || n->width <= 0 || n->text_rows < 0) return BYA_ERR_SHAPE;
@@ -511,7 +510,7 @@ extern "C" int bya_gemm_qkv_norm_rope(const void* A, const void* W, const void* 
     if (d->lda % 8 || d->ldw % 8) return BYA_ERR_ALIGN;
     if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)bias | (uintptr_t)n->qw | (uintptr_t)n->qb | (uintptr_t)n->kw |
          (uintptr_t)n->kb | (uintptr_t)n->cos | (uintptr_t)n->sin) & 15) return BYA_ERR_ALIGN;
-    GemmArgs a;
+    GemmArgs& a = *out;
     a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C;
     a.res = nullptr; a.gate0 = nullptr; a.gate1 = nullptr;
     a.M = d->M; a.N = d->N; a.K = d->K;
@@ -524,8 +523,49 @@ extern "C" int bya_gemm_qkv_norm_rope(const void* A, const void* W, const void* 
     a.qkn_cos = n->cos; a.qkn_sin = n->sin; a.qkn_text_rows = n->text_rows; a.qkn_width = n->width;
     a.qkn_eps = n->eps; a.qkn_kscale = n->k_scale == 0.0f ? 1.0f : n->k_scale;
     if (!v4_eligible(a) || !gemm_rows_reachable(a, a.M)) return BYA_ERR_UNSUPPORTED;
+    return BYA_OK;
+}
+
+// the q|k|v launch's row plan (0: 256-row tiles, 1: 128-row tiles, 2: both, rows split at *m0)
+inline int qkn_plan(const GemmArgs& a, int batch, int* m0) {
+    *m0 = 0;
+    return p128_eligible(a) ? plan_rows_qkn(a.M, a.N, batch, m0) : 0;
+}
+}  // namespace
+
+extern "C" int bya_gemm_bf16(const void* A, const void* W, const void* bias, void* C, const void* res,
+                             const void* gate0, const void* gate1, const bya_gemm_desc* d, hipStream_t stream) {
+    GemmArgs a;
+    const int rc = bf16_args(A, W, bias, C, res, gate0, gate1, d, &a);
+    if (rc != BYA_OK) return rc;
+    return gemm_row_chunks(a, d->batch, 2, [&](const GemmArgs& piece, int batch, long long) {
+        return dispatch_gemm(piece, batch, stream);
+    });
+}
+
+extern "C" int bya_gemm_bf16_plan(const void* A, const void* W, const void* bias, const void* C, const void* res,
+                                  const void* gate0, const void* gate1, const bya_gemm_desc* d, bya_gemm_plan* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    GemmArgs a, piece;
+    int rc = bf16_args(A, W, bias, C, res, gate0, gate1, d, &a), nb = 0;
+    if (rc != BYA_OK) return rc;
+    const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
+    if (!chunks) return BYA_ERR_UNSUPPORTED;
+    plan_gemm(piece, nb, plan);
+    plan->row_chunks = chunks;
+    return BYA_OK;
+}
+
+// The packed q|k|v projection with the q/k LayerNorm(64) + RoPE (+ the k pre-scale) in its epilogue: one launch, q and k
+// written once (include/bya.h).  Only the persistent one-wave-per-SIMD kernel has that epilogue: anything it does not take
+// is BYA_ERR_UNSUPPORTED and the caller keeps bya_gemm_bf16 + bya_qknorm_rope.
+extern "C" int bya_gemm_qkv_norm_rope(const void* A, const void* W, const void* bias, void* C, const bya_gemm_desc* d,
+                                      const bya_qknorm_desc* n, hipStream_t stream) {
+    GemmArgs a;
+    const int rc0 = qkn_args(A, W, bias, C, d, n, &a);
+    if (rc0 != BYA_OK) return rc0;
     int m0 = 0;
-    const int plan = p128_eligible(a) ? plan_rows_qkn(a.M, a.N, d->batch, &m0) : 0;
+    const int plan = qkn_plan(a, d->batch, &m0);
     if (plan == 1) return bya_launch_gemm128p_qkn(&a, d->batch, stream);
     if (plan == 2) {                                             // rows [0, m0): 256-row tiles; the rest: 128-row tiles
         GemmArgs lo = a, hi = a;
@@ -543,6 +583,22 @@ extern "C" int bya_gemm_qkv_norm_rope(const void* A, const void* W, const void* 
         return rc != BYA_OK ? rc : bya_launch_gemm128p_qkn(&hi, 1, stream);
     }
     return bya_launch_gemm256p_qkn(&a, d->batch, stream);
+}
+
+extern "C" int bya_gemm_qkv_norm_rope_plan(const void* A, const void* W, const void* bias, const void* C, const bya_gemm_desc* d,
+                                           const bya_qknorm_desc* n, bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    GemmArgs a;
+    const int rc = qkn_args(A, W, bias, C, d, n, &a);
+    if (rc != BYA_OK) return rc;
+    int m0 = 0;
+    const int plan = qkn_plan(a, d->batch, &m0);
+    p->path = plan == 1 ? BYA_GEMM_PATH_P128 : BYA_GEMM_PATH_P256;
+    p->m0 = plan == 2 ? m0 : 0;
+    p->tail = plan == 2 ? BYA_GEMM_PATH_P128 : -1;
+    p->split_k = 0;
+    p->row_chunks = 1;
+    return BYA_OK;
 }
 
 namespace {
@@ -665,30 +721,25 @@ int launch_skinny(const GemmArgs& a0, int nbatch, hipStream_t stream) {
     }
 }
 
-int dispatch_gemm(const GemmArgs& a, int nbatch, hipStream_t stream) {
-    char* const ws = reinterpret_cast<char*>(a.ws_counters);
-    struct { int M, N, K, batch, act; } dd{a.M, a.N, a.K, nbatch, a.act};
-    const auto* d = &dd;
+// Which kernels a launch runs (bya_gemm_bf16 and its query bya_gemm_bf16_plan).
+void plan_gemm(const GemmArgs& a, int nbatch, bya_gemm_plan* p) {
+    p->path = -1; p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = 1;
+    const bool ws = a.ws_counters != nullptr;
     const int forced = bya_opt(BYA_OPT_GEMM_TILE);              // tuning / test option
     const bool splitk = ws && bya_opt(BYA_OPT_GEMM_SPLITK) != 0 && a.K / BK >= 2 * bya_gemm_split_min_ktiles() && v4_eligible(a) &&
         bya_opt(BYA_OPT_GEMM_VARIANT) != 1;
-    switch (pick_tile(d->M, d->N, d->K, d->batch, forced, d->act, splitk, p128_eligible(a))) {
-        case 0: return launch<128, 64, 2, 2>(a, d->batch, stream);
-        case 1: return launch<128, 128, 2, 2>(a, d->batch, stream);
-        case 2: return launch<256, 128, 4, 2>(a, d->batch, stream);
-        case 3: return launch<256, 256, 2, 4>(a, d->batch, stream);
-        case 5: if (p128_eligible(a)) return bya_launch_gemm128p(&a, d->batch, stream); break;     // (forced only; else: the 256 x 256 path below)
-        case 6: if (p128_eligible(a)) return bya_launch_gemm128s(&a, d->batch, stream); break;
-        default: break;
-    }
+    const int tile = pick_tile(a.M, a.N, a.K, nbatch, forced, a.act, splitk, p128_eligible(a));
+    if (tile >= 0 && tile <= 3) { p->path = tile; return; }
+    if ((tile == 5 || tile == 6) && p128_eligible(a)) { p->path = tile; return; }     // (5: forced only; else: the 256 x 256 path below)
     // Pipelined 256x256 tiles, one workgroup per CU.  When the last round of tiles would leave most CUs idle
     // (N = 3072 at 17776 rows: 840 tiles = 3.28 rounds), the rows of the complete rounds go to the pipelined kernel
     // and the remaining rows to the 128x128 kernel, whose many small tiles fill all CUs at once.
+    p->path = path256(a);
     const int tn = (a.N + 255) / 256, tm = (a.M + 255) / 256;
     const long long tiles = (long long)tm * tn;
     const long long full = tiles / 256;
     // (with a split-K workspace the persistent kernel cuts that last round along K itself: no row split)
-    if (!splitk && d->batch == 1 && full >= 1 && tiles % 256 != 0) {
+    if (!splitk && nbatch == 1 && full >= 1 && tiles % 256 != 0) {
         const int main_tm = (int)(full * 256 / tn);
         const int m0 = main_tm * 256;
         if (m0 > 0 && m0 < a.M) {
@@ -707,21 +758,45 @@ int dispatch_gemm(const GemmArgs& a, int nbatch, hipStream_t stream) {
             if (tail_128p) tail_cost = rounds_128(a.M - m0, a.N, 1, REL_128S) + 0.05;
             const double main_cost = (double)(((long long)main_tm * tn + 255) / 256);
             if (main_cost + tail_cost < (double)((tiles + 255) / 256) - 0.15) {
-                GemmArgs lo = a, hi = a;
-                lo.M = m0;
-                hi.M = a.M - m0;
-                hi.A += (long long)m0 * a.lda;
-                hi.C += (long long)m0 * a.ldc;
-                if (hi.res) hi.res += (long long)m0 * a.ldres;
-                if (hi.bias_rowscale) hi.bias_rowscale += m0;
-                hi.gate_split = a.gate_split > m0 ? a.gate_split - m0 : 0;
-                const int rc = launch256(lo, 1, stream);
-                if (rc != BYA_OK) return rc;
-                return tail_128p ? bya_launch_gemm128s(&hi, 1, stream) : launch<128, 128, 2, 2>(hi, 1, stream);
+                p->m0 = m0;
+                p->tail = tail_128p ? BYA_GEMM_PATH_P128S : BYA_GEMM_PATH_T128X128;
+                return;
             }
         }
     }
-    return launch256(a, d->batch, stream);
+    if (p->path == BYA_GEMM_PATH_P256) p->split_k = bya_gemm256p_split(&a, nbatch);
+}
+
+int launch_path(int path, const GemmArgs& a, int batch, hipStream_t stream) {
+    switch (path) {
+        case BYA_GEMM_PATH_T128X64: return launch<128, 64, 2, 2>(a, batch, stream);
+        case BYA_GEMM_PATH_T128X128: return launch<128, 128, 2, 2>(a, batch, stream);
+        case BYA_GEMM_PATH_T256X128: return launch<256, 128, 4, 2>(a, batch, stream);
+        case BYA_GEMM_PATH_T256X256: return launch<256, 256, 2, 4>(a, batch, stream);
+        case BYA_GEMM_PATH_P256: return bya_launch_gemm256p(&a, batch, stream);
+        case BYA_GEMM_PATH_P128: return bya_launch_gemm128p(&a, batch, stream);
+        case BYA_GEMM_PATH_P128S: return bya_launch_gemm128s(&a, batch, stream);
+        case BYA_GEMM_PATH_W8_256: return launch_w8_256(a, batch, stream);
+        default: return BYA_ERR_UNSUPPORTED;
+    }
+}
+
+int dispatch_gemm(const GemmArgs& a, int nbatch, hipStream_t stream) {
+    bya_gemm_plan p;
+    plan_gemm(a, nbatch, &p);
+    if (p.m0 > 0) {                                              // rows [0, m0) on 256 x 256 tiles, the rest on `tail`
+        GemmArgs lo = a, hi = a;
+        lo.M = p.m0;
+        hi.M = a.M - p.m0;
+        hi.A += (long long)p.m0 * a.lda;
+        hi.C += (long long)p.m0 * a.ldc;
+        if (hi.res) hi.res += (long long)p.m0 * a.ldres;
+        if (hi.bias_rowscale) hi.bias_rowscale += p.m0;
+        hi.gate_split = a.gate_split > p.m0 ? a.gate_split - p.m0 : 0;
+        const int rc = launch_path(p.path, lo, 1, stream);
+        return rc != BYA_OK ? rc : launch_path(p.tail, hi, 1, stream);
+    }
+    return launch_path(p.path, a, nbatch, stream);
 }
 }  // namespace
 

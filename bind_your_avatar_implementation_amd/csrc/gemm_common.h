@@ -200,12 +200,31 @@ inline bool gemm_rows_reachable(const GemmArgs& a, int M) {
     return gemm_span_bytes(a, M, false) < REACH && (!a.res || gemm_span_bytes(a, M, true) < REACH);
 }
 
-template <typename F>
-int gemm_row_chunks(const GemmArgs& a, int batch, int a_elem_bytes, F&& run) {
-    if (gemm_rows_reachable(a, a.M)) return run(a, batch, 0LL);
+// rows per chunk: a.M when the whole launch is in reach, 0 when not even one 256-row block is (strides too large)
+inline int gemm_chunk_rows(const GemmArgs& a) {
+    if (gemm_rows_reachable(a, a.M)) return a.M;
     int chunk = a.M;
     while (chunk > 256 && !gemm_rows_reachable(a, chunk)) chunk = ((chunk / 2 + 255) / 256) * 256;
-    if (!gemm_rows_reachable(a, chunk)) return BYA_ERR_UNSUPPORTED;        // a single 256-row block out of reach: strides too large
+    return gemm_rows_reachable(a, chunk) ? chunk : 0;
+}
+
+// the plan queries (include/bya.h bya_gemm_plan): the first piece gemm_row_chunks runs, its batch, and the number of pieces
+// (0: BYA_ERR_UNSUPPORTED)
+inline int gemm_first_chunk(const GemmArgs& a, int batch, GemmArgs* piece, int* piece_batch) {
+    const int chunk = gemm_chunk_rows(a);
+    *piece = a;
+    *piece_batch = batch;
+    if (chunk == a.M || chunk == 0) return chunk == 0 ? 0 : 1;
+    piece->M = chunk;                                   // (row 0 of batch entry 0: the pointers stay)
+    *piece_batch = 1;
+    return batch * ((a.M + chunk - 1) / chunk);
+}
+
+template <typename F>
+int gemm_row_chunks(const GemmArgs& a, int batch, int a_elem_bytes, F&& run) {
+    const int chunk = gemm_chunk_rows(a);
+    if (chunk == a.M) return run(a, batch, 0LL);
+    if (chunk == 0) return BYA_ERR_UNSUPPORTED;        // a single 256-row block out of reach: strides too large
     for (int z = 0; z < batch; ++z)
         for (int m0 = 0; m0 < a.M; m0 += chunk) {
             GemmArgs s = a;
@@ -235,6 +254,7 @@ inline int gemm_group_m(const GemmArgs& a) { return a.K >= 8192 ? 2 : (a.N >= 81
 int bya_launch_gemm256p(const void* args, int batch, hipStream_t stream);
 int bya_launch_gemm256p_qkn(const void* args, int batch, hipStream_t stream);    // ... its QKN instance (bya_gemm_qkv_norm_rope)
 int bya_gemm_split_min_ktiles();     // K-tiles per K-range below which the persistent kernel does not split a tile
+int bya_gemm256p_split(const void* args, int batch);   // does bya_launch_gemm256p cut its last round along K?  0, 1 or 2
 // defined in gemm_v5.hip: the persistent kernel with 128 x 256 tiles (three-stage ring) for row counts that leave the 256 x 256
 // grid half empty; callers have checked v4_eligible() and K >= 4 K-tiles
 int bya_launch_gemm128p(const void* args, int batch, hipStream_t stream);

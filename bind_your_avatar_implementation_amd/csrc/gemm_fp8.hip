@@ -77,9 +77,10 @@ extern "C" int bya_quantize_rows_fp8(const void* x, void* q, float* scale, int32
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 
-extern "C" int bya_gemm_fp8(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias,
-                            void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
-                            hipStream_t stream) {
+namespace {
+// bya_gemm_fp8's arguments -> GemmArgs; BYA_OK or the error that rejects them
+int fp8_args(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias, const void* C,
+             const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d, GemmArgs* out) {
     if (!A8 || !W8 || !a_scale || !w_scale || !C || !d) return BYA_ERR_SHAPE;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return BYA_ERR_SHAPE;
     if (d->K % BK8 != 0 || d->N % 4 != 0) return BYA_ERR_SHAPE;
@@ -88,7 +89,7 @@ extern "C" int bya_gemm_fp8(const void* A8, const float* a_scale, const void* W8
     if (((uintptr_t)C | (uintptr_t)res | (uintptr_t)bias | (uintptr_t)gate0 | (uintptr_t)gate1) & 7) return BYA_ERR_ALIGN;
     if (!act_on_big_tiles(d->act)) return BYA_ERR_UNSUPPORTED;            // none / GELU(tanh): the DiT Linears
     if (d->n_split < 0 || (d->n_split > 0 && (d->n_split % 4 || d->c_split_stride % 4 || res))) return BYA_ERR_SHAPE;
-    GemmArgs a;
+    GemmArgs& a = *out;
     a.A = (const bf16_t*)A8; a.W = (const bf16_t*)W8; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C;
     a.res = (const bf16_t*)res; a.gate0 = (const bf16_t*)gate0; a.gate1 = (const bf16_t*)(gate1 ? gate1 : gate0);
     a.M = d->M; a.N = d->N; a.K = d->K;
@@ -98,18 +99,48 @@ extern "C" int bya_gemm_fp8(const void* A8, const float* a_scale, const void* W8
     a.n_split = d->n_split; a.c_split_stride = d->c_split_stride;
     a.bias_rowscale = d->bias_rowscale; a.alpha = d->alpha == 0.0f ? 1.0f : d->alpha;
     a.ws_counters = nullptr; a.ws_slabs = nullptr;
-    // Two 128 x 128 workgroups per CU (4 waves, 64 KiB LDS ring each) cover each other's barrier and LDS-DMA waits; a
-    // 256 x 256 form (8 waves, 128 KiB ring, one workgroup per CU, half the L2 -> LDS bytes per FLOP) measured 4-16 %
-    // slower on the four DiT shapes with this simple two-barrier loop, a one-wave-per-SIMD instantiation 8-20 % slower under
-    // hipcc's schedule (profiles/history/r2_fp8_probe.txt; both removed from the tree in round 3).
-    // ... until the loop was placed by hand: gemm_fp8_v4.hip (one wave per SIMD, persistent) takes every launch that is big
-    // enough to fill its 256 x 256 tiles; BYA_FP8_KERNEL=128 (read per call: A/B runs) keeps everything on the kernel above.
-    const long long tiles256 = (long long)((d->M + 255) / 256) * ((d->N + 255) / 256) * d->batch;
+    return BYA_OK;
+}
+
+// Two 128 x 128 workgroups per CU (4 waves, 64 KiB LDS ring each) cover each other's barrier and LDS-DMA waits; a
+// 256 x 256 form (8 waves, 128 KiB ring, one workgroup per CU, half the L2 -> LDS bytes per FLOP) measured 4-16 %
+// slower on the four DiT shapes with this simple two-barrier loop, a one-wave-per-SIMD instantiation 8-20 % slower under
+// hipcc's schedule (profiles/history/r2_fp8_probe.txt; both removed from the tree in round 3).
+// ... until the loop was placed by hand: gemm_fp8_v4.hip (one wave per SIMD, persistent) takes every launch that is big
+// enough to fill its 256 x 256 tiles; BYA_FP8_KERNEL=128 (read per call: A/B runs) keeps everything on the kernel above.
+// `a`: the whole launch (tile count), `piece`: one row chunk of it (eligibility).
+inline int fp8_path(const GemmArgs& a, int batch, const GemmArgs& piece) {
+    const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
     const bool big = !bya_opt(BYA_OPT_FP8_KERNEL) && tiles256 >= 200;        // (about a round of its 256 workgroups, or more)
+    return big && bya_gemm256p_fp8_eligible(&piece) ? BYA_GEMM_PATH_P256 : BYA_GEMM_PATH_T128X128;
+}
+}  // namespace
+
+extern "C" int bya_gemm_fp8(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias,
+                            void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
+                            hipStream_t stream) {
+    GemmArgs a;
+    const int rc = fp8_args(A8, a_scale, W8, w_scale, bias, C, res, gate0, gate1, d, &a);
+    if (rc != BYA_OK) return rc;
     const int gm = 4;                                                 // row-tiles per group of the persistent kernel's tile order
     return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
-        if (big && bya_gemm256p_fp8_eligible(&piece))
+        if (fp8_path(a, d->batch, piece) == BYA_GEMM_PATH_P256)
             return bya_launch_gemm256p_fp8(&piece, a_scale + row0, w_scale, batch, gm, stream);
         return launch_fp8<128, 128, 2, 2>(piece, a_scale + row0, w_scale, batch, stream);
     });
+}
+
+extern "C" int bya_gemm_fp8_plan(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias,
+                                 const void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
+                                 bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    GemmArgs a, piece;
+    int nb = 0;
+    const int rc = fp8_args(A8, a_scale, W8, w_scale, bias, C, res, gate0, gate1, d, &a);
+    if (rc != BYA_OK) return rc;
+    const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
+    if (!chunks) return BYA_ERR_UNSUPPORTED;
+    p->path = fp8_path(a, d->batch, piece);
+    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = chunks;
+    return BYA_OK;
 }

@@ -257,9 +257,10 @@ extern "C" int bya_quantize_mx(const void* x, void* codes, void* scales, int32_t
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 
-extern "C" int bya_gemm_mx(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
-                           void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
-                           int32_t fmt, hipStream_t stream) {
+namespace {
+// bya_gemm_mx's arguments -> GemmArgs; BYA_OK or the error that rejects them
+int mx_args(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, const void* C,
+            const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d, int32_t fmt, GemmArgs* out) {
     if (!A || !W || !a_scales || !w_scales || !C || !d) return BYA_ERR_SHAPE;
     if (fmt != MX_E4M3 && fmt != MX_E2M3) return BYA_ERR_SHAPE;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return BYA_ERR_SHAPE;
@@ -274,7 +275,7 @@ extern "C" int bya_gemm_mx(const void* A, const void* a_scales, const void* W, c
     if (((uintptr_t)C | (uintptr_t)res | (uintptr_t)bias | (uintptr_t)gate0 | (uintptr_t)gate1) & 7) return BYA_ERR_ALIGN;
     if (!act_on_big_tiles(d->act)) return BYA_ERR_UNSUPPORTED;            // none / GELU(tanh): the DiT Linears
     if (d->n_split < 0 || (d->n_split > 0 && (d->n_split % 4 || d->c_split_stride % 4 || res))) return BYA_ERR_SHAPE;
-    GemmArgs a;
+    GemmArgs& a = *out;
     a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C;
     a.res = (const bf16_t*)res; a.gate0 = (const bf16_t*)gate0; a.gate1 = (const bf16_t*)(gate1 ? gate1 : gate0);
     a.M = d->M; a.N = d->N; a.K = d->K;
@@ -284,14 +285,45 @@ extern "C" int bya_gemm_mx(const void* A, const void* a_scales, const void* W, c
     a.n_split = d->n_split; a.c_split_stride = d->c_split_stride;
     a.bias_rowscale = d->bias_rowscale; a.alpha = d->alpha == 0.0f ? 1.0f : d->alpha;
     a.ws_counters = nullptr; a.ws_slabs = nullptr;
+    return BYA_OK;
+}
+
+// e4m3 on 128 x 128 tiles; e2m3 on 256 x 256 tiles when the launch has about a round of 256 CUs of them, or more
+inline int mx_path(const GemmArgs& a, int batch, int32_t fmt) {
+    const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
+    const bool big = BYA_MX_E2M3_BIG_TILE && tiles256 >= 200;
+    return fmt == MX_E2M3 && big ? BYA_GEMM_PATH_T256X256 : BYA_GEMM_PATH_T128X128;
+}
+}  // namespace
+
+extern "C" int bya_gemm_mx(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                           void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
+                           int32_t fmt, hipStream_t stream) {
+    GemmArgs a;
+    const int rc = mx_args(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, fmt, &a);
+    if (rc != BYA_OK) return rc;
     const uint8_t* sa = (const uint8_t*)a_scales;
     const uint8_t* sw = (const uint8_t*)w_scales;
     const long long ks = d->K / 32;
-    const long long tiles256 = (long long)((d->M + 255) / 256) * ((d->N + 255) / 256) * d->batch;
-    const bool big = BYA_MX_E2M3_BIG_TILE && tiles256 >= 200;          // (about a round of 256 CUs, or more)
+    const int path = mx_path(a, d->batch, fmt);
     return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
         if (fmt == MX_E4M3) return launch_mx<MX_E4M3, 128, 128, 2, 2>(piece, sa + row0 * ks, sw, batch, stream);
-        if (big) return launch_mx<MX_E2M3, 256, 256, 4, 2>(piece, sa + row0 * ks, sw, batch, stream);
+        if (path == BYA_GEMM_PATH_T256X256) return launch_mx<MX_E2M3, 256, 256, 4, 2>(piece, sa + row0 * ks, sw, batch, stream);
         return launch_mx<MX_E2M3, 128, 128, 2, 2>(piece, sa + row0 * ks, sw, batch, stream);
     });
+}
+
+extern "C" int bya_gemm_mx_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                                const void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
+                                int32_t fmt, bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    GemmArgs a, piece;
+    int nb = 0;
+    const int rc = mx_args(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, fmt, &a);
+    if (rc != BYA_OK) return rc;
+    const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
+    if (!chunks) return BYA_ERR_UNSUPPORTED;
+    p->path = mx_path(a, d->batch, fmt);
+    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = chunks;
+    return BYA_OK;
 }

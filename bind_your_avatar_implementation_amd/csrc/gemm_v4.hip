@@ -966,21 +966,27 @@ int bya_gemm_split_min_ktiles() {
     return v < 3 ? 3 : v;
 }
 
+// split the last partial round along K when a workspace is registered (option gemm_splitk, read per call) -- and only when
+// some XCD has tiles left over after its full rounds (only then the split instance is worth its epilogue branch)
+int bya_gemm256p_split(const void* args, int batch) {
+    const GemmArgs& a = *static_cast<const GemmArgs*>(args);
+    const long long total = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
+    const int sk = bya_opt(BYA_OPT_GEMM_SPLITK);
+    const int split = (a.ws_slabs && a.ws_counters && sk != 0 && a.K / BK >= 2 * bya_gemm_split_min_ktiles()) ? (sk == 2 ? 2 : 1) : 0;
+    return total % 256 != 0 ? split : 0;
+}
+
 int bya_launch_gemm256p(const void* args, int batch, hipStream_t s) {
     GemmArgs a = *static_cast<const GemmArgs*>(args);
     a.gm = gemm_group_m(a);
     const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
     const long long total = (long long)tiles_m * tiles_n * batch;
-    // split the last partial round along K when a workspace is registered (BYA_GEMM_SPLITK=0 switches it off, read per call)
-    const int sk = bya_opt(BYA_OPT_GEMM_SPLITK);
     const int min_seg = bya_gemm_split_min_ktiles();
-    const int split = (a.ws_slabs && a.ws_counters && sk != 0 && a.K / BK >= 2 * min_seg) ? (sk == 2 ? 2 : 1) : 0;
+    const int split = bya_gemm256p_split(args, batch);
     int blocks = (int)(total < 256 && !split ? (total + 7) / 8 * 8 : 256);
     const size_t lds = 2 * 512 * BK * 2;
     static std::atomic<unsigned long long> attr_done{0}, attr_done_s{0};
-    // would any XCD have tiles left over after its full rounds?  (only then the split instance is worth its epilogue branch)
-    const bool leftover = split && (total % 256 != 0);
-    if (leftover) {
+    if (split) {
         if (bya_allow_big_lds(reinterpret_cast<const void*>(gemm256p_kernel<true>), (int)lds, attr_done_s) != BYA_OK) return BYA_ERR_LAUNCH;
         // launch epoch, 24 bits, never 0 (0 = the zero-filled initial state of a counter word)
         static std::atomic<unsigned> g_epoch{0};

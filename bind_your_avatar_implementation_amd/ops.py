@@ -213,14 +213,32 @@ def kernel_timer_flops():
 
 
 def _p(t):
-    return None if t is None else t.data_ptr()
+    """Device address of a tensor for a launch (meta tensors are refused: there is nothing behind them)."""
+    if t is None:
+        return None
+    if t.is_meta:
+        raise ValueError("a meta tensor cannot be passed to a kernel launch (only the *_plan queries take them)")
+    return t.data_ptr()
 
 
-def _mat(t, name):
-    """-> (batch, rows, cols, batch_stride, row_stride) of a 2-D/3-D view with unit inner stride."""
+# The plan queries (gemm_plan & co.) launch nothing and run without a GPU: there meta tensors may stand for device tensors.
+# Their "address" is this base plus the view's offset, so the 16-byte alignment of a strided view is what it would be on the
+# device.  Launches never see these addresses (_p and _mat refuse meta tensors).
+_META_BASE = 1 << 40
+
+
+def _plan_p(t):
+    if t is None:
+        return None
+    return _META_BASE + t.storage_offset() * t.element_size() if t.is_meta else t.data_ptr()
+
+
+def _mat(t, name, allow_meta=False):
+    """-> (batch, rows, cols, batch_stride, row_stride) of a 2-D/3-D view with unit inner stride (``allow_meta``: the plan
+    queries)."""
     if t.dtype != torch.bfloat16:
         raise TypeError(f"{name}: expected bf16, got {t.dtype}")
-    if not t.is_cuda:
+    if not (t.is_cuda or (allow_meta and t.is_meta)):
         raise ValueError(f"{name}: expected a device tensor (the engine has no CPU path)")
     if t.stride(-1) != 1:
         raise ValueError(f"{name}: inner stride must be 1")
@@ -353,17 +371,9 @@ def attn_workspace_status(device=None):
     return n.value
 
 
-def gemm(a, w, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0, gate_batch_stride=0, act=None,
-         split=None, bias_rowscale=None, alpha=1.0):
-    """out = res + gate * act(a @ w.T + bias).  a: [(B,) M, K], w: [N, K], out/res: [(B,) M, N].
-
-    ``split=(n_split, stride)``: ``out`` is the FIRST of N/n_split equally shaped tensors ``stride`` elements apart;
-    column n of the product lands in tensor n // n_split (packed q|k|v projection -> three buffers, one launch)."""
-    lib = _hip.load()
-    ab, M, K, a_bs, lda = _mat(a, "a")
-    ob, Mo, N, c_bs, ldc = _mat(out, "out")
-    if a.device.index not in _GEMM_WS:
-        ensure_gemm_workspace(a.device)
+def _gemm_desc(a, w, out, res, gate_split, gate_batch_stride, act, split, bias_rowscale, alpha, plan=False):
+    ab, M, K, a_bs, lda = _mat(a, "a", plan)
+    ob, Mo, N, c_bs, ldc = _mat(out, "out", plan)
     if split is not None:
         N = w.shape[0]
     if w.dim() != 2 or w.shape[1] != K or w.shape[0] != N or w.stride(1) != 1 or w.dtype != torch.bfloat16:
@@ -376,15 +386,35 @@ def gemm(a, w, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0, g
     d.a_batch_stride, d.c_batch_stride = a_bs, c_bs
     d.ldres, d.res_batch_stride = 0, 0
     if res is not None:
-        rb, Mr, Nr, r_bs, ldres = _mat(res, "res")
+        rb, Mr, Nr, r_bs, ldres = _mat(res, "res", plan)
         if (Mr, Nr) != (M, N) or rb not in (1, ab):
             raise ValueError("res shape mismatch")
         d.ldres, d.res_batch_stride = ldres, (r_bs if rb == ab else 0)
     d.gate_batch_stride, d.gate_split, d.act = gate_batch_stride, gate_split, ACT[act]
     d.n_split, d.c_split_stride = (0, 0) if split is None else split
-    d.bias_rowscale, d.alpha = _p(bias_rowscale), float(alpha)
+    d.bias_rowscale, d.alpha = (_plan_p if plan else _p)(bias_rowscale), float(alpha)
     if bias_rowscale is not None:
         assert bias_rowscale.dtype == torch.float32 and bias_rowscale.is_contiguous() and bias_rowscale.numel() == ab * M
+    return d
+
+
+def _takes_skinny(d, gate0, bias_rowscale, split):
+    """ops.gemm sends the launch to the weight-streaming kernel (``weight_streaming``)."""
+    return (_WEIGHT_STREAMING and d.M <= 64 and d.N <= 8192 and d.N % 16 == 0 and d.K % 32 == 0 and d.K >= 256 and gate0 is None
+            and bias_rowscale is None and split is None and d.a_batch_stride % 8 == 0)
+
+
+def gemm(a, w, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0, gate_batch_stride=0, act=None,
+         split=None, bias_rowscale=None, alpha=1.0):
+    """out = res + gate * act(a @ w.T + bias).  a: [(B,) M, K], w: [N, K], out/res: [(B,) M, N].
+
+    ``split=(n_split, stride)``: ``out`` is the FIRST of N/n_split equally shaped tensors ``stride`` elements apart;
+    column n of the product lands in tensor n // n_split (packed q|k|v projection -> three buffers, one launch)."""
+    lib = _hip.load()
+    d = _gemm_desc(a, w, out, res, gate_split, gate_batch_stride, act, split, bias_rowscale, alpha)     # (validates first)
+    if a.device.index not in _GEMM_WS:
+        ensure_gemm_workspace(a.device)
+    ab, M, N, K = d.batch, d.M, d.N, d.K
     # per-kernel timers: Linears over fewer than 1024 rows (the step-invariant conditioning: 32 face tokens, 52 audio windows,
     # 577 ViT tokens against 2048..49152-wide weights) stream their WEIGHTS and are bound by HBM, not by the matrix cores --
     # they get their own bucket so that the MFMA roofline of bench.py is taken over the launches it applies to
@@ -392,8 +422,7 @@ def gemm(a, w, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0, g
     if _SHAPE_LABELS:
         name += f":{ab}x{M}x{N}x{K}:{act or 'none'}{'+gate' if gate0 is not None else ''}{'+res' if res is not None else ''}"
     tok = _begin(name, 2.0 * ab * M * N * K)
-    if (_WEIGHT_STREAMING and M <= 64 and N <= 8192 and N % 16 == 0 and K % 32 == 0 and K >= 256 and gate0 is None
-            and bias_rowscale is None and split is None and a_bs % 8 == 0):
+    if _takes_skinny(d, gate0, bias_rowscale, split):
         check(lib.bya_gemm_skinny_bf16(_p(a), _p(w), _p(bias), _p(out), _p(res), ctypes.byref(d), _stream()),
               "bya_gemm_skinny_bf16")
     else:
@@ -403,13 +432,42 @@ def gemm(a, w, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0, g
     return out
 
 
-def gemm_qkv_norm_rope(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6, k_scale=1.0, tensors=3):
-    """The packed q|k|v projection with the q/k LayerNorm(64) + RoPE in its epilogue (bya_gemm_qkv_norm_rope): equals
-    ``gemm(..., split=split)`` followed by ``qknorm_rope`` bit for bit, in one launch.  Returns False (nothing launched) when
-    the library does not take the shape -- the caller then issues the two launches."""
+# ---- plan queries (include/bya.h bya_gemm_plan): which kernels a GEMM launch with these arguments runs, under the current
+# options and the current device's split-K workspace.  They launch nothing; meta tensors stand for device tensors.  Given
+# device tensors they register the device's workspace as the launch would (else a query made before the device's first GEMM
+# would miss a split-K the launch then takes).
+GEMM_PATHS = _hip.GEMM_PATHS
+
+
+def _plan_dict(p):
+    return {"path": GEMM_PATHS[p.path], "m0": p.m0, "tail": GEMM_PATHS.get(p.tail) if p.m0 > 0 else None,
+            "split_k": p.split_k, "row_chunks": p.row_chunks}
+
+
+def plan_key(plan):
+    """One name per distinct kernel sequence: "p256", "p256|t128x128" (row split, tail kernel), "p256+splitk"."""
+    return plan["path"] + (f"|{plan['tail']}" if plan["tail"] else "") + ("+splitk" if plan["split_k"] else "")
+
+
+def gemm_plan(a, w, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0, gate_batch_stride=0, act=None,
+              split=None, bias_rowscale=None, alpha=1.0):
+    """What ``gemm`` with the same arguments would run: {"path", "m0", "tail", "split_k", "row_chunks"} (kernel names of
+    ``GEMM_PATHS``, or path "skinny" for the weight-streaming kernel).  Raises what ``gemm`` would raise."""
     lib = _hip.load()
-    ab, M, K, a_bs, lda = _mat(a, "a")
-    ob, Mo, _, c_bs, ldc = _mat(out, "out")
+    d = _gemm_desc(a, w, out, res, gate_split, gate_batch_stride, act, split, bias_rowscale, alpha, plan=True)
+    if a.is_cuda and a.device.index not in _GEMM_WS:
+        ensure_gemm_workspace(a.device)
+    if _takes_skinny(d, gate0, bias_rowscale, split):
+        return {"path": "skinny", "m0": 0, "tail": None, "split_k": 0, "row_chunks": 1}
+    p, q = _hip.GemmPlan(), _plan_p
+    check(lib.bya_gemm_bf16_plan(q(a), q(w), q(bias), q(out), q(res), q(gate0), q(gate1), ctypes.byref(d),
+                                 ctypes.byref(p)), "bya_gemm_bf16_plan")
+    return _plan_dict(p)
+
+
+def _qkn_descs(a, w, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors, plan=False):
+    ab, M, K, a_bs, lda = _mat(a, "a", plan)
+    ob, Mo, _, c_bs, ldc = _mat(out, "out", plan)
     N = w.shape[0]
     if w.dim() != 2 or w.shape[1] != K or w.stride(1) != 1 or w.dtype != torch.bfloat16 or tensors not in (2, 3) or N % tensors \
             or (ab, M) != (ob, Mo):
@@ -422,11 +480,22 @@ def gemm_qkv_norm_rope(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, text_ro
     d.n_split, d.c_split_stride = split
     d.alpha = 1.0
     n = _hip.QkNormDesc()
-    n.qw, n.qb, n.kw, n.kb, n.cos, n.sin = _p(qw), _p(qb), _p(kw), _p(kb), _p(cos), _p(sin)
+    ptr = _plan_p if plan else _p
+    n.qw, n.qb, n.kw, n.kb, n.cos, n.sin = ptr(qw), ptr(qb), ptr(kw), ptr(kb), ptr(cos), ptr(sin)
     n.text_rows, n.width, n.eps, n.k_scale = int(text_rows), N // tensors, float(eps), float(k_scale)
     if cos is not None:
         assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
         assert cos.shape == (M - text_rows, 64)
+    return d, n
+
+
+def gemm_qkv_norm_rope(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6, k_scale=1.0, tensors=3):
+    """The packed q|k|v projection with the q/k LayerNorm(64) + RoPE in its epilogue (bya_gemm_qkv_norm_rope): equals
+    ``gemm(..., split=split)`` followed by ``qknorm_rope`` bit for bit, in one launch.  Returns False (nothing launched) when
+    the library does not take the shape -- the caller then issues the two launches."""
+    lib = _hip.load()
+    d, n = _qkn_descs(a, w, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors)
+    ab, M, N, K = d.batch, d.M, d.N, d.K
     tok = _begin("bya_gemm_bf16" if M >= 1024 else "bya_gemm_bf16_small_m")
     rc = lib.bya_gemm_qkv_norm_rope(_p(a), _p(w), _p(bias), _p(out), ctypes.byref(d), ctypes.byref(n), _stream())
     if rc == -4:                       # BYA_ERR_UNSUPPORTED: not this kernel's shape -- nothing was launched, nothing is counted
@@ -436,6 +505,19 @@ def gemm_qkv_norm_rope(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, text_ro
         _FLOPS[tok[0]] = _FLOPS.get(tok[0], 0.0) + 2.0 * ab * M * N * K
     _end(tok)
     return True
+
+
+def gemm_qkv_norm_rope_plan(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6, k_scale=1.0, tensors=3):
+    """What ``gemm_qkv_norm_rope`` would run (``gemm_plan``'s dict): path "p256" (its row plan 0), "p128" (plan 1), or
+    "p256" with m0 and tail "p128" (plan 2); None where it declines the shape (the caller's two launches)."""
+    lib = _hip.load()
+    d, n = _qkn_descs(a, w, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors, plan=True)
+    p, q = _hip.GemmPlan(), _plan_p
+    rc = lib.bya_gemm_qkv_norm_rope_plan(q(a), q(w), q(bias), q(out), ctypes.byref(d), ctypes.byref(n), ctypes.byref(p))
+    if rc == -4:
+        return None
+    check(rc, "bya_gemm_qkv_norm_rope_plan")
+    return _plan_dict(p)
 
 
 def quantize_rows_fp8(x, q=None, scale=None):
@@ -456,15 +538,12 @@ def quantize_rows_fp8(x, q=None, scale=None):
     return q, scale
 
 
-def gemm_fp8(a8, a_scale, w8, w_scale, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0,
-             gate_batch_stride=0, act=None, split=None, alpha=1.0):
-    """out = res + gate * act(a_scale * w_scale * (a8 @ w8.T) + bias) with e4m3 operands (``quantize_rows_fp8``)."""
-    lib = _hip.load()
+def _fp8_desc(a8, a_scale, w8, w_scale, out, res, gate_split, gate_batch_stride, act, split, alpha, plan=False):
     if a8.dim() == 2:
         ab, (M, K) = 1, a8.shape
     else:
         ab, M, K = a8.shape
-    ob, Mo, N, c_bs, ldc = _mat(out, "out")
+    ob, Mo, N, c_bs, ldc = _mat(out, "out", plan)
     if split is not None:
         N = w8.shape[0]
     assert a8.dtype == torch.uint8 and w8.dtype == torch.uint8 and a8.is_contiguous() and w8.is_contiguous()
@@ -477,13 +556,22 @@ def gemm_fp8(a8, a_scale, w8, w_scale, out, bias=None, res=None, gate0=None, gat
     d.a_batch_stride, d.c_batch_stride = M * K, c_bs
     d.ldres, d.res_batch_stride = 0, 0
     if res is not None:
-        rb, Mr, Nr, r_bs, ldres = _mat(res, "res")
+        rb, Mr, Nr, r_bs, ldres = _mat(res, "res", plan)
         if (Mr, Nr) != (M, N) or rb not in (1, ab):
             raise ValueError("res shape mismatch")
         d.ldres, d.res_batch_stride = ldres, (r_bs if rb == ab else 0)
     d.gate_batch_stride, d.gate_split, d.act = gate_batch_stride, gate_split, ACT[act]
     d.n_split, d.c_split_stride = (0, 0) if split is None else split
     d.bias_rowscale, d.alpha = None, float(alpha)
+    return d
+
+
+def gemm_fp8(a8, a_scale, w8, w_scale, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0,
+             gate_batch_stride=0, act=None, split=None, alpha=1.0):
+    """out = res + gate * act(a_scale * w_scale * (a8 @ w8.T) + bias) with e4m3 operands (``quantize_rows_fp8``)."""
+    lib = _hip.load()
+    d = _fp8_desc(a8, a_scale, w8, w_scale, out, res, gate_split, gate_batch_stride, act, split, alpha)
+    ab, M, N, K = d.batch, d.M, d.N, d.K
     name = "bya_gemm_fp8"
     if _SHAPE_LABELS:
         name += f":{ab}x{M}x{N}x{K}:{act or 'none'}{'+gate' if gate0 is not None else ''}{'+res' if res is not None else ''}"
@@ -492,6 +580,17 @@ def gemm_fp8(a8, a_scale, w8, w_scale, out, bias=None, res=None, gate0=None, gat
                            ctypes.byref(d), _stream()), "bya_gemm_fp8")
     _end(tok)
     return out
+
+
+def gemm_fp8_plan(a8, a_scale, w8, w_scale, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0,
+                  gate_batch_stride=0, act=None, split=None, alpha=1.0):
+    """What ``gemm_fp8`` would run (``gemm_plan``'s dict): path "t128x128" or "p256"."""
+    lib = _hip.load()
+    d = _fp8_desc(a8, a_scale, w8, w_scale, out, res, gate_split, gate_batch_stride, act, split, alpha, plan=True)
+    p, q = _hip.GemmPlan(), _plan_p
+    check(lib.bya_gemm_fp8_plan(q(a8), q(a_scale), q(w8), q(w_scale), q(bias), q(out), q(res), q(gate0), q(gate1),
+                                ctypes.byref(d), ctypes.byref(p)), "bya_gemm_fp8_plan")
+    return _plan_dict(p)
 
 
 
@@ -532,17 +631,13 @@ def quantize_mx(x, fmt="mxfp6", codes=None, scales=None):
     return codes, scales
 
 
-def gemm_mx(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, res=None, gate0=None, gate1=None,
-            gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0):
-    """out = res + gate * act(A @ W.T + bias) with both operands in MX form (``quantize_mx``); K is read off the scales."""
-    lib = _hip.load()
-    code = mx_fmt_code(fmt)
+def _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, res, gate_split, gate_batch_stride, act, split, alpha, plan=False):
     if a_scales.dim() == 2:
         ab, (M, KS) = 1, a_scales.shape
     else:
         ab, M, KS = a_scales.shape
     K = KS * 32
-    ob, Mo, N, c_bs, ldc = _mat(out, "out")
+    ob, Mo, N, c_bs, ldc = _mat(out, "out", plan)
     if split is not None:
         N = w_codes.shape[0]
     rb_ = mx_code_bytes(K, fmt)
@@ -556,13 +651,23 @@ def gemm_mx(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, r
     d.a_batch_stride, d.c_batch_stride = M * rb_, c_bs
     d.ldres, d.res_batch_stride = 0, 0
     if res is not None:
-        rb, Mr, Nr, r_bs, ldres = _mat(res, "res")
+        rb, Mr, Nr, r_bs, ldres = _mat(res, "res", plan)
         if (Mr, Nr) != (M, N) or rb not in (1, ab):
             raise ValueError("res shape mismatch")
         d.ldres, d.res_batch_stride = ldres, (r_bs if rb == ab else 0)
     d.gate_batch_stride, d.gate_split, d.act = gate_batch_stride, gate_split, ACT[act]
     d.n_split, d.c_split_stride = (0, 0) if split is None else split
     d.bias_rowscale, d.alpha = None, float(alpha)
+    return d
+
+
+def gemm_mx(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, res=None, gate0=None, gate1=None,
+            gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0):
+    """out = res + gate * act(A @ W.T + bias) with both operands in MX form (``quantize_mx``); K is read off the scales."""
+    lib = _hip.load()
+    code = mx_fmt_code(fmt)
+    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, res, gate_split, gate_batch_stride, act, split, alpha)
+    ab, M, N, K = d.batch, d.M, d.N, d.K
     name = "bya_gemm_mx"
     if _SHAPE_LABELS:
         name += f":{fmt}:{ab}x{M}x{N}x{K}:{act or 'none'}{'+gate' if gate0 is not None else ''}{'+res' if res is not None else ''}"
@@ -571,6 +676,19 @@ def gemm_mx(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, r
                           _p(gate1), ctypes.byref(d), code, _stream()), "bya_gemm_mx")
     _end(tok)
     return out
+
+
+def gemm_mx_plan(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, res=None, gate0=None, gate1=None,
+                 gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0):
+    """What ``gemm_mx`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 only)."""
+    lib = _hip.load()
+    code = mx_fmt_code(fmt)
+    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, res, gate_split, gate_batch_stride, act, split, alpha, plan=True)
+    p, q = _hip.GemmPlan(), _plan_p
+    check(lib.bya_gemm_mx_plan(q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), q(res), q(gate0),
+                               q(gate1), ctypes.byref(d), code, ctypes.byref(p)), "bya_gemm_mx_plan")
+    return _plan_dict(p)
+
 
 def linear_small_m(x, w, bias, out, silu_in=False, act_out=None):
     """out[M<=8, N] = f(x) @ w.T + bias (weight-streaming kernel)."""

@@ -153,6 +153,38 @@ int bya_gemm_workspace_bytes(int64_t* bytes);
  * entry point that synchronises (it copies a word back over `stream`): call it at step or run end, not per launch. */
 int bya_gemm_workspace_status(int32_t* timeouts, hipStream_t stream);
 
+/* Which kernels a GEMM launch runs (host-side queries like bya_attn_variant: they launch nothing and need no GPU).  The GEMM
+ * entry points choose their kernels by shape, pointer alignment, the current device's split-K workspace and the options
+ * table; each query takes the arguments of its entry point (stream replaced by the plan) and reports what a launch with
+ * the same arguments, enqueued now, runs -- the launch calls the same plan functions.  Return value: what the entry point
+ * would return before launching (0, or the BYA_ERR_* that rejects the arguments; the plan is then untouched).
+ * Path codes (the 256 x 256 and 128 x 256 "persistent" kernels run one wave per SIMD): */
+#define BYA_GEMM_PATH_T128X64 0   /* 128 x 64 tiles, 4 waves (option gemm_tile = 0; N <= 64) */
+#define BYA_GEMM_PATH_T128X128 1  /* 128 x 128 tiles, 4 waves (gemm_tile = 1); bya_gemm_fp8 / bya_gemm_mx: their 128 x 128 kernel */
+#define BYA_GEMM_PATH_T256X128 2  /* 256 x 128 tiles, 8 waves (gemm_tile = 2) */
+#define BYA_GEMM_PATH_T256X256 3  /* 256 x 256 tiles, 8 waves (gemm_tile = 3); bya_gemm_mx: the e2m3 256 x 256 kernel */
+#define BYA_GEMM_PATH_P256 4      /* persistent 256 x 256 (csrc/gemm_v4.hip); bya_gemm_fp8: csrc/gemm_fp8_v4.hip */
+#define BYA_GEMM_PATH_P128 5      /* persistent 128 x 256 (csrc/gemm_v5.hip) */
+#define BYA_GEMM_PATH_P128S 6     /* persistent 128 x 256 with loader waves (csrc/gemm_v6.hip) */
+#define BYA_GEMM_PATH_W8_256 7    /* the 8-wave 256 x 256 kernel P256 falls back to (fewer than 3 K-tiles, a C / res / bias /
+                                     gate pointer or stride that is not 16-byte aligned) and that option gemm_variant = 1 takes */
+#define BYA_GEMM_PATH_COUNT 8
+typedef struct bya_gemm_plan {
+    int32_t path;             /* BYA_GEMM_PATH_*; with a row split: the kernel of rows [0, m0) */
+    int32_t m0;               /* > 0: row split -- rows [m0, M) run as a second launch on `tail`; 0: no split */
+    int32_t tail;             /* BYA_GEMM_PATH_* of the rows behind m0; -1 without a row split */
+    int32_t split_k;          /* P256 cuts the tiles of its last, partial round along K (option gemm_splitk: 1 or 2); 0: no */
+    int32_t row_chunks;       /* launches the 2 GiB reach of the epilogues cuts the product into (1: one; the fields above
+                                 describe the first) */
+} bya_gemm_plan;
+/* bya_gemm_bf16 */
+int bya_gemm_bf16_plan(const void* A, const void* W, const void* bias, const void* C, const void* res,
+                       const void* gate0, const void* gate1, const bya_gemm_desc* desc, bya_gemm_plan* plan);
+/* bya_gemm_qkv_norm_rope: path P256 (its plan 0), P128 (plan 1: 128-row tiles) or P256 with m0 and tail P128 (plan 2);
+ * BYA_ERR_UNSUPPORTED where the entry point declines the shape */
+int bya_gemm_qkv_norm_rope_plan(const void* A, const void* W, const void* bias, const void* C, const bya_gemm_desc* desc,
+                                const bya_qknorm_desc* norm, bya_gemm_plan* plan);
+
 /* ---------------------------------------------------------------------------------------------
  * fp8 weights (BASELINE configs[4]; no reference counterpart: the reference runs bf16/fp16 only).
  * OCP e4m3fn bytes, symmetric per-row scales:  x[m,k] ~= scale[m] * fp8(q[m,k]).
@@ -173,6 +205,10 @@ int bya_quantize_rows_fp8(const void* x, void* q, float* scale, int32_t M, int32
                           hipStream_t stream);
 int bya_gemm_fp8(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias, void* C,
                  const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* desc, hipStream_t stream);
+/* its kernel (bya_gemm_bf16_plan): path T128X128 (the 128 x 128 kernel) or P256 (the persistent 256 x 256 one) */
+int bya_gemm_fp8_plan(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias,
+                      const void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* desc,
+                      bya_gemm_plan* plan);
 /* bya_layernorm_fp8: bya_layernorm (same arguments, same arithmetic) followed by bya_quantize_rows_fp8 of each output row,
  * in one pass: the normalised + modulated row is rounded to bf16 exactly as bya_layernorm would store it, then quantised --
  * byte for byte what the two launches produce, without the bf16 round trip.  q uint8 [batch][rows][D] (row stride ldq,
@@ -224,6 +260,10 @@ int bya_layernorm_mx(const void* x, void* q, void* q_scales, const void* w, cons
 int bya_gemm_mx(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, void* C,
                 const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* desc, int32_t fmt,
                 hipStream_t stream);
+/* its kernel (bya_gemm_bf16_plan): path T128X128 (both formats) or T256X256 (e2m3 only) */
+int bya_gemm_mx_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                     const void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* desc,
+                     int32_t fmt, bya_gemm_plan* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Small-M linear (M <= 8 rows):  out[m,n] = sum_k f(x[m,k]) * W[n,k] + bias[n],  f = identity or SiLU.

@@ -23,7 +23,8 @@ def declared_symbols():
 
 def test_header_declares_the_documented_entry_points():
     syms = declared_symbols()
-    for must in ["bya_gemm_bf16", "bya_gemm_skinny_bf16", "bya_attn_fwd", "bya_layernorm", "bya_qknorm_rope", "bya_masked_combine",
+    for must in ["bya_gemm_bf16", "bya_gemm_bf16_plan", "bya_gemm_qkv_norm_rope_plan", "bya_gemm_fp8_plan", "bya_gemm_mx_plan",
+                 "bya_gemm_skinny_bf16", "bya_attn_fwd", "bya_layernorm", "bya_qknorm_rope", "bya_masked_combine",
                  "bya_router_scores", "bya_router_head", "bya_forcing_max_over_frames", "bya_patchify",
                  "bya_unpatchify", "bya_linear_small_m", "bya_timestep_features", "bya_attn_tiny", "bya_act_add",
                  "bya_abi_version"]:
@@ -46,6 +47,20 @@ def test_python_binding_table_matches_header(lib_path):
     assert lib.bya_gemm_bf16(None, None, None, None, None, None, None, ctypes.byref(d), None) == -1
     a = _hip.AttnDesc()
     assert lib.bya_attn_fwd(None, None, None, None, ctypes.byref(a), None) == -1
+    # the GEMM plan queries validate like their entry points and fill the plan (host-side, launch nothing)
+    p = _hip.GemmPlan(-9, -9, -9, -9, -9)
+    assert lib.bya_gemm_bf16_plan(None, None, None, None, None, None, None, ctypes.byref(d), ctypes.byref(p)) == -1
+    assert lib.bya_gemm_fp8_plan(None, None, None, None, None, None, None, None, None, ctypes.byref(d), ctypes.byref(p)) == -1
+    assert lib.bya_gemm_mx_plan(None, None, None, None, None, None, None, None, None, ctypes.byref(d), 2, ctypes.byref(p)) == -1
+    n = _hip.QkNormDesc()
+    assert lib.bya_gemm_qkv_norm_rope_plan(None, None, None, None, ctypes.byref(d), ctypes.byref(n), ctypes.byref(p)) == -1
+    assert (p.path, p.m0) == (-9, -9)                                       # untouched on rejection
+    d.M, d.N, d.K, d.batch, d.lda, d.ldw, d.ldc = 300, 64, 512, 1, 512, 512, 64
+    base = 1 << 40
+    assert lib.bya_gemm_bf16_plan(base, base, None, base, None, None, None, ctypes.byref(d), ctypes.byref(p)) == 0
+    assert (p.path, p.m0, p.tail, p.split_k, p.row_chunks) == (0, 0, -1, 0, 1)    # N <= 64: 128 x 64 tiles
+    assert lib.bya_gemm_bf16_plan(base, base, None, base + 2, None, None, None, ctypes.byref(d), ctypes.byref(p)) == -2
+    assert lib.bya_gemm_bf16_plan(base, base, None, base, None, None, None, ctypes.byref(d), None) == -1
     # the softmax-variant query mirrors bya_attn_fwd's kernel choice (host-side, launches nothing)
     a.head_dim, a.scores_prescaled, a.score_bound = 64, 1, 11.8
     assert lib.bya_attn_variant(ctypes.byref(a)) == 4          # static bound on the one-wave-per-SIMD kernel
@@ -68,10 +83,10 @@ def test_python_binding_table_matches_header(lib_path):
 
 
 def test_struct_layout_matches_header():
-    """ctypes mirrors of bya_gemm_desc / bya_attn_desc: field order and sizes as in the header."""
+    """ctypes mirrors of bya_gemm_desc / bya_attn_desc / bya_gemm_plan: field order and sizes as in the header."""
     from bind_your_avatar_implementation_amd import _hip
     src = open(os.path.join(ROOT, "include", "bya.h")).read()
-    for cname, cls in (("bya_gemm_desc", _hip.GemmDesc), ("bya_attn_desc", _hip.AttnDesc)):
+    for cname, cls in (("bya_gemm_desc", _hip.GemmDesc), ("bya_attn_desc", _hip.AttnDesc), ("bya_gemm_plan", _hip.GemmPlan)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), src, flags=re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         fields = []

@@ -358,11 +358,14 @@ def test_gemm_split_output(ops, dev):
 
 @pytest.mark.parametrize("M,N,K", [(1024, 1024, 64), (2500, 3072, 192), (4100, 768, 3072), (17776, 512, 512)])
 def test_gemm_pipelined_256(ops, dev, M, N, K):
-    """Shapes that select the pipelined 256x256 kernel (ragged M and N tiles, K = 1 and 3 tiles, long K)."""
+    """The 256x256 kernels (ragged M and N tiles, K = 1 and 3 tiles, long K), forced: the cost model sends none of these shapes
+    there (ops.gemm_plan).  K = 1 tile runs the 8-wave kernel, the others the persistent one."""
     a, w, b = rnd((M, K), dev, 16), rnd((N, K), dev, 17, K ** -0.5), rnd((N,), dev, 18)
     res = rnd((M, N), dev, 19)
-    out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
-    ops.gemm(a, w, out, bias=b, res=res, act="gelu_tanh")
+    out = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev)
+    with ops.options(gemm_tile=4):
+        assert ops.plan_key(ops.gemm_plan(a, w, out, bias=b, res=res, act="gelu_tanh")) == ("w8_256" if K < 192 else "p256")
+        ops.gemm(a, w, out, bias=b, res=res, act="gelu_tanh")
     check(out, res.float() + F.gelu(a.float() @ w.float().T + b.float(), approximate="tanh"), what=f"gemm256 {M}x{N}x{K}")
 
 
@@ -1019,7 +1022,8 @@ def test_qkv_projection_with_the_norm_in_its_epilogue_is_bit_identical(ops, dev,
     assert torch.equal(one, two), (float((one.float() - two.float()).abs().max()),
                                    int((one != two).sum()), [int((one[t] != two[t]).sum()) for t in range(3 * blocks)])
     assert float(one[:2 * blocks].float().abs().sum()) > 0
-    # ... on either persistent tile: 256 x 256 (gemm_v4.hip) and 128 x 256 (gemm_v5.hip; the library's choice at 2222 rows)
+    # ... on either persistent tile: 256 x 256 (gemm_v4.hip) and 128 x 256 (gemm_v5.hip; at 2222 rows the library splits the rows
+    # between the two, ops.gemm_qkv_norm_rope_plan)
     for tile in (4, 5):
         forced = outputs()
         with ops.options(gemm_tile=tile):
