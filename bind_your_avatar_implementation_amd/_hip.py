@@ -47,6 +47,19 @@ class AttnMixDesc(_c.Structure):
                 ("v_id", _i64), ("v_grp", _i64), ("v_row", _i64), ("z_grp", _i64), ("z_row", _i64), ("scale", _f32)]
 
 
+class AttnPlan(_c.Structure):
+    _fields_ = [("variant", _i32), ("grid", _i32), ("q_tile", _i32), ("stream_k", _i32), ("sk_rem", _i32), ("sk_cut", _i32),
+                ("o_wide", _i32), ("second_launch", _i32)]
+
+
+class AttnMixPlan(_c.Structure):
+    _fields_ = [("form", _i32), ("head_dim", _i32), ("grid", _i32), ("row_chunks", _i32), ("lds_bytes", _i32), ("big_lds", _i32)]
+
+
+class AttnTinyPlan(_c.Structure):
+    _fields_ = [("instance", _i32), ("grid", _i32), ("waves", _i64)]
+
+
 class SchedCoef(_c.Structure):
     _fields_ = [("guidance", _f32), ("sqrt_alpha", _f32), ("sqrt_beta", _f32), ("k_sample", _f32),
                 ("k_denoised", _f32), ("k_noise", _f32), ("k_cur", _f32), ("k_old", _f32)]
@@ -83,11 +96,14 @@ SIGNATURES = {
     "bya_qknorm_rope": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i32, _f32, _f32, _vp, _i32, _vp],
     "bya_attn_fwd": [_vp, _vp, _vp, _vp, _c.POINTER(AttnDesc), _vp],
     "bya_attn_variant": [_c.POINTER(AttnDesc)],
+    "bya_attn_plan": [_c.POINTER(AttnDesc), _vp, _i32, _c.POINTER(AttnPlan)],
     "bya_set_attn_workspace": [_vp, _i64],
     "bya_attn_workspace_bytes": [_c.POINTER(_i64)],
     "bya_attn_workspace_status": [_c.POINTER(_i32), _vp],
     "bya_attn_kv_mix": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(AttnMixDesc), _vp],
+    "bya_attn_kv_mix_plan": [_vp, _vp, _c.POINTER(AttnMixDesc), _c.POINTER(AttnMixPlan)],
     "bya_attn_tiny": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp],
+    "bya_attn_tiny_plan": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _c.POINTER(AttnTinyPlan)],
     "bya_router_scores": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _vp],
     "bya_router_head": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp],
     "bya_forcing_max_over_frames": [_vp, _vp, _i32, _i64, _i32, _vp],
@@ -139,6 +155,13 @@ ENV_OPTIONS = {
 
 # BYA_GEMM_PATH_* of include/bya.h: the kernels of a GEMM launch (bya_gemm_plan.path / .tail)
 GEMM_PATHS = {0: "t128x64", 1: "t128x128", 2: "t256x128", 3: "t256x256", 4: "p256", 5: "p128", 6: "p128s", 7: "w8_256"}
+
+# BYA_ATTN_* / BYA_KV_MIX_* / BYA_TINY* of include/bya.h: the kernels of the attention launches (the *_plan queries)
+ATTN_VARIANTS = {0: "d64_running_max", 1: "d64_prescaled_running_max", 2: "d64_static_bound", 3: "d128_running_max",
+                 4: "d64_static_bound_w4", 5: "d64_device_bound_w4"}
+KV_MIX_FORMS = {0: "mix32", 1: "one_tile"}
+TINY_INSTANCES = {0: "tiny8<2>", 1: "tiny8<3>", 2: "tiny8<13>", 3: "tiny8<25>", 4: "generic<2>", 5: "generic<4>",
+                  6: "generic<16>", 7: "generic<32>"}
 
 ERRORS = {-1: "BYA_ERR_SHAPE", -2: "BYA_ERR_ALIGN", -3: "BYA_ERR_LAUNCH", -4: "BYA_ERR_UNSUPPORTED"}
 

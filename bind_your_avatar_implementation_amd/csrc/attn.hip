@@ -708,33 +708,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel_d128(AttnArgs p) {
 
 inline float static_bound_limit() { return BYA_ATTN_BOUND_LIMIT; }
 
-template <int D>
-int launch_attn(const AttnArgs& a, hipStream_t s) {
-    const int nbh = a.nb1 * a.nb2 * a.heads;
-    dim3 grid((nbh * a.nqt + 7) / 8 * 8);          // whole groups of 8 (one block per XCD); surplus blocks exit at once
-    const size_t lds = (size_t)ATTN_RING * 2 * KV_TILE * D * 2;
-    if (D == 64 && a.prescaled && a.bound_dev) {
-        // data-dependent bound: the static kernel serves every head whose bound is usable and flags the others, the
-        // running-maximum kernel right behind it serves exactly those (its other workgroups exit at once)
-        const int rc = bya_launch_attn_w4(&a, s);
-        if (rc != BYA_OK) return rc;
-        AttnArgs b = a;
-        b.bound_dev = nullptr; b.score_bound = 0.f; b.only_flagged = a.fallback; b.fallback = nullptr;
-        BYA_LAUNCH(attn_fwd_kernel_d64_prescaled, grid, dim3(256), lds, s, b);
-        return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
-    }
-    if (D == 64 && a.prescaled && a.score_bound > 0.f) return bya_launch_attn_w4(&a, s);
-    if (D == 64 && a.prescaled) BYA_LAUNCH(attn_fwd_kernel_d64_prescaled, grid, dim3(256), lds, s, a);
-    else if (D == 64) BYA_LAUNCH(attn_fwd_kernel_d64, grid, dim3(256), lds, s, a);
-    else BYA_LAUNCH(attn_fwd_kernel_d128, grid, dim3(256), lds, s, a);
-    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
-}
-
-}  // namespace
-
-// Which kernel a descriptor selects (reported to the host so tests and bench.py can say which softmax variant ran).
-extern "C" int bya_attn_variant(const bya_attn_desc* d) {
-    if (!d) return BYA_ERR_SHAPE;
+// Which softmax variant a (validated or not) descriptor selects: the ONE statement of that choice (bya_attn_variant,
+// bya_attn_plan and the launcher all go through it).
+inline int attn_variant_of(const bya_attn_desc* d) {
     if (d->head_dim == 128) return d->scores_prescaled ? BYA_ERR_UNSUPPORTED : BYA_ATTN_D128;
     if (d->head_dim != 64) return BYA_ERR_UNSUPPORTED;
     if (!d->scores_prescaled) return BYA_ATTN_D64_RUNNING_MAX;
@@ -745,8 +721,8 @@ extern "C" int bya_attn_variant(const bya_attn_desc* d) {
     return BYA_ATTN_D64_STATIC_BOUND_W4;
 }
 
-extern "C" int bya_attn_fwd(const void* q, const void* k, const void* v, void* o, const bya_attn_desc* d,
-                            hipStream_t stream) {
+// Argument checks of bya_attn_fwd and the kernel arguments they lead to (shared with bya_attn_plan, which has no q / k / v).
+int attn_args_of(const void* q, const void* k, const void* v, void* o, const bya_attn_desc* d, AttnArgs& a) {
     if (!q || !k || !v || !o || !d) return BYA_ERR_SHAPE;
     if (d->head_dim != 64 && d->head_dim != 128) return BYA_ERR_UNSUPPORTED;
     if (d->heads <= 0 || d->nb1 <= 0 || d->nb2 <= 0 || d->Sq <= 0 || d->Skv <= 0) return BYA_ERR_SHAPE;
@@ -754,7 +730,6 @@ extern "C" int bya_attn_fwd(const void* q, const void* k, const void* v, void* o
     if ((d->o_row | d->o_s1 | d->o_s2) % 4) return BYA_ERR_ALIGN;
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return BYA_ERR_ALIGN;
     if ((uintptr_t)o & 7) return BYA_ERR_ALIGN;
-    AttnArgs a;
     a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o;
     a.heads = d->heads; a.nb1 = d->nb1; a.nb2 = d->nb2; a.Sq = d->Sq; a.Skv = d->Skv;
     a.nqt = (d->Sq + Q_PER_BLOCK - 1) / Q_PER_BLOCK;
@@ -767,6 +742,7 @@ extern "C" int bya_attn_fwd(const void* q, const void* k, const void* v, void* o
     a.prescaled = d->scores_prescaled;
     if (a.prescaled && d->head_dim != 64) return BYA_ERR_UNSUPPORTED;
     a.score_bound = (a.prescaled && d->score_bound > 0.f && d->score_bound <= static_bound_limit()) ? d->score_bound : 0.f;
+    a.sk_part = nullptr; a.sk_flags = nullptr;
     a.bound_dev = nullptr; a.bound_slots = 0; a.bound_heads = 0; a.bound_bh0 = 0; a.bound_limit = BYA_ATTN_BOUND_LIMIT;
     a.fallback = nullptr; a.only_flagged = nullptr;
     if (d->bound_dev && a.prescaled) {
@@ -776,47 +752,146 @@ extern "C" int bya_attn_fwd(const void* q, const void* k, const void* v, void* o
         a.bound_dev = d->bound_dev; a.bound_slots = d->bound_slots; a.bound_heads = d->bound_heads; a.bound_bh0 = d->bound_bh0;
         a.fallback = d->fallback_flags;
     }
+    return BYA_OK;
+}
+
+// The launch decisions of bya_attn_fwd for checked arguments: which kernel(s), which grid, which store width.
+// ws_present: -1 = the current device's registered stream-K workspace decides, 0 / 1 = assume none / one.
+void attn_plan_of(const AttnArgs& a, int D, int ws_present, bya_attn_plan_info* p) {
+    const int nbh = a.nb1 * a.nb2 * a.heads;
+    p->grid = (nbh * a.nqt + 7) / 8 * 8;           // whole groups of 8 (one block per XCD); surplus blocks exit at once
+    p->q_tile = Q_PER_BLOCK;
+    p->stream_k = 0; p->sk_rem = 0; p->sk_cut = 0;
+    p->o_wide = a.o_wide;
+    p->second_launch = 0;
+    if (D == 128) { p->variant = BYA_ATTN_D128; return; }
+    if (!a.prescaled) { p->variant = BYA_ATTN_D64_RUNNING_MAX; return; }
+    if (!a.bound_dev && !(a.score_bound > 0.f)) { p->variant = BYA_ATTN_D64_PRESCALED; return; }
+    // data-dependent bound: the static kernel serves every head whose bound is usable and flags the others, the
+    // running-maximum kernel right behind it serves exactly those (its other workgroups exit at once)
+    p->variant = a.bound_dev ? BYA_ATTN_D64_DEVICE_BOUND_W4 : BYA_ATTN_D64_STATIC_BOUND_W4;
+    p->second_launch = a.bound_dev ? 1 : 0;
+    bya_attn_w4_plan w;
+    bya_plan_attn_w4(&a, ws_present, &w);
+    p->grid = w.grid; p->q_tile = w.q_tile; p->stream_k = w.stream_k; p->sk_rem = w.sk_rem; p->sk_cut = w.sk_cut;
+}
+
+template <int D>
+int launch_attn(const AttnArgs& a, hipStream_t s) {
+    bya_attn_plan_info pl;
+    attn_plan_of(a, D, -1, &pl);
+    const int nbh = a.nb1 * a.nb2 * a.heads;
+    dim3 grid((nbh * a.nqt + 7) / 8 * 8);          // the 128-row kernels' grid (pl.grid unless the hand-placed kernel runs first)
+    const size_t lds = (size_t)ATTN_RING * 2 * KV_TILE * D * 2;
+    switch (pl.variant) {
+        case BYA_ATTN_D64_DEVICE_BOUND_W4: {
+            const int rc = bya_launch_attn_w4(&a, s);
+            if (rc != BYA_OK) return rc;
+            AttnArgs b = a;
+            b.bound_dev = nullptr; b.score_bound = 0.f; b.only_flagged = a.fallback; b.fallback = nullptr;
+            BYA_LAUNCH(attn_fwd_kernel_d64_prescaled, grid, dim3(256), lds, s, b);
+            break;
+        }
+        case BYA_ATTN_D64_STATIC_BOUND_W4: return bya_launch_attn_w4(&a, s);
+        case BYA_ATTN_D64_PRESCALED: BYA_LAUNCH(attn_fwd_kernel_d64_prescaled, grid, dim3(256), lds, s, a); break;
+        case BYA_ATTN_D64_RUNNING_MAX: BYA_LAUNCH(attn_fwd_kernel_d64, grid, dim3(256), lds, s, a); break;
+        default: BYA_LAUNCH(attn_fwd_kernel_d128, grid, dim3(256), lds, s, a); break;
+    }
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+// bya_attn_kv_mix: argument checks and launch decisions in one place (launcher and bya_attn_kv_mix_plan).
+// qkv: the q, k, v addresses OR-ed together (0 in the query: it has none).
+int mix_plan_of(const void* z, const bya_attn_mix_desc* d, int has_af, uintptr_t qkv, bya_attn_kv_mix_plan_info* p) {
+    if (!z || !d) return BYA_ERR_SHAPE;
+    if (d->head_dim != 64 && d->head_dim != 128) return BYA_ERR_UNSUPPORTED;
+    if (d->heads <= 0 || d->n_id < 1 || d->n_id > 4 || d->n_grp <= 0 || d->Sq <= 0 || d->Skv <= 0 || d->Skv > KV_TILE) return BYA_ERR_SHAPE;
+    if (has_af && d->n_id < 2) return BYA_ERR_SHAPE;  // the audio mix (af . r) needs >= 2 streams; routing_weights_of has no 1-stream audio case
+    if ((d->q_grp | d->q_row | d->k_id | d->k_grp | d->k_row | d->v_id | d->v_grp | d->v_row) % 8) return BYA_ERR_ALIGN;
+    if ((d->z_grp | d->z_row) % 4) return BYA_ERR_ALIGN;
+    if (qkv & 15) return BYA_ERR_ALIGN;
+    if ((uintptr_t)z & 7) return BYA_ERR_ALIGN;
+    p->head_dim = d->head_dim;
+    if (d->Skv <= 32 && !bya_ref_form(BYA_REF_KV_MIX_GENERIC) && !((uintptr_t)z & 15) && (d->z_grp | d->z_row) % 8 == 0) {
+        // row chunks per (group, head): about three 32-row tiles per wave, and at least ~4 workgroups per CU in total
+        const int n32 = (d->Sq + 31) / 32;
+        const int nqc = (n32 + 11) / 12;
+        p->form = BYA_KV_MIX_MIX32;
+        p->row_chunks = nqc < 1 ? 1 : nqc;
+        p->lds_bytes = (d->n_id * 2 + 4) * 32 * d->head_dim * 2;    // K, V per identity + a z patch per wave
+        p->big_lds = p->lds_bytes > 64 * 1024;                      // four identities at head_dim 128: 96 KiB
+    } else {
+        p->form = BYA_KV_MIX_ONE_TILE;
+        p->row_chunks = (d->Sq + Q_PER_BLOCK - 1) / Q_PER_BLOCK;
+        p->lds_bytes = 2 * 2 * KV_TILE * d->head_dim * 2;
+        p->big_lds = 0;
+    }
+    p->grid = (int32_t)((long long)p->row_chunks * d->heads * d->n_grp);
+    return BYA_OK;
+}
+
+}  // namespace
+
+// Which kernel a descriptor selects (reported to the host so tests and bench.py can say which softmax variant ran).
+extern "C" int bya_attn_variant(const bya_attn_desc* d) {
+    if (!d) return BYA_ERR_SHAPE;
+    return attn_variant_of(d);
+}
+
+extern "C" int bya_attn_plan(const bya_attn_desc* d, const void* o, int32_t workspace_assumed, bya_attn_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    AttnArgs a;
+    const void* const aligned = reinterpret_cast<const void*>((uintptr_t)16);      // q, k, v stand-ins: the query has none
+    const int rc = attn_args_of(aligned, aligned, aligned, const_cast<void*>(o), d, a);
+    if (rc != BYA_OK) return rc;
+    attn_plan_of(a, d->head_dim, workspace_assumed, plan);
+    return BYA_OK;
+}
+
+extern "C" int bya_attn_fwd(const void* q, const void* k, const void* v, void* o, const bya_attn_desc* d,
+                            hipStream_t stream) {
+    AttnArgs a;
+    const int rc = attn_args_of(q, k, v, o, d, a);
+    if (rc != BYA_OK) return rc;
     return d->head_dim == 64 ? launch_attn<64>(a, stream) : launch_attn<128>(a, stream);
+}
+
+extern "C" int bya_attn_kv_mix_plan(const void* z, const void* af, const bya_attn_mix_desc* d, bya_attn_kv_mix_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_attn_kv_mix_plan_info p;
+    const int rc = mix_plan_of(z, d, af != nullptr, 0, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
 }
 
 extern "C" int bya_attn_kv_mix(const void* q, const void* k, const void* v, const void* r, const void* af, void* z, float* wsum,
                                const bya_attn_mix_desc* d, hipStream_t stream) {
     if (!q || !k || !v || !r || !z || !d) return BYA_ERR_SHAPE;
-    if (d->head_dim != 64 && d->head_dim != 128) return BYA_ERR_UNSUPPORTED;
-    if (d->heads <= 0 || d->n_id < 1 || d->n_id > 4 || d->n_grp <= 0 || d->Sq <= 0 || d->Skv <= 0 || d->Skv > KV_TILE) return BYA_ERR_SHAPE;
-    if (af && d->n_id < 2) return BYA_ERR_SHAPE;      // the audio mix (af . r) needs >= 2 streams; routing_weights_of has no 1-stream audio case
-    if ((d->q_grp | d->q_row | d->k_id | d->k_grp | d->k_row | d->v_id | d->v_grp | d->v_row) % 8) return BYA_ERR_ALIGN;
-    if ((d->z_grp | d->z_row) % 4) return BYA_ERR_ALIGN;
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return BYA_ERR_ALIGN;
-    if ((uintptr_t)z & 7) return BYA_ERR_ALIGN;
+    bya_attn_kv_mix_plan_info pl;
+    const int prc = mix_plan_of(z, d, af != nullptr, (uintptr_t)q | (uintptr_t)k | (uintptr_t)v, &pl);
+    if (prc != BYA_OK) return prc;
     MixArgs a;
     a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.z = (bf16_t*)z;
     a.r = (const bf16_t*)r; a.af = (const bf16_t*)af; a.wsum = wsum;
     a.heads = d->heads; a.n_id = d->n_id; a.n_grp = d->n_grp; a.Sq = d->Sq; a.Skv = d->Skv;
-    a.nqt = (d->Sq + Q_PER_BLOCK - 1) / Q_PER_BLOCK; a.mode = af ? 1 : 0;
+    a.nqt = pl.row_chunks; a.mode = af ? 1 : 0;
     a.q_grp = d->q_grp; a.q_row = d->q_row; a.k_id = d->k_id; a.k_grp = d->k_grp; a.k_row = d->k_row;
     a.v_id = d->v_id; a.v_grp = d->v_grp; a.v_row = d->v_row; a.z_grp = d->z_grp; a.z_row = d->z_row;
     a.scale_log2 = d->scale * 1.4426950408889634f;
-    if (d->Skv <= 32 && !bya_ref_form(BYA_REF_KV_MIX_GENERIC) && !((uintptr_t)z & 15) && (d->z_grp | d->z_row) % 8 == 0) {
-        // row chunks per (group, head): about three 32-row tiles per wave, and at least ~4 workgroups per CU in total
-        const int n32 = (d->Sq + 31) / 32;
-        int nqc = (n32 + 11) / 12;
-        a.nqt = nqc < 1 ? 1 : nqc;
-        const dim3 grid32((unsigned)((long long)a.nqt * a.heads * a.n_grp));
-        const size_t lds32 = (size_t)(a.n_id * 2 + 4) * 32 * d->head_dim * 2;    // K, V per identity + a z patch per wave
-        if (lds32 > 64 * 1024) {                                 // four identities at head_dim 128: 96 KiB
+    const dim3 grid((unsigned)pl.grid);
+    const size_t lds = (size_t)pl.lds_bytes;
+    if (pl.form == BYA_KV_MIX_MIX32) {
+        if (pl.big_lds) {
             static std::atomic<unsigned long long> big64{0}, big128{0};
             const int rc = d->head_dim == 64
                 ? bya_allow_big_lds(reinterpret_cast<const void*>(attn_kv_mix32_kernel_d64), 160 * 1024, big64)
                 : bya_allow_big_lds(reinterpret_cast<const void*>(attn_kv_mix32_kernel_d128), 160 * 1024, big128);
             if (rc != BYA_OK) return rc;
         }
-        if (d->head_dim == 64) BYA_LAUNCH(attn_kv_mix32_kernel_d64, grid32, dim3(256), lds32, stream, a);
-        else BYA_LAUNCH(attn_kv_mix32_kernel_d128, grid32, dim3(256), lds32, stream, a);
+        if (d->head_dim == 64) BYA_LAUNCH(attn_kv_mix32_kernel_d64, grid, dim3(256), lds, stream, a);
+        else BYA_LAUNCH(attn_kv_mix32_kernel_d128, grid, dim3(256), lds, stream, a);
         return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
     }
-    const dim3 grid((unsigned)((long long)a.nqt * a.heads * a.n_grp));
-    const size_t lds = (size_t)2 * 2 * KV_TILE * d->head_dim * 2;
     if (d->head_dim == 64) BYA_LAUNCH(attn_kv_mix_kernel_d64, grid, dim3(256), lds, stream, a);
     else BYA_LAUNCH(attn_kv_mix_kernel_d128, grid, dim3(256), lds, stream, a);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;

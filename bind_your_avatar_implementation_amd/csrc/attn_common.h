@@ -69,3 +69,7 @@ template <int D> __device__ __forceinline__ int vswz(int row) { return D == 64 ?
 // defined in attn_w4.hip: joint attention, head_dim 64, scores pre-scaled and bounded (one wave per SIMD, 512 query rows
 // per workgroup); called from bya_attn_fwd
 int bya_launch_attn_w4(const void* args, hipStream_t stream);
+// its launch decisions (the launcher calls this too): grid, rows per workgroup, whether the stream-K grid runs and where it
+// cuts.  ws_present: -1 = the current device's registered workspace decides, 0 / 1 = assume none / one (host-side queries)
+struct bya_attn_w4_plan { int grid, q_tile, stream_k, sk_rem, sk_cut; };
+void bya_plan_attn_w4(const void* args, int ws_present, bya_attn_w4_plan* plan);

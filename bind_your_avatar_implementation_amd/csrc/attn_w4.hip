@@ -501,15 +501,17 @@ extern "C" int bya_attn_workspace_status(int32_t* timeouts, hipStream_t stream) 
     return BYA_OK;
 }
 
-int bya_launch_attn_w4(const void* args, hipStream_t s) {
-    AttnArgs a = *static_cast<const AttnArgs*>(args);
-    a.nqt = (a.Sq + ROWS_PER_WG - 1) / ROWS_PER_WG;
+void bya_plan_attn_w4(const void* args, int ws_present, bya_attn_w4_plan* plan) {
+    const AttnArgs& a = *static_cast<const AttnArgs*>(args);
+    const int nqt = (a.Sq + ROWS_PER_WG - 1) / ROWS_PER_WG;
     const int nbh = a.nb1 * a.nb2 * a.heads;
-    const int dev = sk_device();
-    char* const ws = dev < 0 ? nullptr : static_cast<char*>(g_attn_ws[dev].load());
+    if (ws_present < 0) {
+        const int dev = sk_device();
+        ws_present = dev >= 0 && g_attn_ws[dev].load() != nullptr;
+    }
     const bool sk_on = bya_opt(BYA_OPT_ATTN_STREAMK) != 0;   // default on when a workspace exists
     const long long nt_all = (a.Skv + KV_TILE - 1) / KV_TILE;
-    const long long items = (long long)nbh * a.nqt;
+    const long long items = (long long)nbh * nqt;
     // stream-K pays when an XCD's items make at least one whole round of its 32 CUs plus a partial one.  Measured
     // (profiles/history/r4_r_attn_streamk_probe.json): +1 % at 48 heads x 17776 (6.56 rounds), +8.5 % at a 2-rank shard's 24 heads
     // (3.28 rounds), +2.7 % at 47026 tokens -- a fraction of what the round counts promise, and a grid that does not fill ONE
@@ -519,17 +521,37 @@ int bya_launch_attn_w4(const void* args, hipStream_t s) {
     // power budget to the busy ones as clock, and filling them buys little; below one round the hand-offs cost more.
     const long long ipx = items / 8;                            // per XCD, +- one item when 8 does not divide
     const long long rem = ipx % (SK_GRID / 8);
-    const bool sk = ws && sk_on && ipx >= SK_GRID / 8 && (items % SK_GRID != 0) && rem * nt_all >= 8 * (SK_GRID / 8) &&
+    const bool sk = ws_present && sk_on && ipx >= SK_GRID / 8 && (items % SK_GRID != 0) && rem * nt_all >= 8 * (SK_GRID / 8) &&
                     nt_all >= 16 && items * nt_all < (1LL << 31);
+    plan->q_tile = ROWS_PER_WG;
+    plan->stream_k = sk ? 1 : 0;
+    plan->grid = sk ? SK_GRID : (nbh * nqt + 7) / 8 * 8;
+    // what the kernel derives for XCD 0 (the others differ by one item when 8 does not divide the item count)
+    plan->sk_rem = 0; plan->sk_cut = 0;
     if (sk) {
+        const int ncu = SK_GRID / 8;
+        int ipx0 = (nbh >> 3) * nqt;
+        if (nbh % 8 != 0) ipx0 = (int)(items >> 3) + ((items & 7) ? 1 : 0);
+        plan->sk_rem = ipx0 % ncu;
+        plan->sk_cut = plan->sk_rem ? (int)((nt_all * plan->sk_rem + ncu - 1) / ncu) : (int)nt_all;
+    }
+}
+
+int bya_launch_attn_w4(const void* args, hipStream_t s) {
+    AttnArgs a = *static_cast<const AttnArgs*>(args);
+    a.nqt = (a.Sq + ROWS_PER_WG - 1) / ROWS_PER_WG;
+    const int dev = sk_device();
+    char* const ws = dev < 0 ? nullptr : static_cast<char*>(g_attn_ws[dev].load());
+    bya_attn_w4_plan pl;
+    bya_plan_attn_w4(args, ws != nullptr, &pl);
+    if (pl.stream_k) {
         a.sk_flags = reinterpret_cast<unsigned*>(ws);
         a.sk_part = reinterpret_cast<float*>(ws + SK_FLAG_BYTES);
-        BYA_LAUNCH(attn_joint_w4_kernel<true>, dim3(SK_GRID), dim3(256), (size_t)NST * STAGE_BYTES, s, a);
+        BYA_LAUNCH(attn_joint_w4_kernel<true>, dim3(pl.grid), dim3(256), (size_t)NST * STAGE_BYTES, s, a);
     } else {
         a.sk_flags = nullptr;
         a.sk_part = nullptr;
-        dim3 grid((nbh * a.nqt + 7) / 8 * 8);
-        BYA_LAUNCH(attn_joint_w4_kernel<false>, grid, dim3(256), (size_t)NST * STAGE_BYTES, s, a);
+        BYA_LAUNCH(attn_joint_w4_kernel<false>, dim3(pl.grid), dim3(256), (size_t)NST * STAGE_BYTES, s, a);
     }
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }

@@ -392,31 +392,53 @@ extern "C" int bya_router_head(const void* x, const void* w, const void* b, void
     return ok();
 }
 
-extern "C" int bya_attn_tiny(const void* q, const void* k, const void* v, void* o, int32_t L, int32_t heads,
-                             int64_t n_outer, int64_t n_inner, int64_t outer_stride, int64_t seq_stride,
-                             int64_t ld_qkv, int64_t ld_o, float scale, hipStream_t stream) {
+// bya_attn_tiny: argument checks and the choice among its eight kernel instances (launcher and bya_attn_tiny_plan).
+static int tiny_plan_of(const void* q, const void* k, const void* v, const void* o, int32_t L, int32_t heads, int64_t n_outer,
+                        int64_t n_inner, int64_t ld_qkv, int64_t ld_o, bya_attn_tiny_plan_info* p) {
     if (!q || !k || !v || !o || L <= 0 || L > 32 || heads <= 0 || n_outer <= 0 || n_inner <= 0) return BYA_ERR_SHAPE;
-#define TINY_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o
-#define TINY_TAIL (long long)n_outer, (long long)n_inner, (long long)outer_stride, (long long)seq_stride, \
-                  (long long)ld_qkv, (long long)ld_o, scale
     // fast path: the sequence lengths of the router (frames per clip: 13 at 49 frames, 25 at 97; identities: 2, 3)
     if (heads % 8 == 0 && (L == 2 || L == 3 || L == 13 || L == 25) && ld_qkv % 8 == 0 && ld_o % 8 == 0 &&
         !(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15)) {
-        const int hgroups = heads / 8;
-        const long long w8 = (long long)n_outer * n_inner * hgroups;
-        dim3 g8((unsigned)((w8 + 3) / 4));
-        if (L == 2) BYA_LAUNCH((attn_tiny8_kernel<2>), g8, dim3(256), 0, stream, TINY_ARGS, hgroups, TINY_TAIL);
-        else if (L == 3) BYA_LAUNCH((attn_tiny8_kernel<3>), g8, dim3(256), 0, stream, TINY_ARGS, hgroups, TINY_TAIL);
-        else if (L == 13) BYA_LAUNCH((attn_tiny8_kernel<13>), g8, dim3(256), 0, stream, TINY_ARGS, hgroups, TINY_TAIL);
-        else BYA_LAUNCH((attn_tiny8_kernel<25>), g8, dim3(256), 0, stream, TINY_ARGS, hgroups, TINY_TAIL);
-        return ok();
+        p->instance = L == 2 ? BYA_TINY8_2 : L == 3 ? BYA_TINY8_3 : L == 13 ? BYA_TINY8_13 : BYA_TINY8_25;
+        p->waves = (long long)n_outer * n_inner * (heads / 8);
+    } else {
+        p->instance = L <= 2 ? BYA_TINY_GENERIC_2 : L <= 4 ? BYA_TINY_GENERIC_4 : L <= 16 ? BYA_TINY_GENERIC_16 : BYA_TINY_GENERIC_32;
+        p->waves = (long long)n_outer * n_inner * heads;
     }
-    const long long waves = (long long)n_outer * n_inner * heads;
-    dim3 grid((unsigned)((waves + 3) / 4));
-    if (L <= 2) BYA_LAUNCH((attn_tiny_kernel<2>), grid, dim3(256), 0, stream, TINY_ARGS, L, heads, TINY_TAIL);
-    else if (L <= 4) BYA_LAUNCH((attn_tiny_kernel<4>), grid, dim3(256), 0, stream, TINY_ARGS, L, heads, TINY_TAIL);
-    else if (L <= 16) BYA_LAUNCH((attn_tiny_kernel<16>), grid, dim3(256), 0, stream, TINY_ARGS, L, heads, TINY_TAIL);
-    else BYA_LAUNCH((attn_tiny_kernel<32>), grid, dim3(256), 0, stream, TINY_ARGS, L, heads, TINY_TAIL);
+    p->grid = (int32_t)((p->waves + 3) / 4);
+    return BYA_OK;
+}
+
+extern "C" int bya_attn_tiny_plan(const void* q, const void* k, const void* v, const void* o, int32_t L, int32_t heads,
+                                  int64_t n_outer, int64_t n_inner, int64_t ld_qkv, int64_t ld_o, bya_attn_tiny_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_attn_tiny_plan_info p;
+    const int rc = tiny_plan_of(q, k, v, o, L, heads, n_outer, n_inner, ld_qkv, ld_o, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_attn_tiny(const void* q, const void* k, const void* v, void* o, int32_t L, int32_t heads,
+                             int64_t n_outer, int64_t n_inner, int64_t outer_stride, int64_t seq_stride,
+                             int64_t ld_qkv, int64_t ld_o, float scale, hipStream_t stream) {
+    bya_attn_tiny_plan_info pl;
+    const int rc = tiny_plan_of(q, k, v, o, L, heads, n_outer, n_inner, ld_qkv, ld_o, &pl);
+    if (rc != BYA_OK) return rc;
+#define TINY_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o
+#define TINY_TAIL (long long)n_outer, (long long)n_inner, (long long)outer_stride, (long long)seq_stride, \
+                  (long long)ld_qkv, (long long)ld_o, scale
+    const dim3 grid((unsigned)pl.grid);
+    const int hgroups = heads / 8;
+    switch (pl.instance) {
+        case BYA_TINY8_2: BYA_LAUNCH((attn_tiny8_kernel<2>), grid, dim3(256), 0, stream, TINY_ARGS, hgroups, TINY_TAIL); break;
+        case BYA_TINY8_3: BYA_LAUNCH((attn_tiny8_kernel<3>), grid, dim3(256), 0, stream, TINY_ARGS, hgroups, TINY_TAIL); break;
+        case BYA_TINY8_13: BYA_LAUNCH((attn_tiny8_kernel<13>), grid, dim3(256), 0, stream, TINY_ARGS, hgroups, TINY_TAIL); break;
+        case BYA_TINY8_25: BYA_LAUNCH((attn_tiny8_kernel<25>), grid, dim3(256), 0, stream, TINY_ARGS, hgroups, TINY_TAIL); break;
+        case BYA_TINY_GENERIC_2: BYA_LAUNCH((attn_tiny_kernel<2>), grid, dim3(256), 0, stream, TINY_ARGS, L, heads, TINY_TAIL); break;
+        case BYA_TINY_GENERIC_4: BYA_LAUNCH((attn_tiny_kernel<4>), grid, dim3(256), 0, stream, TINY_ARGS, L, heads, TINY_TAIL); break;
+        case BYA_TINY_GENERIC_16: BYA_LAUNCH((attn_tiny_kernel<16>), grid, dim3(256), 0, stream, TINY_ARGS, L, heads, TINY_TAIL); break;
+        default: BYA_LAUNCH((attn_tiny_kernel<32>), grid, dim3(256), 0, stream, TINY_ARGS, L, heads, TINY_TAIL); break;
+    }
 #undef TINY_ARGS
 #undef TINY_TAIL
     return ok();

@@ -788,13 +788,8 @@ ATTN_BOUND_LIMIT = 90.0          # BYA_ATTN_BOUND_LIMIT (include/bya.h): |score|
 ATTN_VARIANTS = {}
 
 
-def attention(q, k, v, out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides,
-              scale, tag="other", prescaled=False, score_bound=0.0, bound=None):
-    """Flash attention with explicit (level-1, level-2, row) element strides for q, k, v, out.
-    ``bound`` = (stats, bh0, flags): the data-dependent score bound -- ``stats`` fp32 [slots, 2, n] as written by
-    ``qknorm_rope(stats=...)``, this launch's (batch, head) index bh at column bh0 + bh, ``flags`` int32 [nb1 * nb2 * heads]
-    (scratch: which heads went to the running-maximum kernel)."""
-    lib = _hip.load()
+def _attn_desc(head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale, prescaled, score_bound,
+               bound, plan=False):
     d = AttnDesc()
     d.head_dim, d.heads, d.nb1, d.nb2, d.Sq, d.Skv = head_dim, heads, nb1, nb2, Sq, Skv
     d.q_s1, d.q_s2, d.q_row = q_strides
@@ -804,14 +799,86 @@ def attention(q, k, v, out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_
     d.scale = float(scale)
     d.scores_prescaled = int(prescaled)
     d.score_bound = float(score_bound)
-    for t in (q, k, v, out):
-        assert t.dtype == torch.bfloat16 and t.is_cuda
     if bound is not None:
         stats, bh0, flags = bound
         assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.dim() == 3 and stats.shape[1] == 2
         assert flags.dtype == torch.int32 and flags.is_contiguous() and flags.numel() >= nb1 * nb2 * heads
-        d.bound_dev, d.bound_slots, d.bound_heads, d.bound_bh0 = stats.data_ptr(), stats.shape[0], stats.shape[2], int(bh0)
-        d.fallback_flags = flags.data_ptr()
+        d.bound_dev, d.bound_slots, d.bound_heads, d.bound_bh0 = (_plan_p if plan else _p)(stats), stats.shape[0], stats.shape[2], int(bh0)
+        d.fallback_flags = (_plan_p if plan else _p)(flags)
+    return d
+
+
+# ---- what the attention launches run (bya_attn_plan & co.: host-side, launch nothing, meta tensors may stand for device tensors)
+KV_MIX_FORMS = _hip.KV_MIX_FORMS
+TINY_INSTANCES = _hip.TINY_INSTANCES
+
+
+def attention_plan(out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale,
+                   prescaled=False, score_bound=0.0, bound=None, workspace=None):
+    """What ``attention`` with the same arguments would run: {"variant" (``ATTN_VARIANT_NAMES``), "grid", "q_tile", "stream_k",
+    "sk_rem", "sk_cut", "o_wide", "second_launch"}.  ``workspace``: True / False = as if a stream-K workspace were / were not
+    registered; None = as the launch would find it (a device ``out`` registers the device's workspace like ``attention``
+    does; with a meta ``out``: none)."""
+    lib = _hip.load()
+    d = _attn_desc(head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale, prescaled,
+                   score_bound, bound, plan=True)
+    if workspace is None:
+        if out.is_cuda and prescaled and (score_bound > 0 or bound is not None) and out.device.index not in _ATTN_WS:
+            ensure_attn_workspace(out.device)
+        workspace = -1 if out.is_cuda else 0
+    p = _hip.AttnPlan()
+    check(lib.bya_attn_plan(ctypes.byref(d), _plan_p(out), int(workspace), ctypes.byref(p)), "bya_attn_plan")
+    assert p.variant == lib.bya_attn_variant(ctypes.byref(d))
+    return {"variant": ATTN_VARIANT_NAMES[p.variant], "grid": p.grid, "q_tile": p.q_tile, "stream_k": p.stream_k,
+            "sk_rem": p.sk_rem, "sk_cut": p.sk_cut, "o_wide": p.o_wide, "second_launch": p.second_launch}
+
+
+def attention_plan_key(plan):
+    """One name per distinct attention kernel path: variant, "+streamk", "/wide" or "/narrow" (the store width)."""
+    return plan["variant"] + ("+streamk" if plan["stream_k"] else "") + ("/wide" if plan["o_wide"] else "/narrow")
+
+
+def attn_kv_mix_plan(z, af=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale=1.0):
+    """What ``attn_kv_mix`` would run: {"form" (``KV_MIX_FORMS``), "head_dim", "grid", "row_chunks", "lds_bytes", "big_lds"}."""
+    lib = _hip.load()
+    d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale)
+    p = _hip.AttnMixPlan()
+    check(lib.bya_attn_kv_mix_plan(_plan_p(z), _plan_p(af), ctypes.byref(d), ctypes.byref(p)), "bya_attn_kv_mix_plan")
+    return {"form": KV_MIX_FORMS[p.form], "head_dim": p.head_dim, "grid": p.grid, "row_chunks": p.row_chunks,
+            "lds_bytes": p.lds_bytes, "big_lds": p.big_lds}
+
+
+def attn_tiny_plan(q, k, v, out, L, heads, n_outer, n_inner, ld_qkv, ld_o):
+    """Which of the eight ``attn_tiny`` kernel instances would run: {"instance" (``TINY_INSTANCES``), "grid", "waves"}."""
+    lib = _hip.load()
+    p, a = _hip.AttnTinyPlan(), _plan_p
+    check(lib.bya_attn_tiny_plan(a(q), a(k), a(v), a(out), L, heads, n_outer, n_inner, ld_qkv, ld_o, ctypes.byref(p)),
+          "bya_attn_tiny_plan")
+    return {"instance": TINY_INSTANCES[p.instance], "grid": p.grid, "waves": p.waves}
+
+
+def _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale):
+    d = AttnMixDesc()
+    d.head_dim, d.heads, d.n_id, d.n_grp, d.Sq, d.Skv = head_dim, heads, n_id, n_grp, Sq, Skv
+    d.q_grp, d.q_row = q_strides
+    d.k_id, d.k_grp, d.k_row = k_strides
+    d.v_id, d.v_grp, d.v_row = v_strides
+    d.z_grp, d.z_row = z_strides
+    d.scale = float(scale)
+    return d
+
+
+def attention(q, k, v, out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides,
+              scale, tag="other", prescaled=False, score_bound=0.0, bound=None):
+    """Flash attention with explicit (level-1, level-2, row) element strides for q, k, v, out.
+    ``bound`` = (stats, bh0, flags): the data-dependent score bound -- ``stats`` fp32 [slots, 2, n] as written by
+    ``qknorm_rope(stats=...)``, this launch's (batch, head) index bh at column bh0 + bh, ``flags`` int32 [nb1 * nb2 * heads]
+    (scratch: which heads went to the running-maximum kernel)."""
+    lib = _hip.load()
+    for t in (q, k, v, out):
+        assert t.dtype == torch.bfloat16 and t.is_cuda
+    d = _attn_desc(head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale, prescaled,
+                   score_bound, bound)
     if prescaled and (score_bound > 0 or bound is not None) and q.device.index not in _ATTN_WS:
         ensure_attn_workspace(q.device)
     var = ATTN_VARIANT_NAMES.get(lib.bya_attn_variant(ctypes.byref(d)), "rejected")
@@ -843,13 +910,7 @@ def attn_kv_mix(q, k, v, r, af, z, wsum=None, *, head_dim, heads, n_id, n_grp, S
     with the router's masked combine in its epilogue (bya_attn_kv_mix).  q_strides = (group, row), k / v_strides = (identity,
     group, row), z_strides = (group, row), in elements; r: bf16 [n_grp * Sq, n_id]; af: None (face) or bf16 [n_id, n_id]."""
     lib = _hip.load()
-    d = AttnMixDesc()
-    d.head_dim, d.heads, d.n_id, d.n_grp, d.Sq, d.Skv = head_dim, heads, n_id, n_grp, Sq, Skv
-    d.q_grp, d.q_row = q_strides
-    d.k_id, d.k_grp, d.k_row = k_strides
-    d.v_id, d.v_grp, d.v_row = v_strides
-    d.z_grp, d.z_row = z_strides
-    d.scale = float(scale)
+    d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale)
     for t in (q, k, v, z, r):
         assert t.dtype == torch.bfloat16 and t.is_cuda
     assert r.is_contiguous() and r.numel() == n_grp * Sq * n_id

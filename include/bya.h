@@ -364,6 +364,22 @@ int bya_attn_fwd(const void* q, const void* k, const void* v, void* o, const bya
 #define BYA_ATTN_D64_DEVICE_BOUND_W4 5  /* the same kernel under the data-dependent bound (bound_dev), per-head running-maximum fallback */
 int bya_attn_variant(const bya_attn_desc* desc);
 
+/* What a bya_attn_fwd launch runs (host-side query like bya_gemm_bf16_plan: launches nothing, needs no GPU; the launcher
+ * calls the same decision functions).  `o` is the output address of the launch (it decides the store width).
+ * workspace_assumed: 1 / 0 = answer as if a stream-K workspace were / were not registered, -1 = as the current device's
+ * registration stands.  Returns what bya_attn_fwd would return before launching; the plan is untouched on rejection. */
+typedef struct bya_attn_plan_info {
+    int32_t variant;        /* BYA_ATTN_*, equal to bya_attn_variant(desc) */
+    int32_t grid;           /* workgroups of the (first) launch */
+    int32_t q_tile;         /* query rows per workgroup: 128, or 512 on the hand-placed kernel */
+    int32_t stream_k;       /* 1: 256 persistent workgroups with the leftover items cut along the keys */
+    int32_t sk_rem;         /* stream_k: leftover items of XCD 0 after its whole rounds (mains) */
+    int32_t sk_cut;         /* stream_k: the mains take key tiles [0, sk_cut) of a leftover item, helpers the rest */
+    int32_t o_wide;         /* 1: the epilogue stores 16 bytes per lane, 0: 8 bytes */
+    int32_t second_launch;  /* 1: the running-maximum kernel follows for the flagged heads (device bound) */
+} bya_attn_plan_info;
+int bya_attn_plan(const bya_attn_desc* desc, const void* o, int32_t workspace_assumed, bya_attn_plan_info* plan);
+
 /* Optional stream-K workspace of the static-bound joint-attention kernel (BYA_ATTN_D64_STATIC_BOUND_W4): device memory
  * owned by the caller, 256-byte aligned, at least bya_attn_workspace_bytes (69 MB), ZERO-FILLED once; one per DEVICE, used
  * by launches enqueued under the current device, which must be ordered on one stream.  NULL unregisters.  With it, a
@@ -397,6 +413,18 @@ typedef struct bya_attn_mix_desc {
 } bya_attn_mix_desc;
 int bya_attn_kv_mix(const void* q, const void* k, const void* v, const void* r, const void* af, void* z, float* wsum,
                     const bya_attn_mix_desc* desc, hipStream_t stream);
+/* Which form a bya_attn_kv_mix launch with this z, af (NULL or not) and descriptor runs (host-side query). */
+#define BYA_KV_MIX_MIX32 0      /* <= 32 keys: K / V of every identity resident in LDS, one workgroup per (group, head, row chunk) */
+#define BYA_KV_MIX_ONE_TILE 1   /* one 128-row query tile per workgroup on a 64-key tile */
+typedef struct bya_attn_kv_mix_plan_info {
+    int32_t form;           /* BYA_KV_MIX_* */
+    int32_t head_dim;
+    int32_t grid;
+    int32_t row_chunks;     /* workgroups per (group, head) */
+    int32_t lds_bytes;
+    int32_t big_lds;        /* 1: more than 64 KiB of LDS, the launch opts in (four identities at head_dim 128) */
+} bya_attn_kv_mix_plan_info;
+int bya_attn_kv_mix_plan(const void* z, const void* af, const bya_attn_mix_desc* desc, bya_attn_kv_mix_plan_info* plan);
 
 /* Tiny-sequence self-attention (sequence length L <= 16, head_dim 64) used by the router's temporal
  * (L = frames) and multi-ID (L = ids) attentions (models/router.py:482,488).  Element e of sequence
@@ -405,6 +433,24 @@ int bya_attn_kv_mix(const void* q, const void* k, const void* v, const void* r, 
 int bya_attn_tiny(const void* q, const void* k, const void* v, void* o, int32_t L, int32_t heads,
                   int64_t n_outer, int64_t n_inner, int64_t outer_stride, int64_t seq_stride, int64_t ld_qkv,
                   int64_t ld_o, float scale, hipStream_t stream);
+/* Which of the eight kernel instances a bya_attn_tiny launch runs (host-side query): 8 heads per wave with the sequence in
+ * registers for L in {2, 3, 13, 25} when heads % 8 == 0 and pointers and row strides are 16-byte aligned, else one wave per
+ * (sequence, head) with L rounded up to 2 / 4 / 16 / 32. */
+#define BYA_TINY8_2 0
+#define BYA_TINY8_3 1
+#define BYA_TINY8_13 2
+#define BYA_TINY8_25 3
+#define BYA_TINY_GENERIC_2 4
+#define BYA_TINY_GENERIC_4 5
+#define BYA_TINY_GENERIC_16 6
+#define BYA_TINY_GENERIC_32 7
+typedef struct bya_attn_tiny_plan_info {
+    int32_t instance;       /* BYA_TINY* */
+    int32_t grid;           /* workgroups of 4 waves */
+    int64_t waves;          /* waves with work (the last workgroup may be partly idle) */
+} bya_attn_tiny_plan_info;
+int bya_attn_tiny_plan(const void* q, const void* k, const void* v, const void* o, int32_t L, int32_t heads, int64_t n_outer,
+                       int64_t n_inner, int64_t ld_qkv, int64_t ld_o, bya_attn_tiny_plan_info* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Embedding-Router specific kernels (models/router.py:364-411).

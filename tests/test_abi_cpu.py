@@ -24,7 +24,7 @@ def declared_symbols():
 def test_header_declares_the_documented_entry_points():
     syms = declared_symbols()
     for must in ["bya_gemm_bf16", "bya_gemm_bf16_plan", "bya_gemm_qkv_norm_rope_plan", "bya_gemm_fp8_plan", "bya_gemm_mx_plan",
-                 "bya_gemm_skinny_bf16", "bya_attn_fwd", "bya_layernorm", "bya_qknorm_rope", "bya_masked_combine",
+                 "bya_gemm_skinny_bf16", "bya_attn_fwd", "bya_attn_plan", "bya_attn_kv_mix_plan", "bya_attn_tiny_plan", "bya_layernorm", "bya_qknorm_rope", "bya_masked_combine",
                  "bya_router_scores", "bya_router_head", "bya_forcing_max_over_frames", "bya_patchify",
                  "bya_unpatchify", "bya_linear_small_m", "bya_timestep_features", "bya_attn_tiny", "bya_act_add",
                  "bya_abi_version"]:
@@ -76,6 +76,40 @@ def test_python_binding_table_matches_header(lib_path):
     assert lib.bya_attn_variant(ctypes.byref(a)) == 0
     a.head_dim = 128
     assert lib.bya_attn_variant(ctypes.byref(a)) == 3
+    # the attention plan queries validate like their entry points, fill the plan, and leave it alone on rejection
+    ap = _hip.AttnPlan(-9, -9)
+    a = _hip.AttnDesc()
+    assert lib.bya_attn_plan(None, base, 0, ctypes.byref(ap)) == -1 and lib.bya_attn_plan(ctypes.byref(a), base, 0, None) == -1
+    a.head_dim, a.heads, a.nb1, a.nb2, a.Sq, a.Skv = 64, 48, 1, 1, 17776, 17776
+    a.q_row = a.k_row = a.v_row = a.o_row = 48 * 64
+    a.scores_prescaled, a.score_bound = 1, 11.8
+    assert lib.bya_attn_plan(ctypes.byref(a), None, 0, ctypes.byref(ap)) == -1 and ap.variant == -9
+    assert lib.bya_attn_plan(ctypes.byref(a), base + 4, 0, ctypes.byref(ap)) == -2 and ap.variant == -9      # o not 8-byte aligned
+    assert lib.bya_attn_plan(ctypes.byref(a), base, 1, ctypes.byref(ap)) == 0
+    assert (ap.variant, ap.grid, ap.q_tile, ap.stream_k, ap.o_wide, ap.second_launch) == (4, 256, 512, 1, 1, 0)
+    assert ap.variant == lib.bya_attn_variant(ctypes.byref(a))
+    assert lib.bya_attn_plan(ctypes.byref(a), base + 8, 0, ctypes.byref(ap)) == 0 and (ap.grid, ap.stream_k, ap.o_wide) == (1680, 0, 0)
+    a.o_row = 48 * 64 + 2
+    assert lib.bya_attn_plan(ctypes.byref(a), base, 0, ctypes.byref(ap)) == -2                                 # o_row % 4
+    mp, md = _hip.AttnMixPlan(-9), _hip.AttnMixDesc()
+    assert lib.bya_attn_kv_mix_plan(None, None, ctypes.byref(md), ctypes.byref(mp)) == -1
+    assert lib.bya_attn_kv_mix_plan(base, None, ctypes.byref(md), None) == -1
+    md.head_dim, md.heads, md.n_id, md.n_grp, md.Sq, md.Skv = 64, 48, 2, 13, 1350, 32
+    md.q_row = md.k_row = md.v_row = md.z_row = 48 * 64
+    assert lib.bya_attn_kv_mix_plan(base + 4, None, ctypes.byref(md), ctypes.byref(mp)) == -2 and mp.form == -9
+    assert lib.bya_attn_kv_mix_plan(base, None, ctypes.byref(md), ctypes.byref(mp)) == 0 and (mp.form, mp.head_dim) == (0, 64)
+    assert lib.bya_attn_kv_mix_plan(base + 8, None, ctypes.byref(md), ctypes.byref(mp)) == 0 and mp.form == 1
+    md.n_id = 1
+    assert lib.bya_attn_kv_mix_plan(base, base, ctypes.byref(md), ctypes.byref(mp)) == -1                      # audio needs >= 2 streams
+    md.head_dim = 96
+    assert lib.bya_attn_kv_mix_plan(base, None, ctypes.byref(md), ctypes.byref(mp)) == -4
+    tp = _hip.AttnTinyPlan(-9)
+    assert lib.bya_attn_tiny_plan(None, base, base, base, 13, 8, 2, 90, 1536, 512, ctypes.byref(tp)) == -1 and tp.instance == -9
+    assert lib.bya_attn_tiny_plan(base, base, base, base, 13, 8, 2, 90, 1536, 512, None) == -1
+    assert lib.bya_attn_tiny_plan(base, base, base, base, 33, 8, 2, 90, 1536, 512, ctypes.byref(tp)) == -1
+    assert lib.bya_attn_tiny_plan(base, base, base, base, 13, 8, 2, 90, 1536, 512, ctypes.byref(tp)) == 0
+    assert (tp.instance, tp.grid, tp.waves) == (2, 45, 180)
+    assert lib.bya_attn_tiny_plan(base, base + 8, base, base, 13, 8, 2, 90, 1536, 512, ctypes.byref(tp)) == 0 and tp.instance == 6
     # the RCCL entry points validate their arguments before touching a communicator
     assert lib.bya_allgather_kv(None, None, None, None, 1, 1, None, None) == -1
     cnt = (ctypes.c_int64 * 2)(1, 1)
@@ -86,7 +120,9 @@ def test_struct_layout_matches_header():
     """ctypes mirrors of bya_gemm_desc / bya_attn_desc / bya_gemm_plan: field order and sizes as in the header."""
     from bind_your_avatar_implementation_amd import _hip
     src = open(os.path.join(ROOT, "include", "bya.h")).read()
-    for cname, cls in (("bya_gemm_desc", _hip.GemmDesc), ("bya_attn_desc", _hip.AttnDesc), ("bya_gemm_plan", _hip.GemmPlan)):
+    for cname, cls in (("bya_gemm_desc", _hip.GemmDesc), ("bya_attn_desc", _hip.AttnDesc), ("bya_gemm_plan", _hip.GemmPlan),
+                       ("bya_attn_plan_info", _hip.AttnPlan), ("bya_attn_kv_mix_plan_info", _hip.AttnMixPlan),
+                       ("bya_attn_tiny_plan_info", _hip.AttnTinyPlan)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), src, flags=re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         fields = []
