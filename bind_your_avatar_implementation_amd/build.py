@@ -29,6 +29,17 @@ def _hipcc():
     raise RuntimeError("hipcc not found (set HIPCC or install ROCm)")
 
 
+def compile_flags(src):
+    """hipcc flags of one translation unit (tools/isa_fingerprint.py compiles with the same)."""
+    # -amdgpu-mfma-vgpr-form: MFMA results stay in arch VGPRs (gfx950's register file is unified), which removes
+    # the v_accvgpr_read/write traffic hipcc otherwise inserts wherever VALU code touches an accumulator.
+    form = [] if src in AGPR_SOURCES else ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
+    if src in NO_SLP_SOURCES:
+        form = form + ["-fno-slp-vectorize"]
+    # -fvisibility=hidden: the dynamic symbol table is include/bya.h (which pushes default visibility around its declarations)
+    return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", *form]
+
+
 def needs_build():
     if not os.path.exists(LIB_PATH):
         return True
@@ -48,13 +59,7 @@ def build_hip_library(force=False, verbose=True):
     procs = []
     for src in SOURCES:
         obj = os.path.join(build_dir, src.replace(".hip", ".o"))
-        # -amdgpu-mfma-vgpr-form: MFMA results stay in arch VGPRs (gfx950's register file is unified), which removes
-        # the v_accvgpr_read/write traffic hipcc otherwise inserts wherever VALU code touches an accumulator.
-        form = [] if src in AGPR_SOURCES else ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
-        if src in NO_SLP_SOURCES:
-            form = form + ["-fno-slp-vectorize"]
-        # -fvisibility=hidden: the dynamic symbol table is include/bya.h (which pushes default visibility around its declarations)
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", *form, "-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc, *compile_flags(src), "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

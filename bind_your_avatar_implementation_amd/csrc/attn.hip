@@ -14,6 +14,7 @@
 // and the S^T accumulator is directly the B operand of O^T += V^T.P^T (no LDS round trip for P).
 // Blocks of one (batch, head) are dealt to one XCD so its K/V stream is served by that XCD's L2.
 #include "attn_common.h"
+#include "gemm_persistent.h"      // xcd_range
 #include "routing_weights.h"
 #include <stdlib.h>
 #include "options.h"
@@ -251,11 +252,10 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& p, char* smem) {
         qt = j % p.nqt;
     } else {
         const int total = nbh * p.nqt, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        const int cq = total >> 3, cr = total & 7;
-        const int base = xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-        if (j >= cq + (xcd < cr ? 1 : 0)) return;
-        bh = (base + j) / p.nqt;
-        qt = (base + j) % p.nqt;
+        const XcdRange xr = xcd_range(total, xcd);
+        if (j >= xr.end - xr.base) return;
+        bh = (xr.base + j) / p.nqt;
+        qt = (xr.base + j) % p.nqt;
     }
     if (bh >= nbh) return;
     if (p.only_flagged && !p.only_flagged[bh]) return;       // second pass of the device-bound form: flagged heads only

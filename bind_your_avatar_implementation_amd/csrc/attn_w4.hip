@@ -26,31 +26,13 @@
 // from the q/k-LayerNorm biases, is within the +-90 the softmax promises to handle.)
 // Built WITHOUT -amdgpu-mfma-vgpr-form (O accumulators and the Q fragments live in AGPRs).
 #include "attn_common.h"
+#include "gemm_persistent.h"      // raw_rsrc, dma_piece, xcd_range
 #include <stdlib.h>
 #include "options.h"
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 template <char C> struct IntTagC { static constexpr char value = C; };
-
-__device__ __forceinline__ i32x4 raw_rsrc(const void* base, uint32_t bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffu));
-    r.y = __builtin_amdgcn_readfirstlane((int)((b >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-// one 1-KiB LDS-DMA piece: 64 lanes x 16 bytes from per-lane global offsets to LDS [m0 .. m0 + 1024)
-__device__ __forceinline__ void dma_piece(uint32_t lds_dst, uint32_t voff, const i32x4& rsrc, uint32_t soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :
-                 : "s"(lds_dst), "v"(voff), "s"(rsrc), "s"(soff)
-                 : "memory");
-}
 
 constexpr int QB = 4;                                   // 32-row query blocks per wave
 constexpr int ROWS_PER_WG = 4 * QB * 32;                // 512
@@ -100,9 +82,9 @@ __global__ __launch_bounds__(256, 1) void attn_joint_w4_kernel(AttnArgs p) {
         // (head, q-tile) order -- the same two rules as the one-workgroup-per-item launch below
         int ipx = (nbh >> 3) * p.nqt;
         if (nbh % 8 != 0) {
-            const int total = nbh * p.nqt, cq = total >> 3, cr = total & 7;
-            sk_base = sk_xcd < cr ? sk_xcd * (cq + 1) : cr * (cq + 1) + (sk_xcd - cr) * cq;
-            ipx = cq + (sk_xcd < cr ? 1 : 0);
+            const XcdRange xr = xcd_range(nbh * p.nqt, sk_xcd);
+            sk_base = xr.base;
+            ipx = xr.end - xr.base;
         }
         sk_rfull = ipx / sk_ncu;
         sk_rem = ipx - sk_rfull * sk_ncu;                          // leftover items: mains 0 .. rem-1, helpers rem .. ncu-1
@@ -123,11 +105,10 @@ __global__ __launch_bounds__(256, 1) void attn_joint_w4_kernel(AttnArgs p) {
             it.qt = j % p.nqt;
         } else {
             const int total = nbh * p.nqt, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-            const int cq = total >> 3, cr = total & 7;
-            const int base = xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-            if (j >= cq + (xcd < cr ? 1 : 0)) return;
-            it.bh = (base + j) / p.nqt;
-            it.qt = (base + j) % p.nqt;
+            const XcdRange xr = xcd_range(total, xcd);
+            if (j >= xr.end - xr.base) return;
+            it.bh = (xr.base + j) / p.nqt;
+            it.qt = (xr.base + j) % p.nqt;
         }
         if (it.bh >= nbh) return;
         it.tb = 0; it.nt = nt_all; it.nt_all = nt_all; it.role = 0; it.local = 0;

@@ -177,8 +177,10 @@ __device__ __forceinline__ void epilogue_block(const GemmArgs& p, int z, int m_b
     }
 }
 
-template <int OFF>
-__device__ __forceinline__ void ds_read128(bf16x8& dst, uint32_t addr) {
+// 16 bytes of LDS into a 16-byte register tuple (bf16x8 fragments, the i32x4 halves of an e4m3 fragment)
+template <int OFF, typename T>
+__device__ __forceinline__ void ds_read128(T& dst, uint32_t addr) {
+    static_assert(sizeof(T) == 16, "one ds_read_b128");
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
 }
 

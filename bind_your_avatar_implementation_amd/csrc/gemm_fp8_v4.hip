@@ -32,7 +32,7 @@
 //
 // Inline-asm MFMAs are invisible to hipcc (gemm_v4.hip explains): every fragment is kept allocated to the end of the K-tile,
 // the epilogue starts behind explicit s_nops, and this unit is compiled WITHOUT -amdgpu-mfma-vgpr-form (accumulators in AGPRs).
-#include "gemm_common.h"
+#include "gemm_persistent.h"
 
 #ifndef BYA_F8_PLACE
 #define BYA_F8_PLACE 9      // placement of the 16 LDS-DMA pieces inside a K-tile (tools/gen_gemm_fp8_schedule.py holds the tables)
@@ -43,36 +43,9 @@
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BK8 = 128;          // e4m3 elements (= bytes) per K-tile
-
-__device__ __forceinline__ i32x4 raw_rsrc(const void* base, uint32_t bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffu));
-    r.y = __builtin_amdgcn_readfirstlane((int)((b >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-// one 1-KiB LDS-DMA piece: 64 lanes x 16 bytes from per-lane global offsets to LDS [m0 .. m0 + 1024)
-template <int LDS_OFF>
-__device__ __forceinline__ void dma_piece(uint32_t lds_base, uint32_t voff, const i32x4& rsrc, uint32_t soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :
-                 : "s"(lds_base + LDS_OFF), "v"(voff), "s"(rsrc), "s"(soff)
-                 : "memory");
-}
-
-template <int OFF>
-__device__ __forceinline__ void ds_read16(i32x4& dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
-}
-
-struct Tile8 { int z, m0, n0; bool valid; };
 
 // Wide epilogue of one wave (gemm_v4.hip's, plus the two scale vectors).  The lane (fr = lane & 15, fq = lane >> 4) holds,
 // for row block j and accumulator register e, the EIGHT consecutive columns  n8 = n_wave + (4 e + fq) * 8 + i,  i = 0..7
@@ -171,71 +144,36 @@ __global__ __launch_bounds__(256, 1) void gemm256p_fp8_kernel(GemmArgs p, const 
     const int wm = wave >> 1, wn = wave & 1;
     const int fr = lane & 15, fq = lane >> 4;
 
-    // ---- this workgroup's output tiles: XCD x (= blockIdx % 8 under round-robin dispatch; speed only) owns a contiguous
-    // range of the tile order, its workgroups take every (gridDim / 8)-th tile of it, round after round
-    const int per_z = tiles_m * tiles_n, total = per_z * batch;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int cq = total >> 3, cr = total & 7;
-    const int base = (xcd < cr) ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-    const int end = base + cq + (xcd < cr ? 1 : 0);
-    auto coord = [&](int seq) {
-        Tile8 c;
-        const int id = base + slot + seq * slots;
-        c.valid = id < end;
-        const int idz = c.valid ? id : base;
-        c.z = idz / per_z;
-        const int idt = idz - c.z * per_z;
-        const int per_group = GM * tiles_n;          // group-M order: GM row tiles sweep a column tile before moving on
-        const int group = idt / per_group, first_m = group * GM;
-        const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-        const int in_g = idt - group * per_group;
-        c.m0 = (first_m + in_g % gsz) * BM;
-        c.n0 = (in_g / gsz) * BN;
-        return c;
-    };
+    const TileWalk<BM, BN> walk(tiles_m, tiles_n, batch, GM);
     int seq = 0;
-    Tile8 cur = coord(seq);
+    PersistentTile cur = walk.coord(seq);
     if (!cur.valid) return;
 
-    // fragment read addresses (XOR swizzle on (row >> 1) & 7; row blocks are 16 rows = 2048 bytes apart): the 16-byte chunks
+    // fragment read addresses (the LDS image: gemm_persistent.h): the 16-byte chunks
     // fq and 4 + fq of a row -- bytes 16 fq .. and 64 + 16 fq .. -- are the low and the high half of a lane's 32 operand bytes
     const int a_row = wm * 128 + fr, w_row = wn * 128 + fr;
-    const int a_sw = (a_row >> 1) & 7, w_sw = (w_row >> 1) & 7;
     const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
     // (c*: the stage of the current K-tile, n*: the other one)
-    uint32_t cAl = lds0 + a_row * 128 + ((fq ^ a_sw) << 4), cAh = lds0 + a_row * 128 + (((4 + fq) ^ a_sw) << 4);
-    uint32_t cWl = lds0 + TILE_A + w_row * 128 + ((fq ^ w_sw) << 4);
-    uint32_t cWh = lds0 + TILE_A + w_row * 128 + (((4 + fq) ^ w_sw) << 4);
+    uint32_t cAl = frag_addr(lds0, a_row, fq), cAh = frag_addr(lds0, a_row, 4 + fq);
+    uint32_t cWl = frag_addr(lds0 + TILE_A, w_row, fq);
+    uint32_t cWh = frag_addr(lds0 + TILE_A, w_row, 4 + fq);
     uint32_t fill = __builtin_amdgcn_readfirstlane(lds0 + wave * 64 * 128);     // this wave's first A piece, current stage
 
-    // staging (gemm_v4.hip): wave w moves LDS slot rows [64w, 64w + 64) of the A tile and of the W tile, 8 one-KiB pieces each.
-    // A slot rows are tile rows; W slot row s = 128 h + 16 i + r holds tile column 128 h + ((r & 3) * 4 + (r >> 2)) * 8 + i.
+    // staging (map and source-side swizzle: gemm_persistent.h): wave w moves LDS slot rows [64w, 64w + 64) of the A tile and
+    // of the W tile, 8 one-KiB pieces each
     uint32_t voA[8], voW[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int rl = wave * 64 + q * 8 + (lane >> 3);
-        const int r = rl & 15, i = (rl >> 4) & 7;
-        const int wcol = (rl & 128) + (((r & 3) << 2) | (r >> 2)) * 8 + i;
-        const int chunk16 = ((lane & 7) ^ ((rl >> 1) & 7)) * 16;
-        voA[q] = (uint32_t)rl * (uint32_t)p.lda + chunk16;
-        voW[q] = (uint32_t)wcol * (uint32_t)p.ldw + chunk16;
+        voA[q] = stage_off(lane, rl, rl, (uint32_t)p.lda);
+        voW[q] = stage_off(lane, rl, w_slot_col(rl), (uint32_t)p.ldw);
     }
     const uint8_t* const A8 = reinterpret_cast<const uint8_t*>(p.A);
     const uint8_t* const W8 = reinterpret_cast<const uint8_t*>(p.W);
-    auto a_rsrc = [&](const Tile8& c) {
-        const long long left = (long long)(p.M - 1 - c.m0) * p.lda + p.K;
-        return raw_rsrc(A8 + (long long)c.z * p.a_bs + (long long)c.m0 * p.lda, c.valid && left > 0 ? (uint32_t)left : 0u);
-    };
-    auto w_rsrc = [&](const Tile8& c) {
-        const long long left = (long long)(p.N - 1 - c.n0) * p.ldw + p.K;
-        return raw_rsrc(W8 + (long long)c.n0 * p.ldw, c.valid && left > 0 ? (uint32_t)left : 0u);
-    };
-    i32x4 rsA = a_rsrc(cur), rsW = w_rsrc(cur);
+    i32x4 rsA = tile_rsrc_a(p, A8, cur), rsW = tile_rsrc_w(p, W8, cur);
 
-#define DMA_A(Q, BASE, VO, RS, SOFF) dma_piece<(Q) * 1024>(BASE, VO[Q], RS, SOFF)
-#define DMA_W(Q, BASE, VO, RS, SOFF) dma_piece<TILE_A + (Q) * 1024>(BASE, VO[Q], RS, SOFF)
-#define ALL8(M, ...) M(0, __VA_ARGS__); M(1, __VA_ARGS__); M(2, __VA_ARGS__); M(3, __VA_ARGS__); \
-                     M(4, __VA_ARGS__); M(5, __VA_ARGS__); M(6, __VA_ARGS__); M(7, __VA_ARGS__)
+#define DMA_A(Q, BASE, VO, RS, SOFF) DMA_PIECE(Q, BASE, VO, RS, SOFF)
+#define DMA_W(Q, BASE, VO, RS, SOFF) DMA_PIECE(Q, (BASE) + TILE_A, VO, RS, SOFF)
     // ---- prologue of the FIRST tile only: K-tiles 0 and 1
     ALL8(DMA_A, fill, voA, rsA, 0u);
     ALL8(DMA_W, fill, voW, rsW, 0u);
@@ -250,15 +188,15 @@ __global__ __launch_bounds__(256, 1) void gemm256p_fp8_kernel(GemmArgs p, const 
         // ---- K-tile 0 of this output tile has landed for this wave (prologue wait / the wait in front of the previous
         // epilogue); make that true for everybody, then fetch its A fragments and W(0..3)
         asm volatile("s_barrier" ::: "memory");
-#define RAF(J, LO, HI) do { ds_read16<(J) * 2048>(al[J], LO); ds_read16<(J) * 2048>(ah[J], HI); } while (0)
-#define RWF(I, LO, HI) do { ds_read16<(I) * 2048>(wl[I], LO); ds_read16<(I) * 2048>(wh[I], HI); } while (0)
+#define RAF(J, LO, HI) do { ds_read128<(J) * 2048>(al[J], LO); ds_read128<(J) * 2048>(ah[J], HI); } while (0)
+#define RWF(I, LO, HI) do { ds_read128<(I) * 2048>(wl[I], LO); ds_read128<(I) * 2048>(wh[I], HI); } while (0)
         RAF(0, cAl, cAh); RAF(1, cAl, cAh); RAF(2, cAl, cAh); RAF(3, cAl, cAh);
         RAF(4, cAl, cAh); RAF(5, cAl, cAh); RAF(6, cAl, cAh); RAF(7, cAl, cAh);
         RWF(0, cWl, cWh); RWF(1, cWl, cWh); RWF(2, cWl, cWh); RWF(3, cWl, cWh);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
-        const Tile8 nxt = coord(seq + 1);
-        const i32x4 rsAn = a_rsrc(nxt), rsWn = w_rsrc(nxt);
+        const PersistentTile nxt = walk.coord(seq + 1);
+        const i32x4 rsAn = tile_rsrc_a(p, A8, nxt), rsWn = tile_rsrc_w(p, W8, nxt);
 
         // One K-tile, variant V (see the top); t = its index inside the output tile.
         auto ktile = [&](int t, auto v_c) {
@@ -763,9 +701,7 @@ __global__ __launch_bounds__(256, 1) void gemm256p_fp8_kernel(GemmArgs p, const 
             // covered by that K-tile's wait in front of B1)
             if constexpr (V != 'D') asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
             cAl ^= STAGE; cAh ^= STAGE; cWl ^= STAGE; cWh ^= STAGE; fill ^= STAGE;
-#define KEEP8(F) asm volatile("" :: "v"(F[0]), "v"(F[1]), "v"(F[2]), "v"(F[3]), "v"(F[4]), "v"(F[5]), "v"(F[6]), "v"(F[7]))
             KEEP8(al); KEEP8(ah); KEEP8(wl); KEEP8(wh);
-#undef KEEP8
 #undef PIECE
 #undef MF8
 #undef OPA
@@ -810,11 +746,7 @@ bool bya_gemm256p_fp8_eligible(const void* args) {
 int bya_launch_gemm256p_fp8(const void* args, const float* sa, const float* sw, int batch, int gm, hipStream_t s) {
     const GemmArgs& a = *static_cast<const GemmArgs*>(args);
     const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
-    const long long total = (long long)tiles_m * tiles_n * batch;
-    const int blocks = (int)(total < 256 ? (total + 7) / 8 * 8 : 256);
     const size_t lds = 2 * 512 * BK8;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (bya_allow_big_lds(reinterpret_cast<const void*>(gemm256p_fp8_kernel), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-    BYA_LAUNCH(gemm256p_fp8_kernel, dim3(blocks), dim3(256), lds, s, a, sa, sw, tiles_m, tiles_n, batch, gm < 1 ? 1 : gm);
-    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+    return launch_persistent<gemm256p_fp8_kernel>(persistent_grid((long long)tiles_m * tiles_n * batch), 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch,
+                                                  gm < 1 ? 1 : gm);
 }

@@ -11,8 +11,8 @@
 //    K-tile 0 during the last-but-one K-tile (its stage is free after that K-tile's barrier 3), K-tile 1 during the last
 //    K-tile -- so they have landed when the epilogue ends and the next K-loop starts with its fragment reads.
 //  * NO ACCUMULATOR ZEROING: the first K-tile's first k-step issues its MFMAs with C = 0.
-//  * 16-BYTE EPILOGUE ACCESSES: the W rows of a wave's 128-column span are staged in a permuted order (LDS slot (i, r)
-//    holds column ((r & 3) * 4 + (r >> 2)) * 8 + i), which makes a lane's eight accumulator tiles i = 0..7 hold EIGHT
+//  * 16-BYTE EPILOGUE ACCESSES: the W rows of a wave's 128-column span are staged in a permuted order (gemm_persistent.h
+//    has the LDS image), which makes a lane's eight accumulator tiles i = 0..7 hold EIGHT
 //    CONSECUTIVE output columns: bias / gate / residual are read and C is written 16 bytes per lane, 64 contiguous
 //    bytes per row and instruction -- half the memory instructions of the 8-byte epilogue, all requested in bursts
 //    (gemm_common.h explains why that matters: one serialized round trip per access otherwise).
@@ -83,6 +83,7 @@ __global__ __launch_bounds__(256, 1) void gemm256p_kernel(GemmArgs p, int tiles_
     // range of the tile order, its workgroups take every (gridDim / 8)-th tile of it, round after round
     const int per_z = tiles_m * tiles_n, total = per_z * batch;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
+    // (xcd_range of gemm_persistent.h, spelled out: through the call hipcc moves a wait in the QKN instance's scalar prologue)
     const int cq = total >> 3, cr = total & 7;
     const int base = (xcd < cr) ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
     const int end = base + cq + (xcd < cr ? 1 : 0);
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256, 1) void gemm256p_kernel(GemmArgs p, int tiles_
     TileCoord cur = coord(seq);
     if (!cur.valid) return;
 
-    // fragment read addresses (XOR swizzle on (row >> 1) & 7; row blocks are 16 rows = 2048 bytes apart)
+    // fragment read addresses (the LDS image: gemm_persistent.h)
     const int a_row = wm * 128 + fr, w_row = wn * 128 + fr;
     const int a_sw = (a_row >> 1) & 7, w_sw = (w_row >> 1) & 7;
     const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
@@ -154,19 +155,14 @@ __global__ __launch_bounds__(256, 1) void gemm256p_kernel(GemmArgs p, int tiles_
     uint32_t cW1 = lds0 + TILE_A + w_row * 128 + (((4 + fq) ^ w_sw) << 4);
     uint32_t fill = __builtin_amdgcn_readfirstlane(lds0 + wave * 64 * 128);     // this wave's first A piece, current stage
 
-    // staging: wave w moves LDS slot rows [64w, 64w + 64) of the A tile and of the W tile, 8 one-KiB pieces (8 rows) each.
-    // A slot rows are tile rows; W slot row s = 128 h + 16 i + r holds tile column 128 h + ((r & 3) * 4 + (r >> 2)) * 8 + i
-    // (see the top).  The lane loads the source chunk that belongs at its linear LDS position (source-side XOR swizzle).
-    // The per-lane byte offsets are relative to the TILE origin and never change; the tile origin lives in the buffer
-    // descriptor (base advanced to the tile's first row, size = what is left of the matrix), so rows past M / N fall
-    // outside the descriptor and arrive as zeros, and an invalid (past-the-end) tile gets an empty descriptor.
+    // staging (map, source-side swizzle and descriptors: gemm_persistent.h): wave w moves LDS slot rows [64w, 64w + 64) of the A
+    // tile and of the W tile, 8 one-KiB pieces (8 rows) each
     uint32_t voA[8], voW[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int rl = wave * 64 + q * 8 + (lane >> 3);
-        const int r = rl & 15, i = (rl >> 4) & 7;
-        const int wcol = (rl & 128) + (((r & 3) << 2) | (r >> 2)) * 8 + i;
-        const int chunk16 = ((lane & 7) ^ ((rl >> 1) & 7)) * 16;
+        const int wcol = w_slot_col(rl);
+        const int chunk16 = ((lane & 7) ^ ((rl >> 1) & 7)) * 16;      // (stage_off, spelled out: through the call hipcc moves epilogue padding)
         voA[q] = (uint32_t)rl * (uint32_t)(p.lda * 2) + chunk16;
         voW[q] = (uint32_t)wcol * (uint32_t)(p.ldw * 2) + chunk16;
     }
@@ -183,10 +179,8 @@ __global__ __launch_bounds__(256, 1) void gemm256p_kernel(GemmArgs p, int tiles_
     };
     i32x4 rsA = a_rsrc(cur), rsW = w_rsrc(cur);
 
-#define DMA_A(Q, BASE, VO, RS, SOFF) dma_piece<(Q) * 1024>(BASE, VO[Q], RS, SOFF)
-#define DMA_W(Q, BASE, VO, RS, SOFF) dma_piece<TILE_A + (Q) * 1024>(BASE, VO[Q], RS, SOFF)
-#define ALL8(M, ...) M(0, __VA_ARGS__); M(1, __VA_ARGS__); M(2, __VA_ARGS__); M(3, __VA_ARGS__); \
-                     M(4, __VA_ARGS__); M(5, __VA_ARGS__); M(6, __VA_ARGS__); M(7, __VA_ARGS__)
+#define DMA_A(Q, BASE, VO, RS, SOFF) DMA_PIECE(Q, BASE, VO, RS, SOFF)
+#define DMA_W(Q, BASE, VO, RS, SOFF) DMA_PIECE(Q, (BASE) + TILE_A, VO, RS, SOFF)
     // ---- prologue of the FIRST tile only: K-tiles 0 and 1
     ALL8(DMA_A, fill, voA, rsA, 0u);
     ALL8(DMA_W, fill, voW, rsW, 0u);
@@ -771,10 +765,7 @@ __global__ __launch_bounds__(256, 1) void gemm256p_kernel(GemmArgs p, int tiles_
             MF(1, 7, 7);  FLIP0(); FLIP1();
         }
             // GENERATED-END
-#define KEEP8(F, S) asm volatile("" :: "v"(F[S][0]), "v"(F[S][1]), "v"(F[S][2]), "v"(F[S][3]), "v"(F[S][4]), \
-                                      "v"(F[S][5]), "v"(F[S][6]), "v"(F[S][7]))
-            KEEP8(fa, 0); KEEP8(fw, 0); KEEP8(fa, 1); KEEP8(fw, 1);
-#undef KEEP8
+            KEEP8(fa[0]); KEEP8(fw[0]); KEEP8(fa[1]); KEEP8(fw[1]);
 #undef MF
 #undef MFZ
 #undef DA
@@ -937,13 +928,8 @@ __global__ __launch_bounds__(256, 1) void gemm256p_kernel(GemmArgs p, int tiles_
 int bya_launch_conv256p(const void* args, hipStream_t s) {
     const GemmArgs& a = *static_cast<const GemmArgs*>(args);
     const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
-    const long long total = (long long)tiles_m * tiles_n;
-    const int blocks = (int)(total < 256 ? (total + 7) / 8 * 8 : 256);
     const size_t lds = 2 * 512 * BK * 2;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (bya_allow_big_lds(reinterpret_cast<const void*>(gemm256p_kernel<false, true>), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-    BYA_LAUNCH((gemm256p_kernel<false, true>), dim3(blocks), dim3(256), lds, s, a, tiles_m, tiles_n, 1, 0, 1 << 30, 0u);
-    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+    return launch_persistent<gemm256p_kernel<false, true>>(persistent_grid((long long)tiles_m * tiles_n), 256, lds, s, a, tiles_m, tiles_n, 1, 0, 1 << 30, 0u);
 }
 
 // q|k|v projection with the q/k-norm + RoPE epilogue (bya_gemm_qkv_norm_rope): the QKN instance, never split
@@ -951,13 +937,9 @@ int bya_launch_gemm256p_qkn(const void* args, int batch, hipStream_t s) {
     GemmArgs a = *static_cast<const GemmArgs*>(args);
     a.gm = gemm_group_m(a);
     const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
-    const long long total = (long long)tiles_m * tiles_n * batch;
-    const int blocks = (int)(total < 256 ? (total + 7) / 8 * 8 : 256);
     const size_t lds = 2 * 512 * BK * 2;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (bya_allow_big_lds(reinterpret_cast<const void*>(gemm256p_kernel<false, false, true>), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-    BYA_LAUNCH((gemm256p_kernel<false, false, true>), dim3(blocks), dim3(256), lds, s, a, tiles_m, tiles_n, batch, 0, 1 << 30, 0u);
-    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+    return launch_persistent<gemm256p_kernel<false, false, true>>(persistent_grid((long long)tiles_m * tiles_n * batch), 256, lds, s, a, tiles_m, tiles_n,
+                                                                  batch, 0, 1 << 30, 0u);
 }
 
 int bya_gemm_split_min_ktiles() {
@@ -983,20 +965,13 @@ int bya_launch_gemm256p(const void* args, int batch, hipStream_t s) {
     const long long total = (long long)tiles_m * tiles_n * batch;
     const int min_seg = bya_gemm_split_min_ktiles();
     const int split = bya_gemm256p_split(args, batch);
-    int blocks = (int)(total < 256 && !split ? (total + 7) / 8 * 8 : 256);
     const size_t lds = 2 * 512 * BK * 2;
-    static std::atomic<unsigned long long> attr_done{0}, attr_done_s{0};
     if (split) {
-        if (bya_allow_big_lds(reinterpret_cast<const void*>(gemm256p_kernel<true>), (int)lds, attr_done_s) != BYA_OK) return BYA_ERR_LAUNCH;
         // launch epoch, 24 bits, never 0 (0 = the zero-filled initial state of a counter word)
         static std::atomic<unsigned> g_epoch{0};
         unsigned epoch = (g_epoch.fetch_add(1) + 1u) & 0xffffffu;
         if (epoch == 0u) epoch = (g_epoch.fetch_add(1) + 1u) & 0xffffffu;
-        BYA_LAUNCH(gemm256p_kernel<true>, dim3(blocks), dim3(256), lds, s, a, tiles_m, tiles_n, batch, split, min_seg, epoch);
-    } else {
-        if (bya_allow_big_lds(reinterpret_cast<const void*>(gemm256p_kernel<false>), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-        if (total < 256) blocks = (int)((total + 7) / 8 * 8);
-        BYA_LAUNCH(gemm256p_kernel<false>, dim3(blocks), dim3(256), lds, s, a, tiles_m, tiles_n, batch, 0, min_seg, 0u);
+        return launch_persistent<gemm256p_kernel<true>>(256, 256, lds, s, a, tiles_m, tiles_n, batch, split, min_seg, epoch);      // (every CU: the split needs them)
     }
-    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+    return launch_persistent<gemm256p_kernel<false>>(persistent_grid(total), 256, lds, s, a, tiles_m, tiles_n, batch, 0, min_seg, 0u);
 }

@@ -31,8 +31,6 @@
 
 namespace {
 
-struct Tile128 { int z, m0, n0; bool valid; };
-
 template <bool QKN>
 __global__ __launch_bounds__(256, 1) void gemm128p_kernel(GemmArgs p, int tiles_m, int tiles_n, int batch) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -44,34 +42,13 @@ __global__ __launch_bounds__(256, 1) void gemm128p_kernel(GemmArgs p, int tiles_
     const int wm = wave >> 1, wn = wave & 1;
     const int fr = lane & 15, fq = lane >> 4;
 
-    // ---- this workgroup's output tiles: XCD x owns a contiguous range of the group-M tile order (gemm_v4.hip)
-    const int per_z = tiles_m * tiles_n, total = per_z * batch;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int cq = total >> 3, cr = total & 7;
-    const int base = (xcd < cr) ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-    const int end = base + cq + (xcd < cr ? 1 : 0);
-    auto coord = [&](int seq) {
-        Tile128 c;
-        const int id = base + slot + seq * slots;
-        c.valid = id < end;
-        const int idz = c.valid ? id : base;
-        c.z = idz / per_z;
-        const int idt = idz - c.z * per_z;
-        const int GM = p.gm;
-        const int per_group = GM * tiles_n;
-        const int group = idt / per_group, first_m = group * GM;
-        const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-        const int in_g = idt - group * per_group;
-        c.m0 = (first_m + in_g % gsz) * BM;
-        c.n0 = (in_g / gsz) * BN;
-        return c;
-    };
+    const TileWalk<BM, BN> walk(tiles_m, tiles_n, batch, p.gm);
     int seq = 0;
-    Tile128 cur = coord(seq);
+    PersistentTile cur = walk.coord(seq);
     if (!cur.valid) return;
 
-    // fragment read addresses (XOR swizzle on (row >> 1) & 7; row blocks are 16 rows = 2048 bytes apart).  r?0: k-step 0 of
-    // K-tile t + 1, r?1: k-step 1 of K-tile t -- they sit one ring stage apart and advance together.
+    // fragment read addresses (the LDS image: gemm_persistent.h).  r?0: k-step 0 of K-tile t + 1, r?1: k-step 1 of K-tile t --
+    // they sit one ring stage apart and advance together.
     const int a_row = wm * 64 + fr, w_row = wn * 128 + fr;
     const int a_sw = (a_row >> 1) & 7, w_sw = (w_row >> 1) & 7;
     const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
@@ -83,37 +60,31 @@ __global__ __launch_bounds__(256, 1) void gemm128p_kernel(GemmArgs p, int tiles_
     uint32_t fillW = __builtin_amdgcn_readfirstlane(lds0 + TILE_A + wave * 64 * 128);
     int st = 0;                                                // ring stage of K-tile t
 
-    // staging: wave w moves tile rows [32 w, 32 w + 32) of A (4 one-KiB pieces of 8 rows) and LDS slot rows [64 w, 64 w + 64)
-    // of W (8 pieces); W slot row s = 128 h + 16 i + r holds tile column 128 h + ((r & 3) * 4 + (r >> 2)) * 8 + i.  The lane
-    // loads the source chunk that belongs at its linear LDS position (source-side XOR swizzle).  Offsets are relative to the
-    // tile origin, which lives in the buffer descriptor: rows past M / N arrive as zeros, an invalid tile's descriptor is empty.
+    // staging (map and source-side swizzle: gemm_persistent.h): wave w moves tile rows [32 w, 32 w + 32) of A (4 one-KiB pieces
+    // of 8 rows) and LDS slot rows [64 w, 64 w + 64) of W (8 pieces)
     uint32_t voA[4], voW[8];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int rl = wave * 32 + q * 8 + (lane >> 3);
-        voA[q] = (uint32_t)rl * (uint32_t)(p.lda * 2) + ((lane & 7) ^ ((rl >> 1) & 7)) * 16;
+        voA[q] = stage_off(lane, rl, rl, (uint32_t)(p.lda * 2));
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int rl = wave * 64 + q * 8 + (lane >> 3);
-        const int r = rl & 15, i = (rl >> 4) & 7;
-        const int wcol = (rl & 128) + (((r & 3) << 2) | (r >> 2)) * 8 + i;
-        voW[q] = (uint32_t)wcol * (uint32_t)(p.ldw * 2) + ((lane & 7) ^ ((rl >> 1) & 7)) * 16;
+        voW[q] = stage_off(lane, rl, w_slot_col(rl), (uint32_t)(p.ldw * 2));
     }
-    auto a_rsrc = [&](const Tile128& c) {
+    auto a_rsrc = [&](const PersistentTile& c) {
         const long long left = ((long long)(p.M - 1 - c.m0) * p.lda + p.K) * 2;
         return raw_rsrc(p.A + (long long)c.z * p.a_bs + (long long)c.m0 * p.lda, c.valid && left > 0 ? (uint32_t)left : 0u);
     };
-    auto w_rsrc = [&](const Tile128& c) {
+    auto w_rsrc = [&](const PersistentTile& c) {
         const long long left = ((long long)(p.N - 1 - c.n0) * p.ldw + p.K) * 2;
         return raw_rsrc(p.W + (long long)c.n0 * p.ldw, c.valid && left > 0 ? (uint32_t)left : 0u);
     };
     i32x4 rsA = a_rsrc(cur), rsW = w_rsrc(cur);
 
-#define DMA_A(Q, BASE, RS, SOFF) dma_piece<(Q) * 1024>(BASE, voA[Q], RS, SOFF)
-#define DMA_W(Q, BASE, RS, SOFF) dma_piece<(Q) * 1024>(BASE, voW[Q], RS, SOFF)
-#define ALL4(M, ...) M(0, __VA_ARGS__); M(1, __VA_ARGS__); M(2, __VA_ARGS__); M(3, __VA_ARGS__)
-#define ALL8(M, ...) ALL4(M, __VA_ARGS__); M(4, __VA_ARGS__); M(5, __VA_ARGS__); M(6, __VA_ARGS__); M(7, __VA_ARGS__)
+#define DMA_A(Q, BASE, RS, SOFF) DMA_PIECE(Q, BASE, voA, RS, SOFF)
+#define DMA_W(Q, BASE, RS, SOFF) DMA_PIECE(Q, BASE, voW, RS, SOFF)
     // ---- prologue of the FIRST tile only: K-tiles 0, 1, 2 into stages 0, 1, 2
     ALL4(DMA_A, fillA, rsA, 0u);
     ALL8(DMA_W, fillW, rsW, 0u);
@@ -139,7 +110,7 @@ __global__ __launch_bounds__(256, 1) void gemm128p_kernel(GemmArgs p, int tiles_
     rW0 += STAGE;
 
     for (;;) {
-        const Tile128 nxt = coord(seq + 1);
+        const PersistentTile nxt = walk.coord(seq + 1);
         const i32x4 rsAn = a_rsrc(nxt), rsWn = w_rsrc(nxt);
 
         // One K-tile, variant V; (dA, dW, soff): where the 12 pieces this K-tile requests come from -- K-tile t + 3 of this
@@ -313,12 +284,7 @@ __global__ __launch_bounds__(256, 1) void gemm128p_kernel(GemmArgs p, int tiles_
             MF(1, 7, 3);  NEXT();
         }
             // GENERATED-END
-#define KEEP4(F, S) asm volatile("" :: "v"(F[S][0]), "v"(F[S][1]), "v"(F[S][2]), "v"(F[S][3]))
-#define KEEP8(F, S) asm volatile("" :: "v"(F[S][0]), "v"(F[S][1]), "v"(F[S][2]), "v"(F[S][3]), "v"(F[S][4]), \
-                                      "v"(F[S][5]), "v"(F[S][6]), "v"(F[S][7]))
-            KEEP4(fa, 0); KEEP8(fw, 0); KEEP4(fa, 1); KEEP8(fw, 1);
-#undef KEEP4
-#undef KEEP8
+            KEEP4(fa[0]); KEEP8(fw[0]); KEEP4(fa[1]); KEEP8(fw[1]);
 #undef MF
 #undef MFZ
 #undef DP
@@ -359,6 +325,8 @@ __global__ __launch_bounds__(256, 1) void gemm128p_kernel(GemmArgs p, int tiles_
 #undef RW
 #undef RA_LOOP
 #undef RW_LOOP
+#undef DMA_A
+#undef DMA_W
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the (empty-descriptor) pieces requested for the tile after the last
 }
 
@@ -367,13 +335,8 @@ int launch128p(const GemmArgs& a0, int batch, hipStream_t s) {
     GemmArgs a = a0;
     a.gm = 2 * gemm_group_m(a);                                // the same rows per group as the 256-row tiles' order
     const int tiles_m = (a.M + 127) / 128, tiles_n = (a.N + 255) / 256;
-    const long long total = (long long)tiles_m * tiles_n * batch;
-    const int blocks = (int)(total < 256 ? (total + 7) / 8 * 8 : 256);
     const size_t lds = 3 * (128 + 256) * BK * 2;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (bya_allow_big_lds(reinterpret_cast<const void*>(gemm128p_kernel<QKN>), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-    BYA_LAUNCH((gemm128p_kernel<QKN>), dim3(blocks), dim3(256), lds, s, a, tiles_m, tiles_n, batch);
-    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+    return launch_persistent<gemm128p_kernel<QKN>>(persistent_grid((long long)tiles_m * tiles_n * batch), 256, lds, s, a, tiles_m, tiles_n, batch);
 }
 
 }  // namespace

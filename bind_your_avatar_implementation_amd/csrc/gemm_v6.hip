@@ -31,8 +31,6 @@
 
 namespace {
 
-struct Tile128s { int z, m0, n0; bool valid; };
-
 __global__ __launch_bounds__(512, 1) void gemm128s_kernel(GemmArgs p, int tiles_m, int tiles_n, int batch) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int BM = 128, BN = 256, TILE_A = BM * BK * 2, STAGE = (BM + BN) * BK * 2;
@@ -41,67 +39,34 @@ __global__ __launch_bounds__(512, 1) void gemm128s_kernel(GemmArgs p, int tiles_
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nk = p.K / BK;                                   // >= 4 (launcher)
 
-    // ---- this workgroup's output tiles: XCD x owns a contiguous range of the group-M tile order (gemm_v4.hip)
-    const int per_z = tiles_m * tiles_n, total = per_z * batch;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int cq = total >> 3, cr = total & 7;
-    const int base = (xcd < cr) ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-    const int end = base + cq + (xcd < cr ? 1 : 0);
-    auto coord = [&](int seq) {
-        Tile128s c;
-        const int id = base + slot + seq * slots;
-        c.valid = id < end;
-        const int idz = c.valid ? id : base;
-        c.z = idz / per_z;
-        const int idt = idz - c.z * per_z;
-        const int GM = p.gm;
-        const int per_group = GM * tiles_n;
-        const int group = idt / per_group, first_m = group * GM;
-        const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-        const int in_g = idt - group * per_group;
-        c.m0 = (first_m + in_g % gsz) * BM;
-        c.n0 = (in_g / gsz) * BN;
-        return c;
-    };
+    const TileWalk<BM, BN> walk(tiles_m, tiles_n, batch, p.gm);
     int seq = 0;
-    Tile128s cur = coord(seq);
+    PersistentTile cur = walk.coord(seq);
     if (!cur.valid) return;                                    // (all eight waves alike)
     const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
 
     if (wave >= 4) {
         // ================================================================================================ loader waves
         // wave 4 + w moves tile rows [32 w, 32 w + 32) of A (4 one-KiB pieces of 8 rows) and LDS slot rows [64 w, 64 w + 64) of W
-        // (8 pieces) of every K-tile; layout and source-side swizzle: gemm_v5.hip
+        // (8 pieces) of every K-tile; layout and source-side swizzle: gemm_persistent.h
         const int lw = wave - 4;
         uint32_t voA[4], voW[8];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int rl = lw * 32 + q * 8 + (lane >> 3);
-            voA[q] = (uint32_t)rl * (uint32_t)(p.lda * 2) + ((lane & 7) ^ ((rl >> 1) & 7)) * 16;
+            voA[q] = stage_off(lane, rl, rl, (uint32_t)(p.lda * 2));
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int rl = lw * 64 + q * 8 + (lane >> 3);
-            const int r = rl & 15, i = (rl >> 4) & 7;
-            const int wcol = (rl & 128) + (((r & 3) << 2) | (r >> 2)) * 8 + i;
-            voW[q] = (uint32_t)wcol * (uint32_t)(p.ldw * 2) + ((lane & 7) ^ ((rl >> 1) & 7)) * 16;
+            voW[q] = stage_off(lane, rl, w_slot_col(rl), (uint32_t)(p.ldw * 2));
         }
-        auto a_rsrc = [&](const Tile128s& c) {
-            const long long left = ((long long)(p.M - 1 - c.m0) * p.lda + p.K) * 2;
-            return raw_rsrc(p.A + (long long)c.z * p.a_bs + (long long)c.m0 * p.lda, c.valid && left > 0 ? (uint32_t)left : 0u);
-        };
-        auto w_rsrc = [&](const Tile128s& c) {
-            const long long left = ((long long)(p.N - 1 - c.n0) * p.ldw + p.K) * 2;
-            return raw_rsrc(p.W + (long long)c.n0 * p.ldw, c.valid && left > 0 ? (uint32_t)left : 0u);
-        };
         uint32_t fillA = __builtin_amdgcn_readfirstlane(lds0 + lw * 32 * 128);
         uint32_t fillW = __builtin_amdgcn_readfirstlane(lds0 + TILE_A + lw * 64 * 128);
         int st = 0;                                            // ring stage of K-tile g = the one to refill behind B_g
-        i32x4 rsA = a_rsrc(cur), rsW = w_rsrc(cur);
-#define DMA_A(Q, BASE, RS, SOFF) dma_piece<(Q) * 1024>(BASE, voA[Q], RS, SOFF)
-#define DMA_W(Q, BASE, RS, SOFF) dma_piece<(Q) * 1024>(BASE, voW[Q], RS, SOFF)
-#define ALL4(M, ...) M(0, __VA_ARGS__); M(1, __VA_ARGS__); M(2, __VA_ARGS__); M(3, __VA_ARGS__)
-#define ALL8(M, ...) ALL4(M, __VA_ARGS__); M(4, __VA_ARGS__); M(5, __VA_ARGS__); M(6, __VA_ARGS__); M(7, __VA_ARGS__)
+        i32x4 rsA = tile_rsrc_a(p, p.A, cur), rsW = tile_rsrc_w(p, p.W, cur);
+#define DMA_A(Q, BASE, RS, SOFF) DMA_PIECE(Q, BASE, voA, RS, SOFF)
+#define DMA_W(Q, BASE, RS, SOFF) DMA_PIECE(Q, BASE, voW, RS, SOFF)
         ALL4(DMA_A, fillA, rsA, 0u);
         ALL8(DMA_W, fillW, rsW, 0u);
         ALL4(DMA_A, fillA + STAGE, rsA, (uint32_t)(BK * 2));
@@ -122,8 +87,8 @@ __global__ __launch_bounds__(512, 1) void gemm128s_kernel(GemmArgs p, int tiles_
             st = st == 2 ? 0 : st + 1;
         };
         for (;;) {
-            const Tile128s nxt = coord(seq + 1);
-            const i32x4 rsAn = a_rsrc(nxt), rsWn = w_rsrc(nxt);
+            const PersistentTile nxt = walk.coord(seq + 1);
+            const i32x4 rsAn = tile_rsrc_a(p, p.A, nxt), rsWn = tile_rsrc_w(p, p.W, nxt);
             for (int t = 0; t + 3 < nk; ++t) refill(rsA, rsW, (uint32_t)((t + 3) * (BK * 2)));
             refill(rsAn, rsWn, 0u);
             refill(rsAn, rsWn, (uint32_t)(BK * 2));
@@ -135,8 +100,6 @@ __global__ __launch_bounds__(512, 1) void gemm128s_kernel(GemmArgs p, int tiles_
         }
 #undef DMA_A
 #undef DMA_W
-#undef ALL4
-#undef ALL8
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the (empty-descriptor) pieces requested for the tile after the last
         return;
     }
@@ -144,12 +107,11 @@ __global__ __launch_bounds__(512, 1) void gemm128s_kernel(GemmArgs p, int tiles_
     // ==================================================================================================== compute waves
     const int wm = wave >> 1, wn = wave & 1;
     const int fr = lane & 15, fq = lane >> 4;
-    // fragment read addresses in stage 0 (XOR swizzle on (row >> 1) & 7; row blocks are 16 rows = 2048 bytes apart): k-step 0 / 1
+    // fragment read addresses in stage 0 (the LDS image: gemm_persistent.h): k-step 0 / 1
     const int a_row = wm * 64 + fr, w_row = wn * 128 + fr;
-    const int a_sw = (a_row >> 1) & 7, w_sw = (w_row >> 1) & 7;
-    const uint32_t bA0 = lds0 + a_row * 128 + ((fq ^ a_sw) << 4), bA1 = lds0 + a_row * 128 + (((4 + fq) ^ a_sw) << 4);
-    const uint32_t bW0 = lds0 + TILE_A + w_row * 128 + ((fq ^ w_sw) << 4);
-    const uint32_t bW1 = lds0 + TILE_A + w_row * 128 + (((4 + fq) ^ w_sw) << 4);
+    const uint32_t bA0 = frag_addr(lds0, a_row, fq), bA1 = frag_addr(lds0, a_row, 4 + fq);
+    const uint32_t bW0 = frag_addr(lds0 + TILE_A, w_row, fq);
+    const uint32_t bW1 = frag_addr(lds0 + TILE_A, w_row, 4 + fq);
     uint32_t off1 = 0u, off0 = (uint32_t)STAGE;               // ring stage (as a byte offset) of K-tile g, of K-tile g + 1
     uint32_t rA1 = bA1, rW1 = bW1, rA0 = bA0 + STAGE, rW0 = bW0 + STAGE;
 
@@ -160,7 +122,7 @@ __global__ __launch_bounds__(512, 1) void gemm128s_kernel(GemmArgs p, int tiles_
 #define RA(S, J) ds_read128<(J) * 2048>(fa[S][J], (S) ? rA1 : rA0)
 #define RW(S, I) ds_read128<(I) * 2048>(fw[S][I], (S) ? rW1 : rW0)
     for (;;) {
-        const Tile128s nxt = coord(seq + 1);
+        const PersistentTile nxt = walk.coord(seq + 1);
         // the k-step-0 fragments of this tile's first K-tile (it landed before the previous barrier)
         {
             const uint32_t tA = bA0 + off1, tW = bW0 + off1;
@@ -380,12 +342,7 @@ __global__ __launch_bounds__(512, 1) void gemm128s_kernel(GemmArgs p, int tiles_
             MF(1, 7, 3);  NEXT();
         }
             // GENERATED-END
-#define KEEP4(F, S) asm volatile("" :: "v"(F[S][0]), "v"(F[S][1]), "v"(F[S][2]), "v"(F[S][3]))
-#define KEEP8(F, S) asm volatile("" :: "v"(F[S][0]), "v"(F[S][1]), "v"(F[S][2]), "v"(F[S][3]), "v"(F[S][4]), \
-                                      "v"(F[S][5]), "v"(F[S][6]), "v"(F[S][7]))
-            KEEP4(fa, 0); KEEP8(fw, 0); KEEP4(fa, 1); KEEP8(fw, 1);
-#undef KEEP4
-#undef KEEP8
+            KEEP4(fa[0]); KEEP8(fw[0]); KEEP4(fa[1]); KEEP8(fw[1]);
 #undef MF
 #undef MFZ
 #undef SYNC
@@ -428,11 +385,6 @@ int bya_launch_gemm128s(const void* args, int batch, hipStream_t s) {
     a.gm = 2 * gemm_group_m(a);                                // the same rows per group as the 256-row tiles' order
 #endif
     const int tiles_m = (a.M + 127) / 128, tiles_n = (a.N + 255) / 256;
-    const long long total = (long long)tiles_m * tiles_n * batch;
-    const int blocks = (int)(total < 256 ? (total + 7) / 8 * 8 : 256);
     const size_t lds = 3 * (128 + 256) * BK * 2;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (bya_allow_big_lds(reinterpret_cast<const void*>(gemm128s_kernel), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-    BYA_LAUNCH(gemm128s_kernel, dim3(blocks), dim3(512), lds, s, a, tiles_m, tiles_n, batch);
-    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+    return launch_persistent<gemm128s_kernel>(persistent_grid((long long)tiles_m * tiles_n * batch), 512, lds, s, a, tiles_m, tiles_n, batch);
 }

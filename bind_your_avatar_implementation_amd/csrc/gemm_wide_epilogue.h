@@ -1,37 +1,16 @@
-// The 16-byte ("wide") epilogues and the LDS-DMA helpers shared by the persistent one-wave-per-SIMD GEMM kernels:
-// gemm_v4.hip (256 x 256 tiles, a wave owns 128 x 128: NJ = 8 row blocks) and gemm_v5.hip (128 x 256 tiles, a wave owns
-// 64 x 128: NJ = 4).  Both stage the W rows of a wave's 128-column span in the permuted order that makes a lane's eight
-// accumulator tiles i = 0..7 hold EIGHT CONSECUTIVE output columns (see the top of gemm_v4.hip).
+// The 16-byte ("wide") epilogues of the persistent one-wave-per-SIMD bf16 GEMM kernels: gemm_v4.hip (256 x 256 tiles, a wave
+// owns 128 x 128: NJ = 8 row blocks) and gemm_v5.hip / gemm_v6.hip (128 x 256 tiles, a wave owns 64 x 128: NJ = 4).  They stage
+// the W rows of a wave's 128-column span in the permuted order that makes a lane's eight accumulator tiles i = 0..7 hold
+// EIGHT CONSECUTIVE output columns (the LDS image: top of gemm_persistent.h).
 #pragma once
-#include "gemm_common.h"
+#include "gemm_persistent.h"
 #include "qknorm_math.h"
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ i32x4 raw_rsrc(const void* base, uint32_t bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffu));
-    r.y = __builtin_amdgcn_readfirstlane((int)((b >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-// one 1-KiB LDS-DMA piece: 64 lanes x 16 bytes from per-lane global offsets to LDS [m0 .. m0 + 1024)
-template <int LDS_OFF>
-__device__ __forceinline__ void dma_piece(uint32_t lds_base, uint32_t voff, const i32x4& rsrc, uint32_t soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :
-                 : "s"(lds_base + LDS_OFF), "v"(voff), "s"(rsrc), "s"(soff)
-                 : "memory");
-}
-
 // Wide epilogue of one wave.  The lane (fr = lane & 15, fq = lane >> 4) holds, for row block j and accumulator register e,
 // the EIGHT consecutive columns  n8 = n_wave + (4 e + fq) * 8 + i,  i = 0..7  in acc[i][j][e]  (W rows are staged in the
-// permuted order described at the top), of row  m = m_wave + 16 j + fr.
+// permuted order of gemm_persistent.h), of row  m = m_wave + 16 j + fr.
 // Split tiles (see the top).  A slab holds a tile's partial sums in the order this epilogue walks the accumulators:
 // unit (wave, j, e, half) = the lane's values i = 4 half .. 4 half + 3 of row block j, register e: 16 bytes per lane at
 // ((wave * 64 + (j * 4 + e) * 2 + half) * 64 + lane) * 16, so that one store instruction writes eight whole 128-byte lines.

@@ -166,6 +166,41 @@ def test_generated_gemm_schedules_match_their_tables():
         assert out.returncode == 0, out.stdout + out.stderr
 
 
+def test_isa_fingerprint_reads_streams_and_metadata():
+    """tools/isa_fingerprint.py: the stream filter keeps memory / matrix / wait / barrier / branch instructions in order, with
+    operands only for s_waitcnt and s_nop, and the metadata reader takes a kernel's own fields, not its arguments'; then one
+    small translation unit end to end (hipcc cross-compiles without a GPU)."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import isa_fingerprint as fp
+    finally:
+        sys.path.pop(0)
+    asm = "\n".join([
+        "\t.text", "helper:", "\ts_nop 3", ".Lfunc_end0:",
+        "k1:", "\ts_load_dwordx2 s[2:3], s[0:1], 0x0", "\ts_waitcnt lgkmcnt(0)  ; wait", "\tv_mov_b32_e32 v1, 0",
+        "\tbuffer_load_dwordx4 v[0:3], v4, s[4:7], 0 offen lds", ".LBB1_2:", "\tv_mfma_f32_16x16x32_bf16 a[0:3], v[0:3], v[4:7], a[0:3]",
+        "\ts_nop  15", "\tds_read_b128 v[8:11], v12 offset:2048", "\ts_cbranch_scc1 .LBB1_2", "\ts_barrier", "\ts_endpgm", ".Lfunc_end1:",
+        "\t.amdgpu_metadata", "---", "amdhsa.kernels:",
+        "  - .agpr_count:     128", "    .args:", "      - .name:           p", "        .size:           8",
+        "    .group_segment_fixed_size: 0", "    .name:           k1", "    .private_segment_fixed_size: 16",
+        "    .sgpr_count:     106", "    .sgpr_spill_count: 5", "    .vgpr_count:     384", "    .vgpr_spill_count: 3",
+        "amdhsa.target:   amdgcn-amd-amdhsa--gfx950", "...",
+    ])
+    streams = fp.kernel_streams(asm)
+    assert streams["k1"] == ["s_waitcnt lgkmcnt(0)", "buffer_load_dwordx4", "v_mfma_f32_16x16x32_bf16", "s_nop 15", "ds_read_b128",
+                             "s_cbranch_scc1", "s_barrier", "s_endpgm"]
+    assert streams["helper"] == ["s_nop 3"]
+    meta = fp.kernel_metadata(asm)
+    assert list(meta) == ["k1"]
+    assert meta["k1"][".vgpr_count"] == "384" and meta["k1"][".agpr_count"] == "128" and meta["k1"][".sgpr_spill_count"] == "5"
+    assert meta["k1"][".private_segment_fixed_size"] == "16" and meta["k1"][".group_segment_fixed_size"] == "0"
+    lines = fp.fingerprint("calib.hip")
+    assert len(lines) == 1 and lines[0].startswith("calib.hip ") and "mfma_calibration_kernel" in lines[0]
+    fields = dict(f.split("=") for f in lines[0].split()[2:])
+    assert fields["agpr_count"] == "256" and int(fields["stream_len"]) > 256 and len(fields["stream_sha1"]) == 16
+
+
 def test_valu_only_kernels_hold_no_packed_fp32(lib_path):
     """packed-fp32 VALU arithmetic (v_pk_mul / fma / add / mov) in the VALU-only kernels returned
     wrong lanes whenever another process kept MFMA workgroups resident; build.py compiles those translation units

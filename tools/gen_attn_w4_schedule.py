@@ -36,8 +36,9 @@ then PV_3).  Edit the tables, run the script: it rewrites the block between the 
 --check verifies the committed source is what the tables generate (tests/test_abi_cpu.py).
 """
 import os
-import re
 import sys
+
+import generated_block
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATH = os.path.join(ROOT, "bind_your_avatar_implementation_amd", "csrc", "attn_w4.hip")
@@ -227,23 +228,9 @@ def main():
     if "--ablate" in sys.argv:                              # tools/attn_w4_ablate.py: write a side copy, never the product file
         ABLATE = int(sys.argv[sys.argv.index("--ablate") + 1])
         out = sys.argv[sys.argv.index("--out") + 1]
-        src = open(PATH).read()
-        new, n = re.subn(r"(// GENERATED-BEGIN[^\n]*\n).*?([ \t]*// GENERATED-END)",
-                         lambda m: m.group(1) + emit() + "\n" + m.group(2), src, flags=re.S)
-        assert n == 1
-        open(out, "w").write(new)
+        open(out, "w").write(generated_block.splice(open(PATH).read(), emit()))
         return
-    src = open(PATH).read()
-    new, n = re.subn(r"(// GENERATED-BEGIN[^\n]*\n).*?([ \t]*// GENERATED-END)",
-                     lambda m: m.group(1) + emit() + "\n" + m.group(2), src, flags=re.S)
-    assert n == 1, "GENERATED markers not found"
-    if "--check" in sys.argv:
-        if new != src:
-            raise SystemExit(f"{PATH}: the GENERATED block is out of date (run this script without --check)")
-        print("up to date", PATH)
-        return
-    open(PATH, "w").write(new)
-    print("rewrote", PATH)
+    generated_block.main(PATH, emit())
 
 
 if __name__ == "__main__":

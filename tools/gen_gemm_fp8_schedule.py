@@ -2,7 +2,9 @@
 x A blocks 0..7, phase 1 = W blocks 4..7 x A blocks 0..7 (A-major), with the barriers, the fragment re-reads and the 16 LDS-DMA
 pieces of a K-tile at the positions of the placement table below (a piece "at n" is issued right behind MFMA n).
 usage: python tools/gen_gemm_fp8_schedule.py [--check]"""
-import os, sys
+import os
+
+import generated_block
 
 HIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bind_your_avatar_implementation_amd", "csrc",
                    "gemm_fp8_v4.hip")
@@ -54,8 +56,8 @@ def body(entry):
     return out
 
 
-def generated():
-    lines = ["            // GENERATED-BEGIN (tools/gen_gemm_fp8_schedule.py)"]
+def emit():
+    lines = []
     first = True
     for key, pos in PLACEMENTS.items():
         lines.append(f"#{'if' if first else 'elif'} BYA_F8_PLACE == {key}")
@@ -64,25 +66,14 @@ def generated():
     lines.append("#else")
     lines.append('#error "BYA_F8_PLACE: unknown placement"')
     lines.append("#endif")
-    lines.append("            // GENERATED-END")
-    return lines
+    return "\n".join(lines)
 
 
-def main():
-    src = open(HIP).read().split("\n")
-    a = next(i for i, l in enumerate(src) if "GENERATED-BEGIN" in l)
-    b = next(i for i, l in enumerate(src) if "GENERATED-END" in l)
-    new = src[:a] + generated() + src[b + 1:]
-    if "--check" in sys.argv:
-        if new != src:
-            sys.exit("gemm_fp8_v4.hip: GENERATED block is stale (run tools/gen_gemm_fp8_schedule.py)")
-        want = f"#define BYA_F8_PLACE {PLACE_DEFAULT}"
-        if not any(l.strip().startswith(want) for l in src):
-            sys.exit(f"gemm_fp8_v4.hip: default placement is not {PLACE_DEFAULT}")
-        print("ok")
-        return
-    open(HIP, "w").write("\n".join(new))
+def default_placement(src):
+    want = f"#define BYA_F8_PLACE {PLACE_DEFAULT}"
+    if not any(l.strip().startswith(want) for l in src.split("\n")):
+        return f"default placement is not {PLACE_DEFAULT}"
 
 
 if __name__ == "__main__":
-    main()
+    generated_block.main(HIP, emit(), also_check=default_placement)

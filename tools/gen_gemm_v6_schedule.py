@@ -15,7 +15,8 @@ of a kernel that has 256 per wave).  Edit the tables, run the script: it rewrite
 """
 import os
 import re
-import sys
+
+import generated_block
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATH = os.path.join(ROOT, "bind_your_avatar_implementation_amd", "csrc", "gemm_v6.hip")
@@ -60,19 +61,5 @@ def emit():
     return "\n".join(out)
 
 
-def main():
-    src = open(PATH).read()
-    new, n = re.subn(r"(// GENERATED-BEGIN[^\n]*\n).*?([ \t]*// GENERATED-END)",
-                     lambda m: m.group(1) + emit() + "\n" + m.group(2), src, flags=re.S)
-    assert n == 1, "GENERATED markers not found"
-    if "--check" in sys.argv:
-        if new != src:
-            raise SystemExit(f"{PATH}: the GENERATED block is out of date (run this script without --check)")
-        print("up to date", PATH)
-        return
-    open(PATH, "w").write(new)
-    print("rewrote", PATH)
-
-
 if __name__ == "__main__":
-    main()
+    generated_block.main(PATH, emit())
