@@ -1,5 +1,6 @@
 // MX (OCP Microscaling) "NT" GEMM on the block-scaled CDNA4 matrix instruction, and the block quantiser that feeds it:
-//     C[m,n] = epi( sum_k A[m,k] * W[n,k] ),   A, W = e8m0 scale per 32 consecutive k  x  e4m3 / e2m3 elements
+//     C[m,n] = epi( sum_k A[m,k] * W[n,k] ),   A, W = e8m0 scale per 32 consecutive k  x  e4m3 / e2m3 elements,
+//     or W alone in e2m1 under e4m3 / e2m3 activations (bya_gemm_mx_mixed: the instruction takes a format per operand)
 // Format and storage: include/bya.h, "MX weights".  The four big Linears of a DiT block (attn1.to_q|k|v, attn1.to_out,
 // ff.net.0.proj, ff.net.2 -- models/transformer.py:241-260) when the engine is built with MX weights
 // (enable_mx_weights).  No reference counterpart; parity is against the CPU restatement on the same bytes
@@ -14,14 +15,16 @@
 //     block b is then bytes 16 b .. 16 b + 15 of the first and of the second 64-k half of lanes 32 (b / 2) ..., so a lane
 //     filled with one contiguous 32-byte block (the layout of gemm_fp8_kernel.h, correct there only because its scales are
 //     all 2^0) gets the wrong scale on half its bytes.  The kernel reads 16-byte chunks g and 4 + g of the K-tile for lane
-//     group g: the instruction's block b is then exactly k = 32 b .. 32 b + 31 of the tile, as stored.
+//     group g: the instruction's block b is then exactly k = 32 b .. 32 b + 31 of the tile, as stored;
+//   - e2m1 (the W operand only): four VGPRs = the 16 bytes of block l >> 4, element i at bits 4i.. (low nibble first),
+//     whichever format the other operand has (tests/test_mxfp4_gpu.py, operand-map test on exact data).
 //
 // The kernel is the 128 x 128 tile of gemm_fp8_kernel.h (4 waves of 64 x 64, two-stage LDS ring fed by global_load_lds,
 // group-M tile order) with real block scales, and for big e2m3 launches the same loop on 256 x 256 tiles (8 waves of
 // 64 x 128):
 //   - a K-tile is 128 elements = 128 bytes (e4m3: the XOR-swizzled image of the fp8 kernel) or 96 bytes (e2m3: rows stored
 //     back to back with chunk pairs swapped on every other group of 8 rows, 16 bytes per lane and DMA instruction, the
-//     lane's block read as three 8-byte pieces);
+//     lane's block read as three 8-byte pieces) or 64 bytes (e2m1 W: rows back to back, one 16-byte read per fragment);
 //   - the 4 scale bytes of a row for one K-tile are one dword; the block's 256 rows' dwords ride in the same LDS stage
 //     (one 4-byte global_load_lds per wave), so their wait is the ring's own vmcnt(0).
 #include "gemm_common.h"
@@ -36,7 +39,11 @@ typedef int i32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int MX_BK = 128;                 // elements per K-tile (one MFMA step)
 constexpr int MX_GROUP_M = 8;              // row-tiles per group of the tile order (as the fp8 kernel)
-__host__ __device__ constexpr int mx_tile_row_bytes(int fmt) { return fmt == MX_E4M3 ? 128 : 96; }
+__host__ __device__ constexpr int mx_tile_row_bytes(int fmt) { return fmt == MX_E4M3 ? 128 : fmt == MX_E2M3 ? 96 : 64; }
+// 16-byte global_load_lds instructions of one wave for ROWS rows of a K-tile
+__host__ __device__ constexpr int mx_stage_dmas(int fmt, int rows, int nwaves) {
+    return fmt == MX_E4M3 ? rows / nwaves / 8 : rows * mx_tile_row_bytes(fmt) / 1024 / nwaves;
+}
 // e2m3 launches of >= 200 256 x 256 tiles run on 256 x 256 tiles (8 waves, one workgroup per CU, half the L2 -> LDS bytes
 // per FLOP of the 128 x 128 tile: 572 vs 699 us at q|k|v, 706 vs 978 us at ff.net.2), everything else on 128 x 128 tiles.
 // The ring is two stages deep; three (a counted wait keeping the next K-tile's DMA in flight across the barrier) measured
@@ -67,6 +74,23 @@ __device__ __forceinline__ void stage_mx(const uint8_t* __restrict__ src, int ld
             const uint8_t* g = src + (long long)gr * ld + kb0 + chunk * 16;
             __builtin_amdgcn_global_load_lds(GLOBAL_PTR(g), LDS_PTR(lds_tile + rbase * 128), 16, 0, 0);
         }
+    } else if constexpr (FMT == MX_E2M1) {
+        // 64-byte rows back to back, 16 rows per instruction: a row of the K-tile is one L2 sector.  16-byte chunk c of row r
+        // lands at chunk c ^ (((r >> 2) & 1) << 1): unswizzled, rows r and r + 12 (and r + 4, r + 8 of the next lane group) of
+        // one ds_read_b128 lane group {0-3, 12-15, 20-27} hit the same 16-byte slot of the 256-byte bank row -- a 2-way
+        // conflict on every fragment read; with the XOR the 16 lanes of each group cover the 16 slots once
+        constexpr int RB = 64, INSTR = ROWS * RB / 1024, PER_WAVE = INSTR / NWAVES;
+        static_assert(INSTR % NWAVES == 0, "tile must split evenly over the waves");
+#pragma unroll
+        for (int q = 0; q < PER_WAVE; ++q) {
+            const int qi = wave * PER_WAVE + q;
+            const int rl = qi * 16 + (lane >> 2);
+            const int chunk = (lane & 3) ^ (((rl >> 2) & 1) << 1);
+            int gr = row0 + rl;
+            gr = gr < row_max ? gr : row_max;
+            const uint8_t* g = src + (long long)gr * ld + kb0 + chunk * 16;
+            __builtin_amdgcn_global_load_lds(GLOBAL_PTR(g), LDS_PTR(lds_tile + qi * 1024), 16, 0, 0);
+        }
     } else {
         // 96-byte rows back to back: byte t of the tile is row t / 96, offset t % 96 (a multiple of 16).  16-byte chunk c of
         // row r lands at chunk c ^ ((r >> 3) & 1) (pairs 0|1, 2|3, 4|5 stay in the row): rows r and r + 8, 768 bytes apart, hit
@@ -86,7 +110,7 @@ __device__ __forceinline__ void stage_mx(const uint8_t* __restrict__ src, int ld
     }
 }
 
-// lane group g's operand of one row (e4m3: k = 16 g .. +15 and 64 + 16 g .. +15; e2m3: block g = k = 32 g .. 32 g + 31)
+// lane group g's operand of one row (e4m3: k = 16 g .. +15 and 64 + 16 g .. +15; e2m3, e2m1: block g = k = 32 g .. 32 g + 31)
 template <int FMT>
 __device__ __forceinline__ i32x8 lds_frag_mx(const char* tile, int row, int g) {
     if constexpr (FMT == MX_E4M3) {
@@ -94,6 +118,9 @@ __device__ __forceinline__ i32x8 lds_frag_mx(const char* tile, int row, int g) {
         const i32x4 lo = *reinterpret_cast<const i32x4*>(tile + row * 128 + ((g ^ sw) << 4));
         const i32x4 hi = *reinterpret_cast<const i32x4*>(tile + row * 128 + (((4 + g) ^ sw) << 4));
         return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    } else if constexpr (FMT == MX_E2M1) {
+        const i32x4 b = *reinterpret_cast<const i32x4*>(tile + row * 64 + ((g ^ (((row >> 2) & 1) << 1)) << 4));
+        return i32x8{b[0], b[1], b[2], b[3], 0, 0, 0, 0};
     } else {
         const char* r = tile + row * 96;
         const int x = ((row >> 3) & 1) << 4, o = g * 24;                    // (the staging's chunk swizzle)
@@ -104,12 +131,13 @@ __device__ __forceinline__ i32x8 lds_frag_mx(const char* tile, int row, int g) {
     }
 }
 
-template <int FMT, int BM, int BN, int WAVES_M, int WAVES_N>
+// FMT_A: activations (the instruction's B operand, blgp); FMT_W: weights (its A operand, cbsz)
+template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_kernel(GemmArgs p, const uint8_t* __restrict__ sa,
                                                                          const uint8_t* __restrict__ sw, int GM) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NWAVES = WAVES_M * WAVES_N, RB = mx_tile_row_bytes(FMT);
-    constexpr int TILE_A = BM * RB, TILE_W = BN * RB, SCALES = (BM + BN) * 4, STAGE = TILE_A + TILE_W + SCALES;
+    constexpr int NWAVES = WAVES_M * WAVES_N, RB_A = mx_tile_row_bytes(FMT_A), RB_W = mx_tile_row_bytes(FMT_W);
+    constexpr int TILE_A = BM * RB_A, TILE_W = BN * RB_W, SCALES = (BM + BN) * 4, STAGE = TILE_A + TILE_W + SCALES;
     static_assert(BM + BN == 64 * WAVES_M * WAVES_N, "one scale row per lane of the block");
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, MI = WM / 16, NI = WN / 16;
 
@@ -144,8 +172,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_kernel(GemmArg
     }
     auto stage = [&](int kt, int buf) {
         char* base = smem + buf * STAGE;
-        stage_mx<FMT, BM, NWAVES>(A, p.lda, m0, p.M - 1, kt * RB, base, wave, lane);
-        stage_mx<FMT, BN, NWAVES>(W, p.ldw, n0, p.N - 1, kt * RB, base + TILE_A, wave, lane);
+        stage_mx<FMT_A, BM, NWAVES>(A, p.lda, m0, p.M - 1, kt * RB_A, base, wave, lane);
+        stage_mx<FMT_W, BN, NWAVES>(W, p.ldw, n0, p.N - 1, kt * RB_W, base + TILE_A, wave, lane);
         __builtin_amdgcn_global_load_lds(GLOBAL_PTR(srow + 4 * kt), LDS_PTR(base + TILE_A + TILE_W + wave * 256), 4, 0, 0);
     };
 
@@ -156,11 +184,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_kernel(GemmArg
         for (int j = 0; j < MI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int sh = 8 * fq;                               // this lane's block within the K-tile -> its scale byte
-    // Ring of NST stages.  Two deep (e4m3): every K-tile waits for all its loads, then one barrier.  Three deep (e2m3): the
+    // Ring of NST stages (by the activation format).  Two deep (e4m3): every K-tile waits for all its loads, then one barrier.  Three deep (e2m3): the
     // wait is counted -- the loads of the next K-tile stay in flight across the barrier (a raw s_barrier: __syncthreads
     // would make hipcc drain them), so a K-tile's DMA has two K-tiles of compute to land in instead of none.
-    constexpr int NST = mx_stages(FMT);
-    constexpr int VM_STAGE = (FMT == MX_E4M3 ? (BM + BN) / NWAVES / 8 : (BM + BN) * RB / 1024 / NWAVES) + 1;  // DMAs per wave
+    constexpr int NST = mx_stages(FMT_A);
+    constexpr int VM_STAGE = mx_stage_dmas(FMT_A, BM, NWAVES) + mx_stage_dmas(FMT_W, BN, NWAVES) + 1;           // DMAs per wave
     for (int s0 = 0; s0 < NST - 1 && s0 < nk; ++s0) stage(s0, s0);
     for (int kt = 0; kt < nk; ++kt) {
         if constexpr (NST == 2) {
@@ -182,14 +210,14 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_kernel(GemmArg
         for (int i = 0; i < NI; ++i) xw[i] = (int)(ts[BM + wn * WN + i * 16 + fr] >> sh);
         i32x8 fa[MI], fw[NI];
 #pragma unroll
-        for (int j = 0; j < MI; ++j) fa[j] = lds_frag_mx<FMT>(ta, wm * WM + j * 16 + fr, fq);
+        for (int j = 0; j < MI; ++j) fa[j] = lds_frag_mx<FMT_A>(ta, wm * WM + j * 16 + fr, fq);
 #pragma unroll
-        for (int i = 0; i < NI; ++i) fw[i] = lds_frag_mx<FMT>(tw, wn * WN + i * 16 + fr, fq);
+        for (int i = 0; i < NI; ++i) fw[i] = lds_frag_mx<FMT_W>(tw, wn * WN + i * 16 + fr, fq);
 #pragma unroll
         for (int i = 0; i < NI; ++i)
 #pragma unroll
             for (int j = 0; j < MI; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[i], fa[j], acc[i][j], FMT, FMT,
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[i], fa[j], acc[i][j], FMT_W, FMT_A,
                                                                              0, xw[i], 0, xa[j]);
     }
 
@@ -201,13 +229,13 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_kernel(GemmArg
     dispatch_act_big(p.act, run);
 }
 
-template <int FMT, int BM, int BN, int WAVES_M, int WAVES_N>
+template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
 int launch_mx(const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, int batch, hipStream_t s) {
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
     dim3 grid(tiles_m * tiles_n, 1, batch);
-    const size_t lds = (size_t)mx_stages(FMT) * (BM + BN) * (mx_tile_row_bytes(FMT) + 4);
+    const size_t lds = (size_t)mx_stages(FMT_A) * (BM * (mx_tile_row_bytes(FMT_A) + 4) + BN * (mx_tile_row_bytes(FMT_W) + 4));
     static std::atomic<unsigned long long> attr_done{0};
-    auto kern = gemm_mx_kernel<FMT, BM, BN, WAVES_M, WAVES_N>;
+    auto kern = gemm_mx_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N>;
     if (bya_allow_big_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
     BYA_LAUNCH(kern, grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a, sa, sw, MX_GROUP_M);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
@@ -244,31 +272,35 @@ __global__ __launch_bounds__(256) void quantize_mx_kernel(const bf16_t* __restri
 extern "C" int bya_quantize_mx(const void* x, void* codes, void* scales, int32_t M, int32_t K, int64_t ldx, int32_t fmt,
                                hipStream_t stream) {
     if (!x || !codes || !scales || M <= 0 || K <= 0 || K % 128) return BYA_ERR_SHAPE;
-    if (fmt != MX_E4M3 && fmt != MX_E2M3) return BYA_ERR_SHAPE;
+    if (fmt != MX_E4M3 && fmt != MX_E2M3 && fmt != MX_E2M1) return BYA_ERR_SHAPE;
     if (ldx < K || ldx % 8 || ((uintptr_t)x & 15) || ((uintptr_t)codes & 7)) return BYA_ERR_ALIGN;
     const long long total = (long long)M * (K / 8);
     dim3 grid((unsigned)((total + 255) / 256));
     if (fmt == MX_E4M3)
         BYA_LAUNCH(quantize_mx_kernel<MX_E4M3>, grid, dim3(256), 0, stream, (const bf16_t*)x, (uint8_t*)codes,
                    (uint8_t*)scales, (long long)M, K, (long long)ldx);
-    else
+    else if (fmt == MX_E2M3)
         BYA_LAUNCH(quantize_mx_kernel<MX_E2M3>, grid, dim3(256), 0, stream, (const bf16_t*)x, (uint8_t*)codes,
+                   (uint8_t*)scales, (long long)M, K, (long long)ldx);
+    else
+        BYA_LAUNCH(quantize_mx_kernel<MX_E2M1>, grid, dim3(256), 0, stream, (const bf16_t*)x, (uint8_t*)codes,
                    (uint8_t*)scales, (long long)M, K, (long long)ldx);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 
 namespace {
-// bya_gemm_mx's arguments -> GemmArgs; BYA_OK or the error that rejects them
+// bya_gemm_mx_mixed's arguments -> GemmArgs; BYA_OK or the error that rejects them
 int mx_args(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, const void* C,
-            const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d, int32_t fmt, GemmArgs* out) {
+            const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d, int32_t a_fmt, int32_t w_fmt,
+            GemmArgs* out) {
     if (!A || !W || !a_scales || !w_scales || !C || !d) return BYA_ERR_SHAPE;
-    if (fmt != MX_E4M3 && fmt != MX_E2M3) return BYA_ERR_SHAPE;
+    // activations e4m3 / e2m3; weights in the same format or in e2m1
+    if ((a_fmt != MX_E4M3 && a_fmt != MX_E2M3) || (w_fmt != a_fmt && w_fmt != MX_E2M1)) return BYA_ERR_UNSUPPORTED;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return BYA_ERR_SHAPE;
     if (d->K % MX_BK != 0 || d->N % 4 != 0) return BYA_ERR_SHAPE;
     if ((long long)d->batch * d->M * (d->K / 32) >= (1LL << 31) || (long long)d->N * (d->K / 32) >= (1LL << 31))
         return BYA_ERR_SHAPE;
-    const int row_bytes = d->K / 32 * mx_block_bytes(fmt);
-    if (d->lda < row_bytes || d->ldw < row_bytes) return BYA_ERR_SHAPE;
+    if (d->lda < d->K / 32 * mx_block_bytes(a_fmt) || d->ldw < d->K / 32 * mx_block_bytes(w_fmt)) return BYA_ERR_SHAPE;
     if (d->lda % 16 || d->ldw % 16 || d->ldc % 4 || (res && d->ldres % 4) || d->a_batch_stride % 16) return BYA_ERR_ALIGN;
     if (((uintptr_t)A | (uintptr_t)W) & 15) return BYA_ERR_ALIGN;
     if (((uintptr_t)a_scales | (uintptr_t)w_scales) & 3) return BYA_ERR_ALIGN;
@@ -288,7 +320,7 @@ int mx_args(const void* A, const void* a_scales, const void* W, const void* w_sc
     return BYA_OK;
 }
 
-// e4m3 on 128 x 128 tiles; e2m3 on 256 x 256 tiles when the launch has about a round of 256 CUs of them, or more
+// By the activation format: e4m3 on 128 x 128 tiles; e2m3 on 256 x 256 tiles when the launch has about a round of 256 CUs of them, or more
 inline int mx_path(const GemmArgs& a, int batch, int32_t fmt) {
     const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
     const bool big = BYA_MX_E2M3_BIG_TILE && tiles256 >= 200;
@@ -296,34 +328,55 @@ inline int mx_path(const GemmArgs& a, int batch, int32_t fmt) {
 }
 }  // namespace
 
-extern "C" int bya_gemm_mx(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
-                           void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
-                           int32_t fmt, hipStream_t stream) {
+extern "C" int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                                 void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
+                                 int32_t a_fmt, int32_t w_fmt, hipStream_t stream) {
     GemmArgs a;
-    const int rc = mx_args(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, fmt, &a);
+    const int rc = mx_args(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, a_fmt, w_fmt, &a);
     if (rc != BYA_OK) return rc;
     const uint8_t* sa = (const uint8_t*)a_scales;
     const uint8_t* sw = (const uint8_t*)w_scales;
     const long long ks = d->K / 32;
-    const int path = mx_path(a, d->batch, fmt);
+    const bool big = mx_path(a, d->batch, a_fmt) == BYA_GEMM_PATH_T256X256, w4 = w_fmt == MX_E2M1;
     return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
-        if (fmt == MX_E4M3) return launch_mx<MX_E4M3, 128, 128, 2, 2>(piece, sa + row0 * ks, sw, batch, stream);
-        if (path == BYA_GEMM_PATH_T256X256) return launch_mx<MX_E2M3, 256, 256, 4, 2>(piece, sa + row0 * ks, sw, batch, stream);
-        return launch_mx<MX_E2M3, 128, 128, 2, 2>(piece, sa + row0 * ks, sw, batch, stream);
+        const uint8_t* sp = sa + row0 * ks;
+        if (a_fmt == MX_E4M3)
+            return w4 ? launch_mx<MX_E4M3, MX_E2M1, 128, 128, 2, 2>(piece, sp, sw, batch, stream)
+                      : launch_mx<MX_E4M3, MX_E4M3, 128, 128, 2, 2>(piece, sp, sw, batch, stream);
+        if (big)
+            return w4 ? launch_mx<MX_E2M3, MX_E2M1, 256, 256, 4, 2>(piece, sp, sw, batch, stream)
+                      : launch_mx<MX_E2M3, MX_E2M3, 256, 256, 4, 2>(piece, sp, sw, batch, stream);
+        return w4 ? launch_mx<MX_E2M3, MX_E2M1, 128, 128, 2, 2>(piece, sp, sw, batch, stream)
+                  : launch_mx<MX_E2M3, MX_E2M3, 128, 128, 2, 2>(piece, sp, sw, batch, stream);
     });
+}
+
+extern "C" int bya_gemm_mx_mixed_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                      const void* bias, const void* C, const void* res, const void* gate0, const void* gate1,
+                                      const bya_gemm_desc* d, int32_t a_fmt, int32_t w_fmt, bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    GemmArgs a, piece;
+    int nb = 0;
+    const int rc = mx_args(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, a_fmt, w_fmt, &a);
+    if (rc != BYA_OK) return rc;
+    const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
+    if (!chunks) return BYA_ERR_UNSUPPORTED;
+    p->path = mx_path(a, d->batch, a_fmt);
+    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = chunks;
+    return BYA_OK;
+}
+
+// Both operands in one format: e4m3 or e2m3 (e2m1 activations are not offered)
+extern "C" int bya_gemm_mx(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                           void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
+                           int32_t fmt, hipStream_t stream) {
+    if (fmt != MX_E4M3 && fmt != MX_E2M3) return BYA_ERR_SHAPE;
+    return bya_gemm_mx_mixed(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, fmt, fmt, stream);
 }
 
 extern "C" int bya_gemm_mx_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
                                 const void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
                                 int32_t fmt, bya_gemm_plan* p) {
-    if (!p) return BYA_ERR_SHAPE;
-    GemmArgs a, piece;
-    int nb = 0;
-    const int rc = mx_args(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, fmt, &a);
-    if (rc != BYA_OK) return rc;
-    const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
-    if (!chunks) return BYA_ERR_UNSUPPORTED;
-    p->path = mx_path(a, d->batch, fmt);
-    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = chunks;
-    return BYA_OK;
+    if (fmt != MX_E4M3 && fmt != MX_E2M3) return BYA_ERR_SHAPE;
+    return bya_gemm_mx_mixed_plan(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, fmt, fmt, p);
 }

@@ -7,9 +7,9 @@
 
 namespace {
 
-constexpr int MX_E4M3 = 0, MX_E2M3 = 2;                                   // the instruction's cbsz / blgp codes
-__host__ __device__ constexpr int mx_emax(int fmt) { return fmt == MX_E4M3 ? 8 : 2; }
-__host__ __device__ constexpr int mx_block_bytes(int fmt) { return fmt == MX_E4M3 ? 32 : 24; }
+constexpr int MX_E4M3 = 0, MX_E2M3 = 2, MX_E2M1 = 4;                      // the instruction's cbsz / blgp codes
+__host__ __device__ constexpr int mx_emax(int fmt) { return fmt == MX_E4M3 ? 8 : 2; }                  // (e2m3 and e2m1: 2)
+__host__ __device__ constexpr int mx_block_bytes(int fmt) { return fmt == MX_E4M3 ? 32 : fmt == MX_E2M3 ? 24 : 16; }
 
 // |v| <= 7.5 after the clamp; e2m3 code = (exponent << 3) | mantissa with exponent bias 1.  In each binade the code is
 // an affine function of v / step (step 1/8 below 2, 1/4 in [2, 4), 1/2 in [4, 8)), and rint (v_rndne_f32) is RNE on
@@ -24,9 +24,21 @@ __device__ __forceinline__ uint32_t f32_to_e2m3(float v) {
     return sign | c;
 }
 
+// |v| <= 6 after the clamp; e2m1 code = (exponent << 1) | mantissa with exponent bias 1 (magnitudes 0, 0.5, 1, 1.5, 2, 3, 4,
+// 6).  The same count of steps as f32_to_e2m3: step 1/2 below 2, 1 in [2, 4), 2 from 4.
+__device__ __forceinline__ uint32_t f32_to_e2m1(float v) {
+    const uint32_t sign = (__float_as_uint(v) >> 28) & 0x8u;
+    const float a = fminf(fabsf(v), 6.0f);
+    uint32_t c;
+    if (a < 2.0f) c = (uint32_t)__builtin_rintf(a * 2.0f);
+    else if (a < 4.0f) c = (uint32_t)__builtin_rintf(a) + 2u;
+    else c = (uint32_t)__builtin_rintf(a * 0.5f) + 4u;
+    return sign | c;
+}
+
 // Quantise the 8 values of this lane's share of a 32-block whose |max| over the quad is `amax`.  Writes the lane's codes
 // (fp8: 8 bytes; fp6: 6 bytes = element i at bits 6i.., i = 0..7, since the lane's first element sits at bit 48 * (lane & 3)
-// of the block) through `dst` = start of the lane's bytes, and returns the scale byte.
+// of the block; fp4: one dword, element i at bits 4i..) through `dst` = start of the lane's bytes, and returns the scale byte.
 template <int FMT>
 __device__ __forceinline__ uint32_t mx_quant8(const float* v, float amax, uint8_t* dst) {
     uint32_t sbyte = 127u;
@@ -46,6 +58,12 @@ __device__ __forceinline__ uint32_t mx_quant8(const float* v, float amax, uint8_
         if (amax == 0.0f) w[0] = w[1] = 0u;                                            // -0 inputs: all-zero codes
         u32x2 o; o[0] = w[0]; o[1] = w[1];
         *reinterpret_cast<u32x2*>(dst) = o;
+    } else if constexpr (FMT == MX_E2M1) {
+        uint32_t bits = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) bits |= f32_to_e2m1(v[i] * inv) << (4 * i);
+        if (amax == 0.0f) bits = 0;
+        *reinterpret_cast<uint32_t*>(dst) = bits;
     } else {
         uint64_t bits = 0;
 #pragma unroll

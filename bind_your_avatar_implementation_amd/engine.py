@@ -94,8 +94,10 @@ class DenoiseEngine:
         # MX weights (enable_mx_weights; API only): the selected Linears on OCP MX operands ("mxfp6" / "mxfp8", 32-element
         # blocks with e8m0 scales, quantised by the instruction's own block scales -- include/bya.h, "MX weights")
         self.mx_fmt = getattr(model, "_mx_weights", None)
+        self.mx_wfmt = None                                  # the weights' format: the activations', or "mxfp4" (e2m1)
         if self.mx_fmt is not None:
-            ops.mx_fmt_code(self.mx_fmt)
+            self.mx_wfmt = getattr(model, "_mx_weight_format", None) or self.mx_fmt
+            ops.mx_fmt_pair(self.mx_fmt, self.mx_wfmt)
             if self.fp8_weights:
                 raise ValueError("fp8 weights (enable_fp8_weights / BYA_FP8_WEIGHTS) and MX weights (enable_mx_weights) "
                                  "are both requested: enable one of them")
@@ -220,7 +222,7 @@ class DenoiseEngine:
             for k in FP8_LINEARS:
                 ws = source[k]() if k in keep else None
                 if ws is not None:
-                    self.wmx[k] = [ops.quantize_mx(w.contiguous(), self.mx_fmt) for w in ws]
+                    self.wmx[k] = [ops.quantize_mx(w.contiguous(), self.mx_wfmt) for w in ws]
         pe = getattr(m.patch_embed, "pos_embedding", None)
         use_pe = (not self.cfg.use_rotary_positional_embeddings) or self.cfg.use_learned_positional_embeddings
         self.pos_embedding = pe[0] if (pe is not None and use_pe) else None
@@ -332,7 +334,7 @@ class DenoiseEngine:
                 quantised = ops.quantize_mx(a, self.mx_fmt, *self._amx(a.shape))
             codes, sa = quantised
             wc, sw = self.wmx[which][i]
-            return ops.gemm_mx(codes, sa.view(*a.shape[:-1], -1), wc, sw, out, self.mx_fmt, **kw)
+            return ops.gemm_mx(codes, sa.view(*a.shape[:-1], -1), wc, sw, out, self.mx_fmt, w_fmt=self.mx_wfmt, **kw)
         if self.w8 is None or which not in self.w8:
             return ops.gemm(a, w, out, **kw)
         if quantised is None:

@@ -594,9 +594,11 @@ def gemm_fp8_plan(a8, a_scale, w8, w_scale, out, bias=None, res=None, gate0=None
 
 
 
-# OCP MX element formats (include/bya.h, "MX weights"): name -> the matrix instruction's format code, element bits
+# OCP MX element formats (include/bya.h, "MX weights"): name -> the matrix instruction's format code, element bits.
+# MX_FORMATS: what activations (and weights) may be; MX_WEIGHT_FORMATS: what weights may be -- e2m1 is theirs alone
 MX_FORMATS = {"mxfp8": 0, "mxfp6": 2}
-MX_BITS = {"mxfp8": 8, "mxfp6": 6}
+MX_WEIGHT_FORMATS = {**MX_FORMATS, "mxfp4": 4}
+MX_BITS = {"mxfp8": 8, "mxfp6": 6, "mxfp4": 4}
 
 
 def mx_fmt_code(fmt):
@@ -605,16 +607,32 @@ def mx_fmt_code(fmt):
     return MX_FORMATS[fmt]
 
 
+def mx_weight_fmt_code(fmt):
+    if fmt not in MX_WEIGHT_FORMATS:
+        raise ValueError(f"MX weight format {fmt!r}: expected one of {sorted(MX_WEIGHT_FORMATS)}")
+    return MX_WEIGHT_FORMATS[fmt]
+
+
+def mx_fmt_pair(fmt, w_fmt):
+    """(activation code, weight code) of a GEMM; weights in the activations' format or in "mxfp4"."""
+    a = mx_fmt_code(fmt)
+    w = a if w_fmt is None else mx_weight_fmt_code(w_fmt)
+    if w not in (a, MX_WEIGHT_FORMATS["mxfp4"]):
+        raise ValueError(f"MX weight format {w_fmt!r} under {fmt!r} activations: expected {fmt!r} or 'mxfp4'")
+    return a, w
+
+
 def mx_code_bytes(K, fmt):
     """Bytes of one row of K MX codes (no padding)."""
+    mx_weight_fmt_code(fmt)
     return K * MX_BITS[fmt] // 8
 
 
 def quantize_mx(x, fmt="mxfp6", codes=None, scales=None):
     """OCP MX block quantisation of a bf16 matrix [(B,) M, K] -> (uint8 codes [.., M, K * bits / 8], uint8 e8m0 scales
-    [.., M, K / 32])."""
+    [.., M, K / 32]).  ``fmt`` "mxfp4" (e2m1) is a weight format: no GEMM takes it as its activations."""
     lib = _hip.load()
-    code = mx_fmt_code(fmt)
+    code = mx_weight_fmt_code(fmt)
     b, M, K, bs, ldx = _mat(x, "x")
     if b > 1 and bs != M * ldx:
         raise ValueError("quantize_mx: batch entries must be evenly stacked rows")
@@ -631,7 +649,8 @@ def quantize_mx(x, fmt="mxfp6", codes=None, scales=None):
     return codes, scales
 
 
-def _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, res, gate_split, gate_batch_stride, act, split, alpha, plan=False):
+def _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
+             plan=False):
     if a_scales.dim() == 2:
         ab, (M, KS) = 1, a_scales.shape
     else:
@@ -640,14 +659,14 @@ def _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, res, gate_split, ga
     ob, Mo, N, c_bs, ldc = _mat(out, "out", plan)
     if split is not None:
         N = w_codes.shape[0]
-    rb_ = mx_code_bytes(K, fmt)
+    rb_, rbw = mx_code_bytes(K, fmt), mx_code_bytes(K, w_fmt or fmt)
     assert a_codes.dtype == w_codes.dtype == a_scales.dtype == w_scales.dtype == torch.uint8
     assert a_codes.is_contiguous() and w_codes.is_contiguous() and a_scales.is_contiguous() and w_scales.is_contiguous()
-    assert a_codes.numel() == ab * M * rb_ and w_codes.shape == (N, rb_) and w_scales.shape == (N, KS)
+    assert a_codes.numel() == ab * M * rb_ and w_codes.shape == (N, rbw) and w_scales.shape == (N, KS)
     assert (ab, M) == (ob, Mo)
     d = GemmDesc()
     d.M, d.N, d.K, d.batch = M, N, K, ab
-    d.lda, d.ldw, d.ldc = rb_, rb_, ldc
+    d.lda, d.ldw, d.ldc = rb_, rbw, ldc
     d.a_batch_stride, d.c_batch_stride = M * rb_, c_bs
     d.ldres, d.res_batch_stride = 0, 0
     if res is not None:
@@ -662,31 +681,41 @@ def _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, res, gate_split, ga
 
 
 def gemm_mx(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, res=None, gate0=None, gate1=None,
-            gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0):
-    """out = res + gate * act(A @ W.T + bias) with both operands in MX form (``quantize_mx``); K is read off the scales."""
+            gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0, w_fmt=None):
+    """out = res + gate * act(A @ W.T + bias) with both operands in MX form (``quantize_mx``); K is read off the scales.
+    ``fmt``: the activations' format; ``w_fmt``: the weights' (None = the same, or "mxfp4": bya_gemm_mx_mixed)."""
     lib = _hip.load()
-    code = mx_fmt_code(fmt)
-    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, res, gate_split, gate_batch_stride, act, split, alpha)
+    code, wcode = mx_fmt_pair(fmt, w_fmt)
+    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha)
     ab, M, N, K = d.batch, d.M, d.N, d.K
-    name = "bya_gemm_mx"
+    mixed = wcode != code
+    name = "bya_gemm_mx_mixed" if mixed else "bya_gemm_mx"
     if _SHAPE_LABELS:
-        name += f":{fmt}:{ab}x{M}x{N}x{K}:{act or 'none'}{'+gate' if gate0 is not None else ''}{'+res' if res is not None else ''}"
+        name += f":{fmt + '*' + w_fmt if mixed else fmt}:{ab}x{M}x{N}x{K}:{act or 'none'}{'+gate' if gate0 is not None else ''}{'+res' if res is not None else ''}"
     tok = _begin(name, 2.0 * ab * M * N * K)
-    check(lib.bya_gemm_mx(_p(a_codes), _p(a_scales), _p(w_codes), _p(w_scales), _p(bias), _p(out), _p(res), _p(gate0),
-                          _p(gate1), ctypes.byref(d), code, _stream()), "bya_gemm_mx")
+    args = (_p(a_codes), _p(a_scales), _p(w_codes), _p(w_scales), _p(bias), _p(out), _p(res), _p(gate0), _p(gate1),
+            ctypes.byref(d))
+    if mixed:
+        check(lib.bya_gemm_mx_mixed(*args, code, wcode, _stream()), "bya_gemm_mx_mixed")
+    else:
+        check(lib.bya_gemm_mx(*args, code, _stream()), "bya_gemm_mx")
     _end(tok)
     return out
 
 
 def gemm_mx_plan(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, res=None, gate0=None, gate1=None,
-                 gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0):
-    """What ``gemm_mx`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 only)."""
+                 gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0, w_fmt=None):
+    """What ``gemm_mx`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations only)."""
     lib = _hip.load()
-    code = mx_fmt_code(fmt)
-    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, res, gate_split, gate_batch_stride, act, split, alpha, plan=True)
+    code, wcode = mx_fmt_pair(fmt, w_fmt)
+    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
+                 plan=True)
     p, q = _hip.GemmPlan(), _plan_p
-    check(lib.bya_gemm_mx_plan(q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), q(res), q(gate0),
-                               q(gate1), ctypes.byref(d), code, ctypes.byref(p)), "bya_gemm_mx_plan")
+    args = (q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), q(res), q(gate0), q(gate1), ctypes.byref(d))
+    if wcode != code:
+        check(lib.bya_gemm_mx_mixed_plan(*args, code, wcode, ctypes.byref(p)), "bya_gemm_mx_mixed_plan")
+    else:
+        check(lib.bya_gemm_mx_plan(*args, code, ctypes.byref(p)), "bya_gemm_mx_plan")
     return _plan_dict(p)
 
 

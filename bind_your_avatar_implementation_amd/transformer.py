@@ -380,18 +380,25 @@ class BindyouravatarTransformer3DModel(nn.Module):
         self.invalidate_engine()
         return self
 
-    def enable_mx_weights(self, fmt: str = "mxfp6", enabled: bool = True, linears=None):
+    def enable_mx_weights(self, fmt: str = "mxfp6", enabled: bool = True, linears=None, weight_format=None):
         """Run the selected Linears on OCP MX operands: 32-element blocks along K with one e8m0 scale each, applied by
         gfx950's block-scaled matrix instruction (include/bya.h, "MX weights").  ``fmt``: "mxfp6" (e2m3 elements, the
         instruction's fastest dense rate) or "mxfp8" (e4m3 elements, the more accurate).  Weights are quantised when the
         engine packs them, activations per block on the fly (by the AdaLN LayerNorm itself where it feeds the Linear).
         ``linears``: as for enable_fp8_weights (a subset of engine.FP8_LINEARS or "all"; default engine.FP8_DEFAULT).
-        Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference counterpart (the
-        reference is bf16/fp16 only); returns self."""
-        from .ops import MX_FORMATS
+        ``weight_format``: the weights' element format -- None or ``fmt`` (the same as the activations), or "mxfp4" (e2m1
+        elements, 4.25 bits per parameter) under the activations of ``fmt``; no other combination, and "mxfp4" is never an
+        activation format.  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
+        counterpart (the reference is bf16/fp16 only); returns self."""
+        from .ops import MX_FORMATS, MX_WEIGHT_FORMATS
         if fmt not in MX_FORMATS:
             raise ValueError(f"MX format {fmt!r}: expected one of {sorted(MX_FORMATS)}")
+        if weight_format is not None and weight_format not in MX_WEIGHT_FORMATS:
+            raise ValueError(f"MX weight format {weight_format!r}: expected one of {sorted(MX_WEIGHT_FORMATS)}")
+        if weight_format not in (None, fmt, "mxfp4"):
+            raise ValueError(f"MX weight format {weight_format!r} under {fmt!r} activations: expected {fmt!r} or 'mxfp4'")
         self._mx_weights = fmt if enabled else None
+        self._mx_weight_format = weight_format if enabled else None
         self._mx_linears = (linears if isinstance(linears, str) else tuple(linears)) if linears else None
         self.invalidate_engine()
         return self

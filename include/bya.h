@@ -162,7 +162,7 @@ int bya_gemm_workspace_status(int32_t* timeouts, hipStream_t stream);
 #define BYA_GEMM_PATH_T128X64 0   /* 128 x 64 tiles, 4 waves (option gemm_tile = 0; N <= 64) */
 #define BYA_GEMM_PATH_T128X128 1  /* 128 x 128 tiles, 4 waves (gemm_tile = 1); bya_gemm_fp8 / bya_gemm_mx: their 128 x 128 kernel */
 #define BYA_GEMM_PATH_T256X128 2  /* 256 x 128 tiles, 8 waves (gemm_tile = 2) */
-#define BYA_GEMM_PATH_T256X256 3  /* 256 x 256 tiles, 8 waves (gemm_tile = 3); bya_gemm_mx: the e2m3 256 x 256 kernel */
+#define BYA_GEMM_PATH_T256X256 3  /* 256 x 256 tiles, 8 waves (gemm_tile = 3); bya_gemm_mx: the 256 x 256 kernel of e2m3 activations */
 #define BYA_GEMM_PATH_P256 4      /* persistent 256 x 256 (csrc/gemm_v4.hip); bya_gemm_fp8: csrc/gemm_fp8_v4.hip */
 #define BYA_GEMM_PATH_P128 5      /* persistent 128 x 256 (csrc/gemm_v5.hip) */
 #define BYA_GEMM_PATH_P128S 6     /* persistent 128 x 256 with loader waves (csrc/gemm_v6.hip) */
@@ -228,7 +228,12 @@ int bya_layernorm_fp8(const void* x, void* q, float* q_scale, const void* w, con
  *                    largest finite 7.5, 24 bytes per block: element i at bits 6i .. 6i+5 of the block's 192-bit
  *                    little-endian string (least significant bit first: the order v_mfma_scale_f32_16x16x128_f8f6f4
  *                    reads from its six operand VGPRs, checked on exact data).
- *   Storage is the plain row-major order in both formats; the GEMM kernel arranges the operand VGPRs per format
+ *   BYA_MX_E2M1 = 4: OCP e2m1 (1 sign, 2 exponent bits of bias 1, 1 mantissa bit, no inf / NaN; magnitudes 0, 0.5, 1, 1.5,
+ *                    2, 3, 4, 6), emax_elem = 2, largest finite 6, 16 bytes per block: element i in bits 4 (i % 2) .. +3 of
+ *                    byte i / 2, low nibble first (the order the instruction reads from its four operand VGPRs, measured
+ *                    on exact data: tests/test_mxfp4_gpu.py).  WEIGHTS only: bya_quantize_mx writes it, bya_gemm_mx_mixed
+ *                    multiplies it with e4m3 or e2m3 activations; e2m1 activations are not offered.
+ *   Storage is the plain row-major order in every format; the GEMM kernel arranges the operand VGPRs per format
  *   (csrc/gemm_mx.hip: for e4m3 the instruction's 32-k block spans two 16-byte pieces of different lanes).
  *
  * Scale of block b of row m (amax = max |x| over the block, taken on the bf16 values):
@@ -248,9 +253,13 @@ int bya_layernorm_fp8(const void* x, void* q, float* q_scale, const void* w, con
  *   descriptor and epilogue as bya_gemm_bf16; lda / ldw / a_batch_stride count BYTES of codes; a_scales is
  *   [batch * M, K / 32], w_scales [N, K / 32] (dense).  Both operands use the same element format.
  *   Requirements: K % 128 == 0, N % 4 == 0, lda / ldw % 16 == 0, A / W 16-byte aligned, a_scales / w_scales 4-byte aligned,
- *   batch * M * K / 32 < 2^31; act in {NONE, GELU_TANH(_IEEE)}.
+ *   batch * M * K / 32 < 2^31; act in {NONE, GELU_TANH(_IEEE)}.  fmt = BYA_MX_E2M1: BYA_ERR_SHAPE.
+ * bya_gemm_mx_mixed:  bya_gemm_mx with a format per operand (the instruction's cbsz / blgp): a_fmt in {E4M3, E2M3};
+ *   w_fmt == a_fmt is exactly bya_gemm_mx, w_fmt == BYA_MX_E2M1 multiplies 4-bit weights (codes [N, K / 2]) with the same
+ *   activations; every other pair: BYA_ERR_UNSUPPORTED.  lda / ldw are checked against each operand's own row bytes.  The
+ *   kernel (tile, ring) follows the activation format.
  * --------------------------------------------------------------------------------------------- */
-enum { BYA_MX_E4M3 = 0, BYA_MX_E2M3 = 2 };
+enum { BYA_MX_E4M3 = 0, BYA_MX_E2M3 = 2, BYA_MX_E2M1 = 4 };
 int bya_quantize_mx(const void* x, void* codes, void* scales, int32_t M, int32_t K, int64_t ldx, int32_t fmt,
                     hipStream_t stream);
 int bya_layernorm_mx(const void* x, void* q, void* q_scales, const void* w, const void* b, const void* shift0,
@@ -264,6 +273,13 @@ int bya_gemm_mx(const void* A, const void* a_scales, const void* W, const void* 
 int bya_gemm_mx_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
                      const void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* desc,
                      int32_t fmt, bya_gemm_plan* plan);
+int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, void* C,
+                      const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* desc, int32_t a_fmt,
+                      int32_t w_fmt, hipStream_t stream);
+/* its kernel: path T128X128, or T256X256 for e2m3 activations (bya_gemm_mx_plan's rule, whatever w_fmt) */
+int bya_gemm_mx_mixed_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                           const void* C, const void* res, const void* gate0, const void* gate1,
+                           const bya_gemm_desc* desc, int32_t a_fmt, int32_t w_fmt, bya_gemm_plan* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Small-M linear (M <= 8 rows):  out[m,n] = sum_k f(x[m,k]) * W[n,k] + bias[n],  f = identity or SiLU.

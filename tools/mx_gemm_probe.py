@@ -5,7 +5,10 @@
   2. the headline step (49 x 480 x 720 -> 13 x 60 x 90 latents, 42 layers, 2 identities, eager) in steps/s per mode: three
      interleaved rounds of 5 timed steps each, the best round kept;
   3. the 42-layer output drift of each mode against the bf16 engine (rel. Frobenius; random-init weights).
-usage: python tools/mx_gemm_probe.py [out.json] [--gemm-only]"""
+--fp4: the same three sections for e2m1 weights (enable_mx_weights(fmt, weight_format="mxfp4"), bya_gemm_mx_mixed) against
+same-format weights, for both activation formats: GEMM time per shape in interleaved rounds, the step of the four MX modes
+in interleaved rounds, and each mode's drift against the bf16 engine (profiles/mx_fp4_probe.json).
+usage: python tools/mx_gemm_probe.py [out.json] [--gemm-only] [--fp4]"""
 import json
 import os
 import sys
@@ -35,6 +38,45 @@ def best_us(fn, reps=3, inner=10):
         torch.cuda.synchronize()
         best = min(best, e0.elapsed_time(e1) / inner * 1e3)
     return best
+
+
+def fp4_gemm_section(rounds=3):
+    """bya_gemm_mx_mixed with e2m1 weights next to bya_gemm_mx on the same activations; fraction of the ACTIVATION format's
+    peak (at which rate the mixed instruction issues is one of the things this measures)."""
+    out = {}
+    g = torch.Generator(device=dev).manual_seed(0)
+    for M in (17776, 2222):
+        for name, N, K, act, has_res in SHAPES:
+            a = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+            w = (torch.randn(N, K, device=dev, generator=g) * K ** -0.5).to(torch.bfloat16)
+            b = torch.randn(N, device=dev, generator=g).to(torch.bfloat16)
+            res = torch.randn(M, N, device=dev, generator=g).to(torch.bfloat16) if has_res else None
+            c = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+            wq = {f: ops.quantize_mx(w, f) for f in ("mxfp8", "mxfp6", "mxfp4")}
+            runs = {}
+            for f in ("mxfp8", "mxfp6"):
+                ac, asc = ops.quantize_mx(a, f)
+                for wf in (f, "mxfp4"):
+                    wc, wsc = wq[wf]
+                    runs[f if wf == f else f + "*mxfp4"] = (
+                        lambda ac=ac, asc=asc, wc=wc, wsc=wsc, f=f, wf=wf:
+                        ops.gemm_mx(ac, asc, wc, wsc, c, f, bias=b, res=res, act=act, w_fmt=wf))
+            entry = {"M": M, "N": N, "K": K}
+            flop = 2.0 * M * N * K
+            us = {mode: 1e30 for mode in runs}
+            for _ in range(rounds):                                  # interleaved: every mode once per round
+                for mode, fn in runs.items():
+                    us[mode] = min(us[mode], best_us(fn, reps=1))
+            for mode in runs:
+                tf = flop / us[mode] * 1e-6
+                entry[mode] = {"us": round(us[mode], 1), "tflops": round(tf, 1),
+                               "frac_of_peak": round(tf / PEAK[mode.split("*")[0]], 3)}
+            key = f"{name}@{M}"
+            out[key] = entry
+            print(key, json.dumps(entry), flush=True)
+            del a, w, res, c, wq, runs
+            torch.cuda.empty_cache()
+    return out
 
 
 def gemm_section():
@@ -75,7 +117,7 @@ def gemm_section():
     return out
 
 
-def step_section(steps=5, warmup=2, rounds=3):
+def step_section(steps=5, warmup=2, rounds=3, fp4=False):
     from bind_your_avatar_implementation_amd import BindyouravatarTransformer3DModel
     from bind_your_avatar_implementation_amd.synth import synth_inputs
     kw = dict(num_attention_heads=48, attention_head_dim=64, in_channels=48, out_channels=16, num_layers=42,
@@ -91,6 +133,11 @@ def step_section(steps=5, warmup=2, rounds=3):
     inp["id_vit_hidden"] = [[t.to(dev, torch.bfloat16) for t in l] for l in d["id_vit_hidden"]]
     modes = {"bf16": lambda: None, "fp8": lambda: model.enable_fp8_weights(),
              "mxfp8": lambda: model.enable_mx_weights("mxfp8"), "mxfp6": lambda: model.enable_mx_weights("mxfp6")}
+    if fp4:
+        modes = {"bf16": lambda: None}
+        for f in ("mxfp8", "mxfp6"):
+            modes[f] = lambda f=f: model.enable_mx_weights(f)
+            modes[f + "*mxfp4"] = lambda f=f: model.enable_mx_weights(f, weight_format="mxfp4")
     res, outs = {}, {}
     # rounds x modes, interleaved (each mode rebuilds its engine every round); the best round per mode is kept
     for rnd in range(rounds):
@@ -116,9 +163,11 @@ def step_section(steps=5, warmup=2, rounds=3):
                 r["drift_vs_bf16_42_layers"] = float((outs[mode] - ref).norm() / ref.norm())
             print(rnd, mode, json.dumps(r), flush=True)
     # per-kernel time of the two MX steps' GEMMs and quantisers (kernel timers: one extra step each)
-    for mode in ("fp8", "mxfp6"):
+    for mode in (("mxfp6*mxfp4", "mxfp8*mxfp4") if fp4 else ("fp8", "mxfp6")):
         model.enable_fp8_weights(mode == "fp8")
-        model.enable_mx_weights(enabled=mode == "mxfp6")
+        model.enable_mx_weights(enabled=False)
+        if mode != "fp8":
+            modes[mode]()
         model(return_dict=False, denoise_step=0, **inp)
         ops.enable_kernel_timers()
         model(return_dict=False, denoise_step=0, **inp)
@@ -132,9 +181,10 @@ def step_section(steps=5, warmup=2, rounds=3):
 
 def main():
     out_path = next((a for a in sys.argv[1:] if not a.startswith("--")), None)
-    result = {"device": torch.cuda.get_device_name(0), "gemm": gemm_section()}
+    fp4 = "--fp4" in sys.argv
+    result = {"device": torch.cuda.get_device_name(0), "gemm": fp4_gemm_section() if fp4 else gemm_section()}
     if "--gemm-only" not in sys.argv:
-        result["step"] = step_section()
+        result["step"] = step_section(fp4=fp4)
     if out_path:
         with open(out_path, "w") as f:
             json.dump(result, f, indent=1)
