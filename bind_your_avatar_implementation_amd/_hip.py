@@ -92,6 +92,9 @@ SIGNATURES = {
     "bya_gemm_mx_mixed": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _i32, _i32, _vp],
     "bya_gemm_mx_mixed_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _i32, _i32,
                                _c.POINTER(GemmPlan)],
+    "bya_gemm_mx_quant": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _i32, _i32, _i32, _vp],
+    "bya_gemm_mx_quant_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _i32, _i32, _i32,
+                               _c.POINTER(GemmPlan)],
     "bya_linear_small_m": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "bya_timestep_features": [_vp, _vp, _i32, _i32, _i32, _f32, _vp],
     "bya_layernorm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,

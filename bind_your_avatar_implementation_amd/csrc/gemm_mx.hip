@@ -131,10 +131,128 @@ __device__ __forceinline__ i32x8 lds_frag_mx(const char* tile, int row, int g) {
     }
 }
 
-// FMT_A: activations (the instruction's B operand, blgp); FMT_W: weights (its A operand, cbsz)
-template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
-__global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_kernel(GemmArgs p, const uint8_t* __restrict__ sa,
-                                                                         const uint8_t* __restrict__ sw, int GM) {
+// ---- the quantising epilogue (bya_gemm_mx_quant): the tile leaves as MX codes + scale bytes instead of bf16.
+// Per element  v = bf16( alpha * act(acc + rowscale * bias) )  -- the value the bf16 epilogue stores and bya_quantize_mx reads
+// back --, then the block rule of mx_common.h on it (mx_quant8_bits: the quantisers' own arithmetic).  A 32-column block of
+// row m is the eight values of the four lanes fr + 16 fq, fq = 0..3, in the fragment pair i = 2 b, 2 b + 1: lane fq holds
+// elements 4 fq .. 4 fq + 3 (i even) and 16 + 4 fq .. + 3 (i odd) of the block.  Its |max| is the lane's own eight, then the
+// lane ^ 16 and lane ^ 32 partners (v_permlane16_swap / v_permlane32_swap; a maximum does not depend on the order).  Handed
+// to mx_quant8_bits as "elements 0..3 | 4..7", the low half of the result is the lane's four codes of the even fragment and
+// the high half those of the odd one: 4 bytes each at bytes 4 fq and 16 + 4 fq of an e4m3 block, 24 bits each at bytes 3 fq
+// and 12 + 3 fq of an e2m3 block.
+// Staging (the K-loop's ring is free after one barrier): both formats write ONE DWORD per four codes (e2m3: 24 bits, top byte
+// zero) at byte n_local of row m_local, rows BN + 16 bytes apart -- 36 or 68 dwords, so the 16 rows of a ds_write_b32's 32-lane
+// half fall on banks 4 r + fq (mod 32): 2-way, which costs a b32 write nothing.  Then the whole block reads the image back in
+// 16-byte pieces of OUTPUT row segments, thread t -> piece t % CH of row t / CH, and stores 16 bytes per lane: e4m3 pieces are
+// the staged bytes (one ds_read_b128), an e2m3 piece k of a 48-byte block pair is bits 128 k .. 128 k + 127 of the pair's
+// sixteen 24-bit words = words 5 k .. 5 k + 5 shifted down by 8 k bits.  The scale bytes ride behind the codes, [BM][BN / 32].
+template <int QOUT, int BN> struct MxQuantStage {
+    static constexpr int PITCH = BN + 16;                                   // bytes of a staged row of codes
+    static constexpr int CH = QOUT == MX_E4M3 ? BN / 16 : BN * 3 / 64;      // 16-byte pieces of an output row segment
+    __host__ __device__ static constexpr int bytes(int BM) { return BM * PITCH + BM * (BN / 32); }
+};
+
+template <int ACT, int QOUT, int BM, int BN, int NI, int MI, int NTHREADS>
+__device__ __forceinline__ void epilogue_mx_quant(const GemmArgs& p, uint8_t* __restrict__ qs, int z, int m0, int n0,
+                                                  int ml, int nl, int fq, const f32x4 (&acc)[NI][MI], char* smem, int tid) {
+    using St = MxQuantStage<QOUT, BN>;
+    static_assert(QOUT == MX_E4M3 || QOUT == MX_E2M3, "activation formats only");
+    static_assert(NI % 2 == 0 && (BM * St::CH) % NTHREADS == 0, "whole blocks per wave, whole pieces per thread");
+    constexpr int PITCH = St::PITCH, CH = St::CH, SB = BN / 32;
+    uint8_t* sc = reinterpret_cast<uint8_t*>(smem) + BM * PITCH;
+    const bool has_bias = p.bias != nullptr, has_rs = p.bias_rowscale != nullptr;
+    float rs[MI];
+#pragma unroll
+    for (int j = 0; j < MI; ++j) {
+        const int m = m0 + ml + 16 * j;
+        rs[j] = has_rs ? p.bias_rowscale[(long long)z * p.M + (m < p.M ? m : 0)] : 1.0f;
+    }
+    u32x2 bv[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int n4 = n0 + nl + 16 * i;
+        bv[i] = has_bias ? *reinterpret_cast<const u32x2*>(p.bias + (n4 < p.N ? n4 : 0)) : u32x2{0u, 0u};
+    }
+    auto max16 = [](float x) {
+        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+        return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    };
+    auto max32 = [](float x) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+        return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    };
+    __syncthreads();                                     // every wave has read its last K-tile: the ring is free
+#pragma unroll
+    for (int b = 0; b < NI / 2; ++b) {
+#pragma unroll
+        for (int j = 0; j < MI; ++j) {
+            float v[8];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const u32x2 bb = bv[2 * b + h];
+                const float b4[4] = {bflo(bb[0]), bfhi(bb[0]), bflo(bb[1]), bfhi(bb[1])};
+                float t[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    t[e] = p.alpha * apply_act<ACT>(fmaf(rs[j], b4[e], acc[2 * b + h][j][e]), p.leaky);
+                const uint32_t r0 = pack2bf(t[0], t[1]), r1 = pack2bf(t[2], t[3]);      // the one rounding to bf16
+                v[4 * h] = bflo(r0); v[4 * h + 1] = bfhi(r0); v[4 * h + 2] = bflo(r1); v[4 * h + 3] = bfhi(r1);
+            }
+            float amax = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[e]));
+            amax = max32(max16(amax));
+            uint32_t sbyte;
+            const uint64_t bits = mx_quant8_bits<QOUT>(v, amax, sbyte);
+            const uint32_t lo = QOUT == MX_E4M3 ? (uint32_t)bits : (uint32_t)bits & 0xffffffu;
+            const uint32_t hi = QOUT == MX_E4M3 ? (uint32_t)(bits >> 32) : (uint32_t)(bits >> 24);
+            char* row = smem + (ml + 16 * j) * PITCH + nl + 32 * b;
+            *reinterpret_cast<uint32_t*>(row) = lo;
+            *reinterpret_cast<uint32_t*>(row + 16) = hi;
+            if (fq == 0) sc[(ml + 16 * j) * SB + (nl >> 5) + b] = (uint8_t)sbyte;
+        }
+    }
+    __syncthreads();
+    // columns of this tile inside N (N % 128 == 0: whole 128-column groups = whole pieces and whole scale dwords)
+    const int ncols = p.N - n0 < BN ? p.N - n0 : BN;
+    uint8_t* crow0 = reinterpret_cast<uint8_t*>(p.C) + (long long)z * p.c_bs + (long long)n0 * (QOUT == MX_E4M3 ? 8 : 6) / 8;
+#pragma unroll
+    for (int q = 0; q < BM * CH / NTHREADS; ++q) {
+        const int t = q * NTHREADS + tid, r = t / CH, c = t - r * CH;
+        const int m = m0 + r;
+        u32x4 o;
+        if constexpr (QOUT == MX_E4M3) {
+            o = *reinterpret_cast<const u32x4*>(smem + r * PITCH + c * 16);
+        } else {
+            const int pr = c / 3, k = c - pr * 3;
+            const uint32_t* d = reinterpret_cast<const uint32_t*>(smem + r * PITCH + pr * 64) + 5 * k;
+            const uint64_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4], d5 = d[5];
+            const uint64_t c0 = d0 | (d1 << 24) | (d2 << 48);
+            const uint64_t c1 = (d2 >> 16) | (d3 << 8) | (d4 << 32) | (d5 << 56);
+            const uint64_t c2 = d5 >> 8;
+            const int s = 8 * k;
+            const uint64_t o0 = k ? (c0 >> s) | (c1 << (64 - s)) : c0;
+            const uint64_t o1 = k ? (c1 >> s) | (c2 << (64 - s)) : c1;
+            o[0] = (uint32_t)o0; o[1] = (uint32_t)(o0 >> 32); o[2] = (uint32_t)o1; o[3] = (uint32_t)(o1 >> 32);
+        }
+        const bool ok = m < p.M && c * 16 < ncols * (QOUT == MX_E4M3 ? 8 : 6) / 8;
+        if (ok) *reinterpret_cast<u32x4*>(crow0 + (long long)m * p.ldc + c * 16) = o;
+    }
+    // scale bytes: one dword per row and 128 columns
+    for (int t = tid; t < BM * (SB / 4); t += NTHREADS) {
+        const int r = t / (SB / 4), w = t - r * (SB / 4);
+        const int m = m0 + r;
+        if (m < p.M && w * 128 < ncols)
+            *reinterpret_cast<uint32_t*>(qs + ((long long)z * p.M + m) * (p.N / 32) + n0 / 32 + 4 * w) =
+                *reinterpret_cast<const uint32_t*>(sc + r * SB + 4 * w);
+    }
+}
+
+// FMT_A: activations (the instruction's B operand, blgp); FMT_W: weights (its A operand, cbsz); QOUT < 0: the bf16 epilogue,
+// else the element format of the quantising one (qs = its scale bytes)
+template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N, int QOUT>
+__device__ __forceinline__ void gemm_mx_body(const GemmArgs& p, const uint8_t* __restrict__ sa, const uint8_t* __restrict__ sw,
+                                             int GM, uint8_t* __restrict__ qs) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NWAVES = WAVES_M * WAVES_N, RB_A = mx_tile_row_bytes(FMT_A), RB_W = mx_tile_row_bytes(FMT_W);
     constexpr int TILE_A = BM * RB_A, TILE_W = BN * RB_W, SCALES = (BM + BN) * 4, STAGE = TILE_A + TILE_W + SCALES;
@@ -223,10 +341,33 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_kernel(GemmArg
 
     // Lane holds C[m][n4 .. n4+3], m = m_base + 16 j, n4 = n_base + 16 i (W fragment = the instruction's A operand)
     const int m_base = m0 + wm * WM + fr, n_base = n0 + wn * WN + fq * 4;
-    auto run = [&](auto act_tag) {
-        epilogue_block<decltype(act_tag)::value, NI, MI, (NI * MI > 16 ? 1 : NI)>(p, z, m_base, n_base, acc);
-    };
-    dispatch_act_big(p.act, run);
+    if constexpr (QOUT < 0) {
+        auto run = [&](auto act_tag) {
+            epilogue_block<decltype(act_tag)::value, NI, MI, (NI * MI > 16 ? 1 : NI)>(p, z, m_base, n_base, acc);
+        };
+        dispatch_act_big(p.act, run);
+    } else {
+        static_assert(MxQuantStage<QOUT, BN>::bytes(BM) <= NST * STAGE, "the staged tile must fit the K-loop's ring");
+        auto run = [&](auto act_tag) {
+            epilogue_mx_quant<decltype(act_tag)::value, QOUT, BM, BN, NI, MI, 64 * NWAVES>(
+                p, qs, z, m0, n0, wm * WM + fr, wn * WN + fq * 4, fq, acc, smem, tid);
+        };
+        dispatch_act_big(p.act, run);
+    }
+}
+
+template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_kernel(GemmArgs p, const uint8_t* __restrict__ sa,
+                                                                         const uint8_t* __restrict__ sw, int GM) {
+    gemm_mx_body<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, -1>(p, sa, sw, GM, nullptr);
+}
+
+// ... with the quantising epilogue: C = codes (ldc, c_bs in bytes), qs = scale bytes [batch * M, N / 32]
+template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N, int QOUT>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_quant_kernel(GemmArgs p, const uint8_t* __restrict__ sa,
+                                                                               const uint8_t* __restrict__ sw, int GM,
+                                                                               uint8_t* __restrict__ qs) {
+    gemm_mx_body<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, QOUT>(p, sa, sw, GM, qs);
 }
 
 template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
@@ -239,6 +380,22 @@ int launch_mx(const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, int batch
     if (bya_allow_big_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
     BYA_LAUNCH(kern, grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a, sa, sw, MX_GROUP_M);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
+int launch_mx_quant(const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int out_fmt, int batch,
+                    hipStream_t s) {
+    const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
+    dim3 grid(tiles_m * tiles_n, 1, batch);
+    const size_t lds = (size_t)mx_stages(FMT_A) * (BM * (mx_tile_row_bytes(FMT_A) + 4) + BN * (mx_tile_row_bytes(FMT_W) + 4));
+    auto go = [&](auto kern, std::atomic<unsigned long long>& attr_done) {
+        if (bya_allow_big_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done) != BYA_OK) return (int)BYA_ERR_LAUNCH;
+        BYA_LAUNCH(kern, grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a, sa, sw, MX_GROUP_M, qs);
+        return hipGetLastError() == hipSuccess ? (int)BYA_OK : (int)BYA_ERR_LAUNCH;
+    };
+    static std::atomic<unsigned long long> done8{0}, done6{0};
+    if (out_fmt == MX_E4M3) return go(gemm_mx_quant_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, MX_E4M3>, done8);
+    return go(gemm_mx_quant_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, MX_E2M3>, done6);
 }
 
 // ---- standalone quantiser: one lane per 8 consecutive elements (one 16-byte load), a lane quad per block.
@@ -363,6 +520,61 @@ extern "C" int bya_gemm_mx_mixed_plan(const void* A, const void* a_scales, const
     if (!chunks) return BYA_ERR_UNSUPPORTED;
     p->path = mx_path(a, d->batch, a_fmt);
     p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = chunks;
+    return BYA_OK;
+}
+
+namespace {
+// bya_gemm_mx_quant's arguments -> GemmArgs (C = the codes; ldc, c_bs in bytes); BYA_OK or the error that rejects them
+int mx_quant_args(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                  const void* q_codes, const void* q_scales, const bya_gemm_desc* d, int32_t a_fmt, int32_t w_fmt,
+                  int32_t out_fmt, GemmArgs* out) {
+    if (!A || !W || !a_scales || !w_scales || !q_codes || !q_scales || !d) return BYA_ERR_SHAPE;
+    if (out_fmt != MX_E4M3 && out_fmt != MX_E2M3) return BYA_ERR_UNSUPPORTED;       // e2m1 is never an activation format
+    if ((a_fmt != MX_E4M3 && a_fmt != MX_E2M3) || (w_fmt != a_fmt && w_fmt != MX_E2M1)) return BYA_ERR_UNSUPPORTED;
+    if (d->n_split != 0) return BYA_ERR_UNSUPPORTED;                                 // a codes tensor has no column split
+    if (d->N <= 0 || d->N % 128 != 0) return BYA_ERR_SHAPE;                          // the result is a legal K
+    const long long row_bytes = (long long)d->N / 32 * mx_block_bytes(out_fmt);
+    if (d->ldc < row_bytes) return BYA_ERR_SHAPE;
+    if (d->M > 0 && d->batch > 0 && (long long)d->batch * d->M * (d->N / 32) >= (1LL << 31)) return BYA_ERR_SHAPE;
+    if (d->ldc % 16 || d->c_batch_stride % 16 || ((uintptr_t)q_codes & 15) || ((uintptr_t)q_scales & 3)) return BYA_ERR_ALIGN;
+    bya_gemm_desc e = *d;                                // the operand side: bya_gemm_mx_mixed's own checks
+    e.ldres = 0; e.res_batch_stride = 0; e.gate_batch_stride = 0; e.gate_split = 0; e.c_split_stride = 0;
+    return mx_args(A, a_scales, W, w_scales, bias, q_codes, nullptr, nullptr, nullptr, &e, a_fmt, w_fmt, out);
+}
+}  // namespace
+
+// bya_gemm_mx_mixed whose epilogue writes the MX codes and scale bytes of its bf16-rounded result: byte for byte
+// bya_gemm_mx_mixed followed by bya_quantize_mx(out_fmt), without the bf16 tensor.  The stores are plain 64-bit-addressed
+// vector stores, so no launch is cut into row chunks.
+extern "C" int bya_gemm_mx_quant(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                                 void* q_codes, void* q_scales, const bya_gemm_desc* d, int32_t a_fmt, int32_t w_fmt,
+                                 int32_t out_fmt, hipStream_t stream) {
+    GemmArgs a;
+    const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
+    if (rc != BYA_OK) return rc;
+    const uint8_t* sa = (const uint8_t*)a_scales;
+    const uint8_t* sw = (const uint8_t*)w_scales;
+    uint8_t* qs = (uint8_t*)q_scales;
+    const bool big = mx_path(a, d->batch, a_fmt) == BYA_GEMM_PATH_T256X256, w4 = w_fmt == MX_E2M1;
+    if (a_fmt == MX_E4M3)
+        return w4 ? launch_mx_quant<MX_E4M3, MX_E2M1, 128, 128, 2, 2>(a, sa, sw, qs, out_fmt, d->batch, stream)
+                  : launch_mx_quant<MX_E4M3, MX_E4M3, 128, 128, 2, 2>(a, sa, sw, qs, out_fmt, d->batch, stream);
+    if (big)
+        return w4 ? launch_mx_quant<MX_E2M3, MX_E2M1, 256, 256, 4, 2>(a, sa, sw, qs, out_fmt, d->batch, stream)
+                  : launch_mx_quant<MX_E2M3, MX_E2M3, 256, 256, 4, 2>(a, sa, sw, qs, out_fmt, d->batch, stream);
+    return w4 ? launch_mx_quant<MX_E2M3, MX_E2M1, 128, 128, 2, 2>(a, sa, sw, qs, out_fmt, d->batch, stream)
+              : launch_mx_quant<MX_E2M3, MX_E2M3, 128, 128, 2, 2>(a, sa, sw, qs, out_fmt, d->batch, stream);
+}
+
+extern "C" int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                      const void* bias, const void* q_codes, const void* q_scales, const bya_gemm_desc* d,
+                                      int32_t a_fmt, int32_t w_fmt, int32_t out_fmt, bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    GemmArgs a;
+    const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
+    if (rc != BYA_OK) return rc;
+    p->path = mx_path(a, d->batch, a_fmt);
+    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = 1;
     return BYA_OK;
 }
 

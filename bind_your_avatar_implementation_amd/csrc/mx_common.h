@@ -36,12 +36,13 @@ __device__ __forceinline__ uint32_t f32_to_e2m1(float v) {
     return sign | c;
 }
 
-// Quantise the 8 values of this lane's share of a 32-block whose |max| over the quad is `amax`.  Writes the lane's codes
-// (fp8: 8 bytes; fp6: 6 bytes = element i at bits 6i.., i = 0..7, since the lane's first element sits at bit 48 * (lane & 3)
-// of the block; fp4: one dword, element i at bits 4i..) through `dst` = start of the lane's bytes, and returns the scale byte.
+// The codes of 8 values of a 32-block whose |max| is `amax`, in registers: element i at bits 8i.. (fp8: 64 bits), 6i.. (fp6:
+// 48 bits) or 4i.. (fp4: 32 bits) of the result; the block's scale byte in `sbyte`.  THE arithmetic of the format: the
+// standalone and the LayerNorm-fused quantiser store these bits as they are (mx_quant8), the GEMM's quantising epilogue
+// (gemm_mx.hip) stores their two halves, which sit 16 elements apart in its accumulator layout.
 template <int FMT>
-__device__ __forceinline__ uint32_t mx_quant8(const float* v, float amax, uint8_t* dst) {
-    uint32_t sbyte = 127u;
+__device__ __forceinline__ uint64_t mx_quant8_bits(const float* v, float amax, uint32_t& sbyte) {
+    sbyte = 127u;
     float inv = 0.0f;
     if (amax > 0.0f) {
         int e = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127 - mx_emax(FMT);    // subnormal amax: far below -127
@@ -56,19 +57,35 @@ __device__ __forceinline__ uint32_t mx_quant8(const float* v, float amax, uint8_
             w[h] = f32_to_e4m3(v[4 * h] * inv) | (f32_to_e4m3(v[4 * h + 1] * inv) << 8) |
                    (f32_to_e4m3(v[4 * h + 2] * inv) << 16) | (f32_to_e4m3(v[4 * h + 3] * inv) << 24);
         if (amax == 0.0f) w[0] = w[1] = 0u;                                            // -0 inputs: all-zero codes
-        u32x2 o; o[0] = w[0]; o[1] = w[1];
-        *reinterpret_cast<u32x2*>(dst) = o;
+        return (uint64_t)w[0] | ((uint64_t)w[1] << 32);
     } else if constexpr (FMT == MX_E2M1) {
         uint32_t bits = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) bits |= f32_to_e2m1(v[i] * inv) << (4 * i);
         if (amax == 0.0f) bits = 0;
-        *reinterpret_cast<uint32_t*>(dst) = bits;
+        return bits;
     } else {
         uint64_t bits = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) bits |= (uint64_t)f32_to_e2m3(v[i] * inv) << (6 * i);
         if (amax == 0.0f) bits = 0;
+        return bits;
+    }
+}
+
+// Quantise the 8 values of this lane's share of a 32-block whose |max| over the quad is `amax`.  Writes the lane's codes
+// (fp8: 8 bytes; fp6: 6 bytes = element i at bits 6i.., i = 0..7, since the lane's first element sits at bit 48 * (lane & 3)
+// of the block; fp4: one dword, element i at bits 4i..) through `dst` = start of the lane's bytes, and returns the scale byte.
+template <int FMT>
+__device__ __forceinline__ uint32_t mx_quant8(const float* v, float amax, uint8_t* dst) {
+    uint32_t sbyte;
+    const uint64_t bits = mx_quant8_bits<FMT>(v, amax, sbyte);
+    if constexpr (FMT == MX_E4M3) {
+        u32x2 o; o[0] = (uint32_t)bits; o[1] = (uint32_t)(bits >> 32);
+        *reinterpret_cast<u32x2*>(dst) = o;
+    } else if constexpr (FMT == MX_E2M1) {
+        *reinterpret_cast<uint32_t*>(dst) = (uint32_t)bits;
+    } else {
         uint16_t* d16 = reinterpret_cast<uint16_t*>(dst);                               // 6 bytes at a 2-byte boundary
         d16[0] = (uint16_t)bits; d16[1] = (uint16_t)(bits >> 16); d16[2] = (uint16_t)(bits >> 32);
     }

@@ -101,6 +101,9 @@ class DenoiseEngine:
             if self.fp8_weights:
                 raise ValueError("fp8 weights (enable_fp8_weights / BYA_FP8_WEIGHTS) and MX weights (enable_mx_weights) "
                                  "are both requested: enable one of them")
+        # ... and ff.net.0's GEMM writes ff.net.2's MX operand itself (bya_gemm_mx_quant: byte for byte the GEMM + the 12288-wide
+        # quantiser) when both are MX Linears; enable_mx_weights(fuse_activation_quant=False) keeps the two launches
+        self.mx_fuse_quant = self.mx_fmt is not None and bool(getattr(model, "_mx_fuse_activation_quant", True))
         # the remaining A/B switches of the step, read ONCE here (round 4 looked them up in os.environ on every step / call)
         self.side_stream_conditioning = os.environ.get("BYA_INVARIANTS_SIDE_STREAM", "1") != "0"
         self.sp_allgather = os.environ.get("BYA_SP_ALLGATHER", "0") == "1"       # exchange A as a K/V all-gather (A/B)
@@ -342,6 +345,21 @@ class DenoiseEngine:
         a8, sa = quantised
         w8, sw = self.w8[which][i]
         return ops.gemm_fp8(a8.view(*a.shape), sa.view(*a.shape[:-1]), w8, sw, out, **kw)
+
+    def _ff_pair_fused(self):
+        """Whether ff.net.0's launch writes ff.net.2's MX operand (both MX Linears, and the switch on)."""
+        return self.mx_fuse_quant and self.wmx is not None and "ff1" in self.wmx and "ff2" in self.wmx
+
+    def _ff1_mx_quant(self, i, a, out_shape, bias, quantised=None):
+        """Block ``i``'s ff.net.0 + GELU(tanh) with the quantising epilogue: returns the (codes, scales) of its bf16-rounded
+        output in the ``_amx`` workspace of ``out_shape`` -- what ``quantize_mx`` of the bf16 output would hold."""
+        if quantised is None:
+            quantised = ops.quantize_mx(a, self.mx_fmt, *self._amx(a.shape))
+        codes, sa = quantised
+        wc, sw = self.wmx["ff1"][i]
+        oc, osc = self._amx(out_shape)
+        return ops.gemm_mx_quant(codes, sa.view(*a.shape[:-1], -1), wc, sw, oc, osc, self.mx_fmt, w_fmt=self.mx_wfmt,
+                                 out_fmt=self.mx_fmt, bias=bias, act="gelu_tanh")
 
     def _ln_linear(self, which, i, x, xn, norm, w, out, **kw):
         """LayerNorm(x) -> Linear for the perceiver / audio query projections (models/router.py:246-253,
@@ -805,10 +823,15 @@ class DenoiseEngine:
                     self._dit_linear("out", i, xn, at.to_out[0].weight, x, bias=at.to_out[0].bias, res=x, gate0=mo[:, 5 * D:],
                              gate1=mo[:, 2 * D:], gate_split=Tt_loc, gate_batch_stride=mbs)
                 else:
-                    self._dit_linear("ff1", i, xn, blk.ff.net[0].proj.weight, ff, bias=blk.ff.net[0].proj.bias, act="gelu_tanh",
-                                     quantised=xq)
+                    fq = None
+                    if self._ff_pair_fused():
+                        # the MLP pair is row-local: FF1 emits FF2's MX operand, the bf16 `ff` is neither written nor read
+                        fq = self._ff1_mx_quant(i, xn, ff.shape, blk.ff.net[0].proj.bias, xq)
+                    else:
+                        self._dit_linear("ff1", i, xn, blk.ff.net[0].proj.weight, ff, bias=blk.ff.net[0].proj.bias,
+                                         act="gelu_tanh", quantised=xq)
                     self._dit_linear("ff2", i, ff, blk.ff.net[2].weight, x, bias=blk.ff.net[2].bias, res=x, gate0=mo[:, 5 * D:],
-                             gate1=mo[:, 2 * D:], gate_split=Tt_loc, gate_batch_stride=mbs)
+                             gate1=mo[:, 2 * D:], gate_split=Tt_loc, gate_batch_stride=mbs, quantised=fq)
             if taps is not None:
                 taps[f"block{i}"] = x.clone()
 

@@ -719,6 +719,65 @@ def gemm_mx_plan(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=No
     return _plan_dict(p)
 
 
+def _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, act, alpha):
+    if a_scales.dim() == 2:
+        ab, (M, KS) = 1, a_scales.shape
+    else:
+        ab, M, KS = a_scales.shape
+    K, N = KS * 32, w_codes.shape[0]
+    rb_, rbw, rbo = mx_code_bytes(K, fmt), mx_code_bytes(K, w_fmt or fmt), mx_code_bytes(N, out_fmt)
+    for t in (a_codes, a_scales, w_codes, w_scales, out_codes, out_scales):
+        assert t.dtype == torch.uint8 and t.is_contiguous()
+    assert a_codes.numel() == ab * M * rb_ and w_codes.shape == (N, rbw) and w_scales.shape == (N, KS)
+    if N % 32 or out_codes.numel() != ab * M * rbo or out_scales.numel() != ab * M * (N // 32):
+        raise ValueError("gemm_mx_quant: out_codes / out_scales must hold [batch * M, N * bits / 8] and [batch * M, N / 32]")
+    d = GemmDesc()
+    d.M, d.N, d.K, d.batch = M, N, K, ab
+    d.lda, d.ldw, d.ldc = rb_, rbw, rbo
+    d.a_batch_stride, d.c_batch_stride = M * rb_, M * rbo
+    d.ldres, d.res_batch_stride = 0, 0
+    d.gate_batch_stride, d.gate_split, d.act = 0, 0, ACT[act]
+    d.n_split, d.c_split_stride = 0, 0
+    d.bias_rowscale, d.alpha = None, float(alpha)
+    return d
+
+
+def gemm_mx_quant(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt="mxfp6", w_fmt=None, out_fmt=None,
+                  bias=None, act=None, alpha=1.0):
+    """``quantize_mx(gemm_mx(...), out_fmt)`` in one launch (bya_gemm_mx_quant): the GEMM's epilogue writes the MX codes and
+    block scales of its bf16-rounded result, byte for byte what the two launches write, into the preallocated pair
+    ``out_codes`` [(B,) M, N * bits / 8], ``out_scales`` [(B,) M, N / 32].  ``out_fmt``: "mxfp8" or "mxfp6" (None = ``fmt``).
+    Returns ``(out_codes, out_scales)``: the ``quantised=`` pair of the next MX Linear."""
+    lib = _hip.load()
+    code, wcode = mx_fmt_pair(fmt, w_fmt)
+    out_fmt = fmt if out_fmt is None else out_fmt
+    ocode = mx_fmt_code(out_fmt)
+    d = _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, act, alpha)
+    ab, M, N, K = d.batch, d.M, d.N, d.K
+    name = "bya_gemm_mx_quant"
+    if _SHAPE_LABELS:
+        name += f":{fmt}*{w_fmt or fmt}>{out_fmt}:{ab}x{M}x{N}x{K}:{act or 'none'}"
+    tok = _begin(name, 2.0 * ab * M * N * K)
+    check(lib.bya_gemm_mx_quant(_p(a_codes), _p(a_scales), _p(w_codes), _p(w_scales), _p(bias), _p(out_codes), _p(out_scales),
+                                ctypes.byref(d), code, wcode, ocode, _stream()), "bya_gemm_mx_quant")
+    _end(tok)
+    return out_codes, out_scales
+
+
+def gemm_mx_quant_plan(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt="mxfp6", w_fmt=None, out_fmt=None,
+                       bias=None, act=None, alpha=1.0):
+    """What ``gemm_mx_quant`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations only)."""
+    lib = _hip.load()
+    code, wcode = mx_fmt_pair(fmt, w_fmt)
+    out_fmt = fmt if out_fmt is None else out_fmt
+    d = _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, act, alpha)
+    p, q = _hip.GemmPlan(), _plan_p
+    check(lib.bya_gemm_mx_quant_plan(q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out_codes), q(out_scales),
+                                     ctypes.byref(d), code, wcode, mx_fmt_code(out_fmt), ctypes.byref(p)),
+          "bya_gemm_mx_quant_plan")
+    return _plan_dict(p)
+
+
 def linear_small_m(x, w, bias, out, silu_in=False, act_out=None):
     """out[M<=8, N] = f(x) @ w.T + bias (weight-streaming kernel)."""
     lib = _hip.load()

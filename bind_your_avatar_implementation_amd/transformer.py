@@ -380,7 +380,8 @@ class BindyouravatarTransformer3DModel(nn.Module):
         self.invalidate_engine()
         return self
 
-    def enable_mx_weights(self, fmt: str = "mxfp6", enabled: bool = True, linears=None, weight_format=None):
+    def enable_mx_weights(self, fmt: str = "mxfp6", enabled: bool = True, linears=None, weight_format=None, *,
+                          fuse_activation_quant: bool = True):
         """Run the selected Linears on OCP MX operands: 32-element blocks along K with one e8m0 scale each, applied by
         gfx950's block-scaled matrix instruction (include/bya.h, "MX weights").  ``fmt``: "mxfp6" (e2m3 elements, the
         instruction's fastest dense rate) or "mxfp8" (e4m3 elements, the more accurate).  Weights are quantised when the
@@ -388,7 +389,9 @@ class BindyouravatarTransformer3DModel(nn.Module):
         ``linears``: as for enable_fp8_weights (a subset of engine.FP8_LINEARS or "all"; default engine.FP8_DEFAULT).
         ``weight_format``: the weights' element format -- None or ``fmt`` (the same as the activations), or "mxfp4" (e2m1
         elements, 4.25 bits per parameter) under the activations of ``fmt``; no other combination, and "mxfp4" is never an
-        activation format.  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
+        activation format.  ``fuse_activation_quant`` (keyword only): when ff.net.0 and ff.net.2 are both MX Linears, the
+        ff.net.0 GEMM writes ff.net.2's MX operand from its own epilogue (bya_gemm_mx_quant) instead of a bf16 tensor that a
+        quantiser launch reads back -- the same bytes, so on by default; False keeps the two launches.  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
         counterpart (the reference is bf16/fp16 only); returns self."""
         from .ops import MX_FORMATS, MX_WEIGHT_FORMATS
         if fmt not in MX_FORMATS:
@@ -400,6 +403,7 @@ class BindyouravatarTransformer3DModel(nn.Module):
         self._mx_weights = fmt if enabled else None
         self._mx_weight_format = weight_format if enabled else None
         self._mx_linears = (linears if isinstance(linears, str) else tuple(linears)) if linears else None
+        self._mx_fuse_activation_quant = bool(fuse_activation_quant)
         self.invalidate_engine()
         return self
 

@@ -258,6 +258,17 @@ int bya_layernorm_fp8(const void* x, void* q, float* q_scale, const void* w, con
  *   w_fmt == a_fmt is exactly bya_gemm_mx, w_fmt == BYA_MX_E2M1 multiplies 4-bit weights (codes [N, K / 2]) with the same
  *   activations; every other pair: BYA_ERR_UNSUPPORTED.  lda / ldw are checked against each operand's own row bytes.  The
  *   kernel (tile, ring) follows the activation format.
+ * bya_gemm_mx_quant:  bya_gemm_mx_mixed whose epilogue writes MX codes instead of bf16 -- the A operand of the next MX GEMM:
+ *     v[z][m,n] = bf16( alpha * act( sum_k A[z][m,k] * W[n,k] + rowscale*bias[n] ) ),   (q_codes, q_scales) = MX(out_fmt) of v
+ *   byte for byte bya_gemm_mx_mixed followed by bya_quantize_mx(out_fmt), in one launch and without the bf16 tensor (a block
+ *   of 32 output columns of a row sits in one wave of the kernel).  out_fmt in {E4M3, E2M3}, whatever the operand formats;
+ *   BYA_MX_E2M1 (never an activation format) and every operand pair bya_gemm_mx_mixed refuses: BYA_ERR_UNSUPPORTED.
+ *   q_codes uint8 [batch][M][N * bits / 8]: ldc = row stride and c_batch_stride = batch stride, both in BYTES of codes
+ *   (ldc >= N * bits / 8; bytes of a row behind that are not written); q_scales uint8 [batch * M, N / 32], dense.
+ *   N % 128 == 0 (a legal K); ldc % 16 == 0, c_batch_stride % 16 == 0, q_codes 16-byte and q_scales 4-byte aligned
+ *   (BYA_ERR_ALIGN); the operand side as bya_gemm_mx_mixed.  act in {NONE, GELU_TANH(_IEEE)}; alpha and bias_rowscale as in
+ *   bya_gemm_mx.  Codes cannot carry a residual, gates or a column split: there are no such arguments, ldres / gate fields
+ *   are ignored and n_split != 0 is BYA_ERR_UNSUPPORTED.  Every check runs before any launch (and without a GPU).
  * --------------------------------------------------------------------------------------------- */
 enum { BYA_MX_E4M3 = 0, BYA_MX_E2M3 = 2, BYA_MX_E2M1 = 4 };
 int bya_quantize_mx(const void* x, void* codes, void* scales, int32_t M, int32_t K, int64_t ldx, int32_t fmt,
@@ -280,6 +291,13 @@ int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void* W, const 
 int bya_gemm_mx_mixed_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
                            const void* C, const void* res, const void* gate0, const void* gate1,
                            const bya_gemm_desc* desc, int32_t a_fmt, int32_t w_fmt, bya_gemm_plan* plan);
+int bya_gemm_mx_quant(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                      void* q_codes, void* q_scales, const bya_gemm_desc* desc, int32_t a_fmt, int32_t w_fmt,
+                      int32_t out_fmt, hipStream_t stream);
+/* its kernel: bya_gemm_mx_mixed_plan's rule (path T128X128, or T256X256 for e2m3 activations); never cut into row chunks */
+int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                           const void* q_codes, const void* q_scales, const bya_gemm_desc* desc, int32_t a_fmt,
+                           int32_t w_fmt, int32_t out_fmt, bya_gemm_plan* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Small-M linear (M <= 8 rows):  out[m,n] = sum_k f(x[m,k]) * W[n,k] + bias[n],  f = identity or SiLU.
