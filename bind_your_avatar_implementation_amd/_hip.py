@@ -103,6 +103,8 @@ SIGNATURES = {
     "bya_attn_fwd": [_vp, _vp, _vp, _vp, _c.POINTER(AttnDesc), _vp],
     "bya_attn_variant": [_c.POINTER(AttnDesc)],
     "bya_attn_plan": [_c.POINTER(AttnDesc), _vp, _i32, _c.POINTER(AttnPlan)],
+    "bya_attn_fwd_mx": [_vp, _vp, _vp, _vp, _vp, _c.POINTER(AttnDesc), _i32, _i64, _i64, _i64, _i64, _i64, _i64, _vp],
+    "bya_attn_mx_plan": [_c.POINTER(AttnDesc), _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _c.POINTER(AttnPlan)],
     "bya_set_attn_workspace": [_vp, _i64],
     "bya_attn_workspace_bytes": [_c.POINTER(_i64)],
     "bya_attn_workspace_status": [_c.POINTER(_i32), _vp],

@@ -226,8 +226,11 @@ __device__ __forceinline__ void attn_tile(const char* kt, const uint32_t (&vbase
     pv_mfma<D>(fb, pf[3], oacc);
 }
 
-template <int D, bool PRESCALED, bool BOUNDED = false>
-__device__ __forceinline__ void attn_fwd_body(const AttnArgs& p, char* smem) {
+// MX (head_dim 64 only): the MX epilogue (store_mx_head, attn_common.h) instead of the bf16 one; mx = the scale bytes and the
+// format.  The format is a run-time, wave-uniform branch around the two epilogues, not a template parameter: one more copy
+// of the hot loop per softmax variant instead of two.
+template <int D, bool PRESCALED, bool BOUNDED = false, bool MX = false>
+__device__ __forceinline__ void attn_fwd_body(const AttnArgs& p, char* smem, const AttnMxOut* mx = nullptr) {
     constexpr int ROW_BYTES = D * 2;
     constexpr int TILE_BYTES = KV_TILE * ROW_BYTES;
     constexpr int DSTEPS = D / 16;   // k-steps of the QK^T product
@@ -373,9 +376,18 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& p, char* smem) {
     const auto lsw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
     const float l_tot = __uint_as_float(lsw[0]) + __uint_as_float(lsw[1]);
     const float inv = 1.0f / l_tot;
+    if constexpr (MX) {
+        static_assert(D == 64, "one MX block per 32-column tile, two per head");
+        const long long row = q_valid ? q0 + r : 0;
+        uint8_t* crow = reinterpret_cast<uint8_t*>(p.o) + b1 * p.o_s1 + b2 * p.o_s2 + row * p.o_row + (long long)head * 2 * mx_block_bytes(mx->fmt);
+        uint8_t* srow = mx->scales + b1 * mx->s1 + b2 * mx->s2 + row * mx->row + 2 * head;
+        if (mx->fmt == MX_E4M3) store_mx_head<MX_E4M3>(crow, srow, oacc[0], oacc[1], inv, hf, q_valid);
+        else store_mx_head<MX_E2M3>(crow, srow, oacc[0], oacc[1], inv, hf, q_valid);
+    } else {
     bf16_t* orow = O + (long long)(q_valid ? q0 + r : 0) * p.o_row;
 #pragma unroll
     for (int d = 0; d < DT; ++d) store_o_tile(orow + d * 32, oacc[d], inv, hf, q_valid, p.o_wide != 0);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -701,6 +713,12 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_kernel_d64_prescaled(AttnArgs
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_fwd_body<64, true>(p, smem);
 }
+// the MX-output instances (bya_attn_fwd_mx); resource numbers: DESIGN.md section 11
+template <bool PRESCALED>
+__global__ __launch_bounds__(256, 4) void attn_fwd_mx_kernel_d64(AttnMxArgs pm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_fwd_body<64, PRESCALED, false, true>(pm.a, smem, &pm.mx);
+}
 __global__ __launch_bounds__(256) void attn_fwd_kernel_d128(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_fwd_body<128, false>(p, smem);
@@ -800,6 +818,53 @@ int launch_attn(const AttnArgs& a, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 
+// bya_attn_fwd_mx's arguments -> kernel arguments (shared with bya_attn_mx_plan): the descriptor's checks are those of
+// bya_attn_fwd with an aligned stand-in for o, then a.o / a.o_* address the codes in bytes.
+int attn_mx_args_of(const void* q, const void* k, const void* v, void* codes, void* scales, const bya_attn_desc* d, int out_fmt,
+                    int64_t c_s1, int64_t c_s2, int64_t c_row, int64_t sc_s1, int64_t sc_s2, int64_t sc_row, AttnMxArgs& m) {
+    if (!q || !k || !v || !codes || !scales || !d) return BYA_ERR_SHAPE;
+    if (d->head_dim != 64) return BYA_ERR_UNSUPPORTED;                               // one MX block per 32 columns, two per head
+    if (out_fmt != MX_E4M3 && out_fmt != MX_E2M3) return BYA_ERR_UNSUPPORTED;       // e2m1 is never an activation format
+    if (d->o_s1 || d->o_s2 || d->o_row) return BYA_ERR_SHAPE;                        // there is no bf16 output: its strides stay 0
+    const int rc = attn_args_of(q, k, v, reinterpret_cast<void*>((uintptr_t)16), d, m.a);
+    if (rc != BYA_OK) return rc;
+    const long long row_bytes = (long long)d->heads * 2 * mx_block_bytes(out_fmt);
+    if (c_row < row_bytes || sc_row < 2LL * d->heads || c_s1 < 0 || c_s2 < 0 || sc_s1 < 0 || sc_s2 < 0) return BYA_ERR_SHAPE;
+    if (((uintptr_t)codes | (uintptr_t)c_s1 | (uintptr_t)c_s2 | (uintptr_t)c_row) & 3) return BYA_ERR_ALIGN;   // 4-byte stores
+    m.a.o = static_cast<bf16_t*>(codes); m.a.o_s1 = c_s1; m.a.o_s2 = c_s2; m.a.o_row = c_row; m.a.o_wide = 0;
+    m.mx.scales = static_cast<uint8_t*>(scales); m.mx.s1 = sc_s1; m.mx.s2 = sc_s2; m.mx.row = sc_row; m.mx.fmt = out_fmt;
+    return BYA_OK;
+}
+
+// the launches of launch_attn<64>, MX instances: same plan, same second launch for the flagged heads
+int launch_attn_mx(const AttnMxArgs& m, int fmt, hipStream_t s) {
+    const AttnArgs& a = m.a;
+    bya_attn_plan_info pl;
+    attn_plan_of(a, 64, -1, &pl);
+    const int nbh = a.nb1 * a.nb2 * a.heads;
+    const dim3 grid((nbh * a.nqt + 7) / 8 * 8), block(256);
+    const size_t lds = (size_t)ATTN_RING * 2 * KV_TILE * 64 * 2;
+    auto running = [&](const AttnMxArgs& x, bool prescaled) {
+        if (prescaled) BYA_LAUNCH(attn_fwd_mx_kernel_d64<true>, grid, block, lds, s, x);
+        else BYA_LAUNCH(attn_fwd_mx_kernel_d64<false>, grid, block, lds, s, x);
+    };
+    switch (pl.variant) {
+        case BYA_ATTN_D64_DEVICE_BOUND_W4: {
+            const int rc = bya_launch_attn_w4_mx(&m, fmt, s);
+            if (rc != BYA_OK) return rc;
+            AttnMxArgs b = m;
+            b.a.bound_dev = nullptr; b.a.score_bound = 0.f; b.a.only_flagged = a.fallback; b.a.fallback = nullptr;
+            running(b, true);
+            break;
+        }
+        case BYA_ATTN_D64_STATIC_BOUND_W4: return bya_launch_attn_w4_mx(&m, fmt, s);
+        case BYA_ATTN_D64_PRESCALED: running(m, true); break;
+        case BYA_ATTN_D64_RUNNING_MAX: running(m, false); break;
+        default: return BYA_ERR_UNSUPPORTED;
+    }
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
 // bya_attn_kv_mix: argument checks and launch decisions in one place (launcher and bya_attn_kv_mix_plan).
 // qkv: the q, k, v addresses OR-ed together (0 in the query: it has none).
 int mix_plan_of(const void* z, const bya_attn_mix_desc* d, int has_af, uintptr_t qkv, bya_attn_kv_mix_plan_info* p) {
@@ -854,6 +919,28 @@ extern "C" int bya_attn_fwd(const void* q, const void* k, const void* v, void* o
     const int rc = attn_args_of(q, k, v, o, d, a);
     if (rc != BYA_OK) return rc;
     return d->head_dim == 64 ? launch_attn<64>(a, stream) : launch_attn<128>(a, stream);
+}
+
+extern "C" int bya_attn_mx_plan(const bya_attn_desc* d, const void* codes, const void* scales, int32_t out_fmt, int64_t c_s1,
+                               int64_t c_s2, int64_t c_row, int64_t sc_s1, int64_t sc_s2, int64_t sc_row,
+                               int32_t workspace_assumed, bya_attn_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    AttnMxArgs m;
+    const void* const aligned = reinterpret_cast<const void*>((uintptr_t)16);      // q, k, v stand-ins: the query has none
+    const int rc = attn_mx_args_of(aligned, aligned, aligned, const_cast<void*>(codes), const_cast<void*>(scales), d, out_fmt,
+                                   c_s1, c_s2, c_row, sc_s1, sc_s2, sc_row, m);
+    if (rc != BYA_OK) return rc;
+    attn_plan_of(m.a, 64, workspace_assumed, plan);
+    return BYA_OK;
+}
+
+extern "C" int bya_attn_fwd_mx(const void* q, const void* k, const void* v, void* codes, void* scales, const bya_attn_desc* d,
+                              int32_t out_fmt, int64_t c_s1, int64_t c_s2, int64_t c_row, int64_t sc_s1, int64_t sc_s2,
+                              int64_t sc_row, hipStream_t stream) {
+    AttnMxArgs m;
+    const int rc = attn_mx_args_of(q, k, v, codes, scales, d, out_fmt, c_s1, c_s2, c_row, sc_s1, sc_s2, sc_row, m);
+    if (rc != BYA_OK) return rc;
+    return launch_attn_mx(m, out_fmt, stream);
 }
 
 extern "C" int bya_attn_kv_mix_plan(const void* z, const void* af, const bya_attn_mix_desc* d, bya_attn_kv_mix_plan_info* plan) {

@@ -25,6 +25,11 @@
 // row whose real scores all lay below ~-10 lost its sum in that subtraction -- a constant negative offset of a head, e.g.
 // from the q/k-LayerNorm biases, is within the +-90 the softmax promises to handle.)
 // Built WITHOUT -amdgpu-mfma-vgpr-form (O accumulators and the Q fragments live in AGPRs).
+// The kernel body stands once, under BYA_ATTN_W4_BODY at the end of this file, and is compiled into two kernels by including
+// this file from inside each of them: attn_joint_w4_kernel<SK> (bf16 output: text, name and instruction stream as before the MX
+// epilogue existed) and attn_joint_w4_mx_kernel<SK, MXF>.  A forceinline body function shared by both moved the bf16 instances'
+// accumulator set-up and a branch (tools/isa_fingerprint.py), and a second template parameter renames them.
+#ifndef BYA_ATTN_W4_BODY
 #include "attn_common.h"
 #include "gemm_persistent.h"      // raw_rsrc, dma_piece, xcd_range
 #include <stdlib.h>
@@ -61,8 +66,140 @@ struct SkItem { int bh, qt, tb, nt, nt_all, role, local, slot; };   // role: 0 w
 constexpr int SK_SLOT_FLOATS = 4 * QB * 2 * 16 * 64 + 4 * QB * 64;        // O^T register image + per-lane row sums
 constexpr int SK_FLAG_BYTES = 4096;                                       // 1024 words: [slot] flags, [1023] time-outs
 
+#define BYA_ATTN_W4_BODY
 template <bool SK>
 __global__ __launch_bounds__(256, 1) void attn_joint_w4_kernel(AttnArgs p) {
+    constexpr int MXF = -1;                                // the bf16 epilogue (store_o_tile)
+    const AttnMxOut* const mx = nullptr;
+#include __FILE__
+}
+// the MX epilogue (store_mx_head): MXF = MX_E4M3 / MX_E2M3, p.o / p.o_* address the codes in bytes, mx the scale bytes
+template <bool SK, int MXF>
+__global__ __launch_bounds__(256, 1) void attn_joint_w4_mx_kernel(AttnMxArgs pm) {
+    const AttnArgs& p = pm.a;
+    const AttnMxOut* const mx = &pm.mx;
+#include __FILE__
+}
+#undef BYA_ATTN_W4_BODY
+
+}  // namespace
+
+namespace {
+// stream-K exchange workspace, caller-owned, one per DEVICE (same rules as the GEMM's split-K workspace, gemm.hip)
+constexpr int SK_MAX_DEVICES = 64, SK_GRID = 256, SK_SLOTS = 2 * SK_GRID;  // slot = xcd * 64 + helper + leftover item
+constexpr long long SK_WS_BYTES = SK_FLAG_BYTES + (long long)SK_SLOTS * SK_SLOT_FLOATS * 4;
+std::atomic<void*> g_attn_ws[SK_MAX_DEVICES];
+inline int sk_device() {
+    int dev = 0;
+    return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < SK_MAX_DEVICES ? dev : -1;
+}
+}  // namespace
+
+extern "C" int bya_set_attn_workspace(void* ws, int64_t bytes) {
+    if (ws && (bytes < (int64_t)SK_WS_BYTES || ((uintptr_t)ws & 255))) return BYA_ERR_SHAPE;
+    const int dev = sk_device();
+    if (dev < 0) return BYA_ERR_UNSUPPORTED;
+    g_attn_ws[dev].store(ws);
+    return BYA_OK;
+}
+
+extern "C" int bya_attn_workspace_bytes(int64_t* bytes) {
+    if (!bytes) return BYA_ERR_SHAPE;
+    *bytes = (int64_t)SK_WS_BYTES;
+    return BYA_OK;
+}
+
+extern "C" int bya_attn_workspace_status(int32_t* timeouts, hipStream_t stream) {
+    if (!timeouts) return BYA_ERR_SHAPE;
+    *timeouts = 0;
+    const int dev = sk_device();
+    char* const ws = dev < 0 ? nullptr : static_cast<char*>(g_attn_ws[dev].load());
+    if (!ws) return BYA_OK;
+    unsigned word = 0;
+    if (hipMemcpyAsync(&word, ws + 1023 * 4, 4, hipMemcpyDeviceToHost, stream) != hipSuccess) return BYA_ERR_LAUNCH;
+    if (hipStreamSynchronize(stream) != hipSuccess) return BYA_ERR_LAUNCH;
+    *timeouts = (int32_t)word;
+    return BYA_OK;
+}
+
+void bya_plan_attn_w4(const void* args, int ws_present, bya_attn_w4_plan* plan) {
+    const AttnArgs& a = *static_cast<const AttnArgs*>(args);
+    const int nqt = (a.Sq + ROWS_PER_WG - 1) / ROWS_PER_WG;
+    const int nbh = a.nb1 * a.nb2 * a.heads;
+    if (ws_present < 0) {
+        const int dev = sk_device();
+        ws_present = dev >= 0 && g_attn_ws[dev].load() != nullptr;
+    }
+    const bool sk_on = bya_opt(BYA_OPT_ATTN_STREAMK) != 0;   // default on when a workspace exists
+    const long long nt_all = (a.Skv + KV_TILE - 1) / KV_TILE;
+    const long long items = (long long)nbh * nqt;
+    // stream-K pays when an XCD's items make at least one whole round of its 32 CUs plus a partial one.  Measured
+    // (profiles/history/r4_r_attn_streamk_probe.json): +1 % at 48 heads x 17776 (6.56 rounds), +8.5 % at a 2-rank shard's 24 heads
+    // (3.28 rounds), +2.7 % at 47026 tokens -- a fraction of what the round counts promise, and a grid that does not fill ONE
+    // round (6 heads of an 8-rank shard: 210 items on 256 CUs) LOSES 7 % although every workgroup then has 0.81 items
+    // of work.  Two forms of the cut (contiguous step ranges; mains + helpers at one key tile) measure the same, so it is
+    // not L2 locality: the kernel is power-limited (DESIGN.md section 4), the CUs a partial round leaves idle give their
+    // power budget to the busy ones as clock, and filling them buys little; below one round the hand-offs cost more.
+    const long long ipx = items / 8;                            // per XCD, +- one item when 8 does not divide
+    const long long rem = ipx % (SK_GRID / 8);
+    const bool sk = ws_present && sk_on && ipx >= SK_GRID / 8 && (items % SK_GRID != 0) && rem * nt_all >= 8 * (SK_GRID / 8) &&
+                    nt_all >= 16 && items * nt_all < (1LL << 31);
+    plan->q_tile = ROWS_PER_WG;
+    plan->stream_k = sk ? 1 : 0;
+    plan->grid = sk ? SK_GRID : (nbh * nqt + 7) / 8 * 8;
+    // what the kernel derives for XCD 0 (the others differ by one item when 8 does not divide the item count)
+    plan->sk_rem = 0; plan->sk_cut = 0;
+    if (sk) {
+        const int ncu = SK_GRID / 8;
+        int ipx0 = (nbh >> 3) * nqt;
+        if (nbh % 8 != 0) ipx0 = (int)(items >> 3) + ((items & 7) ? 1 : 0);
+        plan->sk_rem = ipx0 % ncu;
+        plan->sk_cut = plan->sk_rem ? (int)((nt_all * plan->sk_rem + ncu - 1) / ncu) : (int)nt_all;
+    }
+}
+
+int bya_launch_attn_w4_mx(const void* args, int fmt, hipStream_t s) {
+    AttnMxArgs m = *static_cast<const AttnMxArgs*>(args);
+    AttnArgs& a = m.a;
+    a.nqt = (a.Sq + ROWS_PER_WG - 1) / ROWS_PER_WG;
+    const int dev = sk_device();
+    char* const ws = dev < 0 ? nullptr : static_cast<char*>(g_attn_ws[dev].load());
+    bya_attn_w4_plan pl;
+    bya_plan_attn_w4(args, ws != nullptr, &pl);          // (AttnMxArgs begins with its AttnArgs)
+    a.sk_flags = pl.stream_k ? reinterpret_cast<unsigned*>(ws) : nullptr;
+    a.sk_part = pl.stream_k ? reinterpret_cast<float*>(ws + SK_FLAG_BYTES) : nullptr;
+    const dim3 grid(pl.grid), block(256);
+    const size_t lds = (size_t)NST * STAGE_BYTES;
+    if (pl.stream_k) {
+        if (fmt == MX_E4M3) BYA_LAUNCH((attn_joint_w4_mx_kernel<true, MX_E4M3>), grid, block, lds, s, m);
+        else BYA_LAUNCH((attn_joint_w4_mx_kernel<true, MX_E2M3>), grid, block, lds, s, m);
+    } else {
+        if (fmt == MX_E4M3) BYA_LAUNCH((attn_joint_w4_mx_kernel<false, MX_E4M3>), grid, block, lds, s, m);
+        else BYA_LAUNCH((attn_joint_w4_mx_kernel<false, MX_E2M3>), grid, block, lds, s, m);
+    }
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+int bya_launch_attn_w4(const void* args, hipStream_t s) {
+    AttnArgs a = *static_cast<const AttnArgs*>(args);
+    a.nqt = (a.Sq + ROWS_PER_WG - 1) / ROWS_PER_WG;
+    const int dev = sk_device();
+    char* const ws = dev < 0 ? nullptr : static_cast<char*>(g_attn_ws[dev].load());
+    bya_attn_w4_plan pl;
+    bya_plan_attn_w4(args, ws != nullptr, &pl);
+    if (pl.stream_k) {
+        a.sk_flags = reinterpret_cast<unsigned*>(ws);
+        a.sk_part = reinterpret_cast<float*>(ws + SK_FLAG_BYTES);
+        BYA_LAUNCH(attn_joint_w4_kernel<true>, dim3(pl.grid), dim3(256), (size_t)NST * STAGE_BYTES, s, a);
+    } else {
+        a.sk_flags = nullptr;
+        a.sk_part = nullptr;
+        BYA_LAUNCH(attn_joint_w4_kernel<false>, dim3(pl.grid), dim3(256), (size_t)NST * STAGE_BYTES, s, a);
+    }
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+#else  // BYA_ATTN_W4_BODY: the body of attn_joint_w4_kernel / attn_joint_w4_mx_kernel (AttnArgs p, MXF, mx are in scope)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int D = 64;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -280,6 +417,12 @@ __global__ __launch_bounds__(256, 1) void attn_joint_w4_kernel(AttnArgs p) {
         const bf16_t* Kp = p.k + b1 * p.k_s1 + b2 * p.k_s2 + (long long)head * D + (long long)it.tb * KV_TILE * p.k_row;
         const bf16_t* Vp = p.v + b1 * p.v_s1 + b2 * p.v_s2 + (long long)head * D + (long long)it.tb * KV_TILE * p.v_row;
         bf16_t* Op = p.o + b1 * p.o_s1 + b2 * p.o_s2 + (long long)head * D;
+        uint8_t* Cp = nullptr;
+        uint8_t* Sp = nullptr;
+        if constexpr (MXF >= 0) {
+            Cp = reinterpret_cast<uint8_t*>(p.o) + b1 * p.o_s1 + b2 * p.o_s2 + (long long)head * 2 * mx_block_bytes(MXF);
+            Sp = mx->scales + b1 * mx->s1 + b2 * mx->s2 + 2 * head;
+        }
         const int skv_left = p.Skv - it.tb * KV_TILE;             // keys from this piece's first tile to the end of K / V
         rsK = raw_rsrc(Kp, (uint32_t)(((long long)(skv_left - 1) * p.k_row + D) * 2));
         rsV = raw_rsrc(Vp, (uint32_t)(((long long)(skv_left - 1) * p.v_row + D) * 2));
@@ -434,105 +577,15 @@ __global__ __launch_bounds__(256, 1) void attn_joint_w4_kernel(AttnArgs p) {
             const float l_half = psum[b][0] + psum[b][1];
             const auto lsw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_half), __float_as_uint(l_half), false, false);
             const float inv = 1.0f / (__uint_as_float(lsw[0]) + __uint_as_float(lsw[1]));
+            if constexpr (MXF >= 0) {
+                const long long row = q_valid[b] ? q0 + b * 32 + r : 0;
+                store_mx_head<MXF>(Cp + row * p.o_row, Sp + row * mx->row, oacc[b][0], oacc[b][1], inv, hf, q_valid[b]);
+            } else {
             bf16_t* orow = Op + (long long)(q_valid[b] ? q0 + b * 32 + r : 0) * p.o_row;
 #pragma unroll
             for (int d = 0; d < 2; ++d) store_o_tile(orow + d * 32, oacc[b][d], inv, hf, q_valid[b], p.o_wide != 0);
+            }
         }
         if (!SK) break;
     }
-}
-
-}  // namespace
-
-namespace {
-// stream-K exchange workspace, caller-owned, one per DEVICE (same rules as the GEMM's split-K workspace, gemm.hip)
-constexpr int SK_MAX_DEVICES = 64, SK_GRID = 256, SK_SLOTS = 2 * SK_GRID;  // slot = xcd * 64 + helper + leftover item
-constexpr long long SK_WS_BYTES = SK_FLAG_BYTES + (long long)SK_SLOTS * SK_SLOT_FLOATS * 4;
-std::atomic<void*> g_attn_ws[SK_MAX_DEVICES];
-inline int sk_device() {
-    int dev = 0;
-    return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < SK_MAX_DEVICES ? dev : -1;
-}
-}  // namespace
-
-extern "C" int bya_set_attn_workspace(void* ws, int64_t bytes) {
-    if (ws && (bytes < (int64_t)SK_WS_BYTES || ((uintptr_t)ws & 255))) return BYA_ERR_SHAPE;
-    const int dev = sk_device();
-    if (dev < 0) return BYA_ERR_UNSUPPORTED;
-    g_attn_ws[dev].store(ws);
-    return BYA_OK;
-}
-
-extern "C" int bya_attn_workspace_bytes(int64_t* bytes) {
-    if (!bytes) return BYA_ERR_SHAPE;
-    *bytes = (int64_t)SK_WS_BYTES;
-    return BYA_OK;
-}
-
-extern "C" int bya_attn_workspace_status(int32_t* timeouts, hipStream_t stream) {
-    if (!timeouts) return BYA_ERR_SHAPE;
-    *timeouts = 0;
-    const int dev = sk_device();
-    char* const ws = dev < 0 ? nullptr : static_cast<char*>(g_attn_ws[dev].load());
-    if (!ws) return BYA_OK;
-    unsigned word = 0;
-    if (hipMemcpyAsync(&word, ws + 1023 * 4, 4, hipMemcpyDeviceToHost, stream) != hipSuccess) return BYA_ERR_LAUNCH;
-    if (hipStreamSynchronize(stream) != hipSuccess) return BYA_ERR_LAUNCH;
-    *timeouts = (int32_t)word;
-    return BYA_OK;
-}
-
-void bya_plan_attn_w4(const void* args, int ws_present, bya_attn_w4_plan* plan) {
-    const AttnArgs& a = *static_cast<const AttnArgs*>(args);
-    const int nqt = (a.Sq + ROWS_PER_WG - 1) / ROWS_PER_WG;
-    const int nbh = a.nb1 * a.nb2 * a.heads;
-    if (ws_present < 0) {
-        const int dev = sk_device();
-        ws_present = dev >= 0 && g_attn_ws[dev].load() != nullptr;
-    }
-    const bool sk_on = bya_opt(BYA_OPT_ATTN_STREAMK) != 0;   // default on when a workspace exists
-    const long long nt_all = (a.Skv + KV_TILE - 1) / KV_TILE;
-    const long long items = (long long)nbh * nqt;
-    // stream-K pays when an XCD's items make at least one whole round of its 32 CUs plus a partial one.  Measured
-    // (profiles/history/r4_r_attn_streamk_probe.json): +1 % at 48 heads x 17776 (6.56 rounds), +8.5 % at a 2-rank shard's 24 heads
-    // (3.28 rounds), +2.7 % at 47026 tokens -- a fraction of what the round counts promise, and a grid that does not fill ONE
-    // round (6 heads of an 8-rank shard: 210 items on 256 CUs) LOSES 7 % although every workgroup then has 0.81 items
-    // of work.  Two forms of the cut (contiguous step ranges; mains + helpers at one key tile) measure the same, so it is
-    // not L2 locality: the kernel is power-limited (DESIGN.md section 4), the CUs a partial round leaves idle give their
-    // power budget to the busy ones as clock, and filling them buys little; below one round the hand-offs cost more.
-    const long long ipx = items / 8;                            // per XCD, +- one item when 8 does not divide
-    const long long rem = ipx % (SK_GRID / 8);
-    const bool sk = ws_present && sk_on && ipx >= SK_GRID / 8 && (items % SK_GRID != 0) && rem * nt_all >= 8 * (SK_GRID / 8) &&
-                    nt_all >= 16 && items * nt_all < (1LL << 31);
-    plan->q_tile = ROWS_PER_WG;
-    plan->stream_k = sk ? 1 : 0;
-    plan->grid = sk ? SK_GRID : (nbh * nqt + 7) / 8 * 8;
-    // what the kernel derives for XCD 0 (the others differ by one item when 8 does not divide the item count)
-    plan->sk_rem = 0; plan->sk_cut = 0;
-    if (sk) {
-        const int ncu = SK_GRID / 8;
-        int ipx0 = (nbh >> 3) * nqt;
-        if (nbh % 8 != 0) ipx0 = (int)(items >> 3) + ((items & 7) ? 1 : 0);
-        plan->sk_rem = ipx0 % ncu;
-        plan->sk_cut = plan->sk_rem ? (int)((nt_all * plan->sk_rem + ncu - 1) / ncu) : (int)nt_all;
-    }
-}
-
-int bya_launch_attn_w4(const void* args, hipStream_t s) {
-    AttnArgs a = *static_cast<const AttnArgs*>(args);
-    a.nqt = (a.Sq + ROWS_PER_WG - 1) / ROWS_PER_WG;
-    const int dev = sk_device();
-    char* const ws = dev < 0 ? nullptr : static_cast<char*>(g_attn_ws[dev].load());
-    bya_attn_w4_plan pl;
-    bya_plan_attn_w4(args, ws != nullptr, &pl);
-    if (pl.stream_k) {
-        a.sk_flags = reinterpret_cast<unsigned*>(ws);
-        a.sk_part = reinterpret_cast<float*>(ws + SK_FLAG_BYTES);
-        BYA_LAUNCH(attn_joint_w4_kernel<true>, dim3(pl.grid), dim3(256), (size_t)NST * STAGE_BYTES, s, a);
-    } else {
-        a.sk_flags = nullptr;
-        a.sk_part = nullptr;
-        BYA_LAUNCH(attn_joint_w4_kernel<false>, dim3(pl.grid), dim3(256), (size_t)NST * STAGE_BYTES, s, a);
-    }
-    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
-}
+#endif  // BYA_ATTN_W4_BODY

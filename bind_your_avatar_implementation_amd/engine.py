@@ -104,6 +104,9 @@ class DenoiseEngine:
         # ... and ff.net.0's GEMM writes ff.net.2's MX operand itself (bya_gemm_mx_quant: byte for byte the GEMM + the 12288-wide
         # quantiser) when both are MX Linears; enable_mx_weights(fuse_activation_quant=False) keeps the two launches
         self.mx_fuse_quant = self.mx_fmt is not None and bool(getattr(model, "_mx_fuse_activation_quant", True))
+        # ... and the joint attention writes attn1.to_out's MX operand itself (bya_attn_fwd_mx: byte for byte the attention + the
+        # 3072-wide quantiser) when to_out is an MX Linear; enable_mx_weights(fuse_attention_quant=True), off by default
+        self.mx_fuse_attn_quant = self.mx_fmt is not None and bool(getattr(model, "_mx_fuse_attention_quant", False))
         # the remaining A/B switches of the step, read ONCE here (round 4 looked them up in os.environ on every step / call)
         self.side_stream_conditioning = os.environ.get("BYA_INVARIANTS_SIDE_STREAM", "1") != "0"
         self.sp_allgather = os.environ.get("BYA_SP_ALLGATHER", "0") == "1"       # exchange A as a K/V all-gather (A/B)
@@ -349,6 +352,19 @@ class DenoiseEngine:
     def _ff_pair_fused(self):
         """Whether ff.net.0's launch writes ff.net.2's MX operand (both MX Linears, and the switch on)."""
         return self.mx_fuse_quant and self.wmx is not None and "ff1" in self.wmx and "ff2" in self.wmx
+
+    def _attn_out_fused(self):
+        """Whether the joint attention writes to_out's MX operand (to_out an MX Linear, and the switch on)."""
+        return self.mx_fuse_attn_quant and self.wmx is not None and "out" in self.wmx
+
+    def _joint_attention(self, q, k, v, out, **kw):
+        """The joint attention of a DiT block where its output rows are to_out's input rows in place.  Returns to_out's
+        ``quantised=`` operand: None after the bf16 launch into ``out``; fused, the (codes, scales) in the ``_amx`` workspace of
+        ``out``'s shape, ``out`` itself being neither written nor read."""
+        if not self._attn_out_fused():
+            ops.self_attention(q, k, v, out, **kw)
+            return None
+        return ops.self_attention(q, k, v, None, mx_out=(*self._amx(out.shape), self.mx_fmt), **kw)
 
     def _ff1_mx_quant(self, i, a, out_shape, bias, quantised=None):
         """Block ``i``'s ff.net.0 + GELU(tanh) with the quantising epilogue: returns the (codes, scales) of its bf16-rounded
@@ -815,13 +831,13 @@ class DenoiseEngine:
                         else:
                             sh.gather_rows(k[0], k_full[0])
                             sh.gather_rows(v[0], v_full[0])
-                        ops.self_attention(q, k_full, v_full, xn, heads=H, tag="joint", prescaled=True,
-                                           score_bound=self.score_bound[i])
+                        oq = self._joint_attention(q, k_full, v_full, xn, heads=H, tag="joint", prescaled=True,
+                                                   score_bound=self.score_bound[i])
                     else:
-                        ops.self_attention(q, k, v, xn, heads=H, tag="joint", prescaled=True, score_bound=sb,
-                                           bound=None if st is None else (st, 0, self._ws["qk_flags"]))
+                        oq = self._joint_attention(q, k, v, xn, heads=H, tag="joint", prescaled=True, score_bound=sb,
+                                                   bound=None if st is None else (st, 0, self._ws["qk_flags"]))
                     self._dit_linear("out", i, xn, at.to_out[0].weight, x, bias=at.to_out[0].bias, res=x, gate0=mo[:, 5 * D:],
-                             gate1=mo[:, 2 * D:], gate_split=Tt_loc, gate_batch_stride=mbs)
+                             gate1=mo[:, 2 * D:], gate_split=Tt_loc, gate_batch_stride=mbs, quantised=oq)
                 else:
                     fq = None
                     if self._ff_pair_fused():

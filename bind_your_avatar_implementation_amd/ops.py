@@ -896,18 +896,47 @@ def _attn_desc(head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strid
     return d
 
 
+def _attn_mx_out(mx_out, heads, head_dim, nb1, nb2, Sq, o_strides, plan=False):
+    """``mx_out`` = (codes, scales, fmt) of ``attention`` -> (codes, scales, format code, the six byte strides).  The pair holds the
+    [nb1 * nb2 * Sq, heads * 64] output as ``quantize_mx`` would: uint8 codes [.., heads * 64 * bits / 8], uint8 scales [.., heads
+    * 2], contiguous, batches stacked (level 1 over level 2 over rows)."""
+    if o_strides is not None and tuple(o_strides) != (0, 0, 0):
+        raise ValueError("attention: with mx_out there is no bf16 output -- pass out=None and no o_strides")
+    codes, scales, fmt = mx_out
+    code = mx_fmt_code(fmt)                          # "mxfp4" is a weight format: refused here like everywhere for activations
+    if head_dim != 64:
+        raise ValueError("attention: mx_out needs head_dim 64 (one MX block per 32 columns, two per head)")
+    rows, cb, sb = nb1 * nb2 * Sq, mx_code_bytes(heads * 64, fmt), heads * 2
+    for t, name, width in ((codes, "codes", cb), (scales, "scales", sb)):
+        if t.dtype != torch.uint8:
+            raise TypeError(f"attention: mx_out {name}: expected uint8, got {t.dtype}")
+        if not t.is_contiguous() or t.numel() != rows * width or t.shape[-1] != width:
+            raise ValueError(f"attention: mx_out {name} must be a contiguous [{rows} rows, {width}] uint8 tensor, got "
+                             f"{tuple(t.shape)}")
+        if not (t.is_cuda or (plan and t.is_meta)):
+            raise ValueError(f"attention: mx_out {name}: expected a device tensor")
+    return codes, scales, code, (nb2 * Sq * cb, Sq * cb, cb, nb2 * Sq * sb, Sq * sb, sb)
+
+
 # ---- what the attention launches run (bya_attn_plan & co.: host-side, launch nothing, meta tensors may stand for device tensors)
 KV_MIX_FORMS = _hip.KV_MIX_FORMS
 TINY_INSTANCES = _hip.TINY_INSTANCES
 
 
-def attention_plan(out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale,
-                   prescaled=False, score_bound=0.0, bound=None, workspace=None):
+def attention_plan(out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides=None, scale,
+                   prescaled=False, score_bound=0.0, bound=None, workspace=None, mx_out=None):
     """What ``attention`` with the same arguments would run: {"variant" (``ATTN_VARIANT_NAMES``), "grid", "q_tile", "stream_k",
     "sk_rem", "sk_cut", "o_wide", "second_launch"}.  ``workspace``: True / False = as if a stream-K workspace were / were not
     registered; None = as the launch would find it (a device ``out`` registers the device's workspace like ``attention``
-    does; with a meta ``out``: none)."""
+    does; with a meta ``out``: none).  ``mx_out`` (with ``out`` None): the plan of the MX-output launch (bya_attn_mx_plan);
+    the dict then also has "mx_out": the format."""
     lib = _hip.load()
+    mx = None
+    if mx_out is not None:
+        if out is not None:
+            raise ValueError("attention_plan: with mx_out there is no bf16 output -- pass out=None")
+        mx = _attn_mx_out(mx_out, heads, head_dim, nb1, nb2, Sq, o_strides, plan=True)
+        out, o_strides = mx[0], (0, 0, 0)
     d = _attn_desc(head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale, prescaled,
                    score_bound, bound, plan=True)
     if workspace is None:
@@ -915,15 +944,24 @@ def attention_plan(out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_stri
             ensure_attn_workspace(out.device)
         workspace = -1 if out.is_cuda else 0
     p = _hip.AttnPlan()
-    check(lib.bya_attn_plan(ctypes.byref(d), _plan_p(out), int(workspace), ctypes.byref(p)), "bya_attn_plan")
+    if mx is not None:
+        check(lib.bya_attn_mx_plan(ctypes.byref(d), _plan_p(mx[0]), _plan_p(mx[1]), mx[2], *mx[3], int(workspace), ctypes.byref(p)),
+              "bya_attn_mx_plan")
+    else:
+        check(lib.bya_attn_plan(ctypes.byref(d), _plan_p(out), int(workspace), ctypes.byref(p)), "bya_attn_plan")
     assert p.variant == lib.bya_attn_variant(ctypes.byref(d))
-    return {"variant": ATTN_VARIANT_NAMES[p.variant], "grid": p.grid, "q_tile": p.q_tile, "stream_k": p.stream_k,
+    plan = {"variant": ATTN_VARIANT_NAMES[p.variant], "grid": p.grid, "q_tile": p.q_tile, "stream_k": p.stream_k,
             "sk_rem": p.sk_rem, "sk_cut": p.sk_cut, "o_wide": p.o_wide, "second_launch": p.second_launch}
+    if mx is not None:
+        plan["mx_out"] = mx_out[2]
+    return plan
 
 
 def attention_plan_key(plan):
-    """One name per distinct attention kernel path: variant, "+streamk", "/wide" or "/narrow" (the store width)."""
-    return plan["variant"] + ("+streamk" if plan["stream_k"] else "") + ("/wide" if plan["o_wide"] else "/narrow")
+    """One name per distinct attention kernel path: variant, "+streamk", and the epilogue: "/wide" or "/narrow" (the bf16 store
+    width) or "/mxfp8" / "/mxfp6" (the MX-output launch)."""
+    tail = "/" + plan["mx_out"] if plan.get("mx_out") else ("/wide" if plan["o_wide"] else "/narrow")
+    return plan["variant"] + ("+streamk" if plan["stream_k"] else "") + tail
 
 
 def attn_kv_mix_plan(z, af=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale=1.0):
@@ -956,14 +994,23 @@ def _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_str
     return d
 
 
-def attention(q, k, v, out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides,
-              scale, tag="other", prescaled=False, score_bound=0.0, bound=None):
+def attention(q, k, v, out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides=None,
+              scale, tag="other", prescaled=False, score_bound=0.0, bound=None, mx_out=None):
     """Flash attention with explicit (level-1, level-2, row) element strides for q, k, v, out.
     ``bound`` = (stats, bh0, flags): the data-dependent score bound -- ``stats`` fp32 [slots, 2, n] as written by
     ``qknorm_rope(stats=...)``, this launch's (batch, head) index bh at column bh0 + bh, ``flags`` int32 [nb1 * nb2 * heads]
-    (scratch: which heads went to the running-maximum kernel)."""
+    (scratch: which heads went to the running-maximum kernel).
+    ``mx_out`` = (codes, scales, fmt) with ``out`` None (head_dim 64): the output leaves as MX codes and block scales
+    (bya_attn_fwd_mx) -- byte for byte ``quantize_mx(out, fmt)`` of the [nb1 * nb2 * Sq, heads * 64] output, which is never
+    written; returns the pair, the ``quantised=`` operand of the next MX Linear.  fmt: "mxfp8" or "mxfp6"."""
     lib = _hip.load()
-    for t in (q, k, v, out):
+    mx = None
+    if mx_out is not None:
+        if out is not None:
+            raise ValueError("attention: with mx_out there is no bf16 output -- pass out=None")
+        mx = _attn_mx_out(mx_out, heads, head_dim, nb1, nb2, Sq, o_strides)
+        o_strides = (0, 0, 0)
+    for t in (q, k, v) + (() if mx is not None else (out,)):
         assert t.dtype == torch.bfloat16 and t.is_cuda
     d = _attn_desc(head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale, prescaled,
                    score_bound, bound)
@@ -971,25 +1018,35 @@ def attention(q, k, v, out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_
         ensure_attn_workspace(q.device)
     var = ATTN_VARIANT_NAMES.get(lib.bya_attn_variant(ctypes.byref(d)), "rejected")
     ATTN_VARIANTS[tag, var] = ATTN_VARIANTS.get((tag, var), 0) + 1
-    label = "bya_attn_fwd:" + tag
+    label = ("bya_attn_fwd_mx:" if mx is not None else "bya_attn_fwd:") + tag
     if _SHAPE_LABELS:
-        label += f":{nb1}x{nb2}x{heads}h_q{Sq}_kv{Skv}_d{head_dim}"
+        label += f":{nb1}x{nb2}x{heads}h_q{Sq}_kv{Skv}_d{head_dim}" + (f">{mx_out[2]}" if mx is not None else "")
     tok = _begin(label, 4.0 * nb1 * nb2 * heads * Sq * Skv * head_dim)
-    check(lib.bya_attn_fwd(_p(q), _p(k), _p(v), _p(out), ctypes.byref(d), _stream()), "bya_attn_fwd")
+    if mx is not None:
+        check(lib.bya_attn_fwd_mx(_p(q), _p(k), _p(v), _p(mx[0]), _p(mx[1]), ctypes.byref(d), mx[2], *mx[3], _stream()),
+              "bya_attn_fwd_mx")
+    else:
+        check(lib.bya_attn_fwd(_p(q), _p(k), _p(v), _p(out), ctypes.byref(d), _stream()), "bya_attn_fwd")
     _end(tok)
-    return out
+    return (mx[0], mx[1]) if mx is not None else out
 
 
-def self_attention(q, k, v, out, heads, head_dim=64, scale=None, tag="other", prescaled=False, score_bound=0.0, bound=None):
-    """q,k,v,out: [B, S, heads*head_dim] views (row-strided ok)."""
+def self_attention(q, k, v, out, heads, head_dim=64, scale=None, tag="other", prescaled=False, score_bound=0.0, bound=None,
+                   mx_out=None):
+    """q,k,v,out: [B, S, heads*head_dim] views (row-strided ok).  ``mx_out`` = (codes, scales, fmt) with ``out`` None: see
+    ``attention``."""
     b, S, _, q_bs, q_ld = _mat(q, "q")
     _, Skv, _, k_bs, k_ld = _mat(k, "k")
     _, _, _, v_bs, v_ld = _mat(v, "v")
-    _, _, _, o_bs, o_ld = _mat(out, "out")
+    o_strides = None
+    if mx_out is None:
+        _, _, _, o_bs, o_ld = _mat(out, "out")
+        o_strides = (o_bs, 0, o_ld)
     scale = head_dim ** -0.5 if scale is None else scale
     return attention(q, k, v, out, head_dim=head_dim, heads=heads, nb1=b, nb2=1, Sq=S, Skv=Skv,
                      q_strides=(q_bs, 0, q_ld), k_strides=(k_bs, 0, k_ld), v_strides=(v_bs, 0, v_ld),
-                     o_strides=(o_bs, 0, o_ld), scale=scale, tag=tag, prescaled=prescaled, score_bound=score_bound, bound=bound)
+                     o_strides=o_strides, scale=scale, tag=tag, prescaled=prescaled, score_bound=score_bound, bound=bound,
+                     mx_out=mx_out)
 
 
 def attn_kv_mix(q, k, v, r, af, z, wsum=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides,

@@ -414,6 +414,28 @@ typedef struct bya_attn_plan_info {
 } bya_attn_plan_info;
 int bya_attn_plan(const bya_attn_desc* desc, const void* o, int32_t workspace_assumed, bya_attn_plan_info* plan);
 
+/* bya_attn_fwd followed by bya_quantize_mx(out_fmt) on its [rows, heads * 64] output, without the bf16 matrix: the
+ * epilogue of every head_dim-64 kernel (running maximum plain / prescaled, static bound with and without stream-K, device
+ * bound incl. its second launch for the flagged heads) rounds acc / l to bf16 as bya_attn_fwd stores it, takes the |max| of
+ * each 32-column half of a head over the lane pair that holds it, and writes the MX codes and one e8m0 scale byte per
+ * (row, head, half) -- byte for byte what the two launches write (see "MX weights" for the formats).
+ *   codes:  byte (head * 64 + 32 h) * bits / 8 of a row holds half h of the head (32 bytes as e4m3, 24 as e2m3);
+ *   scales: byte 2 * head + h of a row.
+ * Row r of batch (b1, b2) starts at  codes + b1 * c_s1 + b2 * c_s2 + r * c_row  and  scales + b1 * sc_s1 + b2 * sc_s2 +
+ * r * sc_row -- all strides in BYTES.  Rows >= Sq and bytes outside the heads' code / scale bytes are never written.
+ * desc is bya_attn_fwd's descriptor with o_s1 = o_s2 = o_row = 0 (there is no bf16 output; anything else: BYA_ERR_SHAPE).
+ * The kernel / stream-K / second-launch decisions are bya_attn_fwd's; bya_attn_mx_plan answers them (o_wide is 0).
+ * Refused before any launch: head_dim != 64, out_fmt other than e4m3 (0) / e2m3 (2) -> BYA_ERR_UNSUPPORTED; codes or a
+ * code stride not a multiple of 4 bytes (a lane stores 16 or 12 bytes as dwords; scale bytes are stored one by one and
+ * need no alignment) -> BYA_ERR_ALIGN; c_row < heads * 64 * bits / 8, sc_row < 2 * heads, a negative batch stride or
+ * anything bya_attn_fwd refuses as a shape -> BYA_ERR_SHAPE. */
+int bya_attn_fwd_mx(const void* q, const void* k, const void* v, void* codes, void* scales, const bya_attn_desc* desc,
+                    int32_t out_fmt, int64_t c_s1, int64_t c_s2, int64_t c_row, int64_t sc_s1, int64_t sc_s2, int64_t sc_row,
+                    hipStream_t stream);
+int bya_attn_mx_plan(const bya_attn_desc* desc, const void* codes, const void* scales, int32_t out_fmt, int64_t c_s1,
+                     int64_t c_s2, int64_t c_row, int64_t sc_s1, int64_t sc_s2, int64_t sc_row, int32_t workspace_assumed,
+                     bya_attn_plan_info* plan);
+
 /* Optional stream-K workspace of the static-bound joint-attention kernel (BYA_ATTN_D64_STATIC_BOUND_W4): device memory
  * owned by the caller, 256-byte aligned, at least bya_attn_workspace_bytes (69 MB), ZERO-FILLED once; one per DEVICE, used
  * by launches enqueued under the current device, which must be ordered on one stream.  NULL unregisters.  With it, a
