@@ -30,6 +30,7 @@
 #include "gemm_common.h"
 #include "mx_common.h"
 #include "options.h"
+#include "qknorm_math.h"
 
 namespace {
 
@@ -248,8 +249,161 @@ __device__ __forceinline__ void epilogue_mx_quant(const GemmArgs& p, uint8_t* __
     }
 }
 
-// FMT_A: activations (the instruction's B operand, blgp); FMT_W: weights (its A operand, cbsz); QOUT < 0: the bf16 epilogue,
-// else the element format of the quantising one (qs = its scale bytes)
+// ---- the q/k-norm epilogue (bya_gemm_mx_qkv_norm_rope): the packed q|k|v projection with the per-head q/k LayerNorm(64) +
+// RoPE of bya_qknorm_rope on its accumulators (reference models/transformer.py:204-208), bit for bit bya_gemm_mx_mixed(...,
+// n_split) followed by bya_qknorm_rope.  Arithmetic: qknorm_math.h, whose eight groups g of a head row are 8 consecutive
+// columns each.  Here a lane (fr, fq) holds columns 16 i + 4 fq .. + 3 of its wave in acc[i][j]: a head is the fragments
+// i = 4 h .. 4 h + 3, group g sits in fragment g >> 1 in the lane pair fq = 2 (g & 1), 2 (g & 1) + 1.  qkn_sum8 and
+// qkn_centre_sq8 run sequentially over a group's eight values, so a lane's own partial sum would round differently: the pair
+// trades its four values instead.  v_permlane16_swap of a register with itself leaves the EVEN lane's value in the first
+// result and the ODD lane's in the second, in both lanes -- the values in column order.  What is traded is
+// bf16(acc + bias), the value the two-launch path stored and read back, two to a register: two swaps per fragment.  Both
+// lanes then evaluate the group's sum; the tree is (g ^ 1) = lane ^ 32 (v_permlane32_swap), (g ^ 2) = the lane's fragments
+// i ^ 1, (g ^ 4) = i ^ 2 -- same operands per addition as the stand-alone kernel (an addition does not depend on the order of
+// its two operands).  qkn_finish8 is element-wise and the RoPE pairs (2 i, 2 i + 1) lie inside four columns.  q, k or v is
+// decided per head (width % 64 == 0), wave-uniformly: a wave or a tile may straddle q | k or k | v; v heads and heads past N
+// take the plain bias epilogue (epilogue_block's arithmetic and 8-byte stores).
+// Stores, STORE16: after the trade the pair holds the eight columns twice, so the even lane finishes and stores fragments
+// 4 h, 4 h + 2 and the odd lane 4 h + 1, 4 h + 3, 16 bytes each; else every lane finishes its own four columns of every
+// fragment and stores 8 bytes.  The same number of finished values, table loads and bytes either way.
+// Rotary rows come through buffer descriptors: rows that are not rotated read zeros from an out-of-range offset, no branch.
+#ifndef BYA_MX_QKN_STORE16
+#define BYA_MX_QKN_STORE16 1
+#endif
+template <int NI, int MI, bool STORE16>
+__device__ __forceinline__ void epilogue_mx_qkn(const GemmArgs& p, int z, int m_base, int n_wave, int fq,
+                                                const f32x4 (&acc)[NI][MI]) {
+    static_assert(NI % 4 == 0, "whole heads per wave");
+    constexpr int NH = NI / 4;
+    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(p.C + (long long)z * p.c_bs), 0, 0x7fffffff, 0x00020000);
+    const long long trows = (long long)p.M - p.qkn_text_rows;
+    const int tbytes = trows > 0 && p.qkn_cos ? (int)(trows * 256) : 0;          // (the launcher keeps this below 2^31)
+    const __amdgpu_buffer_rsrc_t rsCos = __builtin_amdgcn_make_buffer_rsrc((void*)p.qkn_cos, 0, tbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsSin = __builtin_amdgcn_make_buffer_rsrc((void*)p.qkn_sin, 0, tbytes, 0x00020000);
+    const bool has_bias = p.bias != nullptr;
+    const bool odd = fq & 1;
+    auto colbytes = [&](int n) {
+        return ((uint32_t)(n / p.n_split) * (uint32_t)p.c_split_stride + (uint32_t)(n % p.n_split)) * 2u;
+    };
+    // the lane's two finished pieces k = 0, 1 of a head: columns hc[k] .. + 7 (STORE16), or hc[k] .. + 3 and hc[k] + 16 .. + 19
+    int hc[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) hc[k] = STORE16 ? 16 * (2 * k + (fq & 1)) + 8 * (fq >> 1) : 32 * k + 4 * fq;
+    auto load8 = [&](const bf16_t* src, int k) {
+        if constexpr (STORE16) return *reinterpret_cast<const u32x4*>(src + hc[k]);
+        else {
+            const u32x2 a = *reinterpret_cast<const u32x2*>(src + hc[k]), b = *reinterpret_cast<const u32x2*>(src + hc[k] + 16);
+            return u32x4{a[0], a[1], b[0], b[1]};
+        }
+    };
+    auto pair16 = [](uint32_t x) { return __builtin_amdgcn_permlane16_swap(x, x, false, false); };
+    auto add32 = [](float x) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+        return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    };
+    // Head by head, rows inside: one head's parameters and bias are live at a time, and a finished head's accumulators are
+    // dead (the 256 x 256 tile has 128 of them per lane and two heads per wave: rows outside spilled).  The price is that its
+    // second head reads the rotary rows again, from L2.
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        const int n_head = n_wave + 64 * h;
+        const int tsel = n_head / p.qkn_width;                      // 0 = q, 1 = k, else v or past N: wave-uniform
+        u32x2 bv[4];
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            const int n4 = n_head + 16 * f + 4 * fq;
+            bv[f] = has_bias ? *reinterpret_cast<const u32x2*>(p.bias + (n4 < p.N ? n4 : 0)) : u32x2{0u, 0u};
+        }
+        if (tsel < 2) {
+            const float ks = tsel == 1 ? p.qkn_kscale : 1.0f;
+            u32x4 wq[2], bq[2];
+            uint32_t colb[2][2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                wq[k] = load8(p.qkn_w[tsel], k);
+                bq[k] = load8(p.qkn_b[tsel], k);
+                colb[k][0] = colbytes(n_head + hc[k]);
+                colb[k][1] = colbytes(n_head + hc[k] + 16);
+            }
+#pragma unroll
+            for (int j = 0; j < MI; ++j) {
+                const int m = m_base + 16 * j;
+                const bool mok = m < p.M;
+                const uint32_t coff = (mok ? (uint32_t)m : 0u) * (uint32_t)(p.ldc * 2);
+                const bool rope = mok && m >= p.qkn_text_rows;
+                float cc[2][8], ss[2][8];
+                const uint32_t t0 = (uint32_t)(m - p.qkn_text_rows) * 256u;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const uint32_t o0 = rope ? t0 + (uint32_t)hc[k] * 4u : 0xffffffffu;
+                    const uint32_t o1 = rope ? o0 + (STORE16 ? 16u : 64u) : 0xffffffffu;
+                    const f32x4 c0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsCos, o0, 0, 0));
+                    const f32x4 c1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsCos, o1, 0, 0));
+                    const f32x4 s0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsSin, o0, 0, 0));
+                    const f32x4 s1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsSin, o1, 0, 0));
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { cc[k][e] = c0[e]; cc[k][4 + e] = c1[e]; ss[k][e] = s0[e]; ss[k][4 + e] = s1[e]; }
+                }
+                float v[4][8];                                      // group g = 2 f + (fq >> 1) of the head row, in column order
+#pragma unroll
+                for (int f = 0; f < 4; ++f) {
+                    // bf16(acc + bias): the projection as the two-launch path stored it, one rounding
+                    const f32x4 a = acc[4 * h + f][j];
+                    const uint32_t r0 = pack2bf(a[0] + bflo(bv[f][0]), a[1] + bfhi(bv[f][0]));
+                    const uint32_t r1 = pack2bf(a[2] + bflo(bv[f][1]), a[3] + bfhi(bv[f][1]));
+                    const auto s0 = pair16(r0), s1 = pair16(r1);
+                    unpack8(u32x4{s0[0], s1[0], s0[1], s1[1]}, v[f]);
+                }
+                float s[4];
+#pragma unroll
+                for (int f = 0; f < 4; ++f) s[f] = add32(qkn_sum8(v[f]));
+                const float mean = ((s[0] + s[1]) + (s[2] + s[3])) * (1.0f / 64);
+#pragma unroll
+                for (int f = 0; f < 4; ++f) s[f] = add32(qkn_centre_sq8(v[f], mean));
+                const float rstd = rsqrtf(((s[0] + s[1]) + (s[2] + s[3])) * (1.0f / 64) + p.qkn_eps);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    float u[8], w8[8], b8[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        if constexpr (STORE16) u[e] = odd ? v[2 * k + 1][e] : v[2 * k][e];
+                        else u[e] = odd ? v[2 * k + (e >> 2)][4 + (e & 3)] : v[2 * k + (e >> 2)][e & 3];
+                    }
+                    unpack8(wq[k], w8);
+                    unpack8(bq[k], b8);
+                    qkn_finish8(u, rstd, w8, b8, rope, cc[k], ss[k], ks);
+                    const u32x4 o = pack8(u);
+                    if constexpr (STORE16) {
+                        __builtin_amdgcn_raw_buffer_store_b128(o, rsC, mok ? coff + colb[k][0] : 0xffffffffu, 0, 0);
+                    } else {
+                        __builtin_amdgcn_raw_buffer_store_b64(u32x2{o[0], o[1]}, rsC, mok ? coff + colb[k][0] : 0xffffffffu, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b64(u32x2{o[2], o[3]}, rsC, mok ? coff + colb[k][1] : 0xffffffffu, 0, 0);
+                    }
+                }
+            }
+        } else {
+            // v, or columns past N: epilogue_block's arithmetic (alpha = 1, no activation) and stores
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+                const int n4 = n_head + 16 * f + 4 * fq;
+                const uint32_t colb = n4 < p.N ? colbytes(n4) : 0xffffffffu;
+#pragma unroll
+                for (int j = 0; j < MI; ++j) {
+                    const int m = m_base + 16 * j;
+                    const f32x4 a = acc[4 * h + f][j];
+                    u32x2 o;
+                    o[0] = pack2bf(a[0] + bflo(bv[f][0]), a[1] + bfhi(bv[f][0]));
+                    o[1] = pack2bf(a[2] + bflo(bv[f][1]), a[3] + bfhi(bv[f][1]));
+                    __builtin_amdgcn_raw_buffer_store_b64(o, rsC, (m < p.M && n4 < p.N) ? (uint32_t)m * (uint32_t)(p.ldc * 2) + colb : 0xffffffffu, 0, 0);
+                }
+            }
+        }
+    }
+}
+
+// FMT_A: activations (the instruction's B operand, blgp); FMT_W: weights (its A operand, cbsz); QOUT = -1: the bf16 epilogue,
+// MX_EPI_QKN: the q/k-norm one (p.qkn_*); else the element format of the quantising one (qs = its scale bytes)
+constexpr int MX_EPI_QKN = -2;
 template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N, int QOUT>
 __device__ __forceinline__ void gemm_mx_body(const GemmArgs& p, const uint8_t* __restrict__ sa, const uint8_t* __restrict__ sw,
                                              int GM, uint8_t* __restrict__ qs) {
@@ -341,11 +495,13 @@ __device__ __forceinline__ void gemm_mx_body(const GemmArgs& p, const uint8_t* _
 
     // Lane holds C[m][n4 .. n4+3], m = m_base + 16 j, n4 = n_base + 16 i (W fragment = the instruction's A operand)
     const int m_base = m0 + wm * WM + fr, n_base = n0 + wn * WN + fq * 4;
-    if constexpr (QOUT < 0) {
+    if constexpr (QOUT == -1) {
         auto run = [&](auto act_tag) {
             epilogue_block<decltype(act_tag)::value, NI, MI, (NI * MI > 16 ? 1 : NI)>(p, z, m_base, n_base, acc);
         };
         dispatch_act_big(p.act, run);
+    } else if constexpr (QOUT == MX_EPI_QKN) {
+        epilogue_mx_qkn<NI, MI, BYA_MX_QKN_STORE16 != 0>(p, z, m_base, n0 + wn * WN, fq, acc);
     } else {
         static_assert(MxQuantStage<QOUT, BN>::bytes(BM) <= NST * STAGE, "the staged tile must fit the K-loop's ring");
         auto run = [&](auto act_tag) {
@@ -370,6 +526,13 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_quant_kernel(G
     gemm_mx_body<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, QOUT>(p, sa, sw, GM, qs);
 }
 
+// ... with the q/k-norm epilogue (GemmArgs::qkn_*)
+template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_qkn_kernel(GemmArgs p, const uint8_t* __restrict__ sa,
+                                                                             const uint8_t* __restrict__ sw, int GM) {
+    gemm_mx_body<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, MX_EPI_QKN>(p, sa, sw, GM, nullptr);
+}
+
 template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
 int launch_mx(const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, int batch, hipStream_t s) {
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
@@ -377,6 +540,18 @@ int launch_mx(const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, int batch
     const size_t lds = (size_t)mx_stages(FMT_A) * (BM * (mx_tile_row_bytes(FMT_A) + 4) + BN * (mx_tile_row_bytes(FMT_W) + 4));
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = gemm_mx_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N>;
+    if (bya_allow_big_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
+    BYA_LAUNCH(kern, grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a, sa, sw, MX_GROUP_M);
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
+int launch_mx_qkn(const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, int batch, hipStream_t s) {
+    const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
+    dim3 grid(tiles_m * tiles_n, 1, batch);
+    const size_t lds = (size_t)mx_stages(FMT_A) * (BM * (mx_tile_row_bytes(FMT_A) + 4) + BN * (mx_tile_row_bytes(FMT_W) + 4));
+    static std::atomic<unsigned long long> attr_done{0};
+    auto kern = gemm_mx_qkn_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N>;
     if (bya_allow_big_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
     BYA_LAUNCH(kern, grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a, sa, sw, MX_GROUP_M);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
@@ -574,6 +749,69 @@ extern "C" int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const
     const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
     if (rc != BYA_OK) return rc;
     p->path = mx_path(a, d->batch, a_fmt);
+    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = 1;
+    return BYA_OK;
+}
+
+namespace {
+// bya_gemm_mx_qkv_norm_rope's arguments -> GemmArgs; BYA_ERR_UNSUPPORTED: not this epilogue's shape (the caller keeps
+// bya_gemm_mx_mixed + bya_qknorm_rope); malformed arguments: the errors of qkn_args (gemm.hip) and mx_args
+int mx_qkn_args(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, const void* C,
+                const bya_gemm_desc* d, const bya_qknorm_desc* n, int32_t a_fmt, int32_t w_fmt, GemmArgs* out) {
+    if (!d || !n) return BYA_ERR_SHAPE;
+    if (!n->qw || !n->qb || !n->kw || !n->kb || n->width <= 0 || n->text_rows < 0) return BYA_ERR_SHAPE;
+    if (d->M > 0 && n->text_rows < d->M && (!n->cos || !n->sin)) return BYA_ERR_SHAPE;
+    bya_gemm_desc e = *d;                                // the operand side: bya_gemm_mx_mixed's own checks
+    e.ldres = 0; e.res_batch_stride = 0; e.gate_batch_stride = 0; e.gate_split = 0;
+    const int rc = mx_args(A, a_scales, W, w_scales, bias, C, nullptr, nullptr, nullptr, &e, a_fmt, w_fmt, out);
+    if (rc != BYA_OK) return rc;
+    if ((d->N != 3 * n->width && d->N != 2 * n->width) || n->width % 64 != 0 || d->n_split <= 0 || d->act != 0 ||
+        d->bias_rowscale || (d->alpha != 0.0f && d->alpha != 1.0f))
+        return BYA_ERR_UNSUPPORTED;
+    // eight consecutive columns leave as one 16-byte store
+    if (d->n_split % 8 || d->c_split_stride % 8 || d->ldc % 8 || d->c_batch_stride % 8) return BYA_ERR_ALIGN;
+    if (((uintptr_t)C | (uintptr_t)n->qw | (uintptr_t)n->qb | (uintptr_t)n->kw | (uintptr_t)n->kb | (uintptr_t)n->cos |
+         (uintptr_t)n->sin) & 15) return BYA_ERR_ALIGN;
+    GemmArgs& a = *out;
+    a.act = 0; a.alpha = 1.0f; a.bias_rowscale = nullptr;
+    a.qkn_w[0] = (const bf16_t*)n->qw; a.qkn_b[0] = (const bf16_t*)n->qb; a.qkn_w[1] = (const bf16_t*)n->kw; a.qkn_b[1] = (const bf16_t*)n->kb;
+    a.qkn_cos = n->cos; a.qkn_sin = n->sin; a.qkn_text_rows = n->text_rows; a.qkn_width = n->width;
+    a.qkn_eps = n->eps; a.qkn_kscale = n->k_scale == 0.0f ? 1.0f : n->k_scale;
+    // one launch: its rows and its rotary rows within the 2 GiB reach of the buffer descriptors
+    if (!gemm_rows_reachable(a, a.M) || ((long long)a.M - a.qkn_text_rows) * 256 >= 0x7fffffffLL) return BYA_ERR_UNSUPPORTED;
+    return BYA_OK;
+}
+}  // namespace
+
+// bya_gemm_mx_mixed of the packed q|k|v (or q|k) projection with the per-head q/k LayerNorm(64) + RoPE in its epilogue: bit for
+// bit bya_gemm_mx_mixed(..., n_split) followed by bya_qknorm_rope, q and k written once.  Tile by mx_path, as every MX GEMM.
+extern "C" int bya_gemm_mx_qkv_norm_rope(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                         const void* bias, void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* d,
+                                         const bya_qknorm_desc* n, hipStream_t stream) {
+    GemmArgs a;
+    const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
+    if (rc != BYA_OK) return rc;
+    const uint8_t* sa = (const uint8_t*)a_scales;
+    const uint8_t* sw = (const uint8_t*)w_scales;
+    const bool big = mx_path(a, d->batch, fmt) == BYA_GEMM_PATH_T256X256, w4 = w_fmt == MX_E2M1;
+    if (fmt == MX_E4M3)
+        return w4 ? launch_mx_qkn<MX_E4M3, MX_E2M1, 128, 128, 2, 2>(a, sa, sw, d->batch, stream)
+                  : launch_mx_qkn<MX_E4M3, MX_E4M3, 128, 128, 2, 2>(a, sa, sw, d->batch, stream);
+    if (big)
+        return w4 ? launch_mx_qkn<MX_E2M3, MX_E2M1, 256, 256, 4, 2>(a, sa, sw, d->batch, stream)
+                  : launch_mx_qkn<MX_E2M3, MX_E2M3, 256, 256, 4, 2>(a, sa, sw, d->batch, stream);
+    return w4 ? launch_mx_qkn<MX_E2M3, MX_E2M1, 128, 128, 2, 2>(a, sa, sw, d->batch, stream)
+              : launch_mx_qkn<MX_E2M3, MX_E2M3, 128, 128, 2, 2>(a, sa, sw, d->batch, stream);
+}
+
+extern "C" int bya_gemm_mx_qkv_norm_rope_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                              const void* bias, const void* C, int32_t fmt, int32_t w_fmt,
+                                              const bya_gemm_desc* d, const bya_qknorm_desc* n, bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    GemmArgs a;
+    const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
+    if (rc != BYA_OK) return rc;
+    p->path = mx_path(a, d->batch, fmt);
     p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = 1;
     return BYA_OK;
 }

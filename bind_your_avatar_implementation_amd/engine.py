@@ -107,6 +107,9 @@ class DenoiseEngine:
         # ... and the joint attention writes attn1.to_out's MX operand itself (bya_attn_fwd_mx: byte for byte the attention + the
         # 3072-wide quantiser) when to_out is an MX Linear; enable_mx_weights(fuse_attention_quant=True), off by default
         self.mx_fuse_attn_quant = self.mx_fmt is not None and bool(getattr(model, "_mx_fuse_attention_quant", False))
+        # ... and the q|k|v projection norms and rotates q and k in its own epilogue (bya_gemm_mx_qkv_norm_rope: bit for bit the
+        # GEMM + bya_qknorm_rope) when "qkv" is an MX Linear; enable_mx_weights(fuse_qk_norm=True), off by default
+        self.mx_fuse_qk_norm = self.mx_fmt is not None and bool(getattr(model, "_mx_fuse_qk_norm", False))
         # the remaining A/B switches of the step, read ONCE here (round 4 looked them up in os.environ on every step / call)
         self.side_stream_conditioning = os.environ.get("BYA_INVARIANTS_SIDE_STREAM", "1") != "0"
         self.sp_allgather = os.environ.get("BYA_SP_ALLGATHER", "0") == "1"       # exchange A as a K/V all-gather (A/B)
@@ -320,13 +323,20 @@ class DenoiseEngine:
 
     def _qkv_norm_rope(self, i, at, xn, out, split, xq, cos, sin, text_rows, heads, q_view, k_view, stats):
         """Block ``i``'s packed q|k|v projection + q/k LayerNorm + RoPE (models/transformer.py:200-209, 241-245): ONE launch
-        with the norm in the GEMM's epilogue where the library takes it (bf16 weights, no statistics wanted), else the
-        projection and ``bya_qknorm_rope`` on its output -- the same bits either way."""
+        with the norm in the GEMM's epilogue where the library takes it (bf16 weights, or MX weights behind the LayerNorm-fused
+        quantiser with ``fuse_qk_norm``; no statistics wanted), else the projection and ``bya_qknorm_rope`` on its output -- the
+        same bits either way."""
         fused = self.qkn_epilogue and stats is None and not self._quantised("qkv") and xq is None
         if fused and ops.gemm_qkv_norm_rope(xn, self.qkv_w[i], out, self.qkv_b[i], split, at.norm_q.weight, at.norm_q.bias,
                                             at.norm_k.weight, at.norm_k.bias, cos, sin, text_rows, eps=at.norm_q.eps,
                                             k_scale=self.k_scale):
             return
+        if self.mx_fuse_qk_norm and stats is None and xq is not None and self.wmx is not None and "qkv" in self.wmx:
+            wc, sw = self.wmx["qkv"][i]
+            if ops.gemm_mx_qkv_norm_rope(xq[0], xq[1].view(*xn.shape[:-1], -1), wc, sw, out, self.qkv_b[i], split,
+                                         at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin, text_rows,
+                                         eps=at.norm_q.eps, k_scale=self.k_scale, fmt=self.mx_fmt, w_fmt=self.mx_wfmt):
+                return
         self._dit_linear("qkv", i, xn, self.qkv_w[i], out, bias=self.qkv_b[i], split=split, quantised=xq)
         ops.qknorm_rope(q_view, k_view, at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin,
                         heads=heads, text_rows=text_rows, eps=at.norm_q.eps, k_scale=self.k_scale, stats=stats)

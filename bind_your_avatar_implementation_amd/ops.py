@@ -719,6 +719,66 @@ def gemm_mx_plan(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=No
     return _plan_dict(p)
 
 
+def _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, qw, qb, kw, kb, cos, sin, text_rows, eps,
+                  k_scale, tensors, act=None, alpha=1.0, plan=False):
+    if tensors not in (2, 3) or w_codes.shape[0] % tensors or split is None:
+        raise ValueError("gemm_mx_qkv_norm_rope: w_codes [3 * width, ..] (or [2 * width, ..]: q | k alone, tensors=2), "
+                         "out = the first of the split outputs, split = (n_split, c_split_stride)")
+    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, None, 0, 0, act, split, alpha, plan=plan)
+    n = _hip.QkNormDesc()
+    ptr = _plan_p if plan else _p
+    n.qw, n.qb, n.kw, n.kb, n.cos, n.sin = ptr(qw), ptr(qb), ptr(kw), ptr(kb), ptr(cos), ptr(sin)
+    n.text_rows, n.width, n.eps, n.k_scale = int(text_rows), d.N // tensors, float(eps), float(k_scale)
+    if cos is not None:
+        assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
+        assert cos.shape == (d.M - text_rows, 64)
+    return d, n
+
+
+def gemm_mx_qkv_norm_rope(a_codes, a_scales, w_codes, w_scales, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows,
+                          eps=1e-6, k_scale=1.0, tensors=3, fmt="mxfp6", w_fmt=None):
+    """The packed q|k|v projection on MX operands with the q/k LayerNorm(64) + RoPE in its epilogue
+    (bya_gemm_mx_qkv_norm_rope): equals ``gemm_mx(..., split=split)`` followed by ``qknorm_rope`` bit for bit, in one launch.
+    Returns False (nothing launched, nothing counted) when the library does not take the shape -- the caller then issues the
+    two launches."""
+    lib = _hip.load()
+    code, wcode = mx_fmt_pair(fmt, w_fmt)
+    d, n = _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, qw, qb, kw, kb, cos, sin, text_rows, eps,
+                         k_scale, tensors)
+    ab, M, N, K = d.batch, d.M, d.N, d.K
+    name = "bya_gemm_mx_qkv_norm_rope"
+    if _SHAPE_LABELS:
+        name += f":{fmt}*{w_fmt or fmt}:{ab}x{M}x{N}x{K}"
+    tok = _begin(name)
+    rc = lib.bya_gemm_mx_qkv_norm_rope(_p(a_codes), _p(a_scales), _p(w_codes), _p(w_scales), _p(bias), _p(out), code, wcode,
+                                       ctypes.byref(d), ctypes.byref(n), _stream())
+    if rc == -4:                       # BYA_ERR_UNSUPPORTED: nothing was launched (the caller's gemm_mx counts the FLOPs)
+        return False
+    check(rc, "bya_gemm_mx_qkv_norm_rope")
+    if tok is not None:
+        _FLOPS[tok[0]] = _FLOPS.get(tok[0], 0.0) + 2.0 * ab * M * N * K
+    _end(tok)
+    return True
+
+
+def gemm_mx_qkv_norm_rope_plan(a_codes, a_scales, w_codes, w_scales, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows,
+                               eps=1e-6, k_scale=1.0, tensors=3, fmt="mxfp6", w_fmt=None, act=None, alpha=1.0):
+    """What ``gemm_mx_qkv_norm_rope`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations
+    only); None where it declines the shape (the caller's two launches).  ``act`` / ``alpha``: descriptor fields the launch
+    wrapper never sets, here to ask what the library answers to them."""
+    lib = _hip.load()
+    code, wcode = mx_fmt_pair(fmt, w_fmt)
+    d, n = _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, qw, qb, kw, kb, cos, sin, text_rows, eps,
+                         k_scale, tensors, act=act, alpha=alpha, plan=True)
+    p, q = _hip.GemmPlan(), _plan_p
+    rc = lib.bya_gemm_mx_qkv_norm_rope_plan(q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), code, wcode,
+                                            ctypes.byref(d), ctypes.byref(n), ctypes.byref(p))
+    if rc == -4:
+        return None
+    check(rc, "bya_gemm_mx_qkv_norm_rope_plan")
+    return _plan_dict(p)
+
+
 def _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, act, alpha):
     if a_scales.dim() == 2:
         ab, (M, KS) = 1, a_scales.shape

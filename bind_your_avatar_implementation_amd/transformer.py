@@ -381,7 +381,8 @@ class BindyouravatarTransformer3DModel(nn.Module):
         return self
 
     def enable_mx_weights(self, fmt: str = "mxfp6", enabled: bool = True, linears=None, weight_format=None, *,
-                          fuse_activation_quant: bool = True, fuse_attention_quant: bool = False):
+                          fuse_activation_quant: bool = True, fuse_attention_quant: bool = False,
+                          fuse_qk_norm: bool = False):
         """Run the selected Linears on OCP MX operands: 32-element blocks along K with one e8m0 scale each, applied by
         gfx950's block-scaled matrix instruction (include/bya.h, "MX weights").  ``fmt``: "mxfp6" (e2m3 elements, the
         instruction's fastest dense rate) or "mxfp8" (e4m3 elements, the more accurate).  Weights are quantised when the
@@ -394,11 +395,17 @@ class BindyouravatarTransformer3DModel(nn.Module):
         quantiser launch reads back -- the same bytes, so on by default; False keeps the two launches.
         ``fuse_attention_quant`` (keyword only, a bool): when attn1.to_out is an MX Linear, the joint attention writes to_out's
         MX operand from its own epilogue (bya_attn_fwd_mx) instead of a bf16 tensor that a quantiser launch reads back -- the
-        same bytes; off by default (opt-in; the head-parallel sharded step keeps the two launches).  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
+        same bytes; off by default (opt-in; the head-parallel sharded step keeps the two launches).
+        ``fuse_qk_norm`` (keyword only, a bool): when attn1.to_q|k|v is an MX Linear fed by the LayerNorm-fused quantiser, its
+        GEMM norms and rotates q and k in its own epilogue (bya_gemm_mx_qkv_norm_rope) instead of writing them in bf16 for a
+        bya_qknorm_rope launch to read and rewrite -- the same bits; off by default (opt-in; a layer whose attention wants
+        the norm statistics keeps the two launches).  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
         counterpart (the reference is bf16/fp16 only); returns self."""
         from .ops import MX_FORMATS, MX_WEIGHT_FORMATS
         if not isinstance(fuse_attention_quant, bool):
             raise TypeError(f"fuse_attention_quant: expected a bool, got {type(fuse_attention_quant).__name__}")
+        if not isinstance(fuse_qk_norm, bool):
+            raise TypeError(f"fuse_qk_norm: expected a bool, got {type(fuse_qk_norm).__name__}")
         if fmt not in MX_FORMATS:
             raise ValueError(f"MX format {fmt!r}: expected one of {sorted(MX_FORMATS)}")
         if weight_format is not None and weight_format not in MX_WEIGHT_FORMATS:
@@ -410,6 +417,7 @@ class BindyouravatarTransformer3DModel(nn.Module):
         self._mx_linears = (linears if isinstance(linears, str) else tuple(linears)) if linears else None
         self._mx_fuse_activation_quant = bool(fuse_activation_quant)
         self._mx_fuse_attention_quant = fuse_attention_quant
+        self._mx_fuse_qk_norm = fuse_qk_norm
         self.invalidate_engine()
         return self
 

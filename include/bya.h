@@ -269,6 +269,20 @@ int bya_layernorm_fp8(const void* x, void* q, float* q_scale, const void* w, con
  *   (BYA_ERR_ALIGN); the operand side as bya_gemm_mx_mixed.  act in {NONE, GELU_TANH(_IEEE)}; alpha and bias_rowscale as in
  *   bya_gemm_mx.  Codes cannot carry a residual, gates or a column split: there are no such arguments, ldres / gate fields
  *   are ignored and n_split != 0 is BYA_ERR_UNSUPPORTED.  Every check runs before any launch (and without a GPU).
+ * bya_gemm_mx_qkv_norm_rope:  bya_gemm_mx_mixed of the packed q|k|v projection WITH the per-head q/k LayerNorm(64) + RoPE of
+ *   bya_qknorm_rope in its epilogue (bya_gemm_qkv_norm_rope's counterpart on MX operands): bit for bit bya_gemm_mx_mixed(...,
+ *   n_split) followed by bya_qknorm_rope -- q and k are normalised from the bf16-ROUNDED projection with the arithmetic of
+ *   csrc/qknorm_math.h and written once; v columns take the plain bias epilogue.  The two descriptors mean what they mean for
+ *   bya_gemm_qkv_norm_rope: N = 3 width (q | k | v) or 2 width (q | k alone), n_split > 0 with c_split_stride (n_split = width,
+ *   or a column block n_split < width), text_rows, cos / sin [M - text_rows, 64] fp32, k_scale (0 is read as 1), batch.
+ *   q, k or v is decided per 64-column head, so width % 64 == 0 is enough (a tile may straddle q | k); the tile follows the
+ *   activation format as for every MX GEMM (bya_gemm_mx_mixed_plan's rule).  The norm statistics of bya_qknorm_rope are not
+ *   offered.  BYA_ERR_UNSUPPORTED, nothing launched (the caller keeps the two launches): an activation, bias_rowscale, alpha
+ *   other than 0 / 1, n_split == 0, width % 64, N neither 2 nor 3 widths, e2m1 activations (every operand pair
+ *   bya_gemm_mx_mixed refuses), rows or rotary rows beyond the 2 GiB reach of one launch's buffer descriptors.  There are no
+ *   residual / gate arguments; those descriptor fields are ignored.  n_split, c_split_stride, ldc, c_batch_stride % 8 == 0 and
+ *   C, the four norm vectors, cos and sin 16-byte aligned (BYA_ERR_ALIGN); otherwise the checks of bya_gemm_mx_mixed and of
+ *   bya_gemm_qkv_norm_rope's norm descriptor (BYA_ERR_SHAPE).  Every check runs before any launch (and without a GPU).
  * --------------------------------------------------------------------------------------------- */
 enum { BYA_MX_E4M3 = 0, BYA_MX_E2M3 = 2, BYA_MX_E2M1 = 4 };
 int bya_quantize_mx(const void* x, void* codes, void* scales, int32_t M, int32_t K, int64_t ldx, int32_t fmt,
@@ -298,6 +312,14 @@ int bya_gemm_mx_quant(const void* A, const void* a_scales, const void* W, const 
 int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
                            const void* q_codes, const void* q_scales, const bya_gemm_desc* desc, int32_t a_fmt,
                            int32_t w_fmt, int32_t out_fmt, bya_gemm_plan* plan);
+int bya_gemm_mx_qkv_norm_rope(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                              void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* desc, const bya_qknorm_desc* norm,
+                              hipStream_t stream);
+/* its kernel: bya_gemm_mx_mixed_plan's rule (path T128X128, or T256X256 for e2m3 activations); always one launch;
+ * BYA_ERR_UNSUPPORTED where the entry point declines the shape */
+int bya_gemm_mx_qkv_norm_rope_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                   const void* bias, const void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* desc,
+                                   const bya_qknorm_desc* norm, bya_gemm_plan* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Small-M linear (M <= 8 rows):  out[m,n] = sum_k f(x[m,k]) * W[n,k] + bias[n],  f = identity or SiLU.
