@@ -151,8 +151,15 @@ SIGNATURES = {
 
 # bya_option keys / BYA_REF_* bits of include/bya.h
 OPTIONS = {"gemm_splitk": 0, "gemm_splitk_min": 1, "gemm_tile": 2, "gemm_variant": 3, "attn_streamk": 4, "fp8_kernel": 5,
-           "p2p_groups": 6, "reference_forms": 7}
+           "p2p_groups": 6, "reference_forms": 7, "mx_kernel": 8}
 REFERENCE_FORMS = {"rowgemm_chunked": 1, "kv_mix_generic": 2, "ln_generic": 4, "router_scores_wave": 8, "attn_narrow_store": 16}
+def _named_value(var, v, table):
+    """The option value a variable's text stands for; an unknown text is an error, not a silent default."""
+    if v not in table:
+        raise ValueError(f"{var}={v!r}: expected one of {sorted(table)}")
+    return table[v]
+
+
 # environment variable -> (option, parser): read ONCE, when the library is loaded (the C entry points never call getenv)
 ENV_OPTIONS = {
     "BYA_GEMM_SPLITK": ("gemm_splitk", int),
@@ -162,6 +169,7 @@ ENV_OPTIONS = {
     "BYA_ATTN_STREAMK": ("attn_streamk", int),
     "BYA_FP8_KERNEL": ("fp8_kernel", lambda v: 1 if v.startswith("1") else 0),
     "BYA_P2P_GROUPS": ("p2p_groups", int),
+    "BYA_MX_KERNEL": ("mx_kernel", lambda v: _named_value("BYA_MX_KERNEL", v, {"0": 0, "1": 1, "p256": 1, "2": 2, "always": 2})),
 }
 
 # BYA_GEMM_PATH_* of include/bya.h: the kernels of a GEMM launch (bya_gemm_plan.path / .tail)
@@ -214,7 +222,7 @@ def get_option(name):
 
 
 OPTION_DEFAULTS = {"gemm_splitk": 0, "gemm_splitk_min": 0, "gemm_tile": -1, "gemm_variant": 0, "attn_streamk": 1, "fp8_kernel": 0,
-                   "p2p_groups": 0, "reference_forms": 0}
+                   "p2p_groups": 0, "reference_forms": 0, "mx_kernel": 0}
 
 
 def apply_env_options():

@@ -32,6 +32,11 @@
 #include "options.h"
 #include "qknorm_math.h"
 
+// defined in gemm_mx_v4.hip (accumulators in AGPRs): the persistent one-wave-per-SIMD 256 x 256 kernel for e4m3 x e4m3, plain
+// (qs null) or quantising (out e4m3) epilogue
+bool bya_gemm256p_mx_eligible(const void* args, bool quant);
+int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int batch, int gm, hipStream_t s);
+
 namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -658,6 +663,19 @@ inline int mx_path(const GemmArgs& a, int batch, int32_t fmt) {
     const bool big = BYA_MX_E2M3_BIG_TILE && tiles256 >= 200;
     return fmt == MX_E2M3 && big ? BYA_GEMM_PATH_T256X256 : BYA_GEMM_PATH_T128X128;
 }
+// ... and under option mx_kernel (1; 2: without the tile count) the persistent kernel of gemm_mx_v4.hip for e4m3 x e4m3, by the
+// rule of fp8_path (gemm_fp8.hip): `a` = the whole launch (tile count), `piece` = one row chunk of it (eligibility).  quant:
+// the quantising epilogue (out_fmt: its element format; e2m3 stays on the tiled kernel)
+inline int mx_path_p256(const GemmArgs& a, int batch, const GemmArgs& piece, int32_t a_fmt, int32_t w_fmt, bool quant = false,
+                        int32_t out_fmt = MX_E4M3) {
+    const int opt = bya_opt(BYA_OPT_MX_KERNEL);
+    const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
+    if (opt != 0 && a_fmt == MX_E4M3 && w_fmt == MX_E4M3 && out_fmt == MX_E4M3 && (opt == 2 || tiles256 >= 200) &&
+        bya_gemm256p_mx_eligible(&piece, quant))
+        return BYA_GEMM_PATH_P256;
+    return mx_path(a, batch, a_fmt);
+}
+constexpr int MX_P256_GROUP_M = 4;         // row-tiles per group of the persistent kernel's tile order (as bya_gemm_fp8)
 }  // namespace
 
 extern "C" int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
@@ -672,6 +690,8 @@ extern "C" int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void
     const bool big = mx_path(a, d->batch, a_fmt) == BYA_GEMM_PATH_T256X256, w4 = w_fmt == MX_E2M1;
     return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
         const uint8_t* sp = sa + row0 * ks;
+        if (mx_path_p256(a, d->batch, piece, a_fmt, w_fmt) == BYA_GEMM_PATH_P256)
+            return bya_launch_gemm256p_mx(&piece, sp, sw, nullptr, batch, MX_P256_GROUP_M, stream);
         if (a_fmt == MX_E4M3)
             return w4 ? launch_mx<MX_E4M3, MX_E2M1, 128, 128, 2, 2>(piece, sp, sw, batch, stream)
                       : launch_mx<MX_E4M3, MX_E4M3, 128, 128, 2, 2>(piece, sp, sw, batch, stream);
@@ -693,7 +713,7 @@ extern "C" int bya_gemm_mx_mixed_plan(const void* A, const void* a_scales, const
     if (rc != BYA_OK) return rc;
     const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
     if (!chunks) return BYA_ERR_UNSUPPORTED;
-    p->path = mx_path(a, d->batch, a_fmt);
+    p->path = mx_path_p256(a, d->batch, piece, a_fmt, w_fmt);
     p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = chunks;
     return BYA_OK;
 }
@@ -731,6 +751,8 @@ extern "C" int bya_gemm_mx_quant(const void* A, const void* a_scales, const void
     const uint8_t* sw = (const uint8_t*)w_scales;
     uint8_t* qs = (uint8_t*)q_scales;
     const bool big = mx_path(a, d->batch, a_fmt) == BYA_GEMM_PATH_T256X256, w4 = w_fmt == MX_E2M1;
+    if (mx_path_p256(a, d->batch, a, a_fmt, w_fmt, true, out_fmt) == BYA_GEMM_PATH_P256)
+        return bya_launch_gemm256p_mx(&a, sa, sw, qs, d->batch, MX_P256_GROUP_M, stream);
     if (a_fmt == MX_E4M3)
         return w4 ? launch_mx_quant<MX_E4M3, MX_E2M1, 128, 128, 2, 2>(a, sa, sw, qs, out_fmt, d->batch, stream)
                   : launch_mx_quant<MX_E4M3, MX_E4M3, 128, 128, 2, 2>(a, sa, sw, qs, out_fmt, d->batch, stream);
@@ -748,7 +770,7 @@ extern "C" int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const
     GemmArgs a;
     const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
     if (rc != BYA_OK) return rc;
-    p->path = mx_path(a, d->batch, a_fmt);
+    p->path = mx_path_p256(a, d->batch, a, a_fmt, w_fmt, true, out_fmt);
     p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = 1;
     return BYA_OK;
 }

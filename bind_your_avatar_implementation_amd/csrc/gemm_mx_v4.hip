@@ -1,0 +1,459 @@
+// Persistent 256 x 256 x 128 MX GEMM for e4m3 activations x e4m3 weights: gemm256p_fp8_kernel (gemm_fp8_v4.hip) on the
+// block-scaled instruction, with real e8m0 block scales -- ONE wave per SIMD, 128 x 128 per wave, 256 accumulator AGPRs, the
+// hand-placed two-phase K-tile of that file, its barriers B1 / B2, its four K-tile variants A / B / C / D, the next output
+// tile's first two K-tiles requested while this one drains.  Operands, epilogues and RESULT BITS are those of the 128 x 128
+// kernel of gemm_mx.hip (gemm_mx_body<MX_E4M3, MX_E4M3>): per 16 x 16 block one v_mfma_scale_f32_16x16x128_f8f6f4 per
+// K-tile, K-tiles ascending, W fragment first, the first K-tile on C = 0, on the same operand bytes (a lane's 32 bytes are
+// chunks fq and 4 + fq of the K-tile row: the lane order the block-scaled e4m3 instruction wants, gemm_mx.hip) under the
+// same scales -- the same instruction sequence per output element, so the two kernels agree bit for bit.
+//
+// What this file adds to gemm_fp8_v4.hip is the scale side:
+//   * LDS: the two 64 KiB code stages stay where they are (the stage flip is address bit 16); behind them, at 128 KiB, two
+//     2 KiB scale areas flipped by bit 11: one dword per row and K-tile (the row's 4 block scales), A rows 0..255 at 4 row,
+//     W SLOT rows at 1024 + 4 slot.  132 KiB of the CU's 160.
+//   * staging: a wave moves the scale dwords of its 64 A rows and of its 64 W slot rows as two 4-byte-per-lane LDS-DMA pieces
+//     per K-tile (18 pieces instead of 16), the W ones through the SAME slot -> source-row map as the W codes (w_slot_col),
+//     so the fragment of slot row r finds its scales in slot row r.  Buffer descriptors with the tile's extent, as for the
+//     codes: a row past M or N lands as zero bytes -- scale 2^-127 on zero codes.
+//   * reads: lane (fr, fq) needs byte fq of the dword of row 16 j + fr, for 8 A blocks and 8 W blocks: 16 ds_read_u8 per
+//     K-tile (the byte arrives in position 0: no VALU between LDS and the MFMA, so no VALU-write -> MFMA-read hazard to pad
+//     inside asm), each issued right behind the fragment read of its block, so it retires with it: W(0..3) at the phase
+//     boundary, A(j) behind A(j)'s last MFMA, W(4..7) at the head of the next K-tile.
+// Counted waits: B2 counts the pieces of K-tile t + 2 requested so far (tools/gen_gemm_mx_schedule.py), the prologue and
+// the tile end wait for all but the 18 youngest, a K-tile ends on lgkmcnt(3) = A(7)'s two fragment reads and its scale.
+//
+// The quantising epilogue (bya_gemm_mx_quant, out e4m3) needs no staging here: in the wide layout a lane holds EIGHT
+// consecutive columns, an MX block of a row is exactly the four lanes fq = 0..3, and the lane's 8 code bytes are contiguous.
+// (The ring is not free either: the next tile's first two K-tiles are in it.)
+// K >= 512; e2m1 weights, e2m3 operands (64- and 96-byte LDS rows) and the q/k-norm epilogue stay on gemm_mx.hip.
+// Compiled WITHOUT -amdgpu-mfma-vgpr-form, like gemm_fp8_v4.hip.
+#include "gemm_persistent.h"
+#include "mx_common.h"
+
+namespace {
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+
+constexpr int BK8 = 128;                                   // e4m3 elements (= bytes) per K-tile
+constexpr int SC_BASE = 2 * 65536, SC_STAGE = 2048, SC_W = 1024;   // the scale areas behind the two code stages
+
+// one 256-byte LDS-DMA piece of scales: lane l's dword from its global offset to LDS m0 + 4 l
+template <int LDS_OFF>
+__device__ __forceinline__ void dma_scale_piece(uint32_t lds_base, uint32_t voff, const i32x4& rsrc, uint32_t soff) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds"
+                 :
+                 : "s"(lds_base + LDS_OFF), "v"(voff), "s"(rsrc), "s"(soff)
+                 : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void ds_read_byte(int& dst, uint32_t addr) {
+    asm volatile("ds_read_u8 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
+}
+// the scale rows of tile c behind its origin: what is left of [batch * M, ks] (A) or [N, ks] (W), nothing for an invalid tile
+__device__ __forceinline__ i32x4 tile_rsrc_sa(const GemmArgs& p, const uint8_t* sa, int ks, const PersistentTile& c) {
+    const long long left = (long long)(p.M - c.m0) * ks;
+    return raw_rsrc(sa + ((long long)c.z * p.M + c.m0) * ks, c.valid && left > 0 ? (uint32_t)left : 0u);
+}
+__device__ __forceinline__ i32x4 tile_rsrc_sw(const GemmArgs& p, const uint8_t* sw, int ks, const PersistentTile& c) {
+    const long long left = (long long)(p.N - c.n0) * ks;
+    return raw_rsrc(sw + (long long)c.n0 * ks, c.valid && left > 0 ? (uint32_t)left : 0u);
+}
+
+// Wide epilogue of one wave: epilogue_wide8 of gemm_fp8_v4.hip without the row x channel scale product.  The lane
+// (fr = lane & 15, fq = lane >> 4) holds, for row block j and accumulator register e, the EIGHT consecutive columns
+// n8 = n_wave + (4 e + fq) * 8 + i,  i = 0..7  in acc[i][j][e], of row  m = m_wave + 16 j + fr.  Per element the expression
+// of epilogue_block (gemm_common.h), which the 128 x 128 kernel evaluates.
+template <int ACT, int JB>
+__device__ __forceinline__ void epilogue_mx_wide8(const GemmArgs& p, int z, int m_wave, int n_wave, int fr, int fq,
+                                                  f32x4 (&acc)[8][8]) {
+    const bool has_res = p.res != nullptr, has_gate = p.gate0 != nullptr, has_bias = p.bias != nullptr;
+    const bool has_rs = p.bias_rowscale != nullptr;
+    const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((has_res ? p.res : p.C) + (long long)z * p.res_bs), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(p.C + (long long)z * p.c_bs), 0, 0x7fffffff, 0x00020000);
+    const char* g0base = reinterpret_cast<const char*>(p.gate0 + (long long)z * p.gate_bs);
+    const char* g1base = reinterpret_cast<const char*>(p.gate1 + (long long)z * p.gate_bs);
+    u32x4 bv[4], g0[4], g1[4];
+    uint32_t ncb[4], colb[4];
+    bool nok[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int n8 = n_wave + (4 * e + fq) * 8;
+        nok[e] = n8 < p.N;                                       // N % 8 == 0 on this kernel's shapes (checked by the launcher)
+        ncb[e] = nok[e] ? (uint32_t)n8 * 2u : 0u;
+        colb[e] = (uint32_t)n8 * 2u;
+        if (p.n_split > 0) colb[e] = ((uint32_t)(n8 / p.n_split) * (uint32_t)p.c_split_stride + (uint32_t)(n8 % p.n_split)) * 2u;
+        bv[e] = has_bias ? *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(p.bias) + ncb[e]) : u32x4{0u, 0u, 0u, 0u};
+        if (has_gate) {
+            g0[e] = *reinterpret_cast<const u32x4*>(g0base + ncb[e]);
+            g1[e] = *reinterpret_cast<const u32x4*>(g1base + ncb[e]);
+        }
+    }
+#pragma unroll
+    for (int jb = 0; jb < 8; jb += JB) {
+        u32x4 rv[JB][4];
+        float rs[JB];
+        bool mok[JB];
+        uint32_t roff[JB], coff[JB];
+        // The accumulators stay in their AGPRs until the row blocks of this burst are due: an asm that takes them as "a" here
+        // makes every earlier copy of them pointless.  Without it hipcc's allocator opened the epilogue with over a hundred
+        // v_accvgpr_read at once (as many accumulators as VGPRs were free at that point) and then sent two lane constants
+        // to scratch.
+#pragma unroll
+        for (int jj = 0; jj < JB; ++jj)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) asm volatile("" : "+a"(acc[i][jb + jj]));
+#pragma unroll
+        for (int jj = 0; jj < JB; ++jj) {
+            const int m = m_wave + 16 * (jb + jj) + fr;
+            mok[jj] = m < p.M;
+            const uint32_t mc = mok[jj] ? (uint32_t)m : 0u;
+            rs[jj] = has_rs ? p.bias_rowscale[(long long)z * p.M + mc] : 1.0f;
+            // 32-bit byte offsets behind descriptors of 0x7fffffff records, as in every bf16 epilogue here: the host cuts a launch
+            // whose C or residual rows span 2 GiB into row chunks (gemm_row_chunks, gemm_common.h) before it gets here.  (The
+            // quantising epilogue below is never chunked and addresses through 64-bit pointers.)
+            roff[jj] = mc * (uint32_t)(p.ldres * 2);
+            coff[jj] = mc * (uint32_t)(p.ldc * 2);
+            if (has_res) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    rv[jj][e] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                        rsR, (mok[jj] && nok[e]) ? roff[jj] + ncb[e] : 0xffffffffu, 0, 0));
+            }
+        }
+#pragma unroll
+        for (int jj = 0; jj < JB; ++jj) {
+            const int j = jb + jj;
+            const int m = m_wave + 16 * j + fr;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float b8[8], v[8];
+                unpack8(bv[e], b8);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = p.alpha * apply_act<ACT>(fmaf(rs[jj], b8[i], acc[i][j][e]), p.leaky);
+                if (has_gate) {
+                    float g8[8];
+                    unpack8(m < p.gate_split ? g0[e] : g1[e], g8);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) v[i] *= g8[i];
+                }
+                if (has_res) {
+                    float r8[8];
+                    unpack8(rv[jj][e], r8);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) v[i] += r8[i];
+                }
+                __builtin_amdgcn_raw_buffer_store_b128(pack8(v), rsC, (mok[jj] && nok[e]) ? coff[jj] + colb[e] : 0xffffffffu, 0, 0);
+            }
+        }
+    }
+}
+
+// Quantising epilogue of one wave (bya_gemm_mx_quant, out e4m3): per element  v = bf16( alpha * act(acc + rowscale * bias) ),
+// then the block rule of mx_common.h.  MX block e of row 16 j + fr (32 columns from n_wave + 32 e) is the four lanes
+// fq = 0..3: |max| over the lane's eight values and its lane ^ 16 / lane ^ 32 partners, mx_quant8_bits on the eight values =
+// the lane's 8 code bytes at byte 8 fq of the block, one 8-byte store; the four scale bytes of a row's 128 columns leave as one
+// dword from the lane fq = 0.  Rows past M and columns past N (N % 128 == 0: whole 128-column groups) write nothing.  The
+// arithmetic per element is epilogue_mx_quant's (gemm_mx.hip), so the bytes are the 128 x 128 kernel's.
+template <int ACT>
+__device__ __forceinline__ void epilogue_mx_wide8_quant(const GemmArgs& p, uint8_t* __restrict__ qs, int z, int m_wave, int n_wave,
+                                                        int fr, int fq, const f32x4 (&acc)[8][8]) {
+    const bool has_bias = p.bias != nullptr, has_rs = p.bias_rowscale != nullptr;
+    const bool nok = n_wave < p.N;
+    uint8_t* const cbase = reinterpret_cast<uint8_t*>(p.C) + (long long)z * p.c_bs;
+    u32x4 bv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int n8 = n_wave + (4 * e + fq) * 8;
+        bv[e] = has_bias ? *reinterpret_cast<const u32x4*>(p.bias + (nok ? n8 : 0)) : u32x4{0u, 0u, 0u, 0u};
+    }
+    auto max16 = [](float x) {
+        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+        return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    };
+    auto max32 = [](float x) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+        return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    };
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int m = m_wave + 16 * j + fr;
+        const bool ok = m < p.M && nok;
+        const float rs = has_rs ? p.bias_rowscale[(long long)z * p.M + (m < p.M ? m : 0)] : 1.0f;
+        uint32_t sdword = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float b8[8], t[8], v[8];
+            unpack8(bv[e], b8);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) t[i] = p.alpha * apply_act<ACT>(fmaf(rs, b8[i], acc[i][j][e]), p.leaky);
+            unpack8(pack8(t), v);                                 // the one rounding to bf16
+            float amax = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
+            amax = max32(max16(amax));
+            uint32_t sbyte;
+            const uint64_t bits = mx_quant8_bits<MX_E4M3>(v, amax, sbyte);
+            sdword |= sbyte << (8 * e);
+            if (ok)
+                *reinterpret_cast<u32x2*>(cbase + (long long)m * p.ldc + n_wave + 32 * e + 8 * fq) =
+                    u32x2{(uint32_t)bits, (uint32_t)(bits >> 32)};
+        }
+        if (ok && fq == 0)
+            *reinterpret_cast<uint32_t*>(qs + ((long long)z * p.M + m) * (p.N / 32) + n_wave / 32) = sdword;
+    }
+}
+
+// QOUT = -1: the bf16 epilogue; MX_E4M3: the quantising one (C = codes with ldc / c_bs in bytes, qs = its scale bytes)
+template <int QOUT>
+__global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const uint8_t* __restrict__ sa,
+                                                            const uint8_t* __restrict__ sw, int tiles_m, int tiles_n, int batch,
+                                                            int GM, uint8_t* __restrict__ qs) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int BM = 256, BN = 256, STAGE = (BM + BN) * BK8, TILE_A = BM * BK8;
+    static_assert(STAGE == 65536 && SC_BASE == 2 * STAGE, "stage flip uses one address bit; the scales sit behind the codes");
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nk = p.K / BK8, ks = p.K / 32;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    const TileWalk<BM, BN> walk(tiles_m, tiles_n, batch, GM);
+    int seq = 0;
+    PersistentTile cur = walk.coord(seq);
+    if (!cur.valid) return;
+
+    // fragment read addresses (the LDS image: gemm_persistent.h; c*: the stage of the current K-tile).  The lane's scale byte
+    // is byte fq of the dword of row a_row (A) / slot row w_row (W), blocks 16 rows = 64 bytes apart (cSa / cSw, below)
+    const int a_row = wm * 128 + fr, w_row = wn * 128 + fr;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
+    uint32_t cAl = frag_addr(lds0, a_row, fq), cAh = frag_addr(lds0, a_row, 4 + fq);
+    uint32_t cWl = frag_addr(lds0 + TILE_A, w_row, fq);
+    uint32_t cWh = frag_addr(lds0 + TILE_A, w_row, 4 + fq);
+    uint32_t fill = __builtin_amdgcn_readfirstlane(lds0 + wave * 64 * 128);     // this wave's first A piece, current stage
+    uint32_t sfill = __builtin_amdgcn_readfirstlane(lds0 + SC_BASE + wave * 256);   // ... its A scale piece
+    // the lane's scale byte: byte fq of the dword of row a_row (A) / slot row w_row (W), blocks 16 rows = 64 bytes apart
+    uint32_t cSa = lds0 + SC_BASE + 4 * a_row + fq, cSw = lds0 + SC_BASE + SC_W + 4 * w_row + fq;
+
+    // staging (map and source-side swizzle: gemm_persistent.h): wave w moves LDS slot rows [64w, 64w + 64) of the A tile and
+    // of the W tile, 8 one-KiB pieces each, and their scale dwords, lane l = slot row 64w + l
+    uint32_t voA[8], voW[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int rl = wave * 64 + q * 8 + (lane >> 3);
+        voA[q] = stage_off(lane, rl, rl, (uint32_t)p.lda);
+        voW[q] = stage_off(lane, rl, w_slot_col(rl), (uint32_t)p.ldw);
+    }
+    const uint32_t voSa = (uint32_t)(wave * 64 + lane) * (uint32_t)ks;
+    const uint32_t voSw = (uint32_t)w_slot_col(wave * 64 + lane) * (uint32_t)ks;
+    const uint8_t* const A8 = reinterpret_cast<const uint8_t*>(p.A);
+    const uint8_t* const W8 = reinterpret_cast<const uint8_t*>(p.W);
+    i32x4 rsA = tile_rsrc_a(p, A8, cur), rsW = tile_rsrc_w(p, W8, cur);
+    i32x4 rsSa = tile_rsrc_sa(p, sa, ks, cur), rsSw = tile_rsrc_sw(p, sw, ks, cur);
+
+#define DMA_A(Q, BASE, VO, RS, SOFF) DMA_PIECE(Q, BASE, VO, RS, SOFF)
+#define DMA_W(Q, BASE, VO, RS, SOFF) DMA_PIECE(Q, (BASE) + TILE_A, VO, RS, SOFF)
+#define DMA_SA(BASE, RS, SOFF) dma_scale_piece<0>(BASE, voSa, RS, SOFF)
+#define DMA_SW(BASE, RS, SOFF) dma_scale_piece<SC_W>(BASE, voSw, RS, SOFF)
+    // ---- prologue of the FIRST tile only: K-tiles 0 and 1
+    ALL8(DMA_A, fill, voA, rsA, 0u);
+    ALL8(DMA_W, fill, voW, rsW, 0u);
+    DMA_SA(sfill, rsSa, 0u);
+    DMA_SW(sfill, rsSw, 0u);
+    ALL8(DMA_A, fill ^ STAGE, voA, rsA, (uint32_t)BK8);
+    ALL8(DMA_W, fill ^ STAGE, voW, rsW, (uint32_t)BK8);
+    DMA_SA(sfill ^ SC_STAGE, rsSa, 4u);
+    DMA_SW(sfill ^ SC_STAGE, rsSw, 4u);
+    asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
+
+    f32x4 acc[8][8];
+    i32x4 al[8], ah[8], wl[8], wh[8];            // low / high 16 bytes of the A (row block j) and W (column block i) fragments
+    int xa[8], xw[8];                            // their scale bytes for this lane's K-block fq, in byte 0
+
+    for (;;) {
+        // ---- K-tile 0 of this output tile has landed for this wave (prologue wait / the wait in front of the previous
+        // epilogue); make that true for everybody, then fetch its A fragments and W(0..3), each with its scale
+        asm volatile("s_barrier" ::: "memory");
+#define RAF(J, LO, HI, SC) do { ds_read128<(J) * 2048>(al[J], LO); ds_read128<(J) * 2048>(ah[J], HI); ds_read_byte<(J) * 64>(xa[J], SC); } while (0)
+#define RWF(I, LO, HI, SC) do { ds_read128<(I) * 2048>(wl[I], LO); ds_read128<(I) * 2048>(wh[I], HI); ds_read_byte<(I) * 64>(xw[I], SC); } while (0)
+        RAF(0, cAl, cAh, cSa); RAF(1, cAl, cAh, cSa); RAF(2, cAl, cAh, cSa); RAF(3, cAl, cAh, cSa);
+        RAF(4, cAl, cAh, cSa); RAF(5, cAl, cAh, cSa); RAF(6, cAl, cAh, cSa); RAF(7, cAl, cAh, cSa);
+        RWF(0, cWl, cWh, cSw); RWF(1, cWl, cWh, cSw); RWF(2, cWl, cWh, cSw); RWF(3, cWl, cWh, cSw);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+        const PersistentTile nxt = walk.coord(seq + 1);
+        const i32x4 rsAn = tile_rsrc_a(p, A8, nxt), rsWn = tile_rsrc_w(p, W8, nxt);
+        const i32x4 rsSan = tile_rsrc_sa(p, sa, ks, nxt), rsSwn = tile_rsrc_sw(p, sw, ks, nxt);
+
+        // One K-tile, variant V (gemm_fp8_v4.hip); t = its index inside the output tile.
+        auto ktile = [&](int t, auto v_c) {
+            constexpr char V = decltype(v_c)::value;
+            const uint32_t soff = (uint32_t)((t + 2) * BK8), ssoff = (uint32_t)((t + 2) * 4);
+            const uint32_t nAl = cAl ^ STAGE, nAh = cAh ^ STAGE, nWl = cWl ^ STAGE, nWh = cWh ^ STAGE;
+            const uint32_t nSa = cSa ^ SC_STAGE, nSw = cSw ^ SC_STAGE;
+#define OPW(I) __builtin_shufflevector(wl[I], wh[I], 0, 1, 2, 3, 4, 5, 6, 7)
+#define OPA(J) __builtin_shufflevector(al[J], ah[J], 0, 1, 2, 3, 4, 5, 6, 7)
+#define MFX(I, J) do {                                                                                                   \
+                if constexpr (V == 'A')                                                                                    \
+                    asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, 0, %3, %4 op_sel_hi:[0,0,0]"               \
+                                 : "=a"(acc[I][J]) : "v"(OPW(I)), "v"(OPA(J)), "v"(xw[I]), "v"(xa[J]));                    \
+                else                                                                                                       \
+                    asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]"              \
+                                 : "+a"(acc[I][J]) : "v"(OPW(I)), "v"(OPA(J)), "v"(xw[I]), "v"(xa[J]));                    \
+            } while (0)
+            // one LDS-DMA piece: K-tile t + 2 of this tile, or the next tile's first two
+#define PIECE(Q, IS_W) do {                                                                                              \
+                if constexpr (V == 'C') { if (IS_W) DMA_W(Q, fill, voW, rsWn, 0u); else DMA_A(Q, fill, voA, rsAn, 0u); }  \
+                else if constexpr (V == 'D') { if (IS_W) DMA_W(Q, fill, voW, rsWn, (uint32_t)BK8); else DMA_A(Q, fill, voA, rsAn, (uint32_t)BK8); } \
+                else { if (IS_W) DMA_W(Q, fill, voW, rsW, soff); else DMA_A(Q, fill, voA, rsA, soff); }                   \
+            } while (0)
+#define SPIECE(IS_W) do {                                                                                                \
+                if constexpr (V == 'C') { if (IS_W) DMA_SW(sfill, rsSwn, 0u); else DMA_SA(sfill, rsSan, 0u); }            \
+                else if constexpr (V == 'D') { if (IS_W) DMA_SW(sfill, rsSwn, 4u); else DMA_SA(sfill, rsSan, 4u); }       \
+                else { if (IS_W) DMA_SW(sfill, rsSw, ssoff); else DMA_SA(sfill, rsSa, ssoff); }                           \
+            } while (0)
+            // B1: this K-tile's stage is free (W(4..7) and their scales, the last reads of it, have returned for every wave)
+#define B1() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+            // B2: K-tile t + 1 has landed for everybody (N = the pieces of K-tile t + 2 requested so far in this K-tile)
+#define B2(N) do { if constexpr (V != 'D') asm volatile("s_waitcnt vmcnt(" #N ")\n\ts_barrier" ::: "memory"); } while (0)
+#define REREAD_W() do { if constexpr (V != 'D') { RWF(0, nWl, nWh, nSw); RWF(1, nWl, nWh, nSw); RWF(2, nWl, nWh, nSw); RWF(3, nWl, nWh, nSw); } } while (0)
+#define REREAD_A(J) do { if constexpr (V != 'D') RAF(J, nAl, nAh, nSa); } while (0)
+            // GENERATED-BEGIN (tools/gen_gemm_mx_schedule.py)
+            RWF(4, cWl, cWh, cSw);
+            MFX(0, 0); RWF(5, cWl, cWh, cSw);
+            MFX(1, 0); RWF(6, cWl, cWh, cSw);
+            MFX(2, 0); RWF(7, cWl, cWh, cSw);
+            MFX(3, 0);
+            MFX(0, 1);
+            MFX(1, 1);
+            MFX(2, 1);
+            MFX(3, 1);
+            MFX(0, 2);
+            MFX(1, 2); B1();
+            MFX(2, 2); PIECE(0, false);
+            MFX(3, 2);
+            MFX(0, 3);
+            MFX(1, 3); PIECE(1, false);
+            MFX(2, 3);
+            MFX(3, 3);
+            MFX(0, 4); PIECE(2, false);
+            MFX(1, 4);
+            MFX(2, 4);
+            MFX(3, 4); PIECE(3, false);
+            MFX(0, 5);
+            MFX(1, 5);
+            MFX(2, 5); PIECE(4, false);
+            MFX(3, 5);
+            MFX(0, 6);
+            MFX(1, 6); PIECE(5, false);
+            MFX(2, 6);
+            MFX(3, 6);
+            MFX(0, 7); PIECE(6, false);
+            MFX(1, 7);
+            MFX(2, 7); B2(7);
+            MFX(3, 7); REREAD_W();
+            MFX(4, 0); PIECE(7, false);
+            MFX(5, 0);
+            MFX(6, 0);
+            MFX(7, 0); PIECE(0, true); REREAD_A(0);
+            MFX(4, 1);
+            MFX(5, 1);
+            MFX(6, 1); PIECE(1, true);
+            MFX(7, 1); REREAD_A(1);
+            MFX(4, 2);
+            MFX(5, 2); PIECE(2, true);
+            MFX(6, 2);
+            MFX(7, 2); REREAD_A(2);
+            MFX(4, 3); PIECE(3, true);
+            MFX(5, 3);
+            MFX(6, 3);
+            MFX(7, 3); PIECE(4, true); REREAD_A(3);
+            MFX(4, 4);
+            MFX(5, 4);
+            MFX(6, 4); PIECE(5, true);
+            MFX(7, 4); REREAD_A(4);
+            MFX(4, 5);
+            MFX(5, 5); PIECE(6, true);
+            MFX(6, 5);
+            MFX(7, 5); REREAD_A(5);
+            MFX(4, 6); PIECE(7, true);
+            MFX(5, 6);
+            MFX(6, 6);
+            MFX(7, 6); SPIECE(false); REREAD_A(6);
+            MFX(4, 7);
+            MFX(5, 7);
+            MFX(6, 7); SPIECE(true);
+            MFX(7, 7); REREAD_A(7);
+            // GENERATED-END
+#undef B1
+#undef B2
+#undef REREAD_W
+#undef REREAD_A
+            // the next K-tile starts with A(0) and W(0..3): everything but A(7)'s three reads (LDS returns in order; they are
+            // covered by that K-tile's wait in front of B1)
+            if constexpr (V != 'D') asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
+            cAl ^= STAGE; cAh ^= STAGE; cWl ^= STAGE; cWh ^= STAGE; fill ^= STAGE;
+            cSa ^= SC_STAGE; cSw ^= SC_STAGE; sfill ^= SC_STAGE;
+            KEEP8(al); KEEP8(ah); KEEP8(wl); KEEP8(wh); KEEP8(xa); KEEP8(xw);
+#undef SPIECE
+#undef PIECE
+#undef MFX
+#undef OPA
+#undef OPW
+        };
+        ktile(0, IntTag<'A'>{});
+        for (int t = 1; t + 2 < nk; ++t) ktile(t, IntTag<'B'>{});
+        ktile(nk - 2, IntTag<'C'>{});
+        ktile(nk - 1, IntTag<'D'>{});
+#undef RAF
+#undef RWF
+        // K-tile 0 of the next output tile (18 pieces, requested during variant C) has landed once all but the 18 younger
+        // pieces of its K-tile 1 have; the MFMAs are inline asm, so pad their last results before the epilogue reads them
+        asm volatile("s_waitcnt vmcnt(18)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+
+        auto run = [&](auto act_tag) {
+            if constexpr (QOUT == -1)
+                epilogue_mx_wide8<decltype(act_tag)::value, 2>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc);
+            else
+                epilogue_mx_wide8_quant<decltype(act_tag)::value>(p, qs, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc);
+        };
+        dispatch_act_big(p.act, run);
+
+        if (!nxt.valid) break;
+        ++seq;
+        cur = nxt;
+        rsA = rsAn;
+        rsW = rsWn;
+        rsSa = rsSan;
+        rsSw = rsSwn;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the (empty-descriptor) prefetch pieces of the tile after the last
+}
+
+}  // namespace
+
+// Is the persistent MX kernel applicable?  The rules of bya_gemm256p_fp8_eligible (16-byte epilogue accesses aligned, at least
+// four K-tiles, 16-byte operand rows); quant: C = the codes, ldc / c_bs in bytes (bya_gemm_mx_quant has checked their
+// 16-byte alignment and N % 128 == 0)
+bool bya_gemm256p_mx_eligible(const void* args, bool quant) {
+    const GemmArgs& a = *static_cast<const GemmArgs*>(args);
+    if (!(a.K % BK8 == 0 && a.K >= 4 * BK8 && a.N % 8 == 0 && a.lda % 16 == 0 && a.ldw % 16 == 0 &&
+          (long long)a.M * a.lda < (1LL << 32) && (long long)a.N * a.ldw < (1LL << 32)))
+        return false;
+    if (quant) return a.N % 128 == 0 && a.ldc % 16 == 0 && a.c_bs % 16 == 0 && !(((uintptr_t)a.C | (uintptr_t)a.bias) & 15);
+    return a.n_split % 8 == 0 && a.ldc % 8 == 0 && (!a.res || a.ldres % 8 == 0) &&
+        !(((uintptr_t)a.C | (uintptr_t)a.res | (uintptr_t)a.bias | (uintptr_t)a.gate0 | (uintptr_t)a.gate1) & 15) &&
+        a.c_bs % 8 == 0 && a.res_bs % 8 == 0 && a.gate_bs % 8 == 0 && a.c_split_stride % 8 == 0;
+}
+
+// sa / sw: the e8m0 scale bytes [batch * M, K / 32] / [N, K / 32]; qs: the scale bytes of the quantising epilogue, or null
+int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int batch, int gm, hipStream_t s) {
+    const GemmArgs& a = *static_cast<const GemmArgs*>(args);
+    const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
+    const size_t lds = SC_BASE + 2 * SC_STAGE;
+    const int grid = persistent_grid((long long)tiles_m * tiles_n * batch);
+    if (qs)
+        return launch_persistent<gemm256p_mx_kernel<MX_E4M3>>(grid, 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch, gm < 1 ? 1 : gm, qs);
+    return launch_persistent<gemm256p_mx_kernel<-1>>(grid, 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch, gm < 1 ? 1 : gm, qs);
+}

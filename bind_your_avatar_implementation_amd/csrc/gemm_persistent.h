@@ -1,7 +1,8 @@
 // What the persistent one-wave-per-SIMD kernels share AROUND their hand-placed K-loops: the XCD-contiguous group-M tile walk,
 // the staging map, the buffer-descriptor and LDS-DMA helpers, the piece / fragment macro families, the launcher tail -- and
 // the description of the LDS image of a K-tile that staging, fragment reads and epilogues have to agree on.
-// Users: gemm_v4.hip (256 x 256 bf16), gemm_v5.hip / gemm_v6.hip (128 x 256 bf16), gemm_fp8_v4.hip (256 x 256 e4m3), attn_w4.hip
+// Users: gemm_v4.hip (256 x 256 bf16), gemm_v5.hip / gemm_v6.hip (128 x 256 bf16), gemm_fp8_v4.hip (256 x 256 e4m3),
+// gemm_mx_v4.hip (256 x 256 e4m3 with e8m0 block scales), attn_w4.hip
 // (descriptors, LDS-DMA, XCD range) and attn.hip (XCD range).  The K-loops, their schedules and their rings stay in those files.
 //
 // THE LDS IMAGE OF A K-TILE (the contract between staging, fragment reads and gemm_wide_epilogue.h -- written down here only)

@@ -110,6 +110,12 @@ class DenoiseEngine:
         # ... and the q|k|v projection norms and rotates q and k in its own epilogue (bya_gemm_mx_qkv_norm_rope: bit for bit the
         # GEMM + bya_qknorm_rope) when "qkv" is an MX Linear; enable_mx_weights(fuse_qk_norm=True), off by default
         self.mx_fuse_qk_norm = self.mx_fmt is not None and bool(getattr(model, "_mx_fuse_qk_norm", False))
+        # ... and the MX Linear launches run under library option mx_kernel (1, or 2 for "always") when activations and weights
+        # are both "mxfp8": the persistent 256 x 256 kernel where a launch fills it, the same bits;
+        # enable_mx_weights(persistent_gemm=True), off by default
+        pg = getattr(model, "_mx_persistent_gemm", False)
+        mx8 = self.mx_fmt == "mxfp8" and self.mx_wfmt == "mxfp8"
+        self.mx_kernel = (2 if pg == "always" else 1) if (pg and mx8) else 0
         # the remaining A/B switches of the step, read ONCE here (round 4 looked them up in os.environ on every step / call)
         self.side_stream_conditioning = os.environ.get("BYA_INVARIANTS_SIDE_STREAM", "1") != "0"
         self.sp_allgather = os.environ.get("BYA_SP_ALLGATHER", "0") == "1"       # exchange A as a K/V all-gather (A/B)
@@ -350,7 +356,8 @@ class DenoiseEngine:
                 quantised = ops.quantize_mx(a, self.mx_fmt, *self._amx(a.shape))
             codes, sa = quantised
             wc, sw = self.wmx[which][i]
-            return ops.gemm_mx(codes, sa.view(*a.shape[:-1], -1), wc, sw, out, self.mx_fmt, w_fmt=self.mx_wfmt, **kw)
+            with self._mx_kernel_option():
+                return ops.gemm_mx(codes, sa.view(*a.shape[:-1], -1), wc, sw, out, self.mx_fmt, w_fmt=self.mx_wfmt, **kw)
         if self.w8 is None or which not in self.w8:
             return ops.gemm(a, w, out, **kw)
         if quantised is None:
@@ -358,6 +365,10 @@ class DenoiseEngine:
         a8, sa = quantised
         w8, sw = self.w8[which][i]
         return ops.gemm_fp8(a8.view(*a.shape), sa.view(*a.shape[:-1]), w8, sw, out, **kw)
+
+    def _mx_kernel_option(self):
+        """The library option block of an MX Linear launch: mx_kernel as enable_mx_weights(persistent_gemm=...) asked."""
+        return ops.options(mx_kernel=self.mx_kernel) if self.mx_kernel else contextlib.nullcontext()
 
     def _ff_pair_fused(self):
         """Whether ff.net.0's launch writes ff.net.2's MX operand (both MX Linears, and the switch on)."""
@@ -384,8 +395,9 @@ class DenoiseEngine:
         codes, sa = quantised
         wc, sw = self.wmx["ff1"][i]
         oc, osc = self._amx(out_shape)
-        return ops.gemm_mx_quant(codes, sa.view(*a.shape[:-1], -1), wc, sw, oc, osc, self.mx_fmt, w_fmt=self.mx_wfmt,
-                                 out_fmt=self.mx_fmt, bias=bias, act="gelu_tanh")
+        with self._mx_kernel_option():
+            return ops.gemm_mx_quant(codes, sa.view(*a.shape[:-1], -1), wc, sw, oc, osc, self.mx_fmt, w_fmt=self.mx_wfmt,
+                                     out_fmt=self.mx_fmt, bias=bias, act="gelu_tanh")
 
     def _ln_linear(self, which, i, x, xn, norm, w, out, **kw):
         """LayerNorm(x) -> Linear for the perceiver / audio query projections (models/router.py:246-253,

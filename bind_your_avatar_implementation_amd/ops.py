@@ -705,7 +705,8 @@ def gemm_mx(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, r
 
 def gemm_mx_plan(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, res=None, gate0=None, gate1=None,
                  gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0, w_fmt=None):
-    """What ``gemm_mx`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations only)."""
+    """What ``gemm_mx`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations only), or "p256"
+    (mxfp8 activations and weights under option ``mx_kernel``)."""
     lib = _hip.load()
     code, wcode = mx_fmt_pair(fmt, w_fmt)
     d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
@@ -826,7 +827,8 @@ def gemm_mx_quant(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, f
 
 def gemm_mx_quant_plan(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt="mxfp6", w_fmt=None, out_fmt=None,
                        bias=None, act=None, alpha=1.0):
-    """What ``gemm_mx_quant`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations only)."""
+    """What ``gemm_mx_quant`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations only), or
+    "p256" (mxfp8 activations, weights and output under option ``mx_kernel``)."""
     lib = _hip.load()
     code, wcode = mx_fmt_pair(fmt, w_fmt)
     out_fmt = fmt if out_fmt is None else out_fmt

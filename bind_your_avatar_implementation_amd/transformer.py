@@ -382,7 +382,7 @@ class BindyouravatarTransformer3DModel(nn.Module):
 
     def enable_mx_weights(self, fmt: str = "mxfp6", enabled: bool = True, linears=None, weight_format=None, *,
                           fuse_activation_quant: bool = True, fuse_attention_quant: bool = False,
-                          fuse_qk_norm: bool = False):
+                          fuse_qk_norm: bool = False, persistent_gemm=False):
         """Run the selected Linears on OCP MX operands: 32-element blocks along K with one e8m0 scale each, applied by
         gfx950's block-scaled matrix instruction (include/bya.h, "MX weights").  ``fmt``: "mxfp6" (e2m3 elements, the
         instruction's fastest dense rate) or "mxfp8" (e4m3 elements, the more accurate).  Weights are quantised when the
@@ -399,13 +399,20 @@ class BindyouravatarTransformer3DModel(nn.Module):
         ``fuse_qk_norm`` (keyword only, a bool): when attn1.to_q|k|v is an MX Linear fed by the LayerNorm-fused quantiser, its
         GEMM norms and rotates q and k in its own epilogue (bya_gemm_mx_qkv_norm_rope) instead of writing them in bf16 for a
         bya_qknorm_rope launch to read and rewrite -- the same bits; off by default (opt-in; a layer whose attention wants
-        the norm statistics keeps the two launches).  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
+        the norm statistics keeps the two launches).
+        ``persistent_gemm`` (keyword only; False, True or "always"): with "mxfp8" activations and weights, the MX Linear
+        launches (bya_gemm_mx, bya_gemm_mx_quant) are issued under library option mx_kernel = 1 -- those that fill it run on
+        the persistent one-wave-per-SIMD 256 x 256 kernel (csrc/gemm_mx_v4.hip), the same bits -- or, "always" (tests),
+        mx_kernel = 2: every eligible launch does.  Off by default; with "mxfp6" activations or "mxfp4" weights the switch
+        does nothing.  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
         counterpart (the reference is bf16/fp16 only); returns self."""
         from .ops import MX_FORMATS, MX_WEIGHT_FORMATS
         if not isinstance(fuse_attention_quant, bool):
             raise TypeError(f"fuse_attention_quant: expected a bool, got {type(fuse_attention_quant).__name__}")
         if not isinstance(fuse_qk_norm, bool):
             raise TypeError(f"fuse_qk_norm: expected a bool, got {type(fuse_qk_norm).__name__}")
+        if persistent_gemm not in (False, True, "always"):
+            raise ValueError(f"persistent_gemm: expected False, True or 'always', got {persistent_gemm!r}")
         if fmt not in MX_FORMATS:
             raise ValueError(f"MX format {fmt!r}: expected one of {sorted(MX_FORMATS)}")
         if weight_format is not None and weight_format not in MX_WEIGHT_FORMATS:
@@ -418,6 +425,11 @@ class BindyouravatarTransformer3DModel(nn.Module):
         self._mx_fuse_activation_quant = bool(fuse_activation_quant)
         self._mx_fuse_attention_quant = fuse_attention_quant
         self._mx_fuse_qk_norm = fuse_qk_norm
+        # (set only when on -- absent means off: the attributes a call without the keyword sets are those it always set)
+        if enabled and persistent_gemm:
+            self._mx_persistent_gemm = persistent_gemm
+        elif hasattr(self, "_mx_persistent_gemm"):
+            del self._mx_persistent_gemm
         self.invalidate_engine()
         return self
 

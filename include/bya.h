@@ -62,7 +62,10 @@ enum bya_option {
     BYA_OPT_P2P_GROUPS = 6,       /* workgroups of a push / exchange launch (16..1024); 0 = the built-in default */
     BYA_OPT_REFERENCE_FORMS = 7,  /* bit mask, tests only: take the OLDER kernel form of an A/B the docs call closed; every
                                      form pair is bit-identical, which is what the tests that set these bits assert */
-    BYA_OPT_COUNT = 8
+    BYA_OPT_MX_KERNEL = 8,        /* 0 (default): every MX GEMM on the tiled kernels of csrc/gemm_mx.hip; 1: e4m3 x e4m3 launches that
+                                     fill the persistent 256 x 256 kernel (csrc/gemm_mx_v4.hip: at least 200 of its tiles, batch
+                                     included, and eligible) run on it -- the same bits; 2 (tests): as 1 without the tile count */
+    BYA_OPT_COUNT = 9
 };
 enum { BYA_REF_ROWGEMM_CHUNKED = 1,    /* N = 512 row GEMM: chunk-balanced kernel instead of the W-stationary one */
        BYA_REF_KV_MIX_GENERIC = 2,     /* bya_attn_kv_mix: the generic kernel instead of the <= 32-key one */
@@ -163,7 +166,9 @@ int bya_gemm_workspace_status(int32_t* timeouts, hipStream_t stream);
 #define BYA_GEMM_PATH_T128X128 1  /* 128 x 128 tiles, 4 waves (gemm_tile = 1); bya_gemm_fp8 / bya_gemm_mx: their 128 x 128 kernel */
 #define BYA_GEMM_PATH_T256X128 2  /* 256 x 128 tiles, 8 waves (gemm_tile = 2) */
 #define BYA_GEMM_PATH_T256X256 3  /* 256 x 256 tiles, 8 waves (gemm_tile = 3); bya_gemm_mx: the 256 x 256 kernel of e2m3 activations */
-#define BYA_GEMM_PATH_P256 4      /* persistent 256 x 256 (csrc/gemm_v4.hip); bya_gemm_fp8: csrc/gemm_fp8_v4.hip */
+#define BYA_GEMM_PATH_P256 4      /* persistent 256 x 256 (csrc/gemm_v4.hip); bya_gemm_fp8: csrc/gemm_fp8_v4.hip; bya_gemm_mx /
+                                     bya_gemm_mx_mixed / bya_gemm_mx_quant (out e4m3) under option mx_kernel, e4m3 x e4m3 only:
+                                     csrc/gemm_mx_v4.hip.  bya_gemm_mx_qkv_norm_rope never takes it */
 #define BYA_GEMM_PATH_P128 5      /* persistent 128 x 256 (csrc/gemm_v5.hip) */
 #define BYA_GEMM_PATH_P128S 6     /* persistent 128 x 256 with loader waves (csrc/gemm_v6.hip) */
 #define BYA_GEMM_PATH_W8_256 7    /* the 8-wave 256 x 256 kernel P256 falls back to (fewer than 3 K-tiles, a C / res / bias /
@@ -294,28 +299,33 @@ int bya_layernorm_mx(const void* x, void* q, void* q_scales, const void* w, cons
 int bya_gemm_mx(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, void* C,
                 const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* desc, int32_t fmt,
                 hipStream_t stream);
-/* its kernel (bya_gemm_bf16_plan): path T128X128 (both formats) or T256X256 (e2m3 only) */
+/* its kernel (bya_gemm_bf16_plan): path T128X128 (both formats) or T256X256 (e2m3 only); with option BYA_OPT_MX_KERNEL at 1 a
+ * launch with e4m3 activations AND weights takes path P256 (csrc/gemm_mx_v4.hip, the same bits) when it has at least 200 tiles of
+ * 256 x 256, batch included, and is eligible -- K % 128 == 0, K >= 512, N % 8 == 0, C / res / bias / gates 16-byte aligned,
+ * checked per row chunk; at 2 (tests): without the tile count */
 int bya_gemm_mx_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
                      const void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* desc,
                      int32_t fmt, bya_gemm_plan* plan);
 int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, void* C,
                       const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* desc, int32_t a_fmt,
                       int32_t w_fmt, hipStream_t stream);
-/* its kernel: path T128X128, or T256X256 for e2m3 activations (bya_gemm_mx_plan's rule, whatever w_fmt) */
+/* its kernel: path T128X128, or T256X256 for e2m3 activations (bya_gemm_mx_plan's rule, whatever w_fmt); P256 under option
+ * BYA_OPT_MX_KERNEL only with a_fmt == w_fmt == e4m3 */
 int bya_gemm_mx_mixed_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
                            const void* C, const void* res, const void* gate0, const void* gate1,
                            const bya_gemm_desc* desc, int32_t a_fmt, int32_t w_fmt, bya_gemm_plan* plan);
 int bya_gemm_mx_quant(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
                       void* q_codes, void* q_scales, const bya_gemm_desc* desc, int32_t a_fmt, int32_t w_fmt,
                       int32_t out_fmt, hipStream_t stream);
-/* its kernel: bya_gemm_mx_mixed_plan's rule (path T128X128, or T256X256 for e2m3 activations); never cut into row chunks */
+/* its kernel: bya_gemm_mx_mixed_plan's rule (path T128X128, or T256X256 for e2m3 activations; P256 under option
+ * BYA_OPT_MX_KERNEL when out_fmt is e4m3 as well -- out_fmt e2m3 stays on the 128 x 128 kernel); never cut into row chunks */
 int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
                            const void* q_codes, const void* q_scales, const bya_gemm_desc* desc, int32_t a_fmt,
                            int32_t w_fmt, int32_t out_fmt, bya_gemm_plan* plan);
 int bya_gemm_mx_qkv_norm_rope(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
                               void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* desc, const bya_qknorm_desc* norm,
                               hipStream_t stream);
-/* its kernel: bya_gemm_mx_mixed_plan's rule (path T128X128, or T256X256 for e2m3 activations); always one launch;
+/* its kernel: path T128X128, or T256X256 for e2m3 activations, whatever option BYA_OPT_MX_KERNEL says; always one launch;
  * BYA_ERR_UNSUPPORTED where the entry point declines the shape */
 int bya_gemm_mx_qkv_norm_rope_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
                                    const void* bias, const void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* desc,
