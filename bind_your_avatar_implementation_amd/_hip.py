@@ -98,6 +98,10 @@ SIGNATURES = {
     "bya_gemm_mx_qkv_norm_rope": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _vp],
     "bya_gemm_mx_qkv_norm_rope_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc),
                                        _c.POINTER(GemmPlan)],
+    "bya_gemm_mx_qkv_norm_rope_on": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _i32,
+                                     _vp],
+    "bya_gemm_mx_qkv_norm_rope_on_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc),
+                                          _i32, _c.POINTER(GemmPlan)],
     "bya_linear_small_m": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "bya_timestep_features": [_vp, _vp, _i32, _i32, _i32, _f32, _vp],
     "bya_layernorm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,

@@ -33,9 +33,10 @@
 #include "qknorm_math.h"
 
 // defined in gemm_mx_v4.hip (accumulators in AGPRs): the persistent one-wave-per-SIMD 256 x 256 kernel for e4m3 x e4m3, plain
-// (qs null) or quantising (out e4m3) epilogue
+// (qs null) or quantising (out e4m3) epilogue; _qkn: the q/k-norm epilogue (GemmArgs::qkn_*)
 bool bya_gemm256p_mx_eligible(const void* args, bool quant);
 int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int batch, int gm, hipStream_t s);
+int bya_launch_gemm256p_mx_qkn(const void* args, const uint8_t* sa, const uint8_t* sw, int batch, int gm, hipStream_t s);
 
 namespace {
 
@@ -834,6 +835,46 @@ extern "C" int bya_gemm_mx_qkv_norm_rope_plan(const void* A, const void* a_scale
     const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
     if (rc != BYA_OK) return rc;
     p->path = mx_path(a, d->batch, fmt);
+    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = 1;
+    return BYA_OK;
+}
+
+namespace {
+// bya_gemm_mx_qkv_norm_rope_on's kernel: the argument `kernel` (1; 2: without the tile count) asks for the persistent kernel of
+// gemm_mx_v4.hip, taken for e4m3 x e4m3 by mx_path_p256's rule -- but by the ARGUMENT: no option is read here
+inline int mx_qkn_path_on(const GemmArgs& a, int batch, int32_t fmt, int32_t w_fmt, int32_t kernel) {
+    const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
+    if (kernel != 0 && fmt == MX_E4M3 && w_fmt == MX_E4M3 && (kernel == 2 || tiles256 >= 200) && bya_gemm256p_mx_eligible(&a, false))
+        return BYA_GEMM_PATH_P256;
+    return mx_path(a, batch, fmt);
+}
+}  // namespace
+
+// bya_gemm_mx_qkv_norm_rope with the kernel named by an argument: 0 = that entry point; 1 = the persistent 256 x 256 kernel
+// (gemm256p_mx_kernel<MX_EPI_QKN>, the same bits) where the launch fills it and is eligible, else the tiled one; 2 (tests):
+// without the tile count.  Always one launch; the errors of bya_gemm_mx_qkv_norm_rope.
+extern "C" int bya_gemm_mx_qkv_norm_rope_on(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                            const void* bias, void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* d,
+                                            const bya_qknorm_desc* n, int32_t kernel, hipStream_t stream) {
+    if (kernel < 0 || kernel > 2) return BYA_ERR_SHAPE;
+    if (kernel == 0) return bya_gemm_mx_qkv_norm_rope(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, stream);
+    GemmArgs a;
+    const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
+    if (rc != BYA_OK) return rc;
+    if (mx_qkn_path_on(a, d->batch, fmt, w_fmt, kernel) != BYA_GEMM_PATH_P256)
+        return bya_gemm_mx_qkv_norm_rope(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, stream);
+    return bya_launch_gemm256p_mx_qkn(&a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, d->batch, MX_P256_GROUP_M, stream);
+}
+
+extern "C" int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                                 const void* bias, const void* C, int32_t fmt, int32_t w_fmt,
+                                                 const bya_gemm_desc* d, const bya_qknorm_desc* n, int32_t kernel,
+                                                 bya_gemm_plan* p) {
+    if (!p || kernel < 0 || kernel > 2) return BYA_ERR_SHAPE;
+    GemmArgs a;
+    const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
+    if (rc != BYA_OK) return rc;
+    p->path = mx_qkn_path_on(a, d->batch, fmt, w_fmt, kernel);
     p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = 1;
     return BYA_OK;
 }

@@ -108,7 +108,8 @@ class DenoiseEngine:
         # 3072-wide quantiser) when to_out is an MX Linear; enable_mx_weights(fuse_attention_quant=True), off by default
         self.mx_fuse_attn_quant = self.mx_fmt is not None and bool(getattr(model, "_mx_fuse_attention_quant", False))
         # ... and the q|k|v projection norms and rotates q and k in its own epilogue (bya_gemm_mx_qkv_norm_rope: bit for bit the
-        # GEMM + bya_qknorm_rope) when "qkv" is an MX Linear; enable_mx_weights(fuse_qk_norm=True), off by default
+        # GEMM + bya_qknorm_rope) when "qkv" is an MX Linear; enable_mx_weights(fuse_qk_norm=True), off by default.  With
+        # persistent_gemm on top (mx_kernel, below) that launch runs on the persistent kernel too
         self.mx_fuse_qk_norm = self.mx_fmt is not None and bool(getattr(model, "_mx_fuse_qk_norm", False))
         # ... and the MX Linear launches run under library option mx_kernel (1, or 2 for "always") when activations and weights
         # are both "mxfp8": the persistent 256 x 256 kernel where a launch fills it, the same bits;
@@ -341,7 +342,8 @@ class DenoiseEngine:
             wc, sw = self.wmx["qkv"][i]
             if ops.gemm_mx_qkv_norm_rope(xq[0], xq[1].view(*xn.shape[:-1], -1), wc, sw, out, self.qkv_b[i], split,
                                          at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin, text_rows,
-                                         eps=at.norm_q.eps, k_scale=self.k_scale, fmt=self.mx_fmt, w_fmt=self.mx_wfmt):
+                                         eps=at.norm_q.eps, k_scale=self.k_scale, fmt=self.mx_fmt, w_fmt=self.mx_wfmt,
+                                         kernel=self.mx_kernel):
                 return
         self._dit_linear("qkv", i, xn, self.qkv_w[i], out, bias=self.qkv_b[i], split=split, quantised=xq)
         ops.qknorm_rope(q_view, k_view, at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin,

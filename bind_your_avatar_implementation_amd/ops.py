@@ -737,11 +737,13 @@ def _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, 
 
 
 def gemm_mx_qkv_norm_rope(a_codes, a_scales, w_codes, w_scales, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows,
-                          eps=1e-6, k_scale=1.0, tensors=3, fmt="mxfp6", w_fmt=None):
+                          eps=1e-6, k_scale=1.0, tensors=3, fmt="mxfp6", w_fmt=None, kernel=0):
     """The packed q|k|v projection on MX operands with the q/k LayerNorm(64) + RoPE in its epilogue
     (bya_gemm_mx_qkv_norm_rope): equals ``gemm_mx(..., split=split)`` followed by ``qknorm_rope`` bit for bit, in one launch.
     Returns False (nothing launched, nothing counted) when the library does not take the shape -- the caller then issues the
-    two launches."""
+    two launches.  ``kernel``: 0 = the tiled kernel; 1 = the persistent 256 x 256 kernel where the launch fills it (mxfp8
+    activations and weights only, the same bits; bya_gemm_mx_qkv_norm_rope_on), 2 = without the tile count (tests).  Option
+    ``mx_kernel`` has no say here."""
     lib = _hip.load()
     code, wcode = mx_fmt_pair(fmt, w_fmt)
     d, n = _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, qw, qb, kw, kb, cos, sin, text_rows, eps,
@@ -751,8 +753,11 @@ def gemm_mx_qkv_norm_rope(a_codes, a_scales, w_codes, w_scales, out, bias, split
     if _SHAPE_LABELS:
         name += f":{fmt}*{w_fmt or fmt}:{ab}x{M}x{N}x{K}"
     tok = _begin(name)
-    rc = lib.bya_gemm_mx_qkv_norm_rope(_p(a_codes), _p(a_scales), _p(w_codes), _p(w_scales), _p(bias), _p(out), code, wcode,
-                                       ctypes.byref(d), ctypes.byref(n), _stream())
+    args = (_p(a_codes), _p(a_scales), _p(w_codes), _p(w_scales), _p(bias), _p(out), code, wcode, ctypes.byref(d), ctypes.byref(n))
+    if kernel == 0:
+        rc = lib.bya_gemm_mx_qkv_norm_rope(*args, _stream())
+    else:
+        rc = lib.bya_gemm_mx_qkv_norm_rope_on(*args, int(kernel), _stream())
     if rc == -4:                       # BYA_ERR_UNSUPPORTED: nothing was launched (the caller's gemm_mx counts the FLOPs)
         return False
     check(rc, "bya_gemm_mx_qkv_norm_rope")
@@ -763,17 +768,21 @@ def gemm_mx_qkv_norm_rope(a_codes, a_scales, w_codes, w_scales, out, bias, split
 
 
 def gemm_mx_qkv_norm_rope_plan(a_codes, a_scales, w_codes, w_scales, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows,
-                               eps=1e-6, k_scale=1.0, tensors=3, fmt="mxfp6", w_fmt=None, act=None, alpha=1.0):
+                               eps=1e-6, k_scale=1.0, tensors=3, fmt="mxfp6", w_fmt=None, act=None, alpha=1.0, kernel=0):
     """What ``gemm_mx_qkv_norm_rope`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations
-    only); None where it declines the shape (the caller's two launches).  ``act`` / ``alpha``: descriptor fields the launch
-    wrapper never sets, here to ask what the library answers to them."""
+    only), or "p256" (``kernel`` 1 or 2, mxfp8 activations and weights); None where it declines the shape (the caller's two
+    launches).  ``act`` / ``alpha``: descriptor fields the launch wrapper never sets, here to ask what the library answers
+    to them."""
     lib = _hip.load()
     code, wcode = mx_fmt_pair(fmt, w_fmt)
     d, n = _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, qw, qb, kw, kb, cos, sin, text_rows, eps,
                          k_scale, tensors, act=act, alpha=alpha, plan=True)
     p, q = _hip.GemmPlan(), _plan_p
-    rc = lib.bya_gemm_mx_qkv_norm_rope_plan(q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), code, wcode,
-                                            ctypes.byref(d), ctypes.byref(n), ctypes.byref(p))
+    args = (q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), code, wcode, ctypes.byref(d), ctypes.byref(n))
+    if kernel == 0:
+        rc = lib.bya_gemm_mx_qkv_norm_rope_plan(*args, ctypes.byref(p))
+    else:
+        rc = lib.bya_gemm_mx_qkv_norm_rope_on_plan(*args, int(kernel), ctypes.byref(p))
     if rc == -4:
         return None
     check(rc, "bya_gemm_mx_qkv_norm_rope_plan")

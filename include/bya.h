@@ -168,7 +168,8 @@ int bya_gemm_workspace_status(int32_t* timeouts, hipStream_t stream);
 #define BYA_GEMM_PATH_T256X256 3  /* 256 x 256 tiles, 8 waves (gemm_tile = 3); bya_gemm_mx: the 256 x 256 kernel of e2m3 activations */
 #define BYA_GEMM_PATH_P256 4      /* persistent 256 x 256 (csrc/gemm_v4.hip); bya_gemm_fp8: csrc/gemm_fp8_v4.hip; bya_gemm_mx /
                                      bya_gemm_mx_mixed / bya_gemm_mx_quant (out e4m3) under option mx_kernel, e4m3 x e4m3 only:
-                                     csrc/gemm_mx_v4.hip.  bya_gemm_mx_qkv_norm_rope never takes it */
+                                     csrc/gemm_mx_v4.hip.  bya_gemm_mx_qkv_norm_rope never takes it;
+                                     bya_gemm_mx_qkv_norm_rope_on takes it by its `kernel` argument */
 #define BYA_GEMM_PATH_P128 5      /* persistent 128 x 256 (csrc/gemm_v5.hip) */
 #define BYA_GEMM_PATH_P128S 6     /* persistent 128 x 256 with loader waves (csrc/gemm_v6.hip) */
 #define BYA_GEMM_PATH_W8_256 7    /* the 8-wave 256 x 256 kernel P256 falls back to (fewer than 3 K-tiles, a C / res / bias /
@@ -330,6 +331,22 @@ int bya_gemm_mx_qkv_norm_rope(const void* A, const void* a_scales, const void* W
 int bya_gemm_mx_qkv_norm_rope_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
                                    const void* bias, const void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* desc,
                                    const bya_qknorm_desc* norm, bya_gemm_plan* plan);
+/* bya_gemm_mx_qkv_norm_rope with its kernel named by an ARGUMENT (no option is read; BYA_OPT_MX_KERNEL has no say):
+ *   kernel = 0: exactly bya_gemm_mx_qkv_norm_rope -- same checks, same launch;
+ *   kernel = 1: path P256 -- the persistent 256 x 256 kernel of csrc/gemm_mx_v4.hip with the same epilogue, the same bits --
+ *     when fmt == w_fmt == e4m3, the launch has at least 200 tiles of 256 x 256 (batch included) and is eligible as for
+ *     bya_gemm_mx_plan (K % 128 == 0, K >= 512, bias 16-byte aligned, on top of this entry point's own checks); otherwise
+ *     the tiled kernel of bya_gemm_mx_qkv_norm_rope;
+ *   kernel = 2 (tests): as 1 without the tile count;
+ *   any other value: BYA_ERR_SHAPE.
+ * Always one launch; every other error is bya_gemm_mx_qkv_norm_rope's. */
+int bya_gemm_mx_qkv_norm_rope_on(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                                 void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* desc, const bya_qknorm_desc* norm,
+                                 int32_t kernel, hipStream_t stream);
+/* its kernel: path T128X128, T256X256 (e2m3 activations) or P256 */
+int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                      const void* bias, const void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* desc,
+                                      const bya_qknorm_desc* norm, int32_t kernel, bya_gemm_plan* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Small-M linear (M <= 8 rows):  out[m,n] = sum_k f(x[m,k]) * W[n,k] + bias[n],  f = identity or SiLU.
