@@ -70,6 +70,28 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// The lane ^ 16 / lane ^ 32 partner's value by v_permlane16_swap / v_permlane32_swap (one VALU instruction each; a __shfl_xor
+// is a ds_bpermute round trip): swapping a register with itself leaves own and partner in the two results -- for lane ^ 16 the
+// EVEN 16-lane group's value first, in both lanes.  lane_add* / lane_max*: the sum / maximum of the two.
+__device__ __forceinline__ auto lane_pair16(uint32_t x) { return __builtin_amdgcn_permlane16_swap(x, x, false, false); }
+__device__ __forceinline__ auto lane_pair32(uint32_t x) { return __builtin_amdgcn_permlane32_swap(x, x, false, false); }
+__device__ __forceinline__ float lane_add16(float x) {
+    const auto r = lane_pair16(__float_as_uint(x));
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float lane_add32(float x) {
+    const auto r = lane_pair32(__float_as_uint(x));
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float lane_max16(float x) {
+    const auto r = lane_pair16(__float_as_uint(x));
+    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float lane_max32(float x) {
+    const auto r = lane_pair32(__float_as_uint(x));
+    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+
 // GELU(tanh):  0.5 x (1 + tanh(u)) = x * sigmoid(2u),  u = k0 (x + k1 x^3).  One v_exp_f32 and one v_rcp_f32 (1 ulp
 // each, far below the bf16 output step) instead of expf + an IEEE division: the FF1 epilogue evaluates it 218 M times
 // per launch (128 values per lane of a 256x256 tile), where the division sequence alone was ~10 instructions a value.

@@ -32,7 +32,7 @@
 //
 // Inline-asm MFMAs are invisible to hipcc (gemm_v4.hip explains): every fragment is kept allocated to the end of the K-tile,
 // the epilogue starts behind explicit s_nops, and this unit is compiled WITHOUT -amdgpu-mfma-vgpr-form (accumulators in AGPRs).
-#include "gemm_persistent.h"
+#include "gemm_wide_epilogue.h"
 
 #ifndef BYA_F8_PLACE
 #define BYA_F8_PLACE 9      // placement of the 16 LDS-DMA pieces inside a K-tile (tools/gen_gemm_fp8_schedule.py holds the tables)
@@ -46,91 +46,6 @@ namespace {
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BK8 = 128;          // e4m3 elements (= bytes) per K-tile
-
-// Wide epilogue of one wave (gemm_v4.hip's, plus the two scale vectors).  The lane (fr = lane & 15, fq = lane >> 4) holds,
-// for row block j and accumulator register e, the EIGHT consecutive columns  n8 = n_wave + (4 e + fq) * 8 + i,  i = 0..7
-// in acc[i][j][e], of row  m = m_wave + 16 j + fr.
-template <int ACT, int JB>
-__device__ __forceinline__ void epilogue_wide8(const GemmArgs& p, const float* __restrict__ sa, const float* __restrict__ sw,
-                                               int z, int m_wave, int n_wave, int fr, int fq, const f32x4 (&acc)[8][8]) {
-    const bool has_res = p.res != nullptr, has_gate = p.gate0 != nullptr, has_bias = p.bias != nullptr;
-    const bool has_rs = p.bias_rowscale != nullptr;
-    const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((has_res ? p.res : p.C) + (long long)z * p.res_bs), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.C + (long long)z * p.c_bs), 0, 0x7fffffff, 0x00020000);
-    const char* g0base = reinterpret_cast<const char*>(p.gate0 + (long long)z * p.gate_bs);
-    const char* g1base = reinterpret_cast<const char*>(p.gate1 + (long long)z * p.gate_bs);
-    u32x4 bv[4], g0[4], g1[4];
-    f32x4 wv[4][2];                                              // the eight channel scales of each column group
-    uint32_t ncb[4], colb[4];
-    bool nok[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int n8 = n_wave + (4 * e + fq) * 8;
-        nok[e] = n8 < p.N;                                       // N % 8 == 0 on this kernel's shapes (checked by the launcher)
-        ncb[e] = nok[e] ? (uint32_t)n8 * 2u : 0u;
-        colb[e] = (uint32_t)n8 * 2u;
-        if (p.n_split > 0) colb[e] = ((uint32_t)(n8 / p.n_split) * (uint32_t)p.c_split_stride + (uint32_t)(n8 % p.n_split)) * 2u;
-        bv[e] = has_bias ? *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(p.bias) + ncb[e]) : u32x4{0u, 0u, 0u, 0u};
-        wv[e][0] = *reinterpret_cast<const f32x4*>(sw + (nok[e] ? n8 : 0));
-        wv[e][1] = *reinterpret_cast<const f32x4*>(sw + (nok[e] ? n8 : 0) + 4);
-        if (has_gate) {
-            g0[e] = *reinterpret_cast<const u32x4*>(g0base + ncb[e]);
-            g1[e] = *reinterpret_cast<const u32x4*>(g1base + ncb[e]);
-        }
-    }
-#pragma unroll
-    for (int jb = 0; jb < 8; jb += JB) {
-        u32x4 rv[JB][4];
-        float rs[JB], ra[JB];
-        bool mok[JB];
-        uint32_t roff[JB], coff[JB];
-#pragma unroll
-        for (int jj = 0; jj < JB; ++jj) {
-            const int m = m_wave + 16 * (jb + jj) + fr;
-            mok[jj] = m < p.M;
-            const uint32_t mc = mok[jj] ? (uint32_t)m : 0u;
-            rs[jj] = has_rs ? p.bias_rowscale[(long long)z * p.M + mc] : 1.0f;
-            ra[jj] = sa[(long long)z * p.M + mc];
-            roff[jj] = mc * (uint32_t)(p.ldres * 2);
-            coff[jj] = mc * (uint32_t)(p.ldc * 2);
-            if (has_res) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    rv[jj][e] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                        rsR, (mok[jj] && nok[e]) ? roff[jj] + ncb[e] : 0xffffffffu, 0, 0));
-            }
-        }
-#pragma unroll
-        for (int jj = 0; jj < JB; ++jj) {
-            const int j = jb + jj;
-            const int m = m_wave + 16 * j + fr;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float b8[8], v[8], a0[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) a0[i] = acc[i][j][e] * (ra[jj] * wv[e][i >> 2][i & 3]);      // row x channel scale
-                unpack8(bv[e], b8);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = p.alpha * apply_act<ACT>(fmaf(rs[jj], b8[i], a0[i]), p.leaky);
-                if (has_gate) {
-                    float g8[8];
-                    unpack8(m < p.gate_split ? g0[e] : g1[e], g8);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] *= g8[i];
-                }
-                if (has_res) {
-                    float r8[8];
-                    unpack8(rv[jj][e], r8);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] += r8[i];
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(pack8(v), rsC, (mok[jj] && nok[e]) ? coff[jj] + colb[e] : 0xffffffffu, 0, 0);
-            }
-        }
-    }
-}
 
 __global__ __launch_bounds__(256, 1) void gemm256p_fp8_kernel(GemmArgs p, const float* __restrict__ sa,
                                                              const float* __restrict__ sw, int tiles_m, int tiles_n, int batch,
@@ -718,7 +633,9 @@ __global__ __launch_bounds__(256, 1) void gemm256p_fp8_kernel(GemmArgs p, const 
         asm volatile("s_waitcnt vmcnt(16)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
 
         auto run = [&](auto act_tag) {
-            epilogue_wide8<decltype(act_tag)::value, 2>(p, sa, sw, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc);
+            // (wave, lane: the split writer's, unused here -- and naming them would capture them: this kernel then compiles differently)
+            epilogue_wide<decltype(act_tag)::value, 2, false, false, 8, false, true>(
+                p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc, 0, 0, nullptr, sa, sw);
         };
         dispatch_act_big(p.act, run);
 

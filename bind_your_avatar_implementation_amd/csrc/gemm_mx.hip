@@ -32,12 +32,6 @@
 #include "options.h"
 #include "qknorm_math.h"
 
-// defined in gemm_mx_v4.hip (accumulators in AGPRs): the persistent one-wave-per-SIMD 256 x 256 kernel for e4m3 x e4m3, plain
-// (qs null) or quantising (out e4m3) epilogue; _qkn: the q/k-norm epilogue (GemmArgs::qkn_*)
-bool bya_gemm256p_mx_eligible(const void* args, bool quant);
-int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int batch, int gm, hipStream_t s);
-int bya_launch_gemm256p_mx_qkn(const void* args, const uint8_t* sa, const uint8_t* sw, int batch, int gm, hipStream_t s);
-
 namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -180,14 +174,6 @@ __device__ __forceinline__ void epilogue_mx_quant(const GemmArgs& p, uint8_t* __
         const int n4 = n0 + nl + 16 * i;
         bv[i] = has_bias ? *reinterpret_cast<const u32x2*>(p.bias + (n4 < p.N ? n4 : 0)) : u32x2{0u, 0u};
     }
-    auto max16 = [](float x) {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-        return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-    };
-    auto max32 = [](float x) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-        return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-    };
     __syncthreads();                                     // every wave has read its last K-tile: the ring is free
 #pragma unroll
     for (int b = 0; b < NI / 2; ++b) {
@@ -208,7 +194,7 @@ __device__ __forceinline__ void epilogue_mx_quant(const GemmArgs& p, uint8_t* __
             float amax = 0.f;
 #pragma unroll
             for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[e]));
-            amax = max32(max16(amax));
+            amax = lane_max32(lane_max16(amax));
             uint32_t sbyte;
             const uint64_t bits = mx_quant8_bits<QOUT>(v, amax, sbyte);
             const uint32_t lo = QOUT == MX_E4M3 ? (uint32_t)bits : (uint32_t)bits & 0xffffffu;
@@ -282,10 +268,7 @@ __device__ __forceinline__ void epilogue_mx_qkn(const GemmArgs& p, int z, int m_
     static_assert(NI % 4 == 0, "whole heads per wave");
     constexpr int NH = NI / 4;
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(p.C + (long long)z * p.c_bs), 0, 0x7fffffff, 0x00020000);
-    const long long trows = (long long)p.M - p.qkn_text_rows;
-    const int tbytes = trows > 0 && p.qkn_cos ? (int)(trows * 256) : 0;          // (the launcher keeps this below 2^31)
-    const __amdgpu_buffer_rsrc_t rsCos = __builtin_amdgcn_make_buffer_rsrc((void*)p.qkn_cos, 0, tbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsSin = __builtin_amdgcn_make_buffer_rsrc((void*)p.qkn_sin, 0, tbytes, 0x00020000);
+    const QknRotary rot = qkn_rotary<false>(p);                    // (the launcher keeps the tables below 2 GiB)
     const bool has_bias = p.bias != nullptr;
     const bool odd = fq & 1;
     auto colbytes = [&](int n) {
@@ -301,11 +284,6 @@ __device__ __forceinline__ void epilogue_mx_qkn(const GemmArgs& p, int z, int m_
             const u32x2 a = *reinterpret_cast<const u32x2*>(src + hc[k]), b = *reinterpret_cast<const u32x2*>(src + hc[k] + 16);
             return u32x4{a[0], a[1], b[0], b[1]};
         }
-    };
-    auto pair16 = [](uint32_t x) { return __builtin_amdgcn_permlane16_swap(x, x, false, false); };
-    auto add32 = [](float x) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-        return __uint_as_float(r[0]) + __uint_as_float(r[1]);
     };
     // Head by head, rows inside: one head's parameters and bias are live at a time, and a finished head's accumulators are
     // dead (the 256 x 256 tile has 128 of them per lane and two heads per wave: rows outside spilled).  The price is that its
@@ -337,18 +315,13 @@ __device__ __forceinline__ void epilogue_mx_qkn(const GemmArgs& p, int z, int m_
                 const bool mok = m < p.M;
                 const uint32_t coff = (mok ? (uint32_t)m : 0u) * (uint32_t)(p.ldc * 2);
                 const bool rope = mok && m >= p.qkn_text_rows;
-                float cc[2][8], ss[2][8];
+                QknRotary8 cs[2];
                 const uint32_t t0 = (uint32_t)(m - p.qkn_text_rows) * 256u;
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                     const uint32_t o0 = rope ? t0 + (uint32_t)hc[k] * 4u : 0xffffffffu;
                     const uint32_t o1 = rope ? o0 + (STORE16 ? 16u : 64u) : 0xffffffffu;
-                    const f32x4 c0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsCos, o0, 0, 0));
-                    const f32x4 c1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsCos, o1, 0, 0));
-                    const f32x4 s0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsSin, o0, 0, 0));
-                    const f32x4 s1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsSin, o1, 0, 0));
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { cc[k][e] = c0[e]; cc[k][4 + e] = c1[e]; ss[k][e] = s0[e]; ss[k][4 + e] = s1[e]; }
+                    cs[k] = qkn_rotary_load8(rot, o0, o1);
                 }
                 float v[4][8];                                      // group g = 2 f + (fq >> 1) of the head row, in column order
 #pragma unroll
@@ -357,15 +330,15 @@ __device__ __forceinline__ void epilogue_mx_qkn(const GemmArgs& p, int z, int m_
                     const f32x4 a = acc[4 * h + f][j];
                     const uint32_t r0 = pack2bf(a[0] + bflo(bv[f][0]), a[1] + bfhi(bv[f][0]));
                     const uint32_t r1 = pack2bf(a[2] + bflo(bv[f][1]), a[3] + bfhi(bv[f][1]));
-                    const auto s0 = pair16(r0), s1 = pair16(r1);
+                    const auto s0 = lane_pair16(r0), s1 = lane_pair16(r1);
                     unpack8(u32x4{s0[0], s1[0], s0[1], s1[1]}, v[f]);
                 }
                 float s[4];
 #pragma unroll
-                for (int f = 0; f < 4; ++f) s[f] = add32(qkn_sum8(v[f]));
+                for (int f = 0; f < 4; ++f) s[f] = lane_add32(qkn_sum8(v[f]));
                 const float mean = ((s[0] + s[1]) + (s[2] + s[3])) * (1.0f / 64);
 #pragma unroll
-                for (int f = 0; f < 4; ++f) s[f] = add32(qkn_centre_sq8(v[f], mean));
+                for (int f = 0; f < 4; ++f) s[f] = lane_add32(qkn_centre_sq8(v[f], mean));
                 const float rstd = rsqrtf(((s[0] + s[1]) + (s[2] + s[3])) * (1.0f / 64) + p.qkn_eps);
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
@@ -377,7 +350,7 @@ __device__ __forceinline__ void epilogue_mx_qkn(const GemmArgs& p, int z, int m_
                     }
                     unpack8(wq[k], w8);
                     unpack8(bq[k], b8);
-                    qkn_finish8(u, rstd, w8, b8, rope, cc[k], ss[k], ks);
+                    qkn_finish8(u, rstd, w8, b8, rope, cs[k].c, cs[k].s, ks);
                     const u32x4 o = pack8(u);
                     if constexpr (STORE16) {
                         __builtin_amdgcn_raw_buffer_store_b128(o, rsC, mok ? coff + colb[k][0] : 0xffffffffu, 0, 0);
@@ -407,9 +380,8 @@ __device__ __forceinline__ void epilogue_mx_qkn(const GemmArgs& p, int z, int m_
     }
 }
 
-// FMT_A: activations (the instruction's B operand, blgp); FMT_W: weights (its A operand, cbsz); QOUT = -1: the bf16 epilogue,
-// MX_EPI_QKN: the q/k-norm one (p.qkn_*); else the element format of the quantising one (qs = its scale bytes)
-constexpr int MX_EPI_QKN = -2;
+// FMT_A: activations (the instruction's B operand, blgp); FMT_W: weights (its A operand, cbsz); QOUT = MX_EPI_BF16: the bf16
+// epilogue, MX_EPI_QKN: the q/k-norm one (p.qkn_*); else the element format of the quantising one (qs = its scale bytes)
 template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N, int QOUT>
 __device__ __forceinline__ void gemm_mx_body(const GemmArgs& p, const uint8_t* __restrict__ sa, const uint8_t* __restrict__ sw,
                                              int GM, uint8_t* __restrict__ qs) {
@@ -501,7 +473,7 @@ __device__ __forceinline__ void gemm_mx_body(const GemmArgs& p, const uint8_t* _
 
     // Lane holds C[m][n4 .. n4+3], m = m_base + 16 j, n4 = n_base + 16 i (W fragment = the instruction's A operand)
     const int m_base = m0 + wm * WM + fr, n_base = n0 + wn * WN + fq * 4;
-    if constexpr (QOUT == -1) {
+    if constexpr (QOUT == MX_EPI_BF16) {
         auto run = [&](auto act_tag) {
             epilogue_block<decltype(act_tag)::value, NI, MI, (NI * MI > 16 ? 1 : NI)>(p, z, m_base, n_base, acc);
         };
@@ -521,7 +493,7 @@ __device__ __forceinline__ void gemm_mx_body(const GemmArgs& p, const uint8_t* _
 template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_kernel(GemmArgs p, const uint8_t* __restrict__ sa,
                                                                          const uint8_t* __restrict__ sw, int GM) {
-    gemm_mx_body<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, -1>(p, sa, sw, GM, nullptr);
+    gemm_mx_body<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, MX_EPI_BF16>(p, sa, sw, GM, nullptr);
 }
 
 // ... with the quantising epilogue: C = codes (ldc, c_bs in bytes), qs = scale bytes [batch * M, N / 32]
@@ -539,44 +511,37 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_mx_qkn_kernel(Gem
     gemm_mx_body<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, MX_EPI_QKN>(p, sa, sw, GM, nullptr);
 }
 
-template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
-int launch_mx(const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, int batch, hipStream_t s) {
-    const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
-    dim3 grid(tiles_m * tiles_n, 1, batch);
-    const size_t lds = (size_t)mx_stages(FMT_A) * (BM * (mx_tile_row_bytes(FMT_A) + 4) + BN * (mx_tile_row_bytes(FMT_W) + 4));
-    static std::atomic<unsigned long long> attr_done{0};
-    auto kern = gemm_mx_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N>;
-    if (bya_allow_big_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-    BYA_LAUNCH(kern, grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a, sa, sw, MX_GROUP_M);
-    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+// The six operand instances of the tiled kernel: e4m3 / e2m3 activations x weights in the same format or in e2m1, the e2m3 ones
+// on 128 x 128 or (big) 256 x 256 tiles.  f(MxInst<...>{}) is called for the one that (a_fmt, w_fmt, big) names.
+template <int FMT_A_, int FMT_W_, int BM_, int BN_, int WAVES_M_, int WAVES_N_> struct MxInst {
+    static constexpr int FMT_A = FMT_A_, FMT_W = FMT_W_, BM = BM_, BN = BN_, WAVES_M = WAVES_M_, WAVES_N = WAVES_N_;
+};
+template <typename F>
+int mx_for_instance(int32_t a_fmt, int32_t w_fmt, bool big, F&& f) {
+    const bool w4 = w_fmt == MX_E2M1;
+    if (a_fmt == MX_E4M3) return w4 ? f(MxInst<MX_E4M3, MX_E2M1, 128, 128, 2, 2>{}) : f(MxInst<MX_E4M3, MX_E4M3, 128, 128, 2, 2>{});
+    if (big) return w4 ? f(MxInst<MX_E2M3, MX_E2M1, 256, 256, 4, 2>{}) : f(MxInst<MX_E2M3, MX_E2M3, 256, 256, 4, 2>{});
+    return w4 ? f(MxInst<MX_E2M3, MX_E2M1, 128, 128, 2, 2>{}) : f(MxInst<MX_E2M3, MX_E2M3, 128, 128, 2, 2>{});
 }
 
-template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
-int launch_mx_qkn(const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, int batch, hipStream_t s) {
+// One launch of instance I of the tiled kernel with epilogue EPI (MX_EPI_BF16, MX_EPI_QKN, or the quantising epilogue's element
+// format; qs: its scale bytes, else unused)
+template <typename I, int EPI>
+int launch_mx(const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int batch, hipStream_t s) {
+    constexpr int FMT_A = I::FMT_A, FMT_W = I::FMT_W, BM = I::BM, BN = I::BN, WAVES_M = I::WAVES_M, WAVES_N = I::WAVES_N;
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
     dim3 grid(tiles_m * tiles_n, 1, batch);
+    // the ring: per stage the two code tiles and one scale dword per row
     const size_t lds = (size_t)mx_stages(FMT_A) * (BM * (mx_tile_row_bytes(FMT_A) + 4) + BN * (mx_tile_row_bytes(FMT_W) + 4));
     static std::atomic<unsigned long long> attr_done{0};
-    auto kern = gemm_mx_qkn_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N>;
-    if (bya_allow_big_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-    BYA_LAUNCH(kern, grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a, sa, sw, MX_GROUP_M);
-    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
-}
-
-template <int FMT_A, int FMT_W, int BM, int BN, int WAVES_M, int WAVES_N>
-int launch_mx_quant(const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int out_fmt, int batch,
-                    hipStream_t s) {
-    const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
-    dim3 grid(tiles_m * tiles_n, 1, batch);
-    const size_t lds = (size_t)mx_stages(FMT_A) * (BM * (mx_tile_row_bytes(FMT_A) + 4) + BN * (mx_tile_row_bytes(FMT_W) + 4));
-    auto go = [&](auto kern, std::atomic<unsigned long long>& attr_done) {
+    auto go = [&](auto kern, auto... tail) {
         if (bya_allow_big_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done) != BYA_OK) return (int)BYA_ERR_LAUNCH;
-        BYA_LAUNCH(kern, grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a, sa, sw, MX_GROUP_M, qs);
+        BYA_LAUNCH(kern, grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a, sa, sw, MX_GROUP_M, tail...);
         return hipGetLastError() == hipSuccess ? (int)BYA_OK : (int)BYA_ERR_LAUNCH;
     };
-    static std::atomic<unsigned long long> done8{0}, done6{0};
-    if (out_fmt == MX_E4M3) return go(gemm_mx_quant_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, MX_E4M3>, done8);
-    return go(gemm_mx_quant_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, MX_E2M3>, done6);
+    if constexpr (EPI == MX_EPI_BF16) return go(gemm_mx_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N>);
+    else if constexpr (EPI == MX_EPI_QKN) return go(gemm_mx_qkn_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N>);
+    else return go(gemm_mx_quant_kernel<FMT_A, FMT_W, BM, BN, WAVES_M, WAVES_N, EPI>, qs);
 }
 
 // ---- standalone quantiser: one lane per 8 consecutive elements (one 16-byte load), a lane quad per block.
@@ -658,25 +623,40 @@ int mx_args(const void* A, const void* a_scales, const void* W, const void* w_sc
     return BYA_OK;
 }
 
-// By the activation format: e4m3 on 128 x 128 tiles; e2m3 on 256 x 256 tiles when the launch has about a round of 256 CUs of them, or more
-inline int mx_path(const GemmArgs& a, int batch, int32_t fmt) {
+// The kernel of one MX GEMM launch.  By the activation format: e4m3 on 128 x 128 tiles; e2m3 on 256 x 256 tiles when the launch
+// has about a round of 256 CUs of them, or more.  kernel = 1 (2: without the tile count) asks for the persistent kernel of
+// gemm_mx_v4.hip instead, taken for e4m3 x e4m3 by the rule of fp8_path (gemm_fp8.hip): `a` = the whole launch (tile count),
+// `piece` = one row chunk of it (eligibility).  bya_gemm_mx_mixed and bya_gemm_mx_quant pass option mx_kernel,
+// bya_gemm_mx_qkv_norm_rope_on its ARGUMENT (no option is read there).  quant: the quantising epilogue (out_fmt: its element
+// format; e2m3 stays on the tiled kernel)
+inline int mx_path(const GemmArgs& a, int batch, const GemmArgs& piece, int32_t a_fmt, int32_t w_fmt, int kernel,
+                   bool quant = false, int32_t out_fmt = MX_E4M3) {
     const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
-    const bool big = BYA_MX_E2M3_BIG_TILE && tiles256 >= 200;
-    return fmt == MX_E2M3 && big ? BYA_GEMM_PATH_T256X256 : BYA_GEMM_PATH_T128X128;
-}
-// ... and under option mx_kernel (1; 2: without the tile count) the persistent kernel of gemm_mx_v4.hip for e4m3 x e4m3, by the
-// rule of fp8_path (gemm_fp8.hip): `a` = the whole launch (tile count), `piece` = one row chunk of it (eligibility).  quant:
-// the quantising epilogue (out_fmt: its element format; e2m3 stays on the tiled kernel)
-inline int mx_path_p256(const GemmArgs& a, int batch, const GemmArgs& piece, int32_t a_fmt, int32_t w_fmt, bool quant = false,
-                        int32_t out_fmt = MX_E4M3) {
-    const int opt = bya_opt(BYA_OPT_MX_KERNEL);
-    const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
-    if (opt != 0 && a_fmt == MX_E4M3 && w_fmt == MX_E4M3 && out_fmt == MX_E4M3 && (opt == 2 || tiles256 >= 200) &&
+    if (kernel != 0 && a_fmt == MX_E4M3 && w_fmt == MX_E4M3 && out_fmt == MX_E4M3 && (kernel == 2 || tiles256 >= 200) &&
         bya_gemm256p_mx_eligible(&piece, quant))
         return BYA_GEMM_PATH_P256;
-    return mx_path(a, batch, a_fmt);
+    return a_fmt == MX_E2M3 && BYA_MX_E2M3_BIG_TILE && tiles256 >= 200 ? BYA_GEMM_PATH_T256X256 : BYA_GEMM_PATH_T128X128;
 }
 constexpr int MX_P256_GROUP_M = 4;         // row-tiles per group of the persistent kernel's tile order (as bya_gemm_fp8)
+
+// One launch on the kernel that `path` (mx_path) names, with epilogue epi: MX_EPI_BF16, MX_EPI_QKN, or the quantising epilogue's
+// element format (qs: its scale bytes)
+int mx_launch(int path, const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int epi, int32_t a_fmt,
+              int32_t w_fmt, int batch, hipStream_t s) {
+    if (path == BYA_GEMM_PATH_P256) return bya_launch_gemm256p_mx(&a, sa, sw, qs, epi, batch, MX_P256_GROUP_M, s);
+    return mx_for_instance(a_fmt, w_fmt, path == BYA_GEMM_PATH_T256X256, [&](auto inst) {
+        using I = decltype(inst);
+        if (epi == MX_EPI_BF16) return launch_mx<I, MX_EPI_BF16>(a, sa, sw, qs, batch, s);
+        if (epi == MX_EPI_QKN) return launch_mx<I, MX_EPI_QKN>(a, sa, sw, qs, batch, s);
+        return epi == MX_E4M3 ? launch_mx<I, MX_E4M3>(a, sa, sw, qs, batch, s) : launch_mx<I, MX_E2M3>(a, sa, sw, qs, batch, s);
+    });
+}
+
+int mx_plan(bya_gemm_plan* p, int path, int row_chunks) {
+    p->path = path;
+    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = row_chunks;
+    return BYA_OK;
+}
 }  // namespace
 
 extern "C" int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
@@ -686,21 +666,10 @@ extern "C" int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void
     const int rc = mx_args(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, a_fmt, w_fmt, &a);
     if (rc != BYA_OK) return rc;
     const uint8_t* sa = (const uint8_t*)a_scales;
-    const uint8_t* sw = (const uint8_t*)w_scales;
     const long long ks = d->K / 32;
-    const bool big = mx_path(a, d->batch, a_fmt) == BYA_GEMM_PATH_T256X256, w4 = w_fmt == MX_E2M1;
     return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
-        const uint8_t* sp = sa + row0 * ks;
-        if (mx_path_p256(a, d->batch, piece, a_fmt, w_fmt) == BYA_GEMM_PATH_P256)
-            return bya_launch_gemm256p_mx(&piece, sp, sw, nullptr, batch, MX_P256_GROUP_M, stream);
-        if (a_fmt == MX_E4M3)
-            return w4 ? launch_mx<MX_E4M3, MX_E2M1, 128, 128, 2, 2>(piece, sp, sw, batch, stream)
-                      : launch_mx<MX_E4M3, MX_E4M3, 128, 128, 2, 2>(piece, sp, sw, batch, stream);
-        if (big)
-            return w4 ? launch_mx<MX_E2M3, MX_E2M1, 256, 256, 4, 2>(piece, sp, sw, batch, stream)
-                      : launch_mx<MX_E2M3, MX_E2M3, 256, 256, 4, 2>(piece, sp, sw, batch, stream);
-        return w4 ? launch_mx<MX_E2M3, MX_E2M1, 128, 128, 2, 2>(piece, sp, sw, batch, stream)
-                  : launch_mx<MX_E2M3, MX_E2M3, 128, 128, 2, 2>(piece, sp, sw, batch, stream);
+        const int path = mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL));
+        return mx_launch(path, piece, sa + row0 * ks, (const uint8_t*)w_scales, nullptr, MX_EPI_BF16, a_fmt, w_fmt, batch, stream);
     });
 }
 
@@ -714,9 +683,7 @@ extern "C" int bya_gemm_mx_mixed_plan(const void* A, const void* a_scales, const
     if (rc != BYA_OK) return rc;
     const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
     if (!chunks) return BYA_ERR_UNSUPPORTED;
-    p->path = mx_path_p256(a, d->batch, piece, a_fmt, w_fmt);
-    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = chunks;
-    return BYA_OK;
+    return mx_plan(p, mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL)), chunks);
 }
 
 namespace {
@@ -748,20 +715,9 @@ extern "C" int bya_gemm_mx_quant(const void* A, const void* a_scales, const void
     GemmArgs a;
     const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
     if (rc != BYA_OK) return rc;
-    const uint8_t* sa = (const uint8_t*)a_scales;
-    const uint8_t* sw = (const uint8_t*)w_scales;
-    uint8_t* qs = (uint8_t*)q_scales;
-    const bool big = mx_path(a, d->batch, a_fmt) == BYA_GEMM_PATH_T256X256, w4 = w_fmt == MX_E2M1;
-    if (mx_path_p256(a, d->batch, a, a_fmt, w_fmt, true, out_fmt) == BYA_GEMM_PATH_P256)
-        return bya_launch_gemm256p_mx(&a, sa, sw, qs, d->batch, MX_P256_GROUP_M, stream);
-    if (a_fmt == MX_E4M3)
-        return w4 ? launch_mx_quant<MX_E4M3, MX_E2M1, 128, 128, 2, 2>(a, sa, sw, qs, out_fmt, d->batch, stream)
-                  : launch_mx_quant<MX_E4M3, MX_E4M3, 128, 128, 2, 2>(a, sa, sw, qs, out_fmt, d->batch, stream);
-    if (big)
-        return w4 ? launch_mx_quant<MX_E2M3, MX_E2M1, 256, 256, 4, 2>(a, sa, sw, qs, out_fmt, d->batch, stream)
-                  : launch_mx_quant<MX_E2M3, MX_E2M3, 256, 256, 4, 2>(a, sa, sw, qs, out_fmt, d->batch, stream);
-    return w4 ? launch_mx_quant<MX_E2M3, MX_E2M1, 128, 128, 2, 2>(a, sa, sw, qs, out_fmt, d->batch, stream)
-              : launch_mx_quant<MX_E2M3, MX_E2M3, 128, 128, 2, 2>(a, sa, sw, qs, out_fmt, d->batch, stream);
+    const int path = mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), true, out_fmt);
+    return mx_launch(path, a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, (uint8_t*)q_scales, out_fmt, a_fmt, w_fmt,
+                     d->batch, stream);
 }
 
 extern "C" int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
@@ -771,9 +727,7 @@ extern "C" int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const
     GemmArgs a;
     const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
     if (rc != BYA_OK) return rc;
-    p->path = mx_path_p256(a, d->batch, a, a_fmt, w_fmt, true, out_fmt);
-    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = 1;
-    return BYA_OK;
+    return mx_plan(p, mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), true, out_fmt), 1);
 }
 
 namespace {
@@ -807,63 +761,19 @@ int mx_qkn_args(const void* A, const void* a_scales, const void* W, const void* 
 }  // namespace
 
 // bya_gemm_mx_mixed of the packed q|k|v (or q|k) projection with the per-head q/k LayerNorm(64) + RoPE in its epilogue: bit for
-// bit bya_gemm_mx_mixed(..., n_split) followed by bya_qknorm_rope, q and k written once.  Tile by mx_path, as every MX GEMM.
-extern "C" int bya_gemm_mx_qkv_norm_rope(const void* A, const void* a_scales, const void* W, const void* w_scales,
-                                         const void* bias, void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* d,
-                                         const bya_qknorm_desc* n, hipStream_t stream) {
-    GemmArgs a;
-    const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
-    if (rc != BYA_OK) return rc;
-    const uint8_t* sa = (const uint8_t*)a_scales;
-    const uint8_t* sw = (const uint8_t*)w_scales;
-    const bool big = mx_path(a, d->batch, fmt) == BYA_GEMM_PATH_T256X256, w4 = w_fmt == MX_E2M1;
-    if (fmt == MX_E4M3)
-        return w4 ? launch_mx_qkn<MX_E4M3, MX_E2M1, 128, 128, 2, 2>(a, sa, sw, d->batch, stream)
-                  : launch_mx_qkn<MX_E4M3, MX_E4M3, 128, 128, 2, 2>(a, sa, sw, d->batch, stream);
-    if (big)
-        return w4 ? launch_mx_qkn<MX_E2M3, MX_E2M1, 256, 256, 4, 2>(a, sa, sw, d->batch, stream)
-                  : launch_mx_qkn<MX_E2M3, MX_E2M3, 256, 256, 4, 2>(a, sa, sw, d->batch, stream);
-    return w4 ? launch_mx_qkn<MX_E2M3, MX_E2M1, 128, 128, 2, 2>(a, sa, sw, d->batch, stream)
-              : launch_mx_qkn<MX_E2M3, MX_E2M3, 128, 128, 2, 2>(a, sa, sw, d->batch, stream);
-}
-
-extern "C" int bya_gemm_mx_qkv_norm_rope_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
-                                              const void* bias, const void* C, int32_t fmt, int32_t w_fmt,
-                                              const bya_gemm_desc* d, const bya_qknorm_desc* n, bya_gemm_plan* p) {
-    if (!p) return BYA_ERR_SHAPE;
-    GemmArgs a;
-    const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
-    if (rc != BYA_OK) return rc;
-    p->path = mx_path(a, d->batch, fmt);
-    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = 1;
-    return BYA_OK;
-}
-
-namespace {
-// bya_gemm_mx_qkv_norm_rope_on's kernel: the argument `kernel` (1; 2: without the tile count) asks for the persistent kernel of
-// gemm_mx_v4.hip, taken for e4m3 x e4m3 by mx_path_p256's rule -- but by the ARGUMENT: no option is read here
-inline int mx_qkn_path_on(const GemmArgs& a, int batch, int32_t fmt, int32_t w_fmt, int32_t kernel) {
-    const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
-    if (kernel != 0 && fmt == MX_E4M3 && w_fmt == MX_E4M3 && (kernel == 2 || tiles256 >= 200) && bya_gemm256p_mx_eligible(&a, false))
-        return BYA_GEMM_PATH_P256;
-    return mx_path(a, batch, fmt);
-}
-}  // namespace
-
-// bya_gemm_mx_qkv_norm_rope with the kernel named by an argument: 0 = that entry point; 1 = the persistent 256 x 256 kernel
+// bit bya_gemm_mx_mixed(..., n_split) followed by bya_qknorm_rope, q and k written once.  The kernel is named by an ARGUMENT
+// (no option is read): 0 = the tiled kernel of mx_path, as every MX GEMM; 1 = the persistent 256 x 256 kernel
 // (gemm256p_mx_kernel<MX_EPI_QKN>, the same bits) where the launch fills it and is eligible, else the tiled one; 2 (tests):
-// without the tile count.  Always one launch; the errors of bya_gemm_mx_qkv_norm_rope.
+// without the tile count.  Always one launch.
 extern "C" int bya_gemm_mx_qkv_norm_rope_on(const void* A, const void* a_scales, const void* W, const void* w_scales,
                                             const void* bias, void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* d,
                                             const bya_qknorm_desc* n, int32_t kernel, hipStream_t stream) {
     if (kernel < 0 || kernel > 2) return BYA_ERR_SHAPE;
-    if (kernel == 0) return bya_gemm_mx_qkv_norm_rope(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, stream);
     GemmArgs a;
     const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
     if (rc != BYA_OK) return rc;
-    if (mx_qkn_path_on(a, d->batch, fmt, w_fmt, kernel) != BYA_GEMM_PATH_P256)
-        return bya_gemm_mx_qkv_norm_rope(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, stream);
-    return bya_launch_gemm256p_mx_qkn(&a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, d->batch, MX_P256_GROUP_M, stream);
+    return mx_launch(mx_path(a, d->batch, a, fmt, w_fmt, kernel), a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, nullptr,
+                     MX_EPI_QKN, fmt, w_fmt, d->batch, stream);
 }
 
 extern "C" int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
@@ -874,9 +784,20 @@ extern "C" int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_sc
     GemmArgs a;
     const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
     if (rc != BYA_OK) return rc;
-    p->path = mx_qkn_path_on(a, d->batch, fmt, w_fmt, kernel);
-    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = 1;
-    return BYA_OK;
+    return mx_plan(p, mx_path(a, d->batch, a, fmt, w_fmt, kernel), 1);
+}
+
+// ... on the tiled kernel (kernel = 0)
+extern "C" int bya_gemm_mx_qkv_norm_rope(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                         const void* bias, void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* d,
+                                         const bya_qknorm_desc* n, hipStream_t stream) {
+    return bya_gemm_mx_qkv_norm_rope_on(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, 0, stream);
+}
+
+extern "C" int bya_gemm_mx_qkv_norm_rope_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                              const void* bias, const void* C, int32_t fmt, int32_t w_fmt,
+                                              const bya_gemm_desc* d, const bya_qknorm_desc* n, bya_gemm_plan* p) {
+    return bya_gemm_mx_qkv_norm_rope_on_plan(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, 0, p);
 }
 
 // Both operands in one format: e4m3 or e2m3 (e2m1 activations are not offered)

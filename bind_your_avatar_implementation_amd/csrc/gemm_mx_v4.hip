@@ -29,9 +29,8 @@
 // (epilogue_mx_wide8_qkn, below).
 // K >= 512; e2m1 weights and e2m3 operands (64- and 96-byte LDS rows) stay on gemm_mx.hip.
 // Compiled WITHOUT -amdgpu-mfma-vgpr-form, like gemm_fp8_v4.hip.
-#include "gemm_persistent.h"
+#include "gemm_wide_epilogue.h"
 #include "mx_common.h"
-#include "qknorm_math.h"
 
 namespace {
 
@@ -62,97 +61,6 @@ __device__ __forceinline__ i32x4 tile_rsrc_sw(const GemmArgs& p, const uint8_t* 
     return raw_rsrc(sw + (long long)c.n0 * ks, c.valid && left > 0 ? (uint32_t)left : 0u);
 }
 
-// Wide epilogue of one wave: epilogue_wide8 of gemm_fp8_v4.hip without the row x channel scale product.  The lane
-// (fr = lane & 15, fq = lane >> 4) holds, for row block j and accumulator register e, the EIGHT consecutive columns
-// n8 = n_wave + (4 e + fq) * 8 + i,  i = 0..7  in acc[i][j][e], of row  m = m_wave + 16 j + fr.  Per element the expression
-// of epilogue_block (gemm_common.h), which the 128 x 128 kernel evaluates.
-template <int ACT, int JB>
-__device__ __forceinline__ void epilogue_mx_wide8(const GemmArgs& p, int z, int m_wave, int n_wave, int fr, int fq,
-                                                  f32x4 (&acc)[8][8]) {
-    const bool has_res = p.res != nullptr, has_gate = p.gate0 != nullptr, has_bias = p.bias != nullptr;
-    const bool has_rs = p.bias_rowscale != nullptr;
-    const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((has_res ? p.res : p.C) + (long long)z * p.res_bs), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.C + (long long)z * p.c_bs), 0, 0x7fffffff, 0x00020000);
-    const char* g0base = reinterpret_cast<const char*>(p.gate0 + (long long)z * p.gate_bs);
-    const char* g1base = reinterpret_cast<const char*>(p.gate1 + (long long)z * p.gate_bs);
-    u32x4 bv[4], g0[4], g1[4];
-    uint32_t ncb[4], colb[4];
-    bool nok[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int n8 = n_wave + (4 * e + fq) * 8;
-        nok[e] = n8 < p.N;                                       // N % 8 == 0 on this kernel's shapes (checked by the launcher)
-        ncb[e] = nok[e] ? (uint32_t)n8 * 2u : 0u;
-        colb[e] = (uint32_t)n8 * 2u;
-        if (p.n_split > 0) colb[e] = ((uint32_t)(n8 / p.n_split) * (uint32_t)p.c_split_stride + (uint32_t)(n8 % p.n_split)) * 2u;
-        bv[e] = has_bias ? *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(p.bias) + ncb[e]) : u32x4{0u, 0u, 0u, 0u};
-        if (has_gate) {
-            g0[e] = *reinterpret_cast<const u32x4*>(g0base + ncb[e]);
-            g1[e] = *reinterpret_cast<const u32x4*>(g1base + ncb[e]);
-        }
-    }
-#pragma unroll
-    for (int jb = 0; jb < 8; jb += JB) {
-        u32x4 rv[JB][4];
-        float rs[JB];
-        bool mok[JB];
-        uint32_t roff[JB], coff[JB];
-        // The accumulators stay in their AGPRs until the row blocks of this burst are due: an asm that takes them as "a" here
-        // makes every earlier copy of them pointless.  Without it hipcc's allocator opened the epilogue with over a hundred
-        // v_accvgpr_read at once (as many accumulators as VGPRs were free at that point) and then sent two lane constants
-        // to scratch.
-#pragma unroll
-        for (int jj = 0; jj < JB; ++jj)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) asm volatile("" : "+a"(acc[i][jb + jj]));
-#pragma unroll
-        for (int jj = 0; jj < JB; ++jj) {
-            const int m = m_wave + 16 * (jb + jj) + fr;
-            mok[jj] = m < p.M;
-            const uint32_t mc = mok[jj] ? (uint32_t)m : 0u;
-            rs[jj] = has_rs ? p.bias_rowscale[(long long)z * p.M + mc] : 1.0f;
-            // 32-bit byte offsets behind descriptors of 0x7fffffff records, as in every bf16 epilogue here: the host cuts a launch
-            // whose C or residual rows span 2 GiB into row chunks (gemm_row_chunks, gemm_common.h) before it gets here.  (The
-            // quantising epilogue below is never chunked and addresses through 64-bit pointers.)
-            roff[jj] = mc * (uint32_t)(p.ldres * 2);
-            coff[jj] = mc * (uint32_t)(p.ldc * 2);
-            if (has_res) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    rv[jj][e] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                        rsR, (mok[jj] && nok[e]) ? roff[jj] + ncb[e] : 0xffffffffu, 0, 0));
-            }
-        }
-#pragma unroll
-        for (int jj = 0; jj < JB; ++jj) {
-            const int j = jb + jj;
-            const int m = m_wave + 16 * j + fr;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float b8[8], v[8];
-                unpack8(bv[e], b8);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = p.alpha * apply_act<ACT>(fmaf(rs[jj], b8[i], acc[i][j][e]), p.leaky);
-                if (has_gate) {
-                    float g8[8];
-                    unpack8(m < p.gate_split ? g0[e] : g1[e], g8);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] *= g8[i];
-                }
-                if (has_res) {
-                    float r8[8];
-                    unpack8(rv[jj][e], r8);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] += r8[i];
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(pack8(v), rsC, (mok[jj] && nok[e]) ? coff[jj] + colb[e] : 0xffffffffu, 0, 0);
-            }
-        }
-    }
-}
-
 // Quantising epilogue of one wave (bya_gemm_mx_quant, out e4m3): per element  v = bf16( alpha * act(acc + rowscale * bias) ),
 // then the block rule of mx_common.h.  MX block e of row 16 j + fr (32 columns from n_wave + 32 e) is the four lanes
 // fq = 0..3: |max| over the lane's eight values and its lane ^ 16 / lane ^ 32 partners, mx_quant8_bits on the eight values =
@@ -171,14 +79,6 @@ __device__ __forceinline__ void epilogue_mx_wide8_quant(const GemmArgs& p, uint8
         const int n8 = n_wave + (4 * e + fq) * 8;
         bv[e] = has_bias ? *reinterpret_cast<const u32x4*>(p.bias + (nok ? n8 : 0)) : u32x4{0u, 0u, 0u, 0u};
     }
-    auto max16 = [](float x) {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-        return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-    };
-    auto max32 = [](float x) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-        return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-    };
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int m = m_wave + 16 * j + fr;
@@ -195,7 +95,7 @@ __device__ __forceinline__ void epilogue_mx_wide8_quant(const GemmArgs& p, uint8
             float amax = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
-            amax = max32(max16(amax));
+            amax = lane_max32(lane_max16(amax));
             uint32_t sbyte;
             const uint64_t bits = mx_quant8_bits<MX_E4M3>(v, amax, sbyte);
             sdword |= sbyte << (8 * e);
@@ -227,7 +127,7 @@ __device__ __forceinline__ void epilogue_mx_wide8_quant(const GemmArgs& p, uint8
 // Rows outside, heads inside: the rotary row of a token is the same for both heads of the wave, so it is fetched once per
 // row block; the two heads' bias and LayerNorm parameters (q's and k's may differ between a wave's two heads) stay PACKED,
 // 52 registers, and are unpacked where they are used.  The accumulators of a burst of JB row blocks are pinned in their
-// AGPRs until the burst is due (epilogue_mx_wide8) and a scheduling barrier keeps a burst's table loads inside it: 201
+// AGPRs until the burst is due (epilogue_wide's PIN) and a scheduling barrier keeps a burst's table loads inside it: 201
 // VGPRs + 256 AGPRs, no scratch.  (Heads outside with the pin inside the q/k | v branch made every accumulator a phi of two
 // AGPR copies: 205 registers of scratch.)
 template <int JB>
@@ -235,20 +135,8 @@ __device__ __forceinline__ void epilogue_mx_wide8_qkn(const GemmArgs& p, int z, 
                                                       f32x4 (&acc)[8][8]) {
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(p.C + (long long)z * p.c_bs), 0, 0x7fffffff, 0x00020000);
-    const long long trows = (long long)p.M - p.qkn_text_rows;
-    const int tbytes = trows > 0 && p.qkn_cos ? (int)(trows * 256) : 0;          // (the launcher keeps this below 2^31)
-    const __amdgpu_buffer_rsrc_t rsCos = __builtin_amdgcn_make_buffer_rsrc((void*)p.qkn_cos, 0, tbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsSin = __builtin_amdgcn_make_buffer_rsrc((void*)p.qkn_sin, 0, tbytes, 0x00020000);
+    const QknRotary rot = qkn_rotary<false>(p);                    // (the launcher keeps the tables below 2 GiB)
     const bool has_bias = p.bias != nullptr;
-    // lane ^ 16 and lane ^ 32 partners: swapping a value with itself leaves (own, partner's) in the two results
-    auto add16 = [](float x) {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-        return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    };
-    auto add32 = [](float x) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-        return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    };
     // per head: q / k / v, bias, column map and (q, k) the LayerNorm parameters of this lane's columns, all packed
     int tsel[2];
     u32x4 bv[2][2], wq[2][2], bq[2][2];
@@ -286,17 +174,12 @@ __device__ __forceinline__ void epilogue_mx_wide8_qkn(const GemmArgs& p, int z, 
             const uint32_t coff = (mok ? (uint32_t)m : 0u) * (uint32_t)(p.ldc * 2);
             const bool rope = any_qk && mok && m >= p.qkn_text_rows;
             const uint32_t t0 = (uint32_t)(m - p.qkn_text_rows) * 256u;
-            float cc[2][8], ss[2][8];                               // the rotary row: the same columns of both heads
+            QknRotary8 cs[2];                                       // the rotary row: the same columns of both heads
 #pragma unroll
             for (int el = 0; el < 2; ++el) {
                 const uint32_t o0 = rope ? t0 + (uint32_t)((4 * el + fq) * 32) : 0xffffffffu;
                 const uint32_t o1 = rope ? o0 + 16u : 0xffffffffu;
-                const f32x4 c0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsCos, o0, 0, 0));
-                const f32x4 c1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsCos, o1, 0, 0));
-                const f32x4 s0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsSin, o0, 0, 0));
-                const f32x4 s1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsSin, o1, 0, 0));
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { cc[el][i] = c0[i]; cc[el][4 + i] = c1[i]; ss[el][i] = s0[i]; ss[el][4 + i] = s1[i]; }
+                cs[el] = qkn_rotary_load8(rot, o0, o1);
             }
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
@@ -316,16 +199,16 @@ __device__ __forceinline__ void epilogue_mx_wide8_qkn(const GemmArgs& p, int z, 
                         const u32x4 r = pack8(v[el]);
                         unpack8(r, v[el]);
                     }
-                    const float s0 = add32(add16(qkn_sum8(v[0]))), s1 = add32(add16(qkn_sum8(v[1])));
+                    const float s0 = lane_add32(lane_add16(qkn_sum8(v[0]))), s1 = lane_add32(lane_add16(qkn_sum8(v[1])));
                     const float mean = (s0 + s1) * (1.0f / 64);
-                    const float q0 = add32(add16(qkn_centre_sq8(v[0], mean))), q1 = add32(add16(qkn_centre_sq8(v[1], mean)));
+                    const float q0 = lane_add32(lane_add16(qkn_centre_sq8(v[0], mean))), q1 = lane_add32(lane_add16(qkn_centre_sq8(v[1], mean)));
                     const float rstd = rsqrtf((q0 + q1) * (1.0f / 64) + p.qkn_eps);
 #pragma unroll
                     for (int el = 0; el < 2; ++el) {
                         float w8[8], b8[8];
                         unpack8(wq[hh][el], w8);
                         unpack8(bq[hh][el], b8);
-                        qkn_finish8(v[el], rstd, w8, b8, rope, cc[el], ss[el], ks);
+                        qkn_finish8(v[el], rstd, w8, b8, rope, cs[el].c, cs[el].s, ks);
                     }
                 }
 #pragma unroll
@@ -336,9 +219,8 @@ __device__ __forceinline__ void epilogue_mx_wide8_qkn(const GemmArgs& p, int z, 
     }
 }
 
-// QOUT = -1: the bf16 epilogue; MX_EPI_QKN: the q/k-norm one (p.qkn_*); MX_E4M3: the quantising one (C = codes with ldc / c_bs
+// QOUT = MX_EPI_BF16: the bf16 epilogue; MX_EPI_QKN: the q/k-norm one (p.qkn_*); MX_E4M3: the quantising one (C = codes with ldc / c_bs
 // in bytes, qs = its scale bytes)
-constexpr int MX_EPI_QKN = -2;
 template <int QOUT>
 __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const uint8_t* __restrict__ sa,
                                                             const uint8_t* __restrict__ sw, int tiles_m, int tiles_n, int batch,
@@ -549,8 +431,8 @@ __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const u
             epilogue_mx_wide8_qkn<2>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc);
         } else {
             auto run = [&](auto act_tag) {
-                if constexpr (QOUT == -1)
-                    epilogue_mx_wide8<decltype(act_tag)::value, 2>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc);
+                if constexpr (QOUT == MX_EPI_BF16)       // (wave, lane: the split writer's, unused here; PIN: acc stays in AGPRs per burst)
+                    epilogue_wide<decltype(act_tag)::value, 2, false, false, 8, true>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc, 0, 0);
                 else
                     epilogue_mx_wide8_quant<decltype(act_tag)::value>(p, qs, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc);
             };
@@ -584,23 +466,17 @@ bool bya_gemm256p_mx_eligible(const void* args, bool quant) {
         a.c_bs % 8 == 0 && a.res_bs % 8 == 0 && a.gate_bs % 8 == 0 && a.c_split_stride % 8 == 0;
 }
 
-// sa / sw: the e8m0 scale bytes [batch * M, K / 32] / [N, K / 32]; qs: the scale bytes of the quantising epilogue, or null
-int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int batch, int gm, hipStream_t s) {
+// sa / sw: the e8m0 scale bytes [batch * M, K / 32] / [N, K / 32].  epi: MX_EPI_BF16, MX_EPI_QKN = the q/k-norm epilogue
+// (GemmArgs::qkn_*; the caller has checked mx_qkn_args' conditions), MX_E4M3 = the quantising one (qs: its scale bytes)
+int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int epi, int batch, int gm,
+                           hipStream_t s) {
     const GemmArgs& a = *static_cast<const GemmArgs*>(args);
     const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
     const size_t lds = SC_BASE + 2 * SC_STAGE;
     const int grid = persistent_grid((long long)tiles_m * tiles_n * batch);
-    if (qs)
-        return launch_persistent<gemm256p_mx_kernel<MX_E4M3>>(grid, 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch, gm < 1 ? 1 : gm, qs);
-    return launch_persistent<gemm256p_mx_kernel<-1>>(grid, 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch, gm < 1 ? 1 : gm, qs);
-}
-
-// ... with the q/k-norm epilogue (GemmArgs::qkn_*; bya_gemm_mx_qkv_norm_rope_on has checked mx_qkn_args' conditions)
-int bya_launch_gemm256p_mx_qkn(const void* args, const uint8_t* sa, const uint8_t* sw, int batch, int gm, hipStream_t s) {
-    const GemmArgs& a = *static_cast<const GemmArgs*>(args);
-    const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
-    const size_t lds = SC_BASE + 2 * SC_STAGE;
-    const int grid = persistent_grid((long long)tiles_m * tiles_n * batch);
-    return launch_persistent<gemm256p_mx_kernel<MX_EPI_QKN>>(grid, 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch, gm < 1 ? 1 : gm,
-                                                             (uint8_t*)nullptr);
+    auto go = [&](auto epi_tag) {
+        return launch_persistent<gemm256p_mx_kernel<decltype(epi_tag)::value>>(grid, 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch,
+                                                                               gm < 1 ? 1 : gm, qs);
+    };
+    return epi == MX_EPI_QKN ? go(IntTag<MX_EPI_QKN>{}) : epi == MX_E4M3 ? go(IntTag<MX_E4M3>{}) : go(IntTag<MX_EPI_BF16>{});
 }

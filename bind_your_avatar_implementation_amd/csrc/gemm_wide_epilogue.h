@@ -5,12 +5,20 @@
 #pragma once
 #include "gemm_persistent.h"
 #include "qknorm_math.h"
+#include <type_traits>
 
 namespace {
 
 // Wide epilogue of one wave.  The lane (fr = lane & 15, fq = lane >> 4) holds, for row block j and accumulator register e,
 // the EIGHT consecutive columns  n8 = n_wave + (4 e + fq) * 8 + i,  i = 0..7  in acc[i][j][e]  (W rows are staged in the
-// permuted order of gemm_persistent.h), of row  m = m_wave + 16 j + fr.
+// permuted order of gemm_persistent.h), of row  m = m_wave + 16 j + fr.  Per element the expression of epilogue_block
+// (gemm_common.h), which the tiled kernels evaluate.  The one copy for every persistent kernel; two compile-time switches:
+//   * SCALED (gemm_fp8_v4.hip): the accumulator is first multiplied by its activation-row x weight-channel scale,
+//     sa[batch * M] x sw[N]; not so for bf16 and for MX, whose block scales are inside the instruction;
+//   * PIN (gemm_mx_v4.hip, whose instance takes a non-const acc): the accumulators stay in their AGPRs until the row blocks of
+//     a burst are due -- an asm that takes them as "+a" at the head of the burst makes every earlier copy of them pointless.
+//     Without it hipcc's allocator opened that kernel's epilogue with over a hundred v_accvgpr_read at once (as many
+//     accumulators as VGPRs were free at that point) and then sent two lane constants to scratch.
 // Split tiles (see the top).  A slab holds a tile's partial sums in the order this epilogue walks the accumulators:
 // unit (wave, j, e, half) = the lane's values i = 4 half .. 4 half + 3 of row block j, register e: 16 bytes per lane at
 // ((wave * 64 + (j * 4 + e) * 2 + half) * 64 + lane) * 16, so that one store instruction writes eight whole 128-byte lines.
@@ -18,9 +26,11 @@ namespace {
 // nothing else happens.  Same call site as the ordinary epilogue and through one VALU multiply: a second kind of consumer
 // of the asm-owned accumulators (a plain store of them) made hipcc put the store's data tuples into AGPRs too and evict
 // accumulators to scratch right behind their last MFMA, inside the K-loop -- 250 registers of scratch traffic per tile.
-template <int ACT, int JB, bool SPLIT, bool CONV = false, int NJ = 8>
+template <int ACT, int JB, bool SPLIT, bool CONV = false, int NJ = 8, bool PIN = false, bool SCALED = false>
 __device__ __forceinline__ void epilogue_wide(const GemmArgs& p, int z, int m_wave, int n_wave, int fr, int fq,
-                                              const f32x4 (&acc)[8][NJ], int wave, int lane, float* raw_out = nullptr) {
+                                              std::conditional_t<PIN, f32x4, const f32x4> (&acc)[8][NJ], int wave, int lane,
+                                              float* raw_out = nullptr, const float* __restrict__ sa = nullptr,
+                                              const float* __restrict__ sw = nullptr) {
     const bool has_res = p.res != nullptr, has_gate = p.gate0 != nullptr, has_bias = p.bias != nullptr;
     const bool has_rs = p.bias_rowscale != nullptr;
     const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(
@@ -30,6 +40,7 @@ __device__ __forceinline__ void epilogue_wide(const GemmArgs& p, int z, int m_wa
     const char* g0base = reinterpret_cast<const char*>(p.gate0 + (long long)z * p.gate_bs);
     const char* g1base = reinterpret_cast<const char*>(p.gate1 + (long long)z * p.gate_bs);
     u32x4 bv[4], g0[4], g1[4];
+    f32x4 wv[4][2];                                              // SCALED: the eight channel scales of each column group
     uint32_t ncb[4], colb[4];
     bool nok[4];
 #pragma unroll
@@ -40,6 +51,10 @@ __device__ __forceinline__ void epilogue_wide(const GemmArgs& p, int z, int m_wa
         colb[e] = (uint32_t)n8 * 2u;
         if (p.n_split > 0) colb[e] = ((uint32_t)(n8 / p.n_split) * (uint32_t)p.c_split_stride + (uint32_t)(n8 % p.n_split)) * 2u;
         bv[e] = has_bias ? *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(p.bias) + ncb[e]) : u32x4{0u, 0u, 0u, 0u};
+        if constexpr (SCALED) {
+            wv[e][0] = *reinterpret_cast<const f32x4*>(sw + (nok[e] ? n8 : 0));
+            wv[e][1] = *reinterpret_cast<const f32x4*>(sw + (nok[e] ? n8 : 0) + 4);
+        }
         if (has_gate) {
             g0[e] = *reinterpret_cast<const u32x4*>(g0base + ncb[e]);
             g1[e] = *reinterpret_cast<const u32x4*>(g1base + ncb[e]);
@@ -48,9 +63,15 @@ __device__ __forceinline__ void epilogue_wide(const GemmArgs& p, int z, int m_wa
 #pragma unroll
     for (int jb = 0; jb < NJ; jb += JB) {
         u32x4 rv[JB][4];
-        float rs[JB];
+        float rs[JB], ra[JB];
         bool mok[JB];
         uint32_t roff[JB], coff[JB];
+        if constexpr (PIN) {
+#pragma unroll
+            for (int jj = 0; jj < JB; ++jj)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) asm volatile("" : "+a"(acc[i][jb + jj]));
+        }
 #pragma unroll
         for (int jj = 0; jj < JB; ++jj) {
             const int m = m_wave + 16 * (jb + jj) + fr;
@@ -66,6 +87,9 @@ __device__ __forceinline__ void epilogue_wide(const GemmArgs& p, int z, int m_wa
                 mc = mok[jj] ? (t * (uint32_t)p.conv_H + h) * (uint32_t)p.conv_W + w : 0u;
             }
             rs[jj] = has_rs ? p.bias_rowscale[(long long)z * p.M + mc] : 1.0f;
+            if constexpr (SCALED) ra[jj] = sa[(long long)z * p.M + mc];
+            // 32-bit byte offsets behind descriptors of 0x7fffffff records, as in every bf16 epilogue here: the host cuts a launch
+            // whose C or residual rows span 2 GiB into row chunks (gemm_row_chunks, gemm_common.h) before it gets here
             roff[jj] = mc * (uint32_t)(p.ldres * 2);
             coff[jj] = mc * (uint32_t)(p.ldc * 2);
             if (has_res) {
@@ -83,7 +107,10 @@ __device__ __forceinline__ void epilogue_wide(const GemmArgs& p, int z, int m_wa
             for (int e = 0; e < 4; ++e) {
                 float b8[8], v[8], a0[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) a0[i] = acc[i][j][e];
+                for (int i = 0; i < 8; ++i) {
+                    if constexpr (SCALED) a0[i] = acc[i][j][e] * (ra[jj] * wv[e][i >> 2][i & 3]);     // row x channel scale
+                    else a0[i] = acc[i][j][e];
+                }
                 if (SPLIT && raw_out) {
                     const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)raw_out, 0, (int)GEMM_WS_SLAB_BYTES, 0x00020000);
                     const uint32_t so = (uint32_t)(((wave * 64 + (j * 4 + e) * 2) * 64 + lane) * 16);
@@ -154,30 +181,21 @@ __device__ __forceinline__ void epilogue_qkn(const GemmArgs& p, int z, int m_wav
         unpack8(*reinterpret_cast<const u32x4*>(p.qkn_b[tn] + hc), bb[e]);
     }
     const float ks = tsel == 1 ? p.qkn_kscale : 1.0f;
-    const long long trows = (long long)p.M - p.qkn_text_rows;
-    const int tbytes = trows > 0 && p.qkn_cos ? (int)(trows * 256 > 0x7fffffffLL ? 0x7fffffffLL : trows * 256) : 0;
-    const __amdgpu_buffer_rsrc_t rsCos = __builtin_amdgcn_make_buffer_rsrc((void*)p.qkn_cos, 0, tbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsSin = __builtin_amdgcn_make_buffer_rsrc((void*)p.qkn_sin, 0, tbytes, 0x00020000);
+    const QknRotary rot = qkn_rotary<true>(p);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int m = m_wave + 16 * j + fr;
         const bool mok = m < p.M;
         const uint32_t coff = (mok ? (uint32_t)m : 0u) * (uint32_t)(p.ldc * 2);
         const bool rope = tsel < 2 && m >= p.qkn_text_rows && mok;
-        // rotary-table row of this token, through buffer descriptors: no branch (other rows read zeros from an out-of-range
-        // offset and do not use them), so hipcc can keep the next row block's loads in flight under this one's arithmetic
-        float cc[2][8], ss[2][8];
+        // rotary-table row of this token (qkn_rotary_load8: no branch, a row that is not rotated reads zeros)
+        QknRotary8 cs[2];
         {
             const uint32_t t0 = rope ? (uint32_t)(m - p.qkn_text_rows) * 256u : 0xffffffffu;
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const uint32_t off = rope ? t0 + (uint32_t)((4 * e + fq) * 32) : 0xffffffffu;
-                const f32x4 c0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsCos, off, 0, 0));
-                const f32x4 c1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsCos, rope ? off + 16u : off, 0, 0));
-                const f32x4 s0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsSin, off, 0, 0));
-                const f32x4 s1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsSin, rope ? off + 16u : off, 0, 0));
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { cc[e][i] = c0[i]; cc[e][4 + i] = c1[i]; ss[e][i] = s0[i]; ss[e][4 + i] = s1[i]; }
+                cs[e] = qkn_rotary_load8(rot, off, rope ? off + 16u : off);
             }
         }
 #pragma unroll
@@ -198,22 +216,12 @@ __device__ __forceinline__ void epilogue_qkn(const GemmArgs& p, int z, int m_wav
                     const u32x4 r = pack8(v[el]);
                     unpack8(r, v[el]);
                 }
-                // lane ^ 16 and lane ^ 32 partners by v_permlane16_swap / v_permlane32_swap (one VALU instruction each; a
-                // __shfl_xor is a ds_bpermute round trip): swapping a value with itself leaves (own, partner's) in the two results
-                auto add16 = [](float x) {
-                    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-                    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-                };
-                auto add32 = [](float x) {
-                    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-                    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-                };
-                float s0 = add32(add16(qkn_sum8(v[0]))), s1 = add32(add16(qkn_sum8(v[1])));
+                float s0 = lane_add32(lane_add16(qkn_sum8(v[0]))), s1 = lane_add32(lane_add16(qkn_sum8(v[1])));
                 const float mean = (s0 + s1) * (1.0f / 64);
-                float q0 = add32(add16(qkn_centre_sq8(v[0], mean))), q1 = add32(add16(qkn_centre_sq8(v[1], mean)));
+                float q0 = lane_add32(lane_add16(qkn_centre_sq8(v[0], mean))), q1 = lane_add32(lane_add16(qkn_centre_sq8(v[1], mean)));
                 const float rstd = rsqrtf((q0 + q1) * (1.0f / 64) + p.qkn_eps);
-                qkn_finish8(v[0], rstd, wv[0], bb[0], rope, cc[0], ss[0], ks);
-                qkn_finish8(v[1], rstd, wv[1], bb[1], rope, cc[1], ss[1], ks);
+                qkn_finish8(v[0], rstd, wv[0], bb[0], rope, cs[0].c, cs[0].s, ks);
+                qkn_finish8(v[1], rstd, wv[1], bb[1], rope, cs[1].c, cs[1].s, ks);
             }
 #pragma unroll
             for (int el = 0; el < 2; ++el) {

@@ -5,9 +5,17 @@
 #pragma once
 #include "bya_common.h"
 
+// gemm_mx_v4.hip, called by gemm_mx.hip: the persistent one-wave-per-SIMD 256 x 256 kernel for e4m3 x e4m3 (args: GemmArgs).
+// quant: eligibility under the quantising epilogue; epi: MX_EPI_BF16, MX_EPI_QKN, or MX_E4M3 = quantising (qs: its scale bytes)
+bool bya_gemm256p_mx_eligible(const void* args, bool quant);
+int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int epi, int batch, int gm,
+                           hipStream_t s);
+
 namespace {
 
 constexpr int MX_E4M3 = 0, MX_E2M3 = 2, MX_E2M1 = 4;                      // the instruction's cbsz / blgp codes
+// the epilogue of an MX GEMM kernel (its QOUT parameter): the element format of the quantising one, or
+constexpr int MX_EPI_BF16 = -1, MX_EPI_QKN = -2;                          // bf16 out; bf16 out with q/k-norm + RoPE (GemmArgs::qkn_*)
 __host__ __device__ constexpr int mx_emax(int fmt) { return fmt == MX_E4M3 ? 8 : 2; }                  // (e2m3 and e2m1: 2)
 __host__ __device__ constexpr int mx_block_bytes(int fmt) { return fmt == MX_E4M3 ? 32 : fmt == MX_E2M3 ? 24 : 16; }
 

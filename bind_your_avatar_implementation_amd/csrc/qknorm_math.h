@@ -43,3 +43,36 @@ __device__ __forceinline__ void qkn_finish8(float (&v)[8], float rstd, const flo
         for (int e = 0; e < 8; ++e) v[e] *= k_scale;
     }
 }
+
+// ---- the rotary tables of the GEMM epilogues (epilogue_qkn, epilogue_mx_wide8_qkn, epilogue_mx_qkn): fp32 [M - text_rows, 64]
+// cos and sin behind buffer descriptors, so that a row that is not rotated reads zeros from an out-of-range offset instead of
+// taking a branch (hipcc can then keep the next row block's loads in flight under this one's arithmetic).
+struct QknRotary {
+    __amdgpu_buffer_rsrc_t cos, sin;
+};
+// ARGS: GemmArgs (M, qkn_text_rows, qkn_cos, qkn_sin).  CLAMP: tables of 2 GiB or more are cut at the descriptor's reach (the
+// bf16 GEMM); the MX launcher refuses such a launch (mx_qkn_args), so its kernels do not carry the comparison.
+template <bool CLAMP, class ARGS>
+__device__ __forceinline__ QknRotary qkn_rotary(const ARGS& p) {
+    const long long trows = (long long)p.M - p.qkn_text_rows;
+    int tbytes;
+    if constexpr (CLAMP) tbytes = trows > 0 && p.qkn_cos ? (int)(trows * 256 > 0x7fffffffLL ? 0x7fffffffLL : trows * 256) : 0;
+    else tbytes = trows > 0 && p.qkn_cos ? (int)(trows * 256) : 0;
+    return QknRotary{__builtin_amdgcn_make_buffer_rsrc((void*)p.qkn_cos, 0, tbytes, 0x00020000),
+                     __builtin_amdgcn_make_buffer_rsrc((void*)p.qkn_sin, 0, tbytes, 0x00020000)};
+}
+// one token's eight cos and eight sin of a lane's eight columns: 16 bytes at byte offsets o0 and o1 of each table
+// (0xffffffff: out of range, zeros)
+struct QknRotary8 {
+    float c[8], s[8];
+};
+__device__ __forceinline__ QknRotary8 qkn_rotary_load8(const QknRotary& r, uint32_t o0, uint32_t o1) {
+    const f32x4 c0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r.cos, o0, 0, 0));
+    const f32x4 c1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r.cos, o1, 0, 0));
+    const f32x4 s0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r.sin, o0, 0, 0));
+    const f32x4 s1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r.sin, o1, 0, 0));
+    QknRotary8 t;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { t.c[i] = c0[i]; t.c[4 + i] = c1[i]; t.s[i] = s0[i]; t.s[4 + i] = s1[i]; }
+    return t;
+}
