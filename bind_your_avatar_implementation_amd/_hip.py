@@ -60,6 +60,19 @@ class AttnTinyPlan(_c.Structure):
     _fields_ = [("instance", _i32), ("grid", _i32), ("waves", _i64)]
 
 
+class RowGemmPlan(_c.Structure):
+    _fields_ = [("form", _i32), ("ln", _i32), ("res", _i32), ("act", _i32), ("grid", _i32), ("crosses_row_block", _i32),
+                ("work_items", _i64)]
+
+
+class GroupAttnPlan(_c.Structure):
+    _fields_ = [("P", _i32), ("G", _i32), ("wide", _i32), ("blocks", _i32), ("tiles", _i64)]
+
+
+class RouterChainPlan(_c.Structure):
+    _fields_ = [("tiles", _i32), ("tp0", _i32), ("grid", _i32), ("passes", _i32), ("tiles_last", _i32), ("wgs_last", _i32)]
+
+
 class SchedCoef(_c.Structure):
     _fields_ = [("guidance", _f32), ("sqrt_alpha", _f32), ("sqrt_beta", _f32), ("k_sample", _f32),
                 ("k_denoised", _f32), ("k_noise", _f32), ("k_cur", _f32), ("k_old", _f32)]
@@ -128,6 +141,12 @@ SIGNATURES = {
     "bya_unpatchify": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "bya_act_add": [_vp, _vp, _vp, _i64, _i32, _vp],
     "bya_rowgemm512": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp],
+    "bya_rowgemm512_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c.POINTER(RowGemmPlan)],
+    "bya_router_group_attn_plan": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64,
+                                   _c.POINTER(GroupAttnPlan)],
+    "bya_router_mlp_fused_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _c.POINTER(RouterChainPlan)],
+    "bya_router_group_attn_out_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32,
+                                       _c.POINTER(RouterChainPlan)],
     "bya_router_group_attn": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _f32, _f32, _vp],
     "bya_router_mlp_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp],
     "bya_router_group_attn_out": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _f32, _f32,
@@ -185,6 +204,8 @@ ATTN_VARIANTS = {0: "d64_running_max", 1: "d64_prescaled_running_max", 2: "d64_s
 KV_MIX_FORMS = {0: "mix32", 1: "one_tile"}
 TINY_INSTANCES = {0: "tiny8<2>", 1: "tiny8<3>", 2: "tiny8<13>", 3: "tiny8<25>", 4: "generic<2>", 5: "generic<4>",
                   6: "generic<16>", 7: "generic<32>"}
+
+ROWGEMM_FORMS = {0: "chunk_balanced", 1: "w_stationary"}       # BYA_ROWGEMM_* (bya_rowgemm512_plan)
 
 ERRORS = {-1: "BYA_ERR_SHAPE", -2: "BYA_ERR_ALIGN", -3: "BYA_ERR_LAUNCH", -4: "BYA_ERR_UNSUPPORTED"}
 

@@ -153,13 +153,13 @@ __device__ __forceinline__ void get2(const T (&A)[16], int c, T& v0, T& v1) {
 
 // the pass schedule both kernels share: pass 0 = tp0 tiles per workgroup, every later pass the remainder dealt over all
 // workgroups (at most CW each)
-struct Passes {              // (32-bit: a launch has fewer than 2^31 / 1024 rows)
+struct Passes {              // (32-bit: a launch has fewer than 2^31 / 1024 rows; host too: chain_plan_of walks it for the plan queries)
     int base, tiles, tpw, grid, wg;
-    __device__ __forceinline__ Passes(int tiles_, int tp0, int grid_, int wg_) : base(0), tiles(tiles_), tpw(tp0), grid(grid_), wg(wg_) {}
-    __device__ __forceinline__ int tile_of(int wave) const { return base + wg * tpw + wave; }
-    __device__ __forceinline__ bool active(int wave) const { return wave < tpw && tile_of(wave) < tiles; }
+    __host__ __device__ __forceinline__ Passes(int tiles_, int tp0, int grid_, int wg_) : base(0), tiles(tiles_), tpw(tp0), grid(grid_), wg(wg_) {}
+    __host__ __device__ __forceinline__ int tile_of(int wave) const { return base + wg * tpw + wave; }
+    __host__ __device__ __forceinline__ bool active(int wave) const { return wave < tpw && tile_of(wave) < tiles; }
     // -> does THIS workgroup have a tile in the next pass?
-    __device__ __forceinline__ bool peek_next(int& nbase, int& ntpw) const {
+    __host__ __device__ __forceinline__ bool peek_next(int& nbase, int& ntpw) const {
         nbase = base + grid * tpw;
         ntpw = 0;
         if (nbase >= tiles) return false;
@@ -553,31 +553,42 @@ int grid_for(int tiles, int tp0) {
     return (int)(g < 256 ? g : 256);
 }
 
-}  // namespace
+// the launch decisions of both chains (launchers and plan queries): tp0, the grid, and -- by walking the kernels' own Passes as
+// workgroup 0, which has a tile in every pass there is -- the number of passes and the shape of the last one
+int chain_plan_of(int tiles, int tiles_pass0, bya_router_chain_plan_info* p) {
+    if (tiles_pass0 < 0 || tiles_pass0 > CW) return BYA_ERR_SHAPE;
+    p->tiles = tiles;
+    p->tp0 = tiles_pass0 ? tiles_pass0 : auto_tp0(tiles);
+    p->grid = grid_for(tiles, p->tp0);
+    Passes ps(tiles, p->tp0, p->grid, 0);
+    p->passes = 1;
+    for (int nbase, ntpw; ps.peek_next(nbase, ntpw); ps.base = nbase, ps.tpw = ntpw) ++p->passes;
+    p->tiles_last = ps.tpw;
+    p->wgs_last = 0;
+    for (ps.wg = 0; ps.wg < p->grid; ++ps.wg) p->wgs_last += ps.active(0) ? 1 : 0;
+    return BYA_OK;
+}
 
-extern "C" int bya_router_mlp_fused(const void* X, const void* W1, const float* colsum1, const float* cvec1, const void* W2,
-                                    const float* cvec2, void* C, int32_t M, int32_t ldx, int32_t ldc, float eps,
-                                    int32_t tiles_pass0, hipStream_t stream) {
+int mlp_plan_of(const void* X, const void* W1, const float* colsum1, const float* cvec1, const void* W2, const float* cvec2,
+                const void* C, int32_t M, int32_t ldx, int32_t ldc, float eps, int32_t tiles_pass0, MlpChainArgs* args,
+                bya_router_chain_plan_info* p) {
     if (!X || !W1 || !colsum1 || !cvec1 || !W2 || !cvec2 || !C || M <= 0) return BYA_ERR_SHAPE;
     if (ldx < RK || ldc < RK || ldx % 8 || ldc % 8) return BYA_ERR_ALIGN;
     if (((uintptr_t)X | (uintptr_t)W1 | (uintptr_t)W2 | (uintptr_t)C) & 15) return BYA_ERR_ALIGN;
     if (((long long)M + 16) * ldx * 2 >= (1LL << 31) || ((long long)M + 16) * ldc * 2 >= (1LL << 31)) return BYA_ERR_SHAPE;
-    if (tiles_pass0 < 0 || tiles_pass0 > CW) return BYA_ERR_SHAPE;
-    MlpChainArgs a;
+    MlpChainArgs& a = *args;
     a.X = (const bf16_t*)X; a.C = (bf16_t*)C; a.W1 = (const bf16_t*)W1; a.colsum1 = colsum1; a.cvec1 = cvec1;
     a.W2 = (const bf16_t*)W2; a.cvec2 = cvec2; a.M = M; a.ldx = ldx; a.ldc = ldc; a.eps = eps;
     a.tiles = (M + 15) / 16;
-    a.tp0 = tiles_pass0 ? tiles_pass0 : auto_tp0(a.tiles);
-    static std::atomic<unsigned long long> attr_done{0};
-    if (bya_allow_big_lds(reinterpret_cast<const void*>(router_mlp_chain_kernel), 160 * 1024, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-    BYA_LAUNCH(router_mlp_chain_kernel, dim3(grid_for(a.tiles, a.tp0)), dim3(64 * CW), (size_t)CONST_MLP + 2 * STAGE_BYTES, stream, a);
-    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+    const int rc = chain_plan_of(a.tiles, tiles_pass0, p);
+    a.tp0 = p->tp0;
+    return rc;
 }
 
-extern "C" int bya_router_group_attn_out(const void* X, const void* Wqkv, const float* colsum, const float* cvec, const void* Wo,
-                                         const float* cvec_o, void* C, int32_t M, int32_t ldx, int32_t ldc, int32_t L,
-                                         int64_t n_outer, int64_t n_inner, int64_t outer_stride, int64_t seq_stride, float eps,
-                                         float scale, int32_t tiles_pass0, hipStream_t stream) {
+int attn_out_plan_of(const void* X, const void* Wqkv, const float* colsum, const float* cvec, const void* Wo, const float* cvec_o,
+                     const void* C, int32_t M, int32_t ldx, int32_t ldc, int32_t L, int64_t n_outer, int64_t n_inner,
+                     int64_t outer_stride, int64_t seq_stride, float eps, float scale, int32_t tiles_pass0, AttnChainArgs* args,
+                     bya_router_chain_plan_info* p) {
     if (!X || !Wqkv || !colsum || !cvec || !Wo || !cvec_o || !C || M <= 0 || n_outer <= 0 || n_inner <= 0) return BYA_ERR_SHAPE;
     if (L < 1) return BYA_ERR_SHAPE;
     if (L > 16) return BYA_ERR_UNSUPPORTED;          // a group must fit the ONE 16-row tile of a wave (longer: the unfused pair)
@@ -587,18 +598,69 @@ extern "C" int bya_router_group_attn_out(const void* X, const void* Wqkv, const 
     if (((uintptr_t)X | (uintptr_t)Wqkv | (uintptr_t)Wo | (uintptr_t)C) & 15) return BYA_ERR_ALIGN;
     if (((long long)M + 1) * ldx * 2 >= (1LL << 31) || ((long long)M + 1) * ldc * 2 >= (1LL << 31)) return BYA_ERR_SHAPE;
     if (tiles_pass0 < 0 || tiles_pass0 > CW) return BYA_ERR_SHAPE;
-    AttnChainArgs a;
+    AttnChainArgs& a = *args;
     a.X = (const bf16_t*)X; a.C = (bf16_t*)C; a.Wqkv = (const bf16_t*)Wqkv; a.colsum = colsum; a.cvec = cvec;
     a.Wo = (const bf16_t*)Wo; a.cvec_o = cvec_o; a.M = M; a.ldx = ldx; a.ldc = ldc; a.L = L;
-    a.P = L <= 1 ? 1 : L <= 2 ? 2 : L <= 4 ? 4 : L <= 8 ? 8 : 16;
-    a.G = 16 / a.P;
+    group_cell(L, a.P, a.G);
     if (n_outer * n_inner > M || n_inner > M || outer_stride > M || seq_stride > M) return BYA_ERR_SHAPE;    // (32-bit from here)
     a.n_groups = (int)(n_outer * n_inner); a.n_inner = (int)n_inner; a.outer_stride = (int)outer_stride; a.seq_stride = (int)seq_stride;
     a.tiles = (a.n_groups + a.G - 1) / a.G;
-    a.tp0 = tiles_pass0 ? tiles_pass0 : auto_tp0(a.tiles);
+    const int rc = chain_plan_of(a.tiles, tiles_pass0, p);
+    a.tp0 = p->tp0;
     a.eps = eps; a.scale_log2 = scale * 1.4426950408889634f;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int bya_router_mlp_fused_plan(const void* X, const void* W1, const float* colsum1, const float* cvec1, const void* W2,
+                                         const float* cvec2, const void* C, int32_t M, int32_t ldx, int32_t ldc,
+                                         int32_t tiles_pass0, bya_router_chain_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    MlpChainArgs a;
+    bya_router_chain_plan_info p;
+    const int rc = mlp_plan_of(X, W1, colsum1, cvec1, W2, cvec2, C, M, ldx, ldc, 0.0f, tiles_pass0, &a, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_router_mlp_fused(const void* X, const void* W1, const float* colsum1, const float* cvec1, const void* W2,
+                                    const float* cvec2, void* C, int32_t M, int32_t ldx, int32_t ldc, float eps,
+                                    int32_t tiles_pass0, hipStream_t stream) {
+    MlpChainArgs a;
+    bya_router_chain_plan_info p;
+    const int rc = mlp_plan_of(X, W1, colsum1, cvec1, W2, cvec2, C, M, ldx, ldc, eps, tiles_pass0, &a, &p);
+    if (rc != BYA_OK) return rc;
+    static std::atomic<unsigned long long> attr_done{0};
+    if (bya_allow_big_lds(reinterpret_cast<const void*>(router_mlp_chain_kernel), 160 * 1024, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
+    BYA_LAUNCH(router_mlp_chain_kernel, dim3(p.grid), dim3(64 * CW), (size_t)CONST_MLP + 2 * STAGE_BYTES, stream, a);
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+extern "C" int bya_router_group_attn_out_plan(const void* X, const void* Wqkv, const float* colsum, const float* cvec,
+                                              const void* Wo, const float* cvec_o, const void* C, int32_t M, int32_t ldx,
+                                              int32_t ldc, int32_t L, int64_t n_outer, int64_t n_inner, int64_t outer_stride,
+                                              int64_t seq_stride, int32_t tiles_pass0, bya_router_chain_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    AttnChainArgs a;
+    bya_router_chain_plan_info p;
+    const int rc = attn_out_plan_of(X, Wqkv, colsum, cvec, Wo, cvec_o, C, M, ldx, ldc, L, n_outer, n_inner, outer_stride, seq_stride,
+                                    0.0f, 0.0f, tiles_pass0, &a, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_router_group_attn_out(const void* X, const void* Wqkv, const float* colsum, const float* cvec, const void* Wo,
+                                         const float* cvec_o, void* C, int32_t M, int32_t ldx, int32_t ldc, int32_t L,
+                                         int64_t n_outer, int64_t n_inner, int64_t outer_stride, int64_t seq_stride, float eps,
+                                         float scale, int32_t tiles_pass0, hipStream_t stream) {
+    AttnChainArgs a;
+    bya_router_chain_plan_info p;
+    const int rc = attn_out_plan_of(X, Wqkv, colsum, cvec, Wo, cvec_o, C, M, ldx, ldc, L, n_outer, n_inner, outer_stride, seq_stride,
+                                    eps, scale, tiles_pass0, &a, &p);
+    if (rc != BYA_OK) return rc;
     static std::atomic<unsigned long long> attr_done{0};
     if (bya_allow_big_lds(reinterpret_cast<const void*>(router_attn_chain_kernel), 160 * 1024, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-    BYA_LAUNCH(router_attn_chain_kernel, dim3(grid_for(a.tiles, a.tp0)), dim3(64 * CW), (size_t)CONST_ATTN + 2 * STAGE_BYTES, stream, a);
+    BYA_LAUNCH(router_attn_chain_kernel, dim3(p.grid), dim3(64 * CW), (size_t)CONST_ATTN + 2 * STAGE_BYTES, stream, a);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }

@@ -83,7 +83,8 @@ __global__ __launch_bounds__(64 * NW, 2) void rowgemm512_kernel(RowGemmArgs p) {
     // give consecutive ranges to the SAME XCD (blockIdx % 8 under round-robin dispatch) so that the second reader of a row
     // block's X finds it in that XCD's L2
     const int rid = (gridDim.x & 7) == 0 ? (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) : (int)blockIdx.x;
-    const int q0 = (int)(total * rid / gridDim.x), q1 = (int)(total * (rid + 1) / gridDim.x);
+    int q0, q1;
+    work_range(total, rid, (int)gridDim.x, q0, q1);
     if (q0 >= q1) return;
 
     // LDS: [colsum: N f32][cvec: N f32][ring: 2 x 64 KiB]
@@ -273,9 +274,7 @@ __global__ __launch_bounds__(64 * NW, 2) void rowgemm512_kernel(RowGemmArgs p) {
 }
 
 template <bool LN, bool RES, int ACT>
-int launch_rowgemm(const RowGemmArgs& a, hipStream_t s) {
-    const long long total = (long long)((a.M + RB - 1) / RB) * (a.N / CH);
-    const int blocks = (int)(total < 256 * WG_PER_CU ? total : 256 * WG_PER_CU);
+int launch_rowgemm(const RowGemmArgs& a, int blocks, hipStream_t s) {
     const size_t lds = (size_t)a.N * 8 + 2 * STAGE_BYTES;
     static std::atomic<unsigned long long> attr_done{0};
     if (bya_allow_big_lds(reinterpret_cast<const void*>(rowgemm512_kernel<LN, RES, ACT>), 160 * 1024, attr_done) != BYA_OK)
@@ -486,12 +485,12 @@ __global__ __launch_bounds__(64 * NW, 2) void rowgemm512q_kernel(RowGemmArgs p) 
 }
 
 template <bool LN, bool RES, int ACT>
-int launch_rowgemm_q(const RowGemmArgs& a, hipStream_t s) {
+int launch_rowgemm_q(const RowGemmArgs& a, int blocks, hipStream_t s) {
     const size_t lds = 1024 + 2 * STAGE_BYTES;
     static std::atomic<unsigned long long> attr_done{0};
     if (bya_allow_big_lds(reinterpret_cast<const void*>(rowgemm512q_kernel<LN, RES, ACT>), 160 * 1024, attr_done) != BYA_OK)
         return BYA_ERR_LAUNCH;
-    BYA_LAUNCH((rowgemm512q_kernel<LN, RES, ACT>), dim3(256), dim3(64 * NW), lds, s, a);
+    BYA_LAUNCH((rowgemm512q_kernel<LN, RES, ACT>), dim3(blocks), dim3(64 * NW), lds, s, a);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 
@@ -568,7 +567,8 @@ __global__ __launch_bounds__(64 * NW, 2) void rowattn512_kernel(RowAttnArgs p) {
     const int nrb = (int)((tiles + NW * HB - 1) / (NW * HB));
     const int total = nrb * RA_HEADS;                                   // (row block, head) units, row-block-major
     const int rid = (gridDim.x & 7) == 0 ? (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) : (int)blockIdx.x;
-    const int u0 = (int)((long long)total * rid / gridDim.x), u1 = (int)((long long)total * (rid + 1) / gridDim.x);
+    int u0, u1;
+    work_range(total, rid, (int)gridDim.x, u0, u1);
     if (u0 >= u1) return;
 
     float* s_lds = reinterpret_cast<float*>(smem);
@@ -828,12 +828,10 @@ __global__ __launch_bounds__(64 * NW, 2) void rowattn512_kernel(RowAttnArgs p) {
     }
 }
 
-}  // namespace
-
-extern "C" int bya_rowgemm512(const void* X, const void* W, const float* colsum, const float* cvec, const void* res,
-                              void* C, int32_t M, int32_t N, int32_t ldx, int32_t ldc, int32_t ldres, int32_t ln,
-                              float eps, int32_t act, int32_t nsplit, hipStream_t stream) {
-    (void)nsplit;      // kept in the ABI as a tuning hint; the persistent schedule balances by itself
+// bya_rowgemm512: argument checks, the kernel arguments and every launch decision (launcher and bya_rowgemm512_plan)
+int rowgemm_plan_of(const void* X, const void* W, const float* colsum, const float* cvec, const void* res, const void* C,
+                    int32_t M, int32_t N, int32_t ldx, int32_t ldc, int32_t ldres, int32_t ln, float eps, int32_t act,
+                    RowGemmArgs* args, bya_rowgemm512_plan_info* p) {
     if (!X || !W || !cvec || !C || M <= 0 || N <= 0) return BYA_ERR_SHAPE;
     if (ln && !colsum) return BYA_ERR_SHAPE;
     if (N % CH != 0 || N > 4096) return BYA_ERR_SHAPE;             // colsum + cvec + ring must fit 160 KiB of LDS
@@ -841,36 +839,45 @@ extern "C" int bya_rowgemm512(const void* X, const void* W, const float* colsum,
     if (((uintptr_t)X | (uintptr_t)W | (uintptr_t)C | (uintptr_t)res) & 15) return BYA_ERR_ALIGN;
     if ((long long)M * ldx * 2 >= (1LL << 31) || (long long)M * ldc * 2 >= (1LL << 31)) return BYA_ERR_SHAPE;
     if (act != BYA_ACT_NONE && act != BYA_ACT_GELU_ERF) return BYA_ERR_UNSUPPORTED;
-    RowGemmArgs a;
+    RowGemmArgs& a = *args;
     a.X = (const bf16_t*)X; a.W = (const bf16_t*)W; a.colsum = colsum; a.cvec = cvec; a.res = (const bf16_t*)res;
     a.C = (bf16_t*)C; a.M = M; a.N = N; a.ldx = ldx; a.ldc = ldc; a.ldres = res ? ldres : ldc;
     a.eps = eps;
-    const bool gelu = act == BYA_ACT_GELU_ERF;
+    p->ln = ln ? 1 : 0;
+    p->res = res ? 1 : 0;
+    p->act = act;
     // N = 512: the W-stationary, barrier-free form (one W quarter per workgroup).  The rows M * ld must stay below 2 GiB like
     // everywhere here; tiles outside a wave's range are addressed outside the descriptors.
     // measured (profiles/history/r4_v_rowgemm_q_probe.json): -4 % at 35100 rows, -22 % at 17550, -47 % at 8788, -29 % at 4394 and
     // 2194, level at 70200 -- above that the chunk-balanced kernel's finer work units win back what its barriers cost
+    // (the LayerNorm-folding instance -- mlp[0] -- keeps the chunk-balanced kernel: accumulating the row statistics from
+    // the streamed fragments needs ~40 more registers than two waves per SIMD leave, and spills)
     if (N == 512 && !ln && M >= 2048 && M <= 65536 && !bya_ref_form(BYA_REF_ROWGEMM_CHUNKED)) {
-        // (the LayerNorm-folding instance -- mlp[0] -- keeps the chunk-balanced kernel: accumulating the row statistics from
-        // the streamed fragments needs ~40 more registers than two waves per SIMD leave, and spills)
-        if (res) return gelu ? launch_rowgemm_q<false, true, BYA_ACT_GELU_ERF>(a, stream) : launch_rowgemm_q<false, true, BYA_ACT_NONE>(a, stream);
-        return gelu ? launch_rowgemm_q<false, false, BYA_ACT_GELU_ERF>(a, stream) : launch_rowgemm_q<false, false, BYA_ACT_NONE>(a, stream);
+        p->form = BYA_ROWGEMM_W_STATIONARY;
+        p->grid = 256;                                             // 64 row groups x 4 W quarters
+        p->work_items = (M + 15) / 16;                             // 16-row tiles, dealt over the row groups' waves
+        p->crosses_row_block = 0;
+        return BYA_OK;
     }
-    if (ln) {
-        if (res) return gelu ? launch_rowgemm<true, true, BYA_ACT_GELU_ERF>(a, stream)
-                             : launch_rowgemm<true, true, BYA_ACT_NONE>(a, stream);
-        return gelu ? launch_rowgemm<true, false, BYA_ACT_GELU_ERF>(a, stream)
-                    : launch_rowgemm<true, false, BYA_ACT_NONE>(a, stream);
+    const int ncc = N / CH;
+    const long long total = (long long)((M + RB - 1) / RB) * ncc;
+    p->form = BYA_ROWGEMM_CHUNK_BALANCED;
+    p->grid = (int)(total < 256 * WG_PER_CU ? total : 256 * WG_PER_CU);
+    p->work_items = total;
+    p->crosses_row_block = 0;
+    for (int rid = 0; rid < p->grid; ++rid) {                      // the ranges the kernel cuts (work_range)
+        int q0, q1;
+        work_range(total, rid, p->grid, q0, q1);
+        if (q0 < q1 && q0 / ncc != (q1 - 1) / ncc) p->crosses_row_block = 1;
     }
-    if (res) return gelu ? launch_rowgemm<false, true, BYA_ACT_GELU_ERF>(a, stream)
-                         : launch_rowgemm<false, true, BYA_ACT_NONE>(a, stream);
-    return gelu ? launch_rowgemm<false, false, BYA_ACT_GELU_ERF>(a, stream)
-                : launch_rowgemm<false, false, BYA_ACT_NONE>(a, stream);
+    return BYA_OK;
 }
 
-extern "C" int bya_router_group_attn(const void* X, const void* Wqkv, const float* colsum, const float* cvec, void* O,
-                                     int32_t M, int32_t ldx, int32_t ldo, int32_t L, int64_t n_outer, int64_t n_inner,
-                                     int64_t outer_stride, int64_t seq_stride, float eps, float scale, hipStream_t stream) {
+// bya_router_group_attn: argument checks, the kernel arguments and the cell / width / grid choice (launcher and
+// bya_router_group_attn_plan)
+int group_attn_plan_of(const void* X, const void* Wqkv, const float* colsum, const float* cvec, const void* O, int32_t M,
+                       int32_t ldx, int32_t ldo, int32_t L, int64_t n_outer, int64_t n_inner, int64_t outer_stride,
+                       int64_t seq_stride, float eps, float scale, RowAttnArgs* args, bya_router_group_attn_plan_info* p) {
     if (!X || !Wqkv || !colsum || !cvec || !O || M <= 0 || n_outer <= 0 || n_inner <= 0) return BYA_ERR_SHAPE;
     if (L < 1 || L > 32) return BYA_ERR_UNSUPPORTED;                  // a group must fit the two 16-row MFMA tiles of a wave
     if (outer_stride < 0 || seq_stride < 0) return BYA_ERR_SHAPE;
@@ -878,26 +885,90 @@ extern "C" int bya_router_group_attn(const void* X, const void* Wqkv, const floa
     if (ldx < RK || ldo < RK || ldx % 8 || ldo % 8) return BYA_ERR_ALIGN;
     if (((uintptr_t)X | (uintptr_t)Wqkv | (uintptr_t)O) & 15) return BYA_ERR_ALIGN;
     if (((long long)M + 1) * ldx * 2 >= (1LL << 31) || ((long long)M + 1) * ldo * 2 >= (1LL << 31)) return BYA_ERR_SHAPE;
-    RowAttnArgs a;
+    RowAttnArgs& a = *args;
     a.X = (const bf16_t*)X; a.W = (const bf16_t*)Wqkv; a.colsum = colsum; a.cvec = cvec; a.O = (bf16_t*)O;
     a.M = M; a.ldx = ldx; a.ldo = ldo; a.L = L;
     const bool wide = L > 16;
-    a.P = L <= 1 ? 1 : L <= 2 ? 2 : L <= 4 ? 4 : L <= 8 ? 8 : 16;
-    a.G = 16 / a.P;
+    group_cell(L, a.P, a.G);
     a.n_groups = n_outer * n_inner; a.n_inner = n_inner; a.outer_stride = outer_stride; a.seq_stride = seq_stride;
     a.eps = eps; a.scale_log2 = scale * 1.4426950408889634f;
     const long long tiles = wide ? 2 * a.n_groups : (a.n_groups + a.G - 1) / a.G;
     const long long total = ((tiles + NW * HB - 1) / (NW * HB)) * RA_HEADS;
-    const int blocks = (int)(total < 256 ? total : 256);
+    p->P = a.P;
+    p->G = a.G;
+    p->wide = wide ? 1 : 0;
+    p->blocks = (int)(total < 256 ? total : 256);
+    p->tiles = tiles;
+    return BYA_OK;
+}
+
+}  // namespace
+
+extern "C" int bya_rowgemm512_plan(const void* X, const void* W, const float* colsum, const float* cvec, const void* res,
+                                   const void* C, int32_t M, int32_t N, int32_t ldx, int32_t ldc, int32_t ldres, int32_t ln,
+                                   int32_t act, bya_rowgemm512_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    RowGemmArgs a;
+    bya_rowgemm512_plan_info p;
+    const int rc = rowgemm_plan_of(X, W, colsum, cvec, res, C, M, N, ldx, ldc, ldres, ln, 0.0f, act, &a, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_rowgemm512(const void* X, const void* W, const float* colsum, const float* cvec, const void* res,
+                              void* C, int32_t M, int32_t N, int32_t ldx, int32_t ldc, int32_t ldres, int32_t ln,
+                              float eps, int32_t act, int32_t nsplit, hipStream_t stream) {
+    (void)nsplit;      // kept in the ABI as a tuning hint; the persistent schedule balances by itself
+    RowGemmArgs a;
+    bya_rowgemm512_plan_info p;
+    const int rc = rowgemm_plan_of(X, W, colsum, cvec, res, C, M, N, ldx, ldc, ldres, ln, eps, act, &a, &p);
+    if (rc != BYA_OK) return rc;
+    const bool gelu = p.act == BYA_ACT_GELU_ERF;
+    if (p.form == BYA_ROWGEMM_W_STATIONARY) {
+        if (p.res) return gelu ? launch_rowgemm_q<false, true, BYA_ACT_GELU_ERF>(a, p.grid, stream) : launch_rowgemm_q<false, true, BYA_ACT_NONE>(a, p.grid, stream);
+        return gelu ? launch_rowgemm_q<false, false, BYA_ACT_GELU_ERF>(a, p.grid, stream) : launch_rowgemm_q<false, false, BYA_ACT_NONE>(a, p.grid, stream);
+    }
+    if (p.ln) {
+        if (p.res) return gelu ? launch_rowgemm<true, true, BYA_ACT_GELU_ERF>(a, p.grid, stream)
+                               : launch_rowgemm<true, true, BYA_ACT_NONE>(a, p.grid, stream);
+        return gelu ? launch_rowgemm<true, false, BYA_ACT_GELU_ERF>(a, p.grid, stream)
+                    : launch_rowgemm<true, false, BYA_ACT_NONE>(a, p.grid, stream);
+    }
+    if (p.res) return gelu ? launch_rowgemm<false, true, BYA_ACT_GELU_ERF>(a, p.grid, stream)
+                           : launch_rowgemm<false, true, BYA_ACT_NONE>(a, p.grid, stream);
+    return gelu ? launch_rowgemm<false, false, BYA_ACT_GELU_ERF>(a, p.grid, stream)
+                : launch_rowgemm<false, false, BYA_ACT_NONE>(a, p.grid, stream);
+}
+
+extern "C" int bya_router_group_attn_plan(const void* X, const void* Wqkv, const float* colsum, const float* cvec, const void* O,
+                                          int32_t M, int32_t ldx, int32_t ldo, int32_t L, int64_t n_outer, int64_t n_inner,
+                                          int64_t outer_stride, int64_t seq_stride, bya_router_group_attn_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    RowAttnArgs a;
+    bya_router_group_attn_plan_info p;
+    const int rc = group_attn_plan_of(X, Wqkv, colsum, cvec, O, M, ldx, ldo, L, n_outer, n_inner, outer_stride, seq_stride, 0.0f,
+                                      0.0f, &a, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_router_group_attn(const void* X, const void* Wqkv, const float* colsum, const float* cvec, void* O,
+                                     int32_t M, int32_t ldx, int32_t ldo, int32_t L, int64_t n_outer, int64_t n_inner,
+                                     int64_t outer_stride, int64_t seq_stride, float eps, float scale, hipStream_t stream) {
+    RowAttnArgs a;
+    bya_router_group_attn_plan_info p;
+    const int rc = group_attn_plan_of(X, Wqkv, colsum, cvec, O, M, ldx, ldo, L, n_outer, n_inner, outer_stride, seq_stride, eps,
+                                      scale, &a, &p);
+    if (rc != BYA_OK) return rc;
     const size_t lds = (size_t)RA_CONST_BYTES + 2 * STAGE_BYTES;
     static std::atomic<unsigned long long> attr_done{0};
     static std::atomic<unsigned long long> attr_done_w{0};
-    if (wide) {
+    if (p.wide) {
         if (bya_allow_big_lds(reinterpret_cast<const void*>(rowattn512_kernel<true>), 160 * 1024, attr_done_w) != BYA_OK) return BYA_ERR_LAUNCH;
-        BYA_LAUNCH(rowattn512_kernel<true>, dim3(blocks), dim3(64 * NW), lds, stream, a);
+        BYA_LAUNCH(rowattn512_kernel<true>, dim3(p.blocks), dim3(64 * NW), lds, stream, a);
     } else {
         if (bya_allow_big_lds(reinterpret_cast<const void*>(rowattn512_kernel<false>), 160 * 1024, attr_done) != BYA_OK) return BYA_ERR_LAUNCH;
-        BYA_LAUNCH(rowattn512_kernel<false>, dim3(blocks), dim3(64 * NW), lds, stream, a);
+        BYA_LAUNCH(rowattn512_kernel<false>, dim3(p.blocks), dim3(64 * NW), lds, stream, a);
     }
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }

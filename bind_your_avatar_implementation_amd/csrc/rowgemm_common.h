@@ -24,6 +24,19 @@ __device__ __forceinline__ constexpr uint32_t lane_col(uint32_t g, int u) { retu
 // the attention kernels' q / k chunks: lane group g ends up with 16 consecutive features 16 g + 4 j + e of the head
 __device__ __forceinline__ constexpr uint32_t wrow_lpc(int i, int j) { return (uint32_t)(LPC * (i >> 2) + 4 * j + (i & 3)); }
 
+// Schedule arithmetic that the kernels and the host-side plan queries (bya_rowgemm512_plan & co.) share, written once:
+// the contiguous share [q0, q1) of ``total`` work items that range ``rid`` of ``n`` gets ...
+__host__ __device__ __forceinline__ void work_range(long long total, int rid, int n, int& q0, int& q1) {
+    q0 = (int)(total * rid / n);
+    q1 = (int)(total * (rid + 1) / n);
+}
+// ... and the cell of a group of L <= 16 rows in a 16-row tile: P slots (the power of two >= L), G = 16 / P groups per tile
+// (16 < L <= 32, rowattn512_kernel<true>: P = 16, a group takes the two tiles of one wave)
+inline void group_cell(int L, int& P, int& G) {
+    P = L <= 1 ? 1 : L <= 2 ? 2 : L <= 4 ? 4 : L <= 8 ? 8 : 16;
+    G = 16 / P;
+}
+
 template <int OFF>
 __device__ __forceinline__ void lds_read_w(bf16x8& dst, uint32_t addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));

@@ -1356,6 +1356,77 @@ def router_group_attn_out(x, pack, pack_out, L, n_outer, n_inner, outer_stride, 
     return out
 
 
+# ---- what the router's row kernels run (bya_rowgemm512_plan & co.: host-side, launch nothing).  ``x`` / ``out`` / ``res`` may
+# be device tensors, meta tensors, or -- with a plain row count for ``x`` -- left out (contiguous rows, aligned pointers).
+def _rows_of(x, width=512):
+    """-> (M, row stride, address) of the [M, width] rows ``x`` (a tensor) or of M contiguous rows (an int)."""
+    if isinstance(x, int):
+        return x, width, _META_BASE
+    assert x.dim() == 2 and x.shape[1] == width and x.stride(1) == 1
+    return x.shape[0], x.stride(0), _plan_p(x)
+
+
+def _like_rows(t, M, width):
+    if t is None or t is True:
+        return width, _META_BASE
+    assert tuple(t.shape) == (M, width) and t.stride(1) == 1
+    return t.stride(0), _plan_p(t)
+
+
+def rowgemm512_plan(x, N, out=None, ln=False, res=None, act=None):
+    """What ``rowgemm512`` would run: {"form" (``_hip.ROWGEMM_FORMS``), "ln", "res", "gelu" (the kernel's template instance),
+    "grid", "work_items", "crosses_row_block"}.  ``res``: None, True (some aligned residual) or the tensor."""
+    lib = _hip.load()
+    M, ldx, px = _rows_of(x)
+    ldc, pc = _like_rows(out, M, N)
+    ldres, pr = _like_rows(res, M, N) if res is not None else (0, None)
+    p = _hip.RowGemmPlan()
+    check(lib.bya_rowgemm512_plan(px, _META_BASE, _META_BASE if ln else None, _META_BASE, pr, pc, M, N, ldx, ldc, ldres, int(ln),
+                                  ACT[act], ctypes.byref(p)), "bya_rowgemm512_plan")
+    return {"form": _hip.ROWGEMM_FORMS[p.form], "ln": bool(p.ln), "res": bool(p.res), "gelu": p.act == ACT["gelu_erf"],
+            "grid": p.grid, "work_items": p.work_items, "crosses_row_block": bool(p.crosses_row_block)}
+
+
+def _chain_dict(p):
+    return {"tiles": p.tiles, "tp0": p.tp0, "grid": p.grid, "passes": p.passes, "tiles_last": p.tiles_last, "wgs_last": p.wgs_last}
+
+
+def router_mlp_fused_plan(x, out=None, tiles_pass0=0):
+    """What ``router_mlp_fused`` would run: {"tiles", "tp0", "grid", "passes", "tiles_last" (tiles per workgroup in the last
+    pass), "wgs_last" (workgroups that have a tile there)}."""
+    lib = _hip.load()
+    M, ldx, px = _rows_of(x)
+    ldc, pc = _like_rows(out, M, 512) if out is not None else (ldx, px)
+    p, b = _hip.RouterChainPlan(), _META_BASE
+    check(lib.bya_router_mlp_fused_plan(px, b, b, b, b, b, pc, M, ldx, ldc, int(tiles_pass0), ctypes.byref(p)),
+          "bya_router_mlp_fused_plan")
+    return _chain_dict(p)
+
+
+def router_group_attn_out_plan(x, L, n_outer, n_inner, outer_stride, seq_stride, out=None, tiles_pass0=0):
+    """What ``router_group_attn_out`` would run (``router_mlp_fused_plan``'s dict; its tiles hold 16 / P whole groups)."""
+    lib = _hip.load()
+    M, ldx, px = _rows_of(x)
+    ldc, pc = _like_rows(out, M, 512) if out is not None else (ldx, px)
+    p, b = _hip.RouterChainPlan(), _META_BASE
+    check(lib.bya_router_group_attn_out_plan(px, b, b, b, b, b, pc, M, ldx, ldc, int(L), int(n_outer), int(n_inner),
+                                             int(outer_stride), int(seq_stride), int(tiles_pass0), ctypes.byref(p)),
+          "bya_router_group_attn_out_plan")
+    return _chain_dict(p)
+
+
+def router_group_attn_plan(x, L, n_outer, n_inner, outer_stride, seq_stride, out=None):
+    """What ``router_group_attn`` would run: {"P" (slots per group), "G" (groups per 16-row tile), "wide" (16 < L <= 32: the
+    two-tile kernel), "tiles", "blocks"}."""
+    lib = _hip.load()
+    M, ldx, px = _rows_of(x)
+    ldo, po = _like_rows(out, M, 512)
+    p, b = _hip.GroupAttnPlan(), _META_BASE
+    check(lib.bya_router_group_attn_plan(px, b, b, b, po, M, ldx, ldo, int(L), int(n_outer), int(n_inner), int(outer_stride),
+                                         int(seq_stride), ctypes.byref(p)), "bya_router_group_attn_plan")
+    return {"P": p.P, "G": p.G, "wide": bool(p.wide), "tiles": p.tiles, "blocks": p.blocks}
+
+
 # ---- video VAE (SURVEY.md section 8f row 4; csrc/vae.hip) ----------------------------------------------------------
 def vae_patches(x, cache, out, KT, stride, pad, up, tmode, Ho, Wo, t0, nt):
     """Patch matrix of a causal KT x 3 x 3 convolution over channels-last x [Ts, Hs, Ws, C] -> out [nt * Ho * Wo, Kpad]."""

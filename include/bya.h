@@ -623,6 +623,22 @@ int bya_act_add(const void* x, const void* r, void* y, int64_t n, int32_t act, h
 int bya_rowgemm512(const void* X, const void* W, const float* colsum, const float* cvec, const void* res, void* C,
                    int32_t M, int32_t N, int32_t ldx, int32_t ldc, int32_t ldres, int32_t ln, float eps, int32_t act,
                    int32_t nsplit, hipStream_t stream);
+/* What a bya_rowgemm512 launch runs (host-side query like bya_gemm_bf16_plan: validates like the entry point, launches nothing,
+ * needs no GPU; the launcher takes every decision from the same function).  form: the chunk-balanced kernel (every (256-row
+ * block, 64-column chunk) pair, cut into `grid` equal contiguous ranges) or, for N = 512 without LayerNorm at
+ * 2048 <= M <= 65536, the W-stationary one (64 row groups x 4 W quarters; its work items are the 16-row tiles). */
+#define BYA_ROWGEMM_CHUNK_BALANCED 0
+#define BYA_ROWGEMM_W_STATIONARY 1
+typedef struct bya_rowgemm512_plan_info {
+    int32_t form;               /* BYA_ROWGEMM_* */
+    int32_t ln, res, act;       /* the template instance <LN, RES, ACT> */
+    int32_t grid;               /* workgroups of 8 waves */
+    int32_t crosses_row_block;  /* chunk-balanced: some workgroup's range holds chunks of two row blocks */
+    int64_t work_items;         /* chunk-balanced: row blocks x chunks; W-stationary: 16-row tiles */
+} bya_rowgemm512_plan_info;
+int bya_rowgemm512_plan(const void* X, const void* W, const float* colsum, const float* cvec, const void* res, const void* C,
+                        int32_t M, int32_t N, int32_t ldx, int32_t ldc, int32_t ldres, int32_t ln, int32_t act,
+                        bya_rowgemm512_plan_info* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused  LayerNorm(512) -> to_q | to_k | to_v (8 heads x 64) -> softmax(q k^T / 8) v  over SMALL groups of rows: the
@@ -641,6 +657,16 @@ int bya_rowgemm512(const void* X, const void* W, const float* colsum, const floa
 int bya_router_group_attn(const void* X, const void* Wqkv, const float* colsum, const float* cvec, void* O,
                           int32_t M, int32_t ldx, int32_t ldo, int32_t L, int64_t n_outer, int64_t n_inner,
                           int64_t outer_stride, int64_t seq_stride, float eps, float scale, hipStream_t stream);
+/* What a bya_router_group_attn launch runs (host-side query): P slots per group (the power of two >= L; 16 when wide), G = 16 / P
+ * groups per 16-row tile, wide (16 < L <= 32: a group takes the two tiles of one wave), the tiles and the workgroups. */
+typedef struct bya_router_group_attn_plan_info {
+    int32_t P, G, wide;
+    int32_t blocks;             /* workgroups of 8 waves x 2 tiles */
+    int64_t tiles;
+} bya_router_group_attn_plan_info;
+int bya_router_group_attn_plan(const void* X, const void* Wqkv, const float* colsum, const float* cvec, const void* O,
+                               int32_t M, int32_t ldx, int32_t ldo, int32_t L, int64_t n_outer, int64_t n_inner,
+                               int64_t outer_stride, int64_t seq_stride, bya_router_group_attn_plan_info* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Router chains (round 6; csrc/rowchain.hip): two Linears of a SpatialTemporalAttentionBlock sub-block in ONE launch, the
@@ -667,6 +693,19 @@ int bya_router_group_attn_out(const void* X, const void* Wqkv, const float* cols
                               const float* cvec_o, void* C, int32_t M, int32_t ldx, int32_t ldc, int32_t L, int64_t n_outer,
                               int64_t n_inner, int64_t outer_stride, int64_t seq_stride, float eps, float scale,
                               int32_t tiles_pass0, hipStream_t stream);
+/* What a chain launch runs (host-side queries): the 16-row tiles, the first pass's tiles per workgroup (tiles_pass0, or the
+ * library's choice for 0), the grid, the number of passes over the rows, and the last pass: tiles per workgroup there and how
+ * many workgroups have one (the others only keep staging W). */
+typedef struct bya_router_chain_plan_info {
+    int32_t tiles, tp0, grid, passes, tiles_last, wgs_last;
+} bya_router_chain_plan_info;
+int bya_router_mlp_fused_plan(const void* X, const void* W1, const float* colsum1, const float* cvec1, const void* W2,
+                              const float* cvec2, const void* C, int32_t M, int32_t ldx, int32_t ldc, int32_t tiles_pass0,
+                              bya_router_chain_plan_info* plan);
+int bya_router_group_attn_out_plan(const void* X, const void* Wqkv, const float* colsum, const float* cvec, const void* Wo,
+                                   const float* cvec_o, const void* C, int32_t M, int32_t ldx, int32_t ldc, int32_t L,
+                                   int64_t n_outer, int64_t n_inner, int64_t outer_stride, int64_t seq_stride,
+                                   int32_t tiles_pass0, bya_router_chain_plan_info* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Classifier-free-guidance combine + scheduler step in one pass over the latents.

@@ -24,7 +24,8 @@ def declared_symbols():
 def test_header_declares_the_documented_entry_points():
     syms = declared_symbols()
     for must in ["bya_gemm_bf16", "bya_gemm_bf16_plan", "bya_gemm_qkv_norm_rope_plan", "bya_gemm_fp8_plan", "bya_gemm_mx_plan",
-                 "bya_gemm_skinny_bf16", "bya_attn_fwd", "bya_attn_plan", "bya_attn_kv_mix_plan", "bya_attn_tiny_plan", "bya_layernorm", "bya_qknorm_rope", "bya_masked_combine",
+                 "bya_gemm_skinny_bf16", "bya_attn_fwd", "bya_attn_plan", "bya_attn_kv_mix_plan", "bya_attn_tiny_plan", "bya_rowgemm512_plan",
+                 "bya_router_mlp_fused_plan", "bya_router_group_attn_plan", "bya_router_group_attn_out_plan", "bya_layernorm", "bya_qknorm_rope", "bya_masked_combine",
                  "bya_router_scores", "bya_router_head", "bya_forcing_max_over_frames", "bya_patchify",
                  "bya_unpatchify", "bya_linear_small_m", "bya_timestep_features", "bya_attn_tiny", "bya_act_add",
                  "bya_abi_version"]:
@@ -110,6 +111,38 @@ def test_python_binding_table_matches_header(lib_path):
     assert lib.bya_attn_tiny_plan(base, base, base, base, 13, 8, 2, 90, 1536, 512, ctypes.byref(tp)) == 0
     assert (tp.instance, tp.grid, tp.waves) == (2, 45, 180)
     assert lib.bya_attn_tiny_plan(base, base + 8, base, base, 13, 8, 2, 90, 1536, 512, ctypes.byref(tp)) == 0 and tp.instance == 6
+    # the router row kernels' plan queries: validate like their entry points, fill the plan, leave it alone on rejection
+    rp = _hip.RowGemmPlan(-9)
+    assert lib.bya_rowgemm512_plan(None, base, None, base, None, base, 300, 512, 512, 512, 0, 0, 0, ctypes.byref(rp)) == -1 and rp.form == -9
+    assert lib.bya_rowgemm512_plan(base, base, None, base, None, base, 300, 512, 512, 512, 0, 0, 0, None) == -1
+    assert lib.bya_rowgemm512_plan(base, base, None, base, None, base, 300, 512, 512, 512, 0, 1, 0, ctypes.byref(rp)) == -1   # ln without colsum
+    assert lib.bya_rowgemm512_plan(base, base, None, base, None, base + 8, 300, 512, 512, 512, 0, 0, 0, ctypes.byref(rp)) == -2
+    assert lib.bya_rowgemm512_plan(base, base, None, base, None, base, 300, 512, 512, 512, 0, 0, 1, ctypes.byref(rp)) == -4   # gelu_tanh
+    assert lib.bya_rowgemm512_plan(base, base, None, base, None, base, 300, 512, 512, 512, 0, 0, 0, ctypes.byref(rp)) == 0
+    assert (rp.form, rp.ln, rp.res, rp.act, rp.grid, rp.crosses_row_block, rp.work_items) == (0, 0, 0, 0, 16, 0, 16)
+    assert lib.bya_rowgemm512_plan(base, base, None, base, base, base, 35100, 512, 768, 512, 512, 0, 2, ctypes.byref(rp)) == 0
+    assert (rp.form, rp.ln, rp.res, rp.act, rp.grid, rp.work_items) == (1, 0, 1, 2, 256, 2194)
+    assert lib.bya_rowgemm512_plan(base, base, base, base, None, base, 35100, 1536, 512, 1536, 0, 1, 0, ctypes.byref(rp)) == 0
+    assert (rp.form, rp.ln, rp.grid, rp.crosses_row_block, rp.work_items) == (0, 1, 256, 1, 138 * 24)
+    cp = _hip.RouterChainPlan(-9)
+    assert lib.bya_router_mlp_fused_plan(base, base, base, base, base, None, base, 35100, 512, 512, 0, ctypes.byref(cp)) == -1 and cp.tiles == -9
+    assert lib.bya_router_mlp_fused_plan(base, base, base, base, base, base, base, 35100, 512, 512, 9, ctypes.byref(cp)) == -1
+    assert lib.bya_router_mlp_fused_plan(base, base, base, base, base, base, base, 35100, 520, 512, 0, ctypes.byref(cp)) == 0
+    assert (cp.tiles, cp.tp0, cp.grid, cp.passes, cp.tiles_last, cp.wgs_last) == (2194, 8, 256, 2, 1, 146)
+    assert lib.bya_router_group_attn_out_plan(base, base, base, base, base, base, base, 35100, 512, 512, 17, 2, 1350, 17550, 1350, 0,
+                                              ctypes.byref(cp)) == -4
+    assert lib.bya_router_group_attn_out_plan(base, base, base, base, base, base, base, 35100, 512, 512, 13, 2, 1350, 17550, 1350, 0,
+                                              ctypes.byref(cp)) == 0
+    assert (cp.tiles, cp.tp0, cp.grid, cp.passes, cp.tiles_last, cp.wgs_last) == (2700, 8, 256, 2, 3, 218)
+    gp = _hip.GroupAttnPlan(-9)
+    assert lib.bya_router_group_attn_plan(base, base, base, base, base, 35100, 512, 512, 33, 2, 1350, 17550, 1350, ctypes.byref(gp)) == -4
+    assert gp.P == -9 and lib.bya_router_group_attn_plan(base, base, base, base, base, 35100, 512, 512, 13, 2, 1350, 17550, 1350, None) == -1
+    assert lib.bya_router_group_attn_plan(base, base, base, base, base, 35100, 512, 512, 13, 2, 1350, 17550, 1350, ctypes.byref(gp)) == 0
+    assert (gp.P, gp.G, gp.wide, gp.blocks, gp.tiles) == (16, 1, 0, 256, 2700)
+    assert lib.bya_router_group_attn_plan(base, base, base, base, base, 3333, 512, 512, 3, 1, 1111, 0, 1111, ctypes.byref(gp)) == 0
+    assert (gp.P, gp.G, gp.wide, gp.blocks, gp.tiles) == (4, 4, 0, 144, 278)
+    assert lib.bya_router_group_attn_plan(base, base, base, base, base, 2250, 512, 512, 25, 2, 45, 1125, 45, ctypes.byref(gp)) == 0
+    assert (gp.P, gp.G, gp.wide, gp.tiles) == (16, 1, 1, 180)
     # the RCCL entry points validate their arguments before touching a communicator
     assert lib.bya_allgather_kv(None, None, None, None, 1, 1, None, None) == -1
     cnt = (ctypes.c_int64 * 2)(1, 1)
@@ -122,7 +155,8 @@ def test_struct_layout_matches_header():
     src = open(os.path.join(ROOT, "include", "bya.h")).read()
     for cname, cls in (("bya_gemm_desc", _hip.GemmDesc), ("bya_attn_desc", _hip.AttnDesc), ("bya_gemm_plan", _hip.GemmPlan),
                        ("bya_attn_plan_info", _hip.AttnPlan), ("bya_attn_kv_mix_plan_info", _hip.AttnMixPlan),
-                       ("bya_attn_tiny_plan_info", _hip.AttnTinyPlan)):
+                       ("bya_attn_tiny_plan_info", _hip.AttnTinyPlan), ("bya_rowgemm512_plan_info", _hip.RowGemmPlan),
+                       ("bya_router_group_attn_plan_info", _hip.GroupAttnPlan), ("bya_router_chain_plan_info", _hip.RouterChainPlan)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), src, flags=re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         fields = []
