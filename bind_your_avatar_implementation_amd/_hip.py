@@ -69,6 +69,15 @@ class GroupAttnPlan(_c.Structure):
     _fields_ = [("P", _i32), ("G", _i32), ("wide", _i32), ("blocks", _i32), ("tiles", _i64)]
 
 
+class LayerNormPlan(_c.Structure):
+    _fields_ = [("kernel", _i32), ("vec", _i32), ("nv", _i32), ("modulated", _i32), ("rows_per_wave", _i32), ("grid", _i32),
+                ("waves", _i64)]
+
+
+class QkNormRopePlan(_c.Structure):
+    _fields_ = [("stats", _i32), ("only", _i32), ("grid", _i32), ("slots", _i32), ("pairs", _i64), ("waves", _i64)]
+
+
 class RouterChainPlan(_c.Structure):
     _fields_ = [("tiles", _i32), ("tp0", _i32), ("grid", _i32), ("passes", _i32), ("tiles_last", _i32), ("wgs_last", _i32)]
 
@@ -119,6 +128,10 @@ SIGNATURES = {
     "bya_timestep_features": [_vp, _vp, _i32, _i32, _i32, _f32, _vp],
     "bya_layernorm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
                       _f32, _vp],
+    "bya_layernorm_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
+                           _i32, _c.POINTER(LayerNormPlan)],
+    "bya_qknorm_rope_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i32, _vp, _i32,
+                             _c.POINTER(QkNormRopePlan)],
     "bya_qknorm_rope": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i32, _f32, _f32, _vp, _i32, _vp],
     "bya_attn_fwd": [_vp, _vp, _vp, _vp, _c.POINTER(AttnDesc), _vp],
     "bya_attn_variant": [_c.POINTER(AttnDesc)],
@@ -206,6 +219,9 @@ TINY_INSTANCES = {0: "tiny8<2>", 1: "tiny8<3>", 2: "tiny8<13>", 3: "tiny8<25>", 
                   6: "generic<16>", 7: "generic<32>"}
 
 ROWGEMM_FORMS = {0: "chunk_balanced", 1: "w_stationary"}       # BYA_ROWGEMM_* (bya_rowgemm512_plan)
+
+LN_KERNELS = {0: "generic", 1: "rows"}                          # BYA_LN_KERNEL_* (bya_layernorm_plan)
+LN_OUT_KINDS = {"bf16": 0, "fp8": 1, "mxfp8": 2, "mxfp6": 3}    # BYA_LN_OUT_*
 
 ERRORS = {-1: "BYA_ERR_SHAPE", -2: "BYA_ERR_ALIGN", -3: "BYA_ERR_LAUNCH", -4: "BYA_ERR_UNSUPPORTED"}
 

@@ -241,24 +241,66 @@ __global__ __launch_bounds__(256) void layernorm_adaln_rows_kernel(LnArgs p, int
     }
 }
 
+// bya_layernorm / _fp8 / _mx: argument checks, the kernel arguments and every launch decision -- the width switch, the
+// rows kernel against the generic one (the BYA_REF_LN_GENERIC reference form), rows_per_wave, the grid -- for the launchers
+// and bya_layernorm_plan alike.  `y` is the bf16 output, or the fp8 / MX code matrix (ldy / y_bs in bytes).
+int ln_plan_of(int32_t out_kind, const void* x, const void* y, const void* w, const void* b, const void* shift0,
+               const void* scale0, const void* shift1, const void* scale1, int64_t rows_per_batch, int32_t batch, int32_t D,
+               int64_t ldx, int64_t ldy, int64_t x_batch_stride, int64_t y_batch_stride, int64_t mod_batch_stride,
+               int64_t split, float eps, LnArgs* args, bya_layernorm_plan_info* p) {
+    if (out_kind != BYA_LN_OUT_BF16 && out_kind != BYA_LN_OUT_FP8 && out_kind != BYA_LN_OUT_MX_E4M3 &&
+        out_kind != BYA_LN_OUT_MX_E2M3) return BYA_ERR_SHAPE;
+    if (!x || !y || rows_per_batch <= 0 || batch <= 0) return BYA_ERR_SHAPE;
+    if ((shift0 == nullptr) != (scale0 == nullptr)) return BYA_ERR_SHAPE;
+    const bool bf16_out = out_kind == BYA_LN_OUT_BF16;
+    if (((uintptr_t)x & 15) || ((uintptr_t)y & (bf16_out ? 15 : 7))) return BYA_ERR_ALIGN;
+    if ((ldx | ldy | x_batch_stride | y_batch_stride) % 8) return BYA_ERR_ALIGN;
+    const int mxf = out_kind == BYA_LN_OUT_MX_E4M3 ? MX_E4M3 : MX_E2M3;
+    if (!bf16_out && D != 3072) return BYA_ERR_UNSUPPORTED;      // the DiT width: the only LayerNorm in front of a quantised Linear
+    if (out_kind >= BYA_LN_OUT_MX_E4M3 && ldy < (int64_t)D / 32 * mx_block_bytes(mxf)) return BYA_ERR_SHAPE;
+    switch (D) {                                                 // D = 64 * vec * nv
+        case 512: p->vec = 8; p->nv = 1; break;
+        case 768: p->vec = 4; p->nv = 3; break;
+        case 1024: p->vec = 8; p->nv = 2; break;
+        case 2048: p->vec = 8; p->nv = 4; break;
+        case 3072: p->vec = 8; p->nv = 6; break;
+        default: return BYA_ERR_UNSUPPORTED;
+    }
+    LnArgs& a = *args;
+    a.x = (const bf16_t*)x; a.y = (bf16_t*)const_cast<void*>(y); a.w = (const bf16_t*)w; a.b = (const bf16_t*)b;
+    a.shift0 = (const bf16_t*)shift0; a.scale0 = (const bf16_t*)scale0;
+    a.shift1 = (const bf16_t*)(shift1 ? shift1 : shift0); a.scale1 = (const bf16_t*)(scale1 ? scale1 : scale0);
+    a.rows_per_batch = rows_per_batch; a.ldx = ldx; a.ldy = ldy; a.x_bs = x_batch_stride; a.y_bs = y_batch_stride;
+    a.mod_bs = mod_batch_stride; a.split = split; a.batch = batch; a.eps = eps; a.q_scale = nullptr; a.mx_scales = nullptr;
+    const long long total = (long long)rows_per_batch * batch;
+    p->modulated = shift0 ? 1 : 0;
+    // D = 3072 with w and b: the parameters-in-registers kernel (whatever the row count: a shard of the sequence must round
+    // exactly like the whole)
+    if (bf16_out && D == 3072 && w && b && !bya_ref_form(BYA_REF_LN_GENERIC)) {
+        p->kernel = BYA_LN_KERNEL_ROWS;
+        // about 16 waves per CU in flight (4096 waves), at least 2 rows each so the parameter set-up is amortised
+        int rpw = (int)((total + 4095) / 4096);
+        p->rows_per_wave = rpw < 2 ? 2 : rpw;
+    } else {
+        p->kernel = BYA_LN_KERNEL_GENERIC;
+        p->rows_per_wave = 1;
+    }
+    p->waves = (total + p->rows_per_wave - 1) / p->rows_per_wave;
+    p->grid = (int32_t)((p->waves + 3) / 4);
+    return BYA_OK;
+}
+
 template <int NV>
-int launch_ln_adaln_rows(const LnArgs& a, hipStream_t s) {
-    const long long total = a.rows_per_batch * a.batch;
-    // about 16 waves per CU in flight (4096 waves), at least 2 rows each so the parameter set-up is amortised
-    int rpw = (int)((total + 4095) / 4096);
-    rpw = rpw < 2 ? 2 : rpw;
-    const long long waves = (total + rpw - 1) / rpw;
-    dim3 grid((unsigned)((waves + 3) / 4));
-    if (a.shift0) BYA_LAUNCH((layernorm_adaln_rows_kernel<NV, true>), grid, dim3(256), 0, s, a, rpw);
-    else BYA_LAUNCH((layernorm_adaln_rows_kernel<NV, false>), grid, dim3(256), 0, s, a, rpw);
+int launch_ln_adaln_rows(const LnArgs& a, const bya_layernorm_plan_info& p, hipStream_t s) {
+    dim3 grid((unsigned)p.grid);
+    if (p.modulated) BYA_LAUNCH((layernorm_adaln_rows_kernel<NV, true>), grid, dim3(256), 0, s, a, p.rows_per_wave);
+    else BYA_LAUNCH((layernorm_adaln_rows_kernel<NV, false>), grid, dim3(256), 0, s, a, p.rows_per_wave);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 
 template <int VEC, int NV, bool Q8 = false, int MXF = -1>
-int launch_ln(const LnArgs& a, hipStream_t s) {
-    const long long total = a.rows_per_batch * a.batch;
-    dim3 grid((unsigned)((total + 3) / 4));
-    BYA_LAUNCH((layernorm_kernel<VEC, NV, Q8, MXF>), grid, dim3(256), 0, s, a);
+int launch_ln(const LnArgs& a, const bya_layernorm_plan_info& p, hipStream_t s) {
+    BYA_LAUNCH((layernorm_kernel<VEC, NV, Q8, MXF>), dim3((unsigned)p.grid), dim3(256), 0, s, a);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 
@@ -346,31 +388,37 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(QkArgs p) {
 
 }  // namespace
 
+extern "C" int bya_layernorm_plan(const void* x, const void* y, const void* w, const void* b, const void* shift0,
+                                  const void* scale0, const void* shift1, const void* scale1, int64_t rows_per_batch,
+                                  int32_t batch, int32_t D, int64_t ldx, int64_t ldy, int64_t x_batch_stride,
+                                  int64_t y_batch_stride, int64_t mod_batch_stride, int64_t split, int32_t out_kind,
+                                  bya_layernorm_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    LnArgs a;
+    bya_layernorm_plan_info p;
+    const int rc = ln_plan_of(out_kind, x, y, w, b, shift0, scale0, shift1, scale1, rows_per_batch, batch, D, ldx, ldy,
+                              x_batch_stride, y_batch_stride, mod_batch_stride, split, 0.0f, &a, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
 extern "C" int bya_layernorm(const void* x, void* y, const void* w, const void* b, const void* shift0,
                              const void* scale0, const void* shift1, const void* scale1, int64_t rows_per_batch,
                              int32_t batch, int32_t D, int64_t ldx, int64_t ldy, int64_t x_batch_stride,
                              int64_t y_batch_stride, int64_t mod_batch_stride, int64_t split, float eps,
                              hipStream_t stream) {
-    if (!x || !y || rows_per_batch <= 0 || batch <= 0) return BYA_ERR_SHAPE;
-    if ((shift0 == nullptr) != (scale0 == nullptr)) return BYA_ERR_SHAPE;
-    if (((uintptr_t)x | (uintptr_t)y) & 15) return BYA_ERR_ALIGN;
-    if ((ldx | ldy | x_batch_stride | y_batch_stride) % 8) return BYA_ERR_ALIGN;
     LnArgs a;
-    a.x = (const bf16_t*)x; a.y = (bf16_t*)y; a.w = (const bf16_t*)w; a.b = (const bf16_t*)b;
-    a.shift0 = (const bf16_t*)shift0; a.scale0 = (const bf16_t*)scale0;
-    a.shift1 = (const bf16_t*)(shift1 ? shift1 : shift0); a.scale1 = (const bf16_t*)(scale1 ? scale1 : scale0);
-    a.rows_per_batch = rows_per_batch; a.ldx = ldx; a.ldy = ldy; a.x_bs = x_batch_stride; a.y_bs = y_batch_stride;
-    a.mod_bs = mod_batch_stride; a.split = split; a.batch = batch; a.eps = eps; a.q_scale = nullptr; a.mx_scales = nullptr;
-    switch (D) {
-        case 512: return launch_ln<8, 1>(a, stream);
-        case 768: return launch_ln<4, 3>(a, stream);
-        case 1024: return launch_ln<8, 2>(a, stream);
-        case 2048: return launch_ln<8, 4>(a, stream);
-        case 3072: {
-            // (whatever the row count: a shard of the sequence must round exactly like the whole)
-            if (a.w && a.b && !bya_ref_form(BYA_REF_LN_GENERIC)) return launch_ln_adaln_rows<6>(a, stream);
-            return launch_ln<8, 6>(a, stream);
-        }
+    bya_layernorm_plan_info p;
+    const int rc = ln_plan_of(BYA_LN_OUT_BF16, x, y, w, b, shift0, scale0, shift1, scale1, rows_per_batch, batch, D, ldx, ldy,
+                              x_batch_stride, y_batch_stride, mod_batch_stride, split, eps, &a, &p);
+    if (rc != BYA_OK) return rc;
+    if (p.kernel == BYA_LN_KERNEL_ROWS) return launch_ln_adaln_rows<6>(a, p, stream);
+    switch (p.vec * 16 + p.nv) {
+        case 8 * 16 + 1: return launch_ln<8, 1>(a, p, stream);
+        case 4 * 16 + 3: return launch_ln<4, 3>(a, p, stream);
+        case 8 * 16 + 2: return launch_ln<8, 2>(a, p, stream);
+        case 8 * 16 + 4: return launch_ln<8, 4>(a, p, stream);
+        case 8 * 16 + 6: return launch_ln<8, 6>(a, p, stream);
         default: return BYA_ERR_UNSUPPORTED;
     }
 }
@@ -380,18 +428,14 @@ extern "C" int bya_layernorm_fp8(const void* x, void* q, float* q_scale, const v
                                  int32_t batch, int32_t D, int64_t ldx, int64_t ldq, int64_t x_batch_stride,
                                  int64_t q_batch_stride, int64_t mod_batch_stride, int64_t split, float eps,
                                  hipStream_t stream) {
-    if (!x || !q || !q_scale || rows_per_batch <= 0 || batch <= 0) return BYA_ERR_SHAPE;
-    if ((shift0 == nullptr) != (scale0 == nullptr)) return BYA_ERR_SHAPE;
-    if (((uintptr_t)x & 15) || ((uintptr_t)q & 7)) return BYA_ERR_ALIGN;
-    if ((ldx | ldq | x_batch_stride | q_batch_stride) % 8) return BYA_ERR_ALIGN;
+    if (!q_scale) return BYA_ERR_SHAPE;
     LnArgs a;
-    a.x = (const bf16_t*)x; a.y = (bf16_t*)q; a.w = (const bf16_t*)w; a.b = (const bf16_t*)b;
-    a.shift0 = (const bf16_t*)shift0; a.scale0 = (const bf16_t*)scale0;
-    a.shift1 = (const bf16_t*)(shift1 ? shift1 : shift0); a.scale1 = (const bf16_t*)(scale1 ? scale1 : scale0);
-    a.rows_per_batch = rows_per_batch; a.ldx = ldx; a.ldy = ldq; a.x_bs = x_batch_stride; a.y_bs = q_batch_stride;
-    a.mod_bs = mod_batch_stride; a.split = split; a.batch = batch; a.eps = eps; a.q_scale = q_scale; a.mx_scales = nullptr;
-    if (D != 3072) return BYA_ERR_UNSUPPORTED;          // the DiT width: the only LayerNorm in front of an fp8 Linear
-    return launch_ln<8, 6, true>(a, stream);
+    bya_layernorm_plan_info p;
+    const int rc = ln_plan_of(BYA_LN_OUT_FP8, x, q, w, b, shift0, scale0, shift1, scale1, rows_per_batch, batch, D, ldx, ldq,
+                              x_batch_stride, q_batch_stride, mod_batch_stride, split, eps, &a, &p);
+    if (rc != BYA_OK) return rc;
+    a.q_scale = q_scale;
+    return launch_ln<8, 6, true>(a, p, stream);
 }
 
 extern "C" int bya_layernorm_mx(const void* x, void* q, void* q_scales, const void* w, const void* b, const void* shift0,
@@ -399,42 +443,68 @@ extern "C" int bya_layernorm_mx(const void* x, void* q, void* q_scales, const vo
                                 int32_t batch, int32_t D, int64_t ldx, int64_t ldq, int64_t x_batch_stride,
                                 int64_t q_batch_stride, int64_t mod_batch_stride, int64_t split, float eps, int32_t fmt,
                                 hipStream_t stream) {
-    if (!x || !q || !q_scales || rows_per_batch <= 0 || batch <= 0) return BYA_ERR_SHAPE;
+    if (!q_scales) return BYA_ERR_SHAPE;
     if (fmt != MX_E4M3 && fmt != MX_E2M3) return BYA_ERR_SHAPE;
-    if ((shift0 == nullptr) != (scale0 == nullptr)) return BYA_ERR_SHAPE;
-    if (((uintptr_t)x & 15) || ((uintptr_t)q & 7)) return BYA_ERR_ALIGN;
-    if ((ldx | ldq | x_batch_stride | q_batch_stride) % 8) return BYA_ERR_ALIGN;
-    if (D != 3072) return BYA_ERR_UNSUPPORTED;          // the DiT width: the only LayerNorm in front of an MX Linear
-    if (ldq < (int64_t)D / 32 * mx_block_bytes(fmt)) return BYA_ERR_SHAPE;
     LnArgs a;
-    a.x = (const bf16_t*)x; a.y = (bf16_t*)q; a.w = (const bf16_t*)w; a.b = (const bf16_t*)b;
-    a.shift0 = (const bf16_t*)shift0; a.scale0 = (const bf16_t*)scale0;
-    a.shift1 = (const bf16_t*)(shift1 ? shift1 : shift0); a.scale1 = (const bf16_t*)(scale1 ? scale1 : scale0);
-    a.rows_per_batch = rows_per_batch; a.ldx = ldx; a.ldy = ldq; a.x_bs = x_batch_stride; a.y_bs = q_batch_stride;
-    a.mod_bs = mod_batch_stride; a.split = split; a.batch = batch; a.eps = eps; a.q_scale = nullptr;
+    bya_layernorm_plan_info p;
+    const int rc = ln_plan_of(fmt == MX_E4M3 ? BYA_LN_OUT_MX_E4M3 : BYA_LN_OUT_MX_E2M3, x, q, w, b, shift0, scale0, shift1, scale1,
+                              rows_per_batch, batch, D, ldx, ldq, x_batch_stride, q_batch_stride, mod_batch_stride, split, eps,
+                              &a, &p);
+    if (rc != BYA_OK) return rc;
     a.mx_scales = (uint8_t*)q_scales;
-    return fmt == MX_E4M3 ? launch_ln<8, 6, false, MX_E4M3>(a, stream) : launch_ln<8, 6, false, MX_E2M3>(a, stream);
+    return fmt == MX_E4M3 ? launch_ln<8, 6, false, MX_E4M3>(a, p, stream) : launch_ln<8, 6, false, MX_E2M3>(a, p, stream);
 }
 
-extern "C" int bya_qknorm_rope(void* q, void* k, const void* qw, const void* qb, const void* kw, const void* kb,
-                               const float* cos, const float* sin, int32_t batch, int32_t S, int32_t heads,
-                               int64_t ld, int64_t batch_stride, int32_t text_rows, float eps, float k_scale,
-                               float* stats, int32_t stats_slots, hipStream_t stream) {
+namespace {
+// bya_qknorm_rope: argument checks, the kernel arguments, the instance and the grid (launcher and bya_qknorm_rope_plan)
+int qk_plan_of(const void* q, const void* k, const void* qw, const void* qb, const void* kw, const void* kb, const float* cos,
+               const float* sin, int32_t batch, int32_t S, int32_t heads, int64_t ld, int64_t batch_stride, int32_t text_rows,
+               float eps, float k_scale, const float* stats, int32_t stats_slots, QkArgs* args, bya_qknorm_rope_plan_info* p) {
     if ((!q && !k) || !qw || !qb || !kw || !kb || batch <= 0 || S <= 0 || heads <= 0) return BYA_ERR_SHAPE;
     if (text_rows < S && (!cos || !sin)) return BYA_ERR_SHAPE;
     if (stats && (stats_slots < 1 || stats_slots > 64)) return BYA_ERR_SHAPE;
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)cos | (uintptr_t)sin | (uintptr_t)qw | (uintptr_t)kw |
          (uintptr_t)qb | (uintptr_t)kb) & 15) return BYA_ERR_ALIGN;
     if ((ld | batch_stride) % 8 || ((uintptr_t)stats & 3)) return BYA_ERR_ALIGN;
-    QkArgs a;
-    a.q = (bf16_t*)q; a.k = (bf16_t*)k; a.qw = (const bf16_t*)qw; a.qb = (const bf16_t*)qb;
+    QkArgs& a = *args;
+    a.q = (bf16_t*)const_cast<void*>(q); a.k = (bf16_t*)const_cast<void*>(k); a.qw = (const bf16_t*)qw; a.qb = (const bf16_t*)qb;
     a.kw = (const bf16_t*)kw; a.kb = (const bf16_t*)kb; a.cos = cos; a.sin = sin;
     a.batch = batch; a.S = S; a.heads = heads; a.text_rows = text_rows; a.ld = ld; a.bs = batch_stride; a.eps = eps; a.k_scale = k_scale == 0.0f ? 1.0f : k_scale;
     a.only = !k ? 1 : !q ? 2 : 0;                                             // one tensor alone (the other pointer is NULL)
-    a.stats = stats; a.stats_slots = stats_slots;
-    const long long total = ((long long)batch * S * heads * (a.only ? 1 : 2) + 7) / 8;      // waves: 8 (row, head) pairs each
-    dim3 grid((unsigned)((total + 3) / 4));
-    if (stats) BYA_LAUNCH(qknorm_rope_kernel<true>, grid, dim3(256), 0, stream, a);
-    else BYA_LAUNCH(qknorm_rope_kernel<false>, grid, dim3(256), 0, stream, a);
+    a.stats = const_cast<float*>(stats); a.stats_slots = stats_slots;
+    p->stats = stats ? 1 : 0;
+    p->only = a.only;
+    p->slots = stats ? stats_slots : 0;
+    p->pairs = (long long)batch * S * heads * (a.only ? 1 : 2);               // (row, head) pairs, q's before k's
+    p->waves = (p->pairs + 7) / 8;                                            // 8 pairs each
+    p->grid = (int32_t)((p->waves + 3) / 4);
+    return BYA_OK;
+}
+}  // namespace
+
+extern "C" int bya_qknorm_rope_plan(const void* q, const void* k, const void* qw, const void* qb, const void* kw, const void* kb,
+                                    const float* cos, const float* sin, int32_t batch, int32_t S, int32_t heads, int64_t ld,
+                                    int64_t batch_stride, int32_t text_rows, const float* stats, int32_t stats_slots,
+                                    bya_qknorm_rope_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    QkArgs a;
+    bya_qknorm_rope_plan_info p;
+    const int rc = qk_plan_of(q, k, qw, qb, kw, kb, cos, sin, batch, S, heads, ld, batch_stride, text_rows, 0.0f, 1.0f, stats,
+                              stats_slots, &a, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_qknorm_rope(void* q, void* k, const void* qw, const void* qb, const void* kw, const void* kb,
+                               const float* cos, const float* sin, int32_t batch, int32_t S, int32_t heads,
+                               int64_t ld, int64_t batch_stride, int32_t text_rows, float eps, float k_scale,
+                               float* stats, int32_t stats_slots, hipStream_t stream) {
+    QkArgs a;
+    bya_qknorm_rope_plan_info p;
+    const int rc = qk_plan_of(q, k, qw, qb, kw, kb, cos, sin, batch, S, heads, ld, batch_stride, text_rows, eps, k_scale, stats,
+                              stats_slots, &a, &p);
+    if (rc != BYA_OK) return rc;
+    if (p.stats) BYA_LAUNCH(qknorm_rope_kernel<true>, dim3((unsigned)p.grid), dim3(256), 0, stream, a);
+    else BYA_LAUNCH(qknorm_rope_kernel<false>, dim3((unsigned)p.grid), dim3(256), 0, stream, a);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }

@@ -889,16 +889,27 @@ def layernorm(x, out, weight=None, bias=None, eps=1e-5, shift0=None, scale0=None
     return out
 
 
+def _code_rows(q, batch, rows, row_bytes, name):
+    """-> (row stride, batch stride) in bytes of a uint8 code matrix: contiguous [batch * rows * row_bytes] bytes in any shape,
+    or a strided view [(batch,) rows, row_bytes] with unit inner stride (rows padded to a wider pitch)."""
+    assert q.dtype == torch.uint8, f"{name}: expected uint8"
+    if q.is_contiguous():
+        assert q.numel() == batch * rows * row_bytes, f"{name}: {q.numel()} bytes for {batch} x {rows} rows of {row_bytes}"
+        return row_bytes, rows * row_bytes
+    assert q.stride(-1) == 1 and tuple(q.shape) in ((rows, row_bytes), (batch, rows, row_bytes)), f"{name}: shape {tuple(q.shape)}"
+    return q.stride(-2), q.stride(0) if q.dim() == 3 else 0
+
+
 def layernorm_fp8(x, q, q_scale, weight=None, bias=None, eps=1e-5, shift0=None, scale0=None, shift1=None, scale1=None,
                   split=0, mod_batch_stride=0):
     """``layernorm`` + ``quantize_rows_fp8`` of its output in one pass (same bytes, no bf16 round trip)."""
     lib = _hip.load()
     xb, rows, D, x_bs, ldx = _mat(x, "x")
-    assert q.dtype == torch.uint8 and q.is_contiguous() and q.numel() == xb * rows * D
+    ldq, q_bs = _code_rows(q, xb, rows, D, "q")
     assert q_scale.dtype == torch.float32 and q_scale.is_contiguous() and q_scale.numel() == xb * rows
     tok = _begin("bya_layernorm_fp8")
     check(lib.bya_layernorm_fp8(_p(x), _p(q), _p(q_scale), _p(weight), _p(bias), _p(shift0), _p(scale0), _p(shift1),
-                                _p(scale1), rows, xb, D, ldx, D, x_bs, rows * D, mod_batch_stride, split, float(eps),
+                                _p(scale1), rows, xb, D, ldx, ldq, x_bs, q_bs, mod_batch_stride, split, float(eps),
                                 _stream()), "bya_layernorm_fp8")
     _end(tok)
     return q, q_scale
@@ -912,11 +923,11 @@ def layernorm_mx(x, codes, scales, fmt="mxfp6", weight=None, bias=None, eps=1e-5
     code = mx_fmt_code(fmt)
     xb, rows, D, x_bs, ldx = _mat(x, "x")
     rb_ = mx_code_bytes(D, fmt)
-    assert codes.dtype == torch.uint8 and codes.is_contiguous() and codes.numel() == xb * rows * rb_
+    ldq, q_bs = _code_rows(codes, xb, rows, rb_, "codes")
     assert scales.dtype == torch.uint8 and scales.is_contiguous() and scales.numel() == xb * rows * (D // 32)
     tok = _begin("bya_layernorm_mx")
     check(lib.bya_layernorm_mx(_p(x), _p(codes), _p(scales), _p(weight), _p(bias), _p(shift0), _p(scale0), _p(shift1),
-                               _p(scale1), rows, xb, D, ldx, rb_, x_bs, rows * rb_, mod_batch_stride, split, float(eps),
+                               _p(scale1), rows, xb, D, ldx, ldq, x_bs, q_bs, mod_batch_stride, split, float(eps),
                                code, _stream()), "bya_layernorm_mx")
     _end(tok)
     return codes, scales
@@ -938,6 +949,44 @@ def qknorm_rope(q, k, qw, qb, kw, kb, cos, sin, heads, text_rows, eps=1e-6, k_sc
                               bs if b > 1 else 0, text_rows, float(eps), float(k_scale), _p(stats),
                               0 if stats is None else stats.shape[0], _stream()), "bya_qknorm_rope")
     _end(tok)
+
+
+# ---- what the norm kernels run (bya_layernorm_plan / bya_qknorm_rope_plan: host-side, launch nothing; device or meta tensors)
+def layernorm_plan(x, out, weight=None, bias=None, shift0=None, scale0=None, shift1=None, scale1=None, split=0,
+                   mod_batch_stride=0, out_kind="bf16"):
+    """What ``layernorm`` (``out_kind`` "bf16"), ``layernorm_fp8`` ("fp8") or ``layernorm_mx`` ("mxfp8" / "mxfp6") would run:
+    {"kernel" (``_hip.LN_KERNELS``), "vec", "nv", "modulated", "rows_per_wave", "waves", "grid"}.  ``out``: the bf16 output, or
+    the uint8 code matrix [(B,) rows, row bytes] of the quantised forms.  Parameters: tensors, or True for "some aligned vector"."""
+    lib = _hip.load()
+    xb, rows, D, x_bs, ldx = _mat(x, "x", allow_meta=True)
+    if out_kind == "bf16":
+        ob, rows_o, Do, y_bs, ldy = _mat(out, "out", allow_meta=True)
+        assert (xb, rows, D) == (ob, rows_o, Do)
+    else:
+        assert out.dtype == torch.uint8 and out.stride(-1) == 1 and out.dim() in (2, 3) and out.shape[-2] == rows
+        ldy, y_bs = out.stride(-2), out.stride(0) if out.dim() == 3 else 0
+    q = lambda t: _META_BASE if t is True else _plan_p(t)
+    p = _hip.LayerNormPlan()
+    check(lib.bya_layernorm_plan(_plan_p(x), _plan_p(out), q(weight), q(bias), q(shift0), q(scale0), q(shift1), q(scale1), rows, xb,
+                                 D, ldx, ldy, x_bs, y_bs, mod_batch_stride, split, _hip.LN_OUT_KINDS[out_kind], ctypes.byref(p)),
+          "bya_layernorm_plan")
+    return {"kernel": _hip.LN_KERNELS[p.kernel], "vec": p.vec, "nv": p.nv, "modulated": bool(p.modulated),
+            "rows_per_wave": p.rows_per_wave, "waves": p.waves, "grid": p.grid}
+
+
+def qknorm_rope_plan(q, k, heads, text_rows, cos=True, stats=None):
+    """What ``qknorm_rope`` would run: {"stats" (the STATS instance), "only" (0: q and k, 1: q alone, 2: k alone), "slots",
+    "pairs" ((row, head) pairs: q's, then k's), "waves" (8 pairs each), "grid"}.  ``cos``: None, True (tables present) or the
+    tensor; ``stats``: None, the number of slots, or the tensor."""
+    lib = _hip.load()
+    b, S, _, bs, ld = _mat(q if q is not None else k, "q", allow_meta=True)
+    assert q is None or k is None or _mat(k, "k", allow_meta=True) == (b, S, _, bs, ld)
+    pc = _META_BASE if cos is True else _plan_p(cos)
+    ps, slots = (None, 0) if stats is None else (_META_BASE, stats) if isinstance(stats, int) else (_plan_p(stats), stats.shape[0])
+    p, m = _hip.QkNormRopePlan(), _META_BASE
+    check(lib.bya_qknorm_rope_plan(_plan_p(q), _plan_p(k), m, m, m, m, pc, pc, b, S, heads, ld, bs if b > 1 else 0, text_rows, ps,
+                                   slots, ctypes.byref(p)), "bya_qknorm_rope_plan")
+    return {"stats": bool(p.stats), "only": p.only, "slots": p.slots, "pairs": p.pairs, "waves": p.waves, "grid": p.grid}
 
 
 # (call tag, softmax variant) -> launches since the last reset; the variant is reported by the library itself

@@ -377,6 +377,34 @@ int bya_layernorm(const void* x, void* y, const void* w, const void* b, const vo
                   const void* shift1, const void* scale1, int64_t rows_per_batch, int32_t batch, int32_t D,
                   int64_t ldx, int64_t ldy, int64_t x_batch_stride, int64_t y_batch_stride,
                   int64_t mod_batch_stride, int64_t split, float eps, hipStream_t stream);
+/* What a bya_layernorm / bya_layernorm_fp8 / bya_layernorm_mx launch runs (host-side query like bya_gemm_bf16_plan: validates
+ * like the entry point, launches nothing, needs no GPU; the launchers take every decision from the same function).  The
+ * arguments are bya_layernorm's, with y the output of the kind asked for: the bf16 matrix, or the fp8 / MX code matrix (ldy
+ * and y_batch_stride then in bytes; the scale arrays play no part in the plan).
+ *   kernel GENERIC: layernorm_kernel<vec, nv> (D = 64 * vec * nv), one row per wave, parameters re-read for every row; the
+ *                   fp8 / MX outputs are instances of it;
+ *   kernel ROWS:    layernorm_adaln_rows_kernel<nv, modulated> (D = 3072 with w and b, bf16 output, unless the reference form
+ *                   BYA_REF_LN_GENERIC is set): a wave owns rows_per_wave = max(2, ceil(rows / 4096)) consecutive rows of the
+ *                   batch-major row enumeration and keeps the parameter vectors in registers.
+ * waves = ceil(rows / rows_per_wave) waves have work, four to a workgroup. */
+#define BYA_LN_OUT_BF16 0
+#define BYA_LN_OUT_FP8 1
+#define BYA_LN_OUT_MX_E4M3 2
+#define BYA_LN_OUT_MX_E2M3 3
+#define BYA_LN_KERNEL_GENERIC 0
+#define BYA_LN_KERNEL_ROWS 1
+typedef struct bya_layernorm_plan_info {
+    int32_t kernel;         /* BYA_LN_KERNEL_* */
+    int32_t vec, nv;        /* bf16 elements per lane access, accesses per lane and row */
+    int32_t modulated;      /* shift / scale are applied (ROWS: the MOD template instance) */
+    int32_t rows_per_wave;  /* 1 for the generic kernel */
+    int32_t grid;           /* workgroups of 4 waves */
+    int64_t waves;
+} bya_layernorm_plan_info;
+int bya_layernorm_plan(const void* x, const void* y, const void* w, const void* b, const void* shift0, const void* scale0,
+                       const void* shift1, const void* scale1, int64_t rows_per_batch, int32_t batch, int32_t D, int64_t ldx,
+                       int64_t ldy, int64_t x_batch_stride, int64_t y_batch_stride, int64_t mod_batch_stride, int64_t split,
+                       int32_t out_kind, bya_layernorm_plan_info* plan);
 
 /* Per-head LayerNorm(64, eps, affine) on q and k followed by interleaved-pair RoPE on rows >= text_rows
  * (diffusers CogVideoXAttnProcessor2_0 + apply_rotary_emb; models/transformer.py:204-208).  In place.
@@ -394,6 +422,21 @@ int bya_qknorm_rope(void* q, void* k, const void* qw, const void* qb, const void
                     const float* cos, const float* sin, int32_t batch, int32_t S, int32_t heads, int64_t ld,
                     int64_t batch_stride, int32_t text_rows, float eps, float k_scale, float* stats, int32_t stats_slots,
                     hipStream_t stream);
+/* What a bya_qknorm_rope launch runs (host-side query): the STATS or the plain instance, `only` (0: q and k, 1: q alone,
+ * 2: k alone), the (row, head) pairs -- enumerated row-major over all batches, all of q's before k's -- the waves of eight
+ * pairs (one 8-lane group each) and the workgroups of four waves. */
+typedef struct bya_qknorm_rope_plan_info {
+    int32_t stats;          /* 1: qknorm_rope_kernel<true> */
+    int32_t only;
+    int32_t grid;
+    int32_t slots;          /* copies of the statistics table (0 without stats) */
+    int64_t pairs;
+    int64_t waves;
+} bya_qknorm_rope_plan_info;
+int bya_qknorm_rope_plan(const void* q, const void* k, const void* qw, const void* qb, const void* kw, const void* kb,
+                         const float* cos, const float* sin, int32_t batch, int32_t S, int32_t heads, int64_t ld,
+                         int64_t batch_stride, int32_t text_rows, const float* stats, int32_t stats_slots,
+                         bya_qknorm_rope_plan_info* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Flash attention forward, head_dim 64 or 128, no mask, fp32 online softmax, bf16 P.V on MFMA.

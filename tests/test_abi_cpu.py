@@ -25,7 +25,7 @@ def test_header_declares_the_documented_entry_points():
     syms = declared_symbols()
     for must in ["bya_gemm_bf16", "bya_gemm_bf16_plan", "bya_gemm_qkv_norm_rope_plan", "bya_gemm_fp8_plan", "bya_gemm_mx_plan",
                  "bya_gemm_skinny_bf16", "bya_attn_fwd", "bya_attn_plan", "bya_attn_kv_mix_plan", "bya_attn_tiny_plan", "bya_rowgemm512_plan",
-                 "bya_router_mlp_fused_plan", "bya_router_group_attn_plan", "bya_router_group_attn_out_plan", "bya_layernorm", "bya_qknorm_rope", "bya_masked_combine",
+                 "bya_router_mlp_fused_plan", "bya_router_group_attn_plan", "bya_router_group_attn_out_plan", "bya_layernorm", "bya_layernorm_plan", "bya_qknorm_rope", "bya_qknorm_rope_plan", "bya_masked_combine",
                  "bya_router_scores", "bya_router_head", "bya_forcing_max_over_frames", "bya_patchify",
                  "bya_unpatchify", "bya_linear_small_m", "bya_timestep_features", "bya_attn_tiny", "bya_act_add",
                  "bya_abi_version"]:
@@ -143,6 +143,38 @@ def test_python_binding_table_matches_header(lib_path):
     assert (gp.P, gp.G, gp.wide, gp.blocks, gp.tiles) == (4, 4, 0, 144, 278)
     assert lib.bya_router_group_attn_plan(base, base, base, base, base, 2250, 512, 512, 25, 2, 45, 1125, 45, ctypes.byref(gp)) == 0
     assert (gp.P, gp.G, gp.wide, gp.tiles) == (16, 1, 1, 180)
+    # the norm kernels' plan queries: validate like their entry points, fill the plan, leave it alone on rejection
+    lp = _hip.LayerNormPlan(-9)
+    ln = lambda x, y, w, b, sh, rows, batch, D, ldy, kind, plan: lib.bya_layernorm_plan(x, y, w, b, sh, sh, sh, sh, rows, batch, D, D, ldy, rows * D,
+                                                                                   rows * ldy, 2 * D, 226, kind, plan)
+    assert ln(None, base, base, base, None, 4099, 2, 3072, 3072, 0, ctypes.byref(lp)) == -1 and lp.kernel == -9
+    assert ln(base, base, base, base, None, 4099, 2, 3072, 3072, 0, None) == -1
+    assert ln(base, base, base, base, None, 4099, 2, 3072, 3072, 4, ctypes.byref(lp)) == -1                     # unknown output kind
+    assert lib.bya_layernorm_plan(base, base, None, None, base, None, None, None, 4, 1, 512, 512, 512, 0, 0, 0, 0, 0, ctypes.byref(lp)) == -1
+    assert ln(base, base + 8, base, base, None, 4099, 2, 3072, 3072, 0, ctypes.byref(lp)) == -2                 # bf16 output: 16 bytes
+    assert ln(base, base, None, None, None, 300, 1, 640, 640, 0, ctypes.byref(lp)) == -4 and lp.kernel == -9
+    assert ln(base, base, base, base, base, 4099, 2, 3072, 3072, 0, ctypes.byref(lp)) == 0
+    assert (lp.kernel, lp.vec, lp.nv, lp.modulated, lp.rows_per_wave, lp.grid, lp.waves) == (1, 8, 6, 1, 3, 684, 2733)
+    assert ln(base, base, base, None, None, 4099, 2, 3072, 3072, 0, ctypes.byref(lp)) == 0                      # w without b: generic
+    assert (lp.kernel, lp.vec, lp.nv, lp.modulated, lp.rows_per_wave, lp.grid, lp.waves) == (0, 8, 6, 0, 1, 2050, 8198)
+    assert ln(base, base, None, None, None, 333, 1, 768, 768, 0, ctypes.byref(lp)) == 0 and (lp.kernel, lp.vec, lp.nv, lp.grid) == (0, 4, 3, 84)
+    assert ln(base, base + 8, base, base, base, 333, 2, 3072, 3072, 1, ctypes.byref(lp)) == 0                   # fp8 codes: 8 bytes
+    assert (lp.kernel, lp.vec, lp.nv, lp.modulated, lp.rows_per_wave, lp.waves) == (0, 8, 6, 1, 1, 666)
+    assert ln(base, base, base, base, base, 333, 2, 768, 768, 1, ctypes.byref(lp)) == -4                        # fp8 / MX: D = 3072 only
+    assert ln(base, base, base, base, base, 333, 2, 3072, 2304, 3, ctypes.byref(lp)) == 0
+    assert ln(base, base, base, base, base, 333, 2, 3072, 2296, 3, ctypes.byref(lp)) == -1                      # a row of e2m3 codes: 2304 bytes
+    qp = _hip.QkNormRopePlan(-9)
+    qk = lambda q, k, cos, S, heads, text, stats, slots, plan: lib.bya_qknorm_rope_plan(q, k, base, base, base, base, cos, cos, 2, S, heads,
+                                                                                     3 * heads * 64, (S + 3) * 3 * heads * 64, text, stats, slots, plan)
+    assert qk(None, None, base, 37, 6, 5, None, 0, ctypes.byref(qp)) == -1 and qp.stats == -9
+    assert qk(base, base, base, 37, 6, 5, None, 0, None) == -1
+    assert qk(base, base, None, 37, 6, 5, None, 0, ctypes.byref(qp)) == -1                                       # rows to rotate, no tables
+    assert qk(base, base, base, 37, 6, 5, base, 65, ctypes.byref(qp)) == -1
+    assert qk(base + 8, base, base, 37, 6, 5, None, 0, ctypes.byref(qp)) == -2
+    assert qk(base, base, base, 37, 6, 5, None, 0, ctypes.byref(qp)) == 0
+    assert (qp.stats, qp.only, qp.grid, qp.slots, qp.pairs, qp.waves) == (0, 0, 28, 0, 888, 111)
+    assert qk(None, base, None, 37, 6, 37, base, 8, ctypes.byref(qp)) == 0
+    assert (qp.stats, qp.only, qp.grid, qp.slots, qp.pairs, qp.waves) == (1, 2, 14, 8, 444, 56)
     # the RCCL entry points validate their arguments before touching a communicator
     assert lib.bya_allgather_kv(None, None, None, None, 1, 1, None, None) == -1
     cnt = (ctypes.c_int64 * 2)(1, 1)
@@ -156,7 +188,8 @@ def test_struct_layout_matches_header():
     for cname, cls in (("bya_gemm_desc", _hip.GemmDesc), ("bya_attn_desc", _hip.AttnDesc), ("bya_gemm_plan", _hip.GemmPlan),
                        ("bya_attn_plan_info", _hip.AttnPlan), ("bya_attn_kv_mix_plan_info", _hip.AttnMixPlan),
                        ("bya_attn_tiny_plan_info", _hip.AttnTinyPlan), ("bya_rowgemm512_plan_info", _hip.RowGemmPlan),
-                       ("bya_router_group_attn_plan_info", _hip.GroupAttnPlan), ("bya_router_chain_plan_info", _hip.RouterChainPlan)):
+                       ("bya_router_group_attn_plan_info", _hip.GroupAttnPlan), ("bya_router_chain_plan_info", _hip.RouterChainPlan),
+                       ("bya_layernorm_plan_info", _hip.LayerNormPlan), ("bya_qknorm_rope_plan_info", _hip.QkNormRopePlan)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), src, flags=re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         fields = []

@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_fro
+from exact_norm import quant_rows_fp8_ref as quant_ref          # include/bya.h, bya_quantize_rows_fp8, on the CPU
 
 pytestmark = pytest.mark.gpu
 
@@ -16,19 +17,6 @@ pytestmark = pytest.mark.gpu
 def rnd(shape, seed, std=1.0):
     g = torch.Generator().manual_seed(seed)
     return (torch.randn(shape, generator=g) * std).to(torch.bfloat16)
-
-
-def quant_ref(x):
-    """include/bya.h, bya_quantize_rows_fp8, on the CPU."""
-    xf = x.float()
-    amax = xf.abs().amax(dim=-1, keepdim=True)
-    # tensor / tensor: the correctly rounded quotient (torch evaluates `scalar / tensor` as reciprocal * scalar, which is
-    # one ulp off for a third of the rows and flips 0.13 % of the bytes at exact ties)
-    c448 = torch.full_like(amax, 448.0)
-    inv = torch.where(amax > 0, c448 / amax, torch.zeros_like(amax))
-    scale = torch.where(amax > 0, amax / c448, torch.ones_like(amax))
-    q = (xf * inv).to(torch.float8_e4m3fn)
-    return q.view(torch.uint8), scale.squeeze(-1)
 
 
 def dequant(q_u8):
