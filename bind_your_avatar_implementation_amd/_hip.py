@@ -31,6 +31,13 @@ class QkNormDesc(_c.Structure):
                 ("text_rows", _i32), ("width", _i32), ("eps", _f32), ("k_scale", _f32)]
 
 
+class MxGemmCall(_c.Structure):
+    """bya_mx_gemm_call: the operands, epilogue and kernel of one bya_gemm_mx_call."""
+    _fields_ = [("A", _vp), ("a_scales", _vp), ("W", _vp), ("w_scales", _vp), ("bias", _vp), ("C", _vp),
+                ("res", _vp), ("gate0", _vp), ("gate1", _vp), ("q_scales", _vp), ("norm", _c.POINTER(QkNormDesc)),
+                ("a_fmt", _i32), ("w_fmt", _i32), ("out_fmt", _i32), ("kernel", _i32)]
+
+
 class AttnDesc(_c.Structure):
     _fields_ = [("head_dim", _i32), ("heads", _i32), ("nb1", _i32), ("nb2", _i32), ("Sq", _i32), ("Skv", _i32),
                 ("q_s1", _i64), ("q_s2", _i64), ("q_row", _i64),
@@ -124,6 +131,8 @@ SIGNATURES = {
                                      _vp],
     "bya_gemm_mx_qkv_norm_rope_on_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc),
                                           _i32, _c.POINTER(GemmPlan)],
+    "bya_gemm_mx_call": [_c.POINTER(MxGemmCall), _c.POINTER(GemmDesc), _vp],
+    "bya_gemm_mx_call_plan": [_c.POINTER(MxGemmCall), _c.POINTER(GemmDesc), _c.POINTER(GemmPlan)],
     "bya_linear_small_m": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "bya_timestep_features": [_vp, _vp, _i32, _i32, _i32, _f32, _vp],
     "bya_layernorm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,

@@ -627,12 +627,15 @@ int mx_args(const void* A, const void* a_scales, const void* W, const void* w_sc
 // has about a round of 256 CUs of them, or more.  kernel = 1 (2: without the tile count) asks for the persistent kernel of
 // gemm_mx_v4.hip instead, taken for e4m3 x e4m3 by the rule of fp8_path (gemm_fp8.hip): `a` = the whole launch (tile count),
 // `piece` = one row chunk of it (eligibility).  bya_gemm_mx_mixed and bya_gemm_mx_quant pass option mx_kernel,
-// bya_gemm_mx_qkv_norm_rope_on its ARGUMENT (no option is read there).  quant: the quantising epilogue (out_fmt: its element
-// format; e2m3 stays on the tiled kernel)
+// bya_gemm_mx_qkv_norm_rope_on and bya_gemm_mx_call their ARGUMENT (no option is read there).  w4_persistent: whether e2m1
+// weights under e4m3 activations may take the persistent kernel as well (its FMT_W = MX_E2M1 instances) -- bya_gemm_mx_call
+// alone says so: what the older entry points and their plan queries answer for e2m1 weights is pinned to the tiled kernel.
+// quant: the quantising epilogue (out_fmt: its element format; e2m3 stays on the tiled kernel)
 inline int mx_path(const GemmArgs& a, int batch, const GemmArgs& piece, int32_t a_fmt, int32_t w_fmt, int kernel,
-                   bool quant = false, int32_t out_fmt = MX_E4M3) {
+                   bool w4_persistent, bool quant = false, int32_t out_fmt = MX_E4M3) {
     const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
-    if (kernel != 0 && a_fmt == MX_E4M3 && w_fmt == MX_E4M3 && out_fmt == MX_E4M3 && (kernel == 2 || tiles256 >= 200) &&
+    const bool w_ok = w_fmt == MX_E4M3 || (w4_persistent && w_fmt == MX_E2M1);
+    if (kernel != 0 && a_fmt == MX_E4M3 && w_ok && out_fmt == MX_E4M3 && (kernel == 2 || tiles256 >= 200) &&
         bya_gemm256p_mx_eligible(&piece, quant))
         return BYA_GEMM_PATH_P256;
     return a_fmt == MX_E2M3 && BYA_MX_E2M3_BIG_TILE && tiles256 >= 200 ? BYA_GEMM_PATH_T256X256 : BYA_GEMM_PATH_T128X128;
@@ -643,7 +646,7 @@ constexpr int MX_P256_GROUP_M = 4;         // row-tiles per group of the persist
 // element format (qs: its scale bytes)
 int mx_launch(int path, const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int epi, int32_t a_fmt,
               int32_t w_fmt, int batch, hipStream_t s) {
-    if (path == BYA_GEMM_PATH_P256) return bya_launch_gemm256p_mx(&a, sa, sw, qs, epi, batch, MX_P256_GROUP_M, s);
+    if (path == BYA_GEMM_PATH_P256) return bya_launch_gemm256p_mx(&a, sa, sw, qs, epi, w_fmt, batch, MX_P256_GROUP_M, s);
     return mx_for_instance(a_fmt, w_fmt, path == BYA_GEMM_PATH_T256X256, [&](auto inst) {
         using I = decltype(inst);
         if (epi == MX_EPI_BF16) return launch_mx<I, MX_EPI_BF16>(a, sa, sw, qs, batch, s);
@@ -668,7 +671,7 @@ extern "C" int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void
     const uint8_t* sa = (const uint8_t*)a_scales;
     const long long ks = d->K / 32;
     return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
-        const int path = mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL));
+        const int path = mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false);
         return mx_launch(path, piece, sa + row0 * ks, (const uint8_t*)w_scales, nullptr, MX_EPI_BF16, a_fmt, w_fmt, batch, stream);
     });
 }
@@ -683,7 +686,7 @@ extern "C" int bya_gemm_mx_mixed_plan(const void* A, const void* a_scales, const
     if (rc != BYA_OK) return rc;
     const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
     if (!chunks) return BYA_ERR_UNSUPPORTED;
-    return mx_plan(p, mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL)), chunks);
+    return mx_plan(p, mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false), chunks);
 }
 
 namespace {
@@ -715,7 +718,7 @@ extern "C" int bya_gemm_mx_quant(const void* A, const void* a_scales, const void
     GemmArgs a;
     const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
     if (rc != BYA_OK) return rc;
-    const int path = mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), true, out_fmt);
+    const int path = mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, true, out_fmt);
     return mx_launch(path, a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, (uint8_t*)q_scales, out_fmt, a_fmt, w_fmt,
                      d->batch, stream);
 }
@@ -727,7 +730,7 @@ extern "C" int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const
     GemmArgs a;
     const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
     if (rc != BYA_OK) return rc;
-    return mx_plan(p, mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), true, out_fmt), 1);
+    return mx_plan(p, mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, true, out_fmt), 1);
 }
 
 namespace {
@@ -772,7 +775,7 @@ extern "C" int bya_gemm_mx_qkv_norm_rope_on(const void* A, const void* a_scales,
     GemmArgs a;
     const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
     if (rc != BYA_OK) return rc;
-    return mx_launch(mx_path(a, d->batch, a, fmt, w_fmt, kernel), a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, nullptr,
+    return mx_launch(mx_path(a, d->batch, a, fmt, w_fmt, kernel, false), a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, nullptr,
                      MX_EPI_QKN, fmt, w_fmt, d->batch, stream);
 }
 
@@ -784,7 +787,7 @@ extern "C" int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_sc
     GemmArgs a;
     const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
     if (rc != BYA_OK) return rc;
-    return mx_plan(p, mx_path(a, d->batch, a, fmt, w_fmt, kernel), 1);
+    return mx_plan(p, mx_path(a, d->batch, a, fmt, w_fmt, kernel, false), 1);
 }
 
 // ... on the tiled kernel (kernel = 0)
@@ -798,6 +801,63 @@ extern "C" int bya_gemm_mx_qkv_norm_rope_plan(const void* A, const void* a_scale
                                               const void* bias, const void* C, int32_t fmt, int32_t w_fmt,
                                               const bya_gemm_desc* d, const bya_qknorm_desc* n, bya_gemm_plan* p) {
     return bya_gemm_mx_qkv_norm_rope_on_plan(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, 0, p);
+}
+
+namespace {
+// bya_gemm_mx_call (plan == nullptr) and bya_gemm_mx_call_plan: one body, so the query answers what the launch does.  The
+// epilogue's own argument function runs first and refuses what its old entry point refuses, with its code; then mx_path with
+// the call's kernel and e2m1 weights admitted to the persistent kernel.
+int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, hipStream_t stream, bya_gemm_plan* plan) {
+    if (!c || !d) return BYA_ERR_SHAPE;
+    if (c->kernel < 0 || c->kernel > 2) return BYA_ERR_SHAPE;
+    if (c->norm && c->q_scales) return BYA_ERR_SHAPE;
+    if ((c->norm || c->q_scales) && (c->res || c->gate0 || c->gate1)) return BYA_ERR_SHAPE;
+    const uint8_t* const sa = (const uint8_t*)c->a_scales;
+    const uint8_t* const sw = (const uint8_t*)c->w_scales;
+    GemmArgs a;
+    if (c->norm) {
+        const int rc = mx_qkn_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, d, c->norm, c->a_fmt, c->w_fmt, &a);
+        if (rc != BYA_OK) return rc;
+        const int path = mx_path(a, d->batch, a, c->a_fmt, c->w_fmt, c->kernel, true);
+        if (plan) return mx_plan(plan, path, 1);
+        return mx_launch(path, a, sa, sw, nullptr, MX_EPI_QKN, c->a_fmt, c->w_fmt, d->batch, stream);
+    }
+    if (c->q_scales) {
+        const int rc = mx_quant_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, c->q_scales, d, c->a_fmt, c->w_fmt,
+                                     c->out_fmt, &a);
+        if (rc != BYA_OK) return rc;
+        const int path = mx_path(a, d->batch, a, c->a_fmt, c->w_fmt, c->kernel, true, true, c->out_fmt);
+        if (plan) return mx_plan(plan, path, 1);
+        return mx_launch(path, a, sa, sw, (uint8_t*)c->q_scales, c->out_fmt, c->a_fmt, c->w_fmt, d->batch, stream);
+    }
+    const int rc = mx_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, c->res, c->gate0, c->gate1, d, c->a_fmt,
+                           c->w_fmt, &a);
+    if (rc != BYA_OK) return rc;
+    if (plan) {
+        GemmArgs piece;
+        int nb = 0;
+        const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
+        if (!chunks) return BYA_ERR_UNSUPPORTED;
+        return mx_plan(plan, mx_path(a, d->batch, piece, c->a_fmt, c->w_fmt, c->kernel, true), chunks);
+    }
+    const long long ks = d->K / 32;
+    return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
+        const int path = mx_path(a, d->batch, piece, c->a_fmt, c->w_fmt, c->kernel, true);
+        return mx_launch(path, piece, sa + row0 * ks, sw, nullptr, MX_EPI_BF16, c->a_fmt, c->w_fmt, batch, stream);
+    });
+}
+}  // namespace
+
+// Any MX GEMM of this file with its kernel named by an ARGUMENT (no option is read): the epilogue is chosen by which of
+// `norm` / `q_scales` is set, kernel = 0 is the old entry point of that epilogue under option mx_kernel = 0, and kernel = 1 / 2
+// admit e4m3 x e4m3 AND e4m3 x e2m1 launches to the persistent 256 x 256 kernel (gemm_mx_v4.hip), the same bits.
+extern "C" int bya_gemm_mx_call(const bya_mx_gemm_call* call, const bya_gemm_desc* desc, hipStream_t stream) {
+    return mx_call(call, desc, stream, nullptr);
+}
+
+extern "C" int bya_gemm_mx_call_plan(const bya_mx_gemm_call* call, const bya_gemm_desc* desc, bya_gemm_plan* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    return mx_call(call, desc, nullptr, plan);
 }
 
 // Both operands in one format: e4m3 or e2m3 (e2m1 activations are not offered)

@@ -27,7 +27,14 @@
 // (The ring is not free either: the next tile's first two K-tiles are in it.)
 // The q/k-norm epilogue (bya_gemm_mx_qkv_norm_rope_on) needs none either: a head row is the four lanes fq = 0..3 too
 // (epilogue_mx_wide8_qkn, below).
-// K >= 512; e2m1 weights and e2m3 operands (64- and 96-byte LDS rows) stay on gemm_mx.hip.
+//
+// FMT_W = MX_E2M1 (e2m1 weights under the same e4m3 activations; bya_gemm_mx_call): the W side alone changes.  A W row of a
+// K-tile is 64 bytes -- the 64-byte-row image of gemm_persistent.h at TILE_A of the stage, 16 KiB of its 32 -- so a wave moves
+// its 64 W slot rows as FOUR pieces (14 pieces per K-tile: the second generated body below, and vmcnt(14) where the e4m3 form
+// waits on 18), a W fragment is ONE ds_read_b128 (wh[] is gone: 32 VGPRs), and the MFMA takes it as a four-register operand
+// under cbsz:4 -- the instruction sequence of gemm_mx_body<MX_E4M3, MX_E2M1>, so the bits are that kernel's.  Slot map
+// (w_slot_col), scales, A side, tile walk, accumulator layout and the three epilogues are shared with the e4m3 form.
+// K >= 512; e2m3 operands (96-byte LDS rows) stay on gemm_mx.hip.
 // Compiled WITHOUT -amdgpu-mfma-vgpr-form, like gemm_fp8_v4.hip.
 #include "gemm_wide_epilogue.h"
 #include "mx_common.h"
@@ -220,14 +227,18 @@ __device__ __forceinline__ void epilogue_mx_wide8_qkn(const GemmArgs& p, int z, 
 }
 
 // QOUT = MX_EPI_BF16: the bf16 epilogue; MX_EPI_QKN: the q/k-norm one (p.qkn_*); MX_E4M3: the quantising one (C = codes with ldc / c_bs
-// in bytes, qs = its scale bytes)
-template <int QOUT>
+// in bytes, qs = its scale bytes).  FMT_W: the weights' element format, MX_E4M3 or MX_E2M1 (the top of the file)
+template <int QOUT, int FMT_W>
 __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const uint8_t* __restrict__ sa,
                                                             const uint8_t* __restrict__ sw, int tiles_m, int tiles_n, int batch,
                                                             int GM, uint8_t* __restrict__ qs) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int BM = 256, BN = 256, STAGE = (BM + BN) * BK8, TILE_A = BM * BK8;
     static_assert(STAGE == 65536 && SC_BASE == 2 * STAGE, "stage flip uses one address bit; the scales sit behind the codes");
+    static_assert(FMT_W == MX_E4M3 || FMT_W == MX_E2M1, "weights: e4m3 or e2m1");
+    constexpr bool W4 = FMT_W == MX_E2M1;
+    constexpr int BKW = W4 ? 64 : BK8;                         // bytes of a W row per K-tile
+    constexpr int NPW = W4 ? 4 : 8;                            // W code pieces of a wave per K-tile
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nk = p.K / BK8, ks = p.K / 32;
@@ -244,46 +255,61 @@ __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const u
     const int a_row = wm * 128 + fr, w_row = wn * 128 + fr;
     const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
     uint32_t cAl = frag_addr(lds0, a_row, fq), cAh = frag_addr(lds0, a_row, 4 + fq);
-    uint32_t cWl = frag_addr(lds0 + TILE_A, w_row, fq);
-    uint32_t cWh = frag_addr(lds0 + TILE_A, w_row, 4 + fq);
+    uint32_t cWl = W4 ? frag_addr64(lds0 + TILE_A, w_row, fq) : frag_addr(lds0 + TILE_A, w_row, fq);
+    uint32_t cWh = frag_addr(lds0 + TILE_A, w_row, 4 + fq);                     // (e2m1: unused)
     uint32_t fill = __builtin_amdgcn_readfirstlane(lds0 + wave * 64 * 128);     // this wave's first A piece, current stage
     uint32_t sfill = __builtin_amdgcn_readfirstlane(lds0 + SC_BASE + wave * 256);   // ... its A scale piece
     // the lane's scale byte: byte fq of the dword of row a_row (A) / slot row w_row (W), blocks 16 rows = 64 bytes apart
     uint32_t cSa = lds0 + SC_BASE + 4 * a_row + fq, cSw = lds0 + SC_BASE + SC_W + 4 * w_row + fq;
 
     // staging (map and source-side swizzle: gemm_persistent.h): wave w moves LDS slot rows [64w, 64w + 64) of the A tile and
-    // of the W tile, 8 one-KiB pieces each, and their scale dwords, lane l = slot row 64w + l
-    uint32_t voA[8], voW[8];
+    // of the W tile, 8 one-KiB pieces each (e2m1 W: 4, sixteen 64-byte rows each, which start 4 KiB per wave apart: w_back),
+    // and their scale dwords, lane l = slot row 64w + l
+    uint32_t voA[8], voW[8];                                   // (e2m1: voW[0..3])
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int rl = wave * 64 + q * 8 + (lane >> 3);
         voA[q] = stage_off(lane, rl, rl, (uint32_t)p.lda);
-        voW[q] = stage_off(lane, rl, w_slot_col(rl), (uint32_t)p.ldw);
+        if constexpr (!W4) voW[q] = stage_off(lane, rl, w_slot_col(rl), (uint32_t)p.ldw);
     }
+    if constexpr (W4) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int rl = wave * 64 + q * 16 + (lane >> 2);
+            voW[q] = stage_off64(lane, rl, w_slot_col(rl), (uint32_t)p.ldw);
+        }
+    }
+    const uint32_t w_back = W4 ? (uint32_t)wave * 4096u : 0u;     // `fill` steps 8 KiB per wave, the e2m1 W image 4 KiB
     const uint32_t voSa = (uint32_t)(wave * 64 + lane) * (uint32_t)ks;
     const uint32_t voSw = (uint32_t)w_slot_col(wave * 64 + lane) * (uint32_t)ks;
     const uint8_t* const A8 = reinterpret_cast<const uint8_t*>(p.A);
     const uint8_t* const W8 = reinterpret_cast<const uint8_t*>(p.W);
-    i32x4 rsA = tile_rsrc_a(p, A8, cur), rsW = tile_rsrc_w(p, W8, cur);
+    const int kw_bytes = W4 ? p.K / 2 : p.K;                        // bytes of a W row that the GEMM reads
+    i32x4 rsA = tile_rsrc_a(p, A8, cur), rsW = tile_rsrc_w(p, W8, cur, kw_bytes);
     i32x4 rsSa = tile_rsrc_sa(p, sa, ks, cur), rsSw = tile_rsrc_sw(p, sw, ks, cur);
 
 #define DMA_A(Q, BASE, VO, RS, SOFF) DMA_PIECE(Q, BASE, VO, RS, SOFF)
-#define DMA_W(Q, BASE, VO, RS, SOFF) DMA_PIECE(Q, (BASE) + TILE_A, VO, RS, SOFF)
+#define DMA_W(Q, BASE, VO, RS, SOFF) DMA_PIECE(Q, (BASE) + TILE_A - w_back, VO, RS, SOFF)
+#define ALLW(M, ...) do { if constexpr (W4) { ALL4(M, __VA_ARGS__); } else { ALL8(M, __VA_ARGS__); } } while (0)
 #define DMA_SA(BASE, RS, SOFF) dma_scale_piece<0>(BASE, voSa, RS, SOFF)
 #define DMA_SW(BASE, RS, SOFF) dma_scale_piece<SC_W>(BASE, voSw, RS, SOFF)
     // ---- prologue of the FIRST tile only: K-tiles 0 and 1
     ALL8(DMA_A, fill, voA, rsA, 0u);
-    ALL8(DMA_W, fill, voW, rsW, 0u);
+    ALLW(DMA_W, fill, voW, rsW, 0u);
     DMA_SA(sfill, rsSa, 0u);
     DMA_SW(sfill, rsSw, 0u);
     ALL8(DMA_A, fill ^ STAGE, voA, rsA, (uint32_t)BK8);
-    ALL8(DMA_W, fill ^ STAGE, voW, rsW, (uint32_t)BK8);
+    ALLW(DMA_W, fill ^ STAGE, voW, rsW, (uint32_t)BKW);
     DMA_SA(sfill ^ SC_STAGE, rsSa, 4u);
     DMA_SW(sfill ^ SC_STAGE, rsSw, 4u);
-    asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
+    // K-tile 0 has landed once all but the pieces of K-tile 1 have: 8 + NPW + 2 of them
+#define WAIT_KTILE(TAIL) do { if constexpr (W4) asm volatile("s_waitcnt vmcnt(14)" TAIL ::: "memory"); else asm volatile("s_waitcnt vmcnt(18)" TAIL ::: "memory"); } while (0)
+    static_assert(8 + NPW + 2 == (W4 ? 14 : 18), "the counted waits follow the pieces of a K-tile");
+    WAIT_KTILE("");
 
     f32x4 acc[8][8];
-    i32x4 al[8], ah[8], wl[8], wh[8];            // low / high 16 bytes of the A (row block j) and W (column block i) fragments
+    // low / high 16 bytes of the A (row block j) and W (column block i) fragments; an e2m1 W fragment is wl alone
+    i32x4 al[8], ah[8], wl[8], wh[8];
     int xa[8], xw[8];                            // their scale bytes for this lane's K-block fq, in byte 0
 
     for (;;) {
@@ -291,26 +317,38 @@ __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const u
         // epilogue); make that true for everybody, then fetch its A fragments and W(0..3), each with its scale
         asm volatile("s_barrier" ::: "memory");
 #define RAF(J, LO, HI, SC) do { ds_read128<(J) * 2048>(al[J], LO); ds_read128<(J) * 2048>(ah[J], HI); ds_read_byte<(J) * 64>(xa[J], SC); } while (0)
-#define RWF(I, LO, HI, SC) do { ds_read128<(I) * 2048>(wl[I], LO); ds_read128<(I) * 2048>(wh[I], HI); ds_read_byte<(I) * 64>(xw[I], SC); } while (0)
+#define RWF(I, LO, HI, SC) do {                                                                                          \
+            if constexpr (W4) { ds_read128<(I) * 1024>(wl[I], LO); }                                                       \
+            else { ds_read128<(I) * 2048>(wl[I], LO); ds_read128<(I) * 2048>(wh[I], HI); }                                 \
+            ds_read_byte<(I) * 64>(xw[I], SC);                                                                             \
+        } while (0)
         RAF(0, cAl, cAh, cSa); RAF(1, cAl, cAh, cSa); RAF(2, cAl, cAh, cSa); RAF(3, cAl, cAh, cSa);
         RAF(4, cAl, cAh, cSa); RAF(5, cAl, cAh, cSa); RAF(6, cAl, cAh, cSa); RAF(7, cAl, cAh, cSa);
         RWF(0, cWl, cWh, cSw); RWF(1, cWl, cWh, cSw); RWF(2, cWl, cWh, cSw); RWF(3, cWl, cWh, cSw);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
         const PersistentTile nxt = walk.coord(seq + 1);
-        const i32x4 rsAn = tile_rsrc_a(p, A8, nxt), rsWn = tile_rsrc_w(p, W8, nxt);
+        const i32x4 rsAn = tile_rsrc_a(p, A8, nxt), rsWn = tile_rsrc_w(p, W8, nxt, kw_bytes);
         const i32x4 rsSan = tile_rsrc_sa(p, sa, ks, nxt), rsSwn = tile_rsrc_sw(p, sw, ks, nxt);
 
         // One K-tile, variant V (gemm_fp8_v4.hip); t = its index inside the output tile.
         auto ktile = [&](int t, auto v_c) {
             constexpr char V = decltype(v_c)::value;
             const uint32_t soff = (uint32_t)((t + 2) * BK8), ssoff = (uint32_t)((t + 2) * 4);
+            const uint32_t wsoff = (uint32_t)((t + 2) * BKW);
             const uint32_t nAl = cAl ^ STAGE, nAh = cAh ^ STAGE, nWl = cWl ^ STAGE, nWh = cWh ^ STAGE;
             const uint32_t nSa = cSa ^ SC_STAGE, nSw = cSw ^ SC_STAGE;
 #define OPW(I) __builtin_shufflevector(wl[I], wh[I], 0, 1, 2, 3, 4, 5, 6, 7)
 #define OPA(J) __builtin_shufflevector(al[J], ah[J], 0, 1, 2, 3, 4, 5, 6, 7)
+            // e2m1 W: the four registers of the lane's block under cbsz:4 (activations: blgp:0, the default)
 #define MFX(I, J) do {                                                                                                   \
-                if constexpr (V == 'A')                                                                                    \
+                if constexpr (W4 && V == 'A')                                                                              \
+                    asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, 0, %3, %4 op_sel_hi:[0,0,0] cbsz:4"        \
+                                 : "=a"(acc[I][J]) : "v"(wl[I]), "v"(OPA(J)), "v"(xw[I]), "v"(xa[J]));                     \
+                else if constexpr (W4)                                                                                     \
+                    asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:4"       \
+                                 : "+a"(acc[I][J]) : "v"(wl[I]), "v"(OPA(J)), "v"(xw[I]), "v"(xa[J]));                     \
+                else if constexpr (V == 'A')                                                                                    \
                     asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, 0, %3, %4 op_sel_hi:[0,0,0]"               \
                                  : "=a"(acc[I][J]) : "v"(OPW(I)), "v"(OPA(J)), "v"(xw[I]), "v"(xa[J]));                    \
                 else                                                                                                       \
@@ -320,8 +358,8 @@ __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const u
             // one LDS-DMA piece: K-tile t + 2 of this tile, or the next tile's first two
 #define PIECE(Q, IS_W) do {                                                                                              \
                 if constexpr (V == 'C') { if (IS_W) DMA_W(Q, fill, voW, rsWn, 0u); else DMA_A(Q, fill, voA, rsAn, 0u); }  \
-                else if constexpr (V == 'D') { if (IS_W) DMA_W(Q, fill, voW, rsWn, (uint32_t)BK8); else DMA_A(Q, fill, voA, rsAn, (uint32_t)BK8); } \
-                else { if (IS_W) DMA_W(Q, fill, voW, rsW, soff); else DMA_A(Q, fill, voA, rsA, soff); }                   \
+                else if constexpr (V == 'D') { if (IS_W) DMA_W(Q, fill, voW, rsWn, (uint32_t)BKW); else DMA_A(Q, fill, voA, rsAn, (uint32_t)BK8); } \
+                else { if (IS_W) DMA_W(Q, fill, voW, rsW, wsoff); else DMA_A(Q, fill, voA, rsA, soff); }                  \
             } while (0)
 #define SPIECE(IS_W) do {                                                                                                \
                 if constexpr (V == 'C') { if (IS_W) DMA_SW(sfill, rsSwn, 0u); else DMA_SA(sfill, rsSan, 0u); }            \
@@ -334,6 +372,7 @@ __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const u
 #define B2(N) do { if constexpr (V != 'D') asm volatile("s_waitcnt vmcnt(" #N ")\n\ts_barrier" ::: "memory"); } while (0)
 #define REREAD_W() do { if constexpr (V != 'D') { RWF(0, nWl, nWh, nSw); RWF(1, nWl, nWh, nSw); RWF(2, nWl, nWh, nSw); RWF(3, nWl, nWh, nSw); } } while (0)
 #define REREAD_A(J) do { if constexpr (V != 'D') RAF(J, nAl, nAh, nSa); } while (0)
+            if constexpr (!W4) {
             // GENERATED-BEGIN (tools/gen_gemm_mx_schedule.py)
             RWF(4, cWl, cWh, cSw);
             MFX(0, 0); RWF(5, cWl, cWh, cSw);
@@ -401,6 +440,75 @@ __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const u
             MFX(6, 7); SPIECE(true);
             MFX(7, 7); REREAD_A(7);
             // GENERATED-END
+            } else {
+            // GENERATED-W4-BEGIN (tools/gen_gemm_mx_schedule.py: 8 A, 4 W and 2 scale pieces)
+            RWF(4, cWl, cWh, cSw);
+            MFX(0, 0); RWF(5, cWl, cWh, cSw);
+            MFX(1, 0); RWF(6, cWl, cWh, cSw);
+            MFX(2, 0); RWF(7, cWl, cWh, cSw);
+            MFX(3, 0);
+            MFX(0, 1);
+            MFX(1, 1);
+            MFX(2, 1);
+            MFX(3, 1);
+            MFX(0, 2);
+            MFX(1, 2); B1();
+            MFX(2, 2); PIECE(0, false);
+            MFX(3, 2);
+            MFX(0, 3);
+            MFX(1, 3); PIECE(1, false);
+            MFX(2, 3);
+            MFX(3, 3);
+            MFX(0, 4); PIECE(2, false);
+            MFX(1, 4);
+            MFX(2, 4);
+            MFX(3, 4); PIECE(3, false);
+            MFX(0, 5);
+            MFX(1, 5);
+            MFX(2, 5); PIECE(4, false);
+            MFX(3, 5);
+            MFX(0, 6);
+            MFX(1, 6); PIECE(5, false);
+            MFX(2, 6);
+            MFX(3, 6);
+            MFX(0, 7); PIECE(6, false);
+            MFX(1, 7);
+            MFX(2, 7); B2(7);
+            MFX(3, 7); REREAD_W();
+            MFX(4, 0); PIECE(7, false);
+            MFX(5, 0);
+            MFX(6, 0);
+            MFX(7, 0); PIECE(0, true); REREAD_A(0);
+            MFX(4, 1);
+            MFX(5, 1);
+            MFX(6, 1);
+            MFX(7, 1); REREAD_A(1);
+            MFX(4, 2);
+            MFX(5, 2); PIECE(1, true);
+            MFX(6, 2);
+            MFX(7, 2); REREAD_A(2);
+            MFX(4, 3);
+            MFX(5, 3);
+            MFX(6, 3);
+            MFX(7, 3); PIECE(2, true); REREAD_A(3);
+            MFX(4, 4);
+            MFX(5, 4);
+            MFX(6, 4);
+            MFX(7, 4); REREAD_A(4);
+            MFX(4, 5);
+            MFX(5, 5); PIECE(3, true);
+            MFX(6, 5);
+            MFX(7, 5); REREAD_A(5);
+            MFX(4, 6);
+            MFX(5, 6);
+            MFX(6, 6);
+            MFX(7, 6); SPIECE(false); REREAD_A(6);
+            MFX(4, 7);
+            MFX(5, 7);
+            MFX(6, 7); SPIECE(true);
+            MFX(7, 7); REREAD_A(7);
+            // GENERATED-W4-END
+            }
 #undef B1
 #undef B2
 #undef REREAD_W
@@ -410,7 +518,8 @@ __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const u
             if constexpr (V != 'D') asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
             cAl ^= STAGE; cAh ^= STAGE; cWl ^= STAGE; cWh ^= STAGE; fill ^= STAGE;
             cSa ^= SC_STAGE; cSw ^= SC_STAGE; sfill ^= SC_STAGE;
-            KEEP8(al); KEEP8(ah); KEEP8(wl); KEEP8(wh); KEEP8(xa); KEEP8(xw);
+            KEEP8(al); KEEP8(ah); KEEP8(wl); KEEP8(xa); KEEP8(xw);
+            if constexpr (!W4) KEEP8(wh);
 #undef SPIECE
 #undef PIECE
 #undef MFX
@@ -423,9 +532,11 @@ __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const u
         ktile(nk - 1, IntTag<'D'>{});
 #undef RAF
 #undef RWF
-        // K-tile 0 of the next output tile (18 pieces, requested during variant C) has landed once all but the 18 younger
-        // pieces of its K-tile 1 have; the MFMAs are inline asm, so pad their last results before the epilogue reads them
-        asm volatile("s_waitcnt vmcnt(18)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+        // K-tile 0 of the next output tile (18 pieces, e2m1 W: 14, requested during variant C) has landed once all but the as
+        // many younger pieces of its K-tile 1 have; the MFMAs are inline asm, so pad their last results before the epilogue
+        // reads them
+        WAIT_KTILE("\n\ts_nop 15\n\ts_nop 15");
+#undef WAIT_KTILE
 
         if constexpr (QOUT == MX_EPI_QKN) {
             epilogue_mx_wide8_qkn<2>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc);
@@ -454,7 +565,8 @@ __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const u
 
 // Is the persistent MX kernel applicable?  The rules of bya_gemm256p_fp8_eligible (16-byte epilogue accesses aligned, at least
 // four K-tiles, 16-byte operand rows); quant: C = the codes, ldc / c_bs in bytes (bya_gemm_mx_quant has checked their
-// 16-byte alignment and N % 128 == 0)
+// 16-byte alignment and N % 128 == 0).  lda / ldw are BYTES of a code row, so the rules hold for e2m1 weights (ldw >= K / 2) as
+// they stand
 bool bya_gemm256p_mx_eligible(const void* args, bool quant) {
     const GemmArgs& a = *static_cast<const GemmArgs*>(args);
     if (!(a.K % BK8 == 0 && a.K >= 4 * BK8 && a.N % 8 == 0 && a.lda % 16 == 0 && a.ldw % 16 == 0 &&
@@ -467,16 +579,22 @@ bool bya_gemm256p_mx_eligible(const void* args, bool quant) {
 }
 
 // sa / sw: the e8m0 scale bytes [batch * M, K / 32] / [N, K / 32].  epi: MX_EPI_BF16, MX_EPI_QKN = the q/k-norm epilogue
-// (GemmArgs::qkn_*; the caller has checked mx_qkn_args' conditions), MX_E4M3 = the quantising one (qs: its scale bytes)
-int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int epi, int batch, int gm,
-                           hipStream_t s) {
+// (GemmArgs::qkn_*; the caller has checked mx_qkn_args' conditions), MX_E4M3 = the quantising one (qs: its scale bytes);
+// w_fmt: MX_E4M3 or MX_E2M1, the weights' format (the activations are e4m3)
+int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int epi, int w_fmt, int batch,
+                           int gm, hipStream_t s) {
     const GemmArgs& a = *static_cast<const GemmArgs*>(args);
     const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
     const size_t lds = SC_BASE + 2 * SC_STAGE;
     const int grid = persistent_grid((long long)tiles_m * tiles_n * batch);
+    if (w_fmt != MX_E4M3 && w_fmt != MX_E2M1) return BYA_ERR_UNSUPPORTED;
     auto go = [&](auto epi_tag) {
-        return launch_persistent<gemm256p_mx_kernel<decltype(epi_tag)::value>>(grid, 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch,
-                                                                               gm < 1 ? 1 : gm, qs);
+        constexpr int EPI = decltype(epi_tag)::value;
+        if (w_fmt == MX_E2M1)
+            return launch_persistent<gemm256p_mx_kernel<EPI, MX_E2M1>>(grid, 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch,
+                                                                       gm < 1 ? 1 : gm, qs);
+        return launch_persistent<gemm256p_mx_kernel<EPI, MX_E4M3>>(grid, 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch,
+                                                                   gm < 1 ? 1 : gm, qs);
     };
     return epi == MX_EPI_QKN ? go(IntTag<MX_EPI_QKN>{}) : epi == MX_E4M3 ? go(IntTag<MX_E4M3>{}) : go(IntTag<MX_EPI_BF16>{});
 }

@@ -24,6 +24,19 @@
 //  * Fragments: the lane (fr = lane & 15, fq = lane >> 4) reads chunk fq (k-step 0) and chunk 4 + fq (k-step 1) of row
 //    row0 + fr; row blocks are 16 rows = 2048 bytes apart (the ds_read's immediate offset).  The e4m3 kernel's one
 //    k-step takes both chunks as the low and high half of its 32 operand bytes.
+//
+// THE 64-BYTE-ROW IMAGE (e2m1 weights of gemm_mx_v4.hip: 128 four-bit values of one matrix row per K-tile)
+//
+//  * A K-tile of the operand is `rows` LDS rows of 64 BYTES back to back: four 16-byte chunks = the four 32-element MX blocks
+//    of the row.  Chunk c of row `row` sits at chunk position  c ^ (((row >> 2) & 1) << 1)  -- the image of a 16-row block is
+//    the tiled kernel's (stage_mx<MX_E2M1> / lds_frag_mx<MX_E2M1>, gemm_mx.hip): unswizzled, the rows of a ds_read_b128 lane
+//    group would meet two to a 16-byte slot of the 256-byte bank row; with the XOR each group covers the 16 slots once.
+//  * Source-side swizzle again: a piece writes 1 KiB linearly = SIXTEEN rows, lane l's 16 bytes to row l >> 2, chunk position
+//    l & 3, so the lane loads chunk  (l & 3) ^ (((row >> 2) & 1) << 1)  (stage_off64).  K-tile t is bytes [64 t, 64 t + 64) of
+//    a source row; the descriptor's extent ends K / 2 bytes into the last row (tile_rsrc_w's row_bytes).
+//  * Rows are staged through the SAME slot permutation (w_slot_col), so the accumulator layout and the epilogues do not change.
+//  * Fragments: the lane (fr, fq) reads chunk fq -- block fq, low nibble first, the four-register e2m1 operand of the
+//    block-scaled MFMA -- of row row0 + fr: ONE ds_read_b128; row blocks are 16 rows = 1024 bytes apart (frag_addr64).
 #pragma once
 #include "gemm_common.h"
 
@@ -90,6 +103,11 @@ __device__ __forceinline__ uint32_t stage_off(int lane, int rl, int src_row, uin
     return (uint32_t)src_row * pitch + ((lane & 7) ^ ((rl >> 1) & 7)) * 16;
 }
 
+// ... and of the 64-byte-row image: `lane` moves 16 bytes to LDS row rl (= piece row lane >> 2), chunk position lane & 3
+__device__ __forceinline__ uint32_t stage_off64(int lane, int rl, int src_row, uint32_t pitch) {
+    return (uint32_t)src_row * pitch + ((lane & 3) ^ (((rl >> 2) & 1) << 1)) * 16;
+}
+
 // ---- buffer descriptors and LDS-DMA --------------------------------------------------------------------------------------
 __device__ __forceinline__ i32x4 raw_rsrc(const void* base, uint32_t bytes) {
     const unsigned long long b = (unsigned long long)base;
@@ -116,9 +134,10 @@ __device__ __forceinline__ i32x4 tile_rsrc_a(const GemmArgs& p, const T* A, cons
     const long long left = ((long long)(p.M - 1 - c.m0) * p.lda + p.K) * (long long)sizeof(T);
     return raw_rsrc(A + (long long)c.z * p.a_bs + (long long)c.m0 * p.lda, c.valid && left > 0 ? (uint32_t)left : 0u);
 }
+// row_elems: elements of T that the GEMM reads of a W row where that is not K (e2m1 codes: K / 2 bytes); 0 = K
 template <typename T>
-__device__ __forceinline__ i32x4 tile_rsrc_w(const GemmArgs& p, const T* W, const PersistentTile& c) {
-    const long long left = ((long long)(p.N - 1 - c.n0) * p.ldw + p.K) * (long long)sizeof(T);
+__device__ __forceinline__ i32x4 tile_rsrc_w(const GemmArgs& p, const T* W, const PersistentTile& c, int row_elems = 0) {
+    const long long left = ((long long)(p.N - 1 - c.n0) * p.ldw + (row_elems ? row_elems : p.K)) * (long long)sizeof(T);
     return raw_rsrc(W + (long long)c.n0 * p.ldw, c.valid && left > 0 ? (uint32_t)left : 0u);
 }
 
@@ -126,6 +145,11 @@ __device__ __forceinline__ i32x4 tile_rsrc_w(const GemmArgs& p, const T* W, cons
 // and chunk 4 + fq (k-step 1) of row row0 + fr
 __device__ __forceinline__ uint32_t frag_addr(uint32_t tile, int row, int chunk) {
     return tile + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
+}
+
+// ... of the 64-byte-row image: the lane's one fragment is chunk fq of row row0 + fr
+__device__ __forceinline__ uint32_t frag_addr64(uint32_t tile, int row, int chunk) {
+    return tile + row * 64 + ((chunk ^ (((row >> 2) & 1) << 1)) << 4);
 }
 
 // piece Q of a wave's share (1 KiB apart in LDS), per-lane offsets VO[Q]

@@ -41,6 +41,15 @@ FP8_LINEARS = ("qkv", "out", "ff1", "ff2", "pq", "aq")
 FP8_DEFAULT = ("qkv", "out", "ff1", "ff2")
 
 
+def mx_call_kernel(fmt, w_fmt, persistent_gemm):
+    """The ``kernel`` argument of the engine's ops.gemm_mx_call launches for enable_mx_weights(fmt, weight_format=w_fmt,
+    persistent_gemm=...): 1 (True) or 2 ("always") for "mxfp4" weights under "mxfp8" activations; 0 = the engine issues the
+    launches it always issued (same-format "mxfp8" follows option mx_kernel, "mxfp6" activations ignore the switch)."""
+    if not persistent_gemm or (fmt, w_fmt) != ("mxfp8", "mxfp4"):
+        return 0
+    return 2 if persistent_gemm == "always" else 1
+
+
 class DenoiseEngine:
     # Identities / audio streams per sample.  The reference forward dereferences exactly id_cond[0], id_cond[1]
     # (models/transformer.py:638-639) and repeats the video twice (:784, :881); everything else in it (router, perceiver,
@@ -117,6 +126,10 @@ class DenoiseEngine:
         pg = getattr(model, "_mx_persistent_gemm", False)
         mx8 = self.mx_fmt == "mxfp8" and self.mx_wfmt == "mxfp8"
         self.mx_kernel = (2 if pg == "always" else 1) if (pg and mx8) else 0
+        # ... with "mxfp4" weights under "mxfp8" activations the same switch sends them through ops.gemm_mx_call instead, whose
+        # kernel is an argument (1, or 2 for "always"): the persistent kernel's e2m1-weight instances, the same bits.  0: the
+        # launches of every other mode, as they were
+        self.mx_call_kernel = mx_call_kernel(self.mx_fmt, self.mx_wfmt, pg)
         # the remaining A/B switches of the step, read ONCE here (round 4 looked them up in os.environ on every step / call)
         self.side_stream_conditioning = os.environ.get("BYA_INVARIANTS_SIDE_STREAM", "1") != "0"
         self.sp_allgather = os.environ.get("BYA_SP_ALLGATHER", "0") == "1"       # exchange A as a K/V all-gather (A/B)
@@ -340,7 +353,13 @@ class DenoiseEngine:
             return
         if self.mx_fuse_qk_norm and stats is None and xq is not None and self.wmx is not None and "qkv" in self.wmx:
             wc, sw = self.wmx["qkv"][i]
-            if ops.gemm_mx_qkv_norm_rope(xq[0], xq[1].view(*xn.shape[:-1], -1), wc, sw, out, self.qkv_b[i], split,
+            if self.mx_call_kernel:
+                norm = dict(qw=at.norm_q.weight, qb=at.norm_q.bias, kw=at.norm_k.weight, kb=at.norm_k.bias, cos=cos, sin=sin,
+                            text_rows=text_rows, eps=at.norm_q.eps, k_scale=self.k_scale)
+                if ops.gemm_mx_call(xq[0], xq[1].view(*xn.shape[:-1], -1), wc, sw, out, self.mx_call_kernel, self.mx_fmt,
+                                    self.mx_wfmt, bias=self.qkv_b[i], split=split, norm=norm):
+                    return
+            elif ops.gemm_mx_qkv_norm_rope(xq[0], xq[1].view(*xn.shape[:-1], -1), wc, sw, out, self.qkv_b[i], split,
                                          at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin, text_rows,
                                          eps=at.norm_q.eps, k_scale=self.k_scale, fmt=self.mx_fmt, w_fmt=self.mx_wfmt,
                                          kernel=self.mx_kernel):
@@ -358,6 +377,9 @@ class DenoiseEngine:
                 quantised = ops.quantize_mx(a, self.mx_fmt, *self._amx(a.shape))
             codes, sa = quantised
             wc, sw = self.wmx[which][i]
+            if self.mx_call_kernel:
+                return ops.gemm_mx_call(codes, sa.view(*a.shape[:-1], -1), wc, sw, out, self.mx_call_kernel, self.mx_fmt,
+                                        self.mx_wfmt, **kw)
             with self._mx_kernel_option():
                 return ops.gemm_mx(codes, sa.view(*a.shape[:-1], -1), wc, sw, out, self.mx_fmt, w_fmt=self.mx_wfmt, **kw)
         if self.w8 is None or which not in self.w8:
@@ -397,6 +419,9 @@ class DenoiseEngine:
         codes, sa = quantised
         wc, sw = self.wmx["ff1"][i]
         oc, osc = self._amx(out_shape)
+        if self.mx_call_kernel:
+            return ops.gemm_mx_call(codes, sa.view(*a.shape[:-1], -1), wc, sw, oc, self.mx_call_kernel, self.mx_fmt, self.mx_wfmt,
+                                    out_scales=osc, out_fmt=self.mx_fmt, bias=bias, act="gelu_tanh")
         with self._mx_kernel_option():
             return ops.gemm_mx_quant(codes, sa.view(*a.shape[:-1], -1), wc, sw, oc, osc, self.mx_fmt, w_fmt=self.mx_wfmt,
                                      out_fmt=self.mx_fmt, bias=bias, act="gelu_tanh")

@@ -849,6 +849,88 @@ def gemm_mx_quant_plan(a_codes, a_scales, w_codes, w_scales, out_codes, out_scal
     return _plan_dict(p)
 
 
+def _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, gate_split,
+             gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan):
+    """(bya_mx_gemm_call, bya_gemm_desc, the objects they point into, the epilogue's name) of ``gemm_mx_call``."""
+    code, wcode = mx_fmt_pair(fmt, w_fmt)
+    ptr = _plan_p if plan else _p
+    c = _hip.MxGemmCall()
+    keep = []
+    if norm is not None and out_scales is not None:
+        # (the library refuses the pair; build the bf16 descriptor so that it is asked)
+        d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
+                     plan=plan)
+        c.q_scales = ptr(out_scales)
+        n = _hip.QkNormDesc()
+        keep.append(n)
+        c.norm = ctypes.pointer(n)
+        epi = "both"
+    elif norm is not None:
+        d, n = _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, norm["qw"], norm["qb"], norm["kw"],
+                             norm["kb"], norm.get("cos"), norm.get("sin"), norm["text_rows"], norm.get("eps", 1e-6),
+                             norm.get("k_scale", 1.0), norm.get("tensors", 3), act=act, alpha=alpha, plan=plan)
+        keep.append(n)
+        c.norm = ctypes.pointer(n)
+        epi = "qkn"
+    elif out_scales is not None:
+        out_fmt = fmt if out_fmt is None else out_fmt
+        d = _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out, out_scales, fmt, w_fmt, out_fmt, act, alpha)
+        c.q_scales, c.out_fmt = ptr(out_scales), mx_fmt_code(out_fmt)
+        epi = "quant"
+    else:
+        d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
+                     plan=plan)
+        epi = "bf16"
+    c.A, c.a_scales, c.W, c.w_scales, c.bias, c.C = ptr(a_codes), ptr(a_scales), ptr(w_codes), ptr(w_scales), ptr(bias), ptr(out)
+    c.res, c.gate0, c.gate1 = ptr(res), ptr(gate0), ptr(gate1)
+    c.a_fmt, c.w_fmt, c.kernel = code, wcode, int(kernel)
+    return c, d, keep, epi
+
+
+def gemm_mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8", w_fmt=None, bias=None, res=None, gate0=None,
+                 gate1=None, gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0, out_scales=None, out_fmt=None,
+                 norm=None):
+    """Any MX GEMM as one call whose kernel is an ARGUMENT (bya_gemm_mx_call; option ``mx_kernel`` has no say): ``kernel`` 0 =
+    the tiled kernels, exactly ``gemm_mx`` / ``gemm_mx_quant`` / ``gemm_mx_qkv_norm_rope`` under ``mx_kernel`` 0; 1 = the
+    persistent 256 x 256 kernel where the launch fills it and is eligible -- "mxfp8" activations with "mxfp8" OR "mxfp4"
+    weights, the same bits; 2 (tests) = without the tile count.  The epilogue follows from the arguments: ``out_scales``
+    given = the quantising one (``out`` = the output codes, ``out_fmt``; returns ``(out, out_scales)``); ``norm`` given = the
+    q/k-norm + RoPE one (a dict: qw, qb, kw, kb, cos, sin, text_rows and optionally eps, k_scale, tensors; ``split``
+    required; returns False, nothing launched, where the library declines the shape); else the bf16 one of ``gemm_mx``."""
+    lib = _hip.load()
+    c, d, keep, epi = _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, gate_split,
+                               gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan=False)
+    ab, M, N, K = d.batch, d.M, d.N, d.K
+    name = "bya_gemm_mx_call"
+    if _SHAPE_LABELS:
+        name += f":{epi}:k{int(kernel)}:{fmt}*{w_fmt or fmt}:{ab}x{M}x{N}x{K}:{act or 'none'}"
+    tok = _begin(name)
+    rc = lib.bya_gemm_mx_call(ctypes.byref(c), ctypes.byref(d), _stream())
+    if rc == -4 and epi == "qkn":      # BYA_ERR_UNSUPPORTED: nothing was launched (the caller's two launches count the FLOPs)
+        return False
+    check(rc, "bya_gemm_mx_call")
+    if tok is not None:
+        _FLOPS[tok[0]] = _FLOPS.get(tok[0], 0.0) + 2.0 * ab * M * N * K
+    _end(tok)
+    return True if epi == "qkn" else (out, out_scales) if epi == "quant" else out
+
+
+def gemm_mx_call_plan(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8", w_fmt=None, bias=None, res=None,
+                      gate0=None, gate1=None, gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0,
+                      out_scales=None, out_fmt=None, norm=None):
+    """What ``gemm_mx_call`` would run (``gemm_plan``'s dict): path "t128x128", "t256x256" (mxfp6 activations only) or "p256"
+    (``kernel`` 1 or 2, "mxfp8" activations, "mxfp8" or "mxfp4" weights); None where the q/k-norm epilogue declines the shape."""
+    lib = _hip.load()
+    c, d, keep, epi = _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, gate_split,
+                               gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan=True)
+    p = _hip.GemmPlan()
+    rc = lib.bya_gemm_mx_call_plan(ctypes.byref(c), ctypes.byref(d), ctypes.byref(p))
+    if rc == -4 and epi == "qkn":
+        return None
+    check(rc, "bya_gemm_mx_call_plan")
+    return _plan_dict(p)
+
+
 def linear_small_m(x, w, bias, out, silu_in=False, act_out=None):
     """out[M<=8, N] = f(x) @ w.T + bias (weight-streaming kernel)."""
     lib = _hip.load()

@@ -405,7 +405,9 @@ class BindyouravatarTransformer3DModel(nn.Module):
         the persistent one-wave-per-SIMD 256 x 256 kernel (csrc/gemm_mx_v4.hip), the same bits -- or, "always" (tests),
         mx_kernel = 2: every eligible launch does.  It composes with ``fuse_qk_norm``: with both on, the fused q|k|v launch
         runs on the persistent kernel too (bya_gemm_mx_qkv_norm_rope_on, kernel = 1 or 2 -- one launch per block, the same
-        bits).  Off by default; with "mxfp6" activations or "mxfp4" weights the switch does nothing.  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
+        bits).  With ``weight_format="mxfp4"`` under "mxfp8" activations the same launches (the fused q|k|v one
+        included) go through bya_gemm_mx_call with kernel = 1 (or 2) instead -- the persistent kernel's e2m1-weight instances,
+        the same bits.  Off by default; with "mxfp6" activations the switch does nothing.  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
         counterpart (the reference is bf16/fp16 only); returns self."""
         from .ops import MX_FORMATS, MX_WEIGHT_FORMATS
         if not isinstance(fuse_attention_quant, bool):

@@ -64,7 +64,8 @@ enum bya_option {
                                      form pair is bit-identical, which is what the tests that set these bits assert */
     BYA_OPT_MX_KERNEL = 8,        /* 0 (default): every MX GEMM on the tiled kernels of csrc/gemm_mx.hip; 1: e4m3 x e4m3 launches that
                                      fill the persistent 256 x 256 kernel (csrc/gemm_mx_v4.hip: at least 200 of its tiles, batch
-                                     included, and eligible) run on it -- the same bits; 2 (tests): as 1 without the tile count */
+                                     included, and eligible) run on it -- the same bits; 2 (tests): as 1 without the tile count.
+                                     (e2m1 weights reach that kernel through bya_gemm_mx_call, which reads no option) */
     BYA_OPT_COUNT = 9
 };
 enum { BYA_REF_ROWGEMM_CHUNKED = 1,    /* N = 512 row GEMM: chunk-balanced kernel instead of the W-stationary one */
@@ -169,7 +170,8 @@ int bya_gemm_workspace_status(int32_t* timeouts, hipStream_t stream);
 #define BYA_GEMM_PATH_P256 4      /* persistent 256 x 256 (csrc/gemm_v4.hip); bya_gemm_fp8: csrc/gemm_fp8_v4.hip; bya_gemm_mx /
                                      bya_gemm_mx_mixed / bya_gemm_mx_quant (out e4m3) under option mx_kernel, e4m3 x e4m3 only:
                                      csrc/gemm_mx_v4.hip.  bya_gemm_mx_qkv_norm_rope never takes it;
-                                     bya_gemm_mx_qkv_norm_rope_on takes it by its `kernel` argument */
+                                     bya_gemm_mx_qkv_norm_rope_on takes it by its `kernel` argument, and so does
+                                     bya_gemm_mx_call -- for e4m3 x e2m1 launches too */
 #define BYA_GEMM_PATH_P128 5      /* persistent 128 x 256 (csrc/gemm_v5.hip) */
 #define BYA_GEMM_PATH_P128S 6     /* persistent 128 x 256 with loader waves (csrc/gemm_v6.hip) */
 #define BYA_GEMM_PATH_W8_256 7    /* the 8-wave 256 x 256 kernel P256 falls back to (fewer than 3 K-tiles, a C / res / bias /
@@ -347,6 +349,32 @@ int bya_gemm_mx_qkv_norm_rope_on(const void* A, const void* a_scales, const void
 int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
                                       const void* bias, const void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* desc,
                                       const bya_qknorm_desc* norm, int32_t kernel, bya_gemm_plan* plan);
+/* Any of the MX GEMMs above as ONE call whose kernel is named by an ARGUMENT (no option is read; BYA_OPT_MX_KERNEL has no say),
+ * and the one way e2m1 weights reach the persistent kernel.  The epilogue follows from the fields: `norm` set = the q/k-norm +
+ * RoPE epilogue (bya_gemm_mx_qkv_norm_rope); `q_scales` set = the quantising epilogue (bya_gemm_mx_quant: C = the output codes,
+ * ldc / c_batch_stride in bytes, out_fmt); neither = the bf16 epilogue (bya_gemm_mx_mixed: res, gate0, gate1).
+ *   kernel = 0: exactly the old entry point of that epilogue as it runs with option BYA_OPT_MX_KERNEL at 0 -- same checks, same row
+ *     chunks, same launch;
+ *   kernel = 1: path P256 -- the persistent 256 x 256 kernel of csrc/gemm_mx_v4.hip with the same epilogue, the same bits --
+ *     when a_fmt is e4m3, w_fmt is e4m3 OR e2m1, out_fmt (quantising epilogue) is e4m3, the launch has at least 200 tiles of
+ *     256 x 256 (batch included) and is eligible as for bya_gemm_mx_plan, ldw counting the bytes of the weights' own rows
+ *     (K % 128 == 0, K >= 512, N % 8 == 0, ldw % 16 == 0, N * ldw < 2^32, the epilogue's 16-byte alignments); otherwise what
+ *     the old entry point runs: T128X128, or T256X256 for e2m3 activations;
+ *   kernel = 2 (tests): as 1 without the tile count.
+ * Errors: whatever the old entry point of the epilogue refuses, with its code, before any launch, under every kernel value;
+ * BYA_ERR_SHAPE for a null call / desc / plan, kernel outside 0..2, norm and q_scales both set, and res / gate0 / gate1 set
+ * together with norm or q_scales.  A refused query leaves *plan untouched. */
+typedef struct bya_mx_gemm_call {
+    const void *A, *a_scales, *W, *w_scales, *bias;
+    void* C;                        /* bf16 output; with q_scales set: the output codes (ldc / c_batch_stride in bytes) */
+    const void *res, *gate0, *gate1;/* bf16 epilogue only */
+    void* q_scales;                 /* non-null: the quantising epilogue (bya_gemm_mx_quant), out_fmt */
+    const bya_qknorm_desc* norm;    /* non-null: the q/k-norm + RoPE epilogue (bya_gemm_mx_qkv_norm_rope) */
+    int32_t a_fmt, w_fmt, out_fmt, kernel;
+} bya_mx_gemm_call;
+int bya_gemm_mx_call(const bya_mx_gemm_call* call, const bya_gemm_desc* desc, hipStream_t stream);
+/* its kernel: path T128X128, T256X256 (e2m3 activations) or P256; row_chunks as bya_gemm_mx_mixed_plan's (bf16 epilogue) */
+int bya_gemm_mx_call_plan(const bya_mx_gemm_call* call, const bya_gemm_desc* desc, bya_gemm_plan* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Small-M linear (M <= 8 rows):  out[m,n] = sum_k f(x[m,k]) * W[n,k] + bias[n],  f = identity or SiLU.

@@ -3,6 +3,8 @@ csrc/gemm_fp8_v4.hip (phase 0 = W blocks 0..3 x A blocks 0..7, phase 1 = W block
 and fragment re-reads, and per K-tile 18 LDS-DMA pieces instead of 16: the 8 + 8 one-KiB code pieces and the two 256-byte
 scale pieces (SPIECE) of a wave, each issued right behind the MFMA the table names.  Every fragment read carries the read of
 its scale byte (the RAF / RWF / REREAD macros of the source), so the scale of a block retires with the block.
+The e2m1-weight form of the kernel (FMT_W = MX_E2M1: 64-byte W rows) has a body of its own between the GENERATED-W4 markers:
+the same MFMAs, barriers and re-reads with 14 pieces per K-tile -- 8 A, 4 W, 2 scale.  B2's count comes from each table.
 usage: python tools/gen_gemm_mx_schedule.py [--check]"""
 import os
 
@@ -14,10 +16,15 @@ B1_AFTER = 9            # barrier B1 sits behind this MFMA (the shipped placemen
 B2_AFTER = 30
 # MFMA behind which piece k is issued: code pieces A 0..7, W 0..7 where the fp8 kernel has them, then the A and the W scale piece
 PIECES = list(range(10, 31, 3)) + list(range(32, 57, 3)) + [59, 62]
+# ... of the e2m1-weight form: the A pieces where they are, the four W pieces spread over the slots the eight had
+PIECES_W4 = list(range(10, 31, 3)) + [32] + list(range(35, 57, 6)) + [59, 62]
+N_A = 8                 # A code pieces of a wave and K-tile (both forms); the W pieces follow, then the A and the W scale piece
 
 
-def body():
-    assert len(PIECES) == 18 and all(B1_AFTER < n < 64 for n in PIECES) and PIECES == sorted(PIECES)
+def body(pieces=PIECES):
+    n_w = len(pieces) - N_A - 2
+    assert (pieces is PIECES and n_w == 8) or (pieces is PIECES_W4 and n_w == 4 and len(pieces) == 14)
+    assert all(B1_AFTER < n < 64 for n in pieces) and pieces == sorted(pieces)
     out = ["            RWF(4, cWl, cWh, cSw);"]
     for n in range(64):
         phase, j, i = n >> 5, (n >> 2) & 7, (n & 3) + 4 * (n >> 5)
@@ -26,11 +33,14 @@ def body():
             line += f" RWF({5 + n}, cWl, cWh, cSw);"
         if n == B1_AFTER:
             line += " B1();"
-        for k, at in enumerate(PIECES):
+        for k, at in enumerate(pieces):
             if at == n:
-                line += f" PIECE({k & 7}, {'true' if k >= 8 else 'false'});" if k < 16 else f" SPIECE({'true' if k == 17 else 'false'});"
+                if k < N_A + n_w:
+                    line += f" PIECE({k - N_A if k >= N_A else k}, {'true' if k >= N_A else 'false'});"
+                else:
+                    line += f" SPIECE({'true' if k == N_A + n_w + 1 else 'false'});"
         if n == B2_AFTER:
-            line += f" B2({sum(1 for at in PIECES if at <= B2_AFTER)});"
+            line += f" B2({sum(1 for at in pieces if at <= B2_AFTER)});"
         if n == 31:
             line += " REREAD_W();"
         if phase == 1 and (n & 3) == 3:
@@ -40,4 +50,4 @@ def body():
 
 
 if __name__ == "__main__":
-    generated_block.main(HIP, body())
+    generated_block.main(HIP, body(), tagged={"-W4": body(PIECES_W4)})

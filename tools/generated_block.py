@@ -5,17 +5,21 @@ import re
 import sys
 
 
-def splice(src, body):
-    """`src` with the text between its GENERATED markers replaced by `body` (the marker lines stay)."""
-    new, n = re.subn(r"(// GENERATED-BEGIN[^\n]*\n).*?([ \t]*// GENERATED-END)", lambda m: m.group(1) + body + "\n" + m.group(2), src, flags=re.S)
-    assert n == 1, "GENERATED markers not found"
+def splice(src, body, tag=""):
+    """`src` with the text between its GENERATED markers replaced by `body` (the marker lines stay).  A source with more than
+    one generated block names the others: `tag` "-W4" means the markers ``// GENERATED-W4-BEGIN`` / ``// GENERATED-W4-END``."""
+    new, n = re.subn(rf"(// GENERATED{tag}-BEGIN[^\n]*\n).*?([ \t]*// GENERATED{tag}-END)", lambda m: m.group(1) + body + "\n" + m.group(2), src, flags=re.S)
+    assert n == 1, f"GENERATED{tag} markers not found"
     return new
 
 
-def main(path, body, also_check=None):
-    """Rewrite the block of `path`, or check it (--check; also_check(src) may return one more complaint)."""
+def main(path, body, also_check=None, tagged=None):
+    """Rewrite the block of `path`, or check it (--check; also_check(src) may return one more complaint).  `tagged`: {tag: body}
+    of the source's further blocks (splice)."""
     src = open(path).read()
     new = splice(src, body)
+    for tag, more in (tagged or {}).items():
+        new = splice(new, more, tag)
     if "--check" in sys.argv:
         if new != src:
             raise SystemExit(f"{path}: the GENERATED block is out of date (run this script without --check)")
