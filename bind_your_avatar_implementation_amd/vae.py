@@ -29,6 +29,19 @@ import torch.nn as nn
 from . import ops
 
 
+IMPLICIT_CONV_CHANNELS = (128, 256, 512)      # bya_vae_conv3d: whole 64-channel groups, a power of two of them
+
+
+def conv_path(C, kernel_shape, implicit, stride=1):
+    """Which arm a stride-``stride`` convolution of ``C`` input channels and kernel ``kernel_shape`` ((3, 3, 3) causal, (3, 3)
+    per frame) takes: "implicit" (bya_vae_conv3d on the zero-padded input, no patch matrix) or "patches" (bya_vae_patches +
+    bya_gemm_bf16).  The one place the choice is made: ``_norm_conv`` and ``_upsample_conv`` ask here, ``conv_inventory`` lists
+    what it answers for a whole model."""
+    if implicit and stride == 1 and C in IMPLICIT_CONV_CHANNELS and tuple(kernel_shape) in ((3, 3, 3), (3, 3)):
+        return "implicit"
+    return "patches"
+
+
 class _Causal(nn.Module):           # parameter holders with diffusers' names; never called
     def __init__(self, cin, cout, k):
         super().__init__()
@@ -285,7 +298,7 @@ class BindyouravatarVAE(nn.Module):
         3 x 3 convolution as an implicit GEMM."""
         T, H, W, C = x.shape
         conv = mod.conv if hasattr(mod, "conv") else mod
-        if not self.implicit_conv or C not in (128, 256, 512):
+        if conv_path(C, conv.weight.shape[2:], self.implicit_conv) == "patches":
             return self._conv(key, mod, x, KT=1, up=True, tmode=tmode)[0]
         To = T if tmode == 0 else (2 * T if tmode == 1 else 2 * T - 1)
         kb = ("pad1", To, 2 * H, 2 * W, C)
@@ -306,7 +319,7 @@ class BindyouravatarVAE(nn.Module):
         T, H, W, C = x.shape
         conv = conv_mod.conv if hasattr(conv_mod, "conv") else conv_mod
         cout = conv.weight.shape[0]
-        if not self.implicit_conv or C not in (128, 256, 512) or conv.weight.shape[2:] != (3, 3, 3):
+        if conv_path(C, conv.weight.shape[2:], self.implicit_conv) == "patches":
             h = self._norm(key + ".n", norm, x, zctx)
             if cache is not None and cache.shape[1] == H + 2:                 # (a padded cache from the other path)
                 cache = cache[:, 1:-1, 1:-1].contiguous()
@@ -345,6 +358,54 @@ class BindyouravatarVAE(nn.Module):
             sc = x
         h, new["conv2"] = self._norm_conv(key + ".2", blk.norm2, blk.conv2, h, zctx, cache.get("conv2"), res=sc)
         return h, new
+
+    # ------------------------------------------------------------------------------------------ inventory
+    def conv_inventory(self):
+        """Every convolution of the encoder and the decoder in call order -> list of (name, C, Cout rounded up to 8, kernel,
+        stride, path).  path: ``conv_path``'s answer for the convolutions behind a norm (``_norm_conv``) and the up-samplers
+        (``_upsample_conv``); "patches" for those that call ``_conv``, the patch arm itself (conv_in, the stride-2 down-samplers,
+        the encoder's conv_out behind its plain GroupNorm); "gemm" for 1 x 1 x 1 (shortcuts, conv_y | conv_b stacked).  Reads
+        shapes only: works on a model built on the meta device."""
+        inv = []
+
+        def add(name, conv, path=None, stride=1):
+            cout, cin = conv.weight.shape[:2]
+            k = tuple(conv.weight.shape[2:])
+            if path is None:
+                path = conv_path(cin, k, self.implicit_conv, stride)
+            inv.append((name, cin, (cout + 7) // 8 * 8, k, stride, path))
+
+        def resnet(name, blk, spatial):
+            for i, (norm, conv) in enumerate(((blk.norm1, blk.conv1), (blk.norm2, blk.conv2)), 1):
+                if spatial:
+                    C, zc = norm.conv_y.conv.weight.shape[:2]
+                    inv.append((f"{name}.norm{i}.conv_y|conv_b", zc, 2 * C, (1, 1, 1), 1, "gemm"))
+                add(f"{name}.conv{i}", conv.conv)
+                if i == 1 and blk.cin != blk.cout:
+                    add(f"{name}.conv_shortcut", blk.conv_shortcut, "gemm")
+
+        e, d = self.encoder, self.decoder
+        add("encoder.conv_in", e.conv_in.conv, "patches")
+        for i, db in enumerate(e.down_blocks):
+            for j, blk in enumerate(db.resnets):
+                resnet(f"encoder.down_blocks.{i}.resnets.{j}", blk, False)
+            if hasattr(db, "downsamplers"):
+                add(f"encoder.down_blocks.{i}.downsamplers.0", db.downsamplers[0].conv, "patches", stride=2)
+        for j, blk in enumerate(e.mid_block.resnets):
+            resnet(f"encoder.mid_block.resnets.{j}", blk, False)
+        add("encoder.conv_out", e.conv_out.conv, "patches")
+        add("decoder.conv_in", d.conv_in.conv, "patches")
+        for j, blk in enumerate(d.mid_block.resnets):
+            resnet(f"decoder.mid_block.resnets.{j}", blk, True)
+        for i, ub in enumerate(d.up_blocks):
+            for j, blk in enumerate(ub.resnets):
+                resnet(f"decoder.up_blocks.{i}.resnets.{j}", blk, True)
+            if hasattr(ub, "upsamplers"):
+                add(f"decoder.up_blocks.{i}.upsamplers.0", ub.upsamplers[0].conv)
+        C, zc = d.norm_out.conv_y.conv.weight.shape[:2]
+        inv.append(("decoder.norm_out.conv_y|conv_b", zc, 2 * C, (1, 1, 1), 1, "gemm"))
+        add("decoder.conv_out", d.conv_out.conv)
+        return inv
 
     # ------------------------------------------------------------------------------------------ decode
     def _decode_chunk(self, z, cache):
