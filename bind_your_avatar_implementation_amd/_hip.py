@@ -31,8 +31,12 @@ class QkNormDesc(_c.Structure):
                 ("text_rows", _i32), ("width", _i32), ("eps", _f32), ("k_scale", _f32)]
 
 
+MX_KERNEL_FP6 = 16      # BYA_MX_KERNEL_FP6: flag bit of MxGemmCall.kernel (mxfp6 operands / output may take path "p256")
+
+
 class MxGemmCall(_c.Structure):
-    """bya_mx_gemm_call: the operands, epilogue and kernel of one bya_gemm_mx_call."""
+    """bya_mx_gemm_call: the operands, epilogue and kernel of one bya_gemm_mx_call (kernel: 0, 1, 2, or MX_KERNEL_FP6 + one of
+    them)."""
     _fields_ = [("A", _vp), ("a_scales", _vp), ("W", _vp), ("w_scales", _vp), ("bias", _vp), ("C", _vp),
                 ("res", _vp), ("gate0", _vp), ("gate1", _vp), ("q_scales", _vp), ("norm", _c.POINTER(QkNormDesc)),
                 ("a_fmt", _i32), ("w_fmt", _i32), ("out_fmt", _i32), ("kernel", _i32)]

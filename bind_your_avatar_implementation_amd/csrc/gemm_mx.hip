@@ -630,12 +630,16 @@ int mx_args(const void* A, const void* a_scales, const void* W, const void* w_sc
 // bya_gemm_mx_qkv_norm_rope_on and bya_gemm_mx_call their ARGUMENT (no option is read there).  w4_persistent: whether e2m1
 // weights under e4m3 activations may take the persistent kernel as well (its FMT_W = MX_E2M1 instances) -- bya_gemm_mx_call
 // alone says so: what the older entry points and their plan queries answer for e2m1 weights is pinned to the tiled kernel.
-// quant: the quantising epilogue (out_fmt: its element format; e2m3 stays on the tiled kernel)
+// fp6_persistent: whether a launch with e2m3 activations (weights e2m3 or e2m1) and / or e2m3 output of the quantising
+// epilogue may take it too (its FMT_A = MX_E2M3 / QOUT = MX_E2M3 instances) -- bya_gemm_mx_call under BYA_MX_KERNEL_FP6 alone
+// says so; without it such launches stay on the tiled kernel whatever `kernel` says, which is pinned as well.
+// quant: the quantising epilogue (out_fmt: its element format)
 inline int mx_path(const GemmArgs& a, int batch, const GemmArgs& piece, int32_t a_fmt, int32_t w_fmt, int kernel,
-                   bool w4_persistent, bool quant = false, int32_t out_fmt = MX_E4M3) {
+                   bool w4_persistent, bool fp6_persistent, bool quant = false, int32_t out_fmt = MX_E4M3) {
     const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
-    const bool w_ok = w_fmt == MX_E4M3 || (w4_persistent && w_fmt == MX_E2M1);
-    if (kernel != 0 && a_fmt == MX_E4M3 && w_ok && out_fmt == MX_E4M3 && (kernel == 2 || tiles256 >= 200) &&
+    const bool fp6 = a_fmt == MX_E2M3 || out_fmt == MX_E2M3;
+    const bool w_ok = a_fmt == MX_E4M3 ? w_fmt == MX_E4M3 || (w4_persistent && w_fmt == MX_E2M1) : true;    // (mx_args: e2m3 or e2m1)
+    if (kernel != 0 && w_ok && (!fp6 || fp6_persistent) && (kernel == 2 || tiles256 >= 200) &&
         bya_gemm256p_mx_eligible(&piece, quant))
         return BYA_GEMM_PATH_P256;
     return a_fmt == MX_E2M3 && BYA_MX_E2M3_BIG_TILE && tiles256 >= 200 ? BYA_GEMM_PATH_T256X256 : BYA_GEMM_PATH_T128X128;
@@ -646,7 +650,7 @@ constexpr int MX_P256_GROUP_M = 4;         // row-tiles per group of the persist
 // element format (qs: its scale bytes)
 int mx_launch(int path, const GemmArgs& a, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int epi, int32_t a_fmt,
               int32_t w_fmt, int batch, hipStream_t s) {
-    if (path == BYA_GEMM_PATH_P256) return bya_launch_gemm256p_mx(&a, sa, sw, qs, epi, w_fmt, batch, MX_P256_GROUP_M, s);
+    if (path == BYA_GEMM_PATH_P256) return bya_launch_gemm256p_mx(&a, sa, sw, qs, epi, a_fmt, w_fmt, batch, MX_P256_GROUP_M, s);
     return mx_for_instance(a_fmt, w_fmt, path == BYA_GEMM_PATH_T256X256, [&](auto inst) {
         using I = decltype(inst);
         if (epi == MX_EPI_BF16) return launch_mx<I, MX_EPI_BF16>(a, sa, sw, qs, batch, s);
@@ -671,7 +675,7 @@ extern "C" int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void
     const uint8_t* sa = (const uint8_t*)a_scales;
     const long long ks = d->K / 32;
     return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
-        const int path = mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false);
+        const int path = mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, false);
         return mx_launch(path, piece, sa + row0 * ks, (const uint8_t*)w_scales, nullptr, MX_EPI_BF16, a_fmt, w_fmt, batch, stream);
     });
 }
@@ -686,7 +690,7 @@ extern "C" int bya_gemm_mx_mixed_plan(const void* A, const void* a_scales, const
     if (rc != BYA_OK) return rc;
     const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
     if (!chunks) return BYA_ERR_UNSUPPORTED;
-    return mx_plan(p, mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false), chunks);
+    return mx_plan(p, mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, false), chunks);
 }
 
 namespace {
@@ -718,7 +722,7 @@ extern "C" int bya_gemm_mx_quant(const void* A, const void* a_scales, const void
     GemmArgs a;
     const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
     if (rc != BYA_OK) return rc;
-    const int path = mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, true, out_fmt);
+    const int path = mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, false, true, out_fmt);
     return mx_launch(path, a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, (uint8_t*)q_scales, out_fmt, a_fmt, w_fmt,
                      d->batch, stream);
 }
@@ -730,7 +734,7 @@ extern "C" int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const
     GemmArgs a;
     const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
     if (rc != BYA_OK) return rc;
-    return mx_plan(p, mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, true, out_fmt), 1);
+    return mx_plan(p, mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, false, true, out_fmt), 1);
 }
 
 namespace {
@@ -775,7 +779,7 @@ extern "C" int bya_gemm_mx_qkv_norm_rope_on(const void* A, const void* a_scales,
     GemmArgs a;
     const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
     if (rc != BYA_OK) return rc;
-    return mx_launch(mx_path(a, d->batch, a, fmt, w_fmt, kernel, false), a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, nullptr,
+    return mx_launch(mx_path(a, d->batch, a, fmt, w_fmt, kernel, false, false), a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, nullptr,
                      MX_EPI_QKN, fmt, w_fmt, d->batch, stream);
 }
 
@@ -787,7 +791,7 @@ extern "C" int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_sc
     GemmArgs a;
     const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
     if (rc != BYA_OK) return rc;
-    return mx_plan(p, mx_path(a, d->batch, a, fmt, w_fmt, kernel, false), 1);
+    return mx_plan(p, mx_path(a, d->batch, a, fmt, w_fmt, kernel, false, false), 1);
 }
 
 // ... on the tiled kernel (kernel = 0)
@@ -809,7 +813,9 @@ namespace {
 // the call's kernel and e2m1 weights admitted to the persistent kernel.
 int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, hipStream_t stream, bya_gemm_plan* plan) {
     if (!c || !d) return BYA_ERR_SHAPE;
-    if (c->kernel < 0 || c->kernel > 2) return BYA_ERR_SHAPE;
+    if (c->kernel < 0 || (c->kernel & ~BYA_MX_KERNEL_FP6) > 2) return BYA_ERR_SHAPE;       // 0, 1, 2, 16, 17, 18
+    const int kernel = c->kernel & ~BYA_MX_KERNEL_FP6;
+    const bool fp6 = (c->kernel & BYA_MX_KERNEL_FP6) != 0;
     if (c->norm && c->q_scales) return BYA_ERR_SHAPE;
     if ((c->norm || c->q_scales) && (c->res || c->gate0 || c->gate1)) return BYA_ERR_SHAPE;
     const uint8_t* const sa = (const uint8_t*)c->a_scales;
@@ -818,7 +824,7 @@ int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, hipStream_t strea
     if (c->norm) {
         const int rc = mx_qkn_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, d, c->norm, c->a_fmt, c->w_fmt, &a);
         if (rc != BYA_OK) return rc;
-        const int path = mx_path(a, d->batch, a, c->a_fmt, c->w_fmt, c->kernel, true);
+        const int path = mx_path(a, d->batch, a, c->a_fmt, c->w_fmt, kernel, true, fp6);
         if (plan) return mx_plan(plan, path, 1);
         return mx_launch(path, a, sa, sw, nullptr, MX_EPI_QKN, c->a_fmt, c->w_fmt, d->batch, stream);
     }
@@ -826,7 +832,7 @@ int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, hipStream_t strea
         const int rc = mx_quant_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, c->q_scales, d, c->a_fmt, c->w_fmt,
                                      c->out_fmt, &a);
         if (rc != BYA_OK) return rc;
-        const int path = mx_path(a, d->batch, a, c->a_fmt, c->w_fmt, c->kernel, true, true, c->out_fmt);
+        const int path = mx_path(a, d->batch, a, c->a_fmt, c->w_fmt, kernel, true, fp6, true, c->out_fmt);
         if (plan) return mx_plan(plan, path, 1);
         return mx_launch(path, a, sa, sw, (uint8_t*)c->q_scales, c->out_fmt, c->a_fmt, c->w_fmt, d->batch, stream);
     }
@@ -838,11 +844,11 @@ int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, hipStream_t strea
         int nb = 0;
         const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
         if (!chunks) return BYA_ERR_UNSUPPORTED;
-        return mx_plan(plan, mx_path(a, d->batch, piece, c->a_fmt, c->w_fmt, c->kernel, true), chunks);
+        return mx_plan(plan, mx_path(a, d->batch, piece, c->a_fmt, c->w_fmt, kernel, true, fp6), chunks);
     }
     const long long ks = d->K / 32;
     return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
-        const int path = mx_path(a, d->batch, piece, c->a_fmt, c->w_fmt, c->kernel, true);
+        const int path = mx_path(a, d->batch, piece, c->a_fmt, c->w_fmt, kernel, true, fp6);
         return mx_launch(path, piece, sa + row0 * ks, sw, nullptr, MX_EPI_BF16, c->a_fmt, c->w_fmt, batch, stream);
     });
 }
@@ -850,7 +856,9 @@ int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, hipStream_t strea
 
 // Any MX GEMM of this file with its kernel named by an ARGUMENT (no option is read): the epilogue is chosen by which of
 // `norm` / `q_scales` is set, kernel = 0 is the old entry point of that epilogue under option mx_kernel = 0, and kernel = 1 / 2
-// admit e4m3 x e4m3 AND e4m3 x e2m1 launches to the persistent 256 x 256 kernel (gemm_mx_v4.hip), the same bits.
+// admit e4m3 x e4m3 AND e4m3 x e2m1 launches to the persistent 256 x 256 kernel (gemm_mx_v4.hip), the same bits.  With
+// BYA_MX_KERNEL_FP6 added (17 / 18; 16 = 0) launches with e2m3 activations and / or e2m3 output of the quantising epilogue are
+// admitted as well, by the same rule; without it they stay on the tiled kernel.
 extern "C" int bya_gemm_mx_call(const bya_mx_gemm_call* call, const bya_gemm_desc* desc, hipStream_t stream) {
     return mx_call(call, desc, stream, nullptr);
 }

@@ -37,6 +37,30 @@
 //  * Rows are staged through the SAME slot permutation (w_slot_col), so the accumulator layout and the epilogues do not change.
 //  * Fragments: the lane (fr, fq) reads chunk fq -- block fq, low nibble first, the four-register e2m1 operand of the
 //    block-scaled MFMA -- of row row0 + fr: ONE ds_read_b128; row blocks are 16 rows = 1024 bytes apart (frag_addr64).
+//
+// THE 96-BYTE-ROW IMAGE (e2m3 operands of gemm_mx_v4.hip: 128 six-bit values of one matrix row per K-tile)
+//
+//  * A K-tile of the operand is `rows` LDS rows of 96 BYTES back to back: four 24-byte MX blocks.  Rows whose bit 3 is set
+//    are ROTATED by half a row: byte b of source row `row` sits at byte  (b + 48 s) % 96,  s = (row >> 3) & 1, i.e. block c at
+//    block position  c ^ 2 s.  (The tiled kernel swaps 16-byte chunk pairs instead -- stage_mx<MX_E2M3>, gemm_mx.hip -- which
+//    cuts a lane's 24 bytes in two: three addresses per lane.  Rotating by two whole blocks keeps them together: ONE.)
+//  * Banks (MI355X: a ds_read_b64 is served in two groups of 32 lanes, bank = (address / 4) mod 64, 8 bytes = 2 banks per lane,
+//    so a group is conflict-free exactly when its 32 lanes cover the 64 banks once).  A group is the 16 rows fr of two blocks
+//    fq = 2 g, 2 g + 1.  Row r starts at dword 24 r: 24 r mod 64 runs over the eight multiples of 8 for r = 0..7, and again
+//    for r = 8..15 -- unrotated, rows r and r + 8 would meet in every bank (2-way on every read).  Read p = 0..2 of the lane
+//    takes dwords 24 r + 6 (fq ^ 2 s) + 2 p + {0, 1}.  Every base 24 r mod 64 belongs to one row with s = 0 and one with s = 1,
+//    so the group covers the 64 banks once exactly when the eight dword offsets it adds to a base differ mod 8: they are
+//    2 p + {0, 1, 6, 7} (s = 0) and 2 p + {12, 13, 18, 19} (s = 1), mod 8 the residues 2 p + {0, 1, 6, 7, 4, 5, 2, 3} (the
+//    second group, fq = 2, 3, is the first shifted by 12 dwords).  Three conflict-free ds_read_b64 per fragment: 6 LDS cycles
+//    for 1536 bytes, the array's full 256 bytes per clock.
+//  * Source-side rotation: a wave's 64 rows are 6 KiB = SIX linear 1-KiB pieces; lane l of piece q writes bytes
+//    t .. t + 15, t = 1024 q + 16 l, of the wave's share = row t / 96, byte b = t % 96 (a multiple of 16, as is 48), so it
+//    LOADS source bytes  (b + 48 s) % 96 .. + 15  of that row: one aligned 16-byte chunk that never wraps (stage_off96).
+//    K-tile t is bytes [96 t, 96 t + 96) of a source row; the descriptor's extent ends 3 K / 4 bytes into the last row.
+//  * W rows go through the SAME slot permutation (w_slot_col): accumulator layout and epilogues do not change.
+//  * Fragments: the lane (fr, fq) reads the 24 bytes at block position fq ^ 2 s of row row0 + fr -- block fq, element i at bits
+//    6 i.., the six-register e2m3 operand of the block-scaled MFMA -- as three ds_read_b64 at +0, +8, +16; row blocks are 16
+//    rows = 1536 bytes apart, which leaves s = fr >> 3 alone (frag_addr96).
 #pragma once
 #include "gemm_common.h"
 
@@ -108,6 +132,14 @@ __device__ __forceinline__ uint32_t stage_off64(int lane, int rl, int src_row, u
     return (uint32_t)src_row * pitch + ((lane & 3) ^ (((rl >> 2) & 1) << 1)) * 16;
 }
 
+// ... and of the 96-byte-row image: `lane` moves 16 bytes of piece q (0..5) of a wave's 64 rows.  stage_row96: the row, 0..63,
+// inside the wave's share; stage_off96: the offset, for that row as LDS row rl (its bit 3 decides the rotation)
+__device__ __forceinline__ int stage_row96(int lane, int q) { return (q * 1024 + lane * 16) / 96; }
+__device__ __forceinline__ uint32_t stage_off96(int lane, int q, int rl, int src_row, uint32_t pitch) {
+    const int b = (q * 1024 + lane * 16) % 96;
+    return (uint32_t)src_row * pitch + (uint32_t)((b + 48 * ((rl >> 3) & 1)) % 96);
+}
+
 // ---- buffer descriptors and LDS-DMA --------------------------------------------------------------------------------------
 __device__ __forceinline__ i32x4 raw_rsrc(const void* base, uint32_t bytes) {
     const unsigned long long b = (unsigned long long)base;
@@ -129,9 +161,10 @@ __device__ __forceinline__ void dma_piece(uint32_t lds_base, uint32_t voff, cons
 }
 
 // A / W of tile c behind its origin: what is left of the matrix (T: bf16_t or a byte type for e4m3), nothing for an invalid tile
+// row_elems: as tile_rsrc_w's (e2m3 codes: 3 K / 4 bytes)
 template <typename T>
-__device__ __forceinline__ i32x4 tile_rsrc_a(const GemmArgs& p, const T* A, const PersistentTile& c) {
-    const long long left = ((long long)(p.M - 1 - c.m0) * p.lda + p.K) * (long long)sizeof(T);
+__device__ __forceinline__ i32x4 tile_rsrc_a(const GemmArgs& p, const T* A, const PersistentTile& c, int row_elems = 0) {
+    const long long left = ((long long)(p.M - 1 - c.m0) * p.lda + (row_elems ? row_elems : p.K)) * (long long)sizeof(T);
     return raw_rsrc(A + (long long)c.z * p.a_bs + (long long)c.m0 * p.lda, c.valid && left > 0 ? (uint32_t)left : 0u);
 }
 // row_elems: elements of T that the GEMM reads of a W row where that is not K (e2m1 codes: K / 2 bytes); 0 = K
@@ -152,9 +185,15 @@ __device__ __forceinline__ uint32_t frag_addr64(uint32_t tile, int row, int chun
     return tile + row * 64 + ((chunk ^ (((row >> 2) & 1) << 1)) << 4);
 }
 
+// ... of the 96-byte-row image: the lane's one fragment is the 24 bytes at block position fq ^ 2 s of row row0 + fr
+__device__ __forceinline__ uint32_t frag_addr96(uint32_t tile, int row, int blk) {
+    return tile + row * 96 + (blk ^ (((row >> 3) & 1) << 1)) * 24;
+}
+
 // piece Q of a wave's share (1 KiB apart in LDS), per-lane offsets VO[Q]
 #define DMA_PIECE(Q, BASE, VO, RS, SOFF) dma_piece<(Q) * 1024>(BASE, VO[Q], RS, SOFF)
 #define ALL4(M, ...) M(0, __VA_ARGS__); M(1, __VA_ARGS__); M(2, __VA_ARGS__); M(3, __VA_ARGS__)
+#define ALL6(M, ...) ALL4(M, __VA_ARGS__); M(4, __VA_ARGS__); M(5, __VA_ARGS__)
 #define ALL8(M, ...) ALL4(M, __VA_ARGS__); M(4, __VA_ARGS__); M(5, __VA_ARGS__); M(6, __VA_ARGS__); M(7, __VA_ARGS__)
 // Inline-asm MFMAs are invisible to hipcc: nothing tells it that an LDS return must not land in a register a queued MFMA still
 // has to read, so every fragment stays allocated to its fragment to the end of the K-tile (F: an array of 4 / 8 fragments)

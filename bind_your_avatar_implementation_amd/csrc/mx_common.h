@@ -5,12 +5,13 @@
 #pragma once
 #include "bya_common.h"
 
-// gemm_mx_v4.hip, called by gemm_mx.hip: the persistent one-wave-per-SIMD 256 x 256 kernel for e4m3 activations x e4m3 or e2m1
-// weights (args: GemmArgs).  quant: eligibility under the quantising epilogue; epi: MX_EPI_BF16, MX_EPI_QKN, or MX_E4M3 =
-// quantising (qs: its scale bytes); w_fmt: MX_E4M3 or MX_E2M1
+// gemm_mx_v4.hip, called by gemm_mx.hip: the persistent one-wave-per-SIMD 256 x 256 kernel for e4m3 or e2m3 activations x
+// weights in the same format or in e2m1 (args: GemmArgs).  quant: eligibility under the quantising epilogue; epi: MX_EPI_BF16,
+// MX_EPI_QKN, or MX_E4M3 / MX_E2M3 = quantising to that format (qs: its scale bytes); a_fmt: MX_E4M3 or MX_E2M3; w_fmt: a_fmt
+// or MX_E2M1
 bool bya_gemm256p_mx_eligible(const void* args, bool quant);
-int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int epi, int w_fmt, int batch,
-                           int gm, hipStream_t s);
+int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* sw, uint8_t* qs, int epi, int a_fmt, int w_fmt,
+                           int batch, int gm, hipStream_t s);
 
 namespace {
 

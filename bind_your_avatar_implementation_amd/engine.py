@@ -41,10 +41,14 @@ FP8_LINEARS = ("qkv", "out", "ff1", "ff2", "pq", "aq")
 FP8_DEFAULT = ("qkv", "out", "ff1", "ff2")
 
 
-def mx_call_kernel(fmt, w_fmt, persistent_gemm):
+def mx_call_kernel(fmt, w_fmt, persistent_gemm, persistent_gemm_mxfp6=False):
     """The ``kernel`` argument of the engine's ops.gemm_mx_call launches for enable_mx_weights(fmt, weight_format=w_fmt,
-    persistent_gemm=...): 1 (True) or 2 ("always") for "mxfp4" weights under "mxfp8" activations; 0 = the engine issues the
-    launches it always issued (same-format "mxfp8" follows option mx_kernel, "mxfp6" activations ignore the switch)."""
+    persistent_gemm=..., persistent_gemm_mxfp6=...): 1 (True) or 2 ("always") for "mxfp4" weights under "mxfp8" activations;
+    17 / 18 (the same with BYA_MX_KERNEL_FP6) for "mxfp6" activations, whatever their weights, when ``persistent_gemm_mxfp6``
+    is on; 0 = the engine issues the launches it always issued (same-format "mxfp8" follows option mx_kernel, "mxfp6"
+    activations ignore ``persistent_gemm``, "mxfp8" activations ignore ``persistent_gemm_mxfp6``)."""
+    if fmt == "mxfp6" and persistent_gemm_mxfp6:
+        return 16 + (2 if persistent_gemm_mxfp6 == "always" else 1)
     if not persistent_gemm or (fmt, w_fmt) != ("mxfp8", "mxfp4"):
         return 0
     return 2 if persistent_gemm == "always" else 1
@@ -129,7 +133,9 @@ class DenoiseEngine:
         # ... with "mxfp4" weights under "mxfp8" activations the same switch sends them through ops.gemm_mx_call instead, whose
         # kernel is an argument (1, or 2 for "always"): the persistent kernel's e2m1-weight instances, the same bits.  0: the
         # launches of every other mode, as they were
-        self.mx_call_kernel = mx_call_kernel(self.mx_fmt, self.mx_wfmt, pg)
+        # ... and "mxfp6" activations (weights "mxfp6" or "mxfp4") take the same route with kernel 17 / 18 under the switch of their
+        # own, enable_mx_weights(persistent_gemm_mxfp6=True): the kernel's e2m3 instances, the same bits; off by default
+        self.mx_call_kernel = mx_call_kernel(self.mx_fmt, self.mx_wfmt, pg, getattr(model, "_mx_persistent_gemm_mxfp6", False))
         # the remaining A/B switches of the step, read ONCE here (round 4 looked them up in os.environ on every step / call)
         self.side_stream_conditioning = os.environ.get("BYA_INVARIANTS_SIDE_STREAM", "1") != "0"
         self.sp_allgather = os.environ.get("BYA_SP_ALLGATHER", "0") == "1"       # exchange A as a K/V all-gather (A/B)

@@ -893,7 +893,9 @@ def gemm_mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8
     """Any MX GEMM as one call whose kernel is an ARGUMENT (bya_gemm_mx_call; option ``mx_kernel`` has no say): ``kernel`` 0 =
     the tiled kernels, exactly ``gemm_mx`` / ``gemm_mx_quant`` / ``gemm_mx_qkv_norm_rope`` under ``mx_kernel`` 0; 1 = the
     persistent 256 x 256 kernel where the launch fills it and is eligible -- "mxfp8" activations with "mxfp8" OR "mxfp4"
-    weights, the same bits; 2 (tests) = without the tile count.  The epilogue follows from the arguments: ``out_scales``
+    weights, the same bits; 2 (tests) = without the tile count; 16 + one of them (``_hip.MX_KERNEL_FP6``; 17, 18; 16 = 0) =
+    the same, and "mxfp6" activations (with "mxfp6" or "mxfp4" weights) and "mxfp6" output of the quantising epilogue are
+    admitted to that kernel as well -- without the flag they stay tiled.  The epilogue follows from the arguments: ``out_scales``
     given = the quantising one (``out`` = the output codes, ``out_fmt``; returns ``(out, out_scales)``); ``norm`` given = the
     q/k-norm + RoPE one (a dict: qw, qb, kw, kb, cos, sin, text_rows and optionally eps, k_scale, tensors; ``split``
     required; returns False, nothing launched, where the library declines the shape); else the bf16 one of ``gemm_mx``."""
@@ -919,7 +921,8 @@ def gemm_mx_call_plan(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="
                       gate0=None, gate1=None, gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0,
                       out_scales=None, out_fmt=None, norm=None):
     """What ``gemm_mx_call`` would run (``gemm_plan``'s dict): path "t128x128", "t256x256" (mxfp6 activations only) or "p256"
-    (``kernel`` 1 or 2, "mxfp8" activations, "mxfp8" or "mxfp4" weights); None where the q/k-norm epilogue declines the shape."""
+    (``kernel`` 1 or 2, "mxfp8" activations, "mxfp8" or "mxfp4" weights and "mxfp8" output; ``kernel`` 17 or 18: "mxfp6"
+    activations and / or "mxfp6" output too); None where the q/k-norm epilogue declines the shape."""
     lib = _hip.load()
     c, d, keep, epi = _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, gate_split,
                                gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan=True)

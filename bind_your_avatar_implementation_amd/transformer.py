@@ -382,7 +382,7 @@ class BindyouravatarTransformer3DModel(nn.Module):
 
     def enable_mx_weights(self, fmt: str = "mxfp6", enabled: bool = True, linears=None, weight_format=None, *,
                           fuse_activation_quant: bool = True, fuse_attention_quant: bool = False,
-                          fuse_qk_norm: bool = False, persistent_gemm=False):
+                          fuse_qk_norm: bool = False, persistent_gemm=False, persistent_gemm_mxfp6=False):
         """Run the selected Linears on OCP MX operands: 32-element blocks along K with one e8m0 scale each, applied by
         gfx950's block-scaled matrix instruction (include/bya.h, "MX weights").  ``fmt``: "mxfp6" (e2m3 elements, the
         instruction's fastest dense rate) or "mxfp8" (e4m3 elements, the more accurate).  Weights are quantised when the
@@ -407,7 +407,12 @@ class BindyouravatarTransformer3DModel(nn.Module):
         runs on the persistent kernel too (bya_gemm_mx_qkv_norm_rope_on, kernel = 1 or 2 -- one launch per block, the same
         bits).  With ``weight_format="mxfp4"`` under "mxfp8" activations the same launches (the fused q|k|v one
         included) go through bya_gemm_mx_call with kernel = 1 (or 2) instead -- the persistent kernel's e2m1-weight instances,
-        the same bits.  Off by default; with "mxfp6" activations the switch does nothing.  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
+        the same bits.  Off by default; with "mxfp6" activations the switch does nothing.
+        ``persistent_gemm_mxfp6`` (keyword only; False, True or "always"): the same for "mxfp6" activations, with "mxfp6" or
+        "mxfp4" weights -- every MX Linear launch (q|k|v plain or fused with ``fuse_qk_norm``, to_out, ff.net.0 with its
+        quantising epilogue, ff.net.2) goes through bya_gemm_mx_call with kernel = 17 (or 18): the persistent kernel's e2m3
+        instances where a launch fills it, the same bits.  Off by default (opt-in: its time against the tiled kernel's is
+        shape by shape, tools/mx_p256_fp6_probe.py); with "mxfp8" activations it does nothing.  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
         counterpart (the reference is bf16/fp16 only); returns self."""
         from .ops import MX_FORMATS, MX_WEIGHT_FORMATS
         if not isinstance(fuse_attention_quant, bool):
@@ -416,6 +421,8 @@ class BindyouravatarTransformer3DModel(nn.Module):
             raise TypeError(f"fuse_qk_norm: expected a bool, got {type(fuse_qk_norm).__name__}")
         if persistent_gemm not in (False, True, "always"):
             raise ValueError(f"persistent_gemm: expected False, True or 'always', got {persistent_gemm!r}")
+        if persistent_gemm_mxfp6 not in (False, True, "always"):
+            raise ValueError(f"persistent_gemm_mxfp6: expected False, True or 'always', got {persistent_gemm_mxfp6!r}")
         if fmt not in MX_FORMATS:
             raise ValueError(f"MX format {fmt!r}: expected one of {sorted(MX_FORMATS)}")
         if weight_format is not None and weight_format not in MX_WEIGHT_FORMATS:
@@ -433,6 +440,10 @@ class BindyouravatarTransformer3DModel(nn.Module):
             self._mx_persistent_gemm = persistent_gemm
         elif hasattr(self, "_mx_persistent_gemm"):
             del self._mx_persistent_gemm
+        if enabled and persistent_gemm_mxfp6:
+            self._mx_persistent_gemm_mxfp6 = persistent_gemm_mxfp6
+        elif hasattr(self, "_mx_persistent_gemm_mxfp6"):
+            del self._mx_persistent_gemm_mxfp6
         self.invalidate_engine()
         return self
 

@@ -171,7 +171,8 @@ int bya_gemm_workspace_status(int32_t* timeouts, hipStream_t stream);
                                      bya_gemm_mx_mixed / bya_gemm_mx_quant (out e4m3) under option mx_kernel, e4m3 x e4m3 only:
                                      csrc/gemm_mx_v4.hip.  bya_gemm_mx_qkv_norm_rope never takes it;
                                      bya_gemm_mx_qkv_norm_rope_on takes it by its `kernel` argument, and so does
-                                     bya_gemm_mx_call -- for e4m3 x e2m1 launches too */
+                                     bya_gemm_mx_call -- for e4m3 x e2m1 launches too, and with BYA_MX_KERNEL_FP6 in its
+                                     `kernel` for e2m3 activations (weights e2m3 or e2m1) and e2m3 output as well */
 #define BYA_GEMM_PATH_P128 5      /* persistent 128 x 256 (csrc/gemm_v5.hip) */
 #define BYA_GEMM_PATH_P128S 6     /* persistent 128 x 256 with loader waves (csrc/gemm_v6.hip) */
 #define BYA_GEMM_PATH_W8_256 7    /* the 8-wave 256 x 256 kernel P256 falls back to (fewer than 3 K-tiles, a C / res / bias /
@@ -361,16 +362,21 @@ int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_scales, const
  *     (K % 128 == 0, K >= 512, N % 8 == 0, ldw % 16 == 0, N * ldw < 2^32, the epilogue's 16-byte alignments); otherwise what
  *     the old entry point runs: T128X128, or T256X256 for e2m3 activations;
  *   kernel = 2 (tests): as 1 without the tile count.
+ *   kernel = BYA_MX_KERNEL_FP6 + 1 / + 2 (17, 18): as 1 / 2, and launches whose a_fmt is e2m3 (w_fmt e2m3 or e2m1) and / or whose
+ *     out_fmt (quantising epilogue) is e2m3 take path P256 by the same rule, lda / ldw counting the bytes of a code row -- the
+ *     e2m3-operand and e2m3-output instances of that kernel, the same bits.  Without the flag such launches stay on the tiled
+ *     kernel under every kernel value.  BYA_MX_KERNEL_FP6 alone (16) is 0.
  * Errors: whatever the old entry point of the epilogue refuses, with its code, before any launch, under every kernel value;
- * BYA_ERR_SHAPE for a null call / desc / plan, kernel outside 0..2, norm and q_scales both set, and res / gate0 / gate1 set
- * together with norm or q_scales.  A refused query leaves *plan untouched. */
+ * BYA_ERR_SHAPE for a null call / desc / plan, kernel not one of 0, 1, 2, 16, 17, 18, norm and q_scales both set, and res /
+ * gate0 / gate1 set together with norm or q_scales.  A refused query leaves *plan untouched. */
+#define BYA_MX_KERNEL_FP6 16        /* flag bit of bya_mx_gemm_call::kernel: e2m3 operands / output may take path P256 */
 typedef struct bya_mx_gemm_call {
     const void *A, *a_scales, *W, *w_scales, *bias;
     void* C;                        /* bf16 output; with q_scales set: the output codes (ldc / c_batch_stride in bytes) */
     const void *res, *gate0, *gate1;/* bf16 epilogue only */
     void* q_scales;                 /* non-null: the quantising epilogue (bya_gemm_mx_quant), out_fmt */
     const bya_qknorm_desc* norm;    /* non-null: the q/k-norm + RoPE epilogue (bya_gemm_mx_qkv_norm_rope) */
-    int32_t a_fmt, w_fmt, out_fmt, kernel;
+    int32_t a_fmt, w_fmt, out_fmt, kernel;      /* kernel: 0, 1, 2, or BYA_MX_KERNEL_FP6 + one of them (above) */
 } bya_mx_gemm_call;
 int bya_gemm_mx_call(const bya_mx_gemm_call* call, const bya_gemm_desc* desc, hipStream_t stream);
 /* its kernel: path T128X128, T256X256 (e2m3 activations) or P256; row_chunks as bya_gemm_mx_mixed_plan's (bf16 epilogue) */
