@@ -93,6 +93,11 @@ class RouterChainPlan(_c.Structure):
     _fields_ = [("tiles", _i32), ("tp0", _i32), ("grid", _i32), ("passes", _i32), ("tiles_last", _i32), ("wgs_last", _i32)]
 
 
+class StepPlan(_c.Structure):
+    """bya_step_plan_info: the plan of bya_linear_small_m / bya_router_scores / bya_act_add / bya_cfg_scheduler_step."""
+    _fields_ = [("kernel", _i32), ("grid", _i32), ("rounds", _i32), ("reserved", _i32), ("items", _i64), ("items_per_round", _i64)]
+
+
 class SchedCoef(_c.Structure):
     _fields_ = [("guidance", _f32), ("sqrt_alpha", _f32), ("sqrt_beta", _f32), ("k_sample", _f32),
                 ("k_denoised", _f32), ("k_noise", _f32), ("k_cur", _f32), ("k_old", _f32)]
@@ -138,6 +143,7 @@ SIGNATURES = {
     "bya_gemm_mx_call": [_c.POINTER(MxGemmCall), _c.POINTER(GemmDesc), _vp],
     "bya_gemm_mx_call_plan": [_c.POINTER(MxGemmCall), _c.POINTER(GemmDesc), _c.POINTER(GemmPlan)],
     "bya_linear_small_m": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "bya_linear_small_m_plan": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _c.POINTER(StepPlan)],
     "bya_timestep_features": [_vp, _vp, _i32, _i32, _i32, _f32, _vp],
     "bya_layernorm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
                       _f32, _vp],
@@ -159,6 +165,7 @@ SIGNATURES = {
     "bya_attn_tiny": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp],
     "bya_attn_tiny_plan": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _c.POINTER(AttnTinyPlan)],
     "bya_router_scores": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _vp],
+    "bya_router_scores_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _c.POINTER(StepPlan)],
     "bya_router_head": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp],
     "bya_forcing_max_over_frames": [_vp, _vp, _i32, _i64, _i32, _vp],
     "bya_masked_combine": [_vp, _vp, _vp, _vp, _i32, _f32, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _vp],
@@ -166,6 +173,7 @@ SIGNATURES = {
     "bya_patchify": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "bya_unpatchify": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "bya_act_add": [_vp, _vp, _vp, _i64, _i32, _vp],
+    "bya_act_add_plan": [_vp, _vp, _vp, _i64, _i32, _c.POINTER(StepPlan)],
     "bya_rowgemm512": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp],
     "bya_rowgemm512_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c.POINTER(RowGemmPlan)],
     "bya_router_group_attn_plan": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64,
@@ -196,6 +204,7 @@ SIGNATURES = {
     "bya_p2p_ipc_import": [_vp, _c.POINTER(_vp)],
     "bya_p2p_ipc_release": [_vp],
     "bya_cfg_scheduler_step": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _c.POINTER(SchedCoef), _vp],
+    "bya_cfg_scheduler_step_plan": [_vp, _i32, _i64, _vp, _vp, _i64, _c.POINTER(SchedCoef), _c.POINTER(StepPlan)],
 }
 
 # bya_option keys / BYA_REF_* bits of include/bya.h
@@ -232,6 +241,8 @@ TINY_INSTANCES = {0: "tiny8<2>", 1: "tiny8<3>", 2: "tiny8<13>", 3: "tiny8<25>", 
                   6: "generic<16>", 7: "generic<32>"}
 
 ROWGEMM_FORMS = {0: "chunk_balanced", 1: "w_stationary"}       # BYA_ROWGEMM_* (bya_rowgemm512_plan)
+
+ROUTER_SCORES_KERNELS = {0: "wave", 1: "lds"}                   # BYA_ROUTER_SCORES_* (bya_router_scores_plan)
 
 LN_KERNELS = {0: "generic", 1: "rows"}                          # BYA_LN_KERNEL_* (bya_layernorm_plan)
 LN_OUT_KINDS = {"bf16": 0, "fp8": 1, "mxfp8": 2, "mxfp6": 3}    # BYA_LN_OUT_*

@@ -358,14 +358,38 @@ extern "C" int bya_get_option(int32_t key, int32_t* value) {
     return BYA_OK;
 }
 
-extern "C" int bya_linear_small_m(const void* x, const void* W, const void* bias, void* out, int32_t M, int32_t N,
-                                  int32_t K, int32_t silu_in, int32_t act_out, hipStream_t stream) {
+// bya_linear_small_m: argument checks and the choice between its two instantiations (launcher and bya_linear_small_m_plan).
+static int small_m_plan_of(const void* x, const void* W, const void* out, int32_t M, int32_t N, int32_t K, int32_t act_out,
+                           bya_step_plan_info* p) {
     if (!x || !W || !out || M <= 0 || M > 8 || N <= 0 || K <= 0) return BYA_ERR_SHAPE;
     if (K % 8) return BYA_ERR_SHAPE;
     if (((uintptr_t)x | (uintptr_t)W) & 15) return BYA_ERR_ALIGN;
     if (act_out != BYA_ACT_NONE && act_out != BYA_ACT_SILU) return BYA_ERR_UNSUPPORTED;
-    dim3 grid((unsigned)((N + 3) / 4));
-    if (M <= 2)
+    p->kernel = M <= 2 ? 2 : 8;
+    p->grid = (N + 3) / 4;
+    p->rounds = (K + 511) / 512;
+    p->reserved = 0;
+    p->items = N;
+    p->items_per_round = 512;
+    return BYA_OK;
+}
+
+extern "C" int bya_linear_small_m_plan(const void* x, const void* W, const void* out, int32_t M, int32_t N, int32_t K,
+                                       int32_t act_out, bya_step_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_step_plan_info p;
+    const int rc = small_m_plan_of(x, W, out, M, N, K, act_out, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_linear_small_m(const void* x, const void* W, const void* bias, void* out, int32_t M, int32_t N,
+                                  int32_t K, int32_t silu_in, int32_t act_out, hipStream_t stream) {
+    bya_step_plan_info pl;
+    const int rc = small_m_plan_of(x, W, out, M, N, K, act_out, &pl);
+    if (rc != BYA_OK) return rc;
+    dim3 grid((unsigned)pl.grid);
+    if (pl.kernel == 2)
         BYA_LAUNCH((linear_small_m_kernel<2>), grid, dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)W,
                            (const bf16_t*)bias, (bf16_t*)out, M, N, K, silu_in, act_out);
     else
@@ -389,6 +413,7 @@ extern "C" int bya_masked_combine(void* x, const void* feat, const void* r, cons
     if (!x || !feat || !r || batch <= 0 || N <= 0 || D <= 0) return BYA_ERR_SHAPE;
     if (mode != 0 && mode != 1) return BYA_ERR_UNSUPPORTED;
     if (n_id < 1 || n_id > 4 || (mode == 1 && !af)) return BYA_ERR_UNSUPPORTED;
+    if (mode == 1 && n_id < 2) return BYA_ERR_UNSUPPORTED;     // routing_weights_of has no 1-stream audio case
     if (D % 8 || x_row % 8 || x_batch_stride % 8) return BYA_ERR_ALIGN;
     if (((uintptr_t)x | (uintptr_t)feat) & 15) return BYA_ERR_ALIGN;
     CombArgs a;
@@ -406,6 +431,7 @@ extern "C" int bya_routed_mix(const void* feat, const void* r, const void* af, v
     if (!feat || !r || !z || batch <= 0 || N <= 0 || D <= 0) return BYA_ERR_SHAPE;
     if (mode != 0 && mode != 1) return BYA_ERR_UNSUPPORTED;
     if (n_id < 1 || n_id > 4 || (mode == 1 && !af)) return BYA_ERR_UNSUPPORTED;
+    if (mode == 1 && n_id < 2) return BYA_ERR_UNSUPPORTED;     // routing_weights_of has no 1-stream audio case
     if (D % 8) return BYA_ERR_ALIGN;
     if (((uintptr_t)z | (uintptr_t)feat) & 15) return BYA_ERR_ALIGN;
     CombArgs a;
@@ -448,27 +474,69 @@ extern "C" int bya_unpatchify(const void* y, void* out, int32_t batch, int32_t f
     return ok();
 }
 
-extern "C" int bya_act_add(const void* x, const void* r, void* y, int64_t n, int32_t act, hipStream_t stream) {
+// bya_act_add / bya_cfg_scheduler_step: argument checks and the capped grid of their grid-stride loops (launchers and plan queries).
+static void stride_plan(long long items, long long cap, bya_step_plan_info* p) {
+    long long blocks = (items + 255) / 256;
+    if (blocks > cap) blocks = cap;
+    p->kernel = 0;
+    p->grid = (int32_t)blocks;
+    p->items = items;
+    p->items_per_round = blocks * 256;
+    p->rounds = (int32_t)((items + p->items_per_round - 1) / p->items_per_round);
+    p->reserved = 0;
+}
+
+static int act_add_plan_of(const void* x, const void* r, const void* y, int64_t n, int32_t act, bya_step_plan_info* p) {
     if (!x || !y || n <= 0 || n % 8) return BYA_ERR_SHAPE;
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)r) & 15) return BYA_ERR_ALIGN;
     if (act < 0 || act > 5) return BYA_ERR_UNSUPPORTED;
-    const long long nvec = n / 8;
-    long long blocks = (nvec + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    BYA_LAUNCH(act_add_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t*)x,
-                       (const bf16_t*)r, (bf16_t*)y, nvec, act);
+    stride_plan(n / 8, 4096, p);
+    return BYA_OK;
+}
+
+static int sched_plan_of(const void* pred, int32_t n_pred, int64_t pred_stride, const void* sample, const void* prev_sample,
+                         int64_t n, const bya_sched_coef* coef, bya_step_plan_info* p) {
+    if (!pred || !sample || !prev_sample || !coef || n <= 0) return BYA_ERR_SHAPE;
+    if (n_pred != 1 && n_pred != 2) return BYA_ERR_SHAPE;
+    if (n_pred == 2 && pred_stride < n) return BYA_ERR_SHAPE;
+    stride_plan(n, 8192, p);
+    return BYA_OK;
+}
+
+extern "C" int bya_act_add_plan(const void* x, const void* r, const void* y, int64_t n, int32_t act, bya_step_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_step_plan_info p;
+    const int rc = act_add_plan_of(x, r, y, n, act, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_cfg_scheduler_step_plan(const void* pred, int32_t n_pred, int64_t pred_stride, const void* sample,
+                                           const void* prev_sample, int64_t n, const bya_sched_coef* coef,
+                                           bya_step_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_step_plan_info p;
+    const int rc = sched_plan_of(pred, n_pred, pred_stride, sample, prev_sample, n, coef, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_act_add(const void* x, const void* r, void* y, int64_t n, int32_t act, hipStream_t stream) {
+    bya_step_plan_info pl;
+    const int rc = act_add_plan_of(x, r, y, n, act, &pl);
+    if (rc != BYA_OK) return rc;
+    BYA_LAUNCH(act_add_kernel, dim3((unsigned)pl.grid), dim3(256), 0, stream, (const bf16_t*)x,
+                       (const bf16_t*)r, (bf16_t*)y, (long long)pl.items, act);
     return ok();
 }
 
 extern "C" int bya_cfg_scheduler_step(const void* pred, int32_t n_pred, int64_t pred_stride, const void* sample,
                                       const float* old_x0, const void* noise, void* prev_sample, float* x0_out,
                                       int64_t n, const bya_sched_coef* coef, hipStream_t stream) {
-    if (!pred || !sample || !prev_sample || !coef || n <= 0) return BYA_ERR_SHAPE;
-    if (n_pred != 1 && n_pred != 2) return BYA_ERR_SHAPE;
-    if (n_pred == 2 && pred_stride < n) return BYA_ERR_SHAPE;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    BYA_LAUNCH(cfg_sched_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t*)pred,
+    bya_step_plan_info pl;
+    const int rc = sched_plan_of(pred, n_pred, pred_stride, sample, prev_sample, n, coef, &pl);
+    if (rc != BYA_OK) return rc;
+    BYA_LAUNCH(cfg_sched_kernel, dim3((unsigned)pl.grid), dim3(256), 0, stream, (const bf16_t*)pred,
                (long long)pred_stride, n_pred, (const bf16_t*)sample, old_x0, (const bf16_t*)noise,
                (bf16_t*)prev_sample, x0_out, (long long)n, *coef);
     return ok();

@@ -359,24 +359,54 @@ inline int ok() { const hipError_t e = hipGetLastError(); return e == hipSuccess
 
 }  // namespace
 
-extern "C" int bya_router_scores(const void* qr, const void* kr, const void* ln_w, const void* ln_b,
-                                 const void* pos_emb, void* out, int32_t n_id, int64_t N, int32_t heads,
-                                 int32_t face_tokens, float eps, hipStream_t stream) {
+// bya_router_scores: argument checks and the choice between its two kernels (launcher and bya_router_scores_plan).
+static int scores_plan_of(const void* qr, const void* kr, const void* ln_w, const void* ln_b, const void* pos_emb, const void* out,
+                          int32_t n_id, int64_t N, int32_t heads, int32_t face_tokens, bya_step_plan_info* p) {
     if (!qr || !kr || !ln_w || !ln_b || !pos_emb || !out || n_id <= 0 || N <= 0) return BYA_ERR_SHAPE;
     if (heads != R_HEADS || face_tokens != R_TOK) return BYA_ERR_UNSUPPORTED;
     if (((uintptr_t)qr | (uintptr_t)kr | (uintptr_t)ln_w | (uintptr_t)ln_b | (uintptr_t)pos_emb | (uintptr_t)out) & 15)
         return BYA_ERR_ALIGN;
+    p->items = (N + 15) / 16;
+    p->reserved = 0;
     if (N >= 4096 && n_id <= 256 && !bya_ref_form(BYA_REF_ROUTER_SCORES_WAVE)) {
+        p->kernel = BYA_ROUTER_SCORES_LDS;
+        p->grid = 256 / n_id * n_id;                             // one workgroup per CU, whole identities
+        p->items_per_round = (long long)(p->grid / n_id) * 8;
+        p->rounds = (int32_t)((p->items + p->items_per_round - 1) / p->items_per_round);
+    } else {
+        p->kernel = BYA_ROUTER_SCORES_WAVE;
+        p->grid = (int32_t)((p->items * n_id + 3) / 4);
+        p->items_per_round = p->items;
+        p->rounds = 1;
+    }
+    return BYA_OK;
+}
+
+extern "C" int bya_router_scores_plan(const void* qr, const void* kr, const void* ln_w, const void* ln_b, const void* pos_emb,
+                                      const void* out, int32_t n_id, int64_t N, int32_t heads, int32_t face_tokens,
+                                      bya_step_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_step_plan_info p;
+    const int rc = scores_plan_of(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, heads, face_tokens, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_router_scores(const void* qr, const void* kr, const void* ln_w, const void* ln_b,
+                                 const void* pos_emb, void* out, int32_t n_id, int64_t N, int32_t heads,
+                                 int32_t face_tokens, float eps, hipStream_t stream) {
+    bya_step_plan_info pl;
+    const int rc = scores_plan_of(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, heads, face_tokens, &pl);
+    if (rc != BYA_OK) return rc;
+    if (pl.kernel == BYA_ROUTER_SCORES_LDS) {
         static std::atomic<unsigned long long> big{0};
         if (bya_allow_big_lds(reinterpret_cast<const void*>(router_scores_lds_kernel), 160 * 1024, big) != BYA_OK) return BYA_ERR_LAUNCH;
-        const int grid = 256 / n_id * n_id;                      // one workgroup per CU, whole identities
-        BYA_LAUNCH(router_scores_lds_kernel, dim3((unsigned)grid), dim3(512), (size_t)R_TOK * R_QK * 2, stream,
+        BYA_LAUNCH(router_scores_lds_kernel, dim3((unsigned)pl.grid), dim3(512), (size_t)R_TOK * R_QK * 2, stream,
                    (const bf16_t*)qr, (const bf16_t*)kr, (const bf16_t*)ln_w, (const bf16_t*)ln_b,
                    (const bf16_t*)pos_emb, (bf16_t*)out, n_id, (long long)N, eps);
         return ok();
     }
-    const long long waves = ((N + 15) / 16) * n_id;
-    BYA_LAUNCH(router_scores_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream,
+    BYA_LAUNCH(router_scores_kernel, dim3((unsigned)pl.grid), dim3(256), 0, stream,
                        (const bf16_t*)qr, (const bf16_t*)kr, (const bf16_t*)ln_w, (const bf16_t*)ln_b,
                        (const bf16_t*)pos_emb, (bf16_t*)out, n_id, (long long)N, eps);
     return ok();

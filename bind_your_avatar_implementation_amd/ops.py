@@ -948,6 +948,20 @@ def linear_small_m(x, w, bias, out, silu_in=False, act_out=None):
     return out
 
 
+def _step_plan(p, kernel):
+    return {"kernel": kernel, "grid": p.grid, "rounds": p.rounds, "items": p.items, "items_per_round": p.items_per_round}
+
+
+def linear_small_m_plan(x, w, out, act_out=None):
+    """What ``linear_small_m`` would launch (meta tensors will do): {"kernel": rows of the instantiation (2 / 8), "grid", "rounds"
+    (trips of lane 0 over K), "items" (output columns = waves with work), "items_per_round"}."""
+    lib = _hip.load()
+    p, a = _hip.StepPlan(), _plan_p
+    M, K = x.shape
+    check(lib.bya_linear_small_m_plan(a(x), a(w), a(out), M, w.shape[0], K, ACT[act_out], ctypes.byref(p)), "bya_linear_small_m_plan")
+    return _step_plan(p, p.kernel)
+
+
 def timestep_features(timesteps, out, flip_sin_to_cos=True, freq_shift=0.0):
     lib = _hip.load()
     assert timesteps.dtype == torch.int64 and timesteps.is_cuda and out.dtype == torch.bfloat16
@@ -1292,6 +1306,16 @@ def router_scores(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, eps=1e-5):
     return out
 
 
+def router_scores_plan(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N):
+    """What ``router_scores`` would launch (meta tensors will do): {"kernel": "wave" / "lds", "grid", "rounds", "items" (16-token
+    tiles per identity), "items_per_round" (tiles of one identity per round of the waves' walk)}."""
+    lib = _hip.load()
+    p, a = _hip.StepPlan(), _plan_p
+    check(lib.bya_router_scores_plan(a(qr), a(kr), a(ln_w), a(ln_b), a(pos_emb), a(out), n_id, N, 16, 32, ctypes.byref(p)),
+          "bya_router_scores_plan")
+    return _step_plan(p, _hip.ROUTER_SCORES_KERNELS[p.kernel])
+
+
 def router_head(x, w, b, r, n_id, N):
     lib = _hip.load()
     assert x.is_contiguous() and r.is_contiguous()
@@ -1373,24 +1397,56 @@ def act_add(x, out, act=None, res=None):
     return out
 
 
+def act_add_plan(x, out, act=None, res=None):
+    """What ``act_add`` would launch (meta tensors will do): {"grid", "rounds" of the grid-stride loop, "items" (16-byte pieces),
+    "items_per_round"}."""
+    lib = _hip.load()
+    p, a = _hip.StepPlan(), _plan_p
+    check(lib.bya_act_add_plan(a(x), a(res), a(out), x.numel(), ACT[act], ctypes.byref(p)), "bya_act_add_plan")
+    return _step_plan(p, "act_add")
+
+
+def _sched_pred(pred, n):
+    """-> (n_pred, pred_stride) of a prediction [1 or 2, ...]: the rows may be rows of a wider buffer (stride(0) >= n)."""
+    n_pred = pred.shape[0] if pred.numel() != n else 1
+    assert pred.dtype == torch.bfloat16 and n_pred in (1, 2) and pred.numel() == n_pred * n
+    if n_pred == 1:
+        assert pred.is_contiguous()
+        return 1, n
+    assert pred[0].is_contiguous() and pred.stride(0) >= n
+    return 2, pred.stride(0)
+
+
+def cfg_scheduler_step_plan(pred, sample, coef, out=None):
+    """What ``cfg_scheduler_step`` would launch (meta tensors will do): {"grid", "rounds" of the grid-stride loop, "items"
+    (elements), "items_per_round"}."""
+    lib = _hip.load()
+    p, a = _hip.StepPlan(), _plan_p
+    n = sample.numel()
+    n_pred, stride = _sched_pred(pred, n)
+    c = _hip.SchedCoef(**{k: float(v) for k, v in coef.items()})
+    check(lib.bya_cfg_scheduler_step_plan(a(pred), n_pred, stride, a(sample), a(sample if out is None else out), n, ctypes.byref(c),
+                                          ctypes.byref(p)), "bya_cfg_scheduler_step_plan")
+    return _step_plan(p, "cfg_scheduler_step")
+
+
 def cfg_scheduler_step(pred, sample, coef, old_x0=None, noise=None, x0_out=None, out=None):
     """Fused CFG combine + scheduler step (reference models/pipeline_bindyouravatar.py:924-948).
-    pred: bf16 [1 or 2, ...] model output ([uncond, cond] when 2); sample: bf16 latents [1, ...] (or any shape with the
-    element count of one prediction); coef: dict with the fields of ``bya_sched_coef``; old_x0 / x0_out: fp32;
+    pred: bf16 [1 or 2, ...] model output ([uncond, cond] when 2; the two may be rows of a wider buffer); sample: bf16
+    latents [1, ...] (or any shape with the element count of one prediction); coef: dict with the fields of ``bya_sched_coef``; old_x0 / x0_out: fp32;
     noise: bf16.  Returns the new bf16 latents."""
     import ctypes
     lib = _hip.load()
     n = sample.numel()
-    n_pred = pred.shape[0] if pred.numel() != n else 1
-    assert pred.dtype == sample.dtype == torch.bfloat16 and pred.is_contiguous() and sample.is_contiguous()
-    assert n_pred in (1, 2) and pred.numel() == n_pred * n
+    n_pred, pred_stride = _sched_pred(pred, n)
+    assert sample.dtype == torch.bfloat16 and sample.is_contiguous()
     for t, dt in ((old_x0, torch.float32), (noise, torch.bfloat16), (x0_out, torch.float32)):
         assert t is None or (t.dtype == dt and t.is_contiguous() and t.numel() == n)
     if out is None:
         out = torch.empty_like(sample)
     c = _hip.SchedCoef(**{k: float(v) for k, v in coef.items()})
     tok = _begin("bya_cfg_scheduler_step")
-    check(lib.bya_cfg_scheduler_step(_p(pred), n_pred, n, _p(sample), _p(old_x0), _p(noise), _p(out), _p(x0_out), n,
+    check(lib.bya_cfg_scheduler_step(_p(pred), n_pred, pred_stride, _p(sample), _p(old_x0), _p(noise), _p(out), _p(x0_out), n,
                                      ctypes.byref(c), _stream()), "bya_cfg_scheduler_step")
     _end(tok)
     return out

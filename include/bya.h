@@ -391,6 +391,35 @@ int bya_gemm_mx_call_plan(const bya_mx_gemm_call* call, const bya_gemm_desc* des
 int bya_linear_small_m(const void* x, const void* W, const void* bias, void* out, int32_t M, int32_t N,
                        int32_t K, int32_t silu_in, int32_t act_out, hipStream_t stream);
 
+/* What a launch of one of the small step kernels would do (host-side queries: they launch nothing and run without a GPU).  Each
+ * query takes the arguments of its entry point that the decision depends on, validates them like the entry point and returns 0
+ * with the plan filled, or the BYA_ERR_* that rejects the arguments with the plan untouched (plan == NULL: BYA_ERR_SHAPE).  The
+ * launchers take their decision from the same functions.
+ *   bya_linear_small_m_plan:     kernel = rows of the instantiation (2 for M <= 2, else 8); grid = ceil(N / 4) workgroups of
+ *                                four waves, one wave per output column; items = N; items_per_round = the 512 elements of K the
+ *                                64 lanes take per trip; rounds = ceil(K / 512) trips of lane 0
+ *   bya_router_scores_plan:      kernel = BYA_ROUTER_SCORES_*; items = ceil(N / 16) 16-token tiles per identity;
+ *                                WAVE: grid = ceil(items n_id / 4), one wave per tile (items_per_round = items, rounds = 1);
+ *                                LDS (N >= 4096, n_id <= 256, BYA_REF_ROUTER_SCORES_WAVE not set): grid = 256 / n_id * n_id
+ *                                workgroups of eight waves, grid / n_id per identity; items_per_round = 8 grid / n_id tiles of one
+ *                                identity per round of the waves' walk; rounds = ceil(items / items_per_round)
+ *   bya_act_add_plan:            items = n / 8 16-byte pieces; grid = min(4096, ceil(items / 256)); items_per_round = 256 grid;
+ *                                rounds = ceil(items / items_per_round) trips of the grid-stride loop
+ *   bya_cfg_scheduler_step_plan: items = n elements; grid = min(8192, ceil(n / 256)); items_per_round = 256 grid; rounds as above
+ */
+#define BYA_ROUTER_SCORES_WAVE 0
+#define BYA_ROUTER_SCORES_LDS 1
+typedef struct bya_step_plan_info {
+    int32_t kernel;
+    int32_t grid;             /* workgroups */
+    int32_t rounds;
+    int32_t reserved;
+    int64_t items;
+    int64_t items_per_round;
+} bya_step_plan_info;
+int bya_linear_small_m_plan(const void* x, const void* W, const void* out, int32_t M, int32_t N, int32_t K, int32_t act_out,
+                            bya_step_plan_info* plan);
+
 /* Sinusoidal timestep features (diffusers Timesteps, flip_sin_to_cos, shift 0) in fp32 then rounded
  * to bf16: out[b, 0:dim/2] = cos(t*w_k), out[b, dim/2:] = sin(t*w_k)  (models/transformer.py:679-685). */
 int bya_timestep_features(const int64_t* timesteps, void* out, int32_t batch, int32_t dim,
@@ -644,6 +673,9 @@ int bya_attn_tiny_plan(const void* q, const void* k, const void* v, const void* 
 int bya_router_scores(const void* qr, const void* kr, const void* ln_w, const void* ln_b, const void* pos_emb,
                       void* out, int32_t n_id, int64_t N, int32_t heads, int32_t face_tokens, float eps,
                       hipStream_t stream);
+int bya_router_scores_plan(const void* qr, const void* kr, const void* ln_w, const void* ln_b, const void* pos_emb,
+                           const void* out, int32_t n_id, int64_t N, int32_t heads, int32_t face_tokens,
+                           bya_step_plan_info* plan);           /* see bya_step_plan_info */
 int bya_router_head(const void* x, const void* w, const void* b, void* r, int32_t n_id, int64_t N, int32_t D,
                     hipStream_t stream);
 
@@ -659,6 +691,8 @@ int bya_forcing_max_over_frames(const void* forcing, void* out, int32_t frames, 
  *                  n_id in 3..4 (the reference hard-codes two streams; build-defined): af is [batch, n_id, n_id] and
  *                  w[n,a] = prod_{b != a} bf16(1 - av[n,b]), every product rounded to bf16 (two streams: same bits)
  * r: [batch or 1, N, n_id] (r_batch_stride 0 = shared forcing mask); feat [batch, n_id, N, D]. In place.
+ * n_id in 1..4; mode 1 needs at least two streams: mode == 1 with n_id < 2 is BYA_ERR_UNSUPPORTED, here and in
+ * bya_routed_mix, before any launch (the weights of one stream alone are not defined; bya_attn_kv_mix refuses it too).
  * --------------------------------------------------------------------------------------------- */
 int bya_masked_combine(void* x, const void* feat, const void* r, const void* af, int32_t mode, float alpha,
                        int32_t batch, int32_t n_id, int64_t N, int32_t D, int64_t x_row, int64_t x_batch_stride,
@@ -682,6 +716,8 @@ int bya_unpatchify(const void* y, void* out, int32_t batch, int32_t frames, int3
 
 /* Elementwise helpers: y = act(x) (+ r) over n bf16 elements (n % 8 == 0). */
 int bya_act_add(const void* x, const void* r, void* y, int64_t n, int32_t act, hipStream_t stream);
+int bya_act_add_plan(const void* x, const void* r, const void* y, int64_t n, int32_t act,
+                     bya_step_plan_info* plan);                  /* see bya_step_plan_info */
 
 /* ---------------------------------------------------------------------------------------------
  * Row-stationary GEMM for K = 512 with optional fused LayerNorm, GELU(erf) and residual:
@@ -802,6 +838,9 @@ typedef struct bya_sched_coef {
 int bya_cfg_scheduler_step(const void* pred, int32_t n_pred, int64_t pred_stride, const void* sample,
                            const float* old_x0, const void* noise, void* prev_sample, float* x0_out,
                            int64_t n, const bya_sched_coef* coef, hipStream_t stream);
+int bya_cfg_scheduler_step_plan(const void* pred, int32_t n_pred, int64_t pred_stride, const void* sample,
+                                const void* prev_sample, int64_t n, const bya_sched_coef* coef,
+                                bya_step_plan_info* plan);       /* see bya_step_plan_info */
 
 /* Tracking masks -> routing_logits_forcing (stage 2 of the reference inference; util/utils.py:481-514 resize_mask,
  * :871-936 process_masks_to_routing_logits parts 2-3).  masks: uint8 [n_id, in_frames, in_h, in_w], > 0 = foreground;

@@ -28,6 +28,7 @@ def test_header_declares_the_documented_entry_points():
                  "bya_router_mlp_fused_plan", "bya_router_group_attn_plan", "bya_router_group_attn_out_plan", "bya_layernorm", "bya_layernorm_plan", "bya_qknorm_rope", "bya_qknorm_rope_plan", "bya_masked_combine",
                  "bya_router_scores", "bya_router_head", "bya_forcing_max_over_frames", "bya_patchify",
                  "bya_unpatchify", "bya_linear_small_m", "bya_timestep_features", "bya_attn_tiny", "bya_act_add",
+                 "bya_router_scores_plan", "bya_linear_small_m_plan", "bya_act_add_plan", "bya_cfg_scheduler_step", "bya_cfg_scheduler_step_plan",
                  "bya_abi_version"]:
         assert must in syms
 
@@ -175,6 +176,34 @@ def test_python_binding_table_matches_header(lib_path):
     assert (qp.stats, qp.only, qp.grid, qp.slots, qp.pairs, qp.waves) == (0, 0, 28, 0, 888, 111)
     assert qk(None, base, None, 37, 6, 37, base, 8, ctypes.byref(qp)) == 0
     assert (qp.stats, qp.only, qp.grid, qp.slots, qp.pairs, qp.waves) == (1, 2, 14, 8, 444, 56)
+    # the small step kernels' plan queries: validate like their entry points, fill the plan, leave it alone on rejection
+    sp = _hip.StepPlan(-9)
+    assert lib.bya_linear_small_m_plan(base, None, base, 8, 512, 1280, 0, ctypes.byref(sp)) == -1 and sp.kernel == -9
+    assert lib.bya_linear_small_m_plan(base, base, base, 8, 512, 1280, 0, None) == -1
+    assert lib.bya_linear_small_m_plan(base, base + 8, base, 8, 512, 1280, 0, ctypes.byref(sp)) == -2
+    assert lib.bya_linear_small_m_plan(base, base, base, 8, 512, 1280, 2, ctypes.byref(sp)) == -4 and sp.kernel == -9     # gelu_erf
+    assert lib.bya_linear_small_m_plan(base, base, base, 8, 18432, 1280, 0, ctypes.byref(sp)) == 0                        # the face mapper: 8 rows
+    assert (sp.kernel, sp.grid, sp.rounds, sp.items, sp.items_per_round) == (8, 4608, 3, 18432, 512)
+    assert lib.bya_linear_small_m_plan(base, base, base, 2, 18432, 512, 4, ctypes.byref(sp)) == 0 and (sp.kernel, sp.rounds) == (2, 1)
+    assert lib.bya_router_scores_plan(base, base, base, base, None, base, 2, 17550, 16, 32, ctypes.byref(sp)) == -1
+    assert lib.bya_router_scores_plan(base, base, base, base, base, base, 2, 17550, 16, 31, ctypes.byref(sp)) == -4
+    assert lib.bya_router_scores_plan(base, base, base, base, base, base, 2, 17550, 16, 32, ctypes.byref(sp)) == 0
+    assert (sp.kernel, sp.grid, sp.rounds, sp.items, sp.items_per_round) == (1, 256, 2, 1097, 1024)                       # keys in LDS
+    assert lib.bya_router_scores_plan(base, base, base, base, base, base, 2, 4095, 16, 32, ctypes.byref(sp)) == 0
+    assert (sp.kernel, sp.grid, sp.rounds, sp.items, sp.items_per_round) == (0, 128, 1, 256, 256)                         # one wave per tile
+    assert lib.bya_act_add_plan(base, base, base, 17550 * 3072, 1, ctypes.byref(sp)) == 0
+    assert (sp.kernel, sp.grid, sp.rounds, sp.items, sp.items_per_round) == (0, 4096, 7, 17550 * 384, 4096 * 256)
+    assert lib.bya_act_add_plan(base, base, base + 8, 4096, 1, ctypes.byref(sp)) == -2 and lib.bya_act_add_plan(base, None, base, 4100, 1, ctypes.byref(sp)) == -1
+    sc = _hip.SchedCoef()
+    assert lib.bya_cfg_scheduler_step_plan(base, 2, 100, base, base, 1000, ctypes.byref(sc), ctypes.byref(sp)) == -1      # pred_stride < n
+    assert lib.bya_cfg_scheduler_step_plan(base, 2, 1000, base, None, 1000, ctypes.byref(sc), ctypes.byref(sp)) == -1
+    assert lib.bya_cfg_scheduler_step_plan(base, 2, 1064, base, base, 1000, ctypes.byref(sc), ctypes.byref(sp)) == 0
+    assert (sp.kernel, sp.grid, sp.rounds, sp.items, sp.items_per_round) == (0, 4, 1, 1000, 1024)
+    # one-stream audio weights do not exist: refused before the alignment check behind it, which one face stream reaches
+    assert lib.bya_masked_combine(base, base, base, base, 1, 1.0, 1, 1, 64, 12, 16, 1024, 0, None) == -4
+    assert lib.bya_masked_combine(base, base, base, None, 0, 1.0, 1, 1, 64, 12, 16, 1024, 0, None) == -2
+    assert lib.bya_routed_mix(base, base, base, base, None, 1, 1, 1, 64, 12, 0, None) == -4
+    assert lib.bya_routed_mix(base, base, None, base, None, 0, 1, 1, 64, 12, 0, None) == -2
     # the RCCL entry points validate their arguments before touching a communicator
     assert lib.bya_allgather_kv(None, None, None, None, 1, 1, None, None) == -1
     cnt = (ctypes.c_int64 * 2)(1, 1)
@@ -189,7 +218,8 @@ def test_struct_layout_matches_header():
                        ("bya_attn_plan_info", _hip.AttnPlan), ("bya_attn_kv_mix_plan_info", _hip.AttnMixPlan),
                        ("bya_attn_tiny_plan_info", _hip.AttnTinyPlan), ("bya_rowgemm512_plan_info", _hip.RowGemmPlan),
                        ("bya_router_group_attn_plan_info", _hip.GroupAttnPlan), ("bya_router_chain_plan_info", _hip.RouterChainPlan),
-                       ("bya_layernorm_plan_info", _hip.LayerNormPlan), ("bya_qknorm_rope_plan_info", _hip.QkNormRopePlan)):
+                       ("bya_layernorm_plan_info", _hip.LayerNormPlan), ("bya_qknorm_rope_plan_info", _hip.QkNormRopePlan),
+                       ("bya_step_plan_info", _hip.StepPlan)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), src, flags=re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         fields = []
