@@ -162,6 +162,8 @@ SIGNATURES = {
     "bya_attn_workspace_status": [_c.POINTER(_i32), _vp],
     "bya_attn_kv_mix": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(AttnMixDesc), _vp],
     "bya_attn_kv_mix_plan": [_vp, _vp, _c.POINTER(AttnMixDesc), _c.POINTER(AttnMixPlan)],
+    "bya_attn_kv_mix_mx": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(AttnMixDesc), _i32, _i64, _i64, _i64, _i64, _vp],
+    "bya_attn_kv_mix_mx_plan": [_vp, _vp, _vp, _c.POINTER(AttnMixDesc), _i32, _i64, _i64, _i64, _i64, _c.POINTER(AttnMixPlan)],
     "bya_attn_tiny": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp],
     "bya_attn_tiny_plan": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _c.POINTER(AttnTinyPlan)],
     "bya_router_scores": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _vp],

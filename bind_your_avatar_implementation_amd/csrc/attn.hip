@@ -14,6 +14,7 @@
 // and the S^T accumulator is directly the B operand of O^T += V^T.P^T (no LDS round trip for P).
 // Blocks of one (batch, head) are dealt to one XCD so its K/V stream is served by that XCD's L2.
 #include "attn_common.h"
+#include "attn_mix32.h"         // lds_read128 .. pv_mfma, MixArgs, attn_mix32_body
 #include "gemm_persistent.h"      // xcd_range
 #include "routing_weights.h"
 #include <stdlib.h>
@@ -21,12 +22,6 @@
 
 namespace {
 
-// Ablation build (tools/attn_ablate.py; NEVER defined in the product build): a bit mask of work to leave out of the hot
-// loop, results become meaningless, only the time is read.  1: v_exp -> one FMA, 2: K fragments read from LDS once per
-// block instead of per tile, 4: V fragments likewise, 8: no K/V staging after the first tile, 16: no row-sum adds.
-#ifndef BYA_ATTN_ABLATE
-#define BYA_ATTN_ABLATE 0
-#endif
 // (The build knobs BYA_ATTN_KPREFETCH / OCC / RING of rounds 2-4 -- all K fragment reads of a tile up front: +-1 % on the static-bound
 // kernel, -30 % on the running-maximum one (profiles/history/r2_attn_ablation.json); a third K/V stage: no gain -- are gone since
 // round 6; 2 is the ring depth they left.)
@@ -53,55 +48,6 @@ __device__ __forceinline__ void stage_kv(const bf16_t* __restrict__ src, long lo
         gr = gr < kv_max ? gr : kv_max;
         const bf16_t* g = src + (long long)gr * row_stride + chunk * 8;
         __builtin_amdgcn_global_load_lds(GLOBAL_PTR(g), LDS_PTR(lds_tile + rbase * ROW_BYTES), 16, 0, 0);
-    }
-}
-
-// ds_read_b64_tr_b16 through inline asm: the builtin makes hipcc drain the in-flight LDS-DMA of the NEXT tile
-// (s_waitcnt vmcnt(0)) in the middle of the loop; an asm read is invisible to that bookkeeping.  Waits for these
-// reads are counted by hand (lgkmcnt), always followed by sched_barrier(0) so no MFMA is hoisted above the wait.
-template <int OFF>
-__device__ __forceinline__ s16x4 lds_tr_read(uint32_t addr) {
-    s16x4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-
-template <int OFF>
-__device__ __forceinline__ bf16x8 lds_read128(uint32_t addr) {
-    bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int D>
-struct VFrag {
-    s16x4 lo[D / 32], hi[D / 32];
-};
-
-template <int D, int KS>
-__device__ __forceinline__ void v_issue(VFrag<D>& f, const uint32_t (&vbase)[D / 32]) {
-    constexpr int RB = D * 2;
-    if ((BYA_ATTN_ABLATE & 4) && KS >= 2) return;          // ablation: half of the V reads (k-steps 2, 3 reuse 0, 1)
-#pragma unroll
-    for (int d = 0; d < D / 32; ++d) {
-        f.lo[d] = lds_tr_read<KS * 16 * RB>(vbase[d]);
-        f.hi[d] = lds_tr_read<KS * 16 * RB + 8 * RB>(vbase[d]);
-    }
-}
-
-template <int D>
-__device__ __forceinline__ void pv_mfma(const VFrag<D>& f, const bf16x8& pf, f32x16 (&oacc)[D / 32]) {
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-#pragma unroll
-    for (int d = 0; d < D / 32; ++d) {
-        const s16x8 both = {f.lo[d][0], f.lo[d][1], f.lo[d][2], f.lo[d][3], f.hi[d][0], f.hi[d][1], f.hi[d][2], f.hi[d][3]};
-        oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, both), pf, oacc[d], 0, 0, 0);
     }
 }
 
@@ -402,13 +348,6 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& p, char* smem, con
 //     z = sum_id w[n, id] * (O_id / l_id)      in fp32, rounded to bf16 once,
 // so o never reaches HBM: q is read once, z written once.  The per-identity attention is attn_tile<TAIL> of the generic
 // kernel above (single tile, running maximum, keys past Skv masked), the weights are routing_weights.h.
-struct MixArgs {
-    const bf16_t* q; const bf16_t* k; const bf16_t* v; bf16_t* z; const bf16_t* r; const bf16_t* af; float* wsum;
-    int heads, n_id, n_grp, Sq, Skv, nqt, mode;
-    long long q_grp, q_row, k_id, k_grp, k_row, v_id, v_grp, v_row, z_grp, z_row;
-    float scale_log2;
-};
-
 template <int D>
 __device__ __forceinline__ void attn_mix_body(const MixArgs& p, char* smem) {
     constexpr int ROW_BYTES = D * 2, TILE_BYTES = KV_TILE * ROW_BYTES, DSTEPS = D / 16, DT = D / 32;
@@ -508,175 +447,6 @@ __device__ __forceinline__ void attn_mix_body(const MixArgs& p, char* smem) {
                 o[1] = pack2bf(zacc[d][gq * 4 + 2], zacc[d][gq * 4 + 3]);
                 *reinterpret_cast<u32x2*>(zrow + d * 32 + gq * 8 + hf * 4) = o;
             }
-    }
-}
-
-// ---- the <= 32-key form (both callers: 32 audio context tokens per frame, 32 face tokens per identity) --------------
-// attn_mix_body runs ONE 128-row query tile per workgroup: stage K / V (64-row tiles, half of them padding), rendezvous,
-// attention on a 64-key tile with the upper half masked, store -- 6864 workgroups per audio launch, each a serial chain
-// of memory round trips with a barrier in the middle, twice the MFMAs and exps the 32 keys need: 87 us for 218 MB.
-// Here a workgroup owns one (group, head) and a CHUNK of its query rows: the K / V of every identity are staged once
-// (32 rows each) and stay in LDS, after the one rendezvous every wave walks its own 32-row tiles (tile w, w + 4, ... of the
-// chunk) with no further barrier: per tile 4 K-fragment reads, D / 16 MFMAs for S^T, one softmax over 32 keys (two lanes per
-// query), D / 16 MFMAs for O^T, per identity.  blockIdx runs over the heads fastest, so the workgroups in flight
-// together read the 128-byte head segments of the SAME rows (whole 6-KiB rows over a short time, not one segment per
-// row spread over the launch).  Arithmetic per element is that of attn_tile<TAIL> on a first tile (the two-term bf16
-// maximum, the order of the row sum, k-steps 0 and 1 of P.V) -- so results are BIT-IDENTICAL to attn_mix_body and, for
-// one-hot masks, to bya_attn_fwd's rows (tests/test_kernels_gpu.py).
-template <int D>
-__device__ __forceinline__ void stage_kv32(const bf16_t* __restrict__ src, long long row_stride, int kv_max, char* lds_tile,
-                                           int wave, int lane, bool is_v) {
-    constexpr int ROW_BYTES = D * 2, ROWS_PER_INSTR = 1024 / ROW_BYTES, CHUNKS = ROW_BYTES / 16;
-    for (int q = wave; q < 32 / ROWS_PER_INSTR; q += 4) {
-        const int rbase = q * ROWS_PER_INSTR;
-        const int rl = rbase + lane / CHUNKS;
-        const int slot = lane % CHUNKS;
-        const int chunk = slot ^ (is_v ? vswz<D>(rl) : kswz<D>(rl));
-        const int gr = rl < kv_max ? rl : kv_max;
-        const bf16_t* g = src + (long long)gr * row_stride + chunk * 8;
-        __builtin_amdgcn_global_load_lds(GLOBAL_PTR(g), LDS_PTR(lds_tile + rbase * ROW_BYTES), 16, 0, 0);
-    }
-}
-
-template <int D>
-__device__ __forceinline__ void attn_mix32_body(const MixArgs& p, char* smem) {
-    constexpr int ROW_BYTES = D * 2, KV_BYTES = 32 * ROW_BYTES, DSTEPS = D / 16, DT = D / 32;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, hf = lane >> 5;
-    int bid = blockIdx.x;
-    const int head = bid % p.heads; bid /= p.heads;
-    const int chunk = bid % p.nqt;                               // nqt = row chunks per (group, head) in this form
-    const int grp = bid / p.nqt;
-    const int n32 = (p.Sq + 31) >> 5;
-    const int t0 = (int)((long long)n32 * chunk / p.nqt), t1 = (int)((long long)n32 * (chunk + 1) / p.nqt);
-    const bf16_t* Q = p.q + grp * p.q_grp + (long long)head * D;
-    bf16_t* Z = p.z + grp * p.z_grp + (long long)head * D;
-
-    for (int id = 0; id < p.n_id; ++id) {
-        stage_kv32<D>(p.k + id * p.k_id + grp * p.k_grp + (long long)head * D, p.k_row, p.Skv - 1, smem + id * 2 * KV_BYTES,
-                      wave, lane, false);
-        stage_kv32<D>(p.v + id * p.v_id + grp * p.v_grp + (long long)head * D, p.v_row, p.Skv - 1,
-                      smem + id * 2 * KV_BYTES + KV_BYTES, wave, lane, true);
-    }
-    const int g = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
-    uint32_t voff[DT];
-#pragma unroll
-    for (int d = 0; d < DT; ++d) {
-        const int row = 4 * hf + tq;
-        const int ch = 4 * d + 2 * (g & 1) + (tp >> 1);
-        voff[d] = row * ROW_BYTES + ((ch ^ vswz<D>(row)) << 4) + (tp & 1) * 8;
-    }
-    const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
-    uint32_t koff[DSTEPS];
-#pragma unroll
-    for (int s = 0; s < DSTEPS; ++s) koff[s] = r * ROW_BYTES + (((2 * s + hf) ^ kswz<D>(r)) << 4);
-    const float c = p.scale_log2;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                                             // K / V of every identity are in LDS; no barrier below
-
-    // (measured and dropped: q as whole head segments by LDS-DMA into the wave's patch + ds_read_b128 fragments -- audio
-    // level, face 42 -> 49 us; q requested one tile ahead in registers -- +35 registers, one wave per SIMD less, level)
-    for (int t = t0 + wave; t < t1; t += 4) {
-        int qrow = t * 32 + r;
-        const bool q_valid = qrow < p.Sq;
-        qrow = q_valid ? qrow : p.Sq - 1;
-        bf16x8 qf[DSTEPS];
-#pragma unroll
-        for (int s = 0; s < DSTEPS; ++s)
-            qf[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(Q + (long long)qrow * p.q_row + s * 16 + hf * 8));
-        float w[4];
-        routing_weights_of(p.mode, p.n_id, p.af, p.r + ((long long)grp * p.Sq + qrow) * p.n_id, w);
-        if (p.wsum && head == 0 && hf == 0 && q_valid) {
-            float ws = 0.f;
-            for (int i = 0; i < p.n_id; ++i) ws += w[i];
-            p.wsum[(long long)grp * p.Sq + qrow] = ws;
-        }
-        char* zb = smem + p.n_id * 2 * KV_BYTES + wave * KV_BYTES;
-        constexpr int CHUNKS = ROW_BYTES / 16;
-        f32x16 zacc[DT];
-        for (int id = 0; id < p.n_id; ++id) {
-            const uint32_t kb = lds0 + id * 2 * KV_BYTES, vb = kb + KV_BYTES;
-            // S^T = K . Q^T (32 keys x 32 queries): lane (q = r, hf) gets keys (i & 3) + 8 (i >> 2) + 4 hf
-            bf16x8 kf[DSTEPS];
-#pragma unroll
-            for (int s = 0; s < DSTEPS; ++s) kf[s] = lds_read128<0>(kb + koff[s]);
-            f32x16 sacc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) sacc[i] = 0.f;
-            lgkm_wait<0>();
-#pragma unroll
-            for (int s = 0; s < DSTEPS; ++s) sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[s], qf[s], sacc, 0, 0, 0);
-            // the V fragments fly under the softmax
-            VFrag<D> fa, fb;
-            uint32_t vbase[DT];
-#pragma unroll
-            for (int d = 0; d < DT; ++d) vbase[d] = vb + voff[d];
-            v_issue<D, 0>(fa, vbase);
-            v_issue<D, 1>(fb, vbase);
-            float mx = -INFINITY;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int kv = (i & 3) + 8 * (i >> 2) + 4 * hf;
-                if (kv >= p.Skv) sacc[i] = -INFINITY;
-                mx = fmaxf(mx, sacc[i]);
-            }
-            {
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-                mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-            }
-            // the reference point attn_tile takes on a first tile: the maximum as a two-term bf16 value
-            const float m_hi = bf2f(f2bf(mx));
-            const float m_lo = bf2f(f2bf(mx - m_hi));
-            const float m_new = m_hi + m_lo;
-            float psum = 0.f;
-            bf16x8 pf[2];
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float pv = __builtin_amdgcn_exp2f((sacc[tt * 8 + e] - m_new) * c);
-                    psum += pv;
-                    pf[tt][e] = (__bf16)pv;
-                }
-            const auto lsw = __builtin_amdgcn_permlane32_swap(__float_as_uint(psum), __float_as_uint(psum), false, false);
-            const float sc = w[id] / (__uint_as_float(lsw[0]) + __uint_as_float(lsw[1]));
-            f32x16 oacc[DT];
-#pragma unroll
-            for (int d = 0; d < DT; ++d)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) oacc[d][i] = 0.f;
-            lgkm_wait<2 * DT>();
-            pv_mfma<D>(fa, pf[0], oacc);
-            lgkm_wait<0>();
-            pv_mfma<D>(fb, pf[1], oacc);
-#pragma unroll
-            for (int d = 0; d < DT; ++d)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) zacc[d][i] = id == 0 ? fmaf(sc, oacc[d][i], 0.f) : fmaf(sc, oacc[d][i], zacc[d][i]);
-        }
-        // ---- z through this wave's LDS patch, stored as WHOLE head segments: a lane holds 8-byte pieces of its row (d = 32 dt
-        // + 8 gq + 4 hf ..+3); stored as they stand that is 8 DT instructions each touching 32 rows with 16 bytes -- sixteen
-        // partial-line requests per 128-byte segment.  Re-read row-major, 16 bytes per lane: every request a full line.
-#pragma unroll
-        for (int d = 0; d < DT; ++d)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                u32x2 o;
-                o[0] = pack2bf(zacc[d][gq * 4 + 0], zacc[d][gq * 4 + 1]);
-                o[1] = pack2bf(zacc[d][gq * 4 + 2], zacc[d][gq * 4 + 3]);
-                *reinterpret_cast<u32x2*>(zb + r * ROW_BYTES + (((4 * d + gq) ^ (r & 7)) << 4) + 8 * hf) = o;
-            }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-        for (int j = 0; j < 32 * CHUNKS / 64; ++j) {
-            const int idx = j * 64 + lane, row = idx / CHUNKS, ch = idx % CHUNKS;
-            const u32x4 o = *reinterpret_cast<const u32x4*>(zb + row * ROW_BYTES + ((ch ^ (row & 7)) << 4));
-            if (t * 32 + row < p.Sq) *reinterpret_cast<u32x4*>(Z + (long long)(t * 32 + row) * p.z_row + ch * 8) = o;
-        }
-        __builtin_amdgcn_wave_barrier();                         // the patch is rewritten by the next tile
     }
 }
 
@@ -895,6 +665,22 @@ int mix_plan_of(const void* z, const bya_attn_mix_desc* d, int has_af, uintptr_t
     return BYA_OK;
 }
 
+// bya_attn_kv_mix_mx: argument checks and launch decisions (launcher and bya_attn_kv_mix_mx_plan).  The descriptor's checks
+// and the plan are bya_attn_kv_mix's with an aligned stand-in for z; the MX epilogue exists on the <= 32-key form alone.
+int mix_mx_plan_of(const void* codes, const void* scales, const bya_attn_mix_desc* d, int has_af, uintptr_t qkv, int out_fmt,
+                   int64_t c_grp, int64_t c_row, int64_t sc_grp, int64_t sc_row, bya_attn_kv_mix_plan_info* p) {
+    if (!codes || !scales || !d) return BYA_ERR_SHAPE;
+    if (out_fmt != MX_E4M3 && out_fmt != MX_E2M3) return BYA_ERR_UNSUPPORTED;       // e2m1 is never an activation format
+    if (d->z_grp || d->z_row) return BYA_ERR_SHAPE;                                  // there is no bf16 output: its strides stay 0
+    const int rc = mix_plan_of(reinterpret_cast<const void*>((uintptr_t)16), d, has_af, qkv, p);
+    if (rc != BYA_OK) return rc;
+    if (p->form != BYA_KV_MIX_MIX32) return BYA_ERR_UNSUPPORTED;                     // Skv > 32, or the generic form asked for
+    const long long blocks = (long long)d->heads * d->head_dim / 32;
+    if (((uintptr_t)codes | (uintptr_t)c_grp | (uintptr_t)c_row) & 3) return BYA_ERR_ALIGN;      // (the entry's rule: e4m3 codes leave as dwords; e2m3's 2-byte stores would need less)
+    if (c_row < blocks * mx_block_bytes(out_fmt) || sc_row < blocks || c_grp < 0 || sc_grp < 0) return BYA_ERR_SHAPE;
+    return BYA_OK;
+}
+
 }  // namespace
 
 // Which kernel a descriptor selects (reported to the host so tests and bench.py can say which softmax variant ran).
@@ -958,13 +744,8 @@ extern "C" int bya_attn_kv_mix(const void* q, const void* k, const void* v, cons
     const int prc = mix_plan_of(z, d, af != nullptr, (uintptr_t)q | (uintptr_t)k | (uintptr_t)v, &pl);
     if (prc != BYA_OK) return prc;
     MixArgs a;
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.z = (bf16_t*)z;
-    a.r = (const bf16_t*)r; a.af = (const bf16_t*)af; a.wsum = wsum;
-    a.heads = d->heads; a.n_id = d->n_id; a.n_grp = d->n_grp; a.Sq = d->Sq; a.Skv = d->Skv;
-    a.nqt = pl.row_chunks; a.mode = af ? 1 : 0;
-    a.q_grp = d->q_grp; a.q_row = d->q_row; a.k_id = d->k_id; a.k_grp = d->k_grp; a.k_row = d->k_row;
-    a.v_id = d->v_id; a.v_grp = d->v_grp; a.v_row = d->v_row; a.z_grp = d->z_grp; a.z_row = d->z_row;
-    a.scale_log2 = d->scale * 1.4426950408889634f;
+    mix_args_of(q, k, v, r, af, wsum, d, pl.row_chunks, a);
+    a.z = (bf16_t*)z; a.z_grp = d->z_grp; a.z_row = d->z_row;
     const dim3 grid((unsigned)pl.grid);
     const size_t lds = (size_t)pl.lds_bytes;
     if (pl.form == BYA_KV_MIX_MIX32) {
@@ -982,4 +763,28 @@ extern "C" int bya_attn_kv_mix(const void* q, const void* k, const void* v, cons
     if (d->head_dim == 64) BYA_LAUNCH(attn_kv_mix_kernel_d64, grid, dim3(256), lds, stream, a);
     else BYA_LAUNCH(attn_kv_mix_kernel_d128, grid, dim3(256), lds, stream, a);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+extern "C" int bya_attn_kv_mix_mx_plan(const void* codes, const void* scales, const void* af, const bya_attn_mix_desc* d,
+                                      int32_t out_fmt, int64_t c_grp, int64_t c_row, int64_t sc_grp, int64_t sc_row,
+                                      bya_attn_kv_mix_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_attn_kv_mix_plan_info p;
+    const int rc = mix_mx_plan_of(codes, scales, d, af != nullptr, 0, out_fmt, c_grp, c_row, sc_grp, sc_row, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_attn_kv_mix_mx(const void* q, const void* k, const void* v, const void* r, const void* af, void* codes,
+                                  void* scales, float* wsum, const bya_attn_mix_desc* d, int32_t out_fmt, int64_t c_grp,
+                                  int64_t c_row, int64_t sc_grp, int64_t sc_row, hipStream_t stream) {
+    if (!q || !k || !v || !r) return BYA_ERR_SHAPE;
+    bya_attn_kv_mix_plan_info pl;
+    const int prc = mix_mx_plan_of(codes, scales, d, af != nullptr, (uintptr_t)q | (uintptr_t)k | (uintptr_t)v, out_fmt, c_grp,
+                                   c_row, sc_grp, sc_row, &pl);
+    if (prc != BYA_OK) return prc;
+    ByaMixMxOut out;
+    out.codes = static_cast<uint8_t*>(codes); out.scales = static_cast<uint8_t*>(scales);
+    out.c_grp = c_grp; out.c_row = c_row; out.s_grp = sc_grp; out.s_row = sc_row; out.fmt = out_fmt;
+    return bya_launch_attn_kv_mix32_mx(q, k, v, r, af, wsum, *d, pl, out, stream);
 }

@@ -39,6 +39,31 @@ FP8_LINEARS = ("qkv", "out", "ff1", "ff2", "pq", "aq")
 # error (3.7e-2 against the bf16 engine's 1.8e-2; any one DiT Linear: 1.9-2.0e-2) for 1 % of the step time
 # (tools/fp8_error_by_linear.py, profiles/history/r3_fp8_error_by_linear.json).
 FP8_DEFAULT = ("qkv", "out", "ff1", "ff2")
+# MX alone (enable_mx_weights(linears=...), by name only -- "all" stays the six kinds above): the two cross-attention output
+# projections, perceiver_cross_attention[*].to_out and audio_model.layers[*].attn.to_out[0].  Their operand is the mixed z of
+# bya_attn_kv_mix, whose epilogue can write it as MX codes (bya_attn_kv_mix_mx); per-row fp8 would need the whole row's amax,
+# which no attention epilogue has, so enable_fp8_weights keeps refusing them.  In no default: DESIGN.md section 11.
+MX_CROSS_OUT = ("po", "ao")
+
+
+def _linears_of(keep, allowed, what):
+    """The set of Linear kinds a ``linears=`` value names ("all" = FP8_LINEARS, a comma list, or an iterable); ValueError for a
+    name outside ``allowed``."""
+    keep = set(FP8_LINEARS if keep == "all" else keep.split(",")) if isinstance(keep, str) else set(keep)
+    unknown = keep - set(allowed)
+    if unknown:
+        raise ValueError(f"{what} linears {sorted(unknown)}: expected a subset of {allowed}")
+    return keep
+
+
+def fp8_linears_of(model):
+    """Which Linears enable_fp8_weights(linears=...) / BYA_FP8_LINEARS select ("all" = every kind): the rest stays bf16."""
+    return _linears_of(getattr(model, "_fp8_linears", None) or os.environ.get("BYA_FP8_LINEARS") or FP8_DEFAULT, FP8_LINEARS, "fp8")
+
+
+def mx_linears_of(model):
+    """Which Linears enable_mx_weights(linears=...) selects: the fp8 mode's vocabulary and default, plus MX_CROSS_OUT by name."""
+    return _linears_of(getattr(model, "_mx_linears", None) or FP8_DEFAULT, FP8_LINEARS + MX_CROSS_OUT, "MX")
 
 
 def mx_call_kernel(fmt, w_fmt, persistent_gemm, persistent_gemm_mxfp6=False):
@@ -124,6 +149,9 @@ class DenoiseEngine:
         # GEMM + bya_qknorm_rope) when "qkv" is an MX Linear; enable_mx_weights(fuse_qk_norm=True), off by default.  With
         # persistent_gemm on top (mx_kernel, below) that launch runs on the persistent kernel too
         self.mx_fuse_qk_norm = self.mx_fmt is not None and bool(getattr(model, "_mx_fuse_qk_norm", False))
+        # ... and the cross-attention kv-mix writes its to_out's MX operand itself (bya_attn_kv_mix_mx: byte for byte the kv-mix + the
+        # quantiser) when "po" / "ao" are MX Linears; enable_mx_weights(fuse_cross_attention_quant=False) keeps the two launches
+        self.mx_fuse_cross_quant = self.mx_fmt is not None and bool(getattr(model, "_mx_fuse_cross_attention_quant", True))
         # ... and the MX Linear launches run under library option mx_kernel (1, or 2 for "always") when activations and weights
         # are both "mxfp8": the persistent 256 x 256 kernel where a launch fills it, the same bits;
         # enable_mx_weights(persistent_gemm=True), off by default
@@ -232,14 +260,12 @@ class DenoiseEngine:
                   "ff2": lambda: [b.ff.net[2].weight for b in blocks],
                   # ... and the two 3072-wide query projections that sit directly behind a LayerNorm of the video rows
                   "pq": lambda: [pc.to_q.weight for pc in m.perceiver_cross_attention] if m.is_train_face else None,
-                  "aq": lambda: [al["attn"].to_q.weight for al in m.audio_model.layers] if m.is_train_audio else None}
+                  "aq": lambda: [al["attn"].to_q.weight for al in m.audio_model.layers] if m.is_train_audio else None,
+                  # ... and (MX only) the two cross-attention output projections behind bya_attn_kv_mix
+                  "po": lambda: [pc.to_out.weight for pc in m.perceiver_cross_attention] if m.is_train_face else None,
+                  "ao": lambda: [al["attn"].to_out[0].weight for al in m.audio_model.layers] if m.is_train_audio else None}
         if self.fp8_weights:
-            # which Linears run in e4m3 (enable_fp8_weights(linears=...) / BYA_FP8_LINEARS; "all" = every kind): the rest stays bf16
-            keep = getattr(m, "_fp8_linears", None) or os.environ.get("BYA_FP8_LINEARS") or FP8_DEFAULT
-            keep = set(FP8_LINEARS if keep == "all" else keep.split(",")) if isinstance(keep, str) else set(keep)
-            unknown = keep - set(FP8_LINEARS)
-            if unknown:
-                raise ValueError(f"fp8 linears {sorted(unknown)}: expected a subset of {FP8_LINEARS}")
+            keep = fp8_linears_of(m)
             self.w8 = {}
             for k in FP8_LINEARS:
                 ws = source[k]() if k in keep else None
@@ -247,14 +273,9 @@ class DenoiseEngine:
                     self.w8[k] = [ops.quantize_rows_fp8(w) for w in ws]
         self.wmx = None
         if self.mx_fmt is not None:
-            # the same vocabulary and default as the fp8 mode (enable_mx_weights(linears=...); "all" = every kind)
-            keep = getattr(m, "_mx_linears", None) or FP8_DEFAULT
-            keep = set(FP8_LINEARS if keep == "all" else keep.split(",")) if isinstance(keep, str) else set(keep)
-            unknown = keep - set(FP8_LINEARS)
-            if unknown:
-                raise ValueError(f"MX linears {sorted(unknown)}: expected a subset of {FP8_LINEARS}")
+            keep = mx_linears_of(m)
             self.wmx = {}
-            for k in FP8_LINEARS:
+            for k in FP8_LINEARS + MX_CROSS_OUT:
                 ws = source[k]() if k in keep else None
                 if ws is not None:
                     self.wmx[k] = [ops.quantize_mx(w.contiguous(), self.mx_wfmt) for w in ws]
@@ -381,13 +402,7 @@ class DenoiseEngine:
         if self.wmx is not None and which in self.wmx:
             if quantised is None:
                 quantised = ops.quantize_mx(a, self.mx_fmt, *self._amx(a.shape))
-            codes, sa = quantised
-            wc, sw = self.wmx[which][i]
-            if self.mx_call_kernel:
-                return ops.gemm_mx_call(codes, sa.view(*a.shape[:-1], -1), wc, sw, out, self.mx_call_kernel, self.mx_fmt,
-                                        self.mx_wfmt, **kw)
-            with self._mx_kernel_option():
-                return ops.gemm_mx(codes, sa.view(*a.shape[:-1], -1), wc, sw, out, self.mx_fmt, w_fmt=self.mx_wfmt, **kw)
+            return self._mx_linear(which, i, quantised, a.shape[:-1], out, **kw)
         if self.w8 is None or which not in self.w8:
             return ops.gemm(a, w, out, **kw)
         if quantised is None:
@@ -395,6 +410,33 @@ class DenoiseEngine:
         a8, sa = quantised
         w8, sw = self.w8[which][i]
         return ops.gemm_fp8(a8.view(*a.shape), sa.view(*a.shape[:-1]), w8, sw, out, **kw)
+
+    def _mx_linear(self, which, i, quantised, lead, out, **kw):
+        """MX Linear ``which`` of layer ``i`` on the (codes, scales) of its [*lead, K] operand: through ops.gemm_mx_call where a
+        persistent switch names its kernel, ops.gemm_mx under option mx_kernel otherwise."""
+        codes, sa = quantised
+        wc, sw = self.wmx[which][i]
+        if self.mx_call_kernel:
+            return ops.gemm_mx_call(codes, sa.view(*lead, -1), wc, sw, out, self.mx_call_kernel, self.mx_fmt, self.mx_wfmt, **kw)
+        with self._mx_kernel_option():
+            return ops.gemm_mx(codes, sa.view(*lead, -1), wc, sw, out, self.mx_fmt, w_fmt=self.mx_wfmt, **kw)
+
+    def _cross_out(self, which, i, name, shape, mix, w, out, **kw):
+        """The kv-mix launches of one cross-attention and its output projection ``which`` ("po" / "ao") of layer ``i``.
+        ``mix(z, mx)`` issues the launches into the bf16 [B, rows, K] buffer ``z`` or, ``z`` None, into the (codes, scales) pair
+        ``mx``, and returns False where ops.attn_kv_mix declined the MX epilogue.  bf16 Linear: mix, then ops.gemm.  MX Linear:
+        the mix writes the operand itself (``fuse_cross_attention_quant``), else -- switch off, or declined -- the bf16 mix,
+        ops.quantize_mx and the MX GEMM: the same bytes either way."""
+        if self.wmx is None or which not in self.wmx:
+            z = self._buf(name, *shape)
+            mix(z, None)
+            return ops.gemm(z, w, out, **kw)
+        zq = self._amx(shape)
+        if not (self.mx_fuse_cross_quant and mix(None, zq) is not False):
+            z = self._buf(name, *shape)
+            mix(z, None)
+            zq = ops.quantize_mx(z, self.mx_fmt, *zq)
+        return self._mx_linear(which, i, zq, shape[:-1], out, **kw)
 
     def _mx_kernel_option(self):
         """The library option block of an MX Linear launch: mx_kernel as enable_mx_weights(persistent_gemm=...) asked."""
@@ -937,21 +979,26 @@ class DenoiseEngine:
                     r_logits = forced
                 if fuse_face:
                     # Perceiver attention with the masked combine in its epilogue: z = sum_id r[n, id] * attention_id
-                    z = buf("zmix_p", B, N_loc, inner_p)
                     kvs_p = (ntok * 2 * inner_p, 0, 2 * inner_p)
-                    for b in range(B):
-                        rb = r_logits[b if r_logits.shape[0] > 1 else 0]
-                        ops.attn_kv_mix(qp[b], kv_l[b], kv_l[b][..., inner_p:], rb, None, z[b], head_dim=hd_p, heads=16,
-                                        n_id=n_id, n_grp=1, Sq=N_loc, Skv=ntok, q_strides=(0, inner_p), k_strides=kvs_p,
-                                        v_strides=kvs_p, z_strides=(0, inner_p), scale=hd_p ** -0.5)
-                    ops.gemm(z, pc.to_out.weight, xv, res=xv, alpha=m.local_face_scale)
+
+                    def face_mix(z, mx):
+                        for b in range(B):
+                            rb = r_logits[b if r_logits.shape[0] > 1 else 0]
+                            to = dict(z_strides=(0, inner_p)) if mx is None else dict(mx_out=(mx[0][b], mx[1][b], self.mx_fmt))
+                            if ops.attn_kv_mix(qp[b], kv_l[b], kv_l[b][..., inner_p:], rb, None, None if z is None else z[b],
+                                               head_dim=hd_p, heads=16, n_id=n_id, n_grp=1, Sq=N_loc, Skv=ntok,
+                                               q_strides=(0, inner_p), k_strides=kvs_p, v_strides=kvs_p, scale=hd_p ** -0.5,
+                                               **to) is False:
+                                return False
+                    self._cross_out("po", ca, "zmix_p", (B, N_loc, inner_p), face_mix, pc.to_out.weight, xv, res=xv,
+                                    alpha=m.local_face_scale)
                 elif self.mix_before_projection:
                     # to_out is linear and bias-free: route first, project once (half the GEMM, no feat round trip)
                     z = ops.routed_mix(pout, r_logits, None, "face", buf("zmix_p", B, N_loc, inner_p))
-                    ops.gemm(z, pc.to_out.weight, xv, res=xv, alpha=m.local_face_scale)
+                    self._dit_linear("po", ca, z, pc.to_out.weight, xv, res=xv, alpha=m.local_face_scale)
                 else:
                     feat = buf("feat", B, n_id, N_loc, D)
-                    ops.gemm(pout.view(B * n_id, N_loc, inner_p), pc.to_out.weight, feat.view(B * n_id, N_loc, D))
+                    self._dit_linear("po", ca, pout.view(B * n_id, N_loc, inner_p), pc.to_out.weight, feat.view(B * n_id, N_loc, D))
                     if taps is not None:
                         taps[f"id_feat{ca}"] = feat[0].clone()
                     ops.masked_combine(xv, feat, r_logits, None, "face", alpha=m.local_face_scale)
@@ -976,20 +1023,32 @@ class DenoiseEngine:
                     wsum = self._ws.get("wsum")
                     if wsum is None or wsum.numel() != B * N_loc:
                         wsum = self._ws["wsum"] = torch.empty(B, N_loc, dtype=torch.float32, device=self.dev)
-                    z = buf("zmix_a", B, N_loc, D)
-                    for b in range(B):
-                        rb = r_logits[b if r_logits.shape[0] > 1 else 0]
-                        if not sh.active:
-                            ops.attn_kv_mix(qa[b], ka[b], va[b], rb, af[b], z[b], wsum[b], head_dim=64, heads=H, n_id=n_id,
-                                            n_grp=T, Sq=per_frame, Skv=ntok, q_strides=(per_frame * D, D), k_strides=kvs,
-                                            v_strides=kvs, z_strides=(per_frame * D, D), scale=64 ** -0.5)
-                        else:           # shard boundaries cut frames: one launch per (partial) frame of this rank
+                    ai = i // m.audio_attn_interval
+
+                    def audio_mix(z, mx):
+                        # the MX pair's rows are the rank's own, like z's: a segment writes at a byte offset of `start` rows
+                        for b in range(B):
+                            rb = r_logits[b if r_logits.shape[0] > 1 else 0]
+                            if not sh.active:
+                                to = dict(z_strides=(per_frame * D, D)) if mx is None else dict(mx_out=(mx[0][b], mx[1][b], self.mx_fmt))
+                                if ops.attn_kv_mix(qa[b], ka[b], va[b], rb, af[b], None if z is None else z[b], wsum[b],
+                                                   head_dim=64, heads=H, n_id=n_id, n_grp=T, Sq=per_frame, Skv=ntok,
+                                                   q_strides=(per_frame * D, D), k_strides=kvs, v_strides=kvs, scale=64 ** -0.5,
+                                                   **to) is False:
+                                    return False
+                                continue
+                            # shard boundaries cut frames: one launch per (partial) frame of this rank
                             for f, start, length in sh.frame_segments(per_frame):
-                                ops.attn_kv_mix(qa[b, start:], ka[b, :, f], va[b, :, f], rb[start:start + length], af[b],
-                                                z[b, start:], wsum[b, start:], head_dim=64, heads=H, n_id=n_id, n_grp=1,
-                                                Sq=length, Skv=ntok, q_strides=(0, D), k_strides=(kvs[0], 0, D),
-                                                v_strides=(kvs[0], 0, D), z_strides=(0, D), scale=64 ** -0.5)
-                    ops.gemm(z, at.to_out[0].weight, xv, bias=at.to_out[0].bias, res=xv, bias_rowscale=wsum)
+                                to = dict(z_strides=(0, D)) if mx is None else \
+                                    dict(mx_out=(mx[0][b, start:], mx[1][b, start:], self.mx_fmt))
+                                if ops.attn_kv_mix(qa[b, start:], ka[b, :, f], va[b, :, f], rb[start:start + length], af[b],
+                                                   None if z is None else z[b, start:], wsum[b, start:], head_dim=64, heads=H,
+                                                   n_id=n_id, n_grp=1, Sq=length, Skv=ntok, q_strides=(0, D),
+                                                   k_strides=(kvs[0], 0, D), v_strides=(kvs[0], 0, D), scale=64 ** -0.5,
+                                                   **to) is False:
+                                    return False
+                    self._cross_out("ao", ai, "zmix_a", (B, N_loc, D), audio_mix, at.to_out[0].weight, xv,
+                                    bias=at.to_out[0].bias, res=xv, bias_rowscale=wsum)
                     continue
                 ao = buf("ao", B, n_id, N_loc, D)
                 for b in range(B):      # (id, frame) batch of one sample; q rows shared by both ids
@@ -1007,11 +1066,12 @@ class DenoiseEngine:
                     if wsum is None or wsum.numel() != B * N_loc:
                         wsum = self._ws["wsum"] = torch.empty(B, N_loc, dtype=torch.float32, device=self.dev)
                     z = ops.routed_mix(ao, r_logits, af, "audio", buf("zmix_a", B, N_loc, D), wsum)
-                    ops.gemm(z, at.to_out[0].weight, xv, bias=at.to_out[0].bias, res=xv, bias_rowscale=wsum)
+                    self._dit_linear("ao", i // m.audio_attn_interval, z, at.to_out[0].weight, xv, bias=at.to_out[0].bias, res=xv,
+                                     bias_rowscale=wsum)
                 else:
                     feat = buf("feat", B, n_id, N_loc, D)
-                    ops.gemm(ao.view(B * n_id, N_loc, D), at.to_out[0].weight, feat.view(B * n_id, N_loc, D),
-                             bias=at.to_out[0].bias)
+                    self._dit_linear("ao", i // m.audio_attn_interval, ao.view(B * n_id, N_loc, D), at.to_out[0].weight,
+                                     feat.view(B * n_id, N_loc, D), bias=at.to_out[0].bias)
                     ops.masked_combine(xv, feat, r_logits, af, "audio")
                 if taps is not None:
                     taps[f"audio{i}"] = xv.clone()

@@ -650,7 +650,7 @@ def quantize_mx(x, fmt="mxfp6", codes=None, scales=None):
 
 
 def _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
-             plan=False):
+             plan=False, bias_rowscale=None):
     if a_scales.dim() == 2:
         ab, (M, KS) = 1, a_scales.shape
     else:
@@ -676,17 +676,21 @@ def _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_sp
         d.ldres, d.res_batch_stride = ldres, (r_bs if rb == ab else 0)
     d.gate_batch_stride, d.gate_split, d.act = gate_batch_stride, gate_split, ACT[act]
     d.n_split, d.c_split_stride = (0, 0) if split is None else split
-    d.bias_rowscale, d.alpha = None, float(alpha)
+    d.bias_rowscale, d.alpha = (_plan_p if plan else _p)(bias_rowscale), float(alpha)
+    if bias_rowscale is not None:
+        assert bias_rowscale.dtype == torch.float32 and bias_rowscale.is_contiguous() and bias_rowscale.numel() == ab * M
     return d
 
 
 def gemm_mx(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, res=None, gate0=None, gate1=None,
-            gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0, w_fmt=None):
-    """out = res + gate * act(A @ W.T + bias) with both operands in MX form (``quantize_mx``); K is read off the scales.
-    ``fmt``: the activations' format; ``w_fmt``: the weights' (None = the same, or "mxfp4": bya_gemm_mx_mixed)."""
+            gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0, w_fmt=None, bias_rowscale=None):
+    """out = res + gate * alpha * act(A @ W.T + rowscale * bias) with both operands in MX form (``quantize_mx``); K is read off
+    the scales.  ``fmt``: the activations' format; ``w_fmt``: the weights' (None = the same, or "mxfp4": bya_gemm_mx_mixed).
+    ``bias_rowscale``: fp32 [batch * M] as for ``gemm`` (every MX kernel's bf16 epilogue honours it)."""
     lib = _hip.load()
     code, wcode = mx_fmt_pair(fmt, w_fmt)
-    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha)
+    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
+                 bias_rowscale=bias_rowscale)
     ab, M, N, K = d.batch, d.M, d.N, d.K
     mixed = wcode != code
     name = "bya_gemm_mx_mixed" if mixed else "bya_gemm_mx"
@@ -704,13 +708,13 @@ def gemm_mx(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, r
 
 
 def gemm_mx_plan(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, res=None, gate0=None, gate1=None,
-                 gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0, w_fmt=None):
+                 gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0, w_fmt=None, bias_rowscale=None):
     """What ``gemm_mx`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations only), or "p256"
     (mxfp8 activations and weights under option ``mx_kernel``)."""
     lib = _hip.load()
     code, wcode = mx_fmt_pair(fmt, w_fmt)
     d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
-                 plan=True)
+                 plan=True, bias_rowscale=bias_rowscale)
     p, q = _hip.GemmPlan(), _plan_p
     args = (q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), q(res), q(gate0), q(gate1), ctypes.byref(d))
     if wcode != code:
@@ -850,12 +854,14 @@ def gemm_mx_quant_plan(a_codes, a_scales, w_codes, w_scales, out_codes, out_scal
 
 
 def _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, gate_split,
-             gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan):
+             gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan, bias_rowscale=None):
     """(bya_mx_gemm_call, bya_gemm_desc, the objects they point into, the epilogue's name) of ``gemm_mx_call``."""
     code, wcode = mx_fmt_pair(fmt, w_fmt)
     ptr = _plan_p if plan else _p
     c = _hip.MxGemmCall()
     keep = []
+    if bias_rowscale is not None and (norm is not None or out_scales is not None):
+        raise ValueError("gemm_mx_call: bias_rowscale goes with the bf16 epilogue alone")
     if norm is not None and out_scales is not None:
         # (the library refuses the pair; build the bf16 descriptor so that it is asked)
         d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
@@ -879,7 +885,7 @@ def _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias
         epi = "quant"
     else:
         d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
-                     plan=plan)
+                     plan=plan, bias_rowscale=bias_rowscale)
         epi = "bf16"
     c.A, c.a_scales, c.W, c.w_scales, c.bias, c.C = ptr(a_codes), ptr(a_scales), ptr(w_codes), ptr(w_scales), ptr(bias), ptr(out)
     c.res, c.gate0, c.gate1 = ptr(res), ptr(gate0), ptr(gate1)
@@ -889,7 +895,7 @@ def _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias
 
 def gemm_mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8", w_fmt=None, bias=None, res=None, gate0=None,
                  gate1=None, gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0, out_scales=None, out_fmt=None,
-                 norm=None):
+                 norm=None, bias_rowscale=None):
     """Any MX GEMM as one call whose kernel is an ARGUMENT (bya_gemm_mx_call; option ``mx_kernel`` has no say): ``kernel`` 0 =
     the tiled kernels, exactly ``gemm_mx`` / ``gemm_mx_quant`` / ``gemm_mx_qkv_norm_rope`` under ``mx_kernel`` 0; 1 = the
     persistent 256 x 256 kernel where the launch fills it and is eligible -- "mxfp8" activations with "mxfp8" OR "mxfp4"
@@ -898,10 +904,12 @@ def gemm_mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8
     admitted to that kernel as well -- without the flag they stay tiled.  The epilogue follows from the arguments: ``out_scales``
     given = the quantising one (``out`` = the output codes, ``out_fmt``; returns ``(out, out_scales)``); ``norm`` given = the
     q/k-norm + RoPE one (a dict: qw, qb, kw, kb, cos, sin, text_rows and optionally eps, k_scale, tensors; ``split``
-    required; returns False, nothing launched, where the library declines the shape); else the bf16 one of ``gemm_mx``."""
+    required; returns False, nothing launched, where the library declines the shape); else the bf16 one of ``gemm_mx``, which
+    alone takes ``bias_rowscale`` (fp32 [batch * M], as for ``gemm``)."""
     lib = _hip.load()
     c, d, keep, epi = _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, gate_split,
-                               gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan=False)
+                               gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan=False,
+                               bias_rowscale=bias_rowscale)
     ab, M, N, K = d.batch, d.M, d.N, d.K
     name = "bya_gemm_mx_call"
     if _SHAPE_LABELS:
@@ -919,13 +927,14 @@ def gemm_mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8
 
 def gemm_mx_call_plan(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8", w_fmt=None, bias=None, res=None,
                       gate0=None, gate1=None, gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0,
-                      out_scales=None, out_fmt=None, norm=None):
+                      out_scales=None, out_fmt=None, norm=None, bias_rowscale=None):
     """What ``gemm_mx_call`` would run (``gemm_plan``'s dict): path "t128x128", "t256x256" (mxfp6 activations only) or "p256"
     (``kernel`` 1 or 2, "mxfp8" activations, "mxfp8" or "mxfp4" weights and "mxfp8" output; ``kernel`` 17 or 18: "mxfp6"
     activations and / or "mxfp6" output too); None where the q/k-norm epilogue declines the shape."""
     lib = _hip.load()
     c, d, keep, epi = _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, gate_split,
-                               gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan=True)
+                               gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan=True,
+                               bias_rowscale=bias_rowscale)
     p = _hip.GemmPlan()
     rc = lib.bya_gemm_mx_call_plan(ctypes.byref(c), ctypes.byref(d), ctypes.byref(p))
     if rc == -4 and epi == "qkn":
@@ -1183,14 +1192,57 @@ def attention_plan_key(plan):
     return plan["variant"] + ("+streamk" if plan["stream_k"] else "") + tail
 
 
-def attn_kv_mix_plan(z, af=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale=1.0):
-    """What ``attn_kv_mix`` would run: {"form" (``KV_MIX_FORMS``), "head_dim", "grid", "row_chunks", "lds_bytes", "big_lds"}."""
+def attn_kv_mix_plan(z, af=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides=None,
+                     scale=1.0, mx_out=None):
+    """What ``attn_kv_mix`` would run: {"form" (``KV_MIX_FORMS``), "head_dim", "grid", "row_chunks", "lds_bytes", "big_lds"}.
+    ``mx_out`` (with ``z`` None): the plan of the MX-output launch (bya_attn_kv_mix_mx_plan; the dict then also has "mx_out":
+    the format); None where the library declines it (more than 32 keys, or the generic reference form)."""
     lib = _hip.load()
-    d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale)
     p = _hip.AttnMixPlan()
-    check(lib.bya_attn_kv_mix_plan(_plan_p(z), _plan_p(af), ctypes.byref(d), ctypes.byref(p)), "bya_attn_kv_mix_plan")
-    return {"form": KV_MIX_FORMS[p.form], "head_dim": p.head_dim, "grid": p.grid, "row_chunks": p.row_chunks,
+    if mx_out is not None:
+        mx = _mix_mx_out(mx_out, z, z_strides, heads, head_dim, n_grp, Sq, plan=True)
+        d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, (0, 0), scale)
+        rc = lib.bya_attn_kv_mix_mx_plan(_plan_p(mx[0]), _plan_p(mx[1]), _plan_p(af), ctypes.byref(d), mx[2], *mx[3], ctypes.byref(p))
+        if rc == -4:
+            return None
+        check(rc, "bya_attn_kv_mix_mx_plan")
+    else:
+        d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale)
+        check(lib.bya_attn_kv_mix_plan(_plan_p(z), _plan_p(af), ctypes.byref(d), ctypes.byref(p)), "bya_attn_kv_mix_plan")
+    plan = {"form": KV_MIX_FORMS[p.form], "head_dim": p.head_dim, "grid": p.grid, "row_chunks": p.row_chunks,
             "lds_bytes": p.lds_bytes, "big_lds": p.big_lds}
+    if mx_out is not None:
+        plan["mx_out"] = mx_out[2]
+    return plan
+
+
+def _mix_mx_out(mx_out, z, z_strides, heads, head_dim, n_grp, Sq, plan=False):
+    """``mx_out`` = (codes, scales, fmt) of ``attn_kv_mix`` -> (codes, scales, format code, (c_grp, c_row, sc_grp, sc_row) in
+    bytes).  The pair holds rows of the [n_grp * Sq, heads * head_dim] mix as ``quantize_mx`` would: uint8, last dimension
+    contiguous and at least heads * head_dim * bits / 8 (codes) / heads * head_dim / 32 (scales) wide.  2-D [n_grp * Sq, width]:
+    groups are stacked rows; 3-D [n_grp, Sq, width]: the strides are the tensor's (views of larger buffers are fine)."""
+    if z is not None or z_strides is not None:
+        raise ValueError("attn_kv_mix: with mx_out there is no bf16 output -- pass z=None and no z_strides")
+    codes, scales, fmt = mx_out
+    code = mx_fmt_code(fmt)                          # "mxfp4" is a weight format: refused here like everywhere for activations
+    strides = []
+    for t, name, width in ((codes, "codes", mx_code_bytes(heads * head_dim, fmt)), (scales, "scales", heads * head_dim // 32)):
+        if t.dtype != torch.uint8:
+            raise TypeError(f"attn_kv_mix: mx_out {name}: expected uint8, got {t.dtype}")
+        if not (t.is_cuda or (plan and t.is_meta)):
+            raise ValueError(f"attn_kv_mix: mx_out {name}: expected a device tensor")
+        ok = t.dim() in (2, 3) and t.stride(-1) == 1 and t.shape[-1] >= width
+        if ok and t.dim() == 2:
+            ok = t.shape[0] >= n_grp * Sq
+            grp, row = Sq * t.stride(0), t.stride(0)
+        elif ok:
+            ok = t.shape[0] >= n_grp and t.shape[1] >= Sq
+            grp, row = t.stride(0), t.stride(1)
+        if not ok:
+            raise ValueError(f"attn_kv_mix: mx_out {name} must be uint8 [{n_grp * Sq}, >= {width}] or [{n_grp}, {Sq}, >= {width}] "
+                             f"with a contiguous last dimension, got {tuple(t.shape)} strides {tuple(t.stride())}")
+        strides += [grp, row]
+    return codes, scales, code, tuple(strides)
 
 
 def attn_tiny_plan(q, k, v, out, L, heads, n_outer, n_inner, ld_qkv, ld_o):
@@ -1269,18 +1321,38 @@ def self_attention(q, k, v, out, heads, head_dim=64, scale=None, tag="other", pr
 
 
 def attn_kv_mix(q, k, v, r, af, z, wsum=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides,
-                z_strides, scale):
+                z_strides=None, scale, mx_out=None):
     """z[g, n] = sum_id w[g n, id] * softmax(q[g, n] . K[id, g]^T * scale) V[id, g]: cross-attention onto <= 64 keys per identity
     with the router's masked combine in its epilogue (bya_attn_kv_mix).  q_strides = (group, row), k / v_strides = (identity,
-    group, row), z_strides = (group, row), in elements; r: bf16 [n_grp * Sq, n_id]; af: None (face) or bf16 [n_id, n_id]."""
+    group, row), z_strides = (group, row), in elements; r: bf16 [n_grp * Sq, n_id]; af: None (face) or bf16 [n_id, n_id].
+    ``mx_out`` = (codes, scales, fmt) with ``z`` None and no ``z_strides``: the mix leaves as MX codes and block scales
+    (bya_attn_kv_mix_mx; layout: ``_mix_mx_out``) -- byte for byte ``quantize_mx(z, fmt)``, z itself never written; returns the
+    pair, the ``quantised=`` operand of the next MX Linear, or False (nothing launched, nothing counted) where the library
+    declines (more than 32 keys, the generic reference form): the caller then issues the two launches."""
     lib = _hip.load()
+    mx = None
+    if mx_out is not None:
+        mx = _mix_mx_out(mx_out, z, z_strides, heads, head_dim, n_grp, Sq)
+        z_strides = (0, 0)
     d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale)
-    for t in (q, k, v, z, r):
+    for t in (q, k, v, r) + (() if mx is not None else (z,)):
         assert t.dtype == torch.bfloat16 and t.is_cuda
     assert r.is_contiguous() and r.numel() == n_grp * Sq * n_id
     assert af is None or (af.is_contiguous() and af.dtype == torch.bfloat16 and af.numel() == n_id * n_id)
     assert wsum is None or (wsum.dtype == torch.float32 and wsum.is_contiguous() and wsum.numel() >= n_grp * Sq)
-    tok = _begin("bya_attn_kv_mix", 4.0 * n_id * n_grp * heads * Sq * Skv * head_dim)
+    flops = 4.0 * n_id * n_grp * heads * Sq * Skv * head_dim
+    if mx is not None:
+        tok = _begin("bya_attn_kv_mix_mx")
+        rc = lib.bya_attn_kv_mix_mx(_p(q), _p(k), _p(v), _p(r), _p(af), _p(mx[0]), _p(mx[1]), _p(wsum), ctypes.byref(d), mx[2],
+                                    *mx[3], _stream())
+        if rc == -4:                   # BYA_ERR_UNSUPPORTED: nothing was launched (the caller's two launches count the FLOPs)
+            return False
+        check(rc, "bya_attn_kv_mix_mx")
+        if tok is not None:
+            _FLOPS[tok[0]] = _FLOPS.get(tok[0], 0.0) + flops
+        _end(tok)
+        return mx[0], mx[1]
+    tok = _begin("bya_attn_kv_mix", flops)
     check(lib.bya_attn_kv_mix(_p(q), _p(k), _p(v), _p(r), _p(af), _p(z), _p(wsum), ctypes.byref(d), _stream()), "bya_attn_kv_mix")
     _end(tok)
     return z

@@ -382,12 +382,16 @@ class BindyouravatarTransformer3DModel(nn.Module):
 
     def enable_mx_weights(self, fmt: str = "mxfp6", enabled: bool = True, linears=None, weight_format=None, *,
                           fuse_activation_quant: bool = True, fuse_attention_quant: bool = False,
-                          fuse_qk_norm: bool = False, persistent_gemm=False, persistent_gemm_mxfp6=False):
+                          fuse_qk_norm: bool = False, persistent_gemm=False, persistent_gemm_mxfp6=False,
+                          fuse_cross_attention_quant: bool = True):
         """Run the selected Linears on OCP MX operands: 32-element blocks along K with one e8m0 scale each, applied by
         gfx950's block-scaled matrix instruction (include/bya.h, "MX weights").  ``fmt``: "mxfp6" (e2m3 elements, the
         instruction's fastest dense rate) or "mxfp8" (e4m3 elements, the more accurate).  Weights are quantised when the
         engine packs them, activations per block on the fly (by the AdaLN LayerNorm itself where it feeds the Linear).
-        ``linears``: as for enable_fp8_weights (a subset of engine.FP8_LINEARS or "all"; default engine.FP8_DEFAULT).
+        ``linears``: as for enable_fp8_weights (a subset of engine.FP8_LINEARS or "all"; default engine.FP8_DEFAULT) -- and, by
+        name only (an explicit tuple or comma list; "all" stays the six kinds), engine.MX_CROSS_OUT = ("po", "ao"): the
+        cross-attention output projections perceiver_cross_attention[*].to_out and audio_model.layers[*].attn.to_out[0], which
+        enable_fp8_weights refuses.  They are in no default.
         ``weight_format``: the weights' element format -- None or ``fmt`` (the same as the activations), or "mxfp4" (e2m1
         elements, 4.25 bits per parameter) under the activations of ``fmt``; no other combination, and "mxfp4" is never an
         activation format.  ``fuse_activation_quant`` (keyword only): when ff.net.0 and ff.net.2 are both MX Linears, the
@@ -412,11 +416,17 @@ class BindyouravatarTransformer3DModel(nn.Module):
         "mxfp4" weights -- every MX Linear launch (q|k|v plain or fused with ``fuse_qk_norm``, to_out, ff.net.0 with its
         quantising epilogue, ff.net.2) goes through bya_gemm_mx_call with kernel = 17 (or 18): the persistent kernel's e2m3
         instances where a launch fills it, the same bits.  Off by default (opt-in: its time against the tiled kernel's is
-        shape by shape, tools/mx_p256_fp6_probe.py); with "mxfp8" activations it does nothing.  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
+        shape by shape, tools/mx_p256_fp6_probe.py); with "mxfp8" activations it does nothing.
+        ``fuse_cross_attention_quant`` (keyword only, a bool): acts only when "po" or "ao" is chosen -- the cross-attention's
+        kv-mix launch (bya_attn_kv_mix_mx) writes that to_out's MX operand from its own epilogue instead of a bf16 tensor that a
+        quantiser launch reads back -- the same bytes, so on by default; False, or a launch the library declines (more than
+        32 keys), keeps the two launches.  Cannot be combined with enable_fp8_weights: the engine build raises ValueError.  No reference
         counterpart (the reference is bf16/fp16 only); returns self."""
         from .ops import MX_FORMATS, MX_WEIGHT_FORMATS
         if not isinstance(fuse_attention_quant, bool):
             raise TypeError(f"fuse_attention_quant: expected a bool, got {type(fuse_attention_quant).__name__}")
+        if not isinstance(fuse_cross_attention_quant, bool):
+            raise TypeError(f"fuse_cross_attention_quant: expected a bool, got {type(fuse_cross_attention_quant).__name__}")
         if not isinstance(fuse_qk_norm, bool):
             raise TypeError(f"fuse_qk_norm: expected a bool, got {type(fuse_qk_norm).__name__}")
         if persistent_gemm not in (False, True, "always"):
@@ -435,6 +445,11 @@ class BindyouravatarTransformer3DModel(nn.Module):
         self._mx_fuse_activation_quant = bool(fuse_activation_quant)
         self._mx_fuse_attention_quant = fuse_attention_quant
         self._mx_fuse_qk_norm = fuse_qk_norm
+        # (set only when off -- absent means on: a call without the keyword sets the attributes it always set)
+        if enabled and not fuse_cross_attention_quant:
+            self._mx_fuse_cross_attention_quant = False
+        elif hasattr(self, "_mx_fuse_cross_attention_quant"):
+            del self._mx_fuse_cross_attention_quant
         # (set only when on -- absent means off: the attributes a call without the keyword sets are those it always set)
         if enabled and persistent_gemm:
             self._mx_persistent_gemm = persistent_gemm

@@ -637,6 +637,28 @@ typedef struct bya_attn_kv_mix_plan_info {
 } bya_attn_kv_mix_plan_info;
 int bya_attn_kv_mix_plan(const void* z, const void* af, const bya_attn_mix_desc* desc, bya_attn_kv_mix_plan_info* plan);
 
+/* bya_attn_kv_mix followed by bya_quantize_mx(out_fmt) on its [n_grp * Sq, heads * head_dim] output, without the bf16 matrix:
+ * the operand of the cross-attention's output projection as MX codes, written by the <= 32-key form's epilogue.  There the
+ * mixed z passes through the wave's LDS patch and is re-read row-major, 8 consecutive bf16 columns per lane, so a 32-column
+ * MX block of a row is one aligned lane quad: |max| over the quad by cross-lane moves, then the standalone quantiser's
+ * arithmetic on the bf16 value of the patch -- byte for byte what the two launches write (see "MX weights" for the formats).
+ *   codes:  byte (head * head_dim + 32 j) * bits / 8 of a row holds block j of the head (32 bytes as e4m3, 24 as e2m3);
+ *   scales: byte head * head_dim / 32 + j of a row.
+ * Row n of group g starts at  codes + g * c_grp + n * c_row  and  scales + g * sc_grp + n * sc_row  -- strides in BYTES.
+ * Rows >= Sq and bytes outside the heads' code / scale bytes are never written; wsum is written as by bya_attn_kv_mix.
+ * desc is bya_attn_kv_mix's descriptor with z_grp = z_row = 0 (there is no bf16 output; anything else: BYA_ERR_SHAPE).
+ * Refused before any launch: out_fmt other than e4m3 (0) / e2m3 (2), Skv > 32 or reference form BYA_REF_KV_MIX_GENERIC set
+ * (the MX epilogue exists on the BYA_KV_MIX_MIX32 form alone: the caller then issues the two launches) -> BYA_ERR_UNSUPPORTED;
+ * codes or a code stride not a multiple of 4 bytes -> BYA_ERR_ALIGN; c_row < heads * head_dim * bits / 8, sc_row < heads *
+ * head_dim / 32, a negative group stride or anything bya_attn_kv_mix refuses -> BYA_ERR_SHAPE.  bya_attn_kv_mix_mx_plan
+ * answers with bya_attn_kv_mix_plan's struct: the same grid, row chunks and LDS rule as the bf16 launch (form = MIX32). */
+int bya_attn_kv_mix_mx(const void* q, const void* k, const void* v, const void* r, const void* af, void* codes, void* scales,
+                       float* wsum, const bya_attn_mix_desc* desc, int32_t out_fmt, int64_t c_grp, int64_t c_row,
+                       int64_t sc_grp, int64_t sc_row, hipStream_t stream);
+int bya_attn_kv_mix_mx_plan(const void* codes, const void* scales, const void* af, const bya_attn_mix_desc* desc,
+                            int32_t out_fmt, int64_t c_grp, int64_t c_row, int64_t sc_grp, int64_t sc_row,
+                            bya_attn_kv_mix_plan_info* plan);
+
 /* Tiny-sequence self-attention (sequence length L <= 16, head_dim 64) used by the router's temporal
  * (L = frames) and multi-ID (L = ids) attentions (models/router.py:482,488).  Element e of sequence
  * `g` lives at row  g_outer(g)*outer_stride + e*seq_stride + g_inner(g)  of the [rows, ld] matrices,
