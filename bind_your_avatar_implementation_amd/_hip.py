@@ -120,6 +120,9 @@ SIGNATURES = {
     "bya_quantize_rows_fp8": [_vp, _vp, _vp, _i32, _i32, _i64, _i64, _vp],
     "bya_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _vp],
     "bya_gemm_fp8_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(GemmPlan)],
+    "bya_gemm_fp8_qkv_norm_rope": [_vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _vp],
+    "bya_gemm_fp8_qkv_norm_rope_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc),
+                                        _c.POINTER(GemmPlan)],
     "bya_layernorm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
                           _f32, _vp],
     "bya_quantize_mx": [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp],

@@ -244,6 +244,35 @@ int gemm_row_chunks(const GemmArgs& a, int batch, int a_elem_bytes, F&& run) {
         }
     return BYA_OK;
 }
+// ---- host side: the q/k-norm epilogue's arguments on the tiled / wide kernels that decide q, k or v per 64-column head
+// (bya_gemm_mx_qkv_norm_rope, bya_gemm_fp8_qkv_norm_rope).  Two steps around the operand family's own argument function:
+// qkn_norm_desc_check before it (a malformed norm descriptor: BYA_ERR_SHAPE), qkn_head_args behind it -- BYA_ERR_UNSUPPORTED:
+// not this epilogue's shape (the caller keeps its GEMM + bya_qknorm_rope), BYA_ERR_ALIGN, else GemmArgs::qkn_* filled.
+inline int qkn_norm_desc_check(const bya_gemm_desc* d, const bya_qknorm_desc* n) {
+    if (!d || !n) return BYA_ERR_SHAPE;
+    if (!n->qw || !n->qb || !n->kw || !n->kb || n->width <= 0 || n->text_rows < 0) return BYA_ERR_SHAPE;
+    if (d->M > 0 && n->text_rows < d->M && (!n->cos || !n->sin)) return BYA_ERR_SHAPE;
+    return BYA_OK;
+}
+
+inline int qkn_head_args(const void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n, GemmArgs* out) {
+    if ((d->N != 3 * n->width && d->N != 2 * n->width) || n->width % 64 != 0 || d->n_split <= 0 || d->act != 0 ||
+        d->bias_rowscale || (d->alpha != 0.0f && d->alpha != 1.0f))
+        return BYA_ERR_UNSUPPORTED;
+    // eight consecutive columns leave as one 16-byte store
+    if (d->n_split % 8 || d->c_split_stride % 8 || d->ldc % 8 || d->c_batch_stride % 8) return BYA_ERR_ALIGN;
+    if (((uintptr_t)C | (uintptr_t)n->qw | (uintptr_t)n->qb | (uintptr_t)n->kw | (uintptr_t)n->kb | (uintptr_t)n->cos |
+         (uintptr_t)n->sin) & 15) return BYA_ERR_ALIGN;
+    GemmArgs& a = *out;
+    a.act = 0; a.alpha = 1.0f; a.bias_rowscale = nullptr;
+    a.qkn_w[0] = (const bf16_t*)n->qw; a.qkn_b[0] = (const bf16_t*)n->qb; a.qkn_w[1] = (const bf16_t*)n->kw; a.qkn_b[1] = (const bf16_t*)n->kb;
+    a.qkn_cos = n->cos; a.qkn_sin = n->sin; a.qkn_text_rows = n->text_rows; a.qkn_width = n->width;
+    a.qkn_eps = n->eps; a.qkn_kscale = n->k_scale == 0.0f ? 1.0f : n->k_scale;
+    // one launch: its rows and its rotary rows within the 2 GiB reach of the buffer descriptors
+    if (!gemm_rows_reachable(a, a.M) || ((long long)a.M - a.qkn_text_rows) * 256 >= 0x7fffffffLL) return BYA_ERR_UNSUPPORTED;
+    return BYA_OK;
+}
+
 // Persistent kernels: group-M width of the tile order, in 256-row tiles, by shape: a long K sweep wants few row tiles per group
 // (the W panel of a column tile is re-read by fewer row tiles, but each stays in flight longer), wide outputs want more
 // (same-box sweep: tools/gemm_gm_probe.py, profiles/r6_k_gemm_gm_probe.json)

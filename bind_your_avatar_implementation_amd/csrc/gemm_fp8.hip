@@ -16,6 +16,8 @@
 
 bool bya_gemm256p_fp8_eligible(const void* args);                                                       // gemm_fp8_v4.hip
 int bya_launch_gemm256p_fp8(const void* args, const float* sa, const float* sw, int batch, int gm, hipStream_t s);
+// ... its q/k-norm instance (gemm_fp8_v4_qkn.hip; GemmArgs::qkn_* filled)
+int bya_launch_gemm256p_fp8_qkn(const void* args, const float* sa, const float* sw, int batch, int gm, hipStream_t s);
 
 namespace {
 
@@ -114,6 +116,7 @@ inline int fp8_path(const GemmArgs& a, int batch, const GemmArgs& piece) {
     const bool big = !bya_opt(BYA_OPT_FP8_KERNEL) && tiles256 >= 200;        // (about a round of its 256 workgroups, or more)
     return big && bya_gemm256p_fp8_eligible(&piece) ? BYA_GEMM_PATH_P256 : BYA_GEMM_PATH_T128X128;
 }
+constexpr int FP8_P256_GROUP_M = 4;        // row-tiles per group of the persistent kernel's tile order
 }  // namespace
 
 extern "C" int bya_gemm_fp8(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias,
@@ -122,7 +125,7 @@ extern "C" int bya_gemm_fp8(const void* A8, const float* a_scale, const void* W8
     GemmArgs a;
     const int rc = fp8_args(A8, a_scale, W8, w_scale, bias, C, res, gate0, gate1, d, &a);
     if (rc != BYA_OK) return rc;
-    const int gm = 4;                                                 // row-tiles per group of the persistent kernel's tile order
+    const int gm = FP8_P256_GROUP_M;
     return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
         if (fp8_path(a, d->batch, piece) == BYA_GEMM_PATH_P256)
             return bya_launch_gemm256p_fp8(&piece, a_scale + row0, w_scale, batch, gm, stream);
@@ -143,4 +146,53 @@ extern "C" int bya_gemm_fp8_plan(const void* A8, const float* a_scale, const voi
     p->path = fp8_path(a, d->batch, piece);
     p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = chunks;
     return BYA_OK;
+}
+
+namespace {
+// bya_gemm_fp8_qkv_norm_rope's arguments -> GemmArgs; BYA_ERR_UNSUPPORTED: not this epilogue's shape (the caller keeps
+// bya_gemm_fp8 + bya_qknorm_rope); malformed arguments: the errors of fp8_args and of the norm descriptor (gemm_common.h)
+int fp8_qkn_args(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias, const void* C,
+                 const bya_gemm_desc* d, const bya_qknorm_desc* n, GemmArgs* out) {
+    const int rc0 = qkn_norm_desc_check(d, n);
+    if (rc0 != BYA_OK) return rc0;
+    const int rc = fp8_args(A8, a_scale, W8, w_scale, bias, C, nullptr, nullptr, nullptr, d, out);
+    if (rc != BYA_OK) return rc;
+    // there is no residual argument: a descriptor that describes one is not this entry point's launch
+    if (d->ldres != 0 || d->res_batch_stride != 0) return BYA_ERR_UNSUPPORTED;
+    return qkn_head_args(C, d, n, out);
+}
+
+// the launch (plan == nullptr) and its plan query: one body, so the query answers what the launch does
+int fp8_qkn(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias, const void* C,
+            const bya_gemm_desc* d, const bya_qknorm_desc* n, hipStream_t stream, bya_gemm_plan* plan) {
+    GemmArgs a;
+    const int rc = fp8_qkn_args(A8, a_scale, W8, w_scale, bias, C, d, n, &a);
+    if (rc != BYA_OK) return rc;
+    // bya_gemm_fp8's own choice for this descriptor (one row chunk: qkn_head_args): the two kernels differ in last bits, so
+    // following it is what keeps fused == two launches in every option state
+    const int path = fp8_path(a, d->batch, a);
+    if (plan) {
+        plan->path = path;
+        plan->m0 = 0; plan->tail = -1; plan->split_k = 0; plan->row_chunks = 1;
+        return BYA_OK;
+    }
+    if (path == BYA_GEMM_PATH_P256) return bya_launch_gemm256p_fp8_qkn(&a, a_scale, w_scale, d->batch, FP8_P256_GROUP_M, stream);
+    return launch_fp8<128, 128, 2, 2, true>(a, a_scale, w_scale, d->batch, stream);
+}
+}  // namespace
+
+// bya_gemm_fp8 of the packed q|k|v (or q|k) projection with the per-head q/k LayerNorm(64) + RoPE in its epilogue: bit for bit
+// bya_gemm_fp8(..., n_split) followed by bya_qknorm_rope on the kernel bya_gemm_fp8 would take, q and k written once.  Always
+// one launch.
+extern "C" int bya_gemm_fp8_qkv_norm_rope(const void* A8, const float* a_scale, const void* W8, const float* w_scale,
+                                          const void* bias, void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n,
+                                          hipStream_t stream) {
+    return fp8_qkn(A8, a_scale, W8, w_scale, bias, C, d, n, stream, nullptr);
+}
+
+extern "C" int bya_gemm_fp8_qkv_norm_rope_plan(const void* A8, const float* a_scale, const void* W8, const float* w_scale,
+                                               const void* bias, const void* C, const bya_gemm_desc* d,
+                                               const bya_qknorm_desc* n, bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    return fp8_qkn(A8, a_scale, W8, w_scale, bias, C, d, n, nullptr, p);
 }

@@ -32,7 +32,20 @@
 //
 // Inline-asm MFMAs are invisible to hipcc (gemm_v4.hip explains): every fragment is kept allocated to the end of the K-tile,
 // the epilogue starts behind explicit s_nops, and this unit is compiled WITHOUT -amdgpu-mfma-vgpr-form (accumulators in AGPRs).
+//
+// BYA_F8_QKN (gemm_fp8_v4_qkn.hip compiles this file under it, as a translation unit of its own): the same kernel as
+// gemm256p_fp8_qkn_kernel, whose epilogue is the q/k-norm + RoPE one (bya_gemm_fp8_qkv_norm_rope; epilogue_mx_wide8_qkn with
+// SCALED, gemm_wide_epilogue.h), and its launcher; nothing else of this file is emitted there.
 #include "gemm_wide_epilogue.h"
+
+#ifndef BYA_F8_QKN
+#define BYA_F8_QKN 0
+#endif
+#if BYA_F8_QKN
+#define F8_KERNEL gemm256p_fp8_qkn_kernel
+#else
+#define F8_KERNEL gemm256p_fp8_kernel
+#endif
 
 #ifndef BYA_F8_PLACE
 #define BYA_F8_PLACE 9      // placement of the 16 LDS-DMA pieces inside a K-tile (tools/gen_gemm_fp8_schedule.py holds the tables)
@@ -47,9 +60,8 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BK8 = 128;          // e4m3 elements (= bytes) per K-tile
 
-__global__ __launch_bounds__(256, 1) void gemm256p_fp8_kernel(GemmArgs p, const float* __restrict__ sa,
-                                                             const float* __restrict__ sw, int tiles_m, int tiles_n, int batch,
-                                                             int GM) {
+__global__ __launch_bounds__(256, 1) void F8_KERNEL(GemmArgs p, const float* __restrict__ sa,
+                                                   const float* __restrict__ sw, int tiles_m, int tiles_n, int batch, int GM) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int BM = 256, BN = 256, STAGE = (BM + BN) * BK8, TILE_A = BM * BK8;
     static_assert(STAGE == 65536, "stage flip uses one address bit");
@@ -632,12 +644,17 @@ __global__ __launch_bounds__(256, 1) void gemm256p_fp8_kernel(GemmArgs p, const 
         // pieces of its K-tile 1 have; the MFMAs are inline asm, so pad their last results before the epilogue reads them
         asm volatile("s_waitcnt vmcnt(16)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
 
+#if BYA_F8_QKN
+        // bit for bit the epilogue of the #else branch (alpha = 1, no activation) followed by bya_qknorm_rope
+        epilogue_mx_wide8_qkn<2, true>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc, sa, sw);
+#else
         auto run = [&](auto act_tag) {
             // (wave, lane: the split writer's, unused here -- and naming them would capture them: this kernel then compiles differently)
             epilogue_wide<decltype(act_tag)::value, 2, false, false, 8, false, true>(
                 p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc, 0, 0, nullptr, sa, sw);
         };
         dispatch_act_big(p.act, run);
+#endif
 
         if (!nxt.valid) break;
         ++seq;
@@ -650,6 +667,7 @@ __global__ __launch_bounds__(256, 1) void gemm256p_fp8_kernel(GemmArgs p, const 
 
 }  // namespace
 
+#if !BYA_F8_QKN
 // Is the persistent kernel applicable?  (16-byte epilogue accesses aligned, at least four K-tiles, 16-byte operand rows)
 bool bya_gemm256p_fp8_eligible(const void* args) {
     const GemmArgs& a = *static_cast<const GemmArgs*>(args);
@@ -660,10 +678,15 @@ bool bya_gemm256p_fp8_eligible(const void* args) {
         (long long)a.M * a.lda < (1LL << 32) && (long long)a.N * a.ldw < (1LL << 32);
 }
 
-int bya_launch_gemm256p_fp8(const void* args, const float* sa, const float* sw, int batch, int gm, hipStream_t s) {
+#define F8_LAUNCH bya_launch_gemm256p_fp8
+#else
+// ... with the q/k-norm epilogue: the caller (bya_gemm_fp8_qkv_norm_rope) has filled GemmArgs::qkn_* and checked eligibility
+#define F8_LAUNCH bya_launch_gemm256p_fp8_qkn
+#endif
+int F8_LAUNCH(const void* args, const float* sa, const float* sw, int batch, int gm, hipStream_t s) {
     const GemmArgs& a = *static_cast<const GemmArgs*>(args);
     const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
     const size_t lds = 2 * 512 * BK8;
-    return launch_persistent<gemm256p_fp8_kernel>(persistent_grid((long long)tiles_m * tiles_n * batch), 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch,
+    return launch_persistent<F8_KERNEL>(persistent_grid((long long)tiles_m * tiles_n * batch), 256, lds, s, a, sa, sw, tiles_m, tiles_n, batch,
                                                   gm < 1 ? 1 : gm);
 }

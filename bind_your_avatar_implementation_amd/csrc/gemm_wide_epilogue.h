@@ -232,4 +232,137 @@ __device__ __forceinline__ void epilogue_qkn(const GemmArgs& p, int z, int m_wav
     }
 }
 
+// The q/k-norm epilogue of one wave (bya_gemm_mx_qkv_norm_rope_on): the packed q|k|v projection with the per-head q/k
+// LayerNorm(64) + RoPE of bya_qknorm_rope on its accumulators -- epilogue_qkn (gemm_wide_epilogue.h) on this kernel's
+// accumulators, with q, k or v decided per 64-column HEAD (as epilogue_mx_qkn of gemm_mx.hip does), wave-uniformly:
+// head hh of the wave is registers e = 2 hh, 2 hh + 1, columns n_wave + 64 hh .. + 63, tsel = (n_wave + 64 hh) / width, so
+// width % 64 == 0 is enough and a wave may straddle q | k or k | v.  Bit for bit bya_gemm_mx_mixed(..., n_split) followed by
+// bya_qknorm_rope; arithmetic: qknorm_math.h, whose eight groups g of a head row are 8 consecutive columns each.  The lane
+// (fr, fq) holds columns n_wave + 64 hh + (4 el + fq) * 8 + i of row 16 j + fr in acc[i][j][2 hh + el]: group g = 4 el + fq.
+// What is normalised is bf16(acc + bias), the value the two-launch path stored and read back (one rounding: pack, unpack);
+// qkn_sum8 / qkn_centre_sq8 run over the lane's eight values in column order = one whole group; the tree (g ^ 1), (g ^ 2),
+// (g ^ 4) is lane ^ 16 (v_permlane16_swap), lane ^ 32 (v_permlane32_swap), then the lane's own two registers (s_e0 + s_e1):
+// the same operands per addition as the stand-alone kernel (an addition does not depend on the order of its two operands),
+// in the same order.  qkn_finish8 is element-wise and the RoPE pairs (2 i, 2 i + 1) lie inside the lane's eight columns.
+// v heads and heads past N take the plain bias epilogue: acc + bias rounded to bf16, epilogue_block's value for alpha = 1
+// and no activation.  Rotary rows come through buffer descriptors: rows that are not rotated read zeros from an
+// out-of-range offset, no per-row branch.  16-byte stores through the C descriptor with the n_split / c_split_stride column
+// map; rows past M and columns past N write nothing.
+// Rows outside, heads inside: the rotary row of a token is the same for both heads of the wave, so it is fetched once per
+// row block; the two heads' bias and LayerNorm parameters (q's and k's may differ between a wave's two heads) stay PACKED,
+// 52 registers, and are unpacked where they are used.  The accumulators of a burst of JB row blocks are pinned in their
+// AGPRs until the burst is due (epilogue_wide's PIN) and a scheduling barrier keeps a burst's table loads inside it: 201
+// VGPRs + 256 AGPRs, no scratch.  (Heads outside with the pin inside the q/k | v branch made every accumulator a phi of two
+// AGPR copies: 205 registers of scratch.)
+// SCALED (gemm_fp8_v4.hip's QKN instance, bya_gemm_fp8_qkv_norm_rope): the accumulator is first multiplied by its
+// activation-row x weight-channel scale, sa[batch * M] x sw[N], the product of the two scales formed first -- epilogue_wide's
+// SCALED expression -- and that product is rounded to fp32 before the bias is added, as the two-launch path's fmaf(1, bias,
+// scaled) does: an empty asm that owns the register keeps hipcc's default -ffp-contract from merging the multiply and the
+// addition into one fma(acc, scale, bias), which rounds once less.  The eight channel scales of each of the lane's four column
+// groups stay in 32 registers for the whole tile.
+template <int JB, bool SCALED = false>
+__device__ __forceinline__ void epilogue_mx_wide8_qkn(const GemmArgs& p, int z, int m_wave, int n_wave, int fr, int fq,
+                                                      f32x4 (&acc)[8][8], const float* __restrict__ sa = nullptr,
+                                                      const float* __restrict__ sw = nullptr) {
+    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(p.C + (long long)z * p.c_bs), 0, 0x7fffffff, 0x00020000);
+    const QknRotary rot = qkn_rotary<false>(p);                    // (the launcher keeps the tables below 2 GiB)
+    const bool has_bias = p.bias != nullptr;
+    // per head: q / k / v, bias, column map and (q, k) the LayerNorm parameters of this lane's columns, all packed
+    int tsel[2];
+    u32x4 bv[2][2], wq[2][2], bq[2][2];
+    uint32_t colb[2][2];
+    bool nok[2][2];
+    f32x4 wsc[2][2][2];                                             // SCALED: the eight channel scales of each column group
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+        const int n_head = n_wave + 64 * hh;
+        tsel[hh] = n_head / p.qkn_width;                            // 0 = q, 1 = k, else v or past N: wave-uniform
+#pragma unroll
+        for (int el = 0; el < 2; ++el) {
+            const int n8 = n_head + (4 * el + fq) * 8;
+            nok[hh][el] = n8 < p.N;
+            colb[hh][el] = ((uint32_t)(n8 / p.n_split) * (uint32_t)p.c_split_stride + (uint32_t)(n8 % p.n_split)) * 2u;
+            bv[hh][el] = has_bias ? *reinterpret_cast<const u32x4*>(p.bias + (nok[hh][el] ? n8 : 0)) : u32x4{0u, 0u, 0u, 0u};
+            const bf16_t* const lw = tsel[hh] == 1 ? p.qkn_w[1] : p.qkn_w[0];       // (v heads load q's and do not use them)
+            const bf16_t* const lb = tsel[hh] == 1 ? p.qkn_b[1] : p.qkn_b[0];
+            wq[hh][el] = *reinterpret_cast<const u32x4*>(lw + (4 * el + fq) * 8);
+            bq[hh][el] = *reinterpret_cast<const u32x4*>(lb + (4 * el + fq) * 8);
+            if constexpr (SCALED) {
+                wsc[hh][el][0] = *reinterpret_cast<const f32x4*>(sw + (nok[hh][el] ? n8 : 0));
+                wsc[hh][el][1] = *reinterpret_cast<const f32x4*>(sw + (nok[hh][el] ? n8 : 0) + 4);
+            }
+        }
+    }
+    const bool any_qk = tsel[0] < 2;                                // (tsel ascends: a q or k head, if any, is head 0)
+#pragma unroll
+    for (int jb = 0; jb < 8; jb += JB) {
+        __builtin_amdgcn_sched_barrier(0);                          // a burst's table loads stay inside the burst
+#pragma unroll
+        for (int jj = 0; jj < JB; ++jj)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) asm volatile("" : "+a"(acc[i][jb + jj]));
+#pragma unroll
+        for (int jj = 0; jj < JB; ++jj) {
+            const int j = jb + jj;
+            const int m = m_wave + 16 * j + fr;
+            const bool mok = m < p.M;
+            const uint32_t coff = (mok ? (uint32_t)m : 0u) * (uint32_t)(p.ldc * 2);
+            const bool rope = any_qk && mok && m >= p.qkn_text_rows;
+            const uint32_t t0 = (uint32_t)(m - p.qkn_text_rows) * 256u;
+            float ra = 1.0f;
+            if constexpr (SCALED) ra = sa[(long long)z * p.M + (mok ? m : 0)];
+            QknRotary8 cs[2];                                       // the rotary row: the same columns of both heads
+#pragma unroll
+            for (int el = 0; el < 2; ++el) {
+                const uint32_t o0 = rope ? t0 + (uint32_t)((4 * el + fq) * 32) : 0xffffffffu;
+                const uint32_t o1 = rope ? o0 + 16u : 0xffffffffu;
+                cs[el] = qkn_rotary_load8(rot, o0, o1);
+            }
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                float v[2][8];
+#pragma unroll
+                for (int el = 0; el < 2; ++el) {
+                    float b8[8];
+                    unpack8(bv[hh][el], b8);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        if constexpr (SCALED) {
+                            float s = acc[i][j][2 * hh + el] * (ra * wsc[hh][el][i >> 2][i & 3]);      // row x channel scale
+                            asm("" : "+v"(s));                      // (rounded here: no fma with the bias)
+                            v[el][i] = s + b8[i];
+                        } else {
+                            v[el][i] = acc[i][j][2 * hh + el] + b8[i];
+                        }
+                    }
+                }
+                if (tsel[hh] < 2) {
+                    const float ks = tsel[hh] == 1 ? p.qkn_kscale : 1.0f;
+                    // the projection as the two-launch path stored it: one rounding to bf16
+#pragma unroll
+                    for (int el = 0; el < 2; ++el) {
+                        const u32x4 r = pack8(v[el]);
+                        unpack8(r, v[el]);
+                    }
+                    const float s0 = lane_add32(lane_add16(qkn_sum8(v[0]))), s1 = lane_add32(lane_add16(qkn_sum8(v[1])));
+                    const float mean = (s0 + s1) * (1.0f / 64);
+                    const float q0 = lane_add32(lane_add16(qkn_centre_sq8(v[0], mean))), q1 = lane_add32(lane_add16(qkn_centre_sq8(v[1], mean)));
+                    const float rstd = rsqrtf((q0 + q1) * (1.0f / 64) + p.qkn_eps);
+#pragma unroll
+                    for (int el = 0; el < 2; ++el) {
+                        float w8[8], b8[8];
+                        unpack8(wq[hh][el], w8);
+                        unpack8(bq[hh][el], b8);
+                        qkn_finish8(v[el], rstd, w8, b8, rope, cs[el].c, cs[el].s, ks);
+                    }
+                }
+#pragma unroll
+                for (int el = 0; el < 2; ++el)
+                    __builtin_amdgcn_raw_buffer_store_b128(pack8(v[el]), rsC, (mok && nok[hh][el]) ? coff + colb[hh][el] : 0xffffffffu, 0, 0);
+            }
+        }
+    }
+}
+
 }  // namespace

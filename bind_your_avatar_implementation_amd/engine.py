@@ -129,6 +129,10 @@ class DenoiseEngine:
         # pack time, per-row activation scales on the fly; fp32 accumulation, bf16 everywhere else)
         self.fp8_weights = bool(getattr(model, "_fp8_weights", False)) or os.environ.get("BYA_FP8_WEIGHTS") == "1"
         self.fuse_ln_quant = os.environ.get("BYA_FP8_FUSED_LN", "1") != "0"     # AdaLN LayerNorm writes e4m3 directly
+        # ... and the q|k|v projection norms and rotates q and k in its own epilogue (bya_gemm_fp8_qkv_norm_rope: bit for bit the
+        # GEMM + bya_qknorm_rope, on the kernel the GEMM would take) when "qkv" is an fp8 Linear;
+        # enable_fp8_weights(fuse_qk_norm=True), off by default
+        self.fp8_fuse_qk_norm = self.fp8_weights and bool(getattr(model, "_fp8_fuse_qk_norm", False))
         # MX weights (enable_mx_weights; API only): the selected Linears on OCP MX operands ("mxfp6" / "mxfp8", 32-element
         # blocks with e8m0 scales, quantised by the instruction's own block scales -- include/bya.h, "MX weights")
         self.mx_fmt = getattr(model, "_mx_weights", None)
@@ -370,8 +374,8 @@ class DenoiseEngine:
 
     def _qkv_norm_rope(self, i, at, xn, out, split, xq, cos, sin, text_rows, heads, q_view, k_view, stats):
         """Block ``i``'s packed q|k|v projection + q/k LayerNorm + RoPE (models/transformer.py:200-209, 241-245): ONE launch
-        with the norm in the GEMM's epilogue where the library takes it (bf16 weights, or MX weights behind the LayerNorm-fused
-        quantiser with ``fuse_qk_norm``; no statistics wanted), else the projection and ``bya_qknorm_rope`` on its output -- the
+        with the norm in the GEMM's epilogue where the library takes it (bf16 weights, or MX / fp8 weights behind the
+        LayerNorm-fused quantiser with their ``fuse_qk_norm``; no statistics wanted), else the projection and ``bya_qknorm_rope`` on its output -- the
         same bits either way."""
         fused = self.qkn_epilogue and stats is None and not self._quantised("qkv") and xq is None
         if fused and ops.gemm_qkv_norm_rope(xn, self.qkv_w[i], out, self.qkv_b[i], split, at.norm_q.weight, at.norm_q.bias,
@@ -390,6 +394,12 @@ class DenoiseEngine:
                                          at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin, text_rows,
                                          eps=at.norm_q.eps, k_scale=self.k_scale, fmt=self.mx_fmt, w_fmt=self.mx_wfmt,
                                          kernel=self.mx_kernel):
+                return
+        if self.fp8_fuse_qk_norm and stats is None and xq is not None and self.w8 is not None and "qkv" in self.w8:
+            w8, sw = self.w8["qkv"][i]
+            if ops.gemm_fp8_qkv_norm_rope(xq[0].view(*xn.shape), xq[1].view(*xn.shape[:-1]), w8, sw, out, self.qkv_b[i], split,
+                                          at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin,
+                                          text_rows, eps=at.norm_q.eps, k_scale=self.k_scale):
                 return
         self._dit_linear("qkv", i, xn, self.qkv_w[i], out, bias=self.qkv_b[i], split=split, quantised=xq)
         ops.qknorm_rope(q_view, k_view, at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin,

@@ -593,6 +593,66 @@ def gemm_fp8_plan(a8, a_scale, w8, w_scale, out, bias=None, res=None, gate0=None
     return _plan_dict(p)
 
 
+def _fp8_qkn_descs(a8, a_scale, w8, w_scale, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors, act=None,
+                   res=None, alpha=1.0, plan=False):
+    if tensors not in (2, 3) or w8.shape[0] % tensors or split is None:
+        raise ValueError("gemm_fp8_qkv_norm_rope: w8 [3 * width, K] (or [2 * width, K]: q | k alone, tensors=2), "
+                         "out = the first of the split outputs, split = (n_split, c_split_stride)")
+    d = _fp8_desc(a8, a_scale, w8, w_scale, out, None, 0, 0, act, split, alpha, plan=plan)
+    if res is not None:                 # (the entry point has no residual argument: the descriptor says so and it declines)
+        d.ldres, d.res_batch_stride = res.stride(-2), (res.stride(0) if res.dim() == 3 else 0)
+    n = _hip.QkNormDesc()
+    ptr = _plan_p if plan else _p
+    n.qw, n.qb, n.kw, n.kb, n.cos, n.sin = ptr(qw), ptr(qb), ptr(kw), ptr(kb), ptr(cos), ptr(sin)
+    n.text_rows, n.width, n.eps, n.k_scale = int(text_rows), d.N // tensors, float(eps), float(k_scale)
+    if cos is not None:
+        assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
+        assert cos.shape == (d.M - text_rows, 64)
+    return d, n
+
+
+def gemm_fp8_qkv_norm_rope(a8, a_scale, w8, w_scale, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6,
+                           k_scale=1.0, tensors=3, *, act=None, res=None):
+    """The packed q|k|v projection on e4m3 operands with the q/k LayerNorm(64) + RoPE in its epilogue
+    (bya_gemm_fp8_qkv_norm_rope): equals ``gemm_fp8(..., split=split)`` followed by ``qknorm_rope`` bit for bit, in one launch
+    on the kernel ``gemm_fp8`` would take (``gemm_fp8_plan``'s path, option ``fp8_kernel`` included).  Returns False (nothing
+    launched, nothing counted) when the library does not take the shape -- the caller then issues the two launches.
+    ``act`` / ``res`` (keyword only): what the engine never asks of this launch, here so that a caller that does is told False."""
+    lib = _hip.load()
+    d, n = _fp8_qkn_descs(a8, a_scale, w8, w_scale, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors,
+                          act=act, res=res)
+    ab, M, N, K = d.batch, d.M, d.N, d.K
+    name = "bya_gemm_fp8_qkv_norm_rope"
+    if _SHAPE_LABELS:
+        name += f":{ab}x{M}x{N}x{K}"
+    tok = _begin(name)
+    rc = lib.bya_gemm_fp8_qkv_norm_rope(_p(a8), _p(a_scale), _p(w8), _p(w_scale), _p(bias), _p(out), ctypes.byref(d),
+                                        ctypes.byref(n), _stream())
+    if rc == -4:                       # BYA_ERR_UNSUPPORTED: nothing was launched (the caller's gemm_fp8 counts the FLOPs)
+        return False
+    check(rc, "bya_gemm_fp8_qkv_norm_rope")
+    if tok is not None:
+        _FLOPS[tok[0]] = _FLOPS.get(tok[0], 0.0) + 2.0 * ab * M * N * K
+    _end(tok)
+    return True
+
+
+def gemm_fp8_qkv_norm_rope_plan(a8, a_scale, w8, w_scale, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6,
+                                k_scale=1.0, tensors=3, *, act=None, res=None, alpha=1.0):
+    """What ``gemm_fp8_qkv_norm_rope`` would run (``gemm_plan``'s dict): path "t128x128" or "p256", one row chunk; None where
+    it declines the shape (the caller's two launches).  ``act`` / ``res`` / ``alpha``: descriptor fields the launch wrapper's
+    callers never set, here to ask what the library answers to them."""
+    lib = _hip.load()
+    d, n = _fp8_qkn_descs(a8, a_scale, w8, w_scale, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors,
+                          act=act, res=res, alpha=alpha, plan=True)
+    p, q = _hip.GemmPlan(), _plan_p
+    rc = lib.bya_gemm_fp8_qkv_norm_rope_plan(q(a8), q(a_scale), q(w8), q(w_scale), q(bias), q(out), ctypes.byref(d),
+                                             ctypes.byref(n), ctypes.byref(p))
+    if rc == -4:
+        return None
+    check(rc, "bya_gemm_fp8_qkv_norm_rope_plan")
+    return _plan_dict(p)
+
 
 # OCP MX element formats (include/bya.h, "MX weights"): name -> the matrix instruction's format code, element bits.
 # MX_FORMATS: what activations (and weights) may be; MX_WEIGHT_FORMATS: what weights may be -- e2m1 is theirs alone

@@ -368,15 +368,26 @@ class BindyouravatarTransformer3DModel(nn.Module):
         self._pending_lora = []
         return n
 
-    def enable_fp8_weights(self, enabled: bool = True, linears=None):
+    def enable_fp8_weights(self, enabled: bool = True, linears=None, *, fuse_qk_norm: bool = False):
         """BASELINE configs[4]: run attn1.to_q|k|v / to_out and the MLP of every DiT block on OCP e4m3 operands (weights
         quantised per output channel when the engine packs them, activations per row on the fly; everything else stays
         bf16).  ``linears``: which of engine.FP8_LINEARS ("qkv", "out", "ff1", "ff2", "pq", "aq") to quantise, a subset or "all";
         default engine.FP8_DEFAULT = the four DiT Linears -- the perceiver / audio query projections stay bf16 because the
-        routing amplifies their error (tools/fp8_error_by_linear.py measures what each costs).  No reference counterpart (the
+        routing amplifies their error (tools/fp8_error_by_linear.py measures what each costs).
+        ``fuse_qk_norm`` (keyword only, a bool): when attn1.to_q|k|v is an fp8 Linear fed by the LayerNorm-fused quantiser, its
+        GEMM norms and rotates q and k in its own epilogue (bya_gemm_fp8_qkv_norm_rope, on the kernel the plain launch would
+        take) instead of writing them in bf16 for a bya_qknorm_rope launch to read and rewrite -- the same bits; off by default
+        (opt-in; a layer whose attention wants the norm statistics keeps the two launches).  No reference counterpart (the
         reference is bf16/fp16 only); returns self."""
+        if not isinstance(fuse_qk_norm, bool):
+            raise TypeError(f"fuse_qk_norm: expected a bool, got {type(fuse_qk_norm).__name__}")
         self._fp8_weights = bool(enabled)
         self._fp8_linears = (linears if isinstance(linears, str) else tuple(linears)) if linears else None
+        # (set only when on -- absent means off: a call without the keyword sets the attributes it always set)
+        if enabled and fuse_qk_norm:
+            self._fp8_fuse_qk_norm = True
+        elif hasattr(self, "_fp8_fuse_qk_norm"):
+            del self._fp8_fuse_qk_norm
         self.invalidate_engine()
         return self
 

@@ -218,6 +218,31 @@ int bya_gemm_fp8(const void* A8, const float* a_scale, const void* W8, const flo
 int bya_gemm_fp8_plan(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias,
                       const void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* desc,
                       bya_gemm_plan* plan);
+/* bya_gemm_fp8_qkv_norm_rope:  bya_gemm_fp8 of the packed q|k|v projection WITH the per-head q/k LayerNorm(64) + RoPE of
+ *   bya_qknorm_rope in its epilogue (bya_gemm_qkv_norm_rope's counterpart on e4m3 operands): bit for bit bya_gemm_fp8(...,
+ *   n_split) followed by bya_qknorm_rope -- per element a_scale[m] * w_scale[n] is formed first and multiplies the accumulator,
+ *   the bias is added to that fp32 product (no fused multiply-add across the two), the sum is rounded to bf16 ONCE (the value
+ *   the two-launch path stored and read back), and q and k are normalised from it with the arithmetic of csrc/qknorm_math.h and
+ *   written once; v columns take the plain bias epilogue.  The two descriptors mean what they mean for bya_gemm_qkv_norm_rope:
+ *   N = 3 width (q | k | v) or 2 width (q | k alone), n_split > 0 with c_split_stride (n_split = width, or a column block
+ *   n_split < width), text_rows, cos / sin [M - text_rows, 64] fp32, k_scale (0 is read as 1), batch (the rotary row index
+ *   restarts per batch entry).  q, k or v is decided per 64-column head, so width % 64 == 0 is enough (a tile may straddle
+ *   q | k).  Always ONE launch, on the kernel bya_gemm_fp8 would choose for the same descriptor (option BYA_OPT_FP8_KERNEL, at
+ *   least 200 tiles of 256 x 256, eligibility: bya_gemm_fp8_plan's rule) -- the two fp8 kernels differ in last bits, so the
+ *   path is never swapped.  The norm statistics of bya_qknorm_rope are not offered.  BYA_ERR_UNSUPPORTED, nothing launched (the
+ *   caller keeps the two launches): an activation, bias_rowscale, alpha other than 0 / 1, n_split == 0, width % 64, N neither
+ *   2 nor 3 widths, a descriptor that describes a residual (ldres or res_batch_stride != 0: there are no residual / gate
+ *   arguments), rows or rotary rows beyond the 2 GiB reach of one launch's buffer descriptors.  n_split, c_split_stride, ldc,
+ *   c_batch_stride % 8 == 0 and C, the four norm vectors, cos and sin 16-byte aligned (BYA_ERR_ALIGN); otherwise the checks of
+ *   bya_gemm_fp8 and of bya_gemm_qkv_norm_rope's norm descriptor (BYA_ERR_SHAPE; cos / sin may be null when every row is
+ *   text).  Every check runs before any launch (and without a GPU); a refused plan query leaves *plan untouched. */
+int bya_gemm_fp8_qkv_norm_rope(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias,
+                               void* C, const bya_gemm_desc* desc, const bya_qknorm_desc* norm, hipStream_t stream);
+/* its kernel: path T128X128 or P256 (bya_gemm_fp8_plan's answer for the same descriptor), row_chunks 1, no split;
+ * BYA_ERR_UNSUPPORTED where the entry point declines the shape */
+int bya_gemm_fp8_qkv_norm_rope_plan(const void* A8, const float* a_scale, const void* W8, const float* w_scale,
+                                    const void* bias, const void* C, const bya_gemm_desc* desc, const bya_qknorm_desc* norm,
+                                    bya_gemm_plan* plan);
 /* bya_layernorm_fp8: bya_layernorm (same arguments, same arithmetic) followed by bya_quantize_rows_fp8 of each output row,
  * in one pass: the normalised + modulated row is rounded to bf16 exactly as bya_layernorm would store it, then quantised --
  * byte for byte what the two launches produce, without the bf16 round trip.  q uint8 [batch][rows][D] (row stride ldq,
