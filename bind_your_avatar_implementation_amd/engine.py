@@ -377,33 +377,22 @@ class DenoiseEngine:
         with the norm in the GEMM's epilogue where the library takes it (bf16 weights, or MX / fp8 weights behind the
         LayerNorm-fused quantiser with their ``fuse_qk_norm``; no statistics wanted), else the projection and ``bya_qknorm_rope`` on its output -- the
         same bits either way."""
+        qk = (at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias)
+        ek = dict(eps=at.norm_q.eps, k_scale=self.k_scale)
         fused = self.qkn_epilogue and stats is None and not self._quantised("qkv") and xq is None
-        if fused and ops.gemm_qkv_norm_rope(xn, self.qkv_w[i], out, self.qkv_b[i], split, at.norm_q.weight, at.norm_q.bias,
-                                            at.norm_k.weight, at.norm_k.bias, cos, sin, text_rows, eps=at.norm_q.eps,
-                                            k_scale=self.k_scale):
+        if fused and ops.gemm_qkv_norm_rope(xn, self.qkv_w[i], out, self.qkv_b[i], split, *qk, cos, sin, text_rows, **ek):
             return
         if self.mx_fuse_qk_norm and stats is None and xq is not None and self.wmx is not None and "qkv" in self.wmx:
-            wc, sw = self.wmx["qkv"][i]
-            if self.mx_call_kernel:
-                norm = dict(qw=at.norm_q.weight, qb=at.norm_q.bias, kw=at.norm_k.weight, kb=at.norm_k.bias, cos=cos, sin=sin,
-                            text_rows=text_rows, eps=at.norm_q.eps, k_scale=self.k_scale)
-                if ops.gemm_mx_call(xq[0], xq[1].view(*xn.shape[:-1], -1), wc, sw, out, self.mx_call_kernel, self.mx_fmt,
-                                    self.mx_wfmt, bias=self.qkv_b[i], split=split, norm=norm):
-                    return
-            elif ops.gemm_mx_qkv_norm_rope(xq[0], xq[1].view(*xn.shape[:-1], -1), wc, sw, out, self.qkv_b[i], split,
-                                         at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin, text_rows,
-                                         eps=at.norm_q.eps, k_scale=self.k_scale, fmt=self.mx_fmt, w_fmt=self.mx_wfmt,
-                                         kernel=self.mx_kernel):
+            norm = dict(zip(("qw", "qb", "kw", "kb"), qk), cos=cos, sin=sin, text_rows=text_rows, **ek)
+            if self._mx_linear("qkv", i, xq, xn.shape[:-1], out, norm=norm, bias=self.qkv_b[i], split=split):
                 return
         if self.fp8_fuse_qk_norm and stats is None and xq is not None and self.w8 is not None and "qkv" in self.w8:
             w8, sw = self.w8["qkv"][i]
             if ops.gemm_fp8_qkv_norm_rope(xq[0].view(*xn.shape), xq[1].view(*xn.shape[:-1]), w8, sw, out, self.qkv_b[i], split,
-                                          at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin,
-                                          text_rows, eps=at.norm_q.eps, k_scale=self.k_scale):
+                                          *qk, cos, sin, text_rows, **ek):
                 return
         self._dit_linear("qkv", i, xn, self.qkv_w[i], out, bias=self.qkv_b[i], split=split, quantised=xq)
-        ops.qknorm_rope(q_view, k_view, at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin,
-                        heads=heads, text_rows=text_rows, eps=at.norm_q.eps, k_scale=self.k_scale, stats=stats)
+        ops.qknorm_rope(q_view, k_view, *qk, cos, sin, heads=heads, text_rows=text_rows, stats=stats, **ek)
 
     def _dit_linear(self, which, i, a, w, out, quantised=None, **kw):
         """One of the four big Linears of DiT block ``i`` (models/transformer.py:241-260): the bf16 GEMM, or -- when the
@@ -421,15 +410,29 @@ class DenoiseEngine:
         w8, sw = self.w8[which][i]
         return ops.gemm_fp8(a8.view(*a.shape), sa.view(*a.shape[:-1]), w8, sw, out, **kw)
 
-    def _mx_linear(self, which, i, quantised, lead, out, **kw):
-        """MX Linear ``which`` of layer ``i`` on the (codes, scales) of its [*lead, K] operand: through ops.gemm_mx_call where a
-        persistent switch names its kernel, ops.gemm_mx under option mx_kernel otherwise."""
+    def _mx_linear(self, which, i, quantised, lead, out, out_scales=None, out_fmt=None, norm=None, **kw):
+        """MX Linear ``which`` of layer ``i`` on the (codes, scales) of its [*lead, K] operand, and the one place that chooses
+        between the two MX routes: ops.gemm_mx_call where a persistent switch names its kernel, else the older entry points under
+        option mx_kernel.  The epilogue follows from the arguments as in ops.gemm_mx_call: ``out_scales`` / ``out_fmt`` = the
+        quantising one (``out`` = the output codes), ``norm`` (its dict, eps and k_scale included) = the q/k-norm + RoPE one,
+        which returns False where the library declines the shape; else the bf16 one."""
         codes, sa = quantised
         wc, sw = self.wmx[which][i]
+        sa = sa.view(*lead, -1)
         if self.mx_call_kernel:
-            return ops.gemm_mx_call(codes, sa.view(*lead, -1), wc, sw, out, self.mx_call_kernel, self.mx_fmt, self.mx_wfmt, **kw)
+            if norm is not None:
+                kw["norm"] = norm
+            elif out_scales is not None:
+                kw.update(out_scales=out_scales, out_fmt=out_fmt)
+            return ops.gemm_mx_call(codes, sa, wc, sw, out, self.mx_call_kernel, self.mx_fmt, self.mx_wfmt, **kw)
+        if norm is not None:                 # (its kernel is an argument: option mx_kernel has no say there)
+            return ops.gemm_mx_qkv_norm_rope(codes, sa, wc, sw, out, kw["bias"], kw["split"], norm["qw"], norm["qb"], norm["kw"],
+                                             norm["kb"], norm["cos"], norm["sin"], norm["text_rows"], eps=norm["eps"],
+                                             k_scale=norm["k_scale"], fmt=self.mx_fmt, w_fmt=self.mx_wfmt, kernel=self.mx_kernel)
         with self._mx_kernel_option():
-            return ops.gemm_mx(codes, sa.view(*lead, -1), wc, sw, out, self.mx_fmt, w_fmt=self.mx_wfmt, **kw)
+            if out_scales is not None:
+                return ops.gemm_mx_quant(codes, sa, wc, sw, out, out_scales, self.mx_fmt, w_fmt=self.mx_wfmt, out_fmt=out_fmt, **kw)
+            return ops.gemm_mx(codes, sa, wc, sw, out, self.mx_fmt, w_fmt=self.mx_wfmt, **kw)
 
     def _cross_out(self, which, i, name, shape, mix, w, out, **kw):
         """The kv-mix launches of one cross-attention and its output projection ``which`` ("po" / "ao") of layer ``i``.
@@ -474,15 +477,8 @@ class DenoiseEngine:
         output in the ``_amx`` workspace of ``out_shape`` -- what ``quantize_mx`` of the bf16 output would hold."""
         if quantised is None:
             quantised = ops.quantize_mx(a, self.mx_fmt, *self._amx(a.shape))
-        codes, sa = quantised
-        wc, sw = self.wmx["ff1"][i]
         oc, osc = self._amx(out_shape)
-        if self.mx_call_kernel:
-            return ops.gemm_mx_call(codes, sa.view(*a.shape[:-1], -1), wc, sw, oc, self.mx_call_kernel, self.mx_fmt, self.mx_wfmt,
-                                    out_scales=osc, out_fmt=self.mx_fmt, bias=bias, act="gelu_tanh")
-        with self._mx_kernel_option():
-            return ops.gemm_mx_quant(codes, sa.view(*a.shape[:-1], -1), wc, sw, oc, osc, self.mx_fmt, w_fmt=self.mx_wfmt,
-                                     out_fmt=self.mx_fmt, bias=bias, act="gelu_tanh")
+        return self._mx_linear("ff1", i, quantised, a.shape[:-1], oc, out_scales=osc, out_fmt=self.mx_fmt, bias=bias, act="gelu_tanh")
 
     def _ln_linear(self, which, i, x, xn, norm, w, out, **kw):
         """LayerNorm(x) -> Linear for the perceiver / audio query projections (models/router.py:246-253,

@@ -371,20 +371,22 @@ def attn_workspace_status(device=None):
     return n.value
 
 
-def _gemm_desc(a, w, out, res, gate_split, gate_batch_stride, act, split, bias_rowscale, alpha, plan=False):
-    ab, M, K, a_bs, lda = _mat(a, "a", plan)
-    ob, Mo, N, c_bs, ldc = _mat(out, "out", plan)
-    if split is not None:
-        N = w.shape[0]
-    if w.dim() != 2 or w.shape[1] != K or w.shape[0] != N or w.stride(1) != 1 or w.dtype != torch.bfloat16:
-        raise ValueError(f"w: expected bf16 [{N}, {K}], got {tuple(w.shape)} {w.dtype}")
-    if (ab, M) != (ob, Mo):
-        raise ValueError("a/out row mismatch")
+# ---- the GEMM front end.  Every entry point below is a launch / ``*_plan`` pair over ONE body: an operand reader checks the
+# operands of its format and hands their dimensions to the one descriptor filler (_fill_desc); the body builds the library's
+# argument tuple once, with the pointer function of its mode (_p: launch, _plan_p: query), so the query answers what the launch
+# does by construction; _launch / _plan make the call.
+_UNSUPPORTED = next(rc for rc, name in _hip.ERRORS.items() if name == "BYA_ERR_UNSUPPORTED")
+
+
+def _fill_desc(dims, res, split, epi, plan):
+    """The bya_gemm_desc of one launch.  ``dims`` = (batch, M, N, K, lda, a_batch_stride, ldw, ldc, c_batch_stride) as the
+    operand reader derived them; ``epi`` = (gate_split, gate_batch_stride, act, bias_rowscale, alpha)."""
+    ab, M, N, K, lda, a_bs, ldw, ldc, c_bs = dims
+    gate_split, gate_batch_stride, act, bias_rowscale, alpha = epi
     d = GemmDesc()
     d.M, d.N, d.K, d.batch = M, N, K, ab
-    d.lda, d.ldw, d.ldc = lda, w.stride(0), ldc
+    d.lda, d.ldw, d.ldc = lda, ldw, ldc
     d.a_batch_stride, d.c_batch_stride = a_bs, c_bs
-    d.ldres, d.res_batch_stride = 0, 0
     if res is not None:
         rb, Mr, Nr, r_bs, ldres = _mat(res, "res", plan)
         if (Mr, Nr) != (M, N) or rb not in (1, ab):
@@ -398,10 +400,96 @@ def _gemm_desc(a, w, out, res, gate_split, gate_batch_stride, act, split, bias_r
     return d
 
 
+_NO_EPILOGUE = (0, 0, None, None, 1.0)          # ``epi`` of a launch without gates, activation, row scale or alpha
+_NO_NORM = (None,) * 9                          # the q/k-norm arguments of _qkn_desc, absent (with ``tensors`` 0)
+
+
+def _qkn_desc(d, tensors, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, plan):
+    """The bya_qk_norm_desc of a q|k|v projection with descriptor ``d`` (``tensors`` 0: an empty one)."""
+    n = _hip.QkNormDesc()
+    if not tensors:
+        return n
+    ptr = _plan_p if plan else _p
+    n.qw, n.qb, n.kw, n.kb, n.cos, n.sin = ptr(qw), ptr(qb), ptr(kw), ptr(kb), ptr(cos), ptr(sin)
+    n.text_rows, n.width, n.eps, n.k_scale = int(text_rows), d.N // tensors, float(eps), float(k_scale)
+    if cos is not None:
+        assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
+        assert cos.shape == (d.M - text_rows, 64)
+    return n
+
+
+def _label(d, pre="", act=False, gate0=None, res=None):
+    """The shape label of a GEMM's timer bucket (``enable_kernel_timers(by_shape=True)``): [pre]:BxMxNxK[:epilogue]."""
+    s = f"{pre}:{d.batch}x{d.M}x{d.N}x{d.K}"
+    if act is not False:
+        s += f":{act or 'none'}{'+gate' if gate0 is not None else ''}{'+res' if res is not None else ''}"
+    return s
+
+
+def _launch(bucket, label, work, call, may_decline=False):
+    """Enqueue ``call`` = (entry point, its arguments up to the stream) under timer ``bucket`` (+ ``label`` when shape labels are
+    on) and count its FLOPs there: ``work``, or 2 * batch * M * N * K of the bya_gemm_desc ``work`` (read only with the timers
+    on).  -> True; or False where ``may_decline`` and the library answers BYA_ERR_UNSUPPORTED: nothing was launched, so no
+    timer entry stays and nothing is counted (the caller's other launches count the FLOPs)."""
+    entry, args = call
+    if label:
+        bucket += label
+    tok = _begin(bucket)
+    rc = getattr(_hip.load(), entry)(*args, _stream())
+    if may_decline and rc == _UNSUPPORTED:
+        return False
+    check(rc, entry)
+    if tok is not None:
+        _FLOPS[bucket] += work if isinstance(work, float) else 2.0 * work.batch * work.M * work.N * work.K
+        _end(tok)
+    return True
+
+
+def _plan(call, may_decline=False):
+    """Ask ``<entry point>_plan`` with the arguments of ``call`` (``_launch``): ``gemm_plan``'s dict; None where ``may_decline``
+    and the library answers BYA_ERR_UNSUPPORTED."""
+    entry, args = call
+    p = _hip.GemmPlan()
+    rc = getattr(_hip.load(), entry + "_plan")(*args, ctypes.byref(p))
+    if may_decline and rc == _UNSUPPORTED:
+        return None
+    check(rc, entry + "_plan")
+    return _plan_dict(p)
+
+
+def _gemm_desc(a, w, out, res, split, epi, plan=False):
+    ab, M, K, a_bs, lda = _mat(a, "a", plan)
+    ob, Mo, N, c_bs, ldc = _mat(out, "out", plan)
+    if split is not None:
+        N = w.shape[0]
+    if w.dim() != 2 or w.shape[1] != K or w.shape[0] != N or w.stride(1) != 1 or w.dtype != torch.bfloat16:
+        raise ValueError(f"w: expected bf16 [{N}, {K}], got {tuple(w.shape)} {w.dtype}")
+    if (ab, M) != (ob, Mo):
+        raise ValueError("a/out row mismatch")
+    return _fill_desc((ab, M, N, K, lda, a_bs, w.stride(0), ldc, c_bs), res, split, epi, plan)
+
+
 def _takes_skinny(d, gate0, bias_rowscale, split):
     """ops.gemm sends the launch to the weight-streaming kernel (``weight_streaming``)."""
     return (_WEIGHT_STREAMING and d.M <= 64 and d.N <= 8192 and d.N % 16 == 0 and d.K % 32 == 0 and d.K >= 256 and gate0 is None
             and bias_rowscale is None and split is None and d.a_batch_stride % 8 == 0)
+
+
+def _bf16_bucket(d):
+    # per-kernel timers: Linears over fewer than 1024 rows (the step-invariant conditioning: 32 face tokens, 52 audio windows,
+    # 577 ViT tokens against 2048..49152-wide weights) stream their WEIGHTS and are bound by HBM, not by the matrix cores --
+    # they get their own bucket so that the MFMA roofline of bench.py is taken over the launches it applies to
+    return "bya_gemm_bf16" if d.M >= 1024 else "bya_gemm_bf16_small_m"
+
+
+def _gemm_call(a, w, bias, out, res, gate0, gate1, split, epi, plan):
+    d = _gemm_desc(a, w, out, res, split, epi, plan)                     # (validates first)
+    if a.is_cuda and a.device.index not in _GEMM_WS:                     # (a launch's ``a`` is a device tensor: _mat)
+        ensure_gemm_workspace(a.device)
+    q = _plan_p if plan else _p
+    if _takes_skinny(d, gate0, epi[3], split):                           # (epi[3]: bias_rowscale)
+        return d, ("bya_gemm_skinny_bf16", (q(a), q(w), q(bias), q(out), q(res), ctypes.byref(d)))
+    return d, ("bya_gemm_bf16", (q(a), q(w), q(bias), q(out), q(res), q(gate0), q(gate1), ctypes.byref(d)))
 
 
 def gemm(a, w, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0, gate_batch_stride=0, act=None,
@@ -410,25 +498,8 @@ def gemm(a, w, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0, g
 
     ``split=(n_split, stride)``: ``out`` is the FIRST of N/n_split equally shaped tensors ``stride`` elements apart;
     column n of the product lands in tensor n // n_split (packed q|k|v projection -> three buffers, one launch)."""
-    lib = _hip.load()
-    d = _gemm_desc(a, w, out, res, gate_split, gate_batch_stride, act, split, bias_rowscale, alpha)     # (validates first)
-    if a.device.index not in _GEMM_WS:
-        ensure_gemm_workspace(a.device)
-    ab, M, N, K = d.batch, d.M, d.N, d.K
-    # per-kernel timers: Linears over fewer than 1024 rows (the step-invariant conditioning: 32 face tokens, 52 audio windows,
-    # 577 ViT tokens against 2048..49152-wide weights) stream their WEIGHTS and are bound by HBM, not by the matrix cores --
-    # they get their own bucket so that the MFMA roofline of bench.py is taken over the launches it applies to
-    name = "bya_gemm_bf16" if M >= 1024 else "bya_gemm_bf16_small_m"
-    if _SHAPE_LABELS:
-        name += f":{ab}x{M}x{N}x{K}:{act or 'none'}{'+gate' if gate0 is not None else ''}{'+res' if res is not None else ''}"
-    tok = _begin(name, 2.0 * ab * M * N * K)
-    if _takes_skinny(d, gate0, bias_rowscale, split):
-        check(lib.bya_gemm_skinny_bf16(_p(a), _p(w), _p(bias), _p(out), _p(res), ctypes.byref(d), _stream()),
-              "bya_gemm_skinny_bf16")
-    else:
-        check(lib.bya_gemm_bf16(_p(a), _p(w), _p(bias), _p(out), _p(res), _p(gate0), _p(gate1), ctypes.byref(d),
-                                _stream()), "bya_gemm_bf16")
-    _end(tok)
+    d, call = _gemm_call(a, w, bias, out, res, gate0, gate1, split, (gate_split, gate_batch_stride, act, bias_rowscale, alpha), False)
+    _launch(_bf16_bucket(d), _SHAPE_LABELS and _label(d, "", act, gate0, res), d, call)
     return out
 
 
@@ -453,71 +524,34 @@ def gemm_plan(a, w, out, bias=None, res=None, gate0=None, gate1=None, gate_split
               split=None, bias_rowscale=None, alpha=1.0):
     """What ``gemm`` with the same arguments would run: {"path", "m0", "tail", "split_k", "row_chunks"} (kernel names of
     ``GEMM_PATHS``, or path "skinny" for the weight-streaming kernel).  Raises what ``gemm`` would raise."""
-    lib = _hip.load()
-    d = _gemm_desc(a, w, out, res, gate_split, gate_batch_stride, act, split, bias_rowscale, alpha, plan=True)
-    if a.is_cuda and a.device.index not in _GEMM_WS:
-        ensure_gemm_workspace(a.device)
-    if _takes_skinny(d, gate0, bias_rowscale, split):
+    _, call = _gemm_call(a, w, bias, out, res, gate0, gate1, split, (gate_split, gate_batch_stride, act, bias_rowscale, alpha), True)
+    if call[0] == "bya_gemm_skinny_bf16":                                # (one kernel: the library has no query for it)
         return {"path": "skinny", "m0": 0, "tail": None, "split_k": 0, "row_chunks": 1}
-    p, q = _hip.GemmPlan(), _plan_p
-    check(lib.bya_gemm_bf16_plan(q(a), q(w), q(bias), q(out), q(res), q(gate0), q(gate1), ctypes.byref(d),
-                                 ctypes.byref(p)), "bya_gemm_bf16_plan")
-    return _plan_dict(p)
+    return _plan(call)
 
 
-def _qkn_descs(a, w, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors, plan=False):
-    ab, M, K, a_bs, lda = _mat(a, "a", plan)
-    ob, Mo, _, c_bs, ldc = _mat(out, "out", plan)
-    N = w.shape[0]
-    if w.dim() != 2 or w.shape[1] != K or w.stride(1) != 1 or w.dtype != torch.bfloat16 or tensors not in (2, 3) or N % tensors \
-            or (ab, M) != (ob, Mo):
+def _qkn_call(a, w, out, bias, split, norm, tensors, plan):
+    if tensors not in (2, 3) or w.shape[0] % tensors:
         raise ValueError("gemm_qkv_norm_rope: a [(B,) M, K], w [3 * width, K] (or [2 * width, K]: q | k alone, tensors=2), "
                          "out = the first of the split outputs")
-    d = GemmDesc()
-    d.M, d.N, d.K, d.batch = M, N, K, ab
-    d.lda, d.ldw, d.ldc = lda, w.stride(0), ldc
-    d.a_batch_stride, d.c_batch_stride = a_bs, c_bs
-    d.n_split, d.c_split_stride = split
-    d.alpha = 1.0
-    n = _hip.QkNormDesc()
-    ptr = _plan_p if plan else _p
-    n.qw, n.qb, n.kw, n.kb, n.cos, n.sin = ptr(qw), ptr(qb), ptr(kw), ptr(kb), ptr(cos), ptr(sin)
-    n.text_rows, n.width, n.eps, n.k_scale = int(text_rows), N // tensors, float(eps), float(k_scale)
-    if cos is not None:
-        assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
-        assert cos.shape == (M - text_rows, 64)
-    return d, n
+    d = _gemm_desc(a, w, out, None, tuple(split), _NO_EPILOGUE, plan)    # (``split`` is required: None is a TypeError)
+    n = _qkn_desc(d, tensors, *norm, plan)
+    q = _plan_p if plan else _p
+    return d, ("bya_gemm_qkv_norm_rope", (q(a), q(w), q(bias), q(out), ctypes.byref(d), ctypes.byref(n)))
 
 
 def gemm_qkv_norm_rope(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6, k_scale=1.0, tensors=3):
     """The packed q|k|v projection with the q/k LayerNorm(64) + RoPE in its epilogue (bya_gemm_qkv_norm_rope): equals
     ``gemm(..., split=split)`` followed by ``qknorm_rope`` bit for bit, in one launch.  Returns False (nothing launched) when
     the library does not take the shape -- the caller then issues the two launches."""
-    lib = _hip.load()
-    d, n = _qkn_descs(a, w, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors)
-    ab, M, N, K = d.batch, d.M, d.N, d.K
-    tok = _begin("bya_gemm_bf16" if M >= 1024 else "bya_gemm_bf16_small_m")
-    rc = lib.bya_gemm_qkv_norm_rope(_p(a), _p(w), _p(bias), _p(out), ctypes.byref(d), ctypes.byref(n), _stream())
-    if rc == -4:                       # BYA_ERR_UNSUPPORTED: not this kernel's shape -- nothing was launched, nothing is counted
-        return False                   # (the caller's plain GEMM counts the FLOPs; round 5 counted them here as well)
-    check(rc, "bya_gemm_qkv_norm_rope")
-    if tok is not None:
-        _FLOPS[tok[0]] = _FLOPS.get(tok[0], 0.0) + 2.0 * ab * M * N * K
-    _end(tok)
-    return True
+    d, call = _qkn_call(a, w, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale), tensors, False)
+    return _launch(_bf16_bucket(d), None, d, call, True)         # (the bf16 GEMM's bucket, and no shape label)
 
 
 def gemm_qkv_norm_rope_plan(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6, k_scale=1.0, tensors=3):
     """What ``gemm_qkv_norm_rope`` would run (``gemm_plan``'s dict): path "p256" (its row plan 0), "p128" (plan 1), or
     "p256" with m0 and tail "p128" (plan 2); None where it declines the shape (the caller's two launches)."""
-    lib = _hip.load()
-    d, n = _qkn_descs(a, w, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors, plan=True)
-    p, q = _hip.GemmPlan(), _plan_p
-    rc = lib.bya_gemm_qkv_norm_rope_plan(q(a), q(w), q(bias), q(out), ctypes.byref(d), ctypes.byref(n), ctypes.byref(p))
-    if rc == -4:
-        return None
-    check(rc, "bya_gemm_qkv_norm_rope_plan")
-    return _plan_dict(p)
+    return _plan(_qkn_call(a, w, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale), tensors, True)[1], True)
 
 
 def quantize_rows_fp8(x, q=None, scale=None):
@@ -538,7 +572,7 @@ def quantize_rows_fp8(x, q=None, scale=None):
     return q, scale
 
 
-def _fp8_desc(a8, a_scale, w8, w_scale, out, res, gate_split, gate_batch_stride, act, split, alpha, plan=False):
+def _fp8_desc(a8, a_scale, w8, w_scale, out, res, split, epi, plan=False):
     if a8.dim() == 2:
         ab, (M, K) = 1, a8.shape
     else:
@@ -550,65 +584,40 @@ def _fp8_desc(a8, a_scale, w8, w_scale, out, res, gate_split, gate_batch_stride,
     assert w8.shape == (N, K) and (ab, M) == (ob, Mo)
     assert a_scale.dtype == torch.float32 and a_scale.numel() == ab * M and a_scale.is_contiguous()
     assert w_scale.dtype == torch.float32 and w_scale.numel() == N and w_scale.is_contiguous()
-    d = GemmDesc()
-    d.M, d.N, d.K, d.batch = M, N, K, ab
-    d.lda, d.ldw, d.ldc = K, K, ldc
-    d.a_batch_stride, d.c_batch_stride = M * K, c_bs
-    d.ldres, d.res_batch_stride = 0, 0
-    if res is not None:
-        rb, Mr, Nr, r_bs, ldres = _mat(res, "res", plan)
-        if (Mr, Nr) != (M, N) or rb not in (1, ab):
-            raise ValueError("res shape mismatch")
-        d.ldres, d.res_batch_stride = ldres, (r_bs if rb == ab else 0)
-    d.gate_batch_stride, d.gate_split, d.act = gate_batch_stride, gate_split, ACT[act]
-    d.n_split, d.c_split_stride = (0, 0) if split is None else split
-    d.bias_rowscale, d.alpha = None, float(alpha)
-    return d
+    return _fill_desc((ab, M, N, K, K, M * K, K, ldc, c_bs), res, split, epi, plan)
+
+
+def _fp8_call(a8, a_scale, w8, w_scale, bias, out, res, gate0, gate1, split, epi, plan):
+    d = _fp8_desc(a8, a_scale, w8, w_scale, out, res, split, epi, plan)
+    q = _plan_p if plan else _p
+    return d, ("bya_gemm_fp8", (q(a8), q(a_scale), q(w8), q(w_scale), q(bias), q(out), q(res), q(gate0), q(gate1), ctypes.byref(d)))
 
 
 def gemm_fp8(a8, a_scale, w8, w_scale, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0,
              gate_batch_stride=0, act=None, split=None, alpha=1.0):
     """out = res + gate * act(a_scale * w_scale * (a8 @ w8.T) + bias) with e4m3 operands (``quantize_rows_fp8``)."""
-    lib = _hip.load()
-    d = _fp8_desc(a8, a_scale, w8, w_scale, out, res, gate_split, gate_batch_stride, act, split, alpha)
-    ab, M, N, K = d.batch, d.M, d.N, d.K
-    name = "bya_gemm_fp8"
-    if _SHAPE_LABELS:
-        name += f":{ab}x{M}x{N}x{K}:{act or 'none'}{'+gate' if gate0 is not None else ''}{'+res' if res is not None else ''}"
-    tok = _begin(name, 2.0 * ab * M * N * K)
-    check(lib.bya_gemm_fp8(_p(a8), _p(a_scale), _p(w8), _p(w_scale), _p(bias), _p(out), _p(res), _p(gate0), _p(gate1),
-                           ctypes.byref(d), _stream()), "bya_gemm_fp8")
-    _end(tok)
+    d, call = _fp8_call(a8, a_scale, w8, w_scale, bias, out, res, gate0, gate1, split, (gate_split, gate_batch_stride, act, None, alpha),
+                        False)
+    _launch("bya_gemm_fp8", _SHAPE_LABELS and _label(d, "", act, gate0, res), d, call)
     return out
 
 
 def gemm_fp8_plan(a8, a_scale, w8, w_scale, out, bias=None, res=None, gate0=None, gate1=None, gate_split=0,
                   gate_batch_stride=0, act=None, split=None, alpha=1.0):
     """What ``gemm_fp8`` would run (``gemm_plan``'s dict): path "t128x128" or "p256"."""
-    lib = _hip.load()
-    d = _fp8_desc(a8, a_scale, w8, w_scale, out, res, gate_split, gate_batch_stride, act, split, alpha, plan=True)
-    p, q = _hip.GemmPlan(), _plan_p
-    check(lib.bya_gemm_fp8_plan(q(a8), q(a_scale), q(w8), q(w_scale), q(bias), q(out), q(res), q(gate0), q(gate1),
-                                ctypes.byref(d), ctypes.byref(p)), "bya_gemm_fp8_plan")
-    return _plan_dict(p)
+    return _plan(_fp8_call(a8, a_scale, w8, w_scale, bias, out, res, gate0, gate1, split, (gate_split, gate_batch_stride, act, None, alpha),
+                           True)[1])
 
 
-def _fp8_qkn_descs(a8, a_scale, w8, w_scale, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors, act=None,
-                   res=None, alpha=1.0, plan=False):
+def _fp8_qkn_call(a8, a_scale, w8, w_scale, out, bias, split, norm, tensors, act, res, alpha, plan):
     if tensors not in (2, 3) or w8.shape[0] % tensors or split is None:
         raise ValueError("gemm_fp8_qkv_norm_rope: w8 [3 * width, K] (or [2 * width, K]: q | k alone, tensors=2), "
                          "out = the first of the split outputs, split = (n_split, c_split_stride)")
-    d = _fp8_desc(a8, a_scale, w8, w_scale, out, None, 0, 0, act, split, alpha, plan=plan)
-    if res is not None:                 # (the entry point has no residual argument: the descriptor says so and it declines)
-        d.ldres, d.res_batch_stride = res.stride(-2), (res.stride(0) if res.dim() == 3 else 0)
-    n = _hip.QkNormDesc()
-    ptr = _plan_p if plan else _p
-    n.qw, n.qb, n.kw, n.kb, n.cos, n.sin = ptr(qw), ptr(qb), ptr(kw), ptr(kb), ptr(cos), ptr(sin)
-    n.text_rows, n.width, n.eps, n.k_scale = int(text_rows), d.N // tensors, float(eps), float(k_scale)
-    if cos is not None:
-        assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
-        assert cos.shape == (d.M - text_rows, 64)
-    return d, n
+    # (the entry point has no residual argument: the descriptor says that one was asked for, and it declines)
+    d = _fp8_desc(a8, a_scale, w8, w_scale, out, res, split, (0, 0, act, None, alpha), plan)
+    n = _qkn_desc(d, tensors, *norm, plan)
+    q = _plan_p if plan else _p
+    return d, ("bya_gemm_fp8_qkv_norm_rope", (q(a8), q(a_scale), q(w8), q(w_scale), q(bias), q(out), ctypes.byref(d), ctypes.byref(n)))
 
 
 def gemm_fp8_qkv_norm_rope(a8, a_scale, w8, w_scale, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6,
@@ -618,23 +627,9 @@ def gemm_fp8_qkv_norm_rope(a8, a_scale, w8, w_scale, out, bias, split, qw, qb, k
     on the kernel ``gemm_fp8`` would take (``gemm_fp8_plan``'s path, option ``fp8_kernel`` included).  Returns False (nothing
     launched, nothing counted) when the library does not take the shape -- the caller then issues the two launches.
     ``act`` / ``res`` (keyword only): what the engine never asks of this launch, here so that a caller that does is told False."""
-    lib = _hip.load()
-    d, n = _fp8_qkn_descs(a8, a_scale, w8, w_scale, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors,
-                          act=act, res=res)
-    ab, M, N, K = d.batch, d.M, d.N, d.K
-    name = "bya_gemm_fp8_qkv_norm_rope"
-    if _SHAPE_LABELS:
-        name += f":{ab}x{M}x{N}x{K}"
-    tok = _begin(name)
-    rc = lib.bya_gemm_fp8_qkv_norm_rope(_p(a8), _p(a_scale), _p(w8), _p(w_scale), _p(bias), _p(out), ctypes.byref(d),
-                                        ctypes.byref(n), _stream())
-    if rc == -4:                       # BYA_ERR_UNSUPPORTED: nothing was launched (the caller's gemm_fp8 counts the FLOPs)
-        return False
-    check(rc, "bya_gemm_fp8_qkv_norm_rope")
-    if tok is not None:
-        _FLOPS[tok[0]] = _FLOPS.get(tok[0], 0.0) + 2.0 * ab * M * N * K
-    _end(tok)
-    return True
+    d, call = _fp8_qkn_call(a8, a_scale, w8, w_scale, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale), tensors,
+                               act, res, 1.0, False)
+    return _launch("bya_gemm_fp8_qkv_norm_rope", _SHAPE_LABELS and _label(d), d, call, True)
 
 
 def gemm_fp8_qkv_norm_rope_plan(a8, a_scale, w8, w_scale, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6,
@@ -642,16 +637,8 @@ def gemm_fp8_qkv_norm_rope_plan(a8, a_scale, w8, w_scale, out, bias, split, qw, 
     """What ``gemm_fp8_qkv_norm_rope`` would run (``gemm_plan``'s dict): path "t128x128" or "p256", one row chunk; None where
     it declines the shape (the caller's two launches).  ``act`` / ``res`` / ``alpha``: descriptor fields the launch wrapper's
     callers never set, here to ask what the library answers to them."""
-    lib = _hip.load()
-    d, n = _fp8_qkn_descs(a8, a_scale, w8, w_scale, out, split, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, tensors,
-                          act=act, res=res, alpha=alpha, plan=True)
-    p, q = _hip.GemmPlan(), _plan_p
-    rc = lib.bya_gemm_fp8_qkv_norm_rope_plan(q(a8), q(a_scale), q(w8), q(w_scale), q(bias), q(out), ctypes.byref(d),
-                                             ctypes.byref(n), ctypes.byref(p))
-    if rc == -4:
-        return None
-    check(rc, "bya_gemm_fp8_qkv_norm_rope_plan")
-    return _plan_dict(p)
+    return _plan(_fp8_qkn_call(a8, a_scale, w8, w_scale, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale), tensors,
+                               act, res, alpha, True)[1], True)
 
 
 # OCP MX element formats (include/bya.h, "MX weights"): name -> the matrix instruction's format code, element bits.
@@ -709,8 +696,7 @@ def quantize_mx(x, fmt="mxfp6", codes=None, scales=None):
     return codes, scales
 
 
-def _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
-             plan=False, bias_rowscale=None):
+def _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, split, epi, plan=False):
     if a_scales.dim() == 2:
         ab, (M, KS) = 1, a_scales.shape
     else:
@@ -724,22 +710,15 @@ def _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_sp
     assert a_codes.is_contiguous() and w_codes.is_contiguous() and a_scales.is_contiguous() and w_scales.is_contiguous()
     assert a_codes.numel() == ab * M * rb_ and w_codes.shape == (N, rbw) and w_scales.shape == (N, KS)
     assert (ab, M) == (ob, Mo)
-    d = GemmDesc()
-    d.M, d.N, d.K, d.batch = M, N, K, ab
-    d.lda, d.ldw, d.ldc = rb_, rbw, ldc
-    d.a_batch_stride, d.c_batch_stride = M * rb_, c_bs
-    d.ldres, d.res_batch_stride = 0, 0
-    if res is not None:
-        rb, Mr, Nr, r_bs, ldres = _mat(res, "res", plan)
-        if (Mr, Nr) != (M, N) or rb not in (1, ab):
-            raise ValueError("res shape mismatch")
-        d.ldres, d.res_batch_stride = ldres, (r_bs if rb == ab else 0)
-    d.gate_batch_stride, d.gate_split, d.act = gate_batch_stride, gate_split, ACT[act]
-    d.n_split, d.c_split_stride = (0, 0) if split is None else split
-    d.bias_rowscale, d.alpha = (_plan_p if plan else _p)(bias_rowscale), float(alpha)
-    if bias_rowscale is not None:
-        assert bias_rowscale.dtype == torch.float32 and bias_rowscale.is_contiguous() and bias_rowscale.numel() == ab * M
-    return d
+    return _fill_desc((ab, M, N, K, rb_, M * rb_, rbw, ldc, c_bs), res, split, epi, plan)
+
+
+def _mx_gemm_call(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, bias, res, gate0, gate1, split, epi, plan):
+    code, wcode = mx_fmt_pair(fmt, w_fmt)
+    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, split, epi, plan)
+    q = _plan_p if plan else _p
+    args = (q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), q(res), q(gate0), q(gate1), ctypes.byref(d), code)
+    return d, (("bya_gemm_mx_mixed", (*args, wcode)) if wcode != code else ("bya_gemm_mx", args))
 
 
 def gemm_mx(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, res=None, gate0=None, gate1=None,
@@ -747,23 +726,10 @@ def gemm_mx(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=None, r
     """out = res + gate * alpha * act(A @ W.T + rowscale * bias) with both operands in MX form (``quantize_mx``); K is read off
     the scales.  ``fmt``: the activations' format; ``w_fmt``: the weights' (None = the same, or "mxfp4": bya_gemm_mx_mixed).
     ``bias_rowscale``: fp32 [batch * M] as for ``gemm`` (every MX kernel's bf16 epilogue honours it)."""
-    lib = _hip.load()
-    code, wcode = mx_fmt_pair(fmt, w_fmt)
-    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
-                 bias_rowscale=bias_rowscale)
-    ab, M, N, K = d.batch, d.M, d.N, d.K
-    mixed = wcode != code
-    name = "bya_gemm_mx_mixed" if mixed else "bya_gemm_mx"
-    if _SHAPE_LABELS:
-        name += f":{fmt + '*' + w_fmt if mixed else fmt}:{ab}x{M}x{N}x{K}:{act or 'none'}{'+gate' if gate0 is not None else ''}{'+res' if res is not None else ''}"
-    tok = _begin(name, 2.0 * ab * M * N * K)
-    args = (_p(a_codes), _p(a_scales), _p(w_codes), _p(w_scales), _p(bias), _p(out), _p(res), _p(gate0), _p(gate1),
-            ctypes.byref(d))
-    if mixed:
-        check(lib.bya_gemm_mx_mixed(*args, code, wcode, _stream()), "bya_gemm_mx_mixed")
-    else:
-        check(lib.bya_gemm_mx(*args, code, _stream()), "bya_gemm_mx")
-    _end(tok)
+    d, call = _mx_gemm_call(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, bias, res, gate0, gate1, split,
+                            (gate_split, gate_batch_stride, act, bias_rowscale, alpha), False)
+    mixed = call[0] == "bya_gemm_mx_mixed"
+    _launch(call[0], _SHAPE_LABELS and _label(d, f":{fmt + '*' + w_fmt if mixed else fmt}", act, gate0, res), d, call)
     return out
 
 
@@ -771,33 +737,24 @@ def gemm_mx_plan(a_codes, a_scales, w_codes, w_scales, out, fmt="mxfp6", bias=No
                  gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0, w_fmt=None, bias_rowscale=None):
     """What ``gemm_mx`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations only), or "p256"
     (mxfp8 activations and weights under option ``mx_kernel``)."""
-    lib = _hip.load()
-    code, wcode = mx_fmt_pair(fmt, w_fmt)
-    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
-                 plan=True, bias_rowscale=bias_rowscale)
-    p, q = _hip.GemmPlan(), _plan_p
-    args = (q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), q(res), q(gate0), q(gate1), ctypes.byref(d))
-    if wcode != code:
-        check(lib.bya_gemm_mx_mixed_plan(*args, code, wcode, ctypes.byref(p)), "bya_gemm_mx_mixed_plan")
-    else:
-        check(lib.bya_gemm_mx_plan(*args, code, ctypes.byref(p)), "bya_gemm_mx_plan")
-    return _plan_dict(p)
+    return _plan(_mx_gemm_call(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, bias, res, gate0, gate1, split,
+                               (gate_split, gate_batch_stride, act, bias_rowscale, alpha), True)[1])
 
 
-def _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, qw, qb, kw, kb, cos, sin, text_rows, eps,
-                  k_scale, tensors, act=None, alpha=1.0, plan=False):
+def _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, norm, tensors, act, alpha, plan):
     if tensors not in (2, 3) or w_codes.shape[0] % tensors or split is None:
         raise ValueError("gemm_mx_qkv_norm_rope: w_codes [3 * width, ..] (or [2 * width, ..]: q | k alone, tensors=2), "
                          "out = the first of the split outputs, split = (n_split, c_split_stride)")
-    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, None, 0, 0, act, split, alpha, plan=plan)
-    n = _hip.QkNormDesc()
-    ptr = _plan_p if plan else _p
-    n.qw, n.qb, n.kw, n.kb, n.cos, n.sin = ptr(qw), ptr(qb), ptr(kw), ptr(kb), ptr(cos), ptr(sin)
-    n.text_rows, n.width, n.eps, n.k_scale = int(text_rows), d.N // tensors, float(eps), float(k_scale)
-    if cos is not None:
-        assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
-        assert cos.shape == (d.M - text_rows, 64)
-    return d, n
+    d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, None, split, (0, 0, act, None, alpha), plan)
+    return d, _qkn_desc(d, tensors, *norm, plan)
+
+
+def _mx_qkn_call(a_codes, a_scales, w_codes, w_scales, out, bias, split, norm, tensors, fmt, w_fmt, act, alpha, kernel, plan):
+    code, wcode = mx_fmt_pair(fmt, w_fmt)
+    d, n = _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, norm, tensors, act, alpha, plan)
+    q = _plan_p if plan else _p
+    args = (q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), code, wcode, ctypes.byref(d), ctypes.byref(n))
+    return d, (("bya_gemm_mx_qkv_norm_rope", args) if kernel == 0 else ("bya_gemm_mx_qkv_norm_rope_on", (*args, int(kernel))))
 
 
 def gemm_mx_qkv_norm_rope(a_codes, a_scales, w_codes, w_scales, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows,
@@ -808,27 +765,9 @@ def gemm_mx_qkv_norm_rope(a_codes, a_scales, w_codes, w_scales, out, bias, split
     two launches.  ``kernel``: 0 = the tiled kernel; 1 = the persistent 256 x 256 kernel where the launch fills it (mxfp8
     activations and weights only, the same bits; bya_gemm_mx_qkv_norm_rope_on), 2 = without the tile count (tests).  Option
     ``mx_kernel`` has no say here."""
-    lib = _hip.load()
-    code, wcode = mx_fmt_pair(fmt, w_fmt)
-    d, n = _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, qw, qb, kw, kb, cos, sin, text_rows, eps,
-                         k_scale, tensors)
-    ab, M, N, K = d.batch, d.M, d.N, d.K
-    name = "bya_gemm_mx_qkv_norm_rope"
-    if _SHAPE_LABELS:
-        name += f":{fmt}*{w_fmt or fmt}:{ab}x{M}x{N}x{K}"
-    tok = _begin(name)
-    args = (_p(a_codes), _p(a_scales), _p(w_codes), _p(w_scales), _p(bias), _p(out), code, wcode, ctypes.byref(d), ctypes.byref(n))
-    if kernel == 0:
-        rc = lib.bya_gemm_mx_qkv_norm_rope(*args, _stream())
-    else:
-        rc = lib.bya_gemm_mx_qkv_norm_rope_on(*args, int(kernel), _stream())
-    if rc == -4:                       # BYA_ERR_UNSUPPORTED: nothing was launched (the caller's gemm_mx counts the FLOPs)
-        return False
-    check(rc, "bya_gemm_mx_qkv_norm_rope")
-    if tok is not None:
-        _FLOPS[tok[0]] = _FLOPS.get(tok[0], 0.0) + 2.0 * ab * M * N * K
-    _end(tok)
-    return True
+    d, call = _mx_qkn_call(a_codes, a_scales, w_codes, w_scales, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale),
+                              tensors, fmt, w_fmt, None, 1.0, kernel, False)
+    return _launch("bya_gemm_mx_qkv_norm_rope", _SHAPE_LABELS and _label(d, f":{fmt}*{w_fmt or fmt}"), d, call, True)
 
 
 def gemm_mx_qkv_norm_rope_plan(a_codes, a_scales, w_codes, w_scales, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows,
@@ -837,20 +776,8 @@ def gemm_mx_qkv_norm_rope_plan(a_codes, a_scales, w_codes, w_scales, out, bias, 
     only), or "p256" (``kernel`` 1 or 2, mxfp8 activations and weights); None where it declines the shape (the caller's two
     launches).  ``act`` / ``alpha``: descriptor fields the launch wrapper never sets, here to ask what the library answers
     to them."""
-    lib = _hip.load()
-    code, wcode = mx_fmt_pair(fmt, w_fmt)
-    d, n = _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, qw, qb, kw, kb, cos, sin, text_rows, eps,
-                         k_scale, tensors, act=act, alpha=alpha, plan=True)
-    p, q = _hip.GemmPlan(), _plan_p
-    args = (q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), code, wcode, ctypes.byref(d), ctypes.byref(n))
-    if kernel == 0:
-        rc = lib.bya_gemm_mx_qkv_norm_rope_plan(*args, ctypes.byref(p))
-    else:
-        rc = lib.bya_gemm_mx_qkv_norm_rope_on_plan(*args, int(kernel), ctypes.byref(p))
-    if rc == -4:
-        return None
-    check(rc, "bya_gemm_mx_qkv_norm_rope_plan")
-    return _plan_dict(p)
+    return _plan(_mx_qkn_call(a_codes, a_scales, w_codes, w_scales, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale),
+                              tensors, fmt, w_fmt, act, alpha, kernel, True)[1], True)
 
 
 def _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, act, alpha):
@@ -865,15 +792,17 @@ def _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, 
     assert a_codes.numel() == ab * M * rb_ and w_codes.shape == (N, rbw) and w_scales.shape == (N, KS)
     if N % 32 or out_codes.numel() != ab * M * rbo or out_scales.numel() != ab * M * (N // 32):
         raise ValueError("gemm_mx_quant: out_codes / out_scales must hold [batch * M, N * bits / 8] and [batch * M, N / 32]")
-    d = GemmDesc()
-    d.M, d.N, d.K, d.batch = M, N, K, ab
-    d.lda, d.ldw, d.ldc = rb_, rbw, rbo
-    d.a_batch_stride, d.c_batch_stride = M * rb_, M * rbo
-    d.ldres, d.res_batch_stride = 0, 0
-    d.gate_batch_stride, d.gate_split, d.act = 0, 0, ACT[act]
-    d.n_split, d.c_split_stride = 0, 0
-    d.bias_rowscale, d.alpha = None, float(alpha)
-    return d
+    return _fill_desc((ab, M, N, K, rb_, M * rb_, rbw, rbo, M * rbo), None, None, (0, 0, act, None, alpha), False)
+
+
+def _mx_quant_call(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, bias, act, alpha, plan):
+    code, wcode = mx_fmt_pair(fmt, w_fmt)
+    out_fmt = fmt if out_fmt is None else out_fmt
+    ocode = mx_fmt_code(out_fmt)
+    d = _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, act, alpha)
+    q = _plan_p if plan else _p
+    return d, out_fmt, ("bya_gemm_mx_quant", (q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out_codes), q(out_scales),
+                                              ctypes.byref(d), code, wcode, ocode))
 
 
 def gemm_mx_quant(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt="mxfp6", w_fmt=None, out_fmt=None,
@@ -882,19 +811,9 @@ def gemm_mx_quant(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, f
     block scales of its bf16-rounded result, byte for byte what the two launches write, into the preallocated pair
     ``out_codes`` [(B,) M, N * bits / 8], ``out_scales`` [(B,) M, N / 32].  ``out_fmt``: "mxfp8" or "mxfp6" (None = ``fmt``).
     Returns ``(out_codes, out_scales)``: the ``quantised=`` pair of the next MX Linear."""
-    lib = _hip.load()
-    code, wcode = mx_fmt_pair(fmt, w_fmt)
-    out_fmt = fmt if out_fmt is None else out_fmt
-    ocode = mx_fmt_code(out_fmt)
-    d = _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, act, alpha)
-    ab, M, N, K = d.batch, d.M, d.N, d.K
-    name = "bya_gemm_mx_quant"
-    if _SHAPE_LABELS:
-        name += f":{fmt}*{w_fmt or fmt}>{out_fmt}:{ab}x{M}x{N}x{K}:{act or 'none'}"
-    tok = _begin(name, 2.0 * ab * M * N * K)
-    check(lib.bya_gemm_mx_quant(_p(a_codes), _p(a_scales), _p(w_codes), _p(w_scales), _p(bias), _p(out_codes), _p(out_scales),
-                                ctypes.byref(d), code, wcode, ocode, _stream()), "bya_gemm_mx_quant")
-    _end(tok)
+    d, out_fmt, call = _mx_quant_call(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, bias, act, alpha,
+                                      False)
+    _launch("bya_gemm_mx_quant", _SHAPE_LABELS and _label(d, f":{fmt}*{w_fmt or fmt}>{out_fmt}", act), d, call)
     return out_codes, out_scales
 
 
@@ -902,55 +821,40 @@ def gemm_mx_quant_plan(a_codes, a_scales, w_codes, w_scales, out_codes, out_scal
                        bias=None, act=None, alpha=1.0):
     """What ``gemm_mx_quant`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations only), or
     "p256" (mxfp8 activations, weights and output under option ``mx_kernel``)."""
-    lib = _hip.load()
-    code, wcode = mx_fmt_pair(fmt, w_fmt)
-    out_fmt = fmt if out_fmt is None else out_fmt
-    d = _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, act, alpha)
-    p, q = _hip.GemmPlan(), _plan_p
-    check(lib.bya_gemm_mx_quant_plan(q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out_codes), q(out_scales),
-                                     ctypes.byref(d), code, wcode, mx_fmt_code(out_fmt), ctypes.byref(p)),
-          "bya_gemm_mx_quant_plan")
-    return _plan_dict(p)
+    return _plan(_mx_quant_call(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, bias, act, alpha,
+                                True)[2])
 
 
-def _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, gate_split,
-             gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan, bias_rowscale=None):
-    """(bya_mx_gemm_call, bya_gemm_desc, the objects they point into, the epilogue's name) of ``gemm_mx_call``."""
+def _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, split, epi, out_scales,
+             out_fmt, norm, plan):
+    """(bya_mx_gemm_call, bya_gemm_desc, the norm descriptor the call points to, the epilogue's name) of ``gemm_mx_call``."""
     code, wcode = mx_fmt_pair(fmt, w_fmt)
     ptr = _plan_p if plan else _p
-    c = _hip.MxGemmCall()
-    keep = []
+    c, n = _hip.MxGemmCall(), None
+    _, _, act, bias_rowscale, alpha = epi
     if bias_rowscale is not None and (norm is not None or out_scales is not None):
         raise ValueError("gemm_mx_call: bias_rowscale goes with the bf16 epilogue alone")
     if norm is not None and out_scales is not None:
-        # (the library refuses the pair; build the bf16 descriptor so that it is asked)
-        d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
-                     plan=plan)
-        c.q_scales = ptr(out_scales)
-        n = _hip.QkNormDesc()
-        keep.append(n)
-        c.norm = ctypes.pointer(n)
-        epi = "both"
+        # (the library refuses the pair; build the bf16 descriptor and an empty norm so that it is asked)
+        d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, split, epi, plan)
+        c.q_scales, n, name = ptr(out_scales), _qkn_desc(d, 0, *_NO_NORM, plan), "both"
     elif norm is not None:
-        d, n = _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, norm["qw"], norm["qb"], norm["kw"],
-                             norm["kb"], norm.get("cos"), norm.get("sin"), norm["text_rows"], norm.get("eps", 1e-6),
-                             norm.get("k_scale", 1.0), norm.get("tensors", 3), act=act, alpha=alpha, plan=plan)
-        keep.append(n)
-        c.norm = ctypes.pointer(n)
-        epi = "qkn"
+        d, n = _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split,
+                             (norm["qw"], norm["qb"], norm["kw"], norm["kb"], norm.get("cos"), norm.get("sin"), norm["text_rows"],
+                              norm.get("eps", 1e-6), norm.get("k_scale", 1.0)), norm.get("tensors", 3), act, alpha, plan)
+        name = "qkn"
     elif out_scales is not None:
         out_fmt = fmt if out_fmt is None else out_fmt
         d = _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out, out_scales, fmt, w_fmt, out_fmt, act, alpha)
-        c.q_scales, c.out_fmt = ptr(out_scales), mx_fmt_code(out_fmt)
-        epi = "quant"
+        c.q_scales, c.out_fmt, name = ptr(out_scales), mx_fmt_code(out_fmt), "quant"
     else:
-        d = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, gate_split, gate_batch_stride, act, split, alpha,
-                     plan=plan, bias_rowscale=bias_rowscale)
-        epi = "bf16"
+        d, name = _mx_desc(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, res, split, epi, plan), "bf16"
+    if n is not None:
+        c.norm = ctypes.pointer(n)
     c.A, c.a_scales, c.W, c.w_scales, c.bias, c.C = ptr(a_codes), ptr(a_scales), ptr(w_codes), ptr(w_scales), ptr(bias), ptr(out)
     c.res, c.gate0, c.gate1 = ptr(res), ptr(gate0), ptr(gate1)
     c.a_fmt, c.w_fmt, c.kernel = code, wcode, int(kernel)
-    return c, d, keep, epi
+    return c, d, n, name
 
 
 def gemm_mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8", w_fmt=None, bias=None, res=None, gate0=None,
@@ -966,23 +870,12 @@ def gemm_mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8
     q/k-norm + RoPE one (a dict: qw, qb, kw, kb, cos, sin, text_rows and optionally eps, k_scale, tensors; ``split``
     required; returns False, nothing launched, where the library declines the shape); else the bf16 one of ``gemm_mx``, which
     alone takes ``bias_rowscale`` (fp32 [batch * M], as for ``gemm``)."""
-    lib = _hip.load()
-    c, d, keep, epi = _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, gate_split,
-                               gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan=False,
-                               bias_rowscale=bias_rowscale)
-    ab, M, N, K = d.batch, d.M, d.N, d.K
-    name = "bya_gemm_mx_call"
-    if _SHAPE_LABELS:
-        name += f":{epi}:k{int(kernel)}:{fmt}*{w_fmt or fmt}:{ab}x{M}x{N}x{K}:{act or 'none'}"
-    tok = _begin(name)
-    rc = lib.bya_gemm_mx_call(ctypes.byref(c), ctypes.byref(d), _stream())
-    if rc == -4 and epi == "qkn":      # BYA_ERR_UNSUPPORTED: nothing was launched (the caller's two launches count the FLOPs)
+    c, d, n, name = _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, split,
+                             (gate_split, gate_batch_stride, act, bias_rowscale, alpha), out_scales, out_fmt, norm, False)
+    if not _launch("bya_gemm_mx_call", _SHAPE_LABELS and _label(d, f":{name}:k{int(kernel)}:{fmt}*{w_fmt or fmt}", act), d,
+                   ("bya_gemm_mx_call", (ctypes.byref(c), ctypes.byref(d))), name == "qkn"):
         return False
-    check(rc, "bya_gemm_mx_call")
-    if tok is not None:
-        _FLOPS[tok[0]] = _FLOPS.get(tok[0], 0.0) + 2.0 * ab * M * N * K
-    _end(tok)
-    return True if epi == "qkn" else (out, out_scales) if epi == "quant" else out
+    return True if name == "qkn" else (out, out_scales) if name == "quant" else out
 
 
 def gemm_mx_call_plan(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8", w_fmt=None, bias=None, res=None,
@@ -991,16 +884,9 @@ def gemm_mx_call_plan(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="
     """What ``gemm_mx_call`` would run (``gemm_plan``'s dict): path "t128x128", "t256x256" (mxfp6 activations only) or "p256"
     (``kernel`` 1 or 2, "mxfp8" activations, "mxfp8" or "mxfp4" weights and "mxfp8" output; ``kernel`` 17 or 18: "mxfp6"
     activations and / or "mxfp6" output too); None where the q/k-norm epilogue declines the shape."""
-    lib = _hip.load()
-    c, d, keep, epi = _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, gate_split,
-                               gate_batch_stride, act, split, alpha, out_scales, out_fmt, norm, plan=True,
-                               bias_rowscale=bias_rowscale)
-    p = _hip.GemmPlan()
-    rc = lib.bya_gemm_mx_call_plan(ctypes.byref(c), ctypes.byref(d), ctypes.byref(p))
-    if rc == -4 and epi == "qkn":
-        return None
-    check(rc, "bya_gemm_mx_call_plan")
-    return _plan_dict(p)
+    c, d, n, name = _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, split,
+                             (gate_split, gate_batch_stride, act, bias_rowscale, alpha), out_scales, out_fmt, norm, True)
+    return _plan(("bya_gemm_mx_call", (ctypes.byref(c), ctypes.byref(d))), name == "qkn")
 
 
 def linear_small_m(x, w, bias, out, silu_in=False, act_out=None):
@@ -1263,7 +1149,7 @@ def attn_kv_mix_plan(z, af=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_str
         mx = _mix_mx_out(mx_out, z, z_strides, heads, head_dim, n_grp, Sq, plan=True)
         d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, (0, 0), scale)
         rc = lib.bya_attn_kv_mix_mx_plan(_plan_p(mx[0]), _plan_p(mx[1]), _plan_p(af), ctypes.byref(d), mx[2], *mx[3], ctypes.byref(p))
-        if rc == -4:
+        if rc == _UNSUPPORTED:
             return None
         check(rc, "bya_attn_kv_mix_mx_plan")
     else:
@@ -1402,16 +1288,8 @@ def attn_kv_mix(q, k, v, r, af, z, wsum=None, *, head_dim, heads, n_id, n_grp, S
     assert wsum is None or (wsum.dtype == torch.float32 and wsum.is_contiguous() and wsum.numel() >= n_grp * Sq)
     flops = 4.0 * n_id * n_grp * heads * Sq * Skv * head_dim
     if mx is not None:
-        tok = _begin("bya_attn_kv_mix_mx")
-        rc = lib.bya_attn_kv_mix_mx(_p(q), _p(k), _p(v), _p(r), _p(af), _p(mx[0]), _p(mx[1]), _p(wsum), ctypes.byref(d), mx[2],
-                                    *mx[3], _stream())
-        if rc == -4:                   # BYA_ERR_UNSUPPORTED: nothing was launched (the caller's two launches count the FLOPs)
-            return False
-        check(rc, "bya_attn_kv_mix_mx")
-        if tok is not None:
-            _FLOPS[tok[0]] = _FLOPS.get(tok[0], 0.0) + flops
-        _end(tok)
-        return mx[0], mx[1]
+        call = ("bya_attn_kv_mix_mx", (_p(q), _p(k), _p(v), _p(r), _p(af), _p(mx[0]), _p(mx[1]), _p(wsum), ctypes.byref(d), mx[2], *mx[3]))
+        return _launch("bya_attn_kv_mix_mx", None, flops, call, True) and (mx[0], mx[1])
     tok = _begin("bya_attn_kv_mix", flops)
     check(lib.bya_attn_kv_mix(_p(q), _p(k), _p(v), _p(r), _p(af), _p(z), _p(wsum), ctypes.byref(d), _stream()), "bya_attn_kv_mix")
     _end(tok)
