@@ -466,8 +466,7 @@ extern "C" int bya_gemm_workspace_bytes(int64_t* bytes) {
 }
 
 namespace {
-int dispatch_gemm(const GemmArgs& a, int nbatch, hipStream_t stream);
-void plan_gemm(const GemmArgs& a, int nbatch, bya_gemm_plan* p);
+int dispatch_gemm(const GemmArgs& a, int nbatch, hipStream_t stream, bya_gemm_plan* plan);
 
 // bya_gemm_bf16's arguments -> GemmArgs (with the current device's split-K workspace); BYA_OK or the error that rejects them
 int bf16_args(const void* A, const void* W, const void* bias, const void* C, const void* res, const void* gate0,
@@ -475,34 +474,25 @@ int bf16_args(const void* A, const void* W, const void* bias, const void* C, con
     if (!A || !W || !C || !d) return BYA_ERR_SHAPE;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return BYA_ERR_SHAPE;
     if (d->K % BK != 0 || d->N % 4 != 0) return BYA_ERR_SHAPE;
-    if (d->lda % 8 || d->ldw % 8 || d->ldc % 4 || (res && d->ldres % 4)) return BYA_ERR_ALIGN;
+    if (d->lda % 8 || d->ldw % 8) return BYA_ERR_ALIGN;
     if (((uintptr_t)A | (uintptr_t)W) & 15) return BYA_ERR_ALIGN;
-    if (((uintptr_t)C | (uintptr_t)res | (uintptr_t)bias | (uintptr_t)gate0 | (uintptr_t)gate1) & 7) return BYA_ERR_ALIGN;
-    if (d->act < 0 || d->act > 6) return BYA_ERR_UNSUPPORTED;
-    GemmArgs& a = *out;
-    a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C;
-    a.res = (const bf16_t*)res; a.gate0 = (const bf16_t*)gate0; a.gate1 = (const bf16_t*)(gate1 ? gate1 : gate0);
-    a.M = d->M; a.N = d->N; a.K = d->K;
-    a.lda = d->lda; a.ldw = d->ldw; a.ldc = d->ldc; a.ldres = d->ldres;
-    a.a_bs = d->a_batch_stride; a.c_bs = d->c_batch_stride; a.res_bs = d->res_batch_stride;
-    a.gate_bs = d->gate_batch_stride; a.gate_split = d->gate_split; a.act = d->act; a.leaky = 0.01f;
-    a.n_split = d->n_split; a.c_split_stride = d->c_split_stride;
-    a.bias_rowscale = d->bias_rowscale; a.alpha = d->alpha == 0.0f ? 1.0f : d->alpha;
+    const int rc = gemm_epilogue_check(C, res, bias, gate0, gate1, d, d->act >= 0 && d->act <= 6);
+    if (rc != BYA_OK) return rc;
+    gemm_fill_args(A, W, bias, C, res, gate0, gate1, d, out);
     const int dev = current_device();
     char* const ws = dev < 0 ? nullptr : static_cast<char*>(g_gemm_ws[dev].load());
-    a.ws_counters = reinterpret_cast<unsigned*>(ws);
-    a.ws_slabs = ws ? reinterpret_cast<float*>(ws + GEMM_WS_COUNTER_BYTES) : nullptr;
-    if (d->n_split < 0 || (d->n_split > 0 && (d->n_split % 4 || d->c_split_stride % 4 || res))) return BYA_ERR_SHAPE;
+    out->ws_counters = reinterpret_cast<unsigned*>(ws);
+    out->ws_slabs = ws ? reinterpret_cast<float*>(ws + GEMM_WS_COUNTER_BYTES) : nullptr;
     return BYA_OK;
 }
 
 // bya_gemm_qkv_norm_rope's arguments -> GemmArgs; BYA_ERR_UNSUPPORTED: not this kernel's shape (the caller keeps two launches)
 int qkn_args(const void* A, const void* W, const void* bias, const void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n,
              GemmArgs* out) {
-    if (!A || !W || !C || !d || !n) return BYA_ERR_SHAPE;
+    if (!A || !W || !C) return BYA_ERR_SHAPE;
+    const int rc = qkn_norm_desc_check(d, n);
+    if (rc != BYA_OK) return rc;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0 || d->K % BK != 0) return BYA_ERR_SHAPE;
-    if (!n->qw || !n->qb || !n->kw || !n->kb || n->width <= 0 || n->text_rows < 0) return BYA_ERR_SHAPE;
-    if (n->text_rows < d->M && (!n->cos || !n->sin)) return BYA_ERR_SHAPE;
     // N = 3 width: the packed q | k | v projection; N = 2 width (r6): q | k alone -- the sharded step computes v in a launch of
     // its own first and pushes it to the peers underneath this one
     if ((d->N != 3 * n->width && d->N != 2 * n->width) || n->width % 128 != 0 || d->n_split <= 0 || d->act != 0 || d->bias_rowscale || (d->alpha != 0.0f && d->alpha != 1.0f))
@@ -510,95 +500,70 @@ int qkn_args(const void* A, const void* W, const void* bias, const void* C, cons
     if (d->lda % 8 || d->ldw % 8) return BYA_ERR_ALIGN;
     if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)bias | (uintptr_t)n->qw | (uintptr_t)n->qb | (uintptr_t)n->kw |
          (uintptr_t)n->kb | (uintptr_t)n->cos | (uintptr_t)n->sin) & 15) return BYA_ERR_ALIGN;
-    GemmArgs& a = *out;
-    a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C;
-    a.res = nullptr; a.gate0 = nullptr; a.gate1 = nullptr;
-    a.M = d->M; a.N = d->N; a.K = d->K;
-    a.lda = d->lda; a.ldw = d->ldw; a.ldc = d->ldc; a.ldres = 0;
-    a.a_bs = d->a_batch_stride; a.c_bs = d->c_batch_stride; a.res_bs = 0; a.gate_bs = 0; a.gate_split = 0; a.act = 0; a.leaky = 0.01f;
-    a.n_split = d->n_split; a.c_split_stride = d->c_split_stride;
-    a.bias_rowscale = nullptr; a.alpha = 1.0f;
-    a.ws_counters = nullptr; a.ws_slabs = nullptr;                 // (the QKN instance never splits a tile)
-    a.qkn_w[0] = (const bf16_t*)n->qw; a.qkn_b[0] = (const bf16_t*)n->qb; a.qkn_w[1] = (const bf16_t*)n->kw; a.qkn_b[1] = (const bf16_t*)n->kb;
-    a.qkn_cos = n->cos; a.qkn_sin = n->sin; a.qkn_text_rows = n->text_rows; a.qkn_width = n->width;
-    a.qkn_eps = n->eps; a.qkn_kscale = n->k_scale == 0.0f ? 1.0f : n->k_scale;
-    if (!v4_eligible(a) || !gemm_rows_reachable(a, a.M)) return BYA_ERR_UNSUPPORTED;
+    gemm_fill_args(A, W, bias, C, nullptr, nullptr, nullptr, d, out);               // (no workspace: the QKN instance never splits a tile)
+    out->ldres = 0; out->res_bs = 0; out->gate_bs = 0; out->gate_split = 0;          // no residual, no gates: not read from the descriptor
+    qkn_fill_norm(n, out);
+    if (!v4_eligible(*out) || !gemm_rows_reachable(*out, out->M)) return BYA_ERR_UNSUPPORTED;
     return BYA_OK;
 }
 
-// the q|k|v launch's row plan (0: 256-row tiles, 1: 128-row tiles, 2: both, rows split at *m0)
-inline int qkn_plan(const GemmArgs& a, int batch, int* m0) {
-    *m0 = 0;
-    return p128_eligible(a) ? plan_rows_qkn(a.M, a.N, batch, m0) : 0;
-}
-}  // namespace
-
-extern "C" int bya_gemm_bf16(const void* A, const void* W, const void* bias, void* C, const void* res,
-                             const void* gate0, const void* gate1, const bya_gemm_desc* d, hipStream_t stream) {
+// bya_gemm_bf16 (plan == nullptr) and bya_gemm_bf16_plan: one body, so the query answers what the launch does
+int bf16_gemm(const void* A, const void* W, const void* bias, const void* C, const void* res, const void* gate0,
+              const void* gate1, const bya_gemm_desc* d, hipStream_t stream, bya_gemm_plan* plan) {
     GemmArgs a;
     const int rc = bf16_args(A, W, bias, C, res, gate0, gate1, d, &a);
     if (rc != BYA_OK) return rc;
-    return gemm_row_chunks(a, d->batch, 2, [&](const GemmArgs& piece, int batch, long long) {
-        return dispatch_gemm(piece, batch, stream);
+    return gemm_row_chunks(a, d->batch, 2, plan, [&](const GemmArgs& piece, int batch, long long) {
+        return dispatch_gemm(piece, batch, stream, plan);
     });
 }
 
-extern "C" int bya_gemm_bf16_plan(const void* A, const void* W, const void* bias, const void* C, const void* res,
-                                  const void* gate0, const void* gate1, const bya_gemm_desc* d, bya_gemm_plan* plan) {
-    if (!plan) return BYA_ERR_SHAPE;
-    GemmArgs a, piece;
-    int rc = bf16_args(A, W, bias, C, res, gate0, gate1, d, &a), nb = 0;
-    if (rc != BYA_OK) return rc;
-    const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
-    if (!chunks) return BYA_ERR_UNSUPPORTED;
-    plan_gemm(piece, nb, plan);
-    plan->row_chunks = chunks;
-    return BYA_OK;
-}
-
 // The packed q|k|v projection with the q/k LayerNorm(64) + RoPE (+ the k pre-scale) in its epilogue: one launch, q and k
-// written once (include/bya.h).  Only the persistent one-wave-per-SIMD kernel has that epilogue: anything it does not take
-// is BYA_ERR_UNSUPPORTED and the caller keeps bya_gemm_bf16 + bya_qknorm_rope.
-extern "C" int bya_gemm_qkv_norm_rope(const void* A, const void* W, const void* bias, void* C, const bya_gemm_desc* d,
-                                      const bya_qknorm_desc* n, hipStream_t stream) {
+// written once (include/bya.h).  Only the persistent one-wave-per-SIMD kernels have that epilogue: anything they do not take
+// is BYA_ERR_UNSUPPORTED and the caller keeps bya_gemm_bf16 + bya_qknorm_rope.  Launch (plan == nullptr) and plan query.
+int qkn_gemm(const void* A, const void* W, const void* bias, const void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n,
+             hipStream_t stream, bya_gemm_plan* plan) {
     GemmArgs a;
     const int rc0 = qkn_args(A, W, bias, C, d, n, &a);
     if (rc0 != BYA_OK) return rc0;
+    // the row plan (0: 256-row tiles, 1: 128-row tiles, 2: rows [0, m0) on 256-row tiles, the rest on 128-row tiles)
     int m0 = 0;
-    const int plan = qkn_plan(a, d->batch, &m0);
-    if (plan == 1) return bya_launch_gemm128p_qkn(&a, d->batch, stream);
-    if (plan == 2) {                                             // rows [0, m0): 256-row tiles; the rest: 128-row tiles
-        GemmArgs lo = a, hi = a;
-        lo.M = m0;
-        hi.M = a.M - m0;
-        hi.A += (long long)m0 * a.lda;
-        hi.C += (long long)m0 * a.ldc;
-        // the rotary table's row of token m is m - text_rows: the second launch's token 0 is token m0
-        hi.qkn_text_rows = a.qkn_text_rows > m0 ? a.qkn_text_rows - m0 : 0;
-        if (a.qkn_cos && m0 > a.qkn_text_rows) {
-            hi.qkn_cos = a.qkn_cos + (long long)(m0 - a.qkn_text_rows) * 64;
-            hi.qkn_sin = a.qkn_sin + (long long)(m0 - a.qkn_text_rows) * 64;
-        }
+    const int rows = p128_eligible(a) ? plan_rows_qkn(a.M, a.N, d->batch, &m0) : 0;
+    if (plan) {
+        gemm_plan_whole(plan, rows == 1 ? BYA_GEMM_PATH_P128 : BYA_GEMM_PATH_P256, 1);
+        if (rows == 2) { plan->m0 = m0; plan->tail = BYA_GEMM_PATH_P128; }
+        return BYA_OK;
+    }
+    if (rows == 1) return bya_launch_gemm128p_qkn(&a, d->batch, stream);
+    if (rows == 2) {
+        const GemmArgs lo = gemm_rows(a, 0, 0, m0, 2), hi = gemm_rows(a, 0, m0, a.M - m0, 2);
         const int rc = bya_launch_gemm256p_qkn(&lo, 1, stream);
         return rc != BYA_OK ? rc : bya_launch_gemm128p_qkn(&hi, 1, stream);
     }
     return bya_launch_gemm256p_qkn(&a, d->batch, stream);
 }
+}  // namespace
+
+extern "C" int bya_gemm_bf16(const void* A, const void* W, const void* bias, void* C, const void* res,
+                             const void* gate0, const void* gate1, const bya_gemm_desc* d, hipStream_t stream) {
+    return bf16_gemm(A, W, bias, C, res, gate0, gate1, d, stream, nullptr);
+}
+
+extern "C" int bya_gemm_bf16_plan(const void* A, const void* W, const void* bias, const void* C, const void* res,
+                                  const void* gate0, const void* gate1, const bya_gemm_desc* d, bya_gemm_plan* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    return bf16_gemm(A, W, bias, C, res, gate0, gate1, d, nullptr, plan);
+}
+
+extern "C" int bya_gemm_qkv_norm_rope(const void* A, const void* W, const void* bias, void* C, const bya_gemm_desc* d,
+                                      const bya_qknorm_desc* n, hipStream_t stream) {
+    return qkn_gemm(A, W, bias, C, d, n, stream, nullptr);
+}
 
 extern "C" int bya_gemm_qkv_norm_rope_plan(const void* A, const void* W, const void* bias, const void* C, const bya_gemm_desc* d,
                                            const bya_qknorm_desc* n, bya_gemm_plan* p) {
     if (!p) return BYA_ERR_SHAPE;
-    GemmArgs a;
-    const int rc = qkn_args(A, W, bias, C, d, n, &a);
-    if (rc != BYA_OK) return rc;
-    int m0 = 0;
-    const int plan = qkn_plan(a, d->batch, &m0);
-    p->path = plan == 1 ? BYA_GEMM_PATH_P128 : BYA_GEMM_PATH_P256;
-    p->m0 = plan == 2 ? m0 : 0;
-    p->tail = plan == 2 ? BYA_GEMM_PATH_P128 : -1;
-    p->split_k = 0;
-    p->row_chunks = 1;
-    return BYA_OK;
+    return qkn_gemm(A, W, bias, C, d, n, nullptr, p);
 }
 
 namespace {
@@ -723,7 +688,7 @@ int launch_skinny(const GemmArgs& a0, int nbatch, hipStream_t stream) {
 
 // Which kernels a launch runs (bya_gemm_bf16 and its query bya_gemm_bf16_plan).
 void plan_gemm(const GemmArgs& a, int nbatch, bya_gemm_plan* p) {
-    p->path = -1; p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = 1;
+    gemm_plan_whole(p, -1, 1);
     const bool ws = a.ws_counters != nullptr;
     const int forced = bya_opt(BYA_OPT_GEMM_TILE);              // tuning / test option
     const bool splitk = ws && bya_opt(BYA_OPT_GEMM_SPLITK) != 0 && a.K / BK >= 2 * bya_gemm_split_min_ktiles() && v4_eligible(a) &&
@@ -781,20 +746,17 @@ int launch_path(int path, const GemmArgs& a, int batch, hipStream_t stream) {
     }
 }
 
-int dispatch_gemm(const GemmArgs& a, int nbatch, hipStream_t stream) {
+// One piece of a bya_gemm_bf16 launch on the kernels plan_gemm names; a plan query (plan != nullptr) gets that answer instead
+int dispatch_gemm(const GemmArgs& a, int nbatch, hipStream_t stream, bya_gemm_plan* plan) {
     bya_gemm_plan p;
     plan_gemm(a, nbatch, &p);
+    if (plan) {
+        *plan = p;
+        return BYA_OK;
+    }
     if (p.m0 > 0) {                                              // rows [0, m0) on 256 x 256 tiles, the rest on `tail`
-        GemmArgs lo = a, hi = a;
-        lo.M = p.m0;
-        hi.M = a.M - p.m0;
-        hi.A += (long long)p.m0 * a.lda;
-        hi.C += (long long)p.m0 * a.ldc;
-        if (hi.res) hi.res += (long long)p.m0 * a.ldres;
-        if (hi.bias_rowscale) hi.bias_rowscale += p.m0;
-        hi.gate_split = a.gate_split > p.m0 ? a.gate_split - p.m0 : 0;
-        const int rc = launch_path(p.path, lo, 1, stream);
-        return rc != BYA_OK ? rc : launch_path(p.tail, hi, 1, stream);
+        const int rc = launch_path(p.path, gemm_rows(a, 0, 0, p.m0, 2), 1, stream);
+        return rc != BYA_OK ? rc : launch_path(p.tail, gemm_rows(a, 0, p.m0, a.M - p.m0, 2), 1, stream);
     }
     return launch_path(p.path, a, nbatch, stream);
 }
@@ -811,15 +773,8 @@ extern "C" int bya_gemm_skinny_bf16(const void* A, const void* W, const void* bi
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return BYA_ERR_SHAPE;
     if (d->act < 0 || d->act > 6) return BYA_ERR_UNSUPPORTED;
     GemmArgs a;
-    a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C;
-    a.res = (const bf16_t*)res; a.gate0 = nullptr; a.gate1 = nullptr;
-    a.M = d->M; a.N = d->N; a.K = d->K;
-    a.lda = d->lda; a.ldw = d->ldw; a.ldc = d->ldc; a.ldres = d->ldres;
-    a.a_bs = d->a_batch_stride; a.c_bs = d->c_batch_stride; a.res_bs = d->res_batch_stride;
-    a.gate_bs = 0; a.gate_split = 0; a.act = d->act; a.leaky = 0.01f;
-    a.n_split = d->n_split; a.c_split_stride = d->c_split_stride;
-    a.bias_rowscale = d->bias_rowscale; a.alpha = d->alpha == 0.0f ? 1.0f : d->alpha;
-    a.ws_counters = nullptr; a.ws_slabs = nullptr;
+    gemm_fill_args(A, W, bias, C, res, nullptr, nullptr, d, &a);
+    a.gate_bs = 0; a.gate_split = 0;                     // no gates on this path (launch_skinny keeps its fold in gate_split)
     if (!skinny_eligible(a)) return BYA_ERR_UNSUPPORTED;
     return launch_skinny(a, d->batch, stream);
 }

@@ -1,4 +1,6 @@
-// Shared by the GEMM translation units (gemm.hip, gemm_v4.hip, gemm_fp8.hip): argument block, fused epilogue, LDS read helper.
+// Shared by the GEMM translation units (gemm.hip, gemm_v4 / v5 / v6.hip, gemm_fp8.hip, gemm_fp8_v4.hip, gemm_fp8_v4_qkn.hip,
+// gemm_mx.hip, gemm_mx_v4.hip) and the implicit-GEMM convolution (vae.hip): argument block, fused epilogue, LDS read helper, and
+// the host side every GEMM entry point shares -- descriptor -> GemmArgs, the epilogue-side checks, the row cut, the plan fill.
 #pragma once
 #include "bya_common.h"
 #include "../../include/bya.h"
@@ -188,8 +190,8 @@ __device__ __forceinline__ void ds_read128(T& dst, uint32_t addr) {
 // Every epilogue here addresses C and the residual as  base(z) + 32-bit byte offset  under num_records = 0x7fffffff: an
 // element whose byte offset reaches 2^31 - 1 would be silently dropped on store and read as zero (and offsets past 4 GiB
 // would wrap onto valid rows).  97 frames at 720 x 1280 are 90226 joint rows: the MLP's [90226, 12288] bf16 activation is
-// 2.2 GB.  Such a launch is cut into row chunks (and batch entries) that each stay inside the reach; `run(args, batch,
-// row0)` launches one piece, row0 = index of its first row in per-row side arrays ([batch * M] fp32 scales).
+// 2.2 GB.  Such a launch is cut into row chunks (and batch entries) that each stay inside the reach (gemm_row_chunks); `run(args,
+// batch, row0)` launches one piece, row0 = index of its first row in per-row side arrays ([batch * M] fp32 scales).
 inline long long gemm_span_bytes(const GemmArgs& a, int M, bool res) {
     const long long ld = res ? a.ldres : a.ldc;
     const long long col = (!res && a.n_split > 0) ? (long long)(a.N / a.n_split - 1) * a.c_split_stride + a.n_split - 1
@@ -210,40 +212,83 @@ inline int gemm_chunk_rows(const GemmArgs& a) {
     return gemm_rows_reachable(a, chunk) ? chunk : 0;
 }
 
-// the plan queries (include/bya.h bya_gemm_plan): the first piece gemm_row_chunks runs, its batch, and the number of pieces
-// (0: BYA_ERR_UNSUPPORTED)
-inline int gemm_first_chunk(const GemmArgs& a, int batch, GemmArgs* piece, int* piece_batch) {
-    const int chunk = gemm_chunk_rows(a);
-    *piece = a;
-    *piece_batch = batch;
-    if (chunk == a.M || chunk == 0) return chunk == 0 ? 0 : 1;
-    piece->M = chunk;                                   // (row 0 of batch entry 0: the pointers stay)
-    *piece_batch = 1;
-    return batch * ((a.M + chunk - 1) / chunk);
+// The piece of launch `a` that starts at row m0 of batch entry z and has `rows` rows, as a launch of batch 1 (z = 0: of a's batch):
+// every per-row and per-batch-entry base moves there -- A (a_elem_bytes per element: 2 for bf16, 1 for fp8 / MX codes), C, the
+// residual, the per-row bias scale, both gate vectors -- and what counts rows from the launch's first one (gate_split, the
+// q/k-norm epilogue's text rows and its rotary table, whose row of token m is m - text_rows) is re-based on m0.  Null pointers
+// stay null (a null gate1 means one gate for every row).
+inline GemmArgs gemm_rows(const GemmArgs& a, int z, int m0, int rows, int a_elem_bytes) {
+    GemmArgs s = a;
+    s.M = rows;
+    s.A = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(a.A) +
+                                          ((long long)z * a.a_bs + (long long)m0 * a.lda) * a_elem_bytes);
+    s.C = a.C + (long long)z * a.c_bs + (long long)m0 * a.ldc;
+    if (a.res) s.res = a.res + (long long)z * a.res_bs + (long long)m0 * a.ldres;
+    if (a.gate0) s.gate0 = a.gate0 + (long long)z * a.gate_bs;
+    if (a.gate1) s.gate1 = a.gate1 + (long long)z * a.gate_bs;
+    if (a.bias_rowscale) s.bias_rowscale = a.bias_rowscale + (long long)z * a.M + m0;
+    s.gate_split = a.gate_split > m0 ? a.gate_split - m0 : 0;
+    s.qkn_text_rows = a.qkn_text_rows > m0 ? a.qkn_text_rows - m0 : 0;
+    if (a.qkn_cos && m0 > a.qkn_text_rows) {
+        s.qkn_cos = a.qkn_cos + (long long)(m0 - a.qkn_text_rows) * 64;
+        s.qkn_sin = a.qkn_sin + (long long)(m0 - a.qkn_text_rows) * 64;
+    }
+    return s;
 }
 
+// A plan (include/bya.h bya_gemm_plan) of a whole launch on one path: no row split, no split-K
+inline int gemm_plan_whole(bya_gemm_plan* p, int path, int row_chunks) {
+    p->path = path; p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = row_chunks;
+    return BYA_OK;
+}
+
+// run(piece, batch, row0) for every piece of `a`.  A plan query (plan != nullptr; `run` then fills *plan instead of launching)
+// sees the first piece only, which stands for all of them, and gets their number.
 template <typename F>
-int gemm_row_chunks(const GemmArgs& a, int batch, int a_elem_bytes, F&& run) {
+int gemm_row_chunks(const GemmArgs& a, int batch, int a_elem_bytes, bya_gemm_plan* plan, F&& run) {
     const int chunk = gemm_chunk_rows(a);
     if (chunk == a.M) return run(a, batch, 0LL);
     if (chunk == 0) return BYA_ERR_UNSUPPORTED;        // a single 256-row block out of reach: strides too large
     for (int z = 0; z < batch; ++z)
         for (int m0 = 0; m0 < a.M; m0 += chunk) {
-            GemmArgs s = a;
-            s.M = a.M - m0 < chunk ? a.M - m0 : chunk;
-            s.A = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(a.A) +
-                                                  ((long long)z * a.a_bs + (long long)m0 * a.lda) * a_elem_bytes);
-            s.C = a.C + (long long)z * a.c_bs + (long long)m0 * a.ldc;
-            if (a.res) s.res = a.res + (long long)z * a.res_bs + (long long)m0 * a.ldres;
-            if (a.gate0) s.gate0 = a.gate0 + (long long)z * a.gate_bs;
-            if (a.gate1) s.gate1 = a.gate1 + (long long)z * a.gate_bs;      // a null gate1 stays null (one gate for every row)
-            if (a.bias_rowscale) s.bias_rowscale = a.bias_rowscale + (long long)z * a.M + m0;
-            s.gate_split = a.gate_split > m0 ? a.gate_split - m0 : 0;
-            const int rc = run(s, 1, (long long)z * a.M + m0);
+            const int rc = run(gemm_rows(a, z, m0, a.M - m0 < chunk ? a.M - m0 : chunk, a_elem_bytes), 1, (long long)z * a.M + m0);
             if (rc != BYA_OK) return rc;
+            if (plan) {
+                plan->row_chunks = batch * ((a.M + chunk - 1) / chunk);
+                return BYA_OK;
+            }
         }
     return BYA_OK;
 }
+
+// ---- host side: bya_gemm_desc -> GemmArgs.  The ONE place that copies a descriptor: a null gate1 means gate0 for every row,
+// alpha 0 means 1, no split-K workspace (bya_gemm_bf16 installs its device's afterwards).
+inline void gemm_fill_args(const void* A, const void* W, const void* bias, const void* C, const void* res, const void* gate0,
+                           const void* gate1, const bya_gemm_desc* d, GemmArgs* out) {
+    GemmArgs& a = *out;
+    a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C;
+    a.res = (const bf16_t*)res; a.gate0 = (const bf16_t*)gate0; a.gate1 = (const bf16_t*)(gate1 ? gate1 : gate0);
+    a.M = d->M; a.N = d->N; a.K = d->K;
+    a.lda = d->lda; a.ldw = d->ldw; a.ldc = d->ldc; a.ldres = d->ldres;
+    a.a_bs = d->a_batch_stride; a.c_bs = d->c_batch_stride; a.res_bs = d->res_batch_stride;
+    a.gate_bs = d->gate_batch_stride; a.gate_split = d->gate_split; a.act = d->act; a.leaky = 0.01f;
+    a.n_split = d->n_split; a.c_split_stride = d->c_split_stride;
+    a.bias_rowscale = d->bias_rowscale; a.alpha = d->alpha == 0.0f ? 1.0f : d->alpha;
+    a.ws_counters = nullptr; a.ws_slabs = nullptr;
+}
+
+// ... and the epilogue side of the checks in front of it, behind the operand side's own (K tile, lda / ldw, A / W / scale
+// pointers: by format): 8-byte epilogue accesses (BYA_ERR_ALIGN), the activation (act_ok: the format's kernels have it;
+// BYA_ERR_UNSUPPORTED), the column split (BYA_ERR_SHAPE) -- in the order callers have always seen.
+inline int gemm_epilogue_check(const void* C, const void* res, const void* bias, const void* gate0, const void* gate1,
+                               const bya_gemm_desc* d, bool act_ok) {
+    if (d->ldc % 4 || (res && d->ldres % 4)) return BYA_ERR_ALIGN;
+    if (((uintptr_t)C | (uintptr_t)res | (uintptr_t)bias | (uintptr_t)gate0 | (uintptr_t)gate1) & 7) return BYA_ERR_ALIGN;
+    if (!act_ok) return BYA_ERR_UNSUPPORTED;
+    if (d->n_split < 0 || (d->n_split > 0 && (d->n_split % 4 || d->c_split_stride % 4 || res))) return BYA_ERR_SHAPE;
+    return BYA_OK;
+}
+
 // ---- host side: the q/k-norm epilogue's arguments on the tiled / wide kernels that decide q, k or v per 64-column head
 // (bya_gemm_mx_qkv_norm_rope, bya_gemm_fp8_qkv_norm_rope).  Two steps around the operand family's own argument function:
 // qkn_norm_desc_check before it (a malformed norm descriptor: BYA_ERR_SHAPE), qkn_head_args behind it -- BYA_ERR_UNSUPPORTED:
@@ -253,6 +298,14 @@ inline int qkn_norm_desc_check(const bya_gemm_desc* d, const bya_qknorm_desc* n)
     if (!n->qw || !n->qb || !n->kw || !n->kb || n->width <= 0 || n->text_rows < 0) return BYA_ERR_SHAPE;
     if (d->M > 0 && n->text_rows < d->M && (!n->cos || !n->sin)) return BYA_ERR_SHAPE;
     return BYA_OK;
+}
+
+// bya_qknorm_desc -> GemmArgs::qkn_* (k_scale 0 means 1)
+inline void qkn_fill_norm(const bya_qknorm_desc* n, GemmArgs* out) {
+    GemmArgs& a = *out;
+    a.qkn_w[0] = (const bf16_t*)n->qw; a.qkn_b[0] = (const bf16_t*)n->qb; a.qkn_w[1] = (const bf16_t*)n->kw; a.qkn_b[1] = (const bf16_t*)n->kb;
+    a.qkn_cos = n->cos; a.qkn_sin = n->sin; a.qkn_text_rows = n->text_rows; a.qkn_width = n->width;
+    a.qkn_eps = n->eps; a.qkn_kscale = n->k_scale == 0.0f ? 1.0f : n->k_scale;
 }
 
 inline int qkn_head_args(const void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n, GemmArgs* out) {
@@ -265,9 +318,7 @@ inline int qkn_head_args(const void* C, const bya_gemm_desc* d, const bya_qknorm
          (uintptr_t)n->sin) & 15) return BYA_ERR_ALIGN;
     GemmArgs& a = *out;
     a.act = 0; a.alpha = 1.0f; a.bias_rowscale = nullptr;
-    a.qkn_w[0] = (const bf16_t*)n->qw; a.qkn_b[0] = (const bf16_t*)n->qb; a.qkn_w[1] = (const bf16_t*)n->kw; a.qkn_b[1] = (const bf16_t*)n->kb;
-    a.qkn_cos = n->cos; a.qkn_sin = n->sin; a.qkn_text_rows = n->text_rows; a.qkn_width = n->width;
-    a.qkn_eps = n->eps; a.qkn_kscale = n->k_scale == 0.0f ? 1.0f : n->k_scale;
+    qkn_fill_norm(n, out);
     // one launch: its rows and its rotary rows within the 2 GiB reach of the buffer descriptors
     if (!gemm_rows_reachable(a, a.M) || ((long long)a.M - a.qkn_text_rows) * 256 >= 0x7fffffffLL) return BYA_ERR_UNSUPPORTED;
     return BYA_OK;

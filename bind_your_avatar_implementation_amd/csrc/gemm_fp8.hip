@@ -86,21 +86,11 @@ int fp8_args(const void* A8, const float* a_scale, const void* W8, const float* 
     if (!A8 || !W8 || !a_scale || !w_scale || !C || !d) return BYA_ERR_SHAPE;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return BYA_ERR_SHAPE;
     if (d->K % BK8 != 0 || d->N % 4 != 0) return BYA_ERR_SHAPE;
-    if (d->lda % 16 || d->ldw % 16 || d->ldc % 4 || (res && d->ldres % 4)) return BYA_ERR_ALIGN;
+    if (d->lda % 16 || d->ldw % 16) return BYA_ERR_ALIGN;
     if (((uintptr_t)A8 | (uintptr_t)W8 | (uintptr_t)w_scale) & 15) return BYA_ERR_ALIGN;
-    if (((uintptr_t)C | (uintptr_t)res | (uintptr_t)bias | (uintptr_t)gate0 | (uintptr_t)gate1) & 7) return BYA_ERR_ALIGN;
-    if (!act_on_big_tiles(d->act)) return BYA_ERR_UNSUPPORTED;            // none / GELU(tanh): the DiT Linears
-    if (d->n_split < 0 || (d->n_split > 0 && (d->n_split % 4 || d->c_split_stride % 4 || res))) return BYA_ERR_SHAPE;
-    GemmArgs& a = *out;
-    a.A = (const bf16_t*)A8; a.W = (const bf16_t*)W8; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C;
-    a.res = (const bf16_t*)res; a.gate0 = (const bf16_t*)gate0; a.gate1 = (const bf16_t*)(gate1 ? gate1 : gate0);
-    a.M = d->M; a.N = d->N; a.K = d->K;
-    a.lda = d->lda; a.ldw = d->ldw; a.ldc = d->ldc; a.ldres = d->ldres;
-    a.a_bs = d->a_batch_stride; a.c_bs = d->c_batch_stride; a.res_bs = d->res_batch_stride;
-    a.gate_bs = d->gate_batch_stride; a.gate_split = d->gate_split; a.act = d->act; a.leaky = 0.01f;
-    a.n_split = d->n_split; a.c_split_stride = d->c_split_stride;
-    a.bias_rowscale = d->bias_rowscale; a.alpha = d->alpha == 0.0f ? 1.0f : d->alpha;
-    a.ws_counters = nullptr; a.ws_slabs = nullptr;
+    const int rc = gemm_epilogue_check(C, res, bias, gate0, gate1, d, act_on_big_tiles(d->act));      // none / GELU(tanh): the DiT Linears
+    if (rc != BYA_OK) return rc;
+    gemm_fill_args(A8, W8, bias, C, res, gate0, gate1, d, out);
     return BYA_OK;
 }
 
@@ -117,35 +107,34 @@ inline int fp8_path(const GemmArgs& a, int batch, const GemmArgs& piece) {
     return big && bya_gemm256p_fp8_eligible(&piece) ? BYA_GEMM_PATH_P256 : BYA_GEMM_PATH_T128X128;
 }
 constexpr int FP8_P256_GROUP_M = 4;        // row-tiles per group of the persistent kernel's tile order
+
+// bya_gemm_fp8 (plan == nullptr) and bya_gemm_fp8_plan: one body, so the query answers what the launch does
+int fp8_gemm(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias, const void* C,
+             const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d, hipStream_t stream, bya_gemm_plan* plan) {
+    GemmArgs a;
+    const int rc = fp8_args(A8, a_scale, W8, w_scale, bias, C, res, gate0, gate1, d, &a);
+    if (rc != BYA_OK) return rc;
+    return gemm_row_chunks(a, d->batch, 1, plan, [&](const GemmArgs& piece, int batch, long long row0) {
+        const int path = fp8_path(a, d->batch, piece);
+        if (plan) return gemm_plan_whole(plan, path, 1);
+        if (path == BYA_GEMM_PATH_P256)
+            return bya_launch_gemm256p_fp8(&piece, a_scale + row0, w_scale, batch, FP8_P256_GROUP_M, stream);
+        return launch_fp8<128, 128, 2, 2>(piece, a_scale + row0, w_scale, batch, stream);
+    });
+}
 }  // namespace
 
 extern "C" int bya_gemm_fp8(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias,
                             void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
                             hipStream_t stream) {
-    GemmArgs a;
-    const int rc = fp8_args(A8, a_scale, W8, w_scale, bias, C, res, gate0, gate1, d, &a);
-    if (rc != BYA_OK) return rc;
-    const int gm = FP8_P256_GROUP_M;
-    return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
-        if (fp8_path(a, d->batch, piece) == BYA_GEMM_PATH_P256)
-            return bya_launch_gemm256p_fp8(&piece, a_scale + row0, w_scale, batch, gm, stream);
-        return launch_fp8<128, 128, 2, 2>(piece, a_scale + row0, w_scale, batch, stream);
-    });
+    return fp8_gemm(A8, a_scale, W8, w_scale, bias, C, res, gate0, gate1, d, stream, nullptr);
 }
 
 extern "C" int bya_gemm_fp8_plan(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias,
                                  const void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
                                  bya_gemm_plan* p) {
     if (!p) return BYA_ERR_SHAPE;
-    GemmArgs a, piece;
-    int nb = 0;
-    const int rc = fp8_args(A8, a_scale, W8, w_scale, bias, C, res, gate0, gate1, d, &a);
-    if (rc != BYA_OK) return rc;
-    const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
-    if (!chunks) return BYA_ERR_UNSUPPORTED;
-    p->path = fp8_path(a, d->batch, piece);
-    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = chunks;
-    return BYA_OK;
+    return fp8_gemm(A8, a_scale, W8, w_scale, bias, C, res, gate0, gate1, d, nullptr, p);
 }
 
 namespace {
@@ -171,11 +160,7 @@ int fp8_qkn(const void* A8, const float* a_scale, const void* W8, const float* w
     // bya_gemm_fp8's own choice for this descriptor (one row chunk: qkn_head_args): the two kernels differ in last bits, so
     // following it is what keeps fused == two launches in every option state
     const int path = fp8_path(a, d->batch, a);
-    if (plan) {
-        plan->path = path;
-        plan->m0 = 0; plan->tail = -1; plan->split_k = 0; plan->row_chunks = 1;
-        return BYA_OK;
-    }
+    if (plan) return gemm_plan_whole(plan, path, 1);
     if (path == BYA_GEMM_PATH_P256) return bya_launch_gemm256p_fp8_qkn(&a, a_scale, w_scale, d->batch, FP8_P256_GROUP_M, stream);
     return launch_fp8<128, 128, 2, 2, true>(a, a_scale, w_scale, d->batch, stream);
 }

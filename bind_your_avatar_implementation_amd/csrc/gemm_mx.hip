@@ -465,43 +465,36 @@ int mx_args(const void* A, const void* a_scales, const void* W, const void* w_sc
     if ((long long)d->batch * d->M * (d->K / 32) >= (1LL << 31) || (long long)d->N * (d->K / 32) >= (1LL << 31))
         return BYA_ERR_SHAPE;
     if (d->lda < d->K / 32 * mx_block_bytes(a_fmt) || d->ldw < d->K / 32 * mx_block_bytes(w_fmt)) return BYA_ERR_SHAPE;
-    if (d->lda % 16 || d->ldw % 16 || d->ldc % 4 || (res && d->ldres % 4) || d->a_batch_stride % 16) return BYA_ERR_ALIGN;
+    if (d->lda % 16 || d->ldw % 16 || d->a_batch_stride % 16) return BYA_ERR_ALIGN;
     if (((uintptr_t)A | (uintptr_t)W) & 15) return BYA_ERR_ALIGN;
     if (((uintptr_t)a_scales | (uintptr_t)w_scales) & 3) return BYA_ERR_ALIGN;
-    if (((uintptr_t)C | (uintptr_t)res | (uintptr_t)bias | (uintptr_t)gate0 | (uintptr_t)gate1) & 7) return BYA_ERR_ALIGN;
-    if (!act_on_big_tiles(d->act)) return BYA_ERR_UNSUPPORTED;            // none / GELU(tanh): the DiT Linears
-    if (d->n_split < 0 || (d->n_split > 0 && (d->n_split % 4 || d->c_split_stride % 4 || res))) return BYA_ERR_SHAPE;
-    GemmArgs& a = *out;
-    a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C;
-    a.res = (const bf16_t*)res; a.gate0 = (const bf16_t*)gate0; a.gate1 = (const bf16_t*)(gate1 ? gate1 : gate0);
-    a.M = d->M; a.N = d->N; a.K = d->K;
-    a.lda = d->lda; a.ldw = d->ldw; a.ldc = d->ldc; a.ldres = d->ldres;
-    a.a_bs = d->a_batch_stride; a.c_bs = d->c_batch_stride; a.res_bs = d->res_batch_stride;
-    a.gate_bs = d->gate_batch_stride; a.gate_split = d->gate_split; a.act = d->act; a.leaky = 0.01f;
-    a.n_split = d->n_split; a.c_split_stride = d->c_split_stride;
-    a.bias_rowscale = d->bias_rowscale; a.alpha = d->alpha == 0.0f ? 1.0f : d->alpha;
-    a.ws_counters = nullptr; a.ws_slabs = nullptr;
+    const int rc = gemm_epilogue_check(C, res, bias, gate0, gate1, d, act_on_big_tiles(d->act));      // none / GELU(tanh): the DiT Linears
+    if (rc != BYA_OK) return rc;
+    gemm_fill_args(A, W, bias, C, res, gate0, gate1, d, out);
     return BYA_OK;
 }
 
+// What may take the persistent kernel of gemm_mx_v4.hip.  kernel: 0 = nothing, 1 = launches that fill it (the rule of fp8_path,
+// gemm_fp8.hip), 2 = without the tile count (tests); it is admitted for e4m3 x e4m3 always, and
+//   w4:  for e2m1 weights under e4m3 activations as well (its FMT_W = MX_E2M1 instances),
+//   fp6: for e2m3 activations (weights e2m3 or e2m1) and / or e2m3 output of the quantising epilogue as well (its FMT_A = MX_E2M3 /
+//        QOUT = MX_E2M3 instances).
+// bya_gemm_mx_call says all three in its `kernel` ARGUMENT (no option is read; w4 always, fp6 under BYA_MX_KERNEL_FP6).  The older
+// entry points name the kernel only -- option mx_kernel, bya_gemm_mx_qkv_norm_rope_on its argument -- and admit nothing else: what
+// they and their plan queries answer for e2m1 weights and for e2m3 is pinned to the tiled kernel.
+struct MxKernel { int kernel; bool w4, fp6; };
+inline MxKernel mx_kernel_option() { return MxKernel{bya_opt(BYA_OPT_MX_KERNEL), false, false}; }      // (read per launch)
+
 // The kernel of one MX GEMM launch.  By the activation format: e4m3 on 128 x 128 tiles; e2m3 on 256 x 256 tiles when the launch
-// has about a round of 256 CUs of them, or more.  kernel = 1 (2: without the tile count) asks for the persistent kernel of
-// gemm_mx_v4.hip instead, taken for e4m3 x e4m3 by the rule of fp8_path (gemm_fp8.hip): `a` = the whole launch (tile count),
-// `piece` = one row chunk of it (eligibility).  bya_gemm_mx_mixed and bya_gemm_mx_quant pass option mx_kernel,
-// bya_gemm_mx_qkv_norm_rope_on and bya_gemm_mx_call their ARGUMENT (no option is read there).  w4_persistent: whether e2m1
-// weights under e4m3 activations may take the persistent kernel as well (its FMT_W = MX_E2M1 instances) -- bya_gemm_mx_call
-// alone says so: what the older entry points and their plan queries answer for e2m1 weights is pinned to the tiled kernel.
-// fp6_persistent: whether a launch with e2m3 activations (weights e2m3 or e2m1) and / or e2m3 output of the quantising
-// epilogue may take it too (its FMT_A = MX_E2M3 / QOUT = MX_E2M3 instances) -- bya_gemm_mx_call under BYA_MX_KERNEL_FP6 alone
-// says so; without it such launches stay on the tiled kernel whatever `kernel` says, which is pinned as well.
-// quant: the quantising epilogue (out_fmt: its element format)
-inline int mx_path(const GemmArgs& a, int batch, const GemmArgs& piece, int32_t a_fmt, int32_t w_fmt, int kernel,
-                   bool w4_persistent, bool fp6_persistent, bool quant = false, int32_t out_fmt = MX_E4M3) {
+// has about a round of 256 CUs of them, or more; the persistent kernel where `k` admits the launch and it is eligible.  `a` = the
+// whole launch (tile count), `piece` = one row chunk of it (eligibility); epi: MX_EPI_BF16, MX_EPI_QKN, or the quantising
+// epilogue's element format.
+inline int mx_path(const GemmArgs& a, int batch, const GemmArgs& piece, int32_t a_fmt, int32_t w_fmt, int epi, MxKernel k) {
     const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch;
-    const bool fp6 = a_fmt == MX_E2M3 || out_fmt == MX_E2M3;
-    const bool w_ok = a_fmt == MX_E4M3 ? w_fmt == MX_E4M3 || (w4_persistent && w_fmt == MX_E2M1) : true;    // (mx_args: e2m3 or e2m1)
-    if (kernel != 0 && w_ok && (!fp6 || fp6_persistent) && (kernel == 2 || tiles256 >= 200) &&
-        bya_gemm256p_mx_eligible(&piece, quant))
+    const bool fp6 = a_fmt == MX_E2M3 || epi == MX_E2M3;
+    const bool w_ok = a_fmt == MX_E4M3 ? w_fmt == MX_E4M3 || (k.w4 && w_fmt == MX_E2M1) : true;             // (mx_args: e2m3 or e2m1)
+    if (k.kernel != 0 && w_ok && (!fp6 || k.fp6) && (k.kernel == 2 || tiles256 >= 200) &&
+        bya_gemm256p_mx_eligible(&piece, epi >= 0))
         return BYA_GEMM_PATH_P256;
     return a_fmt == MX_E2M3 && BYA_MX_E2M3_BIG_TILE && tiles256 >= 200 ? BYA_GEMM_PATH_T256X256 : BYA_GEMM_PATH_T128X128;
 }
@@ -520,41 +513,6 @@ int mx_launch(int path, const GemmArgs& a, const uint8_t* sa, const uint8_t* sw,
     });
 }
 
-int mx_plan(bya_gemm_plan* p, int path, int row_chunks) {
-    p->path = path;
-    p->m0 = 0; p->tail = -1; p->split_k = 0; p->row_chunks = row_chunks;
-    return BYA_OK;
-}
-}  // namespace
-
-extern "C" int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
-                                 void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
-                                 int32_t a_fmt, int32_t w_fmt, hipStream_t stream) {
-    GemmArgs a;
-    const int rc = mx_args(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, a_fmt, w_fmt, &a);
-    if (rc != BYA_OK) return rc;
-    const uint8_t* sa = (const uint8_t*)a_scales;
-    const long long ks = d->K / 32;
-    return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
-        const int path = mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, false);
-        return mx_launch(path, piece, sa + row0 * ks, (const uint8_t*)w_scales, nullptr, MX_EPI_BF16, a_fmt, w_fmt, batch, stream);
-    });
-}
-
-extern "C" int bya_gemm_mx_mixed_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
-                                      const void* bias, const void* C, const void* res, const void* gate0, const void* gate1,
-                                      const bya_gemm_desc* d, int32_t a_fmt, int32_t w_fmt, bya_gemm_plan* p) {
-    if (!p) return BYA_ERR_SHAPE;
-    GemmArgs a, piece;
-    int nb = 0;
-    const int rc = mx_args(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, a_fmt, w_fmt, &a);
-    if (rc != BYA_OK) return rc;
-    const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
-    if (!chunks) return BYA_ERR_UNSUPPORTED;
-    return mx_plan(p, mx_path(a, d->batch, piece, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, false), chunks);
-}
-
-namespace {
 // bya_gemm_mx_quant's arguments -> GemmArgs (C = the codes; ldc, c_bs in bytes); BYA_OK or the error that rejects them
 int mx_quant_args(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
                   const void* q_codes, const void* q_scales, const bya_gemm_desc* d, int32_t a_fmt, int32_t w_fmt,
@@ -572,33 +530,7 @@ int mx_quant_args(const void* A, const void* a_scales, const void* W, const void
     e.ldres = 0; e.res_batch_stride = 0; e.gate_batch_stride = 0; e.gate_split = 0; e.c_split_stride = 0;
     return mx_args(A, a_scales, W, w_scales, bias, q_codes, nullptr, nullptr, nullptr, &e, a_fmt, w_fmt, out);
 }
-}  // namespace
 
-// bya_gemm_mx_mixed whose epilogue writes the MX codes and scale bytes of its bf16-rounded result: byte for byte
-// bya_gemm_mx_mixed followed by bya_quantize_mx(out_fmt), without the bf16 tensor.  The stores are plain 64-bit-addressed
-// vector stores, so no launch is cut into row chunks.
-extern "C" int bya_gemm_mx_quant(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
-                                 void* q_codes, void* q_scales, const bya_gemm_desc* d, int32_t a_fmt, int32_t w_fmt,
-                                 int32_t out_fmt, hipStream_t stream) {
-    GemmArgs a;
-    const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
-    if (rc != BYA_OK) return rc;
-    const int path = mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, false, true, out_fmt);
-    return mx_launch(path, a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, (uint8_t*)q_scales, out_fmt, a_fmt, w_fmt,
-                     d->batch, stream);
-}
-
-extern "C" int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
-                                      const void* bias, const void* q_codes, const void* q_scales, const bya_gemm_desc* d,
-                                      int32_t a_fmt, int32_t w_fmt, int32_t out_fmt, bya_gemm_plan* p) {
-    if (!p) return BYA_ERR_SHAPE;
-    GemmArgs a;
-    const int rc = mx_quant_args(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, &a);
-    if (rc != BYA_OK) return rc;
-    return mx_plan(p, mx_path(a, d->batch, a, a_fmt, w_fmt, bya_opt(BYA_OPT_MX_KERNEL), false, false, true, out_fmt), 1);
-}
-
-namespace {
 // bya_gemm_mx_qkv_norm_rope's arguments -> GemmArgs; BYA_ERR_UNSUPPORTED: not this epilogue's shape (the caller keeps
 // bya_gemm_mx_mixed + bya_qknorm_rope); malformed arguments: the errors of qkn_norm_desc_check / qkn_head_args (gemm_common.h) and mx_args
 int mx_qkn_args(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, const void* C,
@@ -611,92 +543,68 @@ int mx_qkn_args(const void* A, const void* a_scales, const void* W, const void* 
     if (rc != BYA_OK) return rc;
     return qkn_head_args(C, d, n, out);                  // (gemm_common.h: shared with bya_gemm_fp8_qkv_norm_rope)
 }
-}  // namespace
 
-// bya_gemm_mx_mixed of the packed q|k|v (or q|k) projection with the per-head q/k LayerNorm(64) + RoPE in its epilogue: bit for
-// bit bya_gemm_mx_mixed(..., n_split) followed by bya_qknorm_rope, q and k written once.  The kernel is named by an ARGUMENT
-// (no option is read): 0 = the tiled kernel of mx_path, as every MX GEMM; 1 = the persistent 256 x 256 kernel
-// (gemm256p_mx_kernel<MX_EPI_QKN>, the same bits) where the launch fills it and is eligible, else the tiled one; 2 (tests):
-// without the tile count.  Always one launch.
-extern "C" int bya_gemm_mx_qkv_norm_rope_on(const void* A, const void* a_scales, const void* W, const void* w_scales,
-                                            const void* bias, void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* d,
-                                            const bya_qknorm_desc* n, int32_t kernel, hipStream_t stream) {
-    if (kernel < 0 || kernel > 2) return BYA_ERR_SHAPE;
-    GemmArgs a;
-    const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
-    if (rc != BYA_OK) return rc;
-    return mx_launch(mx_path(a, d->batch, a, fmt, w_fmt, kernel, false, false), a, (const uint8_t*)a_scales, (const uint8_t*)w_scales, nullptr,
-                     MX_EPI_QKN, fmt, w_fmt, d->batch, stream);
-}
-
-extern "C" int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
-                                                 const void* bias, const void* C, int32_t fmt, int32_t w_fmt,
-                                                 const bya_gemm_desc* d, const bya_qknorm_desc* n, int32_t kernel,
-                                                 bya_gemm_plan* p) {
-    if (!p || kernel < 0 || kernel > 2) return BYA_ERR_SHAPE;
-    GemmArgs a;
-    const int rc = mx_qkn_args(A, a_scales, W, w_scales, bias, C, d, n, fmt, w_fmt, &a);
-    if (rc != BYA_OK) return rc;
-    return mx_plan(p, mx_path(a, d->batch, a, fmt, w_fmt, kernel, false, false), 1);
-}
-
-// ... on the tiled kernel (kernel = 0)
-extern "C" int bya_gemm_mx_qkv_norm_rope(const void* A, const void* a_scales, const void* W, const void* w_scales,
-                                         const void* bias, void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* d,
-                                         const bya_qknorm_desc* n, hipStream_t stream) {
-    return bya_gemm_mx_qkv_norm_rope_on(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, 0, stream);
-}
-
-extern "C" int bya_gemm_mx_qkv_norm_rope_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
-                                              const void* bias, const void* C, int32_t fmt, int32_t w_fmt,
-                                              const bya_gemm_desc* d, const bya_qknorm_desc* n, bya_gemm_plan* p) {
-    return bya_gemm_mx_qkv_norm_rope_on_plan(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, 0, p);
-}
-
-namespace {
-// bya_gemm_mx_call (plan == nullptr) and bya_gemm_mx_call_plan: one body, so the query answers what the launch does.  The
-// epilogue's own argument function runs first and refuses what its old entry point refuses, with its code; then mx_path with
-// the call's kernel and e2m1 weights admitted to the persistent kernel.
-int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, hipStream_t stream, bya_gemm_plan* plan) {
+// Every MX GEMM entry point of this file, launch (plan == nullptr) and plan query: one body, so the query answers what the
+// launch does.  The epilogue is the one `c` names (norm: q/k-norm + RoPE; q_scales: quantising; else bf16); its own argument
+// function refuses what it always refused, with its code; then mx_path with what `k` admits to the persistent kernel
+// (c->kernel itself is not read here).  Only the bf16 epilogue is cut into row chunks: the q/k-norm launch is one piece by its
+// argument check, and the quantising epilogue stores through 64-bit addresses.
+int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, MxKernel k, hipStream_t stream, bya_gemm_plan* plan) {
     if (!c || !d) return BYA_ERR_SHAPE;
-    if (c->kernel < 0 || (c->kernel & ~BYA_MX_KERNEL_FP6) > 2) return BYA_ERR_SHAPE;       // 0, 1, 2, 16, 17, 18
-    const int kernel = c->kernel & ~BYA_MX_KERNEL_FP6;
-    const bool fp6 = (c->kernel & BYA_MX_KERNEL_FP6) != 0;
     if (c->norm && c->q_scales) return BYA_ERR_SHAPE;
     if ((c->norm || c->q_scales) && (c->res || c->gate0 || c->gate1)) return BYA_ERR_SHAPE;
-    const uint8_t* const sa = (const uint8_t*)c->a_scales;
-    const uint8_t* const sw = (const uint8_t*)c->w_scales;
     GemmArgs a;
+    int rc, epi = MX_EPI_BF16;
     if (c->norm) {
-        const int rc = mx_qkn_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, d, c->norm, c->a_fmt, c->w_fmt, &a);
-        if (rc != BYA_OK) return rc;
-        const int path = mx_path(a, d->batch, a, c->a_fmt, c->w_fmt, kernel, true, fp6);
-        if (plan) return mx_plan(plan, path, 1);
-        return mx_launch(path, a, sa, sw, nullptr, MX_EPI_QKN, c->a_fmt, c->w_fmt, d->batch, stream);
+        rc = mx_qkn_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, d, c->norm, c->a_fmt, c->w_fmt, &a);
+        epi = MX_EPI_QKN;
+    } else if (c->q_scales) {
+        rc = mx_quant_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, c->q_scales, d, c->a_fmt, c->w_fmt, c->out_fmt, &a);
+        epi = c->out_fmt;
+    } else {
+        rc = mx_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, c->res, c->gate0, c->gate1, d, c->a_fmt, c->w_fmt, &a);
     }
-    if (c->q_scales) {
-        const int rc = mx_quant_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, c->q_scales, d, c->a_fmt, c->w_fmt,
-                                     c->out_fmt, &a);
-        if (rc != BYA_OK) return rc;
-        const int path = mx_path(a, d->batch, a, c->a_fmt, c->w_fmt, kernel, true, fp6, true, c->out_fmt);
-        if (plan) return mx_plan(plan, path, 1);
-        return mx_launch(path, a, sa, sw, (uint8_t*)c->q_scales, c->out_fmt, c->a_fmt, c->w_fmt, d->batch, stream);
-    }
-    const int rc = mx_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, c->res, c->gate0, c->gate1, d, c->a_fmt,
-                           c->w_fmt, &a);
     if (rc != BYA_OK) return rc;
-    if (plan) {
-        GemmArgs piece;
-        int nb = 0;
-        const int chunks = gemm_first_chunk(a, d->batch, &piece, &nb);
-        if (!chunks) return BYA_ERR_UNSUPPORTED;
-        return mx_plan(plan, mx_path(a, d->batch, piece, c->a_fmt, c->w_fmt, kernel, true, fp6), chunks);
-    }
     const long long ks = d->K / 32;
-    return gemm_row_chunks(a, d->batch, 1, [&](const GemmArgs& piece, int batch, long long row0) {
-        const int path = mx_path(a, d->batch, piece, c->a_fmt, c->w_fmt, kernel, true, fp6);
-        return mx_launch(path, piece, sa + row0 * ks, sw, nullptr, MX_EPI_BF16, c->a_fmt, c->w_fmt, batch, stream);
-    });
+    auto run = [&](const GemmArgs& piece, int batch, long long row0) {
+        const int path = mx_path(a, d->batch, piece, c->a_fmt, c->w_fmt, epi, k);
+        if (plan) return gemm_plan_whole(plan, path, 1);
+        return mx_launch(path, piece, (const uint8_t*)c->a_scales + row0 * ks, (const uint8_t*)c->w_scales, (uint8_t*)c->q_scales, epi,
+                         c->a_fmt, c->w_fmt, batch, stream);
+    };
+    return epi == MX_EPI_BF16 ? gemm_row_chunks(a, d->batch, 1, plan, run) : run(a, d->batch, 0LL);
+}
+
+// bya_gemm_mx_call's kernel argument: 0, 1, 2, or BYA_MX_KERNEL_FP6 + one of them; e2m1 weights are admitted with either
+bool mx_kernel_of_call(const bya_mx_gemm_call* c, MxKernel* k) {
+    if (!c || c->kernel < 0 || (c->kernel & ~BYA_MX_KERNEL_FP6) > 2) return false;
+    *k = MxKernel{c->kernel & ~BYA_MX_KERNEL_FP6, true, (c->kernel & BYA_MX_KERNEL_FP6) != 0};
+    return true;
+}
+
+// The older entry points: their arguments as a call on the kernel `kernel` names, nothing else admitted to it.  Each keeps the
+// checks mx_call has no reason for -- a null q_scales / norm would name another epilogue there.
+int mx_mixed(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, const void* C, const void* res,
+             const void* gate0, const void* gate1, const bya_gemm_desc* d, int32_t a_fmt, int32_t w_fmt, hipStream_t stream,
+             bya_gemm_plan* plan) {
+    const bya_mx_gemm_call c = {A, a_scales, W, w_scales, bias, (void*)C, res, gate0, gate1, nullptr, nullptr, a_fmt, w_fmt, MX_E4M3, 0};
+    return mx_call(&c, d, mx_kernel_option(), stream, plan);
+}
+
+int mx_quant(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, const void* q_codes,
+             const void* q_scales, const bya_gemm_desc* d, int32_t a_fmt, int32_t w_fmt, int32_t out_fmt, hipStream_t stream,
+             bya_gemm_plan* plan) {
+    if (!q_scales) return BYA_ERR_SHAPE;
+    const bya_mx_gemm_call c = {A, a_scales, W, w_scales, bias, (void*)q_codes, nullptr, nullptr, nullptr, (void*)q_scales, nullptr,
+                                a_fmt, w_fmt, out_fmt, 0};
+    return mx_call(&c, d, mx_kernel_option(), stream, plan);
+}
+
+int mx_qkn_on(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, const void* C, int32_t fmt,
+              int32_t w_fmt, const bya_gemm_desc* d, const bya_qknorm_desc* n, int32_t kernel, hipStream_t stream, bya_gemm_plan* plan) {
+    if (!n || kernel < 0 || kernel > 2) return BYA_ERR_SHAPE;            // (16, the flag bit of bya_gemm_mx_call, is no kernel here)
+    const bya_mx_gemm_call c = {A, a_scales, W, w_scales, bias, (void*)C, nullptr, nullptr, nullptr, nullptr, n, fmt, w_fmt, MX_E4M3, 0};
+    return mx_call(&c, d, MxKernel{kernel, false, false}, stream, plan);
 }
 }  // namespace
 
@@ -706,12 +614,29 @@ int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, hipStream_t strea
 // BYA_MX_KERNEL_FP6 added (17 / 18; 16 = 0) launches with e2m3 activations and / or e2m3 output of the quantising epilogue are
 // admitted as well, by the same rule; without it they stay on the tiled kernel.
 extern "C" int bya_gemm_mx_call(const bya_mx_gemm_call* call, const bya_gemm_desc* desc, hipStream_t stream) {
-    return mx_call(call, desc, stream, nullptr);
+    MxKernel k;
+    if (!mx_kernel_of_call(call, &k)) return BYA_ERR_SHAPE;
+    return mx_call(call, desc, k, stream, nullptr);
 }
 
 extern "C" int bya_gemm_mx_call_plan(const bya_mx_gemm_call* call, const bya_gemm_desc* desc, bya_gemm_plan* plan) {
-    if (!plan) return BYA_ERR_SHAPE;
-    return mx_call(call, desc, nullptr, plan);
+    MxKernel k;
+    if (!plan || !mx_kernel_of_call(call, &k)) return BYA_ERR_SHAPE;
+    return mx_call(call, desc, k, nullptr, plan);
+}
+
+// Activations e4m3 / e2m3, weights in the same format or in e2m1; the kernel by option mx_kernel
+extern "C" int bya_gemm_mx_mixed(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                                 void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
+                                 int32_t a_fmt, int32_t w_fmt, hipStream_t stream) {
+    return mx_mixed(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, a_fmt, w_fmt, stream, nullptr);
+}
+
+extern "C" int bya_gemm_mx_mixed_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                      const void* bias, const void* C, const void* res, const void* gate0, const void* gate1,
+                                      const bya_gemm_desc* d, int32_t a_fmt, int32_t w_fmt, bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    return mx_mixed(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, a_fmt, w_fmt, nullptr, p);
 }
 
 // Both operands in one format: e4m3 or e2m3 (e2m1 activations are not offered)
@@ -719,12 +644,61 @@ extern "C" int bya_gemm_mx(const void* A, const void* a_scales, const void* W, c
                            void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
                            int32_t fmt, hipStream_t stream) {
     if (fmt != MX_E4M3 && fmt != MX_E2M3) return BYA_ERR_SHAPE;
-    return bya_gemm_mx_mixed(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, fmt, fmt, stream);
+    return mx_mixed(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, fmt, fmt, stream, nullptr);
 }
 
 extern "C" int bya_gemm_mx_plan(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
                                 const void* C, const void* res, const void* gate0, const void* gate1, const bya_gemm_desc* d,
                                 int32_t fmt, bya_gemm_plan* p) {
-    if (fmt != MX_E4M3 && fmt != MX_E2M3) return BYA_ERR_SHAPE;
-    return bya_gemm_mx_mixed_plan(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, fmt, fmt, p);
+    if (!p || (fmt != MX_E4M3 && fmt != MX_E2M3)) return BYA_ERR_SHAPE;
+    return mx_mixed(A, a_scales, W, w_scales, bias, C, res, gate0, gate1, d, fmt, fmt, nullptr, p);
+}
+
+// bya_gemm_mx_mixed whose epilogue writes the MX codes and scale bytes of its bf16-rounded result: byte for byte
+// bya_gemm_mx_mixed followed by bya_quantize_mx(out_fmt), without the bf16 tensor.  The stores are plain 64-bit-addressed
+// vector stores, so no launch is cut into row chunks.
+extern "C" int bya_gemm_mx_quant(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                                 void* q_codes, void* q_scales, const bya_gemm_desc* d, int32_t a_fmt, int32_t w_fmt,
+                                 int32_t out_fmt, hipStream_t stream) {
+    return mx_quant(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, stream, nullptr);
+}
+
+extern "C" int bya_gemm_mx_quant_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                      const void* bias, const void* q_codes, const void* q_scales, const bya_gemm_desc* d,
+                                      int32_t a_fmt, int32_t w_fmt, int32_t out_fmt, bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    return mx_quant(A, a_scales, W, w_scales, bias, q_codes, q_scales, d, a_fmt, w_fmt, out_fmt, nullptr, p);
+}
+
+// bya_gemm_mx_mixed of the packed q|k|v (or q|k) projection with the per-head q/k LayerNorm(64) + RoPE in its epilogue: bit for
+// bit bya_gemm_mx_mixed(..., n_split) followed by bya_qknorm_rope, q and k written once.  The kernel is named by an ARGUMENT
+// (no option is read): 0 = the tiled kernel of mx_path, as every MX GEMM; 1 = the persistent 256 x 256 kernel
+// (gemm256p_mx_kernel<MX_EPI_QKN>, the same bits) where the launch fills it and is eligible, else the tiled one; 2 (tests):
+// without the tile count.  Always one launch.
+extern "C" int bya_gemm_mx_qkv_norm_rope_on(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                            const void* bias, void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* d,
+                                            const bya_qknorm_desc* n, int32_t kernel, hipStream_t stream) {
+    return mx_qkn_on(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, kernel, stream, nullptr);
+}
+
+extern "C" int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                                 const void* bias, const void* C, int32_t fmt, int32_t w_fmt,
+                                                 const bya_gemm_desc* d, const bya_qknorm_desc* n, int32_t kernel,
+                                                 bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    return mx_qkn_on(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, kernel, nullptr, p);
+}
+
+// ... on the tiled kernel (kernel = 0)
+extern "C" int bya_gemm_mx_qkv_norm_rope(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                         const void* bias, void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* d,
+                                         const bya_qknorm_desc* n, hipStream_t stream) {
+    return mx_qkn_on(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, 0, stream, nullptr);
+}
+
+extern "C" int bya_gemm_mx_qkv_norm_rope_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                              const void* bias, const void* C, int32_t fmt, int32_t w_fmt,
+                                              const bya_gemm_desc* d, const bya_qknorm_desc* n, bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    return mx_qkn_on(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, 0, nullptr, p);
 }

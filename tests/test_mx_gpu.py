@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_fro
+from exact_gemm import SENTINEL, assert_exact
 from test_mx_cpu import BITS, dequant_mx, e2m3_encode, pack6, quant_mx_ref
 
 pytestmark = pytest.mark.gpu
@@ -167,6 +168,30 @@ def test_gemm_mx_batched_operands(dev):
         one = torch.empty(300, 256, dtype=torch.bfloat16, device=dev)
         ops.gemm_mx(ac[z].contiguous(), asc[z].contiguous(), wc, wsc, one, fmt)
         assert torch.equal(out[z], one)
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_gemm_mx_row_chunks_past_2gib_on_exact_data(dev, fmt):
+    """An MX launch cut into row chunks: ``out`` is the first 128 columns of rows 2^21 + 64 elements (4 MiB + 128 bytes) apart,
+    so row 512 starts at byte offset 2^31 + 65536 -- past the reach of the epilogue's buffer descriptor -- and the launch runs as
+    pieces of 256, 256 and 1 rows.  Each piece must start at ITS rows of the one-byte codes (row0 * lda bytes), of the scale bytes
+    (row0 * K / 32) and of the output: on exact data (operand-map test above) a piece fed another piece's rows or scales is wrong
+    in almost every element.  The rest of the buffer holds a canary."""
+    from bind_your_avatar_implementation_amd import ops
+    M, N, K, LD = 513, 128, 128, 2 ** 21 + 64
+    ac, asc = exact_operand(M, K, fmt, seed=11)
+    wc, wsc = exact_operand(N, K, fmt, seed=12)
+    meta = lambda t: torch.empty(t.shape, dtype=t.dtype, device="meta")
+    plan = ops.gemm_mx_plan(meta(ac), meta(asc), meta(wc), meta(wsc), torch.empty(M, LD, dtype=torch.bfloat16, device="meta")[:, :N], fmt)
+    assert plan["row_chunks"] == 3 and plan["m0"] == 0, plan             # (needs no GPU: 256 + 256 + 1 rows)
+    buf = torch.full((M, LD), SENTINEL, dtype=torch.int16, device=dev)
+    out = buf.view(torch.bfloat16)[:, :N]
+    assert ops.gemm_mx_plan(ac.to(dev), asc.to(dev), wc.to(dev), wsc.to(dev), out, fmt) == plan
+    ops.gemm_mx(ac.to(dev), asc.to(dev), wc.to(dev), wsc.to(dev), out, fmt)
+    ref = dequant_mx(ac, asc, fmt) @ dequant_mx(wc, wsc, fmt).T
+    assert_exact(out.cpu(), ref, plan, f"{fmt} {M}x{N}x{K}, ldc {LD}")
+    rows = torch.tensor([0, 255, 256, 511, 512], device=dev)
+    assert bool((buf[rows, N:N + 64] == SENTINEL).all()), "canary behind the output columns"
 
 
 # ------------------------------------------------------------------------------------------ forward level
