@@ -202,6 +202,9 @@ SIGNATURES = {
     "bya_p2p_push": [_vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp],
     "bya_p2p_wait": [_vp, _i32, _vp, _i64, _vp],
     "bya_p2p_exchange": [_vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp],
+    "bya_p2p_push_verified": [_vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "bya_p2p_exchange_verified": [_vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "bya_p2p_verify": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
     "bya_p2p_poison": [_vp, _i32, _vp, _i64, _vp],
     "bya_p2p_alloc": [_i64, _i32, _c.POINTER(_vp)],
     "bya_p2p_free": [_vp],

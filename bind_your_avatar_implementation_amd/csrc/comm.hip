@@ -124,6 +124,9 @@ extern "C" int bya_alltoall_router(const void* send, void* recv, const int64_t* 
 // returns, so the remaining launches of the step -- and of the clip -- run through at full speed on garbage.
 // bya_p2p_poison -- the last launch of a sharded step -- overwrites the step's output with NaN if any channel of the group
 // carries a time-out, so a result made from a stale buffer cannot be used, and the host raises at the next check.
+// Opt-in (BYA_SP_VERIFY=all in the host module; include/bya.h has the checksum and the record): the VERIFY instances of the push
+// kernel also sum every piece they copy and send the sums ahead of the flags; bya_p2p_verify, enqueued behind the wait, sums
+// the receiver's own buffers as a consumer would read them and logs exchange, sender and piece of whatever differs.
 namespace {
 
 constexpr int P2P_CHUNK = 64 * 1024;                 // bytes per workgroup iteration
@@ -132,6 +135,8 @@ constexpr int P2P_SENT = 32, P2P_EXPECT = 33, P2P_DONE = 34, P2P_TIMEOUTS = 35, 
                                                                                                    // [35] time-outs, [36] wait workgroups done
 constexpr int P2P_GROUP_TIMEOUTS = 37;               // in the group's FIRST control block only: time-outs of any channel
 constexpr int P2P_MISMATCHES = 38;                   // [38] written by the host module: steps whose exchange checksum differed between the ranks
+constexpr int P2P_XMISMATCHES = 39;                  // [39] pieces whose checksum differed from the sender's record (bya_p2p_verify; sticky)
+constexpr int P2P_GROUP_XMISMATCHES = 40;            // in the group's FIRST control block only: the same of any channel
 constexpr int P2P_WAIT_GROUPS = 16;                  // workgroups of a wait: two per XCD under round-robin dispatch
 constexpr int P2P_THREADS = 256;                    // lanes of a push workgroup: 16 waves x 4 loads of 16 bytes in flight per lane (a 4-wave
                                                      // workgroup per CU kept 16 KB in flight: 11 GB/s per CU at HBM latency)
@@ -147,8 +152,62 @@ constexpr long long P2P_DEFAULT_LIMIT_TICKS = 30ll * 100000000ll;        // s_me
 // The walk therefore goes down the columns of a [world x ceil(chunks / world)] arrangement of the chunk indices: consecutive
 // iterations -- what the workgroups of the grid work on at the same time -- are about one peer's share apart, and rank r
 // starts with the share of peer r + 1, so that the ranks do not all open on peer 0's ingress either.
+//
+// VERIFY (BYA_SP_VERIFY=all; include/bya.h defines the checksum): the words a lane has in registers anyway are added to two
+// per-lane partial sums, reduced per workgroup and chunk and added to acc[entry] with ONE pair of 64-bit atomics.  Integer sums:
+// the walk and the grid size cannot change them.  The VERIFY = false instances are the kernels as they were.
+typedef unsigned long long p2p_u64;
+
+constexpr unsigned P2P_VSUM_MOD = 65521u;
+
+// (va, vb) += the word `w` at word index with residue `m` (= index mod 65521)
+__device__ __forceinline__ void p2p_vsum1(unsigned w, unsigned m, p2p_u64& va, p2p_u64& vb) {
+    va += w;
+    vb += (p2p_u64)(w * (m + 1u));                           // < 2^16 * 2^16
+}
+
+// the 8 words of a 16-byte vector whose first word has index `widx` in its piece
+__device__ __forceinline__ void p2p_vsum8(const u32x4 v, long long widx, p2p_u64& va, p2p_u64& vb) {
+    unsigned m = (unsigned)((p2p_u64)widx % P2P_VSUM_MOD);
+    const unsigned x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        p2p_vsum1(x[k] & 0xffffu, m, va, vb);
+        m = m + 1u == P2P_VSUM_MOD ? 0u : m + 1u;
+        p2p_vsum1(x[k] >> 16, m, va, vb);
+        m = m + 1u == P2P_VSUM_MOD ? 0u : m + 1u;
+    }
+}
+
+__device__ __forceinline__ void p2p_vsum_word(unsigned w, long long widx, p2p_u64& va, p2p_u64& vb) {
+    p2p_vsum1(w, (unsigned)((p2p_u64)widx % P2P_VSUM_MOD), va, vb);
+}
+
+// sum of (va, vb) over the THREADS lanes of the workgroup, valid in thread 0 (every lane calls it; two barriers)
+template <int THREADS>
+__device__ __forceinline__ void p2p_vsum_reduce(p2p_u64& va, p2p_u64& vb) {
+    __shared__ p2p_u64 red[2 * (THREADS / 64)];
+    for (int d = 32; d > 0; d >>= 1) {
+        va += __shfl_down(va, d, 64);
+        vb += __shfl_down(vb, d, 64);
+    }
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0) {
+        red[(tid >> 6) * 2] = va;
+        red[(tid >> 6) * 2 + 1] = vb;
+    }
+    __syncthreads();
+    if (tid == 0)
+        for (int w = 1; w < THREADS / 64; ++w) {
+            va += red[w * 2];
+            vb += red[w * 2 + 1];
+        }
+    __syncthreads();                                         // (`red` is written again by the next call)
+}
+
+template <bool VERIFY>
 __device__ __forceinline__ void p2p_copy_chunks(const bya_p2p_copy* __restrict__ copies, int n_copies, long long total_chunks, int world,
-                                                int rank) {
+                                                int rank, p2p_u64* __restrict__ acc) {
     const int tid = threadIdx.x;
     const long long share = (total_chunks + world - 1) / world, walk = share * world;
     for (long long it = blockIdx.x; it < walk; it += gridDim.x) {
@@ -179,6 +238,10 @@ __device__ __forceinline__ void p2p_copy_chunks(const bya_p2p_copy* __restrict__
         const char* src = static_cast<const char*>(e.src) + row0 * e.src_pitch + col0;
         char* dst = static_cast<char*>(e.dst) + row0 * e.dst_pitch + col0;
         const bool wide = ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) && (nrows == 1 || ((e.src_pitch | e.dst_pitch | n) & 15) == 0);
+        // VERIFY: this lane's partial sums over the chunk; lg0 = logical byte offset of the chunk's first byte in its piece (rows
+        // grouped into one chunk are whole rows: row r of the chunk starts n = row_bytes logical bytes behind row r - 1)
+        p2p_u64 va = 0, vb = 0;
+        const long long lg0 = row0 * e.row_bytes + col0;
         if (wide) {
             // four independent 16-byte loads in flight per lane before the first store (one load -> one store per iteration
             // moved 0.5 TB/s against LOCAL memory: latency-bound long before any link is)
@@ -193,6 +256,12 @@ __device__ __forceinline__ void p2p_copy_chunks(const bya_p2p_copy* __restrict__
                 so = (long long)r * e.src_pitch + b;
                 d_o = (long long)r * e.dst_pitch + b;
             };
+            // VERIFY: word index in the piece of 16-byte unit t of the chunk (wide rows are whole units: n16 == n when nrows > 1)
+            auto widx = [&](int t) -> long long {
+                if (nrows == 1) return (lg0 + ((long long)t << 4)) >> 1;
+                const int r = t / per_row;
+                return (lg0 + (long long)r * n + ((long long)(t - r * per_row) << 4)) >> 1;
+            };
             int t = tid;
             for (; t + 3 * P2P_THREADS < total; t += 4 * P2P_THREADS) {
                 long long s0, s1, s2, s3, d0, d1, d2, d3;
@@ -203,19 +272,52 @@ __device__ __forceinline__ void p2p_copy_chunks(const bya_p2p_copy* __restrict__
                 __builtin_nontemporal_store(b, reinterpret_cast<u32x4*>(dst + d1));
                 __builtin_nontemporal_store(c2, reinterpret_cast<u32x4*>(dst + d2));
                 __builtin_nontemporal_store(d, reinterpret_cast<u32x4*>(dst + d3));
+                if constexpr (VERIFY) {
+                    p2p_vsum8(a, widx(t), va, vb);
+                    p2p_vsum8(b, widx(t + P2P_THREADS), va, vb);
+                    p2p_vsum8(c2, widx(t + 2 * P2P_THREADS), va, vb);
+                    p2p_vsum8(d, widx(t + 3 * P2P_THREADS), va, vb);
+                }
             }
             for (; t < total; t += P2P_THREADS) {
                 long long s0, d0;
                 off(t, s0, d0);
-                *reinterpret_cast<u32x4*>(dst + d0) = *reinterpret_cast<const u32x4*>(src + s0);
+                if constexpr (VERIFY) {
+                    const u32x4 a = *reinterpret_cast<const u32x4*>(src + s0);
+                    *reinterpret_cast<u32x4*>(dst + d0) = a;
+                    p2p_vsum8(a, widx(t), va, vb);
+                } else {
+                    *reinterpret_cast<u32x4*>(dst + d0) = *reinterpret_cast<const u32x4*>(src + s0);
+                }
             }
-            for (int b = n16 + tid * 2; b < n; b += P2P_THREADS * 2)            // (nrows == 1 here: a piece ends on a bf16 element, not on 16 bytes)
-                *reinterpret_cast<uint16_t*>(dst + b) = *reinterpret_cast<const uint16_t*>(src + b);
+            for (int b = n16 + tid * 2; b < n; b += P2P_THREADS * 2) {          // (nrows == 1 here: a piece ends on a bf16 element, not on 16 bytes)
+                if constexpr (VERIFY) {
+                    const uint16_t w = *reinterpret_cast<const uint16_t*>(src + b);
+                    *reinterpret_cast<uint16_t*>(dst + b) = w;
+                    p2p_vsum_word(w, (lg0 + b) >> 1, va, vb);
+                } else {
+                    *reinterpret_cast<uint16_t*>(dst + b) = *reinterpret_cast<const uint16_t*>(src + b);
+                }
+            }
         } else {                                                        // small odd-sized pieces (the router's logits)
             const int per_row = n >> 1, total = per_row * nrows;
             for (int t = tid; t < total; t += P2P_THREADS) {
                 const int r = nrows == 1 ? 0 : t / per_row, b = (t - r * per_row) << 1;
-                *reinterpret_cast<uint16_t*>(dst + (long long)r * e.dst_pitch + b) = *reinterpret_cast<const uint16_t*>(src + (long long)r * e.src_pitch + b);
+                if constexpr (VERIFY) {
+                    const uint16_t w = *reinterpret_cast<const uint16_t*>(src + (long long)r * e.src_pitch + b);
+                    *reinterpret_cast<uint16_t*>(dst + (long long)r * e.dst_pitch + b) = w;
+                    p2p_vsum_word(w, (lg0 + (long long)r * n + b) >> 1, va, vb);
+                } else {
+                    *reinterpret_cast<uint16_t*>(dst + (long long)r * e.dst_pitch + b) = *reinterpret_cast<const uint16_t*>(src + (long long)r * e.src_pitch + b);
+                }
+            }
+        }
+        if constexpr (VERIFY) {
+            // (every lane of the workgroup is here: `c`, and with it every `continue` above, is the same for all of them)
+            p2p_vsum_reduce<P2P_THREADS>(va, vb);
+            if (tid == 0) {
+                __hip_atomic_fetch_add(acc + 2 * i, va, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(acc + 2 * i + 1, vb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     }
@@ -255,14 +357,56 @@ __device__ __forceinline__ void p2p_wait_flags(unsigned* __restrict__ ctrl, unsi
 
 // WAIT: the same workgroups then wait for the peers' pushes of this exchange (push + wait as one launch; every workgroup has
 // finished its own copies before it starts to poll, and publishing never depends on a poller, so nothing can wait in a circle)
-template <bool WAIT>
-__global__ __launch_bounds__(P2P_THREADS) void p2p_push_kernel(const bya_p2p_copy* __restrict__ copies, int n_copies, long long total_chunks,
-                                                        unsigned* const* __restrict__ peer_ctrl, int world, int rank,
-                                                        unsigned* __restrict__ ctrl, unsigned* __restrict__ group_ctrl, long long limit_ticks) {
+// what the VERIFY instances get besides (include/bya.h, bya_p2p_push_verified); all device memory
+struct P2pVerifySend {
+    const long long* pieces;            // [n_copies][4]: destination rank, index in that rank's record, buf_id, dst_byte_offset
+    const long long* counts;            // [world]: pieces per destination rank
+    p2p_u64* acc;                       // [n_copies][2]: the sums of this exchange's pieces so far
+    long long* const* peer_rec;         // [world]: the channel's [32][REC_WORDS] block of rank p's record buffer
+};
+
+constexpr int P2P_REC_WORDS = BYA_P2P_VERIFY_REC_WORDS, P2P_REC_HALF = P2P_REC_WORDS / 2, P2P_REC_PIECE = 7;
+static_assert(2 + BYA_P2P_VERIFY_PIECES * P2P_REC_PIECE <= P2P_REC_HALF, "a record half holds the header and every piece");
+
+__device__ __forceinline__ void p2p_rec_store(long long* p, long long v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// VERIFY, the publishing workgroup's thread 0, before the fence and the flags: one record per destination rank (every
+// workgroup's atomics on `acc` are ordered before its count in P2P_DONE, which this thread has acquired), then `acc` is
+// zeroed for the next launch on this table, as P2P_DONE is
+__device__ __forceinline__ void p2p_write_records(const bya_p2p_copy* __restrict__ copies, int n_copies, int world, int rank, unsigned seq,
+                                                  const P2pVerifySend vs) {
+    const int half = (int)(seq & 1u) * P2P_REC_HALF;
+    for (int p = 0; p < world; ++p) p2p_rec_store(vs.peer_rec[p] + (size_t)rank * P2P_REC_WORDS + half + 1, vs.counts[p]);
+    for (int i = 0; i < n_copies; ++i) {
+        const long long peer = vs.pieces[i * 4], slot = vs.pieces[i * 4 + 1];
+        const p2p_u64 a = __hip_atomic_load(vs.acc + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const p2p_u64 b = __hip_atomic_load(vs.acc + 2 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(vs.acc + 2 * i, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(vs.acc + 2 * i + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (peer < 0 || peer >= world || slot < 0 || slot >= BYA_P2P_VERIFY_PIECES) continue;      // (the place-holder entry)
+        long long* r = vs.peer_rec[peer] + (size_t)rank * P2P_REC_WORDS + half + 2 + slot * P2P_REC_PIECE;
+        p2p_rec_store(r + 0, vs.pieces[i * 4 + 2]);
+        p2p_rec_store(r + 1, vs.pieces[i * 4 + 3]);
+        p2p_rec_store(r + 2, copies[i].row_bytes);
+        p2p_rec_store(r + 3, copies[i].rows);
+        p2p_rec_store(r + 4, copies[i].dst_pitch);
+        p2p_rec_store(r + 5, (long long)a);
+        p2p_rec_store(r + 6, (long long)b);
+    }
+    for (int p = 0; p < world; ++p) p2p_rec_store(vs.peer_rec[p] + (size_t)rank * P2P_REC_WORDS + half, (long long)seq);
+}
+
+template <bool WAIT, bool VERIFY>
+__device__ __forceinline__ void p2p_push_body(const bya_p2p_copy* __restrict__ copies, int n_copies, long long total_chunks,
+                                              unsigned* const* __restrict__ peer_ctrl, int world, int rank, unsigned* __restrict__ ctrl,
+                                              unsigned* __restrict__ group_ctrl, long long limit_ticks, const P2pVerifySend vs) {
     const int tid = threadIdx.x;
     unsigned expect = 0;
     if (WAIT) expect = __hip_atomic_load(ctrl + P2P_EXPECT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;   // (before anybody can advance it)
-    p2p_copy_chunks(copies, n_copies, total_chunks, world, rank);
+    p2p_copy_chunks<VERIFY>(copies, n_copies, total_chunks, world, rank, vs.acc);
+    if constexpr (VERIFY) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (thread 0's atomics on `acc` have been performed)
     __threadfence_system();
     __syncthreads();
     if (tid == 0) {
@@ -271,6 +415,7 @@ __global__ __launch_bounds__(P2P_THREADS) void p2p_push_kernel(const bya_p2p_cop
             __hip_atomic_store(ctrl + P2P_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned seq = __hip_atomic_load(ctrl + P2P_SENT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
             __hip_atomic_store(ctrl + P2P_SENT, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (VERIFY) p2p_write_records(copies, n_copies, world, rank, seq, vs);
             __threadfence_system();
             for (int p = 0; p < world; ++p)
                 __hip_atomic_store(peer_ctrl[p] + rank, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -284,6 +429,151 @@ __global__ __launch_bounds__(P2P_THREADS) void p2p_push_kernel(const bya_p2p_cop
     }
 }
 
+template <bool WAIT>
+__global__ __launch_bounds__(P2P_THREADS) void p2p_push_kernel(const bya_p2p_copy* __restrict__ copies, int n_copies, long long total_chunks,
+                                                        unsigned* const* __restrict__ peer_ctrl, int world, int rank,
+                                                        unsigned* __restrict__ ctrl, unsigned* __restrict__ group_ctrl, long long limit_ticks) {
+    p2p_push_body<WAIT, false>(copies, n_copies, total_chunks, peer_ctrl, world, rank, ctrl, group_ctrl, limit_ticks, P2pVerifySend{});
+}
+
+template <bool WAIT>
+__global__ __launch_bounds__(P2P_THREADS) void p2p_push_verify_kernel(const bya_p2p_copy* __restrict__ copies, int n_copies, long long total_chunks,
+                                                               unsigned* const* __restrict__ peer_ctrl, int world, int rank,
+                                                               unsigned* __restrict__ ctrl, unsigned* __restrict__ group_ctrl,
+                                                               long long limit_ticks, const P2pVerifySend vs) {
+    p2p_push_body<WAIT, true>(copies, n_copies, total_chunks, peer_ctrl, world, rank, ctrl, group_ctrl, limit_ticks, vs);
+}
+
+// ---- the receiver's half of the verification ----------------------------------------------------------------------------------
+constexpr int P2P_VERIFY_THREADS = 256;
+constexpr int P2P_VLOG_ENTRY0 = 16, P2P_VLOG_ENTRY = 16;                                    // log_dev: first entry, words per entry
+constexpr int P2P_VLOG_SCRATCH = P2P_VLOG_ENTRY0 + P2P_VLOG_ENTRY * BYA_P2P_VERIFY_LOG_ENTRIES;   // [32 * PIECES][4]: A, B, parts done
+
+__device__ __forceinline__ unsigned p2p_load16(const char* p, bool sys) {
+    const uint16_t* q = reinterpret_cast<const uint16_t*>(p);
+    return sys ? (unsigned)__hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : (unsigned)*q;
+}
+
+// this workgroup's share (`part` of `parts`) of the sums of the piece at `base`.  SYS = false: ordinary cached loads, 16 bytes
+// wide where the piece allows it -- what a consumer kernel reads.  SYS = true: system-scope loads of aligned 32-bit words, and
+// of the 16-bit word before / behind them where a row starts / ends on an odd word.
+template <bool SYS>
+__device__ __forceinline__ void p2p_piece_sums(const char* __restrict__ base, long long row_bytes, long long rows, long long pitch, int part,
+                                               int parts, p2p_u64& va, p2p_u64& vb) {
+    const int tid = threadIdx.x;
+    const long long wpr = row_bytes >> 1;
+    if (!SYS && (((uintptr_t)base & 15) == 0) && (rows == 1 || (pitch & 15) == 0) && row_bytes >= 16) {
+        const long long per_row = row_bytes >> 4, units = rows * per_row, per = (units + parts - 1) / parts;
+        const long long lo = part * per, hi = lo + per < units ? lo + per : units;
+        for (long long u = lo + tid; u < hi; u += P2P_VERIFY_THREADS) {
+            const long long r = u / per_row, c = u - r * per_row;
+            const u32x4 v = *reinterpret_cast<const u32x4*>(base + r * pitch + (c << 4));
+            p2p_vsum8(v, r * wpr + (c << 3), va, vb);
+        }
+        const long long tw = (row_bytes & 15) >> 1, tails = part == 0 ? rows * tw : 0;         // the words behind a row's last 16 bytes
+        for (long long t = tid; t < tails; t += P2P_VERIFY_THREADS) {
+            const long long r = t / tw, c = (per_row << 3) + (t - r * tw);
+            p2p_vsum_word(p2p_load16(base + r * pitch + (c << 1), false), r * wpr + c, va, vb);
+        }
+        return;
+    }
+    const long long words = rows * wpr, per = (words + parts - 1) / parts;
+    const long long lo = part * per, hi = lo + per < words ? lo + per : words;
+    for (long long i = lo + tid; i < hi; i += P2P_VERIFY_THREADS) {
+        const long long r = i / wpr, c = i - r * wpr;
+        const char* p = base + r * pitch + (c << 1);
+        if (!SYS) {
+            p2p_vsum_word(p2p_load16(p, false), i, va, vb);
+        } else if (((uintptr_t)p & 2) == 0 && c + 1 < wpr) {         // an aligned pair: one 32-bit load, whoever owns word i + 1
+            const unsigned x = __hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            p2p_vsum_word(x & 0xffffu, i, va, vb);
+            p2p_vsum_word(x >> 16, i + 1, va, vb);
+        } else if (((uintptr_t)p & 2) == 0 || c == 0) {              // a row's last word / its first one at an odd word
+            p2p_vsum_word(p2p_load16(p, true), i, va, vb);
+        }                                                            // (else: the upper half of the pair before it)
+    }
+}
+
+__device__ __forceinline__ void p2p_verify_log(unsigned* ctrl, unsigned* group_ctrl, long long* log, long long channel, int sender,
+                                               unsigned seq, int piece, p2p_u64 wa, p2p_u64 wb, p2p_u64 ga, p2p_u64 gb, int reread,
+                                               long long buf_id, int rank, int kind) {
+    const p2p_u64 slot = __hip_atomic_fetch_add(reinterpret_cast<p2p_u64*>(log), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (slot < (p2p_u64)BYA_P2P_VERIFY_LOG_ENTRIES) {                // the FIRST entries are kept
+        long long* e = log + P2P_VLOG_ENTRY0 + slot * P2P_VLOG_ENTRY;
+        const long long v[12] = {channel, sender, (long long)seq, piece, (long long)wa, (long long)wb, (long long)ga, (long long)gb,
+                                 reread, buf_id, rank, kind};
+        for (int k = 0; k < 12; ++k) __hip_atomic_store(e + k, v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __hip_atomic_fetch_add(ctrl + P2P_XMISMATCHES, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(group_ctrl + P2P_GROUP_XMISMATCHES, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// grid (32 senders' worth is never launched: world * PIECES, parts): workgroup (x, y) sums part y of piece x % PIECES of sender
+// x / PIECES; the parts of a piece meet in the log's scratch words, and the one that arrives last compares, re-reads, logs.
+// Launches of one group are stream-ordered (the host module enqueues them on the stream of the wait): the scratch is theirs alone.
+__global__ __launch_bounds__(P2P_VERIFY_THREADS) void p2p_verify_kernel(unsigned* __restrict__ ctrl, const long long* __restrict__ rec,
+                                                                        const long long* __restrict__ bufs, int rank,
+                                                                        unsigned* __restrict__ group_ctrl, long long* __restrict__ log,
+                                                                        long long channel) {
+    const int tid = threadIdx.x, sender = blockIdx.x / BYA_P2P_VERIFY_PIECES, piece = blockIdx.x % BYA_P2P_VERIFY_PIECES;
+    const int part = blockIdx.y, parts = gridDim.y;
+    // a wait that gave up: the data is known bad (and reported); records may be missing
+    if (__hip_atomic_load(ctrl + P2P_TIMEOUTS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
+        __hip_atomic_load(group_ctrl + P2P_GROUP_TIMEOUTS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
+    const unsigned seq = __hip_atomic_load(ctrl + P2P_EXPECT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // what the wait before this launch waited for
+    const long long* r = rec + (size_t)sender * P2P_REC_WORDS + (seq & 1u) * P2P_REC_HALF;
+    auto field = [&](int k) { return __hip_atomic_load(r + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); };
+    const long long rseq = field(0), n_pieces = field(1);
+    if (rseq != (long long)seq || n_pieces < 0 || n_pieces > BYA_P2P_VERIFY_PIECES) {
+        if (piece == 0 && part == 0 && tid == 0)
+            p2p_verify_log(ctrl, group_ctrl, log, channel, sender, seq, -1, (p2p_u64)rseq, (p2p_u64)n_pieces, 0, 0, -1, -1, rank, 1);
+        return;
+    }
+    if (piece >= n_pieces) return;
+    const long long* f = r + 2 + piece * P2P_REC_PIECE;
+    auto pf = [&](int k) { return __hip_atomic_load(f + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); };
+    const long long buf_id = pf(0), off = pf(1), row_bytes = pf(2), rows = pf(3), pitch = pf(4);
+    const p2p_u64 wa = (p2p_u64)pf(5), wb = (p2p_u64)pf(6);
+    // nothing of a record is dereferenced before it is known to lie inside one of this rank's own buffers
+    long long base = 0, size = 0;
+    if (buf_id >= 0 && buf_id < BYA_P2P_VERIFY_BUFS) { base = bufs[buf_id * 2]; size = bufs[buf_id * 2 + 1]; }
+    const bool sane = base != 0 && row_bytes > 0 && rows > 0 && off >= 0 && ((row_bytes | off | pitch) & 1) == 0 && row_bytes <= size &&
+                      rows <= size && (rows == 1 || (pitch >= row_bytes && pitch <= size)) &&
+                      off <= size - row_bytes && (rows == 1 || (rows - 1) <= (size - row_bytes - off) / pitch);
+    if (!sane) {
+        if (part == 0 && tid == 0) p2p_verify_log(ctrl, group_ctrl, log, channel, sender, seq, piece, wa, wb, 0, 0, -1, buf_id, rank, 2);
+        return;
+    }
+    const char* p = reinterpret_cast<const char*>((uintptr_t)base) + off;
+    p2p_u64 va = 0, vb = 0;
+    p2p_piece_sums<false>(p, row_bytes, rows, pitch, part, parts, va, vb);
+    p2p_vsum_reduce<P2P_VERIFY_THREADS>(va, vb);
+    p2p_u64* sc = reinterpret_cast<p2p_u64*>(log) + P2P_VLOG_SCRATCH + (size_t)blockIdx.x * 4;
+    __shared__ int differs;
+    __shared__ p2p_u64 got[2];
+    if (tid == 0) {
+        __hip_atomic_fetch_add(sc, va, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(sc + 1, vb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const p2p_u64 done = __hip_atomic_fetch_add(sc + 2, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        differs = 0;
+        if (done == (p2p_u64)(parts - 1)) {
+            got[0] = __hip_atomic_load(sc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            got[1] = __hip_atomic_load(sc + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int k = 0; k < 3; ++k) __hip_atomic_store(sc + k, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            differs = got[0] != wa || got[1] != wb;
+        }
+    }
+    __syncthreads();
+    if (!differs) return;
+    // ONE second look, past this GPU's caches: does memory hold what was sent?
+    p2p_u64 sa = 0, sb = 0;
+    p2p_piece_sums<true>(p, row_bytes, rows, pitch, 0, 1, sa, sb);
+    p2p_vsum_reduce<P2P_VERIFY_THREADS>(sa, sb);
+    if (tid == 0)
+        p2p_verify_log(ctrl, group_ctrl, log, channel, sender, seq, piece, wa, wb, got[0], got[1], sa == wa && sb == wb, buf_id, rank, 0);
+}
+
 __global__ __launch_bounds__(64) void p2p_wait_kernel(unsigned* __restrict__ ctrl, unsigned* __restrict__ group_ctrl, int world,
                                                       long long limit_ticks) {
     const unsigned expect = __hip_atomic_load(ctrl + P2P_EXPECT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
@@ -291,13 +581,15 @@ __global__ __launch_bounds__(64) void p2p_wait_kernel(unsigned* __restrict__ ctr
 }
 
 // out[0 .. n) := NaN (bf16) if any of the n_channels control blocks starting at ctrl_base carries a time-out (word 35) or a
-// checksum mismatch (word 38)
+// checksum mismatch (word 38: the step's gathered prediction, written by the host module; word 39: a piece of an exchange,
+// bya_p2p_verify)
 __global__ __launch_bounds__(256) void p2p_poison_kernel(const unsigned* __restrict__ ctrl_base, int n_channels, uint16_t* __restrict__ out,
                                                           long long n) {
     int bad = 0;
     for (int c = threadIdx.x; c < n_channels; c += 256)
         bad |= __hip_atomic_load(ctrl_base + (size_t)c * P2P_CTRL_WORDS + P2P_TIMEOUTS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-               __hip_atomic_load(ctrl_base + (size_t)c * P2P_CTRL_WORDS + P2P_MISMATCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+               __hip_atomic_load(ctrl_base + (size_t)c * P2P_CTRL_WORDS + P2P_MISMATCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
+               __hip_atomic_load(ctrl_base + (size_t)c * P2P_CTRL_WORDS + P2P_XMISMATCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
     if (!__syncthreads_or(bad)) return;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) out[i] = 0x7fc0u;
 }
@@ -350,6 +642,65 @@ extern "C" int bya_p2p_exchange(const bya_p2p_copy* copies_dev, int32_t n_copies
     BYA_LAUNCH(p2p_push_kernel<true>, dim3((unsigned)want), dim3(P2P_THREADS), 0, stream, copies_dev, n_copies, (long long)total_chunks,
                reinterpret_cast<unsigned* const*>(peer_ctrl_dev), world, rank, static_cast<unsigned*>(ctrl), static_cast<unsigned*>(group_ctrl),
                p2p_limit_ticks(wait_limit_ms));
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+namespace {
+
+int p2p_verify_send_check(const int64_t* pieces_dev, const int64_t* counts_dev, const void* acc_dev, const void* peer_rec_dev) {
+    if (!pieces_dev || !counts_dev || !acc_dev || !peer_rec_dev) return BYA_ERR_SHAPE;
+    if (((uintptr_t)pieces_dev | (uintptr_t)counts_dev | (uintptr_t)acc_dev | (uintptr_t)peer_rec_dev) & 7) return BYA_ERR_ALIGN;
+    return BYA_OK;
+}
+
+}  // namespace
+
+extern "C" int bya_p2p_push_verified(const bya_p2p_copy* copies_dev, int32_t n_copies, int64_t total_chunks, void* const* peer_ctrl_dev,
+                                     int32_t world, int32_t rank, void* ctrl, const int64_t* pieces_dev, const int64_t* counts_dev,
+                                     void* acc_dev, void* const* peer_rec_dev, hipStream_t stream) {
+    int rc = p2p_check(copies_dev, peer_ctrl_dev, ctrl, n_copies, total_chunks, world, rank);
+    if (rc == BYA_OK) rc = p2p_verify_send_check(pieces_dev, counts_dev, acc_dev, peer_rec_dev);
+    if (rc != BYA_OK) return rc;
+    const long long cap = p2p_max_groups(), want = total_chunks < cap ? total_chunks : cap;
+    const P2pVerifySend vs{reinterpret_cast<const long long*>(pieces_dev), reinterpret_cast<const long long*>(counts_dev),
+                           static_cast<p2p_u64*>(acc_dev), reinterpret_cast<long long* const*>(peer_rec_dev)};
+    BYA_LAUNCH(p2p_push_verify_kernel<false>, dim3((unsigned)want), dim3(P2P_THREADS), 0, stream, copies_dev, n_copies, (long long)total_chunks,
+               reinterpret_cast<unsigned* const*>(peer_ctrl_dev), world, rank, static_cast<unsigned*>(ctrl), static_cast<unsigned*>(nullptr), 0ll,
+               vs);
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+extern "C" int bya_p2p_exchange_verified(const bya_p2p_copy* copies_dev, int32_t n_copies, int64_t total_chunks, void* const* peer_ctrl_dev,
+                                         int32_t world, int32_t rank, void* ctrl, void* group_ctrl, int64_t wait_limit_ms,
+                                         const int64_t* pieces_dev, const int64_t* counts_dev, void* acc_dev, void* const* peer_rec_dev,
+                                         hipStream_t stream) {
+    int rc = p2p_check(copies_dev, peer_ctrl_dev, ctrl, n_copies, total_chunks, world, rank);
+    if (rc == BYA_OK) rc = p2p_verify_send_check(pieces_dev, counts_dev, acc_dev, peer_rec_dev);
+    if (rc != BYA_OK) return rc;
+    if ((uintptr_t)group_ctrl & 3) return BYA_ERR_ALIGN;
+    const long long cap = p2p_max_groups();
+    long long want = total_chunks < cap ? total_chunks : cap;
+    if (want < P2P_WAIT_GROUPS) want = P2P_WAIT_GROUPS;
+    const P2pVerifySend vs{reinterpret_cast<const long long*>(pieces_dev), reinterpret_cast<const long long*>(counts_dev),
+                           static_cast<p2p_u64*>(acc_dev), reinterpret_cast<long long* const*>(peer_rec_dev)};
+    BYA_LAUNCH(p2p_push_verify_kernel<true>, dim3((unsigned)want), dim3(P2P_THREADS), 0, stream, copies_dev, n_copies, (long long)total_chunks,
+               reinterpret_cast<unsigned* const*>(peer_ctrl_dev), world, rank, static_cast<unsigned*>(ctrl), static_cast<unsigned*>(group_ctrl),
+               p2p_limit_ticks(wait_limit_ms), vs);
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+extern "C" int bya_p2p_verify(void* ctrl, const void* rec, const int64_t* buf_bases_dev, int32_t world, int32_t rank, void* group_ctrl,
+                              void* log_dev, hipStream_t stream) {
+    if (!ctrl || !rec || !buf_bases_dev || !group_ctrl || !log_dev) return BYA_ERR_SHAPE;
+    if (world <= 0 || world > 32 || rank < 0 || rank >= world) return BYA_ERR_SHAPE;
+    if (((uintptr_t)ctrl | (uintptr_t)group_ctrl) & 3 || ((uintptr_t)rec | (uintptr_t)buf_bases_dev | (uintptr_t)log_dev) & 7) return BYA_ERR_ALIGN;
+    const ptrdiff_t d = static_cast<char*>(ctrl) - static_cast<char*>(group_ctrl);
+    if (d < 0 || d % (P2P_CTRL_WORDS * 4)) return BYA_ERR_SHAPE;
+    // ~256 workgroups whatever the group's size: the parts of a piece go to different workgroups
+    const int pairs = world * BYA_P2P_VERIFY_PIECES, parts = 256 / pairs > 0 ? 256 / pairs : 1;
+    BYA_LAUNCH(p2p_verify_kernel, dim3((unsigned)pairs, (unsigned)parts), dim3(P2P_VERIFY_THREADS), 0, stream, static_cast<unsigned*>(ctrl),
+               static_cast<const long long*>(rec), reinterpret_cast<const long long*>(buf_bases_dev), rank, static_cast<unsigned*>(group_ctrl),
+               static_cast<long long*>(log_dev), (long long)(d / (P2P_CTRL_WORDS * 4)));
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 

@@ -179,7 +179,9 @@ class DenoiseEngine:
         self.router_chain = os.environ.get("BYA_ROUTER_CHAIN", "1")
         # (r6) sharded step on the P2P transport: compare a checksum of the step's gathered prediction across the ranks, every
         # step (parallel.SeqShard.verify_gathered); bench.py --gpus N and the sharded tests switch it on
-        self.verify_exchanges = os.environ.get("BYA_SP_VERIFY", "0") == "1"
+        # "all": that, and every exchange of the step is verified piece by piece, sender to receiver (a P2PGroup made under
+        # this setting reads it itself: p2p.verify_mode_from_env, Channel.verify; a diagnostic mode)
+        self.verify_exchanges = os.environ.get("BYA_SP_VERIFY", "0") in ("1", "all")
         # (r6) sharded step, P2P transport: exchange A's v third on the side stream underneath the q | k projection
         # ("1" where a rank has at least SP_OVERLAP_V_MIN_ROWS rows, "0" never, "all" always)
         self.sp_overlap_v = os.environ.get("BYA_SP_OVERLAP_V", "1") != "0"
@@ -1095,8 +1097,8 @@ class DenoiseEngine:
         y = ops.gemm(xo, m.proj_out.weight, buf("y", B, N_loc, co), bias=m.proj_out.bias)
         if sh.active:                                        # every rank returns the full latent prediction
             y = sh.gather_video_rows(y, out=buf("y_full", B, N, co), in_place=True)
-            if self.verify_exchanges:
-                sh.verify_gathered(y)          # every rank holds the same gathered prediction -- or a receive buffer went stale
+            if self.verify_exchanges or (sh.p2p is not None and sh.p2p.verify):        # (verify mode implies the canary)
+                sh.verify_gathered(y)         # every rank holds the same gathered prediction -- or a receive buffer went stale
         out = torch.empty(B, T, co // 4, Hh, Ww, dtype=torch.bfloat16, device=self.dev)
         ops.unpatchify(y, out)
         if sh.p2p is not None:

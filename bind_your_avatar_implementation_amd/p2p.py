@@ -23,6 +23,9 @@ and the whole sharded step replays as a graph.
 ``Channel.push(side) / .wait()``   the two halves (``side``: the push runs on the group's side stream behind the work
                                     already enqueued; call ``.wait()`` where the data is needed)
 ``.poison(out)``                   last launch of a sharded step: NaN over ``out`` if any wait of this group ever gave up
+``P2PGroup(verify=True)``          (BYA_SP_VERIFY=all) a diagnostic mode: every exchange carries per-piece checksums to the
+                                    receiver, which sums its own receive buffers behind the wait (``Channel.verify``) and logs
+                                    exchange, sender and piece of whatever differs (``.exchange_mismatches()``, ``.check()``)
 
 All ranks of the group must issue the same sequence of ``symmetric`` calls and, per channel, the same sequence of
 exchanges (sequence numbers live in device memory, one pair per channel).  One process per GPU in production; the tests
@@ -45,6 +48,42 @@ KINDS = {"coarse": 0, "fine": 1, "uncached": 2}
 TABLES_PER_CHANNEL = 4           # copy tables kept per channel besides the ones a captured graph owns
 LIVE_GROUPS = weakref.WeakSet()  # every P2PGroup of this process (ops.check_gemm_workspace asks each for timed-out waits)
 _RETIRED = []                    # buffers of closed groups (P2PGroup.close: never freed while peers might still store into them)
+# exchange verification (BYA_SP_VERIFY=all; BYA_P2P_VERIFY_* of include/bya.h)
+VERIFY_PIECES, VERIFY_BUFS, REC_WORDS, REC_PIECE = 8, 1024, 128, 7
+LOG_ENTRIES, LOG_ENTRY0, LOG_ENTRY = 64, 16, 16
+LOG_WORDS = LOG_ENTRY0 + LOG_ENTRY * LOG_ENTRIES + VERIFY_PIECES * 32 * 4
+LOG_KINDS = {0: "sums differ", 1: "no record of this sequence number", 2: "record names memory outside the receiver's buffers"}
+
+
+def verify_mode_from_env():
+    """BYA_SP_VERIFY=all: every exchange of every group is verified (``P2PGroup(verify=None)`` asks here)."""
+    return os.environ.get("BYA_SP_VERIFY", "0") == "all"
+
+
+def _piece_rows(grp, pieces):
+    """The non-empty pieces of a ``_build_table`` list as (source address, peer, buffer name, byte offset in that buffer, row
+    bytes, rows, source pitch, destination pitch -- bytes), checked against the destination buffer."""
+    out = []
+    for piece in pieces:
+        src, peer, name, offset = piece[:4]
+        if src.numel() == 0:
+            continue
+        es = src.element_size()
+        nrows, ncols, spitch = grp._rows_of(src)
+        dpitch = piece[4] if len(piece) > 4 and piece[4] is not None else ncols
+        if len(piece) > 4 and piece[4] is not None and nrows == 1 and src.dim() >= 2 and src.shape[0] > 1:
+            # a contiguous source scattered to pitched destination rows: its leading dimension is the row index
+            nrows, ncols = src.shape[0], src[0].numel()
+            spitch = ncols
+        dst_t = grp.peers(name)[peer]
+        last = offset + (nrows - 1) * dpitch + ncols
+        if dst_t.dtype != src.dtype or offset < 0 or last > dst_t.numel() or dpitch < ncols:
+            raise ValueError(f"P2P piece does not fit buffer {name!r} on rank {peer}")
+        dst = dst_t.data_ptr() + offset * es
+        if (src.data_ptr() | dst | (ncols * es) | (spitch * es) | (dpitch * es)) & 1:
+            raise ValueError("P2P pieces must be 2-byte aligned in address and size")
+        out.append((src.data_ptr(), peer, name, offset * es, ncols * es, nrows, spitch * es, dpitch * es))
+    return out
 
 
 class PhaseMismatch(RuntimeError):
@@ -115,15 +154,20 @@ class Channel:
         self.ctrl_ptr = grp.ctrl[index].data_ptr()
         self.peer_ctrl = torch.tensor([grp.ctrl_peers[j].data_ptr() + index * CTRL_WORDS * 4 for j in range(grp.kworld)],
                                       dtype=torch.int64, device=grp.dev)
-        self.tables = collections.OrderedDict()      # source-pointer signature -> [table, n_copies, total_chunks, sources, pinned]
+        self.tables = collections.OrderedDict()      # source-pointer signature -> [table, n_copies, total_chunks, sources, pinned, verify tables]
         self.cur = None
         self._join = None
+        if grp.verify:                               # where this channel's records go on every peer (include/bya.h)
+            self.peer_rec = torch.tensor([grp.peers("__verify_rec__")[j].data_ptr() + index * 32 * REC_WORDS * 8 for j in range(grp.kworld)],
+                                         dtype=torch.int64, device=grp.dev)
 
     def bind(self, pieces):
         sig = tuple((p[0].data_ptr(), p[1], p[2], p[3], tuple(p[0].shape), p[0].stride(), p[4] if len(p) > 4 else None) for p in pieces)
         ent = self.tables.get(sig)
         if ent is None:
-            ent = self.tables[sig] = list(self.grp._build_table(pieces)) + [False]
+            # (verify mode: the descriptors first -- a pair with too many pieces raises before anything is kept)
+            vt = self.grp._build_verify_table(pieces) if self.grp.verify else None
+            ent = self.tables[sig] = list(self.grp._build_table(pieces)) + [False, vt]
         else:
             self.tables.move_to_end(sig)
         if torch.cuda.is_current_stream_capturing():
@@ -139,6 +183,8 @@ class Channel:
         g = self.grp
         table, n, total_chunks = self.cur[:3]
         tail = (g.ctrl.data_ptr(), g.wait_limit_ms) if wait else ()     # the group's first control block, this launch's wait limit
+        if g.verify:                                                    # the instance that also sums and writes the records
+            tail += tuple(t.data_ptr() for t in self.cur[5]) + (self.peer_rec.data_ptr(),)
         _hip.check(fn(table.data_ptr(), n, total_chunks, self.peer_ctrl.data_ptr(), g.kworld, g.krank, self.ctrl_ptr, *tail,
                       stream.cuda_stream), fn.__name__)
         g.pushes += 1
@@ -152,7 +198,8 @@ class Channel:
             ev = torch.cuda.Event()
             ev.record(cur)
             stream.wait_event(ev)
-        self._launch(_hip.load().bya_p2p_push, stream)
+        lib = _hip.load()
+        self._launch(lib.bya_p2p_push_verified if g.verify else lib.bya_p2p_push, stream)
         self._join = None
         if stream is not cur:
             self._join = torch.cuda.Event()
@@ -166,26 +213,74 @@ class Channel:
             cur.wait_event(self._join)              # (also rejoins the side stream into a graph capture)
             self._join = None
         _hip.check(_hip.load().bya_p2p_wait(self.ctrl_ptr, g.kworld, g.ctrl.data_ptr(), g.wait_limit_ms, cur.cuda_stream), "bya_p2p_wait")
-        return self
+        return self.verify() if g.verify else self
 
     def exchange(self):
-        """push + wait in one launch (``P2PGroup.MERGED = False``: as two, the round-4 form)."""
+        """push + wait in one launch (``P2PGroup.MERGED = False``: as two, the round-4 form); verify mode: + the verify launch."""
         if not self.grp.MERGED:
             return self.push().wait()
-        self._launch(_hip.load().bya_p2p_exchange, torch.cuda.current_stream(self.grp.dev), wait=True)
+        lib = _hip.load()
+        self._launch(lib.bya_p2p_exchange_verified if self.grp.verify else lib.bya_p2p_exchange, torch.cuda.current_stream(self.grp.dev),
+                     wait=True)
+        return self.verify() if self.grp.verify else self
+
+    def verify(self):
+        """Verify mode: enqueue ``bya_p2p_verify`` on the current stream -- every piece the last exchange this channel has
+        WAITED for brought into this rank's buffers is summed again, as a consumer would read it, and compared with its
+        sender's record (``P2PGroup.exchange_mismatches``).  ``exchange()`` and ``wait()`` end with it; calling it again
+        repeats the check on what the buffers hold now.  No host synchronisation: it is captured with the step."""
+        g = self.grp
+        if not g.verify:
+            raise RuntimeError("P2P exchange verification is off for this group (BYA_SP_VERIFY=all, or P2PGroup(verify=True))")
+        import sys
+        ops = sys.modules.get(__package__ + ".ops")          # (the timers live there; a bucket of its own)
+        tok = ops._begin("bya_p2p_verify") if ops is not None else None
+        _hip.check(_hip.load().bya_p2p_verify(self.ctrl_ptr, g.vrec[self.index].data_ptr(), g.buf_bases.data_ptr(), g.kworld, g.krank,
+                                              g.ctrl.data_ptr(), g.vlog.data_ptr(), torch.cuda.current_stream(g.dev).cuda_stream),
+                   "bya_p2p_verify")
+        if tok is not None:
+            ops._end(tok)
+        g.verifies += 1
         return self
+
+    def records(self):
+        """Verify mode, diagnostics (synchronises): per sender rank the record of the last exchange this channel has waited
+        for, {"sequence", "pieces": [{"buf_id", "buffer", "dst_byte_offset", "row_bytes", "rows", "dst_pitch", "A", "B"}]}."""
+        g = self.grp
+        torch.cuda.synchronize(g.dev)
+        seq = int(g.ctrl[self.index, 33].item()) & 0xFFFFFFFF
+        rec = g.vrec[self.index, :g.kworld].cpu().view(g.kworld, 2, REC_WORDS // 2)[:, seq & 1]
+        names = {i: n for n, i in g._buf_ids.items()}
+        out = []
+        for s in range(g.kworld):
+            r = rec[s].tolist()
+            ps = [dict(zip(("buf_id", "dst_byte_offset", "row_bytes", "rows", "dst_pitch", "A", "B"), r[2 + k * REC_PIECE:2 + (k + 1) * REC_PIECE]))
+                  for k in range(max(0, min(r[1], VERIFY_PIECES)))]
+            for p_ in ps:
+                p_["buffer"] = names.get(p_["buf_id"])
+                p_["A"], p_["B"] = p_["A"] & (2 ** 64 - 1), p_["B"] & (2 ** 64 - 1)
+            out.append({"sequence": r[0], "pieces": ps})
+        return out
 
 
 class P2PGroup:
     MERGED = True
 
-    def __init__(self, group=None, device=None, mem="coarse", solo=None):
-        """``solo=(rank, world)``: PROBE MODE (tools/solo_rank_step.py) -- this one process plays rank ``rank`` of a
+    def __init__(self, group=None, device=None, mem="coarse", solo=None, verify=None):
+        """``verify`` (None: BYA_SP_VERIFY=all): VERIFY MODE, a diagnostic -- every exchange of this group, whoever issues it,
+        carries per-piece checksums from the sender to the receiver, which sums what it reads from its own receive buffers
+        behind the wait and compares (``Channel.verify``, ``exchange_mismatches``, ``check``; include/bya.h defines the
+        checksum and the record).  Collective like everything else here: every rank of the group the same.
+        ``solo=(rank, world)``: PROBE MODE (tools/solo_rank_step.py) -- this one process plays rank ``rank`` of a
         ``world``-rank group whose other ranks do not exist: every "peer" buffer is a second local allocation, pushes store
         into those, and a wait only expects this rank's own flag.  The received data is therefore wrong (the peers' parts
         never arrive) but every kernel and every exchange launch of ONE rank's step runs with its real shapes: what one GPU
         can measure of an N-GPU step.  Never used by the product path."""
         self.solo = solo
+        self.verify = verify_mode_from_env() if verify is None else bool(verify)
+        if self.verify and solo is not None:
+            raise ValueError("P2P exchange verification (BYA_SP_VERIFY=all) on a solo probe group: the peers' parts never arrive, "
+                             "what it receives is wrong by construction")
         if solo is not None:
             self.group, (self.rank, self.world) = None, solo
         else:
@@ -200,10 +295,16 @@ class P2PGroup:
         self.kworld, self.krank = (1, 0) if solo is not None else (self.world, self.rank)
         self.dev = torch.device(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
         self._named = {}
+        self._buf_ids = {}               # name -> place in the order of the ``symmetric`` calls (collective: the same on every rank)
         self._keep = []
         self._channels = {}
         self._p2p_enabled = set()
         self.pushes = 0
+        self.verifies = 0                # verify launches (verify mode: one per exchange, one per push / wait pair)
+        if self.verify:
+            # buf_id -> (local base address, bytes): what a record's (buf_id, offset) means on THIS rank; the mismatch log
+            self.buf_bases = torch.zeros(VERIFY_BUFS, 2, dtype=torch.int64, device=self.dev)
+            self.vlog = torch.zeros(LOG_WORDS, dtype=torch.int64, device=self.dev)
         self.closed = False
         self.side_stream = torch.cuda.Stream(self.dev)
         # seconds a wait of THIS group may take before it gives up (wall clock); handed to every wait / exchange launch -- a
@@ -220,6 +321,14 @@ class P2PGroup:
         if solo is not None:
             self.ctrl_kind = f"local (solo probe, {getattr(self, 'solo_ctrl', 'coarse')})"
         self.ctrl_peers = self._named["__ctrl__"][1]
+        if self.verify:
+            # the records: written by the peers' push kernels, read by this rank's verify kernels -- like the flags, fine-grained
+            # memory where the platform hands it out
+            shape = (MAX_CHANNELS, 32, REC_WORDS)
+            try:
+                self.vrec = self.symmetric("__verify_rec__", shape, torch.int64, zero=True, kind="fine")
+            except _FineUnavailable:
+                self.vrec = self.symmetric("__verify_rec__", shape, torch.int64, zero=True, kind="coarse")
         LIVE_GROUPS.add(self)
 
     def _agree(self, err, what):
@@ -281,11 +390,22 @@ class P2PGroup:
                     peers = [_Peer(t.data_ptr(), shape, dtype, t) for t in sinks]
                     peers.insert(self.rank, _Peer(local.data_ptr(), shape, dtype, local))
                 self._named[name] = (local, peers)
+                self._register(name, local)
                 return local
             # (both end in _agree: nobody pushes before everybody has mapped, and a rank that could not map takes all down with it)
             local, peers = (self._symmetric_torch if kind == "coarse" else self._symmetric_ext)(shape, dtype, zero, kind)
         self._named[name] = (local, peers)
+        self._register(name, local)
         return local
+
+    def _register(self, name, local):
+        """The buffer's ``buf_id`` (its place in the order of the ``symmetric`` calls) and, in verify mode, its entry in the
+        device table the verify kernel resolves a record's (buf_id, offset) with."""
+        i = self._buf_ids[name] = len(self._buf_ids)
+        if self.verify:
+            if i >= VERIFY_BUFS:
+                raise RuntimeError(f"P2P exchange verification: more than {VERIFY_BUFS} symmetric buffers in one group")
+            self.buf_bases[i] = torch.tensor([local.data_ptr(), local.numel() * local.element_size()], dtype=torch.int64)
 
     def _symmetric_torch(self, shape, dtype, zero, kind):
         # the WHOLE allocation is what a peer maps, and it must stay alive for as long as any peer may store into it
@@ -403,26 +523,8 @@ class P2PGroup:
         rank ``peer``'s buffer ``name``; a strided source (see ``_rows_of``) and / or ``dst_pitch`` (elements between the
         starts of consecutive rows at the destination; default: dense) make it a 2-D piece."""
         rows, chunk0 = [], 0
-        for piece in pieces:
-            src, peer, name, offset = piece[:4]
-            if src.numel() == 0:
-                continue
-            es = src.element_size()
-            nrows, ncols, spitch = self._rows_of(src)
-            dpitch = piece[4] if len(piece) > 4 and piece[4] is not None else ncols
-            if len(piece) > 4 and piece[4] is not None and nrows == 1 and src.dim() >= 2 and src.shape[0] > 1:
-                # a contiguous source scattered to pitched destination rows: its leading dimension is the row index
-                nrows, ncols = src.shape[0], src[0].numel()
-                spitch = ncols
-            dst_t = self.peers(name)[peer]
-            last = offset + (nrows - 1) * dpitch + ncols
-            if dst_t.dtype != src.dtype or offset < 0 or last > dst_t.numel() or dpitch < ncols:
-                raise ValueError(f"P2P piece does not fit buffer {name!r} on rank {peer}")
-            dst = dst_t.data_ptr() + offset * es
-            if (src.data_ptr() | dst | (ncols * es) | (spitch * es) | (dpitch * es)) & 1:
-                raise ValueError("P2P pieces must be 2-byte aligned in address and size")
-            row_bytes = ncols * es
-            rows.append((src.data_ptr(), dst, row_bytes, nrows, spitch * es, dpitch * es, chunk0))
+        for src_ptr, peer, name, dst_off, row_bytes, nrows, spitch, dpitch in _piece_rows(self, pieces):
+            rows.append((src_ptr, self.peers(name)[peer].data_ptr() + dst_off, row_bytes, nrows, spitch, dpitch, chunk0))
             if row_bytes > CHUNK:
                 chunk0 += nrows * ((row_bytes + CHUNK - 1) // CHUNK)
             else:
@@ -432,6 +534,24 @@ class P2PGroup:
             rows, chunk0 = [(self.ctrl.data_ptr(), self.ctrl.data_ptr(), 0, 0, 0, 0, 0)], 1
         table = torch.tensor(rows, dtype=torch.int64, device=self.dev)
         return table, len(rows), chunk0, [p[0] for p in pieces]      # (the sources stay alive with the table)
+
+    def _build_verify_table(self, pieces):
+        """Verify mode: what the push kernel needs besides the copy table of ``pieces`` (same entries, same order) to write the
+        records of include/bya.h -- per entry (destination rank, index of the piece in that rank's record, buf_id of the
+        destination buffer = its place in the group's ``symmetric`` order, byte offset from that buffer's base ON THE RECEIVER),
+        the pieces per destination rank, and the accumulator of the sums.  A pair with more than ``VERIFY_PIECES`` pieces is an
+        error: nothing is ever left out of a record silently."""
+        counts, rows = [0] * self.world, []
+        for _, peer, name, dst_off, _, _, _, _ in _piece_rows(self, pieces):
+            if counts[peer] == VERIFY_PIECES:
+                raise ValueError(f"P2P exchange verification: more than {VERIFY_PIECES} pieces for rank {peer} in one exchange "
+                                 f"(a record holds {VERIFY_PIECES})")
+            rows.append((peer, counts[peer], self._buf_ids[name], dst_off))
+            counts[peer] += 1
+        if not rows:
+            rows = [(-1, 0, 0, 0)]                       # (the copy table's place-holder entry)
+        return (torch.tensor(rows, dtype=torch.int64, device=self.dev), torch.tensor(counts, dtype=torch.int64, device=self.dev),
+                torch.zeros(len(rows), 2, dtype=torch.int64, device=self.dev))
 
     def drop_tables(self):
         """Forget every copy table no captured graph owns (the engine calls this when it lets go of a workspace)."""
@@ -511,9 +631,44 @@ class P2PGroup:
         torch.cuda.synchronize(self.dev)
         return int(self.ctrl[0, 38].item())
 
+    def exchange_mismatches(self):
+        """Verify mode: the pieces that did not arrive as they were sent (at most the first ``LOG_ENTRIES``; [] on a healthy
+        run, and with the mode off); synchronises.  One dict per piece: ``key`` = the key its channel was created with (e.g.
+        ("seq", "h2r", S, Tt)), ``channel`` its index, ``sender`` rank, ``piece`` = index among the pieces that sender sends this
+        rank in that exchange (-1: no record of that sequence number arrived), ``buffer`` name, ``sequence`` number, ``want`` =
+        (A, B) of the sender's record, ``got`` = what this rank summed through its caches, ``reread_matches`` = 1 if a second
+        pass with system-scope loads summed to ``want`` (memory holds what was sent; the first pass read something else), 0 if
+        not (memory itself differs), -1 where nothing was read, and ``kind`` (``LOG_KINDS``)."""
+        if not self.verify:
+            return []
+        torch.cuda.synchronize(self.dev)
+        log = self.vlog[:LOG_ENTRY0 + LOG_ENTRY * LOG_ENTRIES].cpu().tolist()
+        keys = {ch.index: k for k, ch in self._channels.items()}
+        names = {i: n for n, i in self._buf_ids.items()}
+        u64 = 2 ** 64 - 1
+        out = []
+        for e in range(min(log[0], LOG_ENTRIES)):
+            ch, sender, seq, piece, wa, wb, ga, gb, reread, buf_id, _, kind = log[LOG_ENTRY0 + e * LOG_ENTRY:][:12]
+            out.append({"key": keys.get(ch), "channel": ch, "sender": sender, "piece": piece, "buffer": names.get(buf_id),
+                        "sequence": seq, "want": (wa & u64, wb & u64), "got": (ga & u64, gb & u64), "reread_matches": reread,
+                        "kind": LOG_KINDS.get(kind, kind)})
+        return out
+
+    def exchange_mismatch_count(self):
+        """Verify mode: pieces that did not arrive as sent, ALL of them (the log keeps the first ``LOG_ENTRIES``); synchronises."""
+        torch.cuda.synchronize(self.dev)
+        return int(self.ctrl[0, 40].item())
+
     def check(self):
-        """Raise if any wait of this group ever gave up (its consumers ran on a stale receive buffer), or a step's exchange
-        checksum differed between the ranks."""
+        """Raise if any wait of this group ever gave up (its consumers ran on a stale receive buffer), a step's exchange
+        checksum differed between the ranks, or (verify mode) a piece of an exchange did not arrive as it was sent."""
+        x = self.exchange_mismatch_count() if self.verify else 0
+        if x:
+            e = self.exchange_mismatches()[0]
+            raise _hip.ByaError(f"{x} piece(s) of P2P exchanges did not arrive as sent (BYA_SP_VERIFY=all); the first: exchange {e['key']!r} "
+                                f"(channel {e['channel']}), sequence number {e['sequence']}, piece {e['piece']} from rank {e['sender']} in "
+                                f"buffer {e['buffer']!r}: {e['kind']}, sent sums {e['want']}, read {e['got']}, reread_matches = "
+                                f"{e['reread_matches']} -- results of this run are not to be trusted")
         m = self.mismatches()
         if m:
             raise _hip.ByaError(f"{m} step(s) ended with DIFFERENT gathered predictions on the ranks of this group (exchange checksum, "
@@ -524,7 +679,8 @@ class P2PGroup:
                                 f"results of this run are not to be trusted")
 
     def poison(self, out):
-        """Enqueue ``bya_p2p_poison``: ``out`` (bf16) becomes NaN if any channel of this group carries a time-out."""
+        """Enqueue ``bya_p2p_poison``: ``out`` (bf16) becomes NaN if any channel of this group carries a time-out, a step
+        checksum that differed between the ranks, or (verify mode) a piece that did not arrive as sent."""
         assert out.dtype == torch.bfloat16 and out.is_contiguous()
         _hip.check(_hip.load().bya_p2p_poison(self.ctrl.data_ptr(), MAX_CHANNELS, out.data_ptr(), out.numel(),
                                               torch.cuda.current_stream(self.dev).cuda_stream), "bya_p2p_poison")

@@ -229,7 +229,16 @@ class SeqShard:
         is re-used by every step): each rank sums its copy as 16-bit integers (exact, order-independent), the sums are traded in
         one 8-byte all-to-all, and a rank whose peers' sums differ from its own bumps word 38 of the group's first control block
         -- sticky: ``bya_p2p_poison`` turns the step's output into NaN, ``P2PGroup.check`` raises.  ~30 us per step;
-        graph-capturable.  (The reductions are torch ops: diagnostics, not the step's arithmetic.)"""
+        graph-capturable.  (The reductions are torch ops: diagnostics, not the step's arithmetic.)
+
+        SCOPE.  ``BYA_SP_VERIFY=1`` is this check alone: it covers the LAST gather of the step.  A stale line in any of the
+        ~280 earlier exchanges of a rank-step corrupts one rank's rows or heads, that rank then pushes the same wrong data to
+        every peer, all final sums agree, nothing is flagged; and when it does fire it says "some step went wrong", not where.
+        ``BYA_SP_VERIFY=all`` (``P2PGroup(verify=True)``; implies this check) covers EVERY exchange of the group -- this
+        function's own 8-byte one included -- as "what was sent is what the receiver reads after the wait": the push kernel
+        sends per-piece checksums, ``Channel.verify`` sums the receive buffer behind the wait and logs exchange, sender and
+        piece of a difference, and whether a second, system-scope read matched (``P2PGroup.exchange_mismatches``).  Neither
+        covers a compute error on the sender: wrong data sent faithfully arrives faithfully."""
         g = self.p2p
         if g is None or g.solo is not None or self.world == 1:
             return

@@ -984,7 +984,8 @@ int bya_alltoall_router(const void* send, void* recv, const int64_t* send_counts
  * the group's word set returns at once, counted as timed out: after the first time-out of a group the rest of the step runs
  * through without polling.  bya_p2p_poison(ctrl_base, n_channels, out, n) -- enqueue it behind the last consumer of a step --
  * overwrites the bf16 tensor `out` with NaN when any of the n_channels control blocks (64 words apart) carries a time-out or a
- * non-zero word 38 (written by the host: "this step's exchange checksum differed between the ranks"), so that a result made
+ * non-zero word 38 (written by the host: "this step's exchange checksum differed between the ranks") or word 39 (written by
+ * bya_p2p_verify, below: "a piece of an exchange did not arrive as it was sent"), so that a result made
  * from a buffer that never arrived, or arrived stale, cannot be consumed.  The caller guarantees that a receive buffer is not
  * pushed into again before its owner has consumed it (the step's data dependencies do).
  * --------------------------------------------------------------------------------------------- */
@@ -997,6 +998,49 @@ typedef struct bya_p2p_copy {      /* a 2-D piece: `rows` rows of `row_bytes` by
     int64_t chunk0;                /* chunks of the entries before this one; an entry has rows * ceil(row_bytes / 64 KiB) chunks
                                       when row_bytes > 64 KiB, else ceil(rows / floor(64 KiB / row_bytes)) */
 } bya_p2p_copy;
+
+/* Exchange verification (opt-in: BYA_SP_VERIFY=all in the host module; csrc/comm.hip).  The CHECKSUM of a piece: its bytes in
+ * logical order (row-major over rows x row_bytes, pitches removed) as 16-bit little-endian words w_i, i = 0, 1, ...:
+ *     A = sum w_i                        mod 2^64
+ *     B = sum w_i * ((i mod 65521) + 1)  mod 2^64
+ * Integer sums: exact, and independent of the order in which workgroups and chunks add to them (the chunk walk, the grid size
+ * and a graph replay cannot change them).  B catches rows that landed at another pitch or offset; A alone would not.
+ * bya_p2p_push_verified / bya_p2p_exchange_verified = bya_p2p_push / bya_p2p_exchange whose copy loop also sums what it has
+ * in registers, per entry of the copy table, into `acc_dev` [n_copies][2] uint64 (zero-filled by the host; zeroed again by
+ * the launch), and whose last workgroup writes, BEFORE it publishes the sequence number, one RECORD per destination rank p
+ * to `peer_rec_dev[p]` + rank * BYA_P2P_VERIFY_REC_WORDS int64 words -- peer_rec_dev[p] = the channel's [32 senders][REC_WORDS]
+ * block of rank p's record buffer (mapped; fine-grained memory where the platform hands it out).  A record has two halves of
+ * 64 words, taken by the parity of the sequence number (a sender can be ONE exchange ahead of a receiver that has not
+ * verified yet, never two): [0] sequence number, [1] n_pieces (<= BYA_P2P_VERIFY_PIECES), then per piece 7 words
+ * {buf_id, dst_byte_offset, row_bytes, rows, dst_pitch, A, B}.  `pieces_dev` [n_copies][4] int64 = {destination rank (< 0:
+ * the place-holder entry), index of the piece in that rank's record, buf_id, dst_byte_offset}; `counts_dev` [world] int64 =
+ * pieces per destination rank.  buf_id = index of the destination buffer in an order every rank agrees on (the host module:
+ * order of allocation); dst_byte_offset is relative to that buffer's base ON THE RECEIVER.
+ * bya_p2p_verify (receiver, behind the wait of the same exchange; no host synchronisation, capturable): for every sender's
+ * record of the sequence number the channel has just waited for, recompute A, B of every piece from the receiver's own
+ * buffer -- `buf_bases_dev` [BYA_P2P_VERIFY_BUFS][2] int64 = {local base address, bytes; 0, 0 = no such buffer} -- with
+ * ordinary cached loads (what a consumer kernel reads) and compare.  On a difference: re-read the piece ONCE with
+ * system-scope loads and note whether that sum matches; append an entry to `log_dev` (int64: [0] entries wanted so far, [16 +
+ * 16 * e ...] entry e < BYA_P2P_VERIFY_LOG_ENTRIES = {channel, sender, sequence, piece, want A, want B, got A, got B,
+ * reread_matches, buf_id, receiver rank, kind: 0 sums differ / 1 no record of that sequence number / 2 record names memory
+ * outside the buffer table (nothing is read)}; behind the entries BYA_P2P_VERIFY_PIECES * 32 * 4 words of scratch; all
+ * BYA_P2P_VERIFY_LOG_WORDS zero-filled by the host); bump word 39 of `ctrl` and word 40 of `group_ctrl` (sticky; bya_p2p_poison
+ * treats word 39 like a time-out).  A channel or group that carries a time-out is not verified (its data is known bad).
+ * `ctrl` must be one of the control blocks that start at `group_ctrl` (its index there is the log's channel). */
+#define BYA_P2P_VERIFY_PIECES 8
+#define BYA_P2P_VERIFY_REC_WORDS 128
+#define BYA_P2P_VERIFY_BUFS 1024
+#define BYA_P2P_VERIFY_LOG_ENTRIES 64
+#define BYA_P2P_VERIFY_LOG_WORDS (16 + 16 * BYA_P2P_VERIFY_LOG_ENTRIES + BYA_P2P_VERIFY_PIECES * 32 * 4)
+int bya_p2p_push_verified(const bya_p2p_copy* copies_dev, int32_t n_copies, int64_t total_chunks, void* const* peer_ctrl_dev,
+                          int32_t world, int32_t rank, void* ctrl, const int64_t* pieces_dev, const int64_t* counts_dev,
+                          void* acc_dev, void* const* peer_rec_dev, hipStream_t stream);
+int bya_p2p_exchange_verified(const bya_p2p_copy* copies_dev, int32_t n_copies, int64_t total_chunks, void* const* peer_ctrl_dev,
+                              int32_t world, int32_t rank, void* ctrl, void* group_ctrl, int64_t wait_limit_ms,
+                              const int64_t* pieces_dev, const int64_t* counts_dev, void* acc_dev, void* const* peer_rec_dev,
+                              hipStream_t stream);
+int bya_p2p_verify(void* ctrl, const void* rec, const int64_t* buf_bases_dev, int32_t world, int32_t rank, void* group_ctrl,
+                   void* log_dev, hipStream_t stream);
 
 int bya_p2p_push(const bya_p2p_copy* copies_dev, int32_t n_copies, int64_t total_chunks, void* const* peer_ctrl_dev,
                  int32_t world, int32_t rank, void* ctrl, hipStream_t stream);
