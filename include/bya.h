@@ -209,6 +209,17 @@ int bya_gemm_qkv_norm_rope_plan(const void* A, const void* W, const void* bias, 
  *   a_batch_stride counted in fp8 elements (bytes).  Replaces attn1.to_q|k|v, attn1.to_out, ff.net.0.proj and ff.net.2 of a
  *   CogVideoXBlock (models/transformer.py:241-260) when the engine is built with fp8 weights.
  *   Requirements: K % 128 == 0, N % 4 == 0, lda/ldw % 16 == 0, A8/W8/w_scale 16-byte aligned; act in {NONE, GELU_TANH(_IEEE)}.
+ *   What it refuses, launch and plan query alike, before anything runs (tests/test_fp8_exact_gpu.py asserts each): any other
+ *   activation (GELU_ERF, RELU, SILU, LEAKY_RELU: BYA_ERR_UNSUPPORTED -- the kernels instantiate the epilogue of the DiT Linears
+ *   only); n_split together with a residual (BYA_ERR_SHAPE, as for bya_gemm_bf16: the residual has no column map); ldc / ldres
+ *   % 4 or a C / res / bias / gate pointer that is not 8-byte aligned (BYA_ERR_ALIGN).
+ *   Which kernel: the persistent 256 x 256 one takes a launch of at least 200 of its tiles (batch included; option
+ *   BYA_OPT_FP8_KERNEL set to 1 keeps every launch off it, no option puts a smaller launch on it) that has at least 4 K-tiles (K >=
+ *   512), N % 8 == 0, n_split / c_split_stride / ldc / ldres / the batch strides of C, res and the gates % 8 == 0 and C, res,
+ *   bias and both gates 16-byte aligned; every other launch -- N = 260, a C view 8 but not 16 bytes aligned, K = 384, a single
+ *   output tile -- runs on the 128 x 128 kernel, which has none of these conditions.  On data whose sums are exact in fp32 the
+ *   two return the same bits.  A launch whose C or residual rows span 2 GiB runs as row chunks of whole 256-row blocks per
+ *   batch entry (bya_gemm_plan::row_chunks), each on the kernel the whole launch's tile count and its own alignment select.
  * --------------------------------------------------------------------------------------------- */
 int bya_quantize_rows_fp8(const void* x, void* q, float* scale, int32_t M, int32_t K, int64_t ldx, int64_t ldq,
                           hipStream_t stream);

@@ -23,6 +23,25 @@ products (multiples of 1/4, at most 9) and applies the scales after, so the sum 
 up to K = 12288) and the scales only move its exponent; MX: ``exact_operand`` of test_mx_gpu.py and ``dequant_mx`` of
 test_mx_cpu.py.
 
+The fp8 product through the whole epilogue of bya_gemm_fp8 (``exact_fp8_epilogue``; tests/test_fp8_exact_*.py).  Write
+S = a_scale[m] * w_scale[n] = 2^s, s in [-4, 4], and K <= 12288:
+    acc          a multiple of 2^-2, |acc| <= 9 K <= 110592 < 2^17 (below 2^19 units): exact in every K order;
+    acc * S      a power of two times acc: exact, a multiple of 2^(s - 2), at most 110592 * 2^s;
+    + bias       bias[n] = b * 2^-2, |b| <= 16 (no bias_rowscale: bya_gemm_fp8's callers have none): a multiple of
+                 u = 2^(min(s, 0) - 2), at most 110592 * 2^s + 4 -- (1769472 + 4) * 4 < 2^23 units at s = 4, below 2^19 units
+                 for s < 0;
+    * alpha * gate   alpha any power of two, gates in {1/2, 1}: value and unit scale alike;
+    + res        res[m, n] = r * 2^-2 * alpha * max(gate0[n], gate1[n]), |r| <= 64 (one gate: that gate; none: 1): a multiple
+                 of U = u * alpha * gate, whichever of the two gates row m takes (max gate >= gate, min(s, 0) <= 0), and at most
+                 32 alpha * gate in magnitude.
+So every value up to the final rounding is a multiple of U = 2^(min(s, 0) - 2) * alpha * gate[row type(m)][n] and at most
+(110592 * 2^s + 36) * 2^(2 - min(s, 0)) <= 7078032 < 2^23 units of U in magnitude: exact in fp32, in every order, on every
+kernel.  (The bf16 residual grid above, r * 2^-3 * alpha * MIN gate, is too fine for these scales: at s = 4 under the larger of two
+different gates its unit is 2^-4 alpha * gate, and 110592 * 2^4 is 2^24.75 of those.  Random data stays far below that bound --
+|acc| is of order 3 sqrt(K) -- so the four older fp8 cases of test_gemm_exact_gpu.py, which use it, are exact all the same; the
+bound here holds for ANY codes of the set, which is what test_fp8_exact_cpu.py checks with a planted row and channel of all
+3 x 3 at scale 4 x 4.)
+
 Outputs are checked inside a guard band (``GuardedOut``): the view is poisoned with NaN before the launch, the rest of the buffer
 (rows and columns around it, gaps between n_split outputs) holds a sentinel that must survive.
 """
@@ -81,6 +100,8 @@ def reference(a, w, bias=None, gate0=None, gate1=None, gate_split=0, res=None, r
     y = y * alpha
     if gate0 is not None:
         g1 = gate0 if gate1 is None else gate1
+        if gate0.dim() == 2:                                  # per batch entry [B, N] (gate_batch_stride = N)
+            gate0, g1 = gate0[:, None], g1[:, None]
         rows = torch.arange(y.shape[-2], device=y.device)[:, None]
         y = y * torch.where(rows < gate_split, gate0.double(), g1.double())
     if res is not None:
@@ -184,3 +205,51 @@ def exact_fp8_operand(rows, K, dev, seed):
     deq = codes.view(torch.float8_e4m3fn).double() * scale.double()[:, None]
     assert torch.equal(deq, el.double() * scale.double()[:, None])
     return codes, scale, deq
+
+
+def exact_fp8_epilogue(N, dev, seed, bias=False, gates=None, alpha=1.0, res_rows=None, batch=1, batch_gates=False):
+    """Epilogue operands of bya_gemm_fp8 on the grid of the module docstring ("The fp8 product through the whole epilogue").
+    ``gates``: None, "one" (gate1 absent) or "two"; ``batch_gates``: gate vectors per batch entry, [batch, N] (the launch's
+    gate_batch_stride is N).  -> dict(bias=, gate0=, gate1=, res=) (None where not asked; res: fp32 values
+    [batch, res_rows, N] = r * 2^-2 * alpha * max gate, to be placed by the caller)."""
+    out = dict(bias=None, gate0=None, gate1=None, res=None)
+    if bias:
+        out["bias"] = (torch.randint(-16, 17, (N,), generator=_gen(dev, seed), device=dev).float() * 2.0 ** -2).to(BF)
+    gshape = (batch, N) if batch_gates else (N,)
+    gmax = torch.ones(gshape, device=dev)
+    if gates:
+        g0 = pow2(gshape, dev, seed + 1, -1, 0)
+        out["gate0"], gmax = g0.to(BF), g0
+        if gates == "two":
+            g1 = pow2(gshape, dev, seed + 2, -1, 0)
+            out["gate1"], gmax = g1.to(BF), torch.maximum(g0, g1)
+    if res_rows is not None:
+        r = torch.randint(-64, 65, (batch, res_rows, N), generator=_gen(dev, seed + 3), device=dev).float()
+        out["res"] = r * (0.25 * alpha * (gmax[:, None] if batch_gates else gmax))
+    return out
+
+
+def bf16_ulps(got, want64):
+    """Error of ``got`` (bf16) against the bf16 rounding of ``want64`` in bf16 ulps of that rounding; results below 2^-6 (the
+    flat tails of GELU / SiLU, where fp32 1 + tanh(u) cancels) count in ulps of 2^-6: the measure of
+    test_activation_of_the_exact_pre_activation.  -> (worst ulps, flat index of the worst element)."""
+    want = want64.to(BF).double()
+    ulp = torch.exp2(torch.floor(torch.log2(want.abs().clamp_min(2.0 ** -6))) - 7)
+    err = (got.double() - want).abs() / ulp
+    return float(err.max()), int(err.flatten().argmax())
+
+
+# Row chunks (the 2 GiB reach of the epilogues' buffer descriptors, csrc/gemm_common.h gemm_row_chunks): an output that is the
+# first N columns of rows CHUNK_LD elements (4 MiB + 128 bytes) apart puts row 512 at byte offset 2^31 + 65536, so a launch of
+# 513 rows runs as pieces of 256, 256 and 1 rows (per batch entry).
+CHUNK_LD = 2 ** 21 + 64
+
+
+def chunk_view(B, M, N, dev, fill=SENTINEL):
+    """-> (int16 buffer [B, M, CHUNK_LD] holding ``fill``, its bf16 view [(B,) M, N] of the first N columns); on the meta
+    device the same geometry for the plan queries."""
+    buf = torch.empty(B, M, CHUNK_LD, dtype=torch.int16, device=dev)
+    if not buf.is_meta:
+        buf.fill_(fill)
+    out = buf.view(BF)[..., :N]
+    return buf, (out if B > 1 else out[0])

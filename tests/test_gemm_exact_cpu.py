@@ -241,6 +241,18 @@ def test_the_exact_gpu_matrix_covers_every_planned_kernel(ops):
     assert g.SKINNY_CASES
     assert {c[-1] for c in g.QKN_CASES} == {"p256", "p128", "p256|p128"}              # row plans 0, 1, 2
     assert {c[-1] for c in g.FP8_CASES} == {"t128x128", "p256"}
+    # ... and the e4m3 GEMM's own matrix (test_fp8_exact_gpu.py) holds, for EACH of its two kernels, every epilogue kind, batch
+    # 2, a launch cut into row chunks, and an odd and an even K-tile count: a case dropped later fails here
+    import test_fp8_exact_gpu as f8
+    for path in ("t128x128", "p256"):
+        cases = [c for c in f8.FP8_EXACT_CASES if c[6] == path and (path == "p256" or c[0].startswith("t-"))]
+        kinds = set().union(*(f8.epilogue_kinds(c[2], c[7]) for c in cases))
+        assert kinds >= f8.REQUIRED_KINDS, (path, sorted(f8.REQUIRED_KINDS - kinds))
+        assert any(c[1] == 2 for c in cases), path
+        assert {(c[4] // 128) % 2 for c in cases} == {0, 1}, path
+        assert any(c[5] == path and c[6] > 1 for c in f8.CHUNK_CASES), path
+    assert {c[4] for c in f8.FP8_EXACT_CASES if c[6] == "t128x128"} >= {128, 256, 384, 12288}
+    assert {c[4] for c in f8.FP8_EXACT_CASES if c[6] == "p256"} >= {512, 640, 768, 1152}
     assert {(c[0], c[-1]) for c in g.MX_CASES} == {("mxfp8", "t128x128"), ("mxfp6", "t128x128"), ("mxfp6", "t256x256")}
 
 
