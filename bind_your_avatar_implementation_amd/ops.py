@@ -228,8 +228,11 @@ _META_BASE = 1 << 40
 
 
 def _plan_p(t):
+    """Address of a tensor for a query; ``True`` stands for "some aligned tensor" (queries alone: ``_p`` has no such thing)."""
     if t is None:
         return None
+    if t is True:
+        return _META_BASE
     return _META_BASE + t.storage_offset() * t.element_size() if t.is_meta else t.data_ptr()
 
 
@@ -371,10 +374,11 @@ def attn_workspace_status(device=None):
     return n.value
 
 
-# ---- the GEMM front end.  Every entry point below is a launch / ``*_plan`` pair over ONE body: an operand reader checks the
-# operands of its format and hands their dimensions to the one descriptor filler (_fill_desc); the body builds the library's
-# argument tuple once, with the pointer function of its mode (_p: launch, _plan_p: query), so the query answers what the launch
-# does by construction; _launch / _plan make the call.
+# ---- the front end.  Every launch below goes through _launch, every query through _plan.  Where an entry point has a query, the
+# launch / ``*_plan`` pair stands over ONE body that checks the operands, derives dimensions, strides and descriptors once and
+# builds the library's argument tuple with the pointer function of its mode (_p: launch, _plan_p: query), so the query answers
+# what the launch does by construction.  The GEMMs first: an operand reader checks the operands of its format and hands their
+# dimensions to the one descriptor filler (_fill_desc).
 _UNSUPPORTED = next(rc for rc, name in _hip.ERRORS.items() if name == "BYA_ERR_UNSUPPORTED")
 
 
@@ -427,11 +431,14 @@ def _label(d, pre="", act=False, gate0=None, res=None):
 
 
 def _launch(bucket, label, work, call, may_decline=False):
-    """Enqueue ``call`` = (entry point, its arguments up to the stream) under timer ``bucket`` (+ ``label`` when shape labels are
-    on) and count its FLOPs there: ``work``, or 2 * batch * M * N * K of the bya_gemm_desc ``work`` (read only with the timers
-    on).  -> True; or False where ``may_decline`` and the library answers BYA_ERR_UNSUPPORTED: nothing was launched, so no
-    timer entry stays and nothing is counted (the caller's other launches count the FLOPs)."""
+    """Enqueue ``call`` = (entry point, its arguments up to the stream) under timer ``bucket`` (None: the entry point's name; a
+    ``bucket`` that starts with ":" is appended to it -- the attention's tag; + ``label`` when shape labels are on) and count its
+    FLOPs there: ``work``, or 2 * batch * M * N * K of the bya_gemm_desc ``work`` (read only with the timers on).  -> True; or
+    False where ``may_decline`` and the library answers BYA_ERR_UNSUPPORTED: nothing was launched, so no timer entry stays and
+    nothing is counted (the caller's other launches count the FLOPs).  A launch that raises counts nothing either."""
     entry, args = call
+    if bucket is None or bucket[0] == ":":
+        bucket = entry + (bucket or "")
     if label:
         bucket += label
     tok = _begin(bucket)
@@ -445,16 +452,16 @@ def _launch(bucket, label, work, call, may_decline=False):
     return True
 
 
-def _plan(call, may_decline=False):
-    """Ask ``<entry point>_plan`` with the arguments of ``call`` (``_launch``): ``gemm_plan``'s dict; None where ``may_decline``
-    and the library answers BYA_ERR_UNSUPPORTED."""
+def _plan(call, may_decline=False, struct=_hip.GemmPlan, to_dict=None):
+    """Ask ``<entry point>_plan`` with the arguments of ``call`` (``_launch``), which fills a ``struct``: its ``to_dict`` (by
+    default ``gemm_plan``'s dict); None where ``may_decline`` and the library answers BYA_ERR_UNSUPPORTED."""
     entry, args = call
-    p = _hip.GemmPlan()
+    p = struct()
     rc = getattr(_hip.load(), entry + "_plan")(*args, ctypes.byref(p))
     if may_decline and rc == _UNSUPPORTED:
         return None
     check(rc, entry + "_plan")
-    return _plan_dict(p)
+    return (to_dict or _plan_dict)(p)
 
 
 def _gemm_desc(a, w, out, res, split, epi, plan=False):
@@ -556,7 +563,6 @@ def gemm_qkv_norm_rope_plan(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, te
 
 def quantize_rows_fp8(x, q=None, scale=None):
     """Per-row symmetric e4m3 quantisation of a bf16 matrix [(B,) M, K] -> (uint8 [.., M, K], fp32 scale [.., M])."""
-    lib = _hip.load()
     b, M, K, bs, ldx = _mat(x, "x")
     if b > 1 and bs != M * ldx:
         raise ValueError("quantize_rows_fp8: batch entries must be evenly stacked rows")
@@ -566,9 +572,7 @@ def quantize_rows_fp8(x, q=None, scale=None):
         scale = torch.empty(*x.shape[:-1], dtype=torch.float32, device=x.device)
     assert q.dtype == torch.uint8 and q.is_contiguous() and scale.dtype == torch.float32 and scale.is_contiguous()
     assert q.numel() == b * M * K and scale.numel() == b * M
-    tok = _begin("bya_quantize_rows_fp8")
-    check(lib.bya_quantize_rows_fp8(_p(x), _p(q), _p(scale), b * M, K, ldx, K, _stream()), "bya_quantize_rows_fp8")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_quantize_rows_fp8", (_p(x), _p(q), _p(scale), b * M, K, ldx, K)))
     return q, scale
 
 
@@ -678,7 +682,6 @@ def mx_code_bytes(K, fmt):
 def quantize_mx(x, fmt="mxfp6", codes=None, scales=None):
     """OCP MX block quantisation of a bf16 matrix [(B,) M, K] -> (uint8 codes [.., M, K * bits / 8], uint8 e8m0 scales
     [.., M, K / 32]).  ``fmt`` "mxfp4" (e2m1) is a weight format: no GEMM takes it as its activations."""
-    lib = _hip.load()
     code = mx_weight_fmt_code(fmt)
     b, M, K, bs, ldx = _mat(x, "x")
     if b > 1 and bs != M * ldx:
@@ -690,9 +693,7 @@ def quantize_mx(x, fmt="mxfp6", codes=None, scales=None):
         scales = torch.empty(*lead, K // 32, dtype=torch.uint8, device=x.device)
     assert codes.dtype == torch.uint8 and codes.is_contiguous() and codes.numel() == b * M * mx_code_bytes(K, fmt)
     assert scales.dtype == torch.uint8 and scales.is_contiguous() and scales.numel() == b * M * (K // 32)
-    tok = _begin("bya_quantize_mx")
-    check(lib.bya_quantize_mx(_p(x), _p(codes), _p(scales), b * M, K, ldx, code, _stream()), "bya_quantize_mx")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_quantize_mx", (_p(x), _p(codes), _p(scales), b * M, K, ldx, code)))
     return codes, scales
 
 
@@ -889,165 +890,156 @@ def gemm_mx_call_plan(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="
     return _plan(("bya_gemm_mx_call", (ctypes.byref(c), ctypes.byref(d))), name == "qkn")
 
 
-def linear_small_m(x, w, bias, out, silu_in=False, act_out=None):
-    """out[M<=8, N] = f(x) @ w.T + bias (weight-streaming kernel)."""
-    lib = _hip.load()
+# ---- the small step kernels.  A ``_*_call`` body serves a launch (``plan`` False) and its query (True): -> (entry point, the
+# arguments of the launch up to the stream, or of ``<entry point>_plan`` up to the answer).
+def _step_plan(p, kernel):
+    return {"kernel": kernel, "grid": p.grid, "rounds": p.rounds, "items": p.items, "items_per_round": p.items_per_round}
+
+
+def _lin_call(x, w, bias, out, silu_in, act_out, plan):
+    q = _plan_p if plan else _p
     M, K = x.shape
     N = w.shape[0]
     assert x.is_contiguous() and w.is_contiguous() and out.is_contiguous() and out.shape == (M, N)
     assert x.dtype == w.dtype == out.dtype == torch.bfloat16 and w.shape[1] == K
-    tok = _begin("bya_linear_small_m")
-    check(lib.bya_linear_small_m(_p(x), _p(w), _p(bias), _p(out), M, N, K, int(silu_in), ACT[act_out], _stream()),
-          "bya_linear_small_m")
-    _end(tok)
+    return "bya_linear_small_m", ((q(x), q(w), q(out), M, N, K, ACT[act_out]) if plan else
+                                  (q(x), q(w), q(bias), q(out), M, N, K, int(silu_in), ACT[act_out]))
+
+
+def linear_small_m(x, w, bias, out, silu_in=False, act_out=None):
+    """out[M<=8, N] = f(x) @ w.T + bias (weight-streaming kernel)."""
+    _launch(None, None, 0.0, _lin_call(x, w, bias, out, silu_in, act_out, False))
     return out
-
-
-def _step_plan(p, kernel):
-    return {"kernel": kernel, "grid": p.grid, "rounds": p.rounds, "items": p.items, "items_per_round": p.items_per_round}
 
 
 def linear_small_m_plan(x, w, out, act_out=None):
     """What ``linear_small_m`` would launch (meta tensors will do): {"kernel": rows of the instantiation (2 / 8), "grid", "rounds"
     (trips of lane 0 over K), "items" (output columns = waves with work), "items_per_round"}."""
-    lib = _hip.load()
-    p, a = _hip.StepPlan(), _plan_p
-    M, K = x.shape
-    check(lib.bya_linear_small_m_plan(a(x), a(w), a(out), M, w.shape[0], K, ACT[act_out], ctypes.byref(p)), "bya_linear_small_m_plan")
-    return _step_plan(p, p.kernel)
+    return _plan(_lin_call(x, w, None, out, False, act_out, True), False, _hip.StepPlan, lambda p: _step_plan(p, p.kernel))
 
 
 def timestep_features(timesteps, out, flip_sin_to_cos=True, freq_shift=0.0):
-    lib = _hip.load()
     assert timesteps.dtype == torch.int64 and timesteps.is_cuda and out.dtype == torch.bfloat16
     b, dim = out.shape
-    tok = _begin("bya_timestep_features")
-    check(lib.bya_timestep_features(_p(timesteps), _p(out), b, dim, int(flip_sin_to_cos), float(freq_shift),
-                                    _stream()), "bya_timestep_features")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_timestep_features", (_p(timesteps), _p(out), b, dim, int(flip_sin_to_cos), float(freq_shift))))
     return out
+
+
+# ---- LayerNorm into its four output kinds, and the q/k norm + RoPE
+def _code_rows(q, batch, rows, row_bytes, name, plan=False):
+    """-> (row stride, batch stride) in bytes of a uint8 code matrix: contiguous [batch * rows * row_bytes] bytes in any shape,
+    or a strided view [(batch,) rows, row_bytes] with unit inner stride (rows padded to a wider pitch).  A query reads a
+    [(batch,) rows, width] matrix by its strides even where it is contiguous (2-D: batch stride 0, as ``_mat`` has it), and leaves
+    the width to the library to judge."""
+    assert q.dtype == torch.uint8, f"{name}: expected uint8"
+    matrix = q.dim() in (2, 3) and q.stride(-1) == 1 and q.shape[-2] == rows
+    if q.is_contiguous() and not (plan and matrix):
+        assert q.numel() == batch * rows * row_bytes, f"{name}: {q.numel()} bytes for {batch} x {rows} rows of {row_bytes}"
+        return row_bytes, rows * row_bytes
+    assert matrix and (plan or tuple(q.shape) in ((rows, row_bytes), (batch, rows, row_bytes))), f"{name}: shape {tuple(q.shape)}"
+    return q.stride(-2), q.stride(0) if q.dim() == 3 else 0
+
+
+def _ln_call(x, out, scales, kind, params, split, mod_batch_stride, eps, plan):
+    """LayerNorm of ``x`` into ``out``: bf16 (``kind`` "bf16"), or the uint8 codes of "fp8" / "mxfp8" / "mxfp6" with their
+    ``scales`` (a launch's; a query has none).  ``params``: weight, bias, shift0, scale0, shift1, scale1."""
+    q = _plan_p if plan else _p
+    last = _hip.LN_OUT_KINDS[kind] if plan else mx_fmt_code(kind) if kind.startswith("mx") else None
+    xb, rows, D, x_bs, ldx = _mat(x, "x", plan)
+    if kind == "bf16":
+        ob, rows_o, Do, y_bs, ldy = _mat(out, "out", plan)
+        assert (xb, rows, D) == (ob, rows_o, Do)
+    else:
+        ldy, y_bs = _code_rows(out, xb, rows, D if kind == "fp8" else mx_code_bytes(D, kind), "q" if kind == "fp8" else "codes", plan)
+    outs = (q(out),)
+    if not plan and kind != "bf16":                  # (a launch's scales: fp32 per row, or an e8m0 byte per block of 32)
+        dtype, n = (torch.float32, xb * rows) if kind == "fp8" else (torch.uint8, xb * rows * (D // 32))
+        assert scales.dtype == dtype and scales.is_contiguous() and scales.numel() == n
+        outs = (q(out), q(scales))
+    args = (q(x), *outs, *(q(t) for t in params), rows, xb, D, ldx, ldy, x_bs, y_bs, mod_batch_stride, split)
+    # (the four kinds have one query: the kind is its last argument)
+    entry ="bya_layernorm" if plan or kind == "bf16" else "bya_layernorm_fp8" if kind == "fp8" else "bya_layernorm_mx"
+    return entry, (*args, last) if plan else (*args, float(eps)) if last is None else (*args, float(eps), last)
 
 
 def layernorm(x, out, weight=None, bias=None, eps=1e-5, shift0=None, scale0=None, shift1=None, scale1=None,
               split=0, mod_batch_stride=0):
     """LayerNorm over the last dim (+ affine, + AdaLN modulation: rows < split use (shift0, scale0))."""
-    lib = _hip.load()
-    xb, rows, D, x_bs, ldx = _mat(x, "x")
-    ob, rows_o, Do, y_bs, ldy = _mat(out, "out")
-    assert (xb, rows, D) == (ob, rows_o, Do)
-    tok = _begin("bya_layernorm")
-    check(lib.bya_layernorm(_p(x), _p(out), _p(weight), _p(bias), _p(shift0), _p(scale0), _p(shift1), _p(scale1),
-                            rows, xb, D, ldx, ldy, x_bs, y_bs, mod_batch_stride, split, float(eps), _stream()),
-          "bya_layernorm")
-    _end(tok)
+    _launch(None, None, 0.0, _ln_call(x, out, None, "bf16", (weight, bias, shift0, scale0, shift1, scale1), split, mod_batch_stride, eps,
+                                      False))
     return out
-
-
-def _code_rows(q, batch, rows, row_bytes, name):
-    """-> (row stride, batch stride) in bytes of a uint8 code matrix: contiguous [batch * rows * row_bytes] bytes in any shape,
-    or a strided view [(batch,) rows, row_bytes] with unit inner stride (rows padded to a wider pitch)."""
-    assert q.dtype == torch.uint8, f"{name}: expected uint8"
-    if q.is_contiguous():
-        assert q.numel() == batch * rows * row_bytes, f"{name}: {q.numel()} bytes for {batch} x {rows} rows of {row_bytes}"
-        return row_bytes, rows * row_bytes
-    assert q.stride(-1) == 1 and tuple(q.shape) in ((rows, row_bytes), (batch, rows, row_bytes)), f"{name}: shape {tuple(q.shape)}"
-    return q.stride(-2), q.stride(0) if q.dim() == 3 else 0
 
 
 def layernorm_fp8(x, q, q_scale, weight=None, bias=None, eps=1e-5, shift0=None, scale0=None, shift1=None, scale1=None,
                   split=0, mod_batch_stride=0):
     """``layernorm`` + ``quantize_rows_fp8`` of its output in one pass (same bytes, no bf16 round trip)."""
-    lib = _hip.load()
-    xb, rows, D, x_bs, ldx = _mat(x, "x")
-    ldq, q_bs = _code_rows(q, xb, rows, D, "q")
-    assert q_scale.dtype == torch.float32 and q_scale.is_contiguous() and q_scale.numel() == xb * rows
-    tok = _begin("bya_layernorm_fp8")
-    check(lib.bya_layernorm_fp8(_p(x), _p(q), _p(q_scale), _p(weight), _p(bias), _p(shift0), _p(scale0), _p(shift1),
-                                _p(scale1), rows, xb, D, ldx, ldq, x_bs, q_bs, mod_batch_stride, split, float(eps),
-                                _stream()), "bya_layernorm_fp8")
-    _end(tok)
+    _launch(None, None, 0.0, _ln_call(x, q, q_scale, "fp8", (weight, bias, shift0, scale0, shift1, scale1), split, mod_batch_stride, eps,
+                                      False))
     return q, q_scale
-
 
 
 def layernorm_mx(x, codes, scales, fmt="mxfp6", weight=None, bias=None, eps=1e-5, shift0=None, scale0=None, shift1=None,
                  scale1=None, split=0, mod_batch_stride=0):
     """``layernorm`` + ``quantize_mx`` of its bf16-rounded output in one pass (same bytes, no bf16 round trip)."""
-    lib = _hip.load()
-    code = mx_fmt_code(fmt)
-    xb, rows, D, x_bs, ldx = _mat(x, "x")
-    rb_ = mx_code_bytes(D, fmt)
-    ldq, q_bs = _code_rows(codes, xb, rows, rb_, "codes")
-    assert scales.dtype == torch.uint8 and scales.is_contiguous() and scales.numel() == xb * rows * (D // 32)
-    tok = _begin("bya_layernorm_mx")
-    check(lib.bya_layernorm_mx(_p(x), _p(codes), _p(scales), _p(weight), _p(bias), _p(shift0), _p(scale0), _p(shift1),
-                               _p(scale1), rows, xb, D, ldx, ldq, x_bs, q_bs, mod_batch_stride, split, float(eps),
-                               code, _stream()), "bya_layernorm_mx")
-    _end(tok)
+    mx_fmt_code(fmt)                                 # ("mxfp4" is a weight format, "bf16" / "fp8" are other wrappers')
+    _launch(None, None, 0.0, _ln_call(x, codes, scales, fmt, (weight, bias, shift0, scale0, shift1, scale1), split, mod_batch_stride, eps,
+                                      False))
     return codes, scales
+
+
+def layernorm_plan(x, out, weight=None, bias=None, shift0=None, scale0=None, shift1=None, scale1=None, split=0,
+                   mod_batch_stride=0, out_kind="bf16"):
+    """What ``layernorm`` (``out_kind`` "bf16"), ``layernorm_fp8`` ("fp8") or ``layernorm_mx`` ("mxfp8" / "mxfp6") would run
+    (host-side, launches nothing; device or meta tensors): {"kernel" (``_hip.LN_KERNELS``), "vec", "nv", "modulated",
+    "rows_per_wave", "waves", "grid"}.  ``out``: the bf16 output, or the uint8 code matrix [(B,) rows, row bytes] of the quantised
+    forms.  Parameters: tensors, or True for "some aligned vector"."""
+    call = _ln_call(x, out, None, out_kind, (weight, bias, shift0, scale0, shift1, scale1), split, mod_batch_stride, 0.0, True)
+    return _plan(call, False, _hip.LayerNormPlan, lambda p: {
+        "kernel": _hip.LN_KERNELS[p.kernel], "vec": p.vec, "nv": p.nv, "modulated": bool(p.modulated), "rows_per_wave": p.rows_per_wave,
+        "waves": p.waves, "grid": p.grid})
+
+
+def _qkn_rope_call(q, k, params, cos, sin, heads, text_rows, eps, k_scale, stats, plan):
+    """``params``: qw, qb, kw, kb.  A query may name its operands loosely: True for a present tensor, a slot count for ``stats``."""
+    ptr = _plan_p if plan else _p
+    layout = b, S, _, bs, ld = _mat(q if q is not None else k, "q", plan)
+    assert q is None or k is None or _mat(k, "k", plan) == layout
+    if plan and isinstance(stats, int):
+        ps, slots = _META_BASE, stats
+    elif stats is not None:
+        assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.dim() == 3 and stats.shape[1:] == (2, b * heads)
+        ps, slots = ptr(stats), stats.shape[0]
+    else:
+        ps, slots = None, 0
+    if cos is not None and cos is not True:
+        assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
+        assert cos.shape == (S - text_rows, 64)
+    args = (ptr(q), ptr(k), *(ptr(t) for t in params), ptr(cos), ptr(sin), b, S, heads, ld, bs if b > 1 else 0, text_rows)
+    return "bya_qknorm_rope", (*args, ps, slots) if plan else (*args, float(eps), float(k_scale), ps, slots)
+
 
 def qknorm_rope(q, k, qw, qb, kw, kb, cos, sin, heads, text_rows, eps=1e-6, k_scale=1.0, stats=None):
     """In place on q, k [B, S, heads*64]; q or k may be None (only the other one is processed).  ``stats``: fp32
     [slots, 2, B * heads], ZEROED by the caller: the kernel raises its entries to the squared norms of the rows it writes
     (max over the slots = max ||q||^2, max ||k||^2 per (batch, head): the data-dependent score bound of ``attention``)."""
-    lib = _hip.load()
-    b, S, _, bs, ld = _mat(q if q is not None else k, "q")
-    assert q is None or k is None or _mat(k, "k") == _mat(q, "q")
-    if stats is not None:
-        assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.dim() == 3 and stats.shape[1:] == (2, b * heads)
-    if cos is not None:
-        assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
-        assert cos.shape == (S - text_rows, 64)
-    tok = _begin("bya_qknorm_rope")
-    check(lib.bya_qknorm_rope(_p(q), _p(k), _p(qw), _p(qb), _p(kw), _p(kb), _p(cos), _p(sin), b, S, heads, ld,
-                              bs if b > 1 else 0, text_rows, float(eps), float(k_scale), _p(stats),
-                              0 if stats is None else stats.shape[0], _stream()), "bya_qknorm_rope")
-    _end(tok)
-
-
-# ---- what the norm kernels run (bya_layernorm_plan / bya_qknorm_rope_plan: host-side, launch nothing; device or meta tensors)
-def layernorm_plan(x, out, weight=None, bias=None, shift0=None, scale0=None, shift1=None, scale1=None, split=0,
-                   mod_batch_stride=0, out_kind="bf16"):
-    """What ``layernorm`` (``out_kind`` "bf16"), ``layernorm_fp8`` ("fp8") or ``layernorm_mx`` ("mxfp8" / "mxfp6") would run:
-    {"kernel" (``_hip.LN_KERNELS``), "vec", "nv", "modulated", "rows_per_wave", "waves", "grid"}.  ``out``: the bf16 output, or
-    the uint8 code matrix [(B,) rows, row bytes] of the quantised forms.  Parameters: tensors, or True for "some aligned vector"."""
-    lib = _hip.load()
-    xb, rows, D, x_bs, ldx = _mat(x, "x", allow_meta=True)
-    if out_kind == "bf16":
-        ob, rows_o, Do, y_bs, ldy = _mat(out, "out", allow_meta=True)
-        assert (xb, rows, D) == (ob, rows_o, Do)
-    else:
-        assert out.dtype == torch.uint8 and out.stride(-1) == 1 and out.dim() in (2, 3) and out.shape[-2] == rows
-        ldy, y_bs = out.stride(-2), out.stride(0) if out.dim() == 3 else 0
-    q = lambda t: _META_BASE if t is True else _plan_p(t)
-    p = _hip.LayerNormPlan()
-    check(lib.bya_layernorm_plan(_plan_p(x), _plan_p(out), q(weight), q(bias), q(shift0), q(scale0), q(shift1), q(scale1), rows, xb,
-                                 D, ldx, ldy, x_bs, y_bs, mod_batch_stride, split, _hip.LN_OUT_KINDS[out_kind], ctypes.byref(p)),
-          "bya_layernorm_plan")
-    return {"kernel": _hip.LN_KERNELS[p.kernel], "vec": p.vec, "nv": p.nv, "modulated": bool(p.modulated),
-            "rows_per_wave": p.rows_per_wave, "waves": p.waves, "grid": p.grid}
+    _launch(None, None, 0.0, _qkn_rope_call(q, k, (qw, qb, kw, kb), cos, sin, heads, text_rows, eps, k_scale, stats, False))
 
 
 def qknorm_rope_plan(q, k, heads, text_rows, cos=True, stats=None):
-    """What ``qknorm_rope`` would run: {"stats" (the STATS instance), "only" (0: q and k, 1: q alone, 2: k alone), "slots",
-    "pairs" ((row, head) pairs: q's, then k's), "waves" (8 pairs each), "grid"}.  ``cos``: None, True (tables present) or the
-    tensor; ``stats``: None, the number of slots, or the tensor."""
-    lib = _hip.load()
-    b, S, _, bs, ld = _mat(q if q is not None else k, "q", allow_meta=True)
-    assert q is None or k is None or _mat(k, "k", allow_meta=True) == (b, S, _, bs, ld)
-    pc = _META_BASE if cos is True else _plan_p(cos)
-    ps, slots = (None, 0) if stats is None else (_META_BASE, stats) if isinstance(stats, int) else (_plan_p(stats), stats.shape[0])
-    p, m = _hip.QkNormRopePlan(), _META_BASE
-    check(lib.bya_qknorm_rope_plan(_plan_p(q), _plan_p(k), m, m, m, m, pc, pc, b, S, heads, ld, bs if b > 1 else 0, text_rows, ps,
-                                   slots, ctypes.byref(p)), "bya_qknorm_rope_plan")
-    return {"stats": bool(p.stats), "only": p.only, "slots": p.slots, "pairs": p.pairs, "waves": p.waves, "grid": p.grid}
+    """What ``qknorm_rope`` would run (host-side; device or meta tensors): {"stats" (the STATS instance), "only" (0: q and k,
+    1: q alone, 2: k alone), "slots", "pairs" ((row, head) pairs: q's, then k's), "waves" (8 pairs each), "grid"}.  ``cos``: None,
+    True (tables present) or the tensor; ``stats``: None, the number of slots, or the tensor."""
+    call = _qkn_rope_call(q, k, (True,) * 4, cos, cos, heads, text_rows, 0.0, 0.0, stats, True)
+    return _plan(call, False, _hip.QkNormRopePlan, lambda p: {
+        "stats": bool(p.stats), "only": p.only, "slots": p.slots, "pairs": p.pairs, "waves": p.waves, "grid": p.grid})
 
 
-# (call tag, softmax variant) -> launches since the last reset; the variant is reported by the library itself
-ATTN_VARIANT_NAMES = {0: "d64_running_max", 1: "d64_prescaled_running_max", 2: "d64_static_bound", 3: "d128_running_max",
-                      4: "d64_static_bound_w4", 5: "d64_device_bound_w4"}
+# ---- attention.  (call tag, softmax variant) -> launches since the last reset; the variant is reported by the library itself
+ATTN_VARIANT_NAMES = _hip.ATTN_VARIANTS
 ATTN_BOUND_LIMIT = 90.0          # BYA_ATTN_BOUND_LIMIT (include/bya.h): |score| <= 90 keeps P = exp2(s) and its row sums normal
 ATTN_VARIANTS = {}
+KV_MIX_FORMS = _hip.KV_MIX_FORMS
+TINY_INSTANCES = _hip.TINY_INSTANCES
 
 
 def _attn_desc(head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale, prescaled, score_bound,
@@ -1070,62 +1062,95 @@ def _attn_desc(head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strid
     return d
 
 
+def _mx_out_pair(mx_out, who, plan):
+    """``mx_out`` = (codes, scales, fmt) -> (codes, scales, format code): uint8 device tensors (a query: or meta tensors) in an
+    activation format.  Where the rows lie is the caller's rule."""
+    codes, scales, fmt = mx_out
+    code = mx_fmt_code(fmt)                          # "mxfp4" is a weight format: refused here like everywhere for activations
+    for t, name in ((codes, "codes"), (scales, "scales")):
+        if t.dtype != torch.uint8:
+            raise TypeError(f"{who}: mx_out {name}: expected uint8, got {t.dtype}")
+        if not (t.is_cuda or (plan and t.is_meta)):
+            raise ValueError(f"{who}: mx_out {name}: expected a device tensor")
+    return codes, scales, code
+
+
 def _attn_mx_out(mx_out, heads, head_dim, nb1, nb2, Sq, o_strides, plan=False):
     """``mx_out`` = (codes, scales, fmt) of ``attention`` -> (codes, scales, format code, the six byte strides).  The pair holds the
     [nb1 * nb2 * Sq, heads * 64] output as ``quantize_mx`` would: uint8 codes [.., heads * 64 * bits / 8], uint8 scales [.., heads
     * 2], contiguous, batches stacked (level 1 over level 2 over rows)."""
     if o_strides is not None and tuple(o_strides) != (0, 0, 0):
         raise ValueError("attention: with mx_out there is no bf16 output -- pass out=None and no o_strides")
-    codes, scales, fmt = mx_out
-    code = mx_fmt_code(fmt)                          # "mxfp4" is a weight format: refused here like everywhere for activations
+    codes, scales, code = _mx_out_pair(mx_out, "attention", plan)
     if head_dim != 64:
         raise ValueError("attention: mx_out needs head_dim 64 (one MX block per 32 columns, two per head)")
-    rows, cb, sb = nb1 * nb2 * Sq, mx_code_bytes(heads * 64, fmt), heads * 2
+    rows, cb, sb = nb1 * nb2 * Sq, mx_code_bytes(heads * 64, mx_out[2]), heads * 2
     for t, name, width in ((codes, "codes", cb), (scales, "scales", sb)):
-        if t.dtype != torch.uint8:
-            raise TypeError(f"attention: mx_out {name}: expected uint8, got {t.dtype}")
         if not t.is_contiguous() or t.numel() != rows * width or t.shape[-1] != width:
             raise ValueError(f"attention: mx_out {name} must be a contiguous [{rows} rows, {width}] uint8 tensor, got "
                              f"{tuple(t.shape)}")
-        if not (t.is_cuda or (plan and t.is_meta)):
-            raise ValueError(f"attention: mx_out {name}: expected a device tensor")
     return codes, scales, code, (nb2 * Sq * cb, Sq * cb, cb, nb2 * Sq * sb, Sq * sb, sb)
 
 
-# ---- what the attention launches run (bya_attn_plan & co.: host-side, launch nothing, meta tensors may stand for device tensors)
-KV_MIX_FORMS = _hip.KV_MIX_FORMS
-TINY_INSTANCES = _hip.TINY_INSTANCES
+def _attn_call(qkv, out, mx_out, workspace, plan, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale,
+               prescaled, score_bound, bound):
+    """-> (descriptor, ``_attn_mx_out``'s tuple or None, the call) of an attention launch (``qkv`` = (q, k, v)) or its query (()).
+    The query's call carries ``workspace``: None = as the launch finds it."""
+    ptr = _plan_p if plan else _p
+    mx = None
+    if mx_out is not None:
+        if out is not None:
+            raise ValueError("attention: with mx_out there is no bf16 output -- pass out=None")
+        mx = _attn_mx_out(mx_out, heads, head_dim, nb1, nb2, Sq, o_strides, plan)
+        o_strides = (0, 0, 0)
+    for t in qkv + (() if mx is not None else (out,)):
+        assert t.dtype == torch.bfloat16 and (t.is_cuda or (plan and t.is_meta))
+    d = _attn_desc(head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale, prescaled,
+                   score_bound, bound, plan)
+    o = out if mx is None else mx[0]
+    if workspace is None and prescaled and (score_bound > 0 or bound is not None) and o.is_cuda and o.device.index not in _ATTN_WS:
+        ensure_attn_workspace(o.device)
+    if plan:                                         # (bya_attn_plan / bya_attn_mx_plan: no q, k, v, and the workspace to assume)
+        if workspace is None:
+            workspace = -1 if o.is_cuda else 0
+        return d, mx, (("bya_attn", (ctypes.byref(d), ptr(out), int(workspace))) if mx is None else
+                       ("bya_attn_mx", (ctypes.byref(d), ptr(mx[0]), ptr(mx[1]), mx[2], *mx[3], int(workspace))))
+    q, k, v = qkv
+    return d, mx, (("bya_attn_fwd", (ptr(q), ptr(k), ptr(v), ptr(out), ctypes.byref(d))) if mx is None else
+                   ("bya_attn_fwd_mx", (ptr(q), ptr(k), ptr(v), ptr(mx[0]), ptr(mx[1]), ctypes.byref(d), mx[2], *mx[3])))
+
+
+def attention(q, k, v, out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides=None,
+              scale, tag="other", prescaled=False, score_bound=0.0, bound=None, mx_out=None):
+    """Flash attention with explicit (level-1, level-2, row) element strides for q, k, v, out.
+    ``bound`` = (stats, bh0, flags): the data-dependent score bound -- ``stats`` fp32 [slots, 2, n] as written by
+    ``qknorm_rope(stats=...)``, this launch's (batch, head) index bh at column bh0 + bh, ``flags`` int32 [nb1 * nb2 * heads]
+    (scratch: which heads went to the running-maximum kernel).
+    ``mx_out`` = (codes, scales, fmt) with ``out`` None (head_dim 64): the output leaves as MX codes and block scales --
+    byte for byte ``quantize_mx(out, fmt)`` of the [nb1 * nb2 * Sq, heads * 64] output, which is never written; returns the
+    pair, the ``quantised=`` operand of the next MX Linear.  fmt: "mxfp8" or "mxfp6"."""
+    d, mx, call = _attn_call((q, k, v), out, mx_out, None, False, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides,
+                             o_strides, scale, prescaled, score_bound, bound)
+    var = ATTN_VARIANT_NAMES.get(_hip.load().bya_attn_variant(ctypes.byref(d)), "rejected")
+    ATTN_VARIANTS[tag, var] = ATTN_VARIANTS.get((tag, var), 0) + 1
+    label = _SHAPE_LABELS and f":{nb1}x{nb2}x{heads}h_q{Sq}_kv{Skv}_d{head_dim}" + (f">{mx_out[2]}" if mx is not None else "")
+    _launch(":" + tag, label, 4.0 * nb1 * nb2 * heads * Sq * Skv * head_dim, call)
+    return (mx[0], mx[1]) if mx is not None else out
 
 
 def attention_plan(out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides=None, scale,
                    prescaled=False, score_bound=0.0, bound=None, workspace=None, mx_out=None):
-    """What ``attention`` with the same arguments would run: {"variant" (``ATTN_VARIANT_NAMES``), "grid", "q_tile", "stream_k",
-    "sk_rem", "sk_cut", "o_wide", "second_launch"}.  ``workspace``: True / False = as if a stream-K workspace were / were not
-    registered; None = as the launch would find it (a device ``out`` registers the device's workspace like ``attention``
-    does; with a meta ``out``: none).  ``mx_out`` (with ``out`` None): the plan of the MX-output launch (bya_attn_mx_plan);
-    the dict then also has "mx_out": the format."""
-    lib = _hip.load()
-    mx = None
-    if mx_out is not None:
-        if out is not None:
-            raise ValueError("attention_plan: with mx_out there is no bf16 output -- pass out=None")
-        mx = _attn_mx_out(mx_out, heads, head_dim, nb1, nb2, Sq, o_strides, plan=True)
-        out, o_strides = mx[0], (0, 0, 0)
-    d = _attn_desc(head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale, prescaled,
-                   score_bound, bound, plan=True)
-    if workspace is None:
-        if out.is_cuda and prescaled and (score_bound > 0 or bound is not None) and out.device.index not in _ATTN_WS:
-            ensure_attn_workspace(out.device)
-        workspace = -1 if out.is_cuda else 0
-    p = _hip.AttnPlan()
-    if mx is not None:
-        check(lib.bya_attn_mx_plan(ctypes.byref(d), _plan_p(mx[0]), _plan_p(mx[1]), mx[2], *mx[3], int(workspace), ctypes.byref(p)),
-              "bya_attn_mx_plan")
-    else:
-        check(lib.bya_attn_plan(ctypes.byref(d), _plan_p(out), int(workspace), ctypes.byref(p)), "bya_attn_plan")
-    assert p.variant == lib.bya_attn_variant(ctypes.byref(d))
-    plan = {"variant": ATTN_VARIANT_NAMES[p.variant], "grid": p.grid, "q_tile": p.q_tile, "stream_k": p.stream_k,
-            "sk_rem": p.sk_rem, "sk_cut": p.sk_cut, "o_wide": p.o_wide, "second_launch": p.second_launch}
+    """What ``attention`` with the same arguments would run (host-side, launches nothing; meta tensors may stand for device
+    tensors): {"variant" (``ATTN_VARIANT_NAMES``), "grid", "q_tile", "stream_k", "sk_rem", "sk_cut", "o_wide", "second_launch"}.
+    ``workspace``: True / False = as if a stream-K workspace were / were not registered; None = as the launch would find it
+    (a device ``out`` registers the device's workspace like ``attention`` does; with a meta ``out``: none).  ``mx_out`` (with
+    ``out`` None): the plan of the MX-output launch; the dict then also has "mx_out": the format."""
+    d, mx, call = _attn_call((), out, mx_out, workspace, True, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides,
+                             o_strides, scale, prescaled, score_bound, bound)
+    plan = _plan(call, False, _hip.AttnPlan, lambda p: {
+        "variant": ATTN_VARIANT_NAMES[p.variant], "grid": p.grid, "q_tile": p.q_tile, "stream_k": p.stream_k, "sk_rem": p.sk_rem,
+        "sk_cut": p.sk_cut, "o_wide": p.o_wide, "second_launch": p.second_launch})
+    assert plan["variant"] == ATTN_VARIANT_NAMES.get(_hip.load().bya_attn_variant(ctypes.byref(d)))
     if mx is not None:
         plan["mx_out"] = mx_out[2]
     return plan
@@ -1136,116 +1161,6 @@ def attention_plan_key(plan):
     width) or "/mxfp8" / "/mxfp6" (the MX-output launch)."""
     tail = "/" + plan["mx_out"] if plan.get("mx_out") else ("/wide" if plan["o_wide"] else "/narrow")
     return plan["variant"] + ("+streamk" if plan["stream_k"] else "") + tail
-
-
-def attn_kv_mix_plan(z, af=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides=None,
-                     scale=1.0, mx_out=None):
-    """What ``attn_kv_mix`` would run: {"form" (``KV_MIX_FORMS``), "head_dim", "grid", "row_chunks", "lds_bytes", "big_lds"}.
-    ``mx_out`` (with ``z`` None): the plan of the MX-output launch (bya_attn_kv_mix_mx_plan; the dict then also has "mx_out":
-    the format); None where the library declines it (more than 32 keys, or the generic reference form)."""
-    lib = _hip.load()
-    p = _hip.AttnMixPlan()
-    if mx_out is not None:
-        mx = _mix_mx_out(mx_out, z, z_strides, heads, head_dim, n_grp, Sq, plan=True)
-        d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, (0, 0), scale)
-        rc = lib.bya_attn_kv_mix_mx_plan(_plan_p(mx[0]), _plan_p(mx[1]), _plan_p(af), ctypes.byref(d), mx[2], *mx[3], ctypes.byref(p))
-        if rc == _UNSUPPORTED:
-            return None
-        check(rc, "bya_attn_kv_mix_mx_plan")
-    else:
-        d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale)
-        check(lib.bya_attn_kv_mix_plan(_plan_p(z), _plan_p(af), ctypes.byref(d), ctypes.byref(p)), "bya_attn_kv_mix_plan")
-    plan = {"form": KV_MIX_FORMS[p.form], "head_dim": p.head_dim, "grid": p.grid, "row_chunks": p.row_chunks,
-            "lds_bytes": p.lds_bytes, "big_lds": p.big_lds}
-    if mx_out is not None:
-        plan["mx_out"] = mx_out[2]
-    return plan
-
-
-def _mix_mx_out(mx_out, z, z_strides, heads, head_dim, n_grp, Sq, plan=False):
-    """``mx_out`` = (codes, scales, fmt) of ``attn_kv_mix`` -> (codes, scales, format code, (c_grp, c_row, sc_grp, sc_row) in
-    bytes).  The pair holds rows of the [n_grp * Sq, heads * head_dim] mix as ``quantize_mx`` would: uint8, last dimension
-    contiguous and at least heads * head_dim * bits / 8 (codes) / heads * head_dim / 32 (scales) wide.  2-D [n_grp * Sq, width]:
-    groups are stacked rows; 3-D [n_grp, Sq, width]: the strides are the tensor's (views of larger buffers are fine)."""
-    if z is not None or z_strides is not None:
-        raise ValueError("attn_kv_mix: with mx_out there is no bf16 output -- pass z=None and no z_strides")
-    codes, scales, fmt = mx_out
-    code = mx_fmt_code(fmt)                          # "mxfp4" is a weight format: refused here like everywhere for activations
-    strides = []
-    for t, name, width in ((codes, "codes", mx_code_bytes(heads * head_dim, fmt)), (scales, "scales", heads * head_dim // 32)):
-        if t.dtype != torch.uint8:
-            raise TypeError(f"attn_kv_mix: mx_out {name}: expected uint8, got {t.dtype}")
-        if not (t.is_cuda or (plan and t.is_meta)):
-            raise ValueError(f"attn_kv_mix: mx_out {name}: expected a device tensor")
-        ok = t.dim() in (2, 3) and t.stride(-1) == 1 and t.shape[-1] >= width
-        if ok and t.dim() == 2:
-            ok = t.shape[0] >= n_grp * Sq
-            grp, row = Sq * t.stride(0), t.stride(0)
-        elif ok:
-            ok = t.shape[0] >= n_grp and t.shape[1] >= Sq
-            grp, row = t.stride(0), t.stride(1)
-        if not ok:
-            raise ValueError(f"attn_kv_mix: mx_out {name} must be uint8 [{n_grp * Sq}, >= {width}] or [{n_grp}, {Sq}, >= {width}] "
-                             f"with a contiguous last dimension, got {tuple(t.shape)} strides {tuple(t.stride())}")
-        strides += [grp, row]
-    return codes, scales, code, tuple(strides)
-
-
-def attn_tiny_plan(q, k, v, out, L, heads, n_outer, n_inner, ld_qkv, ld_o):
-    """Which of the eight ``attn_tiny`` kernel instances would run: {"instance" (``TINY_INSTANCES``), "grid", "waves"}."""
-    lib = _hip.load()
-    p, a = _hip.AttnTinyPlan(), _plan_p
-    check(lib.bya_attn_tiny_plan(a(q), a(k), a(v), a(out), L, heads, n_outer, n_inner, ld_qkv, ld_o, ctypes.byref(p)),
-          "bya_attn_tiny_plan")
-    return {"instance": TINY_INSTANCES[p.instance], "grid": p.grid, "waves": p.waves}
-
-
-def _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale):
-    d = AttnMixDesc()
-    d.head_dim, d.heads, d.n_id, d.n_grp, d.Sq, d.Skv = head_dim, heads, n_id, n_grp, Sq, Skv
-    d.q_grp, d.q_row = q_strides
-    d.k_id, d.k_grp, d.k_row = k_strides
-    d.v_id, d.v_grp, d.v_row = v_strides
-    d.z_grp, d.z_row = z_strides
-    d.scale = float(scale)
-    return d
-
-
-def attention(q, k, v, out, *, head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides=None,
-              scale, tag="other", prescaled=False, score_bound=0.0, bound=None, mx_out=None):
-    """Flash attention with explicit (level-1, level-2, row) element strides for q, k, v, out.
-    ``bound`` = (stats, bh0, flags): the data-dependent score bound -- ``stats`` fp32 [slots, 2, n] as written by
-    ``qknorm_rope(stats=...)``, this launch's (batch, head) index bh at column bh0 + bh, ``flags`` int32 [nb1 * nb2 * heads]
-    (scratch: which heads went to the running-maximum kernel).
-    ``mx_out`` = (codes, scales, fmt) with ``out`` None (head_dim 64): the output leaves as MX codes and block scales
-    (bya_attn_fwd_mx) -- byte for byte ``quantize_mx(out, fmt)`` of the [nb1 * nb2 * Sq, heads * 64] output, which is never
-    written; returns the pair, the ``quantised=`` operand of the next MX Linear.  fmt: "mxfp8" or "mxfp6"."""
-    lib = _hip.load()
-    mx = None
-    if mx_out is not None:
-        if out is not None:
-            raise ValueError("attention: with mx_out there is no bf16 output -- pass out=None")
-        mx = _attn_mx_out(mx_out, heads, head_dim, nb1, nb2, Sq, o_strides)
-        o_strides = (0, 0, 0)
-    for t in (q, k, v) + (() if mx is not None else (out,)):
-        assert t.dtype == torch.bfloat16 and t.is_cuda
-    d = _attn_desc(head_dim, heads, nb1, nb2, Sq, Skv, q_strides, k_strides, v_strides, o_strides, scale, prescaled,
-                   score_bound, bound)
-    if prescaled and (score_bound > 0 or bound is not None) and q.device.index not in _ATTN_WS:
-        ensure_attn_workspace(q.device)
-    var = ATTN_VARIANT_NAMES.get(lib.bya_attn_variant(ctypes.byref(d)), "rejected")
-    ATTN_VARIANTS[tag, var] = ATTN_VARIANTS.get((tag, var), 0) + 1
-    label = ("bya_attn_fwd_mx:" if mx is not None else "bya_attn_fwd:") + tag
-    if _SHAPE_LABELS:
-        label += f":{nb1}x{nb2}x{heads}h_q{Sq}_kv{Skv}_d{head_dim}" + (f">{mx_out[2]}" if mx is not None else "")
-    tok = _begin(label, 4.0 * nb1 * nb2 * heads * Sq * Skv * head_dim)
-    if mx is not None:
-        check(lib.bya_attn_fwd_mx(_p(q), _p(k), _p(v), _p(mx[0]), _p(mx[1]), ctypes.byref(d), mx[2], *mx[3], _stream()),
-              "bya_attn_fwd_mx")
-    else:
-        check(lib.bya_attn_fwd(_p(q), _p(k), _p(v), _p(out), ctypes.byref(d), _stream()), "bya_attn_fwd")
-    _end(tok)
-    return (mx[0], mx[1]) if mx is not None else out
 
 
 def self_attention(q, k, v, out, heads, head_dim=64, scale=None, tag="other", prescaled=False, score_bound=0.0, bound=None,
@@ -1266,88 +1181,146 @@ def self_attention(q, k, v, out, heads, head_dim=64, scale=None, tag="other", pr
                      mx_out=mx_out)
 
 
+def _mix_mx_out(mx_out, z, z_strides, heads, head_dim, n_grp, Sq, plan=False):
+    """``mx_out`` = (codes, scales, fmt) of ``attn_kv_mix`` -> (codes, scales, format code, (c_grp, c_row, sc_grp, sc_row) in
+    bytes).  The pair holds rows of the [n_grp * Sq, heads * head_dim] mix as ``quantize_mx`` would: uint8, last dimension
+    contiguous and at least heads * head_dim * bits / 8 (codes) / heads * head_dim / 32 (scales) wide.  2-D [n_grp * Sq, width]:
+    groups are stacked rows; 3-D [n_grp, Sq, width]: the strides are the tensor's (views of larger buffers are fine)."""
+    if z is not None or z_strides is not None:
+        raise ValueError("attn_kv_mix: with mx_out there is no bf16 output -- pass z=None and no z_strides")
+    codes, scales, code = _mx_out_pair(mx_out, "attn_kv_mix", plan)
+    strides = []
+    for t, name, width in ((codes, "codes", mx_code_bytes(heads * head_dim, mx_out[2])), (scales, "scales", heads * head_dim // 32)):
+        ok = t.dim() in (2, 3) and t.stride(-1) == 1 and t.shape[-1] >= width
+        if ok and t.dim() == 2:
+            ok = t.shape[0] >= n_grp * Sq
+            grp, row = Sq * t.stride(0), t.stride(0)
+        elif ok:
+            ok = t.shape[0] >= n_grp and t.shape[1] >= Sq
+            grp, row = t.stride(0), t.stride(1)
+        if not ok:
+            raise ValueError(f"attn_kv_mix: mx_out {name} must be uint8 [{n_grp * Sq}, >= {width}] or [{n_grp}, {Sq}, >= {width}] "
+                             f"with a contiguous last dimension, got {tuple(t.shape)} strides {tuple(t.stride())}")
+        strides += [grp, row]
+    return codes, scales, code, tuple(strides)
+
+
+def _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale):
+    d = AttnMixDesc()
+    d.head_dim, d.heads, d.n_id, d.n_grp, d.Sq, d.Skv = head_dim, heads, n_id, n_grp, Sq, Skv
+    d.q_grp, d.q_row = q_strides
+    d.k_id, d.k_grp, d.k_row = k_strides
+    d.v_id, d.v_grp, d.v_row = v_strides
+    d.z_grp, d.z_row = z_strides
+    d.scale = float(scale)
+    return d
+
+
+def _mix_call(qkvr, af, z, wsum, mx_out, plan, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale):
+    """-> (``_mix_mx_out``'s tuple or None, the call) of an ``attn_kv_mix`` launch (``qkvr`` = (q, k, v, r)) or its query (())."""
+    ptr = _plan_p if plan else _p
+    mx = None
+    if mx_out is not None:
+        mx = _mix_mx_out(mx_out, z, z_strides, heads, head_dim, n_grp, Sq, plan)
+        z_strides = (0, 0)
+    d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale)
+    for t in qkvr + (() if mx is not None else (z,)):
+        assert t.dtype == torch.bfloat16 and (t.is_cuda or (plan and t.is_meta))
+    assert not qkvr or (qkvr[3].is_contiguous() and qkvr[3].numel() == n_grp * Sq * n_id)
+    assert af is None or (af.is_contiguous() and af.dtype == torch.bfloat16 and af.numel() == n_id * n_id)
+    assert wsum is None or (wsum.dtype == torch.float32 and wsum.is_contiguous() and wsum.numel() >= n_grp * Sq)
+    outs = (ptr(z),) if mx is None else (ptr(mx[0]), ptr(mx[1]))
+    tail = (ctypes.byref(d),) if mx is None else (ctypes.byref(d), mx[2], *mx[3])
+    return mx, ("bya_attn_kv_mix" if mx is None else "bya_attn_kv_mix_mx",
+                (*outs, ptr(af), *tail) if plan else (*(ptr(t) for t in qkvr), ptr(af), *outs, ptr(wsum), *tail))
+
+
 def attn_kv_mix(q, k, v, r, af, z, wsum=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides,
                 z_strides=None, scale, mx_out=None):
     """z[g, n] = sum_id w[g n, id] * softmax(q[g, n] . K[id, g]^T * scale) V[id, g]: cross-attention onto <= 64 keys per identity
-    with the router's masked combine in its epilogue (bya_attn_kv_mix).  q_strides = (group, row), k / v_strides = (identity,
-    group, row), z_strides = (group, row), in elements; r: bf16 [n_grp * Sq, n_id]; af: None (face) or bf16 [n_id, n_id].
+    with the router's masked combine in its epilogue.  q_strides = (group, row), k / v_strides = (identity, group, row),
+    z_strides = (group, row), in elements; r: bf16 [n_grp * Sq, n_id]; af: None (face) or bf16 [n_id, n_id].
     ``mx_out`` = (codes, scales, fmt) with ``z`` None and no ``z_strides``: the mix leaves as MX codes and block scales
-    (bya_attn_kv_mix_mx; layout: ``_mix_mx_out``) -- byte for byte ``quantize_mx(z, fmt)``, z itself never written; returns the
-    pair, the ``quantised=`` operand of the next MX Linear, or False (nothing launched, nothing counted) where the library
-    declines (more than 32 keys, the generic reference form): the caller then issues the two launches."""
-    lib = _hip.load()
-    mx = None
-    if mx_out is not None:
-        mx = _mix_mx_out(mx_out, z, z_strides, heads, head_dim, n_grp, Sq)
-        z_strides = (0, 0)
-    d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale)
-    for t in (q, k, v, r) + (() if mx is not None else (z,)):
-        assert t.dtype == torch.bfloat16 and t.is_cuda
-    assert r.is_contiguous() and r.numel() == n_grp * Sq * n_id
-    assert af is None or (af.is_contiguous() and af.dtype == torch.bfloat16 and af.numel() == n_id * n_id)
-    assert wsum is None or (wsum.dtype == torch.float32 and wsum.is_contiguous() and wsum.numel() >= n_grp * Sq)
-    flops = 4.0 * n_id * n_grp * heads * Sq * Skv * head_dim
-    if mx is not None:
-        call = ("bya_attn_kv_mix_mx", (_p(q), _p(k), _p(v), _p(r), _p(af), _p(mx[0]), _p(mx[1]), _p(wsum), ctypes.byref(d), mx[2], *mx[3]))
-        return _launch("bya_attn_kv_mix_mx", None, flops, call, True) and (mx[0], mx[1])
-    tok = _begin("bya_attn_kv_mix", flops)
-    check(lib.bya_attn_kv_mix(_p(q), _p(k), _p(v), _p(r), _p(af), _p(z), _p(wsum), ctypes.byref(d), _stream()), "bya_attn_kv_mix")
-    _end(tok)
-    return z
+    (layout: ``_mix_mx_out``) -- byte for byte ``quantize_mx(z, fmt)``, z itself never written; returns the pair, the
+    ``quantised=`` operand of the next MX Linear, or False (nothing launched, nothing counted) where the library declines (more
+    than 32 keys, the generic reference form): the caller then issues the two launches."""
+    mx, call = _mix_call((q, k, v, r), af, z, wsum, mx_out, False, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides,
+                         z_strides, scale)
+    launched = _launch(None, None, 4.0 * n_id * n_grp * heads * Sq * Skv * head_dim, call, mx is not None)
+    return z if mx is None else launched and (mx[0], mx[1])
+
+
+def attn_kv_mix_plan(z, af=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides=None,
+                     scale=1.0, mx_out=None):
+    """What ``attn_kv_mix`` would run (host-side; meta tensors may stand for device tensors): {"form" (``KV_MIX_FORMS``),
+    "head_dim", "grid", "row_chunks", "lds_bytes", "big_lds"}.  ``mx_out`` (with ``z`` None): the plan of the MX-output launch
+    (the dict then also has "mx_out": the format); None where the library declines it (more than 32 keys, or the generic
+    reference form)."""
+    mx, call = _mix_call((), af, z, None, mx_out, True, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides,
+                         z_strides, scale)
+    plan = _plan(call, mx is not None, _hip.AttnMixPlan, lambda p: {
+        "form": KV_MIX_FORMS[p.form], "head_dim": p.head_dim, "grid": p.grid, "row_chunks": p.row_chunks, "lds_bytes": p.lds_bytes,
+        "big_lds": p.big_lds})
+    if plan is not None and mx is not None:
+        plan["mx_out"] = mx_out[2]
+    return plan
+
+
+def _tiny_call(q, k, v, out, L, heads, n_outer, n_inner, strides, ld_qkv, ld_o, scale, plan):
+    ptr = _plan_p if plan else _p
+    args = (ptr(q), ptr(k), ptr(v), ptr(out), L, heads, n_outer, n_inner)
+    return "bya_attn_tiny", (*args, ld_qkv, ld_o) if plan else (*args, *strides, ld_qkv, ld_o, float(scale))
 
 
 def attn_tiny(q, k, v, out, L, heads, n_outer, n_inner, outer_stride, seq_stride, ld_qkv, ld_o, scale):
-    lib = _hip.load()
-    tok = _begin("bya_attn_tiny")
-    check(lib.bya_attn_tiny(_p(q), _p(k), _p(v), _p(out), L, heads, n_outer, n_inner, outer_stride, seq_stride,
-                            ld_qkv, ld_o, float(scale), _stream()), "bya_attn_tiny")
-    _end(tok)
+    _launch(None, None, 0.0, _tiny_call(q, k, v, out, L, heads, n_outer, n_inner, (outer_stride, seq_stride), ld_qkv, ld_o, scale, False))
     return out
 
 
-def router_scores(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, eps=1e-5):
-    lib = _hip.load()
+def attn_tiny_plan(q, k, v, out, L, heads, n_outer, n_inner, ld_qkv, ld_o):
+    """Which of the eight ``attn_tiny`` kernel instances would run: {"instance" (``TINY_INSTANCES``), "grid", "waves"}."""
+    return _plan(_tiny_call(q, k, v, out, L, heads, n_outer, n_inner, (), ld_qkv, ld_o, 0.0, True), False, _hip.AttnTinyPlan,
+                 lambda p: {"instance": TINY_INSTANCES[p.instance], "grid": p.grid, "waves": p.waves})
+
+
+# ---- the embedding router's scores, head and combines; patches; the activation; the scheduler step
+def _scores_call(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, eps, plan):
+    ptr = _plan_p if plan else _p
     for t in (qr, kr, ln_w, ln_b, pos_emb, out):
         assert t.is_contiguous() and t.dtype == torch.bfloat16
-    tok = _begin("bya_router_scores", 2.0 * n_id * N * 32 * qr.shape[-1])
-    check(lib.bya_router_scores(_p(qr), _p(kr), _p(ln_w), _p(ln_b), _p(pos_emb), _p(out), n_id, N, 16, 32,
-                                float(eps), _stream()), "bya_router_scores")
-    _end(tok)
+    args = (ptr(qr), ptr(kr), ptr(ln_w), ptr(ln_b), ptr(pos_emb), ptr(out), n_id, N, 16, 32)
+    return "bya_router_scores", args if plan else (*args, float(eps))
+
+
+def router_scores(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, eps=1e-5):
+    _launch(None, None, 2.0 * n_id * N * 32 * qr.shape[-1], _scores_call(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, eps, False))
     return out
 
 
 def router_scores_plan(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N):
     """What ``router_scores`` would launch (meta tensors will do): {"kernel": "wave" / "lds", "grid", "rounds", "items" (16-token
     tiles per identity), "items_per_round" (tiles of one identity per round of the waves' walk)}."""
-    lib = _hip.load()
-    p, a = _hip.StepPlan(), _plan_p
-    check(lib.bya_router_scores_plan(a(qr), a(kr), a(ln_w), a(ln_b), a(pos_emb), a(out), n_id, N, 16, 32, ctypes.byref(p)),
-          "bya_router_scores_plan")
-    return _step_plan(p, _hip.ROUTER_SCORES_KERNELS[p.kernel])
+    return _plan(_scores_call(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, 0.0, True), False, _hip.StepPlan,
+                 lambda p: _step_plan(p, _hip.ROUTER_SCORES_KERNELS[p.kernel]))
 
 
 def router_head(x, w, b, r, n_id, N):
-    lib = _hip.load()
     assert x.is_contiguous() and r.is_contiguous()
-    tok = _begin("bya_router_head")
-    check(lib.bya_router_head(_p(x), _p(w), _p(b), _p(r), n_id, N, x.shape[-1], _stream()), "bya_router_head")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_router_head", (_p(x), _p(w), _p(b), _p(r), n_id, N, x.shape[-1])))
     return r
 
 
 def forcing_max_over_frames(forcing, out, frames, per_frame, n_id):
-    lib = _hip.load()
     assert forcing.is_contiguous() and out.is_contiguous() and forcing.dtype == out.dtype == torch.bfloat16
-    tok = _begin("bya_forcing_max_over_frames")
-    check(lib.bya_forcing_max_over_frames(_p(forcing), _p(out), frames, per_frame, n_id, _stream()),
-          "bya_forcing_max_over_frames")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_forcing_max_over_frames", (_p(forcing), _p(out), frames, per_frame, n_id)))
     return out
+
+
+ROUTE_MODES = {"face": 0, "audio": 1}            # how routing logits become the identities' weights (include/bya.h)
 
 
 def masked_combine(x, feat, r, af, mode, alpha=1.0):
     """x [B, N, D] view (in place) += combine(feat [B, n_id, N, D], r [B or 1, N, n_id])."""
-    lib = _hip.load()
     b, N, D, x_bs, x_row = _mat(x, "x")
     assert feat.is_contiguous() and feat.shape[0] == b and feat.shape[2] == N and feat.shape[3] == D
     n_id = feat.shape[1]
@@ -1355,65 +1328,52 @@ def masked_combine(x, feat, r, af, mode, alpha=1.0):
     r_bs = 0 if r.shape[0] == 1 else N * n_id
     if af is not None:
         assert af.is_contiguous() and af.dtype == torch.bfloat16 and af.shape == (b, n_id, n_id)
-    tok = _begin("bya_masked_combine")
-    check(lib.bya_masked_combine(_p(x), _p(feat), _p(r), _p(af), {"face": 0, "audio": 1}[mode], float(alpha), b,
-                                 n_id, N, D, x_row, x_bs, r_bs, _stream()), "bya_masked_combine")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_masked_combine", (_p(x), _p(feat), _p(r), _p(af), ROUTE_MODES[mode], float(alpha), b, n_id, N, D, x_row,
+                                                     x_bs, r_bs)))
     return x
 
 
 def routed_mix(feat, r, af, mode, z, wsum=None):
     """z [B, N, D] = sum_id w[b,n,id] * feat [B, n_id, N, D]; wsum [B, N] fp32 = sum_id w (optional)."""
-    lib = _hip.load()
     b, n_id, N, D = feat.shape
     assert feat.is_contiguous() and z.is_contiguous() and z.shape == (b, N, D)
     assert r.is_contiguous() and r.shape[-2:] == (N, n_id) and r.dtype == torch.bfloat16
     r_bs = 0 if r.shape[0] == 1 else N * n_id
     if wsum is not None:
         assert wsum.dtype == torch.float32 and wsum.is_contiguous() and wsum.numel() == b * N
-    tok = _begin("bya_routed_mix")
-    check(lib.bya_routed_mix(_p(feat), _p(r), _p(af), _p(z), _p(wsum), {"face": 0, "audio": 1}[mode], b, n_id, N, D,
-                             r_bs, _stream()), "bya_routed_mix")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_routed_mix", (_p(feat), _p(r), _p(af), _p(z), _p(wsum), ROUTE_MODES[mode], b, n_id, N, D, r_bs)))
     return z
 
 
 def patchify(x, cols):
-    lib = _hip.load()
     b, t, c, h, w = x.shape
     assert x.is_contiguous() and cols.is_contiguous() and x.dtype == cols.dtype == torch.bfloat16
-    tok = _begin("bya_patchify")
-    check(lib.bya_patchify(_p(x), _p(cols), b, t, c, h, w, _stream()), "bya_patchify")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_patchify", (_p(x), _p(cols), b, t, c, h, w)))
     return cols
 
 
 def unpatchify(y, out):
-    lib = _hip.load()
     b, t, c, h, w = out.shape
     assert y.is_contiguous() and out.is_contiguous() and y.dtype == out.dtype == torch.bfloat16
-    tok = _begin("bya_unpatchify")
-    check(lib.bya_unpatchify(_p(y), _p(out), b, t, c, h, w, _stream()), "bya_unpatchify")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_unpatchify", (_p(y), _p(out), b, t, c, h, w)))
     return out
 
 
-def act_add(x, out, act=None, res=None):
-    lib = _hip.load()
+def _act_call(x, out, act, res, plan):
+    ptr = _plan_p if plan else _p
     assert x.is_contiguous() and out.is_contiguous() and (res is None or res.is_contiguous())
-    tok = _begin("bya_act_add")
-    check(lib.bya_act_add(_p(x), _p(res), _p(out), x.numel(), ACT[act], _stream()), "bya_act_add")
-    _end(tok)
+    return "bya_act_add", (ptr(x), ptr(res), ptr(out), x.numel(), ACT[act])
+
+
+def act_add(x, out, act=None, res=None):
+    _launch(None, None, 0.0, _act_call(x, out, act, res, False))
     return out
 
 
 def act_add_plan(x, out, act=None, res=None):
     """What ``act_add`` would launch (meta tensors will do): {"grid", "rounds" of the grid-stride loop, "items" (16-byte pieces),
     "items_per_round"}."""
-    lib = _hip.load()
-    p, a = _hip.StepPlan(), _plan_p
-    check(lib.bya_act_add_plan(a(x), a(res), a(out), x.numel(), ACT[act], ctypes.byref(p)), "bya_act_add_plan")
-    return _step_plan(p, "act_add")
+    return _plan(_act_call(x, out, act, res, True), False, _hip.StepPlan, lambda p: _step_plan(p, "act_add"))
 
 
 def _sched_pred(pred, n):
@@ -1427,17 +1387,27 @@ def _sched_pred(pred, n):
     return 2, pred.stride(0)
 
 
+def _sched_call(pred, sample, coef, old_x0, noise, x0_out, out, plan):
+    """-> (the output: ``out``, or where there is none a launch's new tensor / a query's ``sample``, the call)."""
+    ptr = _plan_p if plan else _p
+    n = sample.numel()
+    n_pred, pred_stride = _sched_pred(pred, n)
+    assert sample.dtype == torch.bfloat16 and sample.is_contiguous()
+    for t, dt in ((old_x0, torch.float32), (noise, torch.bfloat16), (x0_out, torch.float32)):
+        assert t is None or (t.dtype == dt and t.is_contiguous() and t.numel() == n)
+    if out is None:
+        out = sample if plan else torch.empty_like(sample)
+    c = _hip.SchedCoef(**{k: float(v) for k, v in coef.items()})
+    head = (ptr(pred), n_pred, pred_stride, ptr(sample))
+    return out, ("bya_cfg_scheduler_step", (*head, ptr(out), n, ctypes.byref(c)) if plan else
+                 (*head, ptr(old_x0), ptr(noise), ptr(out), ptr(x0_out), n, ctypes.byref(c)))
+
+
 def cfg_scheduler_step_plan(pred, sample, coef, out=None):
     """What ``cfg_scheduler_step`` would launch (meta tensors will do): {"grid", "rounds" of the grid-stride loop, "items"
     (elements), "items_per_round"}."""
-    lib = _hip.load()
-    p, a = _hip.StepPlan(), _plan_p
-    n = sample.numel()
-    n_pred, stride = _sched_pred(pred, n)
-    c = _hip.SchedCoef(**{k: float(v) for k, v in coef.items()})
-    check(lib.bya_cfg_scheduler_step_plan(a(pred), n_pred, stride, a(sample), a(sample if out is None else out), n, ctypes.byref(c),
-                                          ctypes.byref(p)), "bya_cfg_scheduler_step_plan")
-    return _step_plan(p, "cfg_scheduler_step")
+    return _plan(_sched_call(pred, sample, coef, None, None, None, out, True)[1], False, _hip.StepPlan,
+                 lambda p: _step_plan(p, "cfg_scheduler_step"))
 
 
 def cfg_scheduler_step(pred, sample, coef, old_x0=None, noise=None, x0_out=None, out=None):
@@ -1445,38 +1415,25 @@ def cfg_scheduler_step(pred, sample, coef, old_x0=None, noise=None, x0_out=None,
     pred: bf16 [1 or 2, ...] model output ([uncond, cond] when 2; the two may be rows of a wider buffer); sample: bf16
     latents [1, ...] (or any shape with the element count of one prediction); coef: dict with the fields of ``bya_sched_coef``; old_x0 / x0_out: fp32;
     noise: bf16.  Returns the new bf16 latents."""
-    import ctypes
-    lib = _hip.load()
-    n = sample.numel()
-    n_pred, pred_stride = _sched_pred(pred, n)
-    assert sample.dtype == torch.bfloat16 and sample.is_contiguous()
-    for t, dt in ((old_x0, torch.float32), (noise, torch.bfloat16), (x0_out, torch.float32)):
-        assert t is None or (t.dtype == dt and t.is_contiguous() and t.numel() == n)
-    if out is None:
-        out = torch.empty_like(sample)
-    c = _hip.SchedCoef(**{k: float(v) for k, v in coef.items()})
-    tok = _begin("bya_cfg_scheduler_step")
-    check(lib.bya_cfg_scheduler_step(_p(pred), n_pred, pred_stride, _p(sample), _p(old_x0), _p(noise), _p(out), _p(x0_out), n,
-                                     ctypes.byref(c), _stream()), "bya_cfg_scheduler_step")
-    _end(tok)
+    out, call = _sched_call(pred, sample, coef, old_x0, noise, x0_out, out, False)
+    _launch(None, None, 0.0, call)
     return out
 
 
 def masks_to_routing_logits(masks, frames=13, h=30, w=45, out=None):
     """Tracking masks uint8 [n_id, T, H, W] (> 0 = foreground) -> ``routing_logits_forcing`` bf16 [1, frames*h*w, n_id]
     (reference util/utils.py:871-936; feed it to ``forward(routing_logits_forcing=...)``)."""
-    lib = _hip.load()
     assert masks.dtype == torch.uint8 and masks.is_contiguous() and masks.dim() == 4
     n_id, Ti, Hi, Wi = masks.shape
     if out is None:
         out = torch.empty(1, frames * h * w, n_id, dtype=torch.bfloat16, device=masks.device)
-    tok = _begin("bya_masks_to_routing_logits")
-    check(lib.bya_masks_to_routing_logits(_p(masks), _p(out), n_id, Ti, Hi, Wi, frames, h, w, _stream()),
-          "bya_masks_to_routing_logits")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_masks_to_routing_logits", (_p(masks), _p(out), n_id, Ti, Hi, Wi, frames, h, w)))
     return out
 
 
+# ---- the router's row kernels (K = 512).  A launch reads its rows off the tensors and its weights off a pack; a query may
+# name them loosely: a plain row count for ``x`` (contiguous rows, aligned pointers), True for "some aligned" residual, output or
+# pack (_SOME_PACK).  Both read row counts and strides in _rows_of / _like_rows.
 def pack_rowgemm512(weight, bias, ln_weight=None, ln_bias=None):
     """Pack a [N, 512] Linear (optionally preceded by LayerNorm(512)) for ``rowgemm512``: gamma folded into the bf16
     weight, its fp32 row sums, and the fp32 constant vector  W . beta + bias  (see include/bya.h)."""
@@ -1488,171 +1445,156 @@ def pack_rowgemm512(weight, bias, ln_weight=None, ln_bias=None):
     return dict(w=wg, colsum=wg.float().sum(1).contiguous(), cvec=(w32 @ ln_bias.float() + b32).contiguous(), ln=True)
 
 
+_SOME_PACK = dict(w=True, colsum=True, cvec=True, ln=True)
+
+
+def _rows_of(x, ptr, width=512):
+    """-> (M, row stride, address) of the [M, width] rows ``x`` (a tensor) or of M contiguous rows (an int: queries)."""
+    if isinstance(x, int):
+        return x, width, ptr(True)
+    (M, K), (ld, inner) = x.shape, x.stride()        # (2-D: anything else does not unpack)
+    assert K == width and inner == 1
+    return M, ld, ptr(x)
+
+
+def _like_rows(t, M, width, ptr):
+    if t is None or t is True:
+        return width, ptr(True)
+    assert tuple(t.shape) == (M, width)
+    ld, inner = t.stride()
+    assert inner == 1
+    return ld, ptr(t)
+
+
+def _rowgemm_call(x, N, pack, out, res, act, eps, nsplit, plan):
+    ptr = _plan_p if plan else _p
+    M, ldx, px = _rows_of(x, ptr)
+    ldc, pc = _like_rows(out, M, N, ptr)
+    ldres, pr = _like_rows(res, M, N, ptr) if res is not None else (0, None)
+    args = (px, ptr(pack["w"]), ptr(pack["colsum"]), ptr(pack["cvec"]), pr, pc, M, N, ldx, ldc, ldres, int(pack["ln"]))
+    return M, ("bya_rowgemm512", (*args, ACT[act]) if plan else (*args, float(eps), ACT[act], int(nsplit)))
+
+
 def rowgemm512(x, pack, out, res=None, act=None, eps=1e-5, nsplit=0):
     """out = res + act( LN?(x) @ W.T + b ) for K = 512 (router projections, reference models/router.py:468-493)."""
-    lib = _hip.load()
-    M, K = x.shape
     N = pack["w"].shape[0]
-    assert K == 512 and x.stride(1) == 1 and out.stride(1) == 1 and out.shape == (M, N)
-    assert res is None or (res.shape == out.shape and res.stride(1) == 1)
-    tok = _begin("bya_rowgemm512", 2.0 * M * N * K)
-    check(lib.bya_rowgemm512(_p(x), _p(pack["w"]), _p(pack["colsum"]), _p(pack["cvec"]), _p(res), _p(out), M, N,
-                             x.stride(0), out.stride(0), res.stride(0) if res is not None else 0, int(pack["ln"]),
-                             float(eps), ACT[act], int(nsplit), _stream()), "bya_rowgemm512")
-    _end(tok)
+    M, call = _rowgemm_call(x, N, pack, out, res, act, eps, nsplit, False)
+    _launch(None, None, 2.0 * M * N * 512, call)
     return out
-
-
-def router_group_attn(x, pack, out, L, n_outer, n_inner, outer_stride, seq_stride, eps=1e-5, scale=0.125):
-    """out = softmax(q k^T * scale) v per group of L rows, (q | k | v) = LN(x) @ Wqkv.T + b, 8 heads x 64: the temporal /
-    multi-ID attention of SpatialTemporalAttentionBlock up to its out-projection in ONE launch (reference
-    models/router.py:476-478, :482-484; include/bya.h bya_router_group_attn).  ``pack`` = ``pack_rowgemm512`` of the
-    concatenated to_q | to_k | to_v with the LayerNorm folded in; groups as for ``attn_tiny``."""
-    lib = _hip.load()
-    M, K = x.shape
-    assert K == 512 and pack["ln"] and pack["w"].shape == (1536, 512) and out.shape == (M, 512)
-    assert x.stride(1) == 1 and out.stride(1) == 1 and x.data_ptr() != out.data_ptr()
-    tok = _begin("bya_router_group_attn", 2.0 * M * 1536 * K + 4.0 * M * L * 512)
-    check(lib.bya_router_group_attn(_p(x), _p(pack["w"]), _p(pack["colsum"]), _p(pack["cvec"]), _p(out), M, x.stride(0),
-                                    out.stride(0), int(L), int(n_outer), int(n_inner), int(outer_stride), int(seq_stride),
-                                    float(eps), float(scale), _stream()), "bya_router_group_attn")
-    _end(tok)
-    return out
-
-
-def router_mlp_fused(x, pack1, pack2, eps=1e-5, out=None, tiles_pass0=0):
-    """x += mlp[2](GELU(mlp[0](LayerNorm(x)))) on router rows in ONE launch, the hidden activation in registers (reference
-    models/router.py:491; include/bya.h bya_router_mlp_fused).  ``pack1`` = ``pack_rowgemm512`` of mlp[0] with norm4 folded
-    in, ``pack2`` of mlp[2].  Bit-identical to ``rowgemm512(x, pack1, h, act="gelu_erf"); rowgemm512(h, pack2, x, res=x)``."""
-    lib = _hip.load()
-    M, K = x.shape
-    out = x if out is None else out
-    assert K == 512 and pack1["ln"] and not pack2["ln"] and pack1["w"].shape == (512, 512) and pack2["w"].shape == (512, 512)
-    assert x.stride(1) == 1 and out.stride(1) == 1 and out.shape == x.shape
-    tok = _begin("bya_router_mlp_fused", 4.0 * M * 512 * K)
-    check(lib.bya_router_mlp_fused(_p(x), _p(pack1["w"]), _p(pack1["colsum"]), _p(pack1["cvec"]), _p(pack2["w"]),
-                                   _p(pack2["cvec"]), _p(out), M, x.stride(0), out.stride(0), float(eps), int(tiles_pass0),
-                                   _stream()), "bya_router_mlp_fused")
-    _end(tok)
-    return out
-
-
-def router_group_attn_out(x, pack, pack_out, L, n_outer, n_inner, outer_stride, seq_stride, eps=1e-5, scale=0.125, out=None,
-                          tiles_pass0=0):
-    """x += to_out(attention over groups of L rows of LayerNorm(x)) in ONE launch (reference models/router.py:482-483,
-    :486-487; include/bya.h bya_router_group_attn_out): ``router_group_attn`` followed by the out-projection + residual, the
-    attention output in registers.  L <= 16.  Bit-identical to the two launches."""
-    lib = _hip.load()
-    M, K = x.shape
-    out = x if out is None else out
-    assert K == 512 and pack["ln"] and pack["w"].shape == (1536, 512) and not pack_out["ln"] and pack_out["w"].shape == (512, 512)
-    assert x.stride(1) == 1 and out.stride(1) == 1 and out.shape == x.shape
-    tok = _begin("bya_router_group_attn_out", 2.0 * M * 2048 * K + 4.0 * M * L * 512)
-    check(lib.bya_router_group_attn_out(_p(x), _p(pack["w"]), _p(pack["colsum"]), _p(pack["cvec"]), _p(pack_out["w"]),
-                                        _p(pack_out["cvec"]), _p(out), M, x.stride(0), out.stride(0), int(L), int(n_outer),
-                                        int(n_inner), int(outer_stride), int(seq_stride), float(eps), float(scale),
-                                        int(tiles_pass0), _stream()), "bya_router_group_attn_out")
-    _end(tok)
-    return out
-
-
-# ---- what the router's row kernels run (bya_rowgemm512_plan & co.: host-side, launch nothing).  ``x`` / ``out`` / ``res`` may
-# be device tensors, meta tensors, or -- with a plain row count for ``x`` -- left out (contiguous rows, aligned pointers).
-def _rows_of(x, width=512):
-    """-> (M, row stride, address) of the [M, width] rows ``x`` (a tensor) or of M contiguous rows (an int)."""
-    if isinstance(x, int):
-        return x, width, _META_BASE
-    assert x.dim() == 2 and x.shape[1] == width and x.stride(1) == 1
-    return x.shape[0], x.stride(0), _plan_p(x)
-
-
-def _like_rows(t, M, width):
-    if t is None or t is True:
-        return width, _META_BASE
-    assert tuple(t.shape) == (M, width) and t.stride(1) == 1
-    return t.stride(0), _plan_p(t)
 
 
 def rowgemm512_plan(x, N, out=None, ln=False, res=None, act=None):
     """What ``rowgemm512`` would run: {"form" (``_hip.ROWGEMM_FORMS``), "ln", "res", "gelu" (the kernel's template instance),
     "grid", "work_items", "crosses_row_block"}.  ``res``: None, True (some aligned residual) or the tensor."""
-    lib = _hip.load()
-    M, ldx, px = _rows_of(x)
-    ldc, pc = _like_rows(out, M, N)
-    ldres, pr = _like_rows(res, M, N) if res is not None else (0, None)
-    p = _hip.RowGemmPlan()
-    check(lib.bya_rowgemm512_plan(px, _META_BASE, _META_BASE if ln else None, _META_BASE, pr, pc, M, N, ldx, ldc, ldres, int(ln),
-                                  ACT[act], ctypes.byref(p)), "bya_rowgemm512_plan")
-    return {"form": _hip.ROWGEMM_FORMS[p.form], "ln": bool(p.ln), "res": bool(p.res), "gelu": p.act == ACT["gelu_erf"],
-            "grid": p.grid, "work_items": p.work_items, "crosses_row_block": bool(p.crosses_row_block)}
+    pack = dict(w=True, colsum=True if ln else None, cvec=True, ln=ln)
+    return _plan(_rowgemm_call(x, N, pack, out, res, act, 0.0, 0, True)[1], False, _hip.RowGemmPlan, lambda p: {
+        "form": _hip.ROWGEMM_FORMS[p.form], "ln": bool(p.ln), "res": bool(p.res), "gelu": p.act == ACT["gelu_erf"], "grid": p.grid,
+        "work_items": p.work_items, "crosses_row_block": bool(p.crosses_row_block)})
+
+
+def _rowk_call(entry, x, packs, out, geometry, floats, tail, plan):
+    """The call of one of the three fused row kernels: ``packs`` = (the pack with the LayerNorm folded in, the out-projection's
+    or second Linear's pack or None); ``out`` None = in place; ``geometry`` = the groups (L, n_outer, n_inner, outer_stride,
+    seq_stride) or (); ``floats`` = eps (, scale): a launch's alone; ``tail`` = (tiles_pass0,) or ().  -> (M, addresses of x and
+    out, the call)."""
+    ptr = _plan_p if plan else _p
+    M, ldx, px = _rows_of(x, ptr)
+    ldc, pc = _like_rows(out, M, 512, ptr) if out is not None else (ldx, px)
+    first, second = packs
+    weights = (ptr(first["w"]), ptr(first["colsum"]), ptr(first["cvec"])) + (() if second is None else (ptr(second["w"]), ptr(second["cvec"])))
+    args = (px, *weights, pc, M, ldx, ldc, *(int(g) for g in geometry))
+    return M, px, pc, (entry, (*args, *(int(t) for t in tail)) if plan else (*args, *(float(f) for f in floats), *(int(t) for t in tail)))
+
+
+def _group_attn_call(x, pack, out, groups, floats, plan):
+    return _rowk_call("bya_router_group_attn", x, (pack, None), out, groups, floats, (), plan)
+
+
+def _mlp_call(x, packs, out, floats, tiles_pass0, plan):
+    return _rowk_call("bya_router_mlp_fused", x, packs, out, (), floats, (tiles_pass0,), plan)
+
+
+def _attn_out_call(x, packs, out, groups, floats, tiles_pass0, plan):
+    return _rowk_call("bya_router_group_attn_out", x, packs, out, groups, floats, (tiles_pass0,), plan)
+
+
+def router_group_attn(x, pack, out, L, n_outer, n_inner, outer_stride, seq_stride, eps=1e-5, scale=0.125):
+    """out = softmax(q k^T * scale) v per group of L rows, (q | k | v) = LN(x) @ Wqkv.T + b, 8 heads x 64: the temporal /
+    multi-ID attention of SpatialTemporalAttentionBlock up to its out-projection in ONE launch (reference
+    models/router.py:476-478, :482-484; include/bya.h).  ``pack`` = ``pack_rowgemm512`` of the concatenated
+    to_q | to_k | to_v with the LayerNorm folded in; groups as for ``attn_tiny``."""
+    assert pack["ln"] and pack["w"].shape == (1536, 512)
+    M, px, po, call = _group_attn_call(x, pack, out, (L, n_outer, n_inner, outer_stride, seq_stride), (eps, scale), False)
+    assert px != po
+    _launch(None, None, 2.0 * M * 1536 * 512 + 4.0 * M * L * 512, call)
+    return out
+
+
+def router_group_attn_plan(x, L, n_outer, n_inner, outer_stride, seq_stride, out=None):
+    """What ``router_group_attn`` would run: {"P" (slots per group), "G" (groups per 16-row tile), "wide" (16 < L <= 32: the
+    two-tile kernel), "tiles", "blocks"}."""
+    call = _group_attn_call(x, _SOME_PACK, True if out is None else out, (L, n_outer, n_inner, outer_stride, seq_stride), (), True)[3]
+    return _plan(call, False, _hip.GroupAttnPlan, lambda p: {"P": p.P, "G": p.G, "wide": bool(p.wide), "tiles": p.tiles, "blocks": p.blocks})
 
 
 def _chain_dict(p):
     return {"tiles": p.tiles, "tp0": p.tp0, "grid": p.grid, "passes": p.passes, "tiles_last": p.tiles_last, "wgs_last": p.wgs_last}
 
 
+def router_mlp_fused(x, pack1, pack2, eps=1e-5, out=None, tiles_pass0=0):
+    """x += mlp[2](GELU(mlp[0](LayerNorm(x)))) on router rows in ONE launch, the hidden activation in registers (reference
+    models/router.py:491; include/bya.h).  ``pack1`` = ``pack_rowgemm512`` of mlp[0] with norm4 folded in, ``pack2`` of
+    mlp[2].  Bit-identical to ``rowgemm512(x, pack1, h, act="gelu_erf"); rowgemm512(h, pack2, x, res=x)``."""
+    assert pack1["ln"] and not pack2["ln"] and pack1["w"].shape == (512, 512) and pack2["w"].shape == (512, 512)
+    M, _, _, call = _mlp_call(x, (pack1, pack2), out, (eps,), tiles_pass0, False)
+    _launch(None, None, 4.0 * M * 512 * 512, call)
+    return x if out is None else out
+
+
 def router_mlp_fused_plan(x, out=None, tiles_pass0=0):
     """What ``router_mlp_fused`` would run: {"tiles", "tp0", "grid", "passes", "tiles_last" (tiles per workgroup in the last
     pass), "wgs_last" (workgroups that have a tile there)}."""
-    lib = _hip.load()
-    M, ldx, px = _rows_of(x)
-    ldc, pc = _like_rows(out, M, 512) if out is not None else (ldx, px)
-    p, b = _hip.RouterChainPlan(), _META_BASE
-    check(lib.bya_router_mlp_fused_plan(px, b, b, b, b, b, pc, M, ldx, ldc, int(tiles_pass0), ctypes.byref(p)),
-          "bya_router_mlp_fused_plan")
-    return _chain_dict(p)
+    return _plan(_mlp_call(x, (_SOME_PACK, _SOME_PACK), out, (), tiles_pass0, True)[3], False, _hip.RouterChainPlan, _chain_dict)
+
+
+def router_group_attn_out(x, pack, pack_out, L, n_outer, n_inner, outer_stride, seq_stride, eps=1e-5, scale=0.125, out=None,
+                          tiles_pass0=0):
+    """x += to_out(attention over groups of L rows of LayerNorm(x)) in ONE launch (reference models/router.py:482-483,
+    :486-487; include/bya.h): ``router_group_attn`` followed by the out-projection + residual, the attention output in
+    registers.  L <= 16.  Bit-identical to the two launches."""
+    assert pack["ln"] and pack["w"].shape == (1536, 512) and not pack_out["ln"] and pack_out["w"].shape == (512, 512)
+    M, _, _, call = _attn_out_call(x, (pack, pack_out), out, (L, n_outer, n_inner, outer_stride, seq_stride), (eps, scale), tiles_pass0,
+                                   False)
+    _launch(None, None, 2.0 * M * 2048 * 512 + 4.0 * M * L * 512, call)
+    return x if out is None else out
 
 
 def router_group_attn_out_plan(x, L, n_outer, n_inner, outer_stride, seq_stride, out=None, tiles_pass0=0):
     """What ``router_group_attn_out`` would run (``router_mlp_fused_plan``'s dict; its tiles hold 16 / P whole groups)."""
-    lib = _hip.load()
-    M, ldx, px = _rows_of(x)
-    ldc, pc = _like_rows(out, M, 512) if out is not None else (ldx, px)
-    p, b = _hip.RouterChainPlan(), _META_BASE
-    check(lib.bya_router_group_attn_out_plan(px, b, b, b, b, b, pc, M, ldx, ldc, int(L), int(n_outer), int(n_inner),
-                                             int(outer_stride), int(seq_stride), int(tiles_pass0), ctypes.byref(p)),
-          "bya_router_group_attn_out_plan")
-    return _chain_dict(p)
-
-
-def router_group_attn_plan(x, L, n_outer, n_inner, outer_stride, seq_stride, out=None):
-    """What ``router_group_attn`` would run: {"P" (slots per group), "G" (groups per 16-row tile), "wide" (16 < L <= 32: the
-    two-tile kernel), "tiles", "blocks"}."""
-    lib = _hip.load()
-    M, ldx, px = _rows_of(x)
-    ldo, po = _like_rows(out, M, 512)
-    p, b = _hip.GroupAttnPlan(), _META_BASE
-    check(lib.bya_router_group_attn_plan(px, b, b, b, po, M, ldx, ldo, int(L), int(n_outer), int(n_inner), int(outer_stride),
-                                         int(seq_stride), ctypes.byref(p)), "bya_router_group_attn_plan")
-    return {"P": p.P, "G": p.G, "wide": bool(p.wide), "tiles": p.tiles, "blocks": p.blocks}
+    call = _attn_out_call(x, (_SOME_PACK, _SOME_PACK), out, (L, n_outer, n_inner, outer_stride, seq_stride), (), tiles_pass0, True)[3]
+    return _plan(call, False, _hip.RouterChainPlan, _chain_dict)
 
 
 # ---- video VAE (SURVEY.md section 8f row 4; csrc/vae.hip) ----------------------------------------------------------
 def vae_patches(x, cache, out, KT, stride, pad, up, tmode, Ho, Wo, t0, nt):
     """Patch matrix of a causal KT x 3 x 3 convolution over channels-last x [Ts, Hs, Ws, C] -> out [nt * Ho * Wo, Kpad]."""
-    lib = _hip.load()
     Ts, Hs, Ws, C = x.shape
     assert x.is_contiguous() and out.is_contiguous() and x.dtype == out.dtype == torch.bfloat16
     assert cache is None or (cache.is_contiguous() and tuple(cache.shape) == (KT - 1, Hs, Ws, C))
     assert out.shape[0] == nt * Ho * Wo
-    tok = _begin("bya_vae_patches")
-    check(lib.bya_vae_patches(_p(x), _p(cache), _p(out), Ts, Hs, Ws, C, KT, stride, pad, int(up), tmode, Ho, Wo, t0, nt,
-                              out.shape[1], _stream()), "bya_vae_patches")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_vae_patches", (_p(x), _p(cache), _p(out), Ts, Hs, Ws, C, KT, stride, pad, int(up), tmode, Ho, Wo, t0, nt,
+                                                  out.shape[1])))
     return out
 
 
 def vae_groupnorm_stats(x2d, sums, groups, partial=None):
-    lib = _hip.load()
     rows, C = x2d.shape
     assert x2d.is_contiguous() and sums.dtype == torch.float32 and sums.numel() == 2 * groups
     need = (rows + 511) // 512 * groups * 2
     if partial is None:
         partial = torch.empty(need, dtype=torch.float32, device=x2d.device)
     assert partial.dtype == torch.float32 and partial.numel() >= need and partial.is_contiguous()
-    tok = _begin("bya_vae_groupnorm_stats")
-    check(lib.bya_vae_groupnorm_stats(_p(x2d), _p(sums), _p(partial), rows, C, groups, _stream()), "bya_vae_groupnorm_stats")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_vae_groupnorm_stats", (_p(x2d), _p(sums), _p(partial), rows, C, groups)))
     return sums
 
 
@@ -1660,24 +1602,20 @@ def vae_norm_act(x, y, sums, gamma, beta, groups, act="silu", eps=1e-6, zy=None,
                  out_pad=False):
     """x: [T, H, W, C] channels-last; y: the same, or (out_pad) the zero-padded conv input [T + 2, H + 2, W + 2, C] whose
     interior frames 2.. are written; zy / zb: [Tz * hz * wz, C] views (row stride = their .stride(0))."""
-    lib = _hip.load()
     T, H, W, C = x.shape
     assert x.is_contiguous() and y.is_contiguous()
     assert tuple(y.shape) == ((T + 2, H + 2, W + 2, C) if out_pad else (T, H, W, C))
     Tz, hz, wz = latent_shape if latent_shape is not None else (T, H, W)
     ldz = zy.stride(0) if zy is not None else 0
-    tok = _begin("bya_vae_norm_act")
-    check(lib.bya_vae_norm_act(_p(x), _p(y), _p(sums), _p(gamma), _p(beta), _p(zy), _p(zb), T * H * W, C, groups,
-                               {None: 0, "none": 0, "silu": 1}[act], float(eps), T, H, W, Tz, hz, wz, tmode, ldz,
-                               int(bool(out_pad)), _stream()), "bya_vae_norm_act")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_vae_norm_act", (_p(x), _p(y), _p(sums), _p(gamma), _p(beta), _p(zy), _p(zb), T * H * W, C, groups,
+                                                   {None: 0, "none": 0, "silu": 1}[act], float(eps), T, H, W, Tz, hz, wz, tmode, ldz,
+                                                   int(bool(out_pad)))))
     return y
 
 
 def vae_conv3d(xpad, w, bias, out, res=None, KT=3):
-    """Causal KT x 3 x 3 convolution as an implicit GEMM (bya_vae_conv3d): xpad [To + KT - 1, H + 2, W + 2, C] zero-padded (KT = 3:
-    its two context frames in front), w [Cout, >= 9 KT C] (tap-major columns), out / res [To, H, W, Cout] (out = res + bias + conv)."""
-    lib = _hip.load()
+    """Causal KT x 3 x 3 convolution as an implicit GEMM: xpad [To + KT - 1, H + 2, W + 2, C] zero-padded (KT = 3: its two
+    context frames in front), w [Cout, >= 9 KT C] (tap-major columns), out / res [To, H, W, Cout] (out = res + bias + conv)."""
     Tp, Hp, Wp, C = xpad.shape
     To, H, W, Cout = out.shape
     assert (Tp, Hp, Wp) == (To + KT - 1, H + 2, W + 2) and xpad.is_contiguous() and w.is_contiguous() and w.shape[0] >= Cout
@@ -1688,20 +1626,16 @@ def vae_conv3d(xpad, w, bias, out, res=None, KT=3):
     if res is not None:
         ldres = res.stride(2)
         assert res.shape == out.shape and res.stride(1) == W * ldres and res.stride(0) == H * W * ldres and res.stride(3) == 1
-    tok = _begin("bya_vae_conv3d", 2.0 * To * H * W * Cout * 9 * KT * C)
-    check(lib.bya_vae_conv3d(_p(xpad), _p(w), _p(bias), _p(res), _p(out), To, H, W, C, Cout, KT, w.stride(0), ldc, ldres,
-                             _stream()), "bya_vae_conv3d")
-    _end(tok)
+    _launch(None, None, 2.0 * To * H * W * Cout * 9 * KT * C,
+            ("bya_vae_conv3d", (_p(xpad), _p(w), _p(bias), _p(res), _p(out), To, H, W, C, Cout, KT, w.stride(0), ldc, ldres)))
     return out
 
 
 def vae_upsample_pad(x, ypad, tmode):
     """Nearest up-sampling of x [T, H, W, C] into the interior of the zero-padded ypad [To, 2 H + 2, 2 W + 2, C]."""
-    lib = _hip.load()
     T, H, W, C = x.shape
     To = T if tmode == 0 else (2 * T if tmode == 1 else 2 * T - 1)
     assert x.is_contiguous() and ypad.is_contiguous() and tuple(ypad.shape) == (To, 2 * H + 2, 2 * W + 2, C)
-    tok = _begin("bya_vae_upsample_pad")
-    check(lib.bya_vae_upsample_pad(_p(x), _p(ypad), T, H, W, C, tmode, _stream()), "bya_vae_upsample_pad")
-    _end(tok)
+    _launch(None, None, 0.0, ("bya_vae_upsample_pad", (_p(x), _p(ypad), T, H, W, C, tmode)))
     return ypad
+
