@@ -61,7 +61,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) sum += v[i][e];
     }
-    const float mean = wave_sum(sum) * (1.0f / D);
+    // a true division: fl(1 / D) is no fp32 number for D = 768, 1536, 3072, and the product with it is an ulp off the mean of a row
+    // whose sum is exact -- a constant row of 50 then comes out as (50 - mean) rstd = 3e-6 / sqrt(eps) instead of 0
+    const float mean = wave_sum(sum) / (float)D;
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
@@ -223,7 +225,7 @@ __global__ __launch_bounds__(256) void layernorm_adaln_rows_kernel(LnArgs p, int
         for (int i = 0; i < NV; ++i)
 #pragma unroll
             for (int e = 0; e < VEC; ++e) sum += v[i][e];
-        const float mean = wave_sum(sum) * (1.0f / D);
+        const float mean = wave_sum(sum) / (float)D;             // (a division: see layernorm_kernel)
         float sq = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i)

@@ -119,58 +119,93 @@ __global__ __launch_bounds__(256) void vae_patches_small_kernel(PatchArgs p) {
 // two <= 64), accumulates them in registers in row order, then the block adds the threads of a channel in thread order and the
 // channels of a group in channel order -> partial[block][group][2].  Pass 2: one block per (group, moment) adds the partials in
 // a fixed order (strided per thread, then a shared-memory tree).
+// Every sum is carried in fp64 and rounded to fp32 once per partial and once per result: bya_vae_norm_act takes
+// var = sum x^2 / n - mean^2, and fp32 sums along this hierarchy (up to 150 additions deep) lost 150 u R^2 of the variance on a group
+// with R = |mean| / spread -- whole bf16 steps of the output at R = 64.  Rounded once, sum x^2 is off by u R^2 of the variance,
+// the best its fp32 slot can hold (bya_vae_groupnorm_moments keeps the fp64 sums to the end).
+// Cost, measured on an MI355X against the fp32 accumulators on tensors of 67 .. 144 MB (one conversion, one add and one fma in fp64
+// per element, 40 KB of LDS per block in place of 20): 20.3 against 19.4 us at C = 128 x 262 657 rows, 49.9 against 49.1 us at
+// C = 512 x 70 200, 35.0 against 33.0 us at C = 256 x 280 800 -- 2 to 6 % slower; bya_vae_groupnorm_moments adds 0.2 .. 0.4 us.
+// (A pivot with Chan's formula would keep fp32 sums, but cannot give this entry point's pair more than its slots hold either.)
 constexpr int GN_ROWS = 512;
 
-__global__ __launch_bounds__(256) void vae_gn_partial_kernel(const bf16_t* __restrict__ x, float* __restrict__ partial, long long rows,
+template <typename P>                                         // float: the partials of bya_vae_groupnorm_stats; double: ..._moments
+__global__ __launch_bounds__(256) void vae_gn_partial_kernel(const bf16_t* __restrict__ x, P* __restrict__ partial, long long rows,
                                                              int C, int groups) {
-    __shared__ float sh[2][256][8];
-    __shared__ float chs[2][512];
+    __shared__ double sh[2][256][8];
+    __shared__ double chs[2][512];
     const int cpr = C >> 3, tid = threadIdx.x;
     const int c8 = tid % cpr, rstep = 256 / cpr;
     const long long r0 = (long long)blockIdx.x * GN_ROWS;
-    float s[8], q[8];
+    double s[8], q[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
+    for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.0;
     for (int rr = tid / cpr; rr < GN_ROWS; rr += rstep) {
         const long long r = r0 + rr;
         if (r >= rows) break;
         float v[8];
         unpack8(*reinterpret_cast<const u32x4*>(x + r * C + c8 * 8), v);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { s[e] += v[e]; q[e] = fmaf(v[e], v[e], q[e]); }
+        for (int e = 0; e < 8; ++e) { const double d = (double)v[e]; s[e] += d; q[e] = fma(d, d, q[e]); }
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) { sh[0][tid][e] = s[e]; sh[1][tid][e] = q[e]; }
     __syncthreads();
     for (int ch = tid; ch < C; ch += 256) {                 // channel sums: the threads of a channel in thread order
         const int cc = ch >> 3, e = ch & 7;
-        float a = 0.f, b = 0.f;
+        double a = 0.0, b = 0.0;
         for (int t = cc; t < 256; t += cpr) { a += sh[0][t][e]; b += sh[1][t][e]; }
         chs[0][ch] = a; chs[1][ch] = b;
     }
     __syncthreads();
     const int cg = C / groups;
     for (int g = tid; g < groups; g += 256) {
-        float a = 0.f, b = 0.f;
+        double a = 0.0, b = 0.0;
         for (int c = g * cg; c < (g + 1) * cg; ++c) { a += chs[0][c]; b += chs[1][c]; }
-        partial[((long long)blockIdx.x * groups + g) * 2] = a;
-        partial[((long long)blockIdx.x * groups + g) * 2 + 1] = b;
+        partial[((long long)blockIdx.x * groups + g) * 2] = (P)a;
+        partial[((long long)blockIdx.x * groups + g) * 2 + 1] = (P)b;
     }
 }
 
 __global__ __launch_bounds__(256) void vae_gn_final_kernel(const float* __restrict__ partial, float* __restrict__ sums, int nblocks,
                                                            int groups) {
-    __shared__ float red[256];
+    __shared__ double red[256];
     const int gm = blockIdx.x, tid = threadIdx.x;            // gm = group * 2 + moment
-    float a = 0.f;
-    for (int b = tid; b < nblocks; b += 256) a += partial[(long long)b * groups * 2 + gm];
+    double a = 0.0;
+    for (int b = tid; b < nblocks; b += 256) a += (double)partial[(long long)b * groups * 2 + gm];
     red[tid] = a;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if (tid < o) red[tid] += red[tid + o];
         __syncthreads();
     }
-    if (tid == 0) sums[gm] = red[0];
+    if (tid == 0) sums[gm] = (float)red[0];
+}
+
+// bya_vae_groupnorm_moments' second pass: one block per group adds the fp64 partials of both moments in a fixed order and forms
+// mean = sum x / n and var = max(sum x^2 / n - mean^2, 0) in fp64, where the cancellation costs 2^-53 R^2 of the variance and not
+// 2^-24 R^2; only then are the two rounded to fp32.
+__global__ __launch_bounds__(256) void vae_gn_moments_kernel(const double* __restrict__ partial, float* __restrict__ moments, int nblocks,
+                                                             int groups, double count) {
+    __shared__ double red[2][256];
+    const int g = blockIdx.x, tid = threadIdx.x;
+    double a = 0.0, b = 0.0;
+    for (int blk = tid; blk < nblocks; blk += 256) {
+        a += partial[((long long)blk * groups + g) * 2];
+        b += partial[((long long)blk * groups + g) * 2 + 1];
+    }
+    red[0][tid] = a; red[1][tid] = b;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double mean = red[0][0] / count;
+        const double var = fmax(red[1][0] / count - mean * mean, 0.0);
+        moments[2 * g] = (float)mean;
+        moments[2 * g + 1] = (float)var;
+    }
 }
 
 struct NormArgs {
@@ -183,7 +218,20 @@ struct NormArgs {
     int ldz;                                 // row stride of zy / zb (they may be the two halves of one GEMM output)
     int out_pad;                             // 1: y is the zero-padded conv input [T + 2, H + 2, W + 2, C] (bya_vae_conv3d)
     int cpr_shift;                           // log2(C / 8) when that is a power of two, else -1
+    int moments;                             // 1: sums holds (mean, var) per group (bya_vae_groupnorm_moments), 0: (sum x, sum x^2)
 };
+
+__device__ __forceinline__ void group_mean_rstd(const NormArgs& p, int g, float& mean, float& rstd) {
+    float var;
+    if (p.moments) {
+        mean = p.sums[2 * g];
+        var = p.sums[2 * g + 1];
+    } else {
+        mean = p.sums[2 * g] / p.count;
+        var = fmaxf(p.sums[2 * g + 1] / p.count - mean * mean, 0.f);
+    }
+    rstd = rsqrtf(var + p.eps);
+}
 
 // One thread = one 16-byte piece (8 channels) of one row.  32-bit index arithmetic (a chunk has < 2^31 pieces: checked by the
 // launcher), the channel-piece count a power of two: the 64-bit divisions of the first version cost more than its HBM bytes.
@@ -219,10 +267,8 @@ __global__ __launch_bounds__(256) void vae_norm_act_kernel(NormArgs p) {
     // the group of these 8 channels (a piece never straddles two groups when the group size is a multiple of 8)
     float o[8];
     if ((cg & 7) == 0) {
-        const int g = c0 / cg;
-        const float mean = p.sums[2 * g] / p.count;
-        const float var = fmaxf(p.sums[2 * g + 1] / p.count - mean * mean, 0.f);
-        const float rstd = rsqrtf(var + p.eps);
+        float mean, rstd;
+        group_mean_rstd(p, c0 / cg, mean, rstd);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             float y = (v[e] - mean) * rstd * gm[e] + bt[e];
@@ -233,10 +279,8 @@ __global__ __launch_bounds__(256) void vae_norm_act_kernel(NormArgs p) {
     } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const int g = (c0 + e) / cg;
-            const float mean = p.sums[2 * g] / p.count;
-            const float var = fmaxf(p.sums[2 * g + 1] / p.count - mean * mean, 0.f);
-            const float rstd = rsqrtf(var + p.eps);
+            float mean, rstd;
+            group_mean_rstd(p, (c0 + e) / cg, mean, rstd);
             float y = (v[e] - mean) * rstd * gm[e] + bt[e];
             if (p.zy) y = y * zy[e] + zb[e];
             if (p.act == 1) y = y / (1.0f + __expf(-y));      // SiLU
@@ -295,15 +339,28 @@ extern "C" int bya_vae_groupnorm_stats(const void* x, float* sums, float* partia
     if (C > 512 || (cpr & (cpr - 1)) || cpr > 64) return BYA_ERR_UNSUPPORTED;      // C / 8 a power of two <= 64
     if ((uintptr_t)x & 15) return BYA_ERR_ALIGN;
     const long long blocks = (rows + GN_ROWS - 1) / GN_ROWS;
-    BYA_LAUNCH(vae_gn_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t*)x, partial, (long long)rows, C, groups);
+    BYA_LAUNCH(vae_gn_partial_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t*)x, partial, (long long)rows, C, groups);
     BYA_LAUNCH(vae_gn_final_kernel, dim3((unsigned)(groups * 2)), dim3(256), 0, stream, (const float*)partial, sums, (int)blocks, groups);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 
-extern "C" int bya_vae_norm_act(const void* x, void* y, const float* sums, const void* gamma, const void* beta, const void* zy,
-                                const void* zb, int64_t rows, int32_t C, int32_t groups, int32_t act, float eps, int32_t T,
-                                int32_t H, int32_t W, int32_t Tz, int32_t hz, int32_t wz, int32_t tmode, int64_t ldz,
-                                int32_t out_pad, hipStream_t stream) {
+extern "C" int bya_vae_groupnorm_moments(const void* x, float* moments, double* partial, int64_t rows, int32_t C, int32_t groups,
+                                         hipStream_t stream) {
+    if (!x || !moments || !partial || rows <= 0 || C <= 0 || groups <= 0 || C % groups || C % 8) return BYA_ERR_SHAPE;
+    const int cpr = C / 8;
+    if (C > 512 || (cpr & (cpr - 1)) || cpr > 64) return BYA_ERR_UNSUPPORTED;      // C / 8 a power of two <= 64
+    if (((uintptr_t)x & 15) || ((uintptr_t)partial & 7)) return BYA_ERR_ALIGN;
+    const long long blocks = (rows + GN_ROWS - 1) / GN_ROWS;
+    BYA_LAUNCH(vae_gn_partial_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t*)x, partial, (long long)rows, C, groups);
+    BYA_LAUNCH(vae_gn_moments_kernel, dim3((unsigned)groups), dim3(256), 0, stream, (const double*)partial, moments, (int)blocks, groups,
+               (double)rows * (C / groups));
+    return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+static int vae_norm_act_launch(const void* x, void* y, const float* sums, int moments, const void* gamma, const void* beta, const void* zy,
+                               const void* zb, int64_t rows, int32_t C, int32_t groups, int32_t act, float eps, int32_t T,
+                               int32_t H, int32_t W, int32_t Tz, int32_t hz, int32_t wz, int32_t tmode, int64_t ldz,
+                               int32_t out_pad, hipStream_t stream) {
     if (!x || !y || !sums || !gamma || !beta || rows <= 0 || C <= 0 || groups <= 0 || C % groups || C % 8) return BYA_ERR_SHAPE;
     if ((zy == nullptr) != (zb == nullptr)) return BYA_ERR_SHAPE;
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)zy | (uintptr_t)zb) & 15) return BYA_ERR_ALIGN;
@@ -313,6 +370,7 @@ extern "C" int bya_vae_norm_act(const void* x, void* y, const float* sums, const
     p.count = (float)((double)rows * (C / groups)); p.eps = eps;
     p.T = T; p.H = H; p.W = W; p.Tz = Tz; p.hz = hz; p.wz = wz; p.tmode = tmode; p.ldz = (int)ldz;
     p.out_pad = out_pad ? 1 : 0;
+    p.moments = moments;
     if (out_pad && (T <= 0 || H <= 0 || W <= 0 || (long long)T * H * W != rows)) return BYA_ERR_SHAPE;
     if (zy) {
         if ((long long)T * H * W != rows || hz <= 0 || wz <= 0 || H % hz || W % wz || H / hz != W / wz || ldz % 8) return BYA_ERR_SHAPE;
@@ -330,6 +388,20 @@ extern "C" int bya_vae_norm_act(const void* x, void* y, const float* sums, const
         if ((C >> 3) == (1 << sft)) p.cpr_shift = sft;
     BYA_LAUNCH(vae_norm_act_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+}
+
+extern "C" int bya_vae_norm_act(const void* x, void* y, const float* sums, const void* gamma, const void* beta, const void* zy,
+                                const void* zb, int64_t rows, int32_t C, int32_t groups, int32_t act, float eps, int32_t T,
+                                int32_t H, int32_t W, int32_t Tz, int32_t hz, int32_t wz, int32_t tmode, int64_t ldz,
+                                int32_t out_pad, hipStream_t stream) {
+    return vae_norm_act_launch(x, y, sums, 0, gamma, beta, zy, zb, rows, C, groups, act, eps, T, H, W, Tz, hz, wz, tmode, ldz, out_pad, stream);
+}
+
+extern "C" int bya_vae_norm_act_moments(const void* x, void* y, const float* moments, const void* gamma, const void* beta, const void* zy,
+                                        const void* zb, int64_t rows, int32_t C, int32_t groups, int32_t act, float eps, int32_t T,
+                                        int32_t H, int32_t W, int32_t Tz, int32_t hz, int32_t wz, int32_t tmode, int64_t ldz,
+                                        int32_t out_pad, hipStream_t stream) {
+    return vae_norm_act_launch(x, y, moments, 1, gamma, beta, zy, zb, rows, C, groups, act, eps, T, H, W, Tz, hz, wz, tmode, ldz, out_pad, stream);
 }
 
 extern "C" int bya_vae_upsample_pad(const void* x, void* ypad, int32_t T, int32_t H, int32_t W, int32_t C, int32_t tmode,

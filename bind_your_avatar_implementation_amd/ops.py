@@ -1587,29 +1587,35 @@ def vae_patches(x, cache, out, KT, stride, pad, up, tmode, Ho, Wo, t0, nt):
     return out
 
 
-def vae_groupnorm_stats(x2d, sums, groups, partial=None):
+def vae_groupnorm_stats(x2d, sums, groups, partial=None, moments=False):
+    """``sums`` [groups, 2] fp32 = (sum x, sum x^2) per group of x2d [rows, C]; ``moments``: (mean, var) instead, formed in fp64
+    before the one rounding (bya_vae_groupnorm_moments; its ``partial`` scratch is fp64) -- what ``vae_norm_act(moments=True)`` reads."""
     rows, C = x2d.shape
     assert x2d.is_contiguous() and sums.dtype == torch.float32 and sums.numel() == 2 * groups
     need = (rows + 511) // 512 * groups * 2
+    pdt = torch.float64 if moments else torch.float32
     if partial is None:
-        partial = torch.empty(need, dtype=torch.float32, device=x2d.device)
-    assert partial.dtype == torch.float32 and partial.numel() >= need and partial.is_contiguous()
-    _launch(None, None, 0.0, ("bya_vae_groupnorm_stats", (_p(x2d), _p(sums), _p(partial), rows, C, groups)))
+        partial = torch.empty(need, dtype=pdt, device=x2d.device)
+    assert partial.dtype == pdt and partial.numel() >= need and partial.is_contiguous()
+    _launch(None, None, 0.0, ("bya_vae_groupnorm_moments" if moments else "bya_vae_groupnorm_stats",
+                              (_p(x2d), _p(sums), _p(partial), rows, C, groups)))
     return sums
 
 
 def vae_norm_act(x, y, sums, gamma, beta, groups, act="silu", eps=1e-6, zy=None, zb=None, latent_shape=None, tmode=1,
-                 out_pad=False):
+                 out_pad=False, moments=False):
     """x: [T, H, W, C] channels-last; y: the same, or (out_pad) the zero-padded conv input [T + 2, H + 2, W + 2, C] whose
-    interior frames 2.. are written; zy / zb: [Tz * hz * wz, C] views (row stride = their .stride(0))."""
+    interior frames 2.. are written; zy / zb: [Tz * hz * wz, C] views (row stride = their .stride(0)).  ``moments``: ``sums``
+    holds (mean, var) per group (``vae_groupnorm_stats(moments=True)``) and not (sum x, sum x^2)."""
     T, H, W, C = x.shape
     assert x.is_contiguous() and y.is_contiguous()
     assert tuple(y.shape) == ((T + 2, H + 2, W + 2, C) if out_pad else (T, H, W, C))
     Tz, hz, wz = latent_shape if latent_shape is not None else (T, H, W)
     ldz = zy.stride(0) if zy is not None else 0
-    _launch(None, None, 0.0, ("bya_vae_norm_act", (_p(x), _p(y), _p(sums), _p(gamma), _p(beta), _p(zy), _p(zb), T * H * W, C, groups,
-                                                   {None: 0, "none": 0, "silu": 1}[act], float(eps), T, H, W, Tz, hz, wz, tmode, ldz,
-                                                   int(bool(out_pad)))))
+    _launch(None, None, 0.0, ("bya_vae_norm_act_moments" if moments else "bya_vae_norm_act",
+                              (_p(x), _p(y), _p(sums), _p(gamma), _p(beta), _p(zy), _p(zb), T * H * W, C, groups,
+                               {None: 0, "none": 0, "silu": 1}[act], float(eps), T, H, W, Tz, hz, wz, tmode, ldz,
+                               int(bool(out_pad)))))
     return y
 
 

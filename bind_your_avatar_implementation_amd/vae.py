@@ -267,8 +267,9 @@ class BindyouravatarVAE(nn.Module):
         T, H, W, C = x.shape
         gn = norm.norm_layer if hasattr(norm, "norm_layer") else norm
         sums = self._buf("gn_sums", 2 * gn.num_groups, dtype=torch.float32)
-        part = self._buf("gn_partial", (T * H * W + 511) // 512 * gn.num_groups * 2, dtype=torch.float32)
-        ops.vae_groupnorm_stats(x.view(-1, C), sums, gn.num_groups, part)
+        # (mean, var) per group, formed in fp64: the pair (sum x, sum x^2) in fp32 loses 3 * 2^-24 * (mean / spread)^2 of the variance
+        part = self._buf("gn_partial", (T * H * W + 511) // 512 * gn.num_groups * 2, dtype=torch.float64)
+        ops.vae_groupnorm_stats(x.view(-1, C), sums, gn.num_groups, part, moments=True)
         y = out_pad if out_pad is not None else torch.empty_like(x)
         pad = out_pad is not None
         if hasattr(norm, "norm_layer"):
@@ -278,9 +279,9 @@ class BindyouravatarVAE(nn.Module):
             ops.gemm(z64, wp, zyb, bias=bp)
             tmode = 2 if (T > 1 and T % 2 == 1) else 1
             ops.vae_norm_act(x, y, sums, gn.weight, gn.bias, gn.num_groups, act=act, eps=gn.eps, zy=zyb[:, :C], zb=zyb[:, C:],
-                             latent_shape=lat, tmode=tmode, out_pad=pad)
+                             latent_shape=lat, tmode=tmode, out_pad=pad, moments=True)
         else:
-            ops.vae_norm_act(x, y, sums, gn.weight, gn.bias, gn.num_groups, act=act, eps=gn.eps, out_pad=pad)
+            ops.vae_norm_act(x, y, sums, gn.weight, gn.bias, gn.num_groups, act=act, eps=gn.eps, out_pad=pad, moments=True)
         return y
 
     def _pad_buf(self, T, H, W, C):

@@ -471,7 +471,11 @@ int bya_timestep_features(const int64_t* timesteps, void* out, int32_t batch, in
  * Affine + modulation are evaluated as ONE fma, y = fma(LN(x), w (1 + scale), b (1 + scale) + shift), in every kernel
  * behind this entry point (at D = 3072 with w and b a wave keeps those two vectors in registers and walks several rows),
  * so a result does not depend on how the rows are cut into launches.
- * --------------------------------------------------------------------------------------------- */
+ * ---------------------------------------------------------------------------------------------
+ * Statistics: centred second pass in fp32 on the row held in registers (mean = sum / D by a true division); within half a bf16
+ * ulp of F.layer_norm in fp32 on every row distribution of tests/cond_norm.py, offset (|mean| / spread up to 256), near-constant
+ * and constant rows included.
+ */
 int bya_layernorm(const void* x, void* y, const void* w, const void* b, const void* shift0, const void* scale0,
                   const void* shift1, const void* scale1, int64_t rows_per_batch, int32_t batch, int32_t D,
                   int64_t ldx, int64_t ldy, int64_t x_batch_stride, int64_t y_batch_stride,
@@ -516,7 +520,10 @@ int bya_layernorm_plan(const void* x, const void* y, const void* w, const void* 
  * raises (atomic maximum on the bit pattern) entry [blockIdx % stats_slots][0 = q, 1 = k][z * heads + head] to the squared
  * Euclidean norm of every finished, bf16-rounded head row it writes: max over the slots = max ||q||^2 / max ||k||^2 per
  * (batch, head) -- the data-dependent score bound  |q . k| <= max||q|| max||k||  that bya_attn_fwd reads from device
- * memory (bya_attn_desc.bound_dev) when the worst case over the LayerNorm's parameters is too large to be useful. */
+ * memory (bya_attn_desc.bound_dev) when the worst case over the LayerNorm's parameters is too large to be useful.
+ * Statistics: centred second pass in fp32 over the 64 values of a head (qknorm_math.h, shared with the fused q|k|v epilogues);
+ * within half a bf16 ulp of the fp32 definition on offset, near-constant and constant head rows (tests/test_norm_cond_gpu.py).
+ */
 int bya_qknorm_rope(void* q, void* k, const void* qw, const void* qb, const void* kw, const void* kb,
                     const float* cos, const float* sin, int32_t batch, int32_t S, int32_t heads, int64_t ld,
                     int64_t batch_stride, int32_t text_rows, float eps, float k_scale, float* stats, int32_t stats_slots,
@@ -727,7 +734,10 @@ int bya_attn_tiny_plan(const void* q, const void* k, const void* v, const void* 
  *                + pos_emb[n]  ->  out[id,n,512]
  * router_head:   r[n,id] = sigmoid(x[id,n,:].w + b)  ->  [N, n_id]  (the [1,N,n_id] routing logits)
  * (router_scores keeps an identity's 32 keys in LDS from 4096 tokens on; same bits as the per-wave form below that.)
- * --------------------------------------------------------------------------------------------- */
+ * ---------------------------------------------------------------------------------------------
+ * Statistics of the LayerNorm(512): centred second pass in fp32 on the accumulators, in both kernels; no restriction on the rows
+ * (tests/test_norm_cond_gpu.py).
+ */
 int bya_router_scores(const void* qr, const void* kr, const void* ln_w, const void* ln_b, const void* pos_emb,
                       void* out, int32_t n_id, int64_t N, int32_t heads, int32_t face_tokens, float eps,
                       hipStream_t stream);
@@ -787,6 +797,12 @@ int bya_act_add_plan(const void* x, const void* r, const void* y, int64_t n, int
  *         cvec[n] = sum_k W[n,k] * beta[k] + bias[n]  (fp32);  the kernel computes the row mean / rstd itself and
  *         applies  rstd * (x . Wg^T - mean * colsum) + cvec.
  * ln = 0: W as is, cvec = bias (fp32), colsum ignored.
+ * Statistics (ln = 1): ONE PASS.  sum x and sum x^2 come from the matrix core in fp32, var = max(E[x^2] - mean^2, 0), and the mean
+ * is folded into the product (acc - mean * colsum): two cancellations.  Supported domain: bf16 rows with |mean| / spread <= 8 (and
+ * colsum of a few units; with colsum = 25.6 only rows without an offset).  There the result is within half a bf16 ulp of what an
+ * fp32 centred LayerNorm followed by the Linear gives (tests/test_norm_cond_gpu.py).  Beyond it the result drifts, measured on an
+ * MI355X in bf16 ulps of the fp64 result: |mean| / spread = 8 with colsum = 25.6: up to 1.14;  64: 3.6 .. 11.5;  256: 32 .. 131;
+ * near-constant rows (8 channels a few bf16 steps off a constant): 98 .. 526;  constant rows: finite, but up to 0.1 off cvec.
  * X: bf16 rows of 512 with row stride ldx; C / res: bf16 with row strides ldc / ldres (C may alias res).
  * N % (64 * nsplit) == 0; nsplit <= 0 lets the library choose how many column groups share a row block.
  * act: BYA_ACT_NONE or BYA_ACT_GELU_ERF.
@@ -824,6 +840,9 @@ int bya_rowgemm512_plan(const void* X, const void* W, const float* colsum, const
  * 16-row MFMA tile in power-of-two cells, groups of 17 .. 32 rows (25 latent frames of a 97-frame clip) take the two
  * tiles of one wave; longer sequences return BYA_ERR_UNSUPPORTED (the unfused pair handles them).
  * scale = 1 / sqrt(64).  q, k, v are rounded to bf16 where the unfused path stored them, P to bf16 before P.V.
+ * Statistics: one pass, as bya_rowgemm512 with ln = 1 -- the same domain (|mean| / spread <= 8) and, measured through a one-key
+ * group (L = 1: O = v), the same drift beyond it: 0.78 bf16 ulp at 8 with colsum = 25.6, 5.9 at 64, 58 at 256, 429 on
+ * near-constant rows.
  * --------------------------------------------------------------------------------------------- */
 int bya_router_group_attn(const void* X, const void* Wqkv, const float* colsum, const float* cvec, void* O,
                           int32_t M, int32_t ldx, int32_t ldo, int32_t L, int64_t n_outer, int64_t n_inner,
@@ -856,6 +875,9 @@ int bya_router_group_attn_plan(const void* X, const void* Wqkv, const float* col
  * Both give, BIT FOR BIT, what their two launches give (same MFMA order over K, same epilogue expressions on the same
  * rounded values).  tiles_pass0: 16-row tiles per workgroup in the first pass over the rows (1..8; 0 = 8); the remainder
  * is dealt over all workgroups in a short second pass.  A tuning hint: results do not depend on it.
+ * Statistics of both chains: one pass (rowgemm_common.h tile_row_stats), the domain and the drift of bya_rowgemm512 with ln = 1:
+ * measured on the value kept in registers, bya_router_mlp_fused is 1.0 bf16 ulp off at |mean| / spread = 8 (as its two-launch
+ * definition in fp32), 4.0 at 64, 34 .. 49 at 256; bya_router_group_attn_out 1.0, 11.5 and 40.
  * --------------------------------------------------------------------------------------------- */
 int bya_router_mlp_fused(const void* X, const void* W1, const float* colsum1, const float* cvec1, const void* W2,
                          const float* cvec2, void* C, int32_t M, int32_t ldx, int32_t ldc, float eps, int32_t tiles_pass0,
@@ -925,20 +947,39 @@ int bya_vae_patches(const void* x, const void* cache, void* out, int32_t Ts, int
                     int32_t Kpad, hipStream_t stream);
 /* GroupNorm statistics of one chunk: sums [groups][2] fp32 = (sum, sum of squares) over x [rows, C], summed in a FIXED order
  * (no atomics: the same chunk gives the same bits every run).  partial: caller's scratch, ceil(rows / 512) * groups * 2 floats.
- * C <= 512 with C / 8 a power of two. */
+ * C <= 512 with C / 8 a power of two.  Every sum is carried in fp64 and rounded to fp32 once per partial and once per result:
+ * the pair is as good as its fp32 slots can hold, whatever the depth of the hierarchy.  Nothing in the package calls this form or
+ * bya_vae_norm_act any more (vae.py runs the two _moments entry points below); they stay for callers that hold such sums. */
 int bya_vae_groupnorm_stats(const void* x, float* sums, float* partial, int64_t rows, int32_t C, int32_t groups,
                             hipStream_t stream);
+/* The same statistics as CENTRED moments: moments [groups][2] fp32 = (mean, var) with var = max(sum x^2 / n - mean^2, 0) formed in
+ * fp64 from fp64 sums (one read of x, like bya_vae_groupnorm_stats) and rounded to fp32 once: the cancellation costs 2^-53 R^2
+ * of the variance of a group with R = |mean| / spread, where the fp32 pair above holds it to 3 * 2^-24 * R^2 at best.  partial:
+ * caller's scratch, ceil(rows / 512) * groups * 2 DOUBLES.  Same shapes, same fixed order.  Read by bya_vae_norm_act_moments. */
+int bya_vae_groupnorm_moments(const void* x, float* moments, double* partial, int64_t rows, int32_t C, int32_t groups,
+                              hipStream_t stream);
 /* y = act( GroupNorm(x; sums, gamma, beta, eps) [ * zy[z(row)] + zb[z(row)] ] ), act 0 = none, 1 = SiLU.  zy / zb (both or
  * neither): conv_y / conv_b of CogVideoXSpatialNorm3D evaluated at LATENT resolution [Tz * hz * wz rows, row stride ldz]; row
  * (t, h, w) of x [T, H, W, C] reads latent position (frame by tmode, h >> log2(H / hz), w >> log2(W / wz)): tmode 0 = same
  * frame, 1 = floor(t Tz / T), 2 = first frame apart (0 -> 0, t -> 1 + floor((t - 1)(Tz - 1) / (T - 1))): torch's nearest
- * F.interpolate, first frame and the rest resized separately when T is odd and > 1. */
+ * F.interpolate, first frame and the rest resized separately when T is odd and > 1.
+ * Statistics of bya_vae_norm_act: ONE PASS, mean = sum / n and var = max(sum of squares / n - mean^2, 0) in fp32 from the fp32 pair
+ * ``sums``, which holds the variance of a group with R = |mean| / spread to about 3 * 2^-24 * R^2.  Supported domain: R <= 8.
+ * Beyond it the result drifts, measured on an MI355X in bf16 ulps of the fp64 result: R = 64: 0.8 .. 3.9 (the worst where gamma,
+ * beta and the modulation cancel);  256: 0.7 .. 18.6;  near-constant groups: 4 .. 179;  constant groups: beta exactly.
+ * bya_vae_norm_act_moments is the same operation on ``moments`` = (mean, var) of bya_vae_groupnorm_moments -- what the VAE runs --
+ * and has no such restriction: within half a bf16 ulp of F.group_norm in fp32 on every distribution of tests/cond_norm.py, R = 256,
+ * near-constant and constant groups included (tests/test_norm_cond_gpu.py). */
 /* out_pad = 1: y is the zero-padded input of bya_vae_conv3d, [T + 2, H + 2, W + 2, C] (the caller zero-fills it once and
  * writes the two context frames; this call writes pixel (t, h, w) at (t + 2, h + 1, w + 1)); rows must be T H W. */
 int bya_vae_norm_act(const void* x, void* y, const float* sums, const void* gamma, const void* beta, const void* zy,
                      const void* zb, int64_t rows, int32_t C, int32_t groups, int32_t act, float eps, int32_t T, int32_t H,
                      int32_t W, int32_t Tz, int32_t hz, int32_t wz, int32_t tmode, int64_t ldz, int32_t out_pad,
                      hipStream_t stream);
+int bya_vae_norm_act_moments(const void* x, void* y, const float* moments, const void* gamma, const void* beta, const void* zy,
+                             const void* zb, int64_t rows, int32_t C, int32_t groups, int32_t act, float eps, int32_t T, int32_t H,
+                             int32_t W, int32_t Tz, int32_t hz, int32_t wz, int32_t tmode, int64_t ldz, int32_t out_pad,
+                             hipStream_t stream);
 
 /* Causal KT x 3 x 3 convolution, stride 1 (KT = 3: diffusers CogVideoXCausalConv3d inside CogVideoXResnetBlock3D and conv_out;
  * KT = 1: the per-frame 3 x 3 convolution of CogVideoXUpsample3D; reached from models/pipeline_bindyouravatar.py:461-466 /

@@ -32,6 +32,7 @@ MEMORY_SIDE = ["bya_quantize_rows_fp8", "bya_quantize_mx", "bya_linear_small_m",
                "bya_layernorm_fp8", "bya_layernorm_mx", "bya_qknorm_rope", "bya_attn_tiny", "bya_router_head",
                "bya_forcing_max_over_frames", "bya_masked_combine", "bya_routed_mix", "bya_patchify", "bya_unpatchify", "bya_act_add",
                "bya_cfg_scheduler_step", "bya_masks_to_routing_logits", "bya_vae_patches", "bya_vae_groupnorm_stats", "bya_vae_norm_act",
+               "bya_vae_groupnorm_moments", "bya_vae_norm_act_moments",
                "bya_vae_upsample_pad"]
 ATTN_SHAPE = f"1x1x{H}h_q{S}_kv{S}_d64"
 
@@ -132,6 +133,8 @@ def launch_everything(o, dev):
     sums = f32(64)
     ops.vae_groupnorm_stats(xv.view(-1, C), sums, 32)
     ops.vae_norm_act(xv, bf(T, Hh, Wv, C), sums, rnd(C) + 1, rnd(C), 32)
+    ops.vae_groupnorm_stats(xv.view(-1, C), sums, 32, moments=True)
+    ops.vae_norm_act(xv, bf(T, Hh, Wv, C), sums, rnd(C) + 1, rnd(C), 32, moments=True)
     xpad = torch.zeros(T + 2, Hh + 2, Wv + 2, C, dtype=BF, device=dev)
     ops.vae_conv3d(xpad, rnd(Cout, 27 * C, std=(27 * C) ** -0.5), rnd(Cout), bf(T, Hh, Wv, Cout))
     ops.vae_upsample_pad(xv, torch.zeros(2 * T, 2 * Hh + 2, 2 * Wv + 2, C, dtype=BF, device=dev), 1)
