@@ -58,6 +58,14 @@ class AttnMixDesc(_c.Structure):
                 ("v_id", _i64), ("v_grp", _i64), ("v_row", _i64), ("z_grp", _i64), ("z_row", _i64), ("scale", _f32)]
 
 
+MIX_MAX_SEGMENTS = 16   # BYA_MIX_MAX_SEGMENTS
+
+
+class AttnMixSegments(_c.Structure):
+    """bya_attn_mix_segments: the table of bya_attn_kv_mix_seg / _mx_seg, (K / V group, first row, rows) per segment."""
+    _fields_ = [("n", _i32), ("grp", _i32 * MIX_MAX_SEGMENTS), ("start", _i32 * MIX_MAX_SEGMENTS), ("len", _i32 * MIX_MAX_SEGMENTS)]
+
+
 class AttnPlan(_c.Structure):
     _fields_ = [("variant", _i32), ("grid", _i32), ("q_tile", _i32), ("stream_k", _i32), ("sk_rem", _i32), ("sk_cut", _i32),
                 ("o_wide", _i32), ("second_launch", _i32)]
@@ -167,6 +175,12 @@ SIGNATURES = {
     "bya_attn_kv_mix_plan": [_vp, _vp, _c.POINTER(AttnMixDesc), _c.POINTER(AttnMixPlan)],
     "bya_attn_kv_mix_mx": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(AttnMixDesc), _i32, _i64, _i64, _i64, _i64, _vp],
     "bya_attn_kv_mix_mx_plan": [_vp, _vp, _vp, _c.POINTER(AttnMixDesc), _i32, _i64, _i64, _i64, _i64, _c.POINTER(AttnMixPlan)],
+    "bya_attn_kv_mix_seg": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(AttnMixDesc), _c.POINTER(AttnMixSegments), _vp],
+    "bya_attn_kv_mix_seg_plan": [_vp, _vp, _c.POINTER(AttnMixDesc), _c.POINTER(AttnMixSegments), _c.POINTER(AttnMixPlan)],
+    "bya_attn_kv_mix_mx_seg": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(AttnMixDesc), _c.POINTER(AttnMixSegments), _i32,
+                               _i64, _i64, _i64, _i64, _vp],
+    "bya_attn_kv_mix_mx_seg_plan": [_vp, _vp, _vp, _c.POINTER(AttnMixDesc), _c.POINTER(AttnMixSegments), _i32, _i64, _i64, _i64,
+                                    _i64, _c.POINTER(AttnMixPlan)],
     "bya_attn_tiny": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp],
     "bya_attn_tiny_plan": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _c.POINTER(AttnTinyPlan)],
     "bya_router_scores": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _vp],

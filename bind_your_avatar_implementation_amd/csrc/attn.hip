@@ -635,6 +635,13 @@ int launch_attn_mx(const AttnMxArgs& m, int fmt, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
 }
 
+// row chunks per (group, head) of the <= 32-key form: about three 32-row tiles per wave, and at least ~4 workgroups per CU in total
+inline int mix32_row_chunks(int rows) {
+    const int n32 = (rows + 31) / 32;
+    const int nqc = (n32 + 11) / 12;
+    return nqc < 1 ? 1 : nqc;
+}
+
 // bya_attn_kv_mix: argument checks and launch decisions in one place (launcher and bya_attn_kv_mix_plan).
 // qkv: the q, k, v addresses OR-ed together (0 in the query: it has none).
 int mix_plan_of(const void* z, const bya_attn_mix_desc* d, int has_af, uintptr_t qkv, bya_attn_kv_mix_plan_info* p) {
@@ -648,11 +655,8 @@ int mix_plan_of(const void* z, const bya_attn_mix_desc* d, int has_af, uintptr_t
     if ((uintptr_t)z & 7) return BYA_ERR_ALIGN;
     p->head_dim = d->head_dim;
     if (d->Skv <= 32 && !bya_ref_form(BYA_REF_KV_MIX_GENERIC) && !((uintptr_t)z & 15) && (d->z_grp | d->z_row) % 8 == 0) {
-        // row chunks per (group, head): about three 32-row tiles per wave, and at least ~4 workgroups per CU in total
-        const int n32 = (d->Sq + 31) / 32;
-        const int nqc = (n32 + 11) / 12;
         p->form = BYA_KV_MIX_MIX32;
-        p->row_chunks = nqc < 1 ? 1 : nqc;
+        p->row_chunks = mix32_row_chunks(d->Sq);
         p->lds_bytes = (d->n_id * 2 + 4) * 32 * d->head_dim * 2;    // K, V per identity + a z patch per wave
         p->big_lds = p->lds_bytes > 64 * 1024;                      // four identities at head_dim 128: 96 KiB
     } else {
@@ -678,6 +682,31 @@ int mix_mx_plan_of(const void* codes, const void* scales, const bya_attn_mix_des
     const long long blocks = (long long)d->heads * d->head_dim / 32;
     if (((uintptr_t)codes | (uintptr_t)c_grp | (uintptr_t)c_row) & 3) return BYA_ERR_ALIGN;      // (the entry's rule: e4m3 codes leave as dwords; e2m3's 2-byte stores would need less)
     if (c_row < blocks * mx_block_bytes(out_fmt) || sc_row < blocks || c_grp < 0 || sc_grp < 0) return BYA_ERR_SHAPE;
+    return BYA_OK;
+}
+
+// bya_attn_kv_mix_seg / _mx_seg, before the grouped entry's own checks: the table against the descriptor (n_grp = the K / V
+// groups it may name, Sq = the rows of q, r, z and wsum), and no group stride on anything the table addresses by row.
+int mix_seg_check(const bya_attn_mix_segments* s, const bya_attn_mix_desc* d) {
+    if (!s || !d) return BYA_ERR_SHAPE;
+    if (s->n < 1 || s->n > BYA_MIX_MAX_SEGMENTS || d->q_grp || d->z_grp) return BYA_ERR_SHAPE;
+    long long end = 0;                                          // ascending, no overlap: a segment starts at or behind the last one's end
+    for (int i = 0; i < s->n; ++i) {
+        if (s->len[i] <= 0 || s->grp[i] < 0 || s->grp[i] >= d->n_grp || s->start[i] < end) return BYA_ERR_SHAPE;
+        end = (long long)s->start[i] + s->len[i];
+        if (end > d->Sq) return BYA_ERR_SHAPE;
+    }
+    return BYA_OK;
+}
+
+// ... and behind them: the segment form exists on the <= 32-key form at head_dim 64 alone (the caller then issues the launches
+// per segment); its row chunks are those of the LONGEST segment, its grid one workgroup per (segment, head, row chunk).
+int mix_seg_plan_of(const bya_attn_mix_segments* s, const bya_attn_mix_desc* d, bya_attn_kv_mix_plan_info* p) {
+    if (p->form != BYA_KV_MIX_MIX32 || d->head_dim != 64) return BYA_ERR_UNSUPPORTED;
+    int longest = 0;
+    for (int i = 0; i < s->n; ++i) longest = s->len[i] > longest ? s->len[i] : longest;
+    p->row_chunks = mix32_row_chunks(longest);
+    p->grid = (int32_t)((long long)p->row_chunks * d->heads * s->n);
     return BYA_OK;
 }
 
@@ -786,5 +815,56 @@ extern "C" int bya_attn_kv_mix_mx(const void* q, const void* k, const void* v, c
     ByaMixMxOut out;
     out.codes = static_cast<uint8_t*>(codes); out.scales = static_cast<uint8_t*>(scales);
     out.c_grp = c_grp; out.c_row = c_row; out.s_grp = sc_grp; out.s_row = sc_row; out.fmt = out_fmt;
-    return bya_launch_attn_kv_mix32_mx(q, k, v, r, af, wsum, *d, pl, out, stream);
+    return bya_launch_attn_kv_mix32_mx(q, k, v, r, af, wsum, *d, pl, out, nullptr, stream);
+}
+
+extern "C" int bya_attn_kv_mix_seg_plan(const void* z, const void* af, const bya_attn_mix_desc* d, const bya_attn_mix_segments* seg,
+                                       bya_attn_kv_mix_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_attn_kv_mix_plan_info p;
+    int rc = mix_seg_check(seg, d);
+    if (rc == BYA_OK) rc = mix_plan_of(z, d, af != nullptr, 0, &p);
+    if (rc == BYA_OK) rc = mix_seg_plan_of(seg, d, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_attn_kv_mix_seg(const void* q, const void* k, const void* v, const void* r, const void* af, void* z, float* wsum,
+                                   const bya_attn_mix_desc* d, const bya_attn_mix_segments* seg, hipStream_t stream) {
+    if (!q || !k || !v || !r || !z) return BYA_ERR_SHAPE;
+    bya_attn_kv_mix_plan_info pl;
+    int rc = mix_seg_check(seg, d);
+    if (rc == BYA_OK) rc = mix_plan_of(z, d, af != nullptr, (uintptr_t)q | (uintptr_t)k | (uintptr_t)v, &pl);
+    if (rc == BYA_OK) rc = mix_seg_plan_of(seg, d, &pl);
+    if (rc != BYA_OK) return rc;
+    return bya_launch_attn_kv_mix32_seg(q, k, v, r, af, z, wsum, *d, pl, *seg, stream);
+}
+
+extern "C" int bya_attn_kv_mix_mx_seg_plan(const void* codes, const void* scales, const void* af, const bya_attn_mix_desc* d,
+                                          const bya_attn_mix_segments* seg, int32_t out_fmt, int64_t c_grp, int64_t c_row,
+                                          int64_t sc_grp, int64_t sc_row, bya_attn_kv_mix_plan_info* plan) {
+    if (!plan || c_grp || sc_grp) return BYA_ERR_SHAPE;
+    bya_attn_kv_mix_plan_info p;
+    int rc = mix_seg_check(seg, d);
+    if (rc == BYA_OK) rc = mix_mx_plan_of(codes, scales, d, af != nullptr, 0, out_fmt, c_grp, c_row, sc_grp, sc_row, &p);
+    if (rc == BYA_OK) rc = mix_seg_plan_of(seg, d, &p);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_attn_kv_mix_mx_seg(const void* q, const void* k, const void* v, const void* r, const void* af, void* codes,
+                                      void* scales, float* wsum, const bya_attn_mix_desc* d, const bya_attn_mix_segments* seg,
+                                      int32_t out_fmt, int64_t c_grp, int64_t c_row, int64_t sc_grp, int64_t sc_row,
+                                      hipStream_t stream) {
+    if (!q || !k || !v || !r || c_grp || sc_grp) return BYA_ERR_SHAPE;
+    bya_attn_kv_mix_plan_info pl;
+    int rc = mix_seg_check(seg, d);
+    if (rc == BYA_OK) rc = mix_mx_plan_of(codes, scales, d, af != nullptr, (uintptr_t)q | (uintptr_t)k | (uintptr_t)v, out_fmt, c_grp,
+                                          c_row, sc_grp, sc_row, &pl);
+    if (rc == BYA_OK) rc = mix_seg_plan_of(seg, d, &pl);
+    if (rc != BYA_OK) return rc;
+    ByaMixMxOut out;
+    out.codes = static_cast<uint8_t*>(codes); out.scales = static_cast<uint8_t*>(scales);
+    out.c_grp = 0; out.c_row = c_row; out.s_grp = 0; out.s_row = sc_row; out.fmt = out_fmt;
+    return bya_launch_attn_kv_mix32_mx(q, k, v, r, af, wsum, *d, pl, out, seg, stream);
 }

@@ -1,6 +1,7 @@
 // The <= 32-key form of bya_attn_kv_mix (attn_mix32_body) and the fragment helpers it shares with the attention kernels of
-// attn.hip.  Two translation units instantiate it: attn.hip (the bf16 instances) and attn_mix_mx.hip (the MX-output instances,
-// built without the SLP vectoriser like every translation unit that holds a quantiser: build.py, NO_SLP_SOURCES).
+// attn.hip.  Three translation units instantiate it: attn.hip (the bf16 instances), attn_mix_seg.hip (the bf16 instance that
+// takes its rows from a segment table, bya_attn_kv_mix_seg) and attn_mix_mx.hip (the MX-output instances of both, built without
+// the SLP vectoriser like every translation unit that holds a quantiser: build.py, NO_SLP_SOURCES).
 #pragma once
 #include "attn_common.h"
 #include "routing_weights.h"
@@ -77,6 +78,10 @@ struct MixArgs {
 // The MX-output instances of the <= 32-key form (bya_attn_kv_mix_mx) take MixArgs with z = nullptr plus a ByaMixMxOut.  The bf16
 // instances' kernel argument stays MixArgs alone.
 struct MixMxArgs { MixArgs a; ByaMixMxOut mx; };
+// The segment instances (bya_attn_kv_mix_seg / _mx_seg) carry the caller's table by value behind them: no device memory, so a
+// captured graph holds it.  There MixArgs.n_grp / Sq bound the table (checked on the host) and the kernel reads neither.
+struct MixSegArgs { MixArgs a; bya_attn_mix_segments seg; };
+struct MixMxSegArgs { MixArgs a; ByaMixMxOut mx; bya_attn_mix_segments seg; };
 
 // bya_attn_kv_mix's descriptor -> kernel arguments (z and its strides: the bf16 entry's alone)
 inline void mix_args_of(const void* q, const void* k, const void* v, const void* r, const void* af, float* wsum,
@@ -125,8 +130,16 @@ __device__ __forceinline__ void stage_kv32(const bf16_t* __restrict__ src, long 
 // quantiser's lane shape and its arithmetic, on the bf16 value in the patch: byte for byte bya_attn_kv_mix followed by
 // bya_quantize_mx on the [rows, heads * D] matrix, which is never written.  All 64 lanes take part in the |max| (rows past Sq
 // hold the clamped row's values, whole quads of them, and store nothing).  The format is a wave-uniform branch.
-template <int D, bool MX = false>
-__device__ __forceinline__ void attn_mix32_body(const MixArgs& p, char* smem, const ByaMixMxOut* mx = nullptr) {
+//
+// SEG = true (bya_attn_kv_mix_seg / _mx_seg): what a workgroup's "group" is -- which K / V block, where its rows start in q / r /
+// z / wsum / the MX pair, how many there are -- comes from entry blockIdx / (heads * nqt) of `seg` instead of one uniform Sq, and
+// nqt is the chunk count of the LONGEST segment: a workgroup whose share of its segment's tiles is empty leaves before it stages
+// anything (uniform over the workgroup, so the one barrier stays legal).  Everything below those few lines is the same code:
+// a row's arithmetic does not know which form runs, and a tile's padding lanes repeat the last row of their OWN segment, as in
+// the one-launch-per-segment form this replaces.
+template <int D, bool MX = false, bool SEG = false>
+__device__ __forceinline__ void attn_mix32_body(const MixArgs& p, char* smem, const ByaMixMxOut* mx = nullptr,
+                                                const bya_attn_mix_segments* seg = nullptr) {
     constexpr int ROW_BYTES = D * 2, KV_BYTES = 32 * ROW_BYTES, DSTEPS = D / 16, DT = D / 32;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -134,17 +147,31 @@ __device__ __forceinline__ void attn_mix32_body(const MixArgs& p, char* smem, co
     int bid = blockIdx.x;
     const int head = bid % p.heads; bid /= p.heads;
     const int chunk = bid % p.nqt;                               // nqt = row chunks per (group, head) in this form
-    const int grp = bid / p.nqt;
-    const int n32 = (p.Sq + 31) >> 5;
+    const int grp = bid / p.nqt;                                 // (SEG: the segment)
+    // the workgroup's rows: Sq of them against K / V group kgrp; the first is row row0 of r and wsum, q_off / z_off elements
+    // into q / z and c_off / s_off bytes into the MX pair
+    int kgrp = grp, Sq = p.Sq;
+    long long row0 = (long long)grp * p.Sq, q_off = grp * p.q_grp, z_off = 0, c_off = 0, s_off = 0;
+    if constexpr (SEG) {
+        kgrp = seg->grp[grp]; Sq = seg->len[grp]; row0 = seg->start[grp];
+        q_off = row0 * p.q_row;
+        if constexpr (MX) { c_off = row0 * mx->c_row; s_off = row0 * mx->s_row; }
+        else z_off = row0 * p.z_row;
+    } else {
+        if constexpr (MX) { c_off = grp * mx->c_grp; s_off = grp * mx->s_grp; }
+        else z_off = grp * p.z_grp;
+    }
+    const int n32 = (Sq + 31) >> 5;
     const int t0 = (int)((long long)n32 * chunk / p.nqt), t1 = (int)((long long)n32 * (chunk + 1) / p.nqt);
-    const bf16_t* Q = p.q + grp * p.q_grp + (long long)head * D;
+    if constexpr (SEG) if (t0 >= t1) return;                     // a segment shorter than the longest one's chunk count
+    const bf16_t* Q = p.q + q_off + (long long)head * D;
     bf16_t* Z = nullptr;
-    if constexpr (!MX) Z = p.z + grp * p.z_grp + (long long)head * D;
+    if constexpr (!MX) Z = p.z + z_off + (long long)head * D;
 
     for (int id = 0; id < p.n_id; ++id) {
-        stage_kv32<D>(p.k + id * p.k_id + grp * p.k_grp + (long long)head * D, p.k_row, p.Skv - 1, smem + id * 2 * KV_BYTES,
+        stage_kv32<D>(p.k + id * p.k_id + kgrp * p.k_grp + (long long)head * D, p.k_row, p.Skv - 1, smem + id * 2 * KV_BYTES,
                       wave, lane, false);
-        stage_kv32<D>(p.v + id * p.v_id + grp * p.v_grp + (long long)head * D, p.v_row, p.Skv - 1,
+        stage_kv32<D>(p.v + id * p.v_id + kgrp * p.v_grp + (long long)head * D, p.v_row, p.Skv - 1,
                       smem + id * 2 * KV_BYTES + KV_BYTES, wave, lane, true);
     }
     const int g = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
@@ -167,18 +194,18 @@ __device__ __forceinline__ void attn_mix32_body(const MixArgs& p, char* smem, co
     // level, face 42 -> 49 us; q requested one tile ahead in registers -- +35 registers, one wave per SIMD less, level)
     for (int t = t0 + wave; t < t1; t += 4) {
         int qrow = t * 32 + r;
-        const bool q_valid = qrow < p.Sq;
-        qrow = q_valid ? qrow : p.Sq - 1;
+        const bool q_valid = qrow < Sq;
+        qrow = q_valid ? qrow : Sq - 1;
         bf16x8 qf[DSTEPS];
 #pragma unroll
         for (int s = 0; s < DSTEPS; ++s)
             qf[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(Q + (long long)qrow * p.q_row + s * 16 + hf * 8));
         float w[4];
-        routing_weights_of(p.mode, p.n_id, p.af, p.r + ((long long)grp * p.Sq + qrow) * p.n_id, w);
+        routing_weights_of(p.mode, p.n_id, p.af, p.r + (row0 + qrow) * p.n_id, w);
         if (p.wsum && head == 0 && hf == 0 && q_valid) {
             float ws = 0.f;
             for (int i = 0; i < p.n_id; ++i) ws += w[i];
-            p.wsum[(long long)grp * p.Sq + qrow] = ws;
+            p.wsum[row0 + qrow] = ws;
         }
         char* zb = smem + p.n_id * 2 * KV_BYTES + wave * KV_BYTES;
         constexpr int CHUNKS = ROW_BYTES / 16;
@@ -270,13 +297,13 @@ __device__ __forceinline__ void attn_mix32_body(const MixArgs& p, char* smem, co
 #pragma unroll
                 for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[e]));
                 amax = quad_amax(amax);
-                if (t * 32 + row < p.Sq) {
+                if (t * 32 + row < Sq) {
                     const long long grow = t * 32 + row;
-                    uint8_t* crow = mx->codes + grp * mx->c_grp + grow * mx->c_row;
+                    uint8_t* crow = mx->codes + c_off + grow * mx->c_row;
                     uint32_t sb;
                     if (mx->fmt == MX_E4M3) sb = mx_quant8<MX_E4M3>(v, amax, crow + head * D + 8 * ch);
                     else sb = mx_quant8<MX_E2M3>(v, amax, crow + head * (D * 3 / 4) + 6 * ch);
-                    if ((ch & 3) == 0) mx->scales[grp * mx->s_grp + grow * mx->s_row + head * (D / 32) + (ch >> 2)] = (uint8_t)sb;
+                    if ((ch & 3) == 0) mx->scales[s_off + grow * mx->s_row + head * (D / 32) + (ch >> 2)] = (uint8_t)sb;
                 }
             }
         } else {
@@ -284,7 +311,7 @@ __device__ __forceinline__ void attn_mix32_body(const MixArgs& p, char* smem, co
         for (int j = 0; j < 32 * CHUNKS / 64; ++j) {
             const int idx = j * 64 + lane, row = idx / CHUNKS, ch = idx % CHUNKS;
             const u32x4 o = *reinterpret_cast<const u32x4*>(zb + row * ROW_BYTES + ((ch ^ (row & 7)) << 4));
-            if (t * 32 + row < p.Sq) *reinterpret_cast<u32x4*>(Z + (long long)(t * 32 + row) * p.z_row + ch * 8) = o;
+            if (t * 32 + row < Sq) *reinterpret_cast<u32x4*>(Z + (long long)(t * 32 + row) * p.z_row + ch * 8) = o;
         }
         }
         __builtin_amdgcn_wave_barrier();                         // the patch is rewritten by the next tile
@@ -294,8 +321,12 @@ __device__ __forceinline__ void attn_mix32_body(const MixArgs& p, char* smem, co
 }  // namespace
 
 // defined in attn_mix_mx.hip: the launch of the MX-output instances of the <= 32-key form for checked arguments (q .. wsum and
-// desc as for bya_attn_kv_mix, plan = its launch decisions, out = where the codes and scale bytes go); called from
-// bya_attn_kv_mix_mx
+// desc as for bya_attn_kv_mix, plan = its launch decisions, out = where the codes and scale bytes go, seg = NULL or the checked
+// table of the segment instance); called from bya_attn_kv_mix_mx and bya_attn_kv_mix_mx_seg
 int bya_launch_attn_kv_mix32_mx(const void* q, const void* k, const void* v, const void* r, const void* af, float* wsum,
                                 const bya_attn_mix_desc& desc, const bya_attn_kv_mix_plan_info& plan, const ByaMixMxOut& out,
-                                hipStream_t stream);
+                                const bya_attn_mix_segments* seg, hipStream_t stream);
+// defined in attn_mix_seg.hip: the launch of the bf16 segment instance for checked arguments; called from bya_attn_kv_mix_seg
+int bya_launch_attn_kv_mix32_seg(const void* q, const void* k, const void* v, const void* r, const void* af, void* z, float* wsum,
+                                 const bya_attn_mix_desc& desc, const bya_attn_kv_mix_plan_info& plan,
+                                 const bya_attn_mix_segments& seg, hipStream_t stream);

@@ -1,6 +1,6 @@
-// The MX-output instances of the <= 32-key kv-mix (bya_attn_kv_mix_mx; the body and its second epilogue: attn_mix32.h).  A
-// translation unit of their own because it is built without the SLP vectoriser (build.py, NO_SLP_SOURCES): the quantiser
-// arithmetic stays free of packed-fp32 VALU instructions, like the standalone and the LayerNorm-fused quantisers.  The
+// The MX-output instances of the <= 32-key kv-mix (bya_attn_kv_mix_mx, bya_attn_kv_mix_mx_seg; the body and its second epilogue:
+// attn_mix32.h).  A translation unit of their own because it is built without the SLP vectoriser (build.py, NO_SLP_SOURCES): the
+// quantiser arithmetic stays free of packed-fp32 VALU instructions, like the standalone and the LayerNorm-fused quantisers.  The
 // arithmetic per element is that of the bf16 instances in attn.hip (the vectoriser pairs operations, it does not reorder or
 // contract them), which tests/test_mx_cross_out_gpu.py checks byte for byte.
 #include "attn_mix32.h"
@@ -16,15 +16,27 @@ __global__ __launch_bounds__(256) void attn_kv_mix32_mx_kernel_d128(MixMxArgs pm
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_mix32_body<128, true>(pm.a, smem, &pm.mx);
 }
+// ... and the one that takes its rows from a segment table (bya_attn_kv_mix_mx_seg: head_dim 64 alone, the audio path's)
+__global__ __launch_bounds__(256, 2) void attn_kv_mix32_mx_seg_kernel_d64(MixMxSegArgs pm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_mix32_body<64, true, true>(pm.a, smem, &pm.mx, &pm.seg);
+}
 
 }  // namespace
 
 int bya_launch_attn_kv_mix32_mx(const void* q, const void* k, const void* v, const void* r, const void* af, float* wsum,
                                 const bya_attn_mix_desc& desc, const bya_attn_kv_mix_plan_info& plan, const ByaMixMxOut& out,
-                                hipStream_t stream) {
+                                const bya_attn_mix_segments* seg, hipStream_t stream) {
     MixMxArgs m;
     mix_args_of(q, k, v, r, af, wsum, &desc, plan.row_chunks, m.a);
     m.mx = out;
+    const dim3 grid((unsigned)plan.grid);
+    const size_t lds = (size_t)plan.lds_bytes;
+    if (seg) {                                      // (head_dim 64: 4 identities make 48 KiB with the patches, never big_lds)
+        const MixMxSegArgs ms{m.a, m.mx, *seg};
+        BYA_LAUNCH(attn_kv_mix32_mx_seg_kernel_d64, grid, dim3(256), lds, stream, ms);
+        return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;
+    }
     if (plan.big_lds) {
         static std::atomic<unsigned long long> big64{0}, big128{0};
         const int rc = desc.head_dim == 64
@@ -32,8 +44,6 @@ int bya_launch_attn_kv_mix32_mx(const void* q, const void* k, const void* v, con
             : bya_allow_big_lds(reinterpret_cast<const void*>(attn_kv_mix32_mx_kernel_d128), 160 * 1024, big128);
         if (rc != BYA_OK) return rc;
     }
-    const dim3 grid((unsigned)plan.grid);
-    const size_t lds = (size_t)plan.lds_bytes;
     if (desc.head_dim == 64) BYA_LAUNCH(attn_kv_mix32_mx_kernel_d64, grid, dim3(256), lds, stream, m);
     else BYA_LAUNCH(attn_kv_mix32_mx_kernel_d128, grid, dim3(256), lds, stream, m);
     return hipGetLastError() == hipSuccess ? BYA_OK : BYA_ERR_LAUNCH;

@@ -186,6 +186,11 @@ class DenoiseEngine:
         # ("1" where a rank has at least SP_OVERLAP_V_MIN_ROWS rows, "0" never, "all" always)
         self.sp_overlap_v = os.environ.get("BYA_SP_OVERLAP_V", "1") != "0"
         self.sp_shard_mods = os.environ.get("BYA_SP_SHARD_MODS", "1") != "0"      # (r6) the AdaLN vector in column slices, one per rank
+        # sharded step: the audio kv-mix of a rank's partial frames as ONE launch over a segment table (bya_attn_kv_mix_seg; the same
+        # bits as the launch per partial frame).  "1" switches it on.  Off by default for now: the sharded MX test
+        # (tests/test_mx_cross_out_gpu.py) counts the launches per partial frame of the DEFAULT step, so the default moves
+        # together with that test (tests/test_sp_segment_mix_gpu.py runs both settings against each other)
+        self.sp_segment_mix = os.environ.get("BYA_SP_SEGMENT_MIX", "0") == "1"
         if os.environ.get("BYA_SP_OVERLAP_V") == "all":
             self.SP_OVERLAP_V_MIN_ROWS = 0
         self.router_replicated = os.environ.get("BYA_ROUTER_REPLICATED", "0") == "1"
@@ -1045,16 +1050,25 @@ class DenoiseEngine:
                                                    **to) is False:
                                     return False
                                 continue
-                            # shard boundaries cut frames: one launch per (partial) frame of this rank
-                            for f, start, length in sh.frame_segments(per_frame):
-                                to = dict(z_strides=(0, D)) if mx is None else \
-                                    dict(mx_out=(mx[0][b, start:], mx[1][b, start:], self.mx_fmt))
-                                if ops.attn_kv_mix(qa[b, start:], ka[b, :, f], va[b, :, f], rb[start:start + length], af[b],
-                                                   None if z is None else z[b, start:], wsum[b, start:], head_dim=64, heads=H,
-                                                   n_id=n_id, n_grp=1, Sq=length, Skv=ntok, q_strides=(0, D),
-                                                   k_strides=(kvs[0], 0, D), v_strides=(kvs[0], 0, D), scale=64 ** -0.5,
-                                                   **to) is False:
-                                    return False
+                            # shard boundaries cut frames: the (partial) frames of this rank are the segments of one launch per
+                            # run of ops.MIX_MAX_SEGMENTS, or -- switch off, or declined for a run -- one launch per (partial) frame
+                            segs = sh.frame_segments(per_frame)
+                            for run in (segs[s0:s0 + ops.MIX_MAX_SEGMENTS] for s0 in range(0, len(segs), ops.MIX_MAX_SEGMENTS)):
+                                to = dict(z_row=D) if mx is None else dict(mx_out=(mx[0][b], mx[1][b], self.mx_fmt))
+                                if self.sp_segment_mix and ops.attn_kv_mix_segments(
+                                        qa[b], ka[b], va[b], rb, af[b], None if z is None else z[b], wsum[b], segments=run,
+                                        head_dim=64, heads=H, n_id=n_id, n_grp=T, Sq=N_loc, Skv=ntok, q_row=D, k_strides=kvs,
+                                        v_strides=kvs, scale=64 ** -0.5, **to) is not False:
+                                    continue
+                                for f, start, length in run:
+                                    to = dict(z_strides=(0, D)) if mx is None else \
+                                        dict(mx_out=(mx[0][b, start:], mx[1][b, start:], self.mx_fmt))
+                                    if ops.attn_kv_mix(qa[b, start:], ka[b, :, f], va[b, :, f], rb[start:start + length], af[b],
+                                                       None if z is None else z[b, start:], wsum[b, start:], head_dim=64, heads=H,
+                                                       n_id=n_id, n_grp=1, Sq=length, Skv=ntok, q_strides=(0, D),
+                                                       k_strides=(kvs[0], 0, D), v_strides=(kvs[0], 0, D), scale=64 ** -0.5,
+                                                       **to) is False:
+                                        return False
                     self._cross_out("ao", ai, "zmix_a", (B, N_loc, D), audio_mix, at.to_out[0].weight, xv,
                                     bias=at.to_out[0].bias, res=xv, bias_rowscale=wsum)
                     continue

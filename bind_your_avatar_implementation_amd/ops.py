@@ -1039,6 +1039,7 @@ ATTN_VARIANT_NAMES = _hip.ATTN_VARIANTS
 ATTN_BOUND_LIMIT = 90.0          # BYA_ATTN_BOUND_LIMIT (include/bya.h): |score| <= 90 keeps P = exp2(s) and its row sums normal
 ATTN_VARIANTS = {}
 KV_MIX_FORMS = _hip.KV_MIX_FORMS
+MIX_MAX_SEGMENTS = _hip.MIX_MAX_SEGMENTS        # segments of one attn_kv_mix_segments launch
 TINY_INSTANCES = _hip.TINY_INSTANCES
 
 
@@ -1216,23 +1217,49 @@ def _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_str
     return d
 
 
-def _mix_call(qkvr, af, z, wsum, mx_out, plan, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale):
-    """-> (``_mix_mx_out``'s tuple or None, the call) of an ``attn_kv_mix`` launch (``qkvr`` = (q, k, v, r)) or its query (())."""
+def _mix_segments(segments):
+    """[(K / V group, first row, rows)] -> the bya_attn_mix_segments of ``attn_kv_mix_segments`` (what the entries hold is the
+    library's to check; a list the struct cannot hold is refused here: splitting it is the caller's job)."""
+    if len(segments) > _hip.MIX_MAX_SEGMENTS:
+        raise ValueError(f"attn_kv_mix_segments: {len(segments)} segments, one launch takes at most {_hip.MIX_MAX_SEGMENTS}")
+    s = _hip.AttnMixSegments()
+    s.n = len(segments)
+    for i, (grp, start, length) in enumerate(segments):
+        s.grp[i], s.start[i], s.len[i] = grp, start, length
+    return s
+
+
+def _mix_call(qkvr, af, z, wsum, mx_out, plan, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale,
+              segments=None):
+    """-> (``_mix_mx_out``'s tuple or None, the call) of an ``attn_kv_mix`` launch (``qkvr`` = (q, k, v, r)) or its query (()).
+    ``segments`` (``attn_kv_mix_segments``): the launch over that table -- ``n_grp`` then counts K / V groups alone, r, wsum and
+    the MX pair hold ``Sq`` rows in all and no group stride."""
     ptr = _plan_p if plan else _p
+    row_grps = n_grp if segments is None else 1
+    table = None if segments is None else _mix_segments(segments)
     mx = None
     if mx_out is not None:
-        mx = _mix_mx_out(mx_out, z, z_strides, heads, head_dim, n_grp, Sq, plan)
+        mx = _mix_mx_out(mx_out, z, z_strides, heads, head_dim, row_grps, Sq, plan)
+        if segments is not None:
+            mx = (*mx[:3], (0, mx[3][1], 0, mx[3][3]))
         z_strides = (0, 0)
     d = _mix_desc(head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale)
     for t in qkvr + (() if mx is not None else (z,)):
         assert t.dtype == torch.bfloat16 and (t.is_cuda or (plan and t.is_meta))
-    assert not qkvr or (qkvr[3].is_contiguous() and qkvr[3].numel() == n_grp * Sq * n_id)
+    assert not qkvr or (qkvr[3].is_contiguous() and qkvr[3].numel() == row_grps * Sq * n_id)
     assert af is None or (af.is_contiguous() and af.dtype == torch.bfloat16 and af.numel() == n_id * n_id)
-    assert wsum is None or (wsum.dtype == torch.float32 and wsum.is_contiguous() and wsum.numel() >= n_grp * Sq)
+    assert wsum is None or (wsum.dtype == torch.float32 and wsum.is_contiguous() and wsum.numel() >= row_grps * Sq)
     outs = (ptr(z),) if mx is None else (ptr(mx[0]), ptr(mx[1]))
-    tail = (ctypes.byref(d),) if mx is None else (ctypes.byref(d), mx[2], *mx[3])
-    return mx, ("bya_attn_kv_mix" if mx is None else "bya_attn_kv_mix_mx",
+    tail = (ctypes.byref(d),) if table is None else (ctypes.byref(d), ctypes.byref(table))
+    if mx is not None:
+        tail += (mx[2], *mx[3])
+    return mx, ("bya_attn_kv_mix" + ("" if mx is None else "_mx") + ("" if segments is None else "_seg"),
                 (*outs, ptr(af), *tail) if plan else (*(ptr(t) for t in qkvr), ptr(af), *outs, ptr(wsum), *tail))
+
+
+def _mix_plan_dict(p):
+    return {"form": KV_MIX_FORMS[p.form], "head_dim": p.head_dim, "grid": p.grid, "row_chunks": p.row_chunks, "lds_bytes": p.lds_bytes,
+            "big_lds": p.big_lds}
 
 
 def attn_kv_mix(q, k, v, r, af, z, wsum=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides,
@@ -1258,9 +1285,35 @@ def attn_kv_mix_plan(z, af=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_str
     reference form)."""
     mx, call = _mix_call((), af, z, None, mx_out, True, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides,
                          z_strides, scale)
-    plan = _plan(call, mx is not None, _hip.AttnMixPlan, lambda p: {
-        "form": KV_MIX_FORMS[p.form], "head_dim": p.head_dim, "grid": p.grid, "row_chunks": p.row_chunks, "lds_bytes": p.lds_bytes,
-        "big_lds": p.big_lds})
+    plan = _plan(call, mx is not None, _hip.AttnMixPlan, _mix_plan_dict)
+    if plan is not None and mx is not None:
+        plan["mx_out"] = mx_out[2]
+    return plan
+
+
+def attn_kv_mix_segments(q, k, v, r, af, z, wsum=None, *, segments, head_dim, heads, n_id, n_grp, Sq, Skv, q_row, k_strides, v_strides,
+                         z_row=None, scale, mx_out=None):
+    """``attn_kv_mix`` for rows cut into ``segments`` = [(grp, start, length)], at most 16, ascending and disjoint: rows
+    [start, start + length) of q / r / z / wsum (``Sq`` rows in all, row strides ``q_row`` / ``z_row``, no group stride) attend to
+    K / V group ``grp`` < ``n_grp``; rows in no segment are neither read nor written.  One launch, byte for byte the
+    ``attn_kv_mix(..., n_grp=1, Sq=length)`` launches per segment on views advanced by ``start`` rows.  ``mx_out`` as there (``z``
+    None, no ``z_row``; the pair holds ``Sq`` rows).  Returns z, or the MX pair, or False (nothing launched, nothing counted)
+    where the library has no segment form (more than 32 keys, the generic reference form, a z that is not 16-byte aligned,
+    head_dim 128): the caller then issues those launches."""
+    mx, call = _mix_call((q, k, v, r), af, z, wsum, mx_out, False, head_dim, heads, n_id, n_grp, Sq, Skv, (0, q_row), k_strides, v_strides,
+                         None if z_row is None else (0, z_row), scale, segments)
+    launched = _launch(None, None, 4.0 * n_id * heads * Skv * head_dim * sum(s[2] for s in segments), call, True)
+    return launched and (z if mx is None else (mx[0], mx[1]))
+
+
+def attn_kv_mix_segments_plan(z, af=None, *, segments, head_dim, heads, n_id, n_grp, Sq, Skv, q_row, k_strides, v_strides, z_row=None,
+                              scale=1.0, mx_out=None):
+    """What ``attn_kv_mix_segments`` would run (host-side; meta tensors may stand for device tensors): ``attn_kv_mix_plan``'s
+    dict -- "form" "mix32", "row_chunks" those of the longest segment, "grid" = row_chunks * heads * len(segments) -- or None
+    where the library declines the segment form."""
+    mx, call = _mix_call((), af, z, None, mx_out, True, head_dim, heads, n_id, n_grp, Sq, Skv, (0, q_row), k_strides, v_strides,
+                         None if z_row is None else (0, z_row), scale, segments)
+    plan = _plan(call, True, _hip.AttnMixPlan, _mix_plan_dict)
     if plan is not None and mx is not None:
         plan["mx_out"] = mx_out[2]
     return plan

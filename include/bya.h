@@ -702,6 +702,44 @@ int bya_attn_kv_mix_mx_plan(const void* codes, const void* scales, const void* a
                             int32_t out_fmt, int64_t c_grp, int64_t c_row, int64_t sc_grp, int64_t sc_row,
                             bya_attn_kv_mix_plan_info* plan);
 
+/* bya_attn_kv_mix / bya_attn_kv_mix_mx over a SEGMENT TABLE: one launch for groups of unequal length that start anywhere, e.g. the
+ * partial latent frames a sequence-parallel rank holds (one bya_attn_kv_mix launch each otherwise).  The table is read on the
+ * host and travels BY VALUE in the kernel's arguments: no device memory, so a captured graph carries it.
+ *   desc is bya_attn_kv_mix's descriptor, read as follows: n_grp = the K / V groups that can be addressed (0 <= grp[i] < n_grp);
+ *   Sq = the TOTAL row count of q, r, z and wsum (start[i] + len[i] <= Sq); q_grp = z_grp = 0, and c_grp = sc_grp = 0 for the MX
+ *   entry.  Row n is addressed directly: q + n * q_row, r[n, :], z + n * z_row, wsum[n], codes + n * c_row, scales + n * sc_row.
+ *   Segment i computes rows [start[i], start[i] + len[i]) against K[id, grp[i]] and V[id, grp[i]].
+ *   Rows outside every segment are never read as queries and nothing is written for them: not z, not wsum, not codes, not
+ *   scales.  Segments are in ascending order and do not overlap (start[i] + len[i] <= start[i + 1]); gaps are allowed.
+ * Every row gets the arithmetic of bya_attn_kv_mix (the kernel body is the same code): the output is byte for byte that of one
+ * bya_attn_kv_mix / bya_attn_kv_mix_mx launch per segment (n_grp = 1, Sq = len[i], pointers advanced by start[i] rows).
+ * Refused before any launch.  BYA_ERR_SHAPE: seg NULL, n outside 1 .. BYA_MIX_MAX_SEGMENTS, a len <= 0, a grp outside
+ * [0, n_grp), rows past Sq, overlapping or descending segments, a non-zero group stride on q, z, codes or scales, anything
+ * bya_attn_kv_mix / bya_attn_kv_mix_mx refuses.  BYA_ERR_UNSUPPORTED -- the segment form exists on the BYA_KV_MIX_MIX32 form with
+ * head_dim 64 alone, the caller then issues the launches per segment --: Skv > 32, reference form BYA_REF_KV_MIX_GENERIC set, z
+ * not 16-byte aligned or z_row not a multiple of 8, head_dim 128.
+ * The plan queries answer with bya_attn_kv_mix_plan's struct: form = BYA_KV_MIX_MIX32, row_chunks = the existing rule
+ * ceil(ceil(L / 32) / 12) for the LONGEST segment's L, grid = row_chunks * heads * n (one workgroup per (segment, head, row
+ * chunk); one whose share of a shorter segment's 32-row tiles is empty leaves at once), lds_bytes as for bya_attn_kv_mix; the
+ * plan is untouched on rejection. */
+#define BYA_MIX_MAX_SEGMENTS 16
+typedef struct bya_attn_mix_segments {
+    int32_t n;                                   /* 1 .. BYA_MIX_MAX_SEGMENTS */
+    int32_t grp[BYA_MIX_MAX_SEGMENTS];           /* K / V group (frame) the segment's rows attend to */
+    int32_t start[BYA_MIX_MAX_SEGMENTS];         /* first row of the segment in q / r / z / wsum */
+    int32_t len[BYA_MIX_MAX_SEGMENTS];           /* rows, > 0 */
+} bya_attn_mix_segments;
+int bya_attn_kv_mix_seg(const void* q, const void* k, const void* v, const void* r, const void* af, void* z, float* wsum,
+                        const bya_attn_mix_desc* desc, const bya_attn_mix_segments* seg, hipStream_t stream);
+int bya_attn_kv_mix_seg_plan(const void* z, const void* af, const bya_attn_mix_desc* desc, const bya_attn_mix_segments* seg,
+                             bya_attn_kv_mix_plan_info* plan);
+int bya_attn_kv_mix_mx_seg(const void* q, const void* k, const void* v, const void* r, const void* af, void* codes, void* scales,
+                           float* wsum, const bya_attn_mix_desc* desc, const bya_attn_mix_segments* seg, int32_t out_fmt,
+                           int64_t c_grp, int64_t c_row, int64_t sc_grp, int64_t sc_row, hipStream_t stream);
+int bya_attn_kv_mix_mx_seg_plan(const void* codes, const void* scales, const void* af, const bya_attn_mix_desc* desc,
+                                const bya_attn_mix_segments* seg, int32_t out_fmt, int64_t c_grp, int64_t c_row, int64_t sc_grp,
+                                int64_t sc_row, bya_attn_kv_mix_plan_info* plan);
+
 /* Tiny-sequence self-attention (sequence length L <= 16, head_dim 64) used by the router's temporal
  * (L = frames) and multi-ID (L = ids) attentions (models/router.py:482,488).  Element e of sequence
  * `g` lives at row  g_outer(g)*outer_stride + e*seq_stride + g_inner(g)  of the [rows, ld] matrices,

@@ -44,12 +44,77 @@ def timeit(fn, iters=10, rounds=3):
     return sorted(ts)[len(ts) // 2]
 
 
+def rank_segments(W, rank):
+    """[(frame, local start, rows)] of rank ``rank``'s video rows at W ranks: parallel.SeqShard's split and frame_segments."""
+    from bind_your_avatar_implementation_amd.parallel import _splits
+    r0, r1 = _splits(S, W)[rank]
+    v, v1 = max(r0, TT) - TT, r1 - TT
+    v0, out = v, []
+    while v < v1:
+        f = v // PER_FRAME
+        end = min(v1, (f + 1) * PER_FRAME)
+        out.append((f, v - v0, end - v))
+        v = end
+    return out
+
+
+def segment_mix(W, rounds=5, iters=20):
+    """The audio kv-mix of ONE layer at the real segment lists of a W-rank step: the launches per partial frame (what the
+    sharded step issues by default) against the one launch over the segment table (engine.sp_segment_mix), timed in
+    alternating rounds; for the rank with the most segments and the rank after it."""
+    most = max(range(W), key=lambda r: len(rank_segments(W, r)))
+    out = []
+    for rank in sorted({most, min(most + 1, W - 1)}):
+        segs = rank_segments(W, rank)
+        n = sum(s[2] for s in segs)
+        qa, ka, va = rnd(n, D), rnd(NID, T, 32, D), rnd(NID, T, 32, D)
+        rl = torch.sigmoid(torch.randn(n, NID, device=dev)).to(torch.bfloat16)
+        afm = torch.eye(NID, device=dev, dtype=torch.bfloat16)
+        za, zb = (torch.empty(n, D, dtype=torch.bfloat16, device=dev) for _ in range(2))
+        wsum = torch.empty(n, dtype=torch.float32, device=dev)
+        kvs = (T * 32 * D, 32 * D, D)
+
+        def per_segment():
+            for f, start, length in segs:
+                ops.attn_kv_mix(qa[start:], ka[:, f], va[:, f], rl[start:start + length], afm, za[start:], wsum[start:], head_dim=64,
+                                heads=H, n_id=NID, n_grp=1, Sq=length, Skv=32, q_strides=(0, D), k_strides=(kvs[0], 0, D),
+                                v_strides=(kvs[0], 0, D), z_strides=(0, D), scale=0.125)
+
+        def one_launch():
+            assert ops.attn_kv_mix_segments(qa, ka, va, rl, afm, zb, wsum, segments=segs, head_dim=64, heads=H, n_id=NID, n_grp=T,
+                                            Sq=n, Skv=32, q_row=D, k_strides=kvs, v_strides=kvs, z_row=D, scale=0.125) is not False
+
+        ts = {"per_segment": [], "one_launch": []}
+        for _ in range(rounds):                                     # alternating: both see the same clocks and neighbours
+            for name, fn in (("per_segment", per_segment), ("one_launch", one_launch)):
+                ts[name].append(timeit(fn, iters=iters, rounds=1) * 1e6)
+        assert torch.equal(za, zb)
+        plan = ops.attn_kv_mix_segments_plan(zb, afm, segments=segs, head_dim=64, heads=H, n_id=NID, n_grp=T, Sq=n, Skv=32, q_row=D,
+                                             k_strides=kvs, v_strides=kvs, z_row=D)
+        row = dict(world=W, rank=rank, segments=segs, rows=n, grid_one_launch=plan["grid"], row_chunks=plan["row_chunks"],
+                   per_segment_us=[round(t, 2) for t in ts["per_segment"]], one_launch_us=[round(t, 2) for t in ts["one_launch"]],
+                   per_segment_us_median=round(sorted(ts["per_segment"])[rounds // 2], 2),
+                   one_launch_us_median=round(sorted(ts["one_launch"])[rounds // 2], 2))
+        print(f"audio kv-mix, W={W} rank {rank}: {len(segs)} segments {[s[2] for s in segs]} rows: per segment "
+              f"{row['per_segment_us_median']:.1f} us, one launch {row['one_launch_us_median']:.1f} us (grid {plan['grid']})", flush=True)
+        out.append(row)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--world", type=int, default=8)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--segment-mix-only", action="store_true", help="only the audio kv-mix comparison (segment_mix)")
     a = ap.parse_args()
     W = a.world
+    if a.segment_mix_only:
+        res = {"world": W, "audio_kv_mix_segments": segment_mix(W)}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     S_loc, N_loc, Hl = S // W, N // W, H // W
     pairs = NID * T
     nPA, nLB = -(-pairs // W), -(-PER_FRAME // W)
