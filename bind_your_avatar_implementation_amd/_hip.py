@@ -122,6 +122,8 @@ SIGNATURES = {
     "bya_gemm_qkv_norm_rope": [_vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _vp],
     "bya_gemm_bf16_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(GemmPlan)],
     "bya_gemm_qkv_norm_rope_plan": [_vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _c.POINTER(GemmPlan)],
+    "bya_gemm_qkv_norm_rope_stats": [_vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _vp, _i32, _vp],
+    "bya_gemm_qkv_norm_rope_stats_plan": [_vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _vp, _i32, _c.POINTER(GemmPlan)],
     "bya_set_gemm_workspace": [_vp, _i64],
     "bya_gemm_workspace_bytes": [_c.POINTER(_i64)],
     "bya_gemm_workspace_status": [_c.POINTER(_i32), _vp],
@@ -131,6 +133,9 @@ SIGNATURES = {
     "bya_gemm_fp8_qkv_norm_rope": [_vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _vp],
     "bya_gemm_fp8_qkv_norm_rope_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc),
                                         _c.POINTER(GemmPlan)],
+    "bya_gemm_fp8_qkv_norm_rope_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _vp, _i32, _vp],
+    "bya_gemm_fp8_qkv_norm_rope_stats_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _vp, _i32,
+                                              _c.POINTER(GemmPlan)],
     "bya_layernorm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
                           _f32, _vp],
     "bya_quantize_mx": [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp],
@@ -151,6 +156,9 @@ SIGNATURES = {
                                      _vp],
     "bya_gemm_mx_qkv_norm_rope_on_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc),
                                           _i32, _c.POINTER(GemmPlan)],
+    "bya_gemm_mx_qkv_norm_rope_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _i32, _vp, _i32, _vp],
+    "bya_gemm_mx_qkv_norm_rope_stats_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _c.POINTER(GemmDesc), _c.POINTER(QkNormDesc), _i32, _vp, _i32,
+                                             _c.POINTER(GemmPlan)],
     "bya_gemm_mx_call": [_c.POINTER(MxGemmCall), _c.POINTER(GemmDesc), _vp],
     "bya_gemm_mx_call_plan": [_c.POINTER(MxGemmCall), _c.POINTER(GemmDesc), _c.POINTER(GemmPlan)],
     "bya_linear_small_m": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],

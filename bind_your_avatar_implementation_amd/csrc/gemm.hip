@@ -488,10 +488,12 @@ int bf16_args(const void* A, const void* W, const void* bias, const void* C, con
 
 // bya_gemm_qkv_norm_rope's arguments -> GemmArgs; BYA_ERR_UNSUPPORTED: not this kernel's shape (the caller keeps two launches)
 int qkn_args(const void* A, const void* W, const void* bias, const void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n,
-             GemmArgs* out) {
+             const QknStats& st, GemmArgs* out) {
     if (!A || !W || !C) return BYA_ERR_SHAPE;
     const int rc = qkn_norm_desc_check(d, n);
     if (rc != BYA_OK) return rc;
+    const int rcs = qkn_stats_check(st);
+    if (rcs != BYA_OK) return rcs;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0 || d->K % BK != 0) return BYA_ERR_SHAPE;
     // N = 3 width: the packed q | k | v projection; N = 2 width (r6): q | k alone -- the sharded step computes v in a launch of
     // its own first and pushes it to the peers underneath this one
@@ -504,7 +506,7 @@ int qkn_args(const void* A, const void* W, const void* bias, const void* C, cons
     out->ldres = 0; out->res_bs = 0; out->gate_bs = 0; out->gate_split = 0;          // no residual, no gates: not read from the descriptor
     qkn_fill_norm(n, out);
     if (!v4_eligible(*out) || !gemm_rows_reachable(*out, out->M)) return BYA_ERR_UNSUPPORTED;
-    return BYA_OK;
+    return qkn_stats_args(d, n, st, out);    // (both kernels of this entry point record the statistics: every plan path does)
 }
 
 // bya_gemm_bf16 (plan == nullptr) and bya_gemm_bf16_plan: one body, so the query answers what the launch does
@@ -522,9 +524,9 @@ int bf16_gemm(const void* A, const void* W, const void* bias, const void* C, con
 // written once (include/bya.h).  Only the persistent one-wave-per-SIMD kernels have that epilogue: anything they do not take
 // is BYA_ERR_UNSUPPORTED and the caller keeps bya_gemm_bf16 + bya_qknorm_rope.  Launch (plan == nullptr) and plan query.
 int qkn_gemm(const void* A, const void* W, const void* bias, const void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n,
-             hipStream_t stream, bya_gemm_plan* plan) {
+             const QknStats& st, hipStream_t stream, bya_gemm_plan* plan) {
     GemmArgs a;
-    const int rc0 = qkn_args(A, W, bias, C, d, n, &a);
+    const int rc0 = qkn_args(A, W, bias, C, d, n, st, &a);
     if (rc0 != BYA_OK) return rc0;
     // the row plan (0: 256-row tiles, 1: 128-row tiles, 2: rows [0, m0) on 256-row tiles, the rest on 128-row tiles)
     int m0 = 0;
@@ -557,13 +559,27 @@ extern "C" int bya_gemm_bf16_plan(const void* A, const void* W, const void* bias
 
 extern "C" int bya_gemm_qkv_norm_rope(const void* A, const void* W, const void* bias, void* C, const bya_gemm_desc* d,
                                       const bya_qknorm_desc* n, hipStream_t stream) {
-    return qkn_gemm(A, W, bias, C, d, n, stream, nullptr);
+    return qkn_gemm(A, W, bias, C, d, n, QknStats{}, stream, nullptr);
 }
 
 extern "C" int bya_gemm_qkv_norm_rope_plan(const void* A, const void* W, const void* bias, const void* C, const bya_gemm_desc* d,
                                            const bya_qknorm_desc* n, bya_gemm_plan* p) {
     if (!p) return BYA_ERR_SHAPE;
-    return qkn_gemm(A, W, bias, C, d, n, nullptr, p);
+    return qkn_gemm(A, W, bias, C, d, n, QknStats{}, nullptr, p);
+}
+
+// ... that also records bya_qknorm_rope's score-bound statistics (include/bya.h): the STATS instances of the same kernels, on
+// every plan path
+extern "C" int bya_gemm_qkv_norm_rope_stats(const void* A, const void* W, const void* bias, void* C, const bya_gemm_desc* d,
+                                            const bya_qknorm_desc* n, float* stats, int32_t stats_slots, hipStream_t stream) {
+    return qkn_gemm(A, W, bias, C, d, n, QknStats{stats, stats_slots}, stream, nullptr);
+}
+
+extern "C" int bya_gemm_qkv_norm_rope_stats_plan(const void* A, const void* W, const void* bias, const void* C,
+                                                 const bya_gemm_desc* d, const bya_qknorm_desc* n, const float* stats,
+                                                 int32_t stats_slots, bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    return qkn_gemm(A, W, bias, C, d, n, QknStats{const_cast<float*>(stats), stats_slots}, nullptr, p);
 }
 
 namespace {

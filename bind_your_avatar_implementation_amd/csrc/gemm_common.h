@@ -1,6 +1,7 @@
 // Shared by the GEMM translation units (gemm.hip, gemm_v4 / v5 / v6.hip, gemm_fp8.hip, gemm_fp8_v4.hip, gemm_fp8_v4_qkn.hip,
-// gemm_mx.hip, gemm_mx_v4.hip) and the implicit-GEMM convolution (vae.hip): argument block, fused epilogue, LDS read helper, and
-// the host side every GEMM entry point shares -- descriptor -> GemmArgs, the epilogue-side checks, the row cut, the plan fill.
+// gemm_fp8_v4_qkn_stats.hip, gemm_mx.hip, gemm_mx_v4.hip) and the implicit-GEMM convolution (vae.hip): argument block, fused
+// epilogue, LDS read helper, and the host side every GEMM entry point shares -- descriptor -> GemmArgs, the epilogue-side
+// checks, the row cut, the plan fill.
 #pragma once
 #include "bya_common.h"
 #include "../../include/bya.h"
@@ -40,6 +41,11 @@ struct GemmArgs {
     int conv_cpg_log2 = -1;            // log2(C / 64); < 0: plain GEMM
     int conv_Hp = 0, conv_Wp = 0, conv_H = 0, conv_W = 0, conv_To = 0;
     long long conv_a_bytes = 0;        // bytes of the padded input from A on (reads past it return zeros)
+    // the q/k-norm epilogue's score-bound statistics (the *_stats entry points; STATS instances only; at the end, so that every
+    // other field keeps its place in the kernels' argument block): fp32 [qkn_stats_slots][2][qkn_stats_nbh], entry
+    // z * (qkn_width / 64) + head of the tensor (qkn_stats_args)
+    float* qkn_stats = nullptr;
+    int qkn_stats_slots = 0, qkn_stats_nbh = 0;
 };
 
 constexpr size_t GEMM_WS_COUNTER_BYTES = 4096, GEMM_WS_SLAB_BYTES = 256 * 256 * 4, GEMM_WS_SLABS = 256;
@@ -300,6 +306,27 @@ inline int qkn_norm_desc_check(const bya_gemm_desc* d, const bya_qknorm_desc* n)
     return BYA_OK;
 }
 
+// The score-bound statistics a fused q/k-norm launch is asked to record (the *_stats entry points of include/bya.h; the plain
+// entry points pass none): bya_qknorm_rope's table and its slot count.
+struct QknStats { float* stats = nullptr; int32_t slots = 0; };
+// ... its own checks, before anything else looks at the launch: the slot count (BYA_ERR_SHAPE), the table's 4 bytes (BYA_ERR_ALIGN)
+inline int qkn_stats_check(const QknStats& s) {
+    if (s.stats && (s.slots < 1 || s.slots > 64)) return BYA_ERR_SHAPE;
+    return ((uintptr_t)s.stats & 3) ? BYA_ERR_ALIGN : BYA_OK;
+}
+// QknStats -> GemmArgs::qkn_stats* (behind qkn_fill_norm and the entry point's own checks).  The table's entry of a head is the one the two-launch path's bya_qknorm_rope call raises:
+// dense (n_split == width) z * heads + head; column blocks of whole heads with one batch entry (the head-parallel sharded
+// step: its bya_qknorm_rope runs over [blocks, rows, n_split] with heads-per-block heads) the global head -- the same formula
+// with z = 0.  Anything else is not a launch whose table this epilogue knows: BYA_ERR_UNSUPPORTED.
+inline int qkn_stats_args(const bya_gemm_desc* d, const bya_qknorm_desc* n, const QknStats& s, GemmArgs* out) {
+    if (!s.stats) return BYA_OK;
+    const bool dense = d->n_split == n->width;
+    const bool blocks = d->n_split > 0 && d->n_split < n->width && n->width % d->n_split == 0 && d->n_split % 64 == 0 && d->batch == 1;
+    if (!dense && !blocks) return BYA_ERR_UNSUPPORTED;
+    out->qkn_stats = s.stats; out->qkn_stats_slots = s.slots; out->qkn_stats_nbh = d->batch * (n->width / 64);
+    return BYA_OK;
+}
+
 // bya_qknorm_desc -> GemmArgs::qkn_* (k_scale 0 means 1)
 inline void qkn_fill_norm(const bya_qknorm_desc* n, GemmArgs* out) {
     GemmArgs& a = *out;
@@ -308,7 +335,7 @@ inline void qkn_fill_norm(const bya_qknorm_desc* n, GemmArgs* out) {
     a.qkn_eps = n->eps; a.qkn_kscale = n->k_scale == 0.0f ? 1.0f : n->k_scale;
 }
 
-inline int qkn_head_args(const void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n, GemmArgs* out) {
+inline int qkn_head_args(const void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n, const QknStats& s, GemmArgs* out) {
     if ((d->N != 3 * n->width && d->N != 2 * n->width) || n->width % 64 != 0 || d->n_split <= 0 || d->act != 0 ||
         d->bias_rowscale || (d->alpha != 0.0f && d->alpha != 1.0f))
         return BYA_ERR_UNSUPPORTED;
@@ -321,7 +348,7 @@ inline int qkn_head_args(const void* C, const bya_gemm_desc* d, const bya_qknorm
     qkn_fill_norm(n, out);
     // one launch: its rows and its rotary rows within the 2 GiB reach of the buffer descriptors
     if (!gemm_rows_reachable(a, a.M) || ((long long)a.M - a.qkn_text_rows) * 256 >= 0x7fffffffLL) return BYA_ERR_UNSUPPORTED;
-    return BYA_OK;
+    return qkn_stats_args(d, n, s, out);   // (which kernel path records them: the entry point, once it knows the path)
 }
 
 // Persistent kernels: group-M width of the tile order, in 256-row tiles, by shape: a long K sweep wants few row tiles per group

@@ -18,6 +18,8 @@ bool bya_gemm256p_fp8_eligible(const void* args);                               
 int bya_launch_gemm256p_fp8(const void* args, const float* sa, const float* sw, int batch, int gm, hipStream_t s);
 // ... its q/k-norm instance (gemm_fp8_v4_qkn.hip; GemmArgs::qkn_* filled)
 int bya_launch_gemm256p_fp8_qkn(const void* args, const float* sa, const float* sw, int batch, int gm, hipStream_t s);
+// ... and that one with the score-bound statistics (gemm_fp8_v4_qkn_stats.hip; GemmArgs::qkn_stats* filled as well)
+int bya_launch_gemm256p_fp8_qkn_stats(const void* args, const float* sa, const float* sw, int batch, int gm, hipStream_t s);
 
 namespace {
 
@@ -141,27 +143,33 @@ namespace {
 // bya_gemm_fp8_qkv_norm_rope's arguments -> GemmArgs; BYA_ERR_UNSUPPORTED: not this epilogue's shape (the caller keeps
 // bya_gemm_fp8 + bya_qknorm_rope); malformed arguments: the errors of fp8_args and of the norm descriptor (gemm_common.h)
 int fp8_qkn_args(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias, const void* C,
-                 const bya_gemm_desc* d, const bya_qknorm_desc* n, GemmArgs* out) {
+                 const bya_gemm_desc* d, const bya_qknorm_desc* n, const QknStats& st, GemmArgs* out) {
     const int rc0 = qkn_norm_desc_check(d, n);
     if (rc0 != BYA_OK) return rc0;
+    const int rcs = qkn_stats_check(st);
+    if (rcs != BYA_OK) return rcs;
     const int rc = fp8_args(A8, a_scale, W8, w_scale, bias, C, nullptr, nullptr, nullptr, d, out);
     if (rc != BYA_OK) return rc;
     // there is no residual argument: a descriptor that describes one is not this entry point's launch
     if (d->ldres != 0 || d->res_batch_stride != 0) return BYA_ERR_UNSUPPORTED;
-    return qkn_head_args(C, d, n, out);
+    return qkn_head_args(C, d, n, st, out);
 }
 
 // the launch (plan == nullptr) and its plan query: one body, so the query answers what the launch does
 int fp8_qkn(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias, const void* C,
-            const bya_gemm_desc* d, const bya_qknorm_desc* n, hipStream_t stream, bya_gemm_plan* plan) {
+            const bya_gemm_desc* d, const bya_qknorm_desc* n, const QknStats& st, hipStream_t stream, bya_gemm_plan* plan) {
     GemmArgs a;
-    const int rc = fp8_qkn_args(A8, a_scale, W8, w_scale, bias, C, d, n, &a);
+    const int rc = fp8_qkn_args(A8, a_scale, W8, w_scale, bias, C, d, n, st, &a);
     if (rc != BYA_OK) return rc;
     // bya_gemm_fp8's own choice for this descriptor (one row chunk: qkn_head_args): the two kernels differ in last bits, so
     // following it is what keeps fused == two launches in every option state
     const int path = fp8_path(a, d->batch, a);
+    // the score-bound statistics (bya_gemm_fp8_qkv_norm_rope_stats) are the persistent kernel's: the tiled one declines them
+    if (a.qkn_stats && path != BYA_GEMM_PATH_P256) return BYA_ERR_UNSUPPORTED;
     if (plan) return gemm_plan_whole(plan, path, 1);
-    if (path == BYA_GEMM_PATH_P256) return bya_launch_gemm256p_fp8_qkn(&a, a_scale, w_scale, d->batch, FP8_P256_GROUP_M, stream);
+    if (path == BYA_GEMM_PATH_P256)
+        return a.qkn_stats ? bya_launch_gemm256p_fp8_qkn_stats(&a, a_scale, w_scale, d->batch, FP8_P256_GROUP_M, stream)
+                           : bya_launch_gemm256p_fp8_qkn(&a, a_scale, w_scale, d->batch, FP8_P256_GROUP_M, stream);
     return launch_fp8<128, 128, 2, 2, true>(a, a_scale, w_scale, d->batch, stream);
 }
 }  // namespace
@@ -172,12 +180,28 @@ int fp8_qkn(const void* A8, const float* a_scale, const void* W8, const float* w
 extern "C" int bya_gemm_fp8_qkv_norm_rope(const void* A8, const float* a_scale, const void* W8, const float* w_scale,
                                           const void* bias, void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n,
                                           hipStream_t stream) {
-    return fp8_qkn(A8, a_scale, W8, w_scale, bias, C, d, n, stream, nullptr);
+    return fp8_qkn(A8, a_scale, W8, w_scale, bias, C, d, n, QknStats{}, stream, nullptr);
 }
 
 extern "C" int bya_gemm_fp8_qkv_norm_rope_plan(const void* A8, const float* a_scale, const void* W8, const float* w_scale,
                                                const void* bias, const void* C, const bya_gemm_desc* d,
                                                const bya_qknorm_desc* n, bya_gemm_plan* p) {
     if (!p) return BYA_ERR_SHAPE;
-    return fp8_qkn(A8, a_scale, W8, w_scale, bias, C, d, n, nullptr, p);
+    return fp8_qkn(A8, a_scale, W8, w_scale, bias, C, d, n, QknStats{}, nullptr, p);
+}
+
+// ... that also records bya_qknorm_rope's score-bound statistics (include/bya.h): on path P256 (gemm256p_fp8_qkn_stats_kernel);
+// where the launch would take the tiled kernel a table is answered BYA_ERR_UNSUPPORTED
+extern "C" int bya_gemm_fp8_qkv_norm_rope_stats(const void* A8, const float* a_scale, const void* W8, const float* w_scale,
+                                                const void* bias, void* C, const bya_gemm_desc* d, const bya_qknorm_desc* n,
+                                                float* stats, int32_t stats_slots, hipStream_t stream) {
+    return fp8_qkn(A8, a_scale, W8, w_scale, bias, C, d, n, QknStats{stats, stats_slots}, stream, nullptr);
+}
+
+extern "C" int bya_gemm_fp8_qkv_norm_rope_stats_plan(const void* A8, const float* a_scale, const void* W8, const float* w_scale,
+                                                     const void* bias, const void* C, const bya_gemm_desc* d,
+                                                     const bya_qknorm_desc* n, const float* stats, int32_t stats_slots,
+                                                     bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    return fp8_qkn(A8, a_scale, W8, w_scale, bias, C, d, n, QknStats{const_cast<float*>(stats), stats_slots}, nullptr, p);
 }

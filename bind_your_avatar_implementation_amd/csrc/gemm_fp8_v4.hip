@@ -41,7 +41,9 @@
 #ifndef BYA_F8_QKN
 #define BYA_F8_QKN 0
 #endif
-#if BYA_F8_QKN
+#if BYA_F8_QKN == 2
+#define F8_KERNEL gemm256p_fp8_qkn_stats_kernel
+#elif BYA_F8_QKN
 #define F8_KERNEL gemm256p_fp8_qkn_kernel
 #else
 #define F8_KERNEL gemm256p_fp8_kernel
@@ -646,7 +648,7 @@ __global__ __launch_bounds__(256, 1) void F8_KERNEL(GemmArgs p, const float* __r
 
 #if BYA_F8_QKN
         // bit for bit the epilogue of the #else branch (alpha = 1, no activation) followed by bya_qknorm_rope
-        epilogue_mx_wide8_qkn<2, true>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc, sa, sw);
+        epilogue_mx_wide8_qkn<2, true, BYA_F8_QKN == 2>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc, sa, sw);
 #else
         auto run = [&](auto act_tag) {
             // (wave, lane: the split writer's, unused here -- and naming them would capture them: this kernel then compiles differently)
@@ -679,6 +681,8 @@ bool bya_gemm256p_fp8_eligible(const void* args) {
 }
 
 #define F8_LAUNCH bya_launch_gemm256p_fp8
+#elif BYA_F8_QKN == 2
+#define F8_LAUNCH bya_launch_gemm256p_fp8_qkn_stats
 #else
 // ... with the q/k-norm epilogue: the caller (bya_gemm_fp8_qkv_norm_rope) has filled GemmArgs::qkn_* and checked eligibility
 #define F8_LAUNCH bya_launch_gemm256p_fp8_qkn

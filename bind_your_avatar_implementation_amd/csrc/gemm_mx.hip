@@ -534,14 +534,16 @@ int mx_quant_args(const void* A, const void* a_scales, const void* W, const void
 // bya_gemm_mx_qkv_norm_rope's arguments -> GemmArgs; BYA_ERR_UNSUPPORTED: not this epilogue's shape (the caller keeps
 // bya_gemm_mx_mixed + bya_qknorm_rope); malformed arguments: the errors of qkn_norm_desc_check / qkn_head_args (gemm_common.h) and mx_args
 int mx_qkn_args(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, const void* C,
-                const bya_gemm_desc* d, const bya_qknorm_desc* n, int32_t a_fmt, int32_t w_fmt, GemmArgs* out) {
+                const bya_gemm_desc* d, const bya_qknorm_desc* n, const QknStats& st, int32_t a_fmt, int32_t w_fmt, GemmArgs* out) {
     const int rc0 = qkn_norm_desc_check(d, n);
     if (rc0 != BYA_OK) return rc0;
+    const int rcs = qkn_stats_check(st);
+    if (rcs != BYA_OK) return rcs;
     bya_gemm_desc e = *d;                                // the operand side: bya_gemm_mx_mixed's own checks
     e.ldres = 0; e.res_batch_stride = 0; e.gate_batch_stride = 0; e.gate_split = 0;
     const int rc = mx_args(A, a_scales, W, w_scales, bias, C, nullptr, nullptr, nullptr, &e, a_fmt, w_fmt, out);
     if (rc != BYA_OK) return rc;
-    return qkn_head_args(C, d, n, out);                  // (gemm_common.h: shared with bya_gemm_fp8_qkv_norm_rope)
+    return qkn_head_args(C, d, n, st, out);              // (gemm_common.h: shared with bya_gemm_fp8_qkv_norm_rope)
 }
 
 // Every MX GEMM entry point of this file, launch (plan == nullptr) and plan query: one body, so the query answers what the
@@ -549,14 +551,16 @@ int mx_qkn_args(const void* A, const void* a_scales, const void* W, const void* 
 // function refuses what it always refused, with its code; then mx_path with what `k` admits to the persistent kernel
 // (c->kernel itself is not read here).  Only the bf16 epilogue is cut into row chunks: the q/k-norm launch is one piece by its
 // argument check, and the quantising epilogue stores through 64-bit addresses.
-int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, MxKernel k, hipStream_t stream, bya_gemm_plan* plan) {
+// `st`: the score-bound statistics of the q/k-norm epilogue (bya_gemm_mx_qkv_norm_rope_stats alone passes a table).
+int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, MxKernel k, hipStream_t stream, bya_gemm_plan* plan,
+            const QknStats& st = QknStats{}) {
     if (!c || !d) return BYA_ERR_SHAPE;
     if (c->norm && c->q_scales) return BYA_ERR_SHAPE;
     if ((c->norm || c->q_scales) && (c->res || c->gate0 || c->gate1)) return BYA_ERR_SHAPE;
     GemmArgs a;
     int rc, epi = MX_EPI_BF16;
     if (c->norm) {
-        rc = mx_qkn_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, d, c->norm, c->a_fmt, c->w_fmt, &a);
+        rc = mx_qkn_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, d, c->norm, st, c->a_fmt, c->w_fmt, &a);
         epi = MX_EPI_QKN;
     } else if (c->q_scales) {
         rc = mx_quant_args(c->A, c->a_scales, c->W, c->w_scales, c->bias, c->C, c->q_scales, d, c->a_fmt, c->w_fmt, c->out_fmt, &a);
@@ -568,6 +572,8 @@ int mx_call(const bya_mx_gemm_call* c, const bya_gemm_desc* d, MxKernel k, hipSt
     const long long ks = d->K / 32;
     auto run = [&](const GemmArgs& piece, int batch, long long row0) {
         const int path = mx_path(a, d->batch, piece, c->a_fmt, c->w_fmt, epi, k);
+        // the score-bound statistics (bya_gemm_mx_qkv_norm_rope_stats) are the persistent kernel's: the tiled ones decline them
+        if (epi == MX_EPI_QKN && a.qkn_stats && path != BYA_GEMM_PATH_P256) return BYA_ERR_UNSUPPORTED;
         if (plan) return gemm_plan_whole(plan, path, 1);
         return mx_launch(path, piece, (const uint8_t*)c->a_scales + row0 * ks, (const uint8_t*)c->w_scales, (uint8_t*)c->q_scales, epi,
                          c->a_fmt, c->w_fmt, batch, stream);
@@ -687,6 +693,36 @@ extern "C" int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_sc
                                                  bya_gemm_plan* p) {
     if (!p) return BYA_ERR_SHAPE;
     return mx_qkn_on(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, kernel, nullptr, p);
+}
+
+// bya_gemm_mx_qkv_norm_rope_on that also records bya_qknorm_rope's score-bound statistics (include/bya.h), with
+// bya_gemm_mx_call's `kernel` argument (so that e2m1 weights and, under BYA_MX_KERNEL_FP6, e2m3 operands reach the persistent
+// kernel, whose STATS instances record them); where the launch would take a tiled kernel a table is answered BYA_ERR_UNSUPPORTED
+namespace {
+int mx_qkn_stats(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias, const void* C,
+                 int32_t fmt, int32_t w_fmt, const bya_gemm_desc* d, const bya_qknorm_desc* n, int32_t kernel, const QknStats& st,
+                 hipStream_t stream, bya_gemm_plan* plan) {
+    const bya_mx_gemm_call c = {A, a_scales, W, w_scales, bias, (void*)C, nullptr, nullptr, nullptr, nullptr, n, fmt, w_fmt, MX_E4M3, kernel};
+    MxKernel k;
+    if (!n || !mx_kernel_of_call(&c, &k)) return BYA_ERR_SHAPE;
+    return mx_call(&c, d, k, stream, plan, st);
+}
+}  // namespace
+
+extern "C" int bya_gemm_mx_qkv_norm_rope_stats(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                               const void* bias, void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* d,
+                                               const bya_qknorm_desc* n, int32_t kernel, float* stats, int32_t stats_slots,
+                                               hipStream_t stream) {
+    return mx_qkn_stats(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, kernel, QknStats{stats, stats_slots}, stream, nullptr);
+}
+
+extern "C" int bya_gemm_mx_qkv_norm_rope_stats_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                                    const void* bias, const void* C, int32_t fmt, int32_t w_fmt,
+                                                    const bya_gemm_desc* d, const bya_qknorm_desc* n, int32_t kernel,
+                                                    const float* stats, int32_t stats_slots, bya_gemm_plan* p) {
+    if (!p) return BYA_ERR_SHAPE;
+    return mx_qkn_stats(A, a_scales, W, w_scales, bias, C, fmt, w_fmt, d, n, kernel, QknStats{const_cast<float*>(stats), stats_slots},
+                        nullptr, p);
 }
 
 // ... on the tiled kernel (kernel = 0)

@@ -194,7 +194,8 @@ __device__ __forceinline__ void epilogue_mx_wide8_quant6(const GemmArgs& p, uint
     row_block(0); row_block(1); row_block(2); row_block(3); row_block(4); row_block(5); row_block(6); row_block(7);
 }
 
-// QOUT = MX_EPI_BF16: the bf16 epilogue; MX_EPI_QKN: the q/k-norm one (p.qkn_*); MX_E4M3 / MX_E2M3: the quantising one for that
+// QOUT = MX_EPI_BF16: the bf16 epilogue; MX_EPI_QKN: the q/k-norm one (p.qkn_*), MX_EPI_QKN_STATS: the same with the score-bound
+// statistics (p.qkn_stats; the launcher takes it where the arguments carry a table); MX_E4M3 / MX_E2M3: the quantising one for that
 // output format (C = codes with ldc / c_bs in bytes, qs = its scale bytes).  FMT_W: the weights' element format, FMT_A or
 // MX_E2M1; FMT_A: the activations', MX_E4M3 or MX_E2M3 (the top of the file)
 template <int QOUT, int FMT_W, int FMT_A>
@@ -698,6 +699,8 @@ __global__ __launch_bounds__(256, 1) void gemm256p_mx_kernel(GemmArgs p, const u
 
         if constexpr (QOUT == MX_EPI_QKN) {
             epilogue_mx_wide8_qkn<2>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc);
+        } else if constexpr (QOUT == MX_EPI_QKN_STATS) {
+            epilogue_mx_wide8_qkn<2, false, true>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc);
         } else {
             auto run = [&](auto act_tag) {
                 if constexpr (QOUT == MX_EPI_BF16)       // (wave, lane: the split writer's, unused here; PIN: acc stays in AGPRs per burst)
@@ -758,6 +761,7 @@ int bya_launch_gemm256p_mx(const void* args, const uint8_t* sa, const uint8_t* s
         if (a_fmt == MX_E2M3) return w_fmt == MX_E2M1 ? on(IntTag<MX_E2M1>{}, IntTag<MX_E2M3>{}) : on(IntTag<MX_E2M3>{}, IntTag<MX_E2M3>{});
         return w_fmt == MX_E2M1 ? on(IntTag<MX_E2M1>{}, IntTag<MX_E4M3>{}) : on(IntTag<MX_E4M3>{}, IntTag<MX_E4M3>{});
     };
+    if (epi == MX_EPI_QKN && a.qkn_stats) return go(IntTag<MX_EPI_QKN_STATS>{});
     return epi == MX_EPI_QKN ? go(IntTag<MX_EPI_QKN>{}) : epi == MX_E4M3 ? go(IntTag<MX_E4M3>{}) :
            epi == MX_E2M3 ? go(IntTag<MX_E2M3>{}) : go(IntTag<MX_EPI_BF16>{});
 }

@@ -64,11 +64,12 @@ constexpr int DEFAULT_MIN_SPLIT_KTILES = 40;
 // SPLIT = false: the instance for launches that will not split a tile (no workspace, short K, or nothing left over): its
 // epilogue has no slab branch -- that branch alone costs the ordinary path 1.5-2.5 % on K = 3072 shapes (same-box A/B,
 // profiles/history/r2_gemm_epilogue_variants_same_box.txt) because it cuts the unrolled epilogue into blocks.
-template <bool SPLIT, bool CONV = false, bool QKN = false>
+template <bool SPLIT, bool CONV = false, bool QKN = false, bool STATS = false>
 __global__ __launch_bounds__(256, 1) void gemm256p_kernel(GemmArgs p, int tiles_m, int tiles_n, int batch, int split_arg,
                                                           int min_seg, unsigned epoch) {
     static_assert(!(SPLIT && CONV), "the convolution instance does not split K");
     static_assert(!(QKN && (SPLIT || CONV)), "the q/k-norm instance is a plain, unsplit GEMM");
+    static_assert(QKN || !STATS, "the score-bound statistics are the q/k-norm epilogue's");
     const int split = SPLIT ? split_arg : 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int BM = 256, BN = 256, STAGE = (BM + BN) * BK * 2, TILE_A = BM * BK * 2;
@@ -875,7 +876,7 @@ __global__ __launch_bounds__(256, 1) void gemm256p_kernel(GemmArgs p, int tiles_
             // ---- whole tile (ordinary epilogue), or (role 1) a split tile's partial sums -> slab, then drained and counted
             float* const raw_out = (SPLIT && cur.role == 1) ? p.ws_slabs + (size_t)cur.slab * (GEMM_WS_SLAB_BYTES / 4) : nullptr;
             if constexpr (QKN) {
-                epilogue_qkn(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc);
+                epilogue_qkn<8, STATS>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc);
             } else {
                 auto run = [&](auto act_tag) {
                     epilogue_wide<decltype(act_tag)::value, 2, SPLIT, CONV>(p, cur.z, cur.m0 + wm * 128, cur.n0 + wn * 128, fr, fq, acc,
@@ -932,14 +933,16 @@ int bya_launch_conv256p(const void* args, hipStream_t s) {
     return launch_persistent<gemm256p_kernel<false, true>>(persistent_grid((long long)tiles_m * tiles_n), 256, lds, s, a, tiles_m, tiles_n, 1, 0, 1 << 30, 0u);
 }
 
-// q|k|v projection with the q/k-norm + RoPE epilogue (bya_gemm_qkv_norm_rope): the QKN instance, never split
+// q|k|v projection with the q/k-norm + RoPE epilogue (bya_gemm_qkv_norm_rope): the QKN instance, never split; its STATS twin
+// where the launch records the score-bound statistics (GemmArgs::qkn_stats)
 int bya_launch_gemm256p_qkn(const void* args, int batch, hipStream_t s) {
     GemmArgs a = *static_cast<const GemmArgs*>(args);
     a.gm = gemm_group_m(a);
     const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
     const size_t lds = 2 * 512 * BK * 2;
-    return launch_persistent<gemm256p_kernel<false, false, true>>(persistent_grid((long long)tiles_m * tiles_n * batch), 256, lds, s, a, tiles_m, tiles_n,
-                                                                  batch, 0, 1 << 30, 0u);
+    const int grid = persistent_grid((long long)tiles_m * tiles_n * batch);
+    if (a.qkn_stats) return launch_persistent<gemm256p_kernel<false, false, true, true>>(grid, 256, lds, s, a, tiles_m, tiles_n, batch, 0, 1 << 30, 0u);
+    return launch_persistent<gemm256p_kernel<false, false, true>>(grid, 256, lds, s, a, tiles_m, tiles_n, batch, 0, 1 << 30, 0u);
 }
 
 int bya_gemm_split_min_ktiles() {

@@ -31,7 +31,7 @@
 
 namespace {
 
-template <bool QKN>
+template <bool QKN, bool STATS = false>
 __global__ __launch_bounds__(256, 1) void gemm128p_kernel(GemmArgs p, int tiles_m, int tiles_n, int batch) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int BM = 128, BN = 256, TILE_A = BM * BK * 2, STAGE = (BM + BN) * BK * 2;
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256, 1) void gemm128p_kernel(GemmArgs p, int tiles_
 #pragma unroll
             for (int i = 0; i < 8; ++i) asm volatile("" :: "a"(acc[i][0]), "a"(acc[i][1]), "a"(acc[i][2]), "a"(acc[i][3]));
         } else if constexpr (QKN) {
-            epilogue_qkn<4>(p, cur.z, cur.m0 + wm * 64, cur.n0 + wn * 128, fr, fq, acc);
+            epilogue_qkn<4, STATS>(p, cur.z, cur.m0 + wm * 64, cur.n0 + wn * 128, fr, fq, acc);
         } else {
             auto run = [&](auto act_tag) {
                 epilogue_wide<decltype(act_tag)::value, 2, false, false, 4>(p, cur.z, cur.m0 + wm * 64, cur.n0 + wn * 128, fr, fq, acc,
@@ -330,17 +330,21 @@ __global__ __launch_bounds__(256, 1) void gemm128p_kernel(GemmArgs p, int tiles_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the (empty-descriptor) pieces requested for the tile after the last
 }
 
-template <bool QKN>
+template <bool QKN, bool STATS = false>
 int launch128p(const GemmArgs& a0, int batch, hipStream_t s) {
     GemmArgs a = a0;
     a.gm = 2 * gemm_group_m(a);                                // the same rows per group as the 256-row tiles' order
     const int tiles_m = (a.M + 127) / 128, tiles_n = (a.N + 255) / 256;
     const size_t lds = 3 * (128 + 256) * BK * 2;
-    return launch_persistent<gemm128p_kernel<QKN>>(persistent_grid((long long)tiles_m * tiles_n * batch), 256, lds, s, a, tiles_m, tiles_n, batch);
+    return launch_persistent<gemm128p_kernel<QKN, STATS>>(persistent_grid((long long)tiles_m * tiles_n * batch), 256, lds, s, a, tiles_m, tiles_n, batch);
 }
 
 }  // namespace
 
 // callers (gemm.hip) have checked v4_eligible() and K >= 4 K-tiles
 int bya_launch_gemm128p(const void* args, int batch, hipStream_t s) { return launch128p<false>(*static_cast<const GemmArgs*>(args), batch, s); }
-int bya_launch_gemm128p_qkn(const void* args, int batch, hipStream_t s) { return launch128p<true>(*static_cast<const GemmArgs*>(args), batch, s); }
+// (the STATS twin where the launch records the q/k-norm epilogue's score-bound statistics: GemmArgs::qkn_stats)
+int bya_launch_gemm128p_qkn(const void* args, int batch, hipStream_t s) {
+    const GemmArgs& a = *static_cast<const GemmArgs*>(args);
+    return a.qkn_stats ? launch128p<true, true>(a, batch, s) : launch128p<true>(a, batch, s);
+}

@@ -155,7 +155,13 @@ __device__ __forceinline__ void epilogue_wide(const GemmArgs& p, int z, int m_wa
 // (g ^ 2), (g ^ 4) is therefore lane ^ 16, lane ^ 32, then the lane's own two registers: same operands, same order, same bits
 // as the stand-alone kernel.  The projection is rounded to bf16 first (the value the two-launch path stored and read back).
 // v tiles (n_wave >= 2 width) take the plain bias epilogue.
-template <int NJ = 8>
+// STATS (the *_stats entry points; an instance of its own, the plain one keeps its instruction stream): the launch also records
+// the score-bound statistics of bya_qknorm_rope -- per finished q / k head row the squared norm of the values AS STORED
+// (pack8, unpack8), group by group (qkn_norm2_8) and by the same tree, so the same bits as the stand-alone kernel's.  Rows
+// past M count as 0.  Nothing touches memory per row: a lane keeps the maximum over its NJ row blocks in one register per
+// head, qkn_row16_umax takes it over the 16 rows of a block, and lane 0 issues ONE atomic maximum per (wave, head, tile) --
+// the stand-alone kernel issues one per (row, head).  Slot = workgroup % slots, as there.
+template <int NJ = 8, bool STATS = false>
 __device__ __forceinline__ void epilogue_qkn(const GemmArgs& p, int z, int m_wave, int n_wave, int fr, int fq, const f32x4 (&acc)[8][NJ]) {
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(p.C + (long long)z * p.c_bs), 0, 0x7fffffff, 0x00020000);
     const int tsel = n_wave / p.qkn_width;                       // 0 = q, 1 = k, 2 = v (a tile never straddles: width % 128 == 0)
@@ -182,6 +188,7 @@ __device__ __forceinline__ void epilogue_qkn(const GemmArgs& p, int z, int m_wav
     }
     const float ks = tsel == 1 ? p.qkn_kscale : 1.0f;
     const QknRotary rot = qkn_rotary<true>(p);
+    uint32_t n2max[2] = {0u, 0u};                                // STATS: per head, the largest squared row norm so far (bits)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int m = m_wave + 16 * j + fr;
@@ -222,11 +229,34 @@ __device__ __forceinline__ void epilogue_qkn(const GemmArgs& p, int z, int m_wav
                 const float rstd = rsqrtf((q0 + q1) * (1.0f / 64) + p.qkn_eps);
                 qkn_finish8(v[0], rstd, wv[0], bb[0], rope, cs[0].c, cs[0].s, ks);
                 qkn_finish8(v[1], rstd, wv[1], bb[1], rope, cs[1].c, cs[1].s, ks);
+                if constexpr (STATS) {
+                    // the row as stored (the same pack8 as the store below), its two groups of this lane, then the tree
+                    float r[2][8];
+                    unpack8(pack8(v[0]), r[0]);
+                    unpack8(pack8(v[1]), r[1]);
+                    const float n2 = lane_add32(lane_add16(qkn_norm2_8(r[0]))) + lane_add32(lane_add16(qkn_norm2_8(r[1])));
+                    const uint32_t nb = (mok && nok[2 * hh]) ? __float_as_uint(n2) : 0u;
+                    n2max[hh] = nb > n2max[hh] ? nb : n2max[hh];
+                }
             }
 #pragma unroll
             for (int el = 0; el < 2; ++el) {
                 const int e = 2 * hh + el;
                 __builtin_amdgcn_raw_buffer_store_b128(pack8(v[el]), rsC, (mok && nok[e]) ? coff + colb[e] : 0xffffffffu, 0, 0);
+            }
+        }
+    }
+    if constexpr (STATS) {
+        if (tsel < 2) {
+            // the wave's two heads are neighbours of one tensor (width % 128 == 0): entries i0 and i0 + 1 of
+            // [slot][tsel][qkn_stats_nbh], i0 = z * heads + head < qkn_stats_nbh (qkn_stats_args, gemm_common.h)
+            unsigned* const tab = reinterpret_cast<unsigned*>(p.qkn_stats) +
+                                  ((long long)(blockIdx.x % (unsigned)p.qkn_stats_slots) * 2 + tsel) * p.qkn_stats_nbh;
+            const long long i0 = (long long)z * (p.qkn_width / 64) + (n_wave - tsel * p.qkn_width) / 64;
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                const uint32_t top = qkn_row16_umax(n2max[hh]);          // (the four fq lanes of a row hold the same value)
+                if ((fr | fq) == 0) qkn_stats_raise(tab, i0 + hh, top);
             }
         }
     }
@@ -260,7 +290,9 @@ __device__ __forceinline__ void epilogue_qkn(const GemmArgs& p, int z, int m_wav
 // scaled) does: an empty asm that owns the register keeps hipcc's default -ffp-contract from merging the multiply and the
 // addition into one fma(acc, scale, bias), which rounds once less.  The eight channel scales of each of the lane's four column
 // groups stay in 32 registers for the whole tile.
-template <int JB, bool SCALED = false>
+// STATS: epilogue_qkn's, with the tensor decided per head -- one register per head holds the largest squared norm of the rows
+// as stored, one atomic maximum per (wave, q or k head, tile) raises entry z * heads + head of the head's tensor.
+template <int JB, bool SCALED = false, bool STATS = false>
 __device__ __forceinline__ void epilogue_mx_wide8_qkn(const GemmArgs& p, int z, int m_wave, int n_wave, int fr, int fq,
                                                       f32x4 (&acc)[8][8], const float* __restrict__ sa = nullptr,
                                                       const float* __restrict__ sw = nullptr) {
@@ -295,6 +327,7 @@ __device__ __forceinline__ void epilogue_mx_wide8_qkn(const GemmArgs& p, int z, 
         }
     }
     const bool any_qk = tsel[0] < 2;                                // (tsel ascends: a q or k head, if any, is head 0)
+    uint32_t n2max[2] = {0u, 0u};                                   // STATS: per head, the largest squared row norm so far (bits)
 #pragma unroll
     for (int jb = 0; jb < 8; jb += JB) {
         __builtin_amdgcn_sched_barrier(0);                          // a burst's table loads stay inside the burst
@@ -356,10 +389,30 @@ __device__ __forceinline__ void epilogue_mx_wide8_qkn(const GemmArgs& p, int z, 
                         unpack8(bq[hh][el], b8);
                         qkn_finish8(v[el], rstd, w8, b8, rope, cs[el].c, cs[el].s, ks);
                     }
+                    if constexpr (STATS) {
+                        float r[2][8];
+                        unpack8(pack8(v[0]), r[0]);
+                        unpack8(pack8(v[1]), r[1]);
+                        const float n2 = lane_add32(lane_add16(qkn_norm2_8(r[0]))) + lane_add32(lane_add16(qkn_norm2_8(r[1])));
+                        const uint32_t nb = (mok && nok[hh][0]) ? __float_as_uint(n2) : 0u;
+                        n2max[hh] = nb > n2max[hh] ? nb : n2max[hh];
+                    }
                 }
 #pragma unroll
                 for (int el = 0; el < 2; ++el)
                     __builtin_amdgcn_raw_buffer_store_b128(pack8(v[el]), rsC, (mok && nok[hh][el]) ? coff + colb[hh][el] : 0xffffffffu, 0, 0);
+            }
+        }
+    }
+    if constexpr (STATS) {
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            if (tsel[hh] < 2) {                                         // (wave-uniform; entry < qkn_stats_nbh: qkn_stats_args)
+                unsigned* const tab = reinterpret_cast<unsigned*>(p.qkn_stats) +
+                                      ((long long)(blockIdx.x % (unsigned)p.qkn_stats_slots) * 2 + tsel[hh]) * p.qkn_stats_nbh;
+                const long long i = (long long)z * (p.qkn_width / 64) + (n_wave + 64 * hh - tsel[hh] * p.qkn_width) / 64;
+                const uint32_t top = qkn_row16_umax(n2max[hh]);
+                if ((fr | fq) == 0) qkn_stats_raise(tab, i, top);
             }
         }
     }

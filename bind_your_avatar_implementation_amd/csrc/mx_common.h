@@ -18,6 +18,7 @@ namespace {
 constexpr int MX_E4M3 = 0, MX_E2M3 = 2, MX_E2M1 = 4;                      // the instruction's cbsz / blgp codes
 // the epilogue of an MX GEMM kernel (its QOUT parameter): the element format of the quantising one, or
 constexpr int MX_EPI_BF16 = -1, MX_EPI_QKN = -2;                          // bf16 out; bf16 out with q/k-norm + RoPE (GemmArgs::qkn_*)
+constexpr int MX_EPI_QKN_STATS = -3;      // the persistent kernel's alone: MX_EPI_QKN that records the score-bound statistics (qkn_stats)
 __host__ __device__ constexpr int mx_emax(int fmt) { return fmt == MX_E4M3 ? 8 : 2; }                  // (e2m3 and e2m1: 2)
 __host__ __device__ constexpr int mx_block_bytes(int fmt) { return fmt == MX_E4M3 ? 32 : fmt == MX_E2M3 ? 24 : 16; }
 

@@ -44,6 +44,31 @@ __device__ __forceinline__ void qkn_finish8(float (&v)[8], float rstd, const flo
     }
 }
 
+// ---- the score-bound statistics (include/bya.h: bya_qknorm_rope's `stats`, the *_stats entry points): the squared norm of a
+// finished head row, taken from the bf16-ROUNDED values as they are stored.  One group's share: its 8 squares added in
+// sequence (the square of a bf16 value is exact in fp32, so a fused multiply-add and a multiply + add give the same bits);
+// the callers then add the groups by the tree (g ^ 1), (g ^ 2), (g ^ 4), like every other sum here.
+__device__ __forceinline__ float qkn_norm2_8(const float (&r)[8]) {
+    float n2 = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) n2 += r[e] * r[e];
+    return n2;
+}
+// Maximum of a 32-bit pattern over the 16 lanes of a DPP row (lane & 15 = the MFMA layout's fr), in every lane of the row:
+// quads, then quad pairs, then the row's two halves.  On bit patterns because that is what the table's atomic maximum compares
+// (a non-negative float orders like its pattern, and a NaN row wins there as it does in the stand-alone kernel).
+__device__ __forceinline__ uint32_t qkn_row16_umax(uint32_t x) {
+    auto step = [](uint32_t v, uint32_t o) { return v > o ? v : o; };
+    x = step(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, true));     // quad_perm [1,0,3,2]
+    x = step(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, true));     // quad_perm [2,3,0,1]
+    x = step(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x141, 0xF, 0xF, true));    // row_half_mirror
+    return step(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x140, 0xF, 0xF, true)); // row_mirror
+}
+// One no-return atomic maximum at agent scope (the stand-alone kernel's) on entry `tab[i]`; a zero raises nothing
+__device__ __forceinline__ void qkn_stats_raise(unsigned* tab, long long i, uint32_t bits) {
+    if (bits) (void)__hip_atomic_fetch_max(tab + i, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ---- the rotary tables of the GEMM epilogues (epilogue_qkn, epilogue_mx_wide8_qkn, epilogue_mx_qkn): fp32 [M - text_rows, 64]
 // cos and sin behind buffer descriptors, so that a row that is not rotated reads zeros from an out-of-range offset instead of
 // taking a branch (hipcc can then keep the next row block's loads in flight under this one's arithmetic).

@@ -196,6 +196,10 @@ class DenoiseEngine:
         self.router_replicated = os.environ.get("BYA_ROUTER_REPLICATED", "0") == "1"
         # q/k-norm + RoPE inside the q|k|v projection's epilogue (bya_gemm_qkv_norm_rope; bit-identical to the two launches)
         self.qkn_epilogue = os.environ.get("BYA_QKN_EPILOGUE", "1") != "0"
+        # ... also on a layer whose attention wants the data-dependent score bound (``_attn_bound``): the fused launch then
+        # records the q/k statistics itself (the *_stats entry points; the same maxima, bit for bit) instead of leaving the layer
+        # to the projection + bya_qknorm_rope.  "1" switches it on.  Off by default: not yet measured at step level
+        self.qkn_stats_epilogue = os.environ.get("BYA_QKN_STATS_EPILOGUE", "0") == "1"
         self._inv_cache = {}
         self._side = None              # side stream of the step-invariant conditioning
         self._ws_key, self._ws = None, None
@@ -382,21 +386,23 @@ class DenoiseEngine:
     def _qkv_norm_rope(self, i, at, xn, out, split, xq, cos, sin, text_rows, heads, q_view, k_view, stats):
         """Block ``i``'s packed q|k|v projection + q/k LayerNorm + RoPE (models/transformer.py:200-209, 241-245): ONE launch
         with the norm in the GEMM's epilogue where the library takes it (bf16 weights, or MX / fp8 weights behind the
-        LayerNorm-fused quantiser with their ``fuse_qk_norm``; no statistics wanted), else the projection and ``bya_qknorm_rope`` on its output -- the
-        same bits either way."""
+        LayerNorm-fused quantiser with their ``fuse_qk_norm``; statistics wanted only under ``qkn_stats_epilogue``, and then
+        recorded by that launch where its kernel does), else the projection and ``bya_qknorm_rope`` on its output -- the same
+        bits either way, and the same maxima in ``stats``."""
         qk = (at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias)
         ek = dict(eps=at.norm_q.eps, k_scale=self.k_scale)
-        fused = self.qkn_epilogue and stats is None and not self._quantised("qkv") and xq is None
-        if fused and ops.gemm_qkv_norm_rope(xn, self.qkv_w[i], out, self.qkv_b[i], split, *qk, cos, sin, text_rows, **ek):
+        may_fuse = stats is None or self.qkn_stats_epilogue
+        fused = self.qkn_epilogue and may_fuse and not self._quantised("qkv") and xq is None
+        if fused and ops.gemm_qkv_norm_rope(xn, self.qkv_w[i], out, self.qkv_b[i], split, *qk, cos, sin, text_rows, stats=stats, **ek):
             return
-        if self.mx_fuse_qk_norm and stats is None and xq is not None and self.wmx is not None and "qkv" in self.wmx:
-            norm = dict(zip(("qw", "qb", "kw", "kb"), qk), cos=cos, sin=sin, text_rows=text_rows, **ek)
+        if self.mx_fuse_qk_norm and may_fuse and xq is not None and self.wmx is not None and "qkv" in self.wmx:
+            norm = dict(zip(("qw", "qb", "kw", "kb"), qk), cos=cos, sin=sin, text_rows=text_rows, stats=stats, **ek)
             if self._mx_linear("qkv", i, xq, xn.shape[:-1], out, norm=norm, bias=self.qkv_b[i], split=split):
                 return
-        if self.fp8_fuse_qk_norm and stats is None and xq is not None and self.w8 is not None and "qkv" in self.w8:
+        if self.fp8_fuse_qk_norm and may_fuse and xq is not None and self.w8 is not None and "qkv" in self.w8:
             w8, sw = self.w8["qkv"][i]
             if ops.gemm_fp8_qkv_norm_rope(xq[0].view(*xn.shape), xq[1].view(*xn.shape[:-1]), w8, sw, out, self.qkv_b[i], split,
-                                          *qk, cos, sin, text_rows, **ek):
+                                          *qk, cos, sin, text_rows, stats=stats, **ek):
                 return
         self._dit_linear("qkv", i, xn, self.qkv_w[i], out, bias=self.qkv_b[i], split=split, quantised=xq)
         ops.qknorm_rope(q_view, k_view, *qk, cos, sin, heads=heads, text_rows=text_rows, stats=stats, **ek)
@@ -435,7 +441,8 @@ class DenoiseEngine:
         if norm is not None:                 # (its kernel is an argument: option mx_kernel has no say there)
             return ops.gemm_mx_qkv_norm_rope(codes, sa, wc, sw, out, kw["bias"], kw["split"], norm["qw"], norm["qb"], norm["kw"],
                                              norm["kb"], norm["cos"], norm["sin"], norm["text_rows"], eps=norm["eps"],
-                                             k_scale=norm["k_scale"], fmt=self.mx_fmt, w_fmt=self.mx_wfmt, kernel=self.mx_kernel)
+                                             k_scale=norm["k_scale"], fmt=self.mx_fmt, w_fmt=self.mx_wfmt, kernel=self.mx_kernel,
+                                             stats=norm.get("stats"))
         with self._mx_kernel_option():
             if out_scales is not None:
                 return ops.gemm_mx_quant(codes, sa, wc, sw, out, out_scales, self.mx_fmt, w_fmt=self.mx_wfmt, out_fmt=out_fmt, **kw)

@@ -422,6 +422,22 @@ def _qkn_desc(d, tensors, qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale, pla
     return n
 
 
+def _with_stats(call, d, n, stats, plan):
+    """``call`` = (fused q|k|v entry point, its arguments) as it is (``stats`` None), or as the call of ``<entry point>_stats``
+    with the table behind the arguments: the score-bound table of ``qknorm_rope`` for the launch to fill -- fp32
+    [slots, 2, batch * width / 64], zeroed by the caller -- or, in a query, its slot count."""
+    if stats is None:
+        return call
+    if plan and isinstance(stats, int):
+        ps, slots = _META_BASE, stats
+    else:
+        assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.dim() == 3
+        assert stats.shape[1:] == (2, d.batch * (n.width // 64))
+        ps, slots = (_plan_p if plan else _p)(stats), stats.shape[0]
+    entry, args = call
+    return entry + "_stats", (*args, ps, slots)
+
+
 def _label(d, pre="", act=False, gate0=None, res=None):
     """The shape label of a GEMM's timer bucket (``enable_kernel_timers(by_shape=True)``): [pre]:BxMxNxK[:epilogue]."""
     s = f"{pre}:{d.batch}x{d.M}x{d.N}x{d.K}"
@@ -537,28 +553,32 @@ def gemm_plan(a, w, out, bias=None, res=None, gate0=None, gate1=None, gate_split
     return _plan(call)
 
 
-def _qkn_call(a, w, out, bias, split, norm, tensors, plan):
+def _qkn_call(a, w, out, bias, split, norm, tensors, plan, stats=None):
     if tensors not in (2, 3) or w.shape[0] % tensors:
         raise ValueError("gemm_qkv_norm_rope: a [(B,) M, K], w [3 * width, K] (or [2 * width, K]: q | k alone, tensors=2), "
                          "out = the first of the split outputs")
     d = _gemm_desc(a, w, out, None, tuple(split), _NO_EPILOGUE, plan)    # (``split`` is required: None is a TypeError)
     n = _qkn_desc(d, tensors, *norm, plan)
     q = _plan_p if plan else _p
-    return d, ("bya_gemm_qkv_norm_rope", (q(a), q(w), q(bias), q(out), ctypes.byref(d), ctypes.byref(n)))
+    return d, _with_stats(("bya_gemm_qkv_norm_rope", (q(a), q(w), q(bias), q(out), ctypes.byref(d), ctypes.byref(n))), d, n, stats, plan)
 
 
-def gemm_qkv_norm_rope(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6, k_scale=1.0, tensors=3):
+def gemm_qkv_norm_rope(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6, k_scale=1.0, tensors=3, stats=None):
     """The packed q|k|v projection with the q/k LayerNorm(64) + RoPE in its epilogue (bya_gemm_qkv_norm_rope): equals
     ``gemm(..., split=split)`` followed by ``qknorm_rope`` bit for bit, in one launch.  Returns False (nothing launched) when
-    the library does not take the shape -- the caller then issues the two launches."""
-    d, call = _qkn_call(a, w, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale), tensors, False)
+    the library does not take the shape -- the caller then issues the two launches.  ``stats``: ``qknorm_rope``'s table (fp32
+    [slots, 2, B * width / 64], ZEROED by the caller) for this launch to fill as that one would: the same maxima over the slots,
+    bit for bit (which slot holds one differs)."""
+    d, call = _qkn_call(a, w, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale), tensors, False, stats)
     return _launch(_bf16_bucket(d), None, d, call, True)         # (the bf16 GEMM's bucket, and no shape label)
 
 
-def gemm_qkv_norm_rope_plan(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6, k_scale=1.0, tensors=3):
+def gemm_qkv_norm_rope_plan(a, w, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6, k_scale=1.0, tensors=3,
+                            stats=None):
     """What ``gemm_qkv_norm_rope`` would run (``gemm_plan``'s dict): path "p256" (its row plan 0), "p128" (plan 1), or
-    "p256" with m0 and tail "p128" (plan 2); None where it declines the shape (the caller's two launches)."""
-    return _plan(_qkn_call(a, w, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale), tensors, True)[1], True)
+    "p256" with m0 and tail "p128" (plan 2); None where it declines the shape (the caller's two launches).  ``stats``: None,
+    the number of slots, or the table (as for ``qknorm_rope_plan``)."""
+    return _plan(_qkn_call(a, w, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale), tensors, True, stats)[1], True)
 
 
 def quantize_rows_fp8(x, q=None, scale=None):
@@ -613,7 +633,7 @@ def gemm_fp8_plan(a8, a_scale, w8, w_scale, out, bias=None, res=None, gate0=None
                            True)[1])
 
 
-def _fp8_qkn_call(a8, a_scale, w8, w_scale, out, bias, split, norm, tensors, act, res, alpha, plan):
+def _fp8_qkn_call(a8, a_scale, w8, w_scale, out, bias, split, norm, tensors, act, res, alpha, plan, stats=None):
     if tensors not in (2, 3) or w8.shape[0] % tensors or split is None:
         raise ValueError("gemm_fp8_qkv_norm_rope: w8 [3 * width, K] (or [2 * width, K]: q | k alone, tensors=2), "
                          "out = the first of the split outputs, split = (n_split, c_split_stride)")
@@ -621,28 +641,30 @@ def _fp8_qkn_call(a8, a_scale, w8, w_scale, out, bias, split, norm, tensors, act
     d = _fp8_desc(a8, a_scale, w8, w_scale, out, res, split, (0, 0, act, None, alpha), plan)
     n = _qkn_desc(d, tensors, *norm, plan)
     q = _plan_p if plan else _p
-    return d, ("bya_gemm_fp8_qkv_norm_rope", (q(a8), q(a_scale), q(w8), q(w_scale), q(bias), q(out), ctypes.byref(d), ctypes.byref(n)))
+    call = ("bya_gemm_fp8_qkv_norm_rope", (q(a8), q(a_scale), q(w8), q(w_scale), q(bias), q(out), ctypes.byref(d), ctypes.byref(n)))
+    return d, _with_stats(call, d, n, stats, plan)
 
 
 def gemm_fp8_qkv_norm_rope(a8, a_scale, w8, w_scale, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6,
-                           k_scale=1.0, tensors=3, *, act=None, res=None):
+                           k_scale=1.0, tensors=3, *, act=None, res=None, stats=None):
     """The packed q|k|v projection on e4m3 operands with the q/k LayerNorm(64) + RoPE in its epilogue
     (bya_gemm_fp8_qkv_norm_rope): equals ``gemm_fp8(..., split=split)`` followed by ``qknorm_rope`` bit for bit, in one launch
     on the kernel ``gemm_fp8`` would take (``gemm_fp8_plan``'s path, option ``fp8_kernel`` included).  Returns False (nothing
     launched, nothing counted) when the library does not take the shape -- the caller then issues the two launches.
-    ``act`` / ``res`` (keyword only): what the engine never asks of this launch, here so that a caller that does is told False."""
+    ``act`` / ``res`` (keyword only): what the engine never asks of this launch, here so that a caller that does is told False.
+    ``stats``: as for ``gemm_qkv_norm_rope``; False where the kernel the launch would take does not record them."""
     d, call = _fp8_qkn_call(a8, a_scale, w8, w_scale, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale), tensors,
-                               act, res, 1.0, False)
+                               act, res, 1.0, False, stats)
     return _launch("bya_gemm_fp8_qkv_norm_rope", _SHAPE_LABELS and _label(d), d, call, True)
 
 
 def gemm_fp8_qkv_norm_rope_plan(a8, a_scale, w8, w_scale, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows, eps=1e-6,
-                                k_scale=1.0, tensors=3, *, act=None, res=None, alpha=1.0):
+                                k_scale=1.0, tensors=3, *, act=None, res=None, alpha=1.0, stats=None):
     """What ``gemm_fp8_qkv_norm_rope`` would run (``gemm_plan``'s dict): path "t128x128" or "p256", one row chunk; None where
     it declines the shape (the caller's two launches).  ``act`` / ``res`` / ``alpha``: descriptor fields the launch wrapper's
     callers never set, here to ask what the library answers to them."""
     return _plan(_fp8_qkn_call(a8, a_scale, w8, w_scale, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale), tensors,
-                               act, res, alpha, True)[1], True)
+                               act, res, alpha, True, stats)[1], True)
 
 
 # OCP MX element formats (include/bya.h, "MX weights"): name -> the matrix instruction's format code, element bits.
@@ -750,35 +772,38 @@ def _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, 
     return d, _qkn_desc(d, tensors, *norm, plan)
 
 
-def _mx_qkn_call(a_codes, a_scales, w_codes, w_scales, out, bias, split, norm, tensors, fmt, w_fmt, act, alpha, kernel, plan):
+def _mx_qkn_call(a_codes, a_scales, w_codes, w_scales, out, bias, split, norm, tensors, fmt, w_fmt, act, alpha, kernel, plan, stats=None):
     code, wcode = mx_fmt_pair(fmt, w_fmt)
     d, n = _mx_qkn_descs(a_codes, a_scales, w_codes, w_scales, out, fmt, w_fmt, split, norm, tensors, act, alpha, plan)
     q = _plan_p if plan else _p
     args = (q(a_codes), q(a_scales), q(w_codes), q(w_scales), q(bias), q(out), code, wcode, ctypes.byref(d), ctypes.byref(n))
+    if stats is not None:                # (bya_gemm_mx_qkv_norm_rope_stats: the kernel is always an argument)
+        return d, _with_stats(("bya_gemm_mx_qkv_norm_rope", (*args, int(kernel))), d, n, stats, plan)
     return d, (("bya_gemm_mx_qkv_norm_rope", args) if kernel == 0 else ("bya_gemm_mx_qkv_norm_rope_on", (*args, int(kernel))))
 
 
 def gemm_mx_qkv_norm_rope(a_codes, a_scales, w_codes, w_scales, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows,
-                          eps=1e-6, k_scale=1.0, tensors=3, fmt="mxfp6", w_fmt=None, kernel=0):
+                          eps=1e-6, k_scale=1.0, tensors=3, fmt="mxfp6", w_fmt=None, kernel=0, stats=None):
     """The packed q|k|v projection on MX operands with the q/k LayerNorm(64) + RoPE in its epilogue
     (bya_gemm_mx_qkv_norm_rope): equals ``gemm_mx(..., split=split)`` followed by ``qknorm_rope`` bit for bit, in one launch.
     Returns False (nothing launched, nothing counted) when the library does not take the shape -- the caller then issues the
     two launches.  ``kernel``: 0 = the tiled kernel; 1 = the persistent 256 x 256 kernel where the launch fills it (mxfp8
     activations and weights only, the same bits; bya_gemm_mx_qkv_norm_rope_on), 2 = without the tile count (tests).  Option
-    ``mx_kernel`` has no say here."""
+    ``mx_kernel`` has no say here.  ``stats``: as for ``gemm_qkv_norm_rope``; False where the kernel the launch would take does
+    not record them (the tiled kernels)."""
     d, call = _mx_qkn_call(a_codes, a_scales, w_codes, w_scales, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale),
-                              tensors, fmt, w_fmt, None, 1.0, kernel, False)
+                              tensors, fmt, w_fmt, None, 1.0, kernel, False, stats)
     return _launch("bya_gemm_mx_qkv_norm_rope", _SHAPE_LABELS and _label(d, f":{fmt}*{w_fmt or fmt}"), d, call, True)
 
 
 def gemm_mx_qkv_norm_rope_plan(a_codes, a_scales, w_codes, w_scales, out, bias, split, qw, qb, kw, kb, cos, sin, text_rows,
-                               eps=1e-6, k_scale=1.0, tensors=3, fmt="mxfp6", w_fmt=None, act=None, alpha=1.0, kernel=0):
+                               eps=1e-6, k_scale=1.0, tensors=3, fmt="mxfp6", w_fmt=None, act=None, alpha=1.0, kernel=0, stats=None):
     """What ``gemm_mx_qkv_norm_rope`` would run (``gemm_plan``'s dict): path "t128x128" or "t256x256" (mxfp6 activations
     only), or "p256" (``kernel`` 1 or 2, mxfp8 activations and weights); None where it declines the shape (the caller's two
     launches).  ``act`` / ``alpha``: descriptor fields the launch wrapper never sets, here to ask what the library answers
     to them."""
     return _plan(_mx_qkn_call(a_codes, a_scales, w_codes, w_scales, out, bias, split, (qw, qb, kw, kb, cos, sin, text_rows, eps, k_scale),
-                              tensors, fmt, w_fmt, act, alpha, kernel, True)[1], True)
+                              tensors, fmt, w_fmt, act, alpha, kernel, True, stats)[1], True)
 
 
 def _mx_quant_desc(a_codes, a_scales, w_codes, w_scales, out_codes, out_scales, fmt, w_fmt, out_fmt, act, alpha):
@@ -858,6 +883,16 @@ def _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias
     return c, d, n, name
 
 
+def _mx_call_with_stats(fn, a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, split, norm, others, alpha):
+    """``gemm_mx_call`` / ``gemm_mx_call_plan`` with a table in the ``norm`` dict: ``fn`` = ``gemm_mx_qkv_norm_rope`` / its
+    ``_plan`` twin with the call's ``kernel``; nothing but the q/k-norm epilogue's own arguments goes with a table."""
+    if any(o is not None for o in others) or alpha != 1.0 or split is None:
+        raise ValueError("gemm_mx_call: a statistics table goes with the q/k-norm epilogue's arguments alone (bias, split)")
+    return fn(a_codes, a_scales, w_codes, w_scales, out, bias, split, norm["qw"], norm["qb"], norm["kw"], norm["kb"], norm.get("cos"),
+              norm.get("sin"), norm["text_rows"], eps=norm.get("eps", 1e-6), k_scale=norm.get("k_scale", 1.0),
+              tensors=norm.get("tensors", 3), fmt=fmt, w_fmt=w_fmt, kernel=kernel, stats=norm["stats"])
+
+
 def gemm_mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8", w_fmt=None, bias=None, res=None, gate0=None,
                  gate1=None, gate_split=0, gate_batch_stride=0, act=None, split=None, alpha=1.0, out_scales=None, out_fmt=None,
                  norm=None, bias_rowscale=None):
@@ -868,9 +903,14 @@ def gemm_mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="mxfp8
     the same, and "mxfp6" activations (with "mxfp6" or "mxfp4" weights) and "mxfp6" output of the quantising epilogue are
     admitted to that kernel as well -- without the flag they stay tiled.  The epilogue follows from the arguments: ``out_scales``
     given = the quantising one (``out`` = the output codes, ``out_fmt``; returns ``(out, out_scales)``); ``norm`` given = the
-    q/k-norm + RoPE one (a dict: qw, qb, kw, kb, cos, sin, text_rows and optionally eps, k_scale, tensors; ``split``
+    q/k-norm + RoPE one (a dict: qw, qb, kw, kb, cos, sin, text_rows and optionally eps, k_scale, tensors, stats; ``split``
     required; returns False, nothing launched, where the library declines the shape); else the bf16 one of ``gemm_mx``, which
-    alone takes ``bias_rowscale`` (fp32 [batch * M], as for ``gemm``)."""
+    alone takes ``bias_rowscale`` (fp32 [batch * M], as for ``gemm``).  A ``norm`` dict with a ``stats`` table goes to
+    ``gemm_mx_qkv_norm_rope(..., kernel=kernel, stats=...)``: bya_mx_gemm_call has no place for a table, and
+    bya_gemm_mx_qkv_norm_rope_stats reads ``kernel`` as this call does."""
+    if norm is not None and norm.get("stats") is not None:
+        return _mx_call_with_stats(gemm_mx_qkv_norm_rope, a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, split, norm,
+                                   (res, gate0, gate1, act, out_scales, bias_rowscale), alpha)
     c, d, n, name = _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, split,
                              (gate_split, gate_batch_stride, act, bias_rowscale, alpha), out_scales, out_fmt, norm, False)
     if not _launch("bya_gemm_mx_call", _SHAPE_LABELS and _label(d, f":{name}:k{int(kernel)}:{fmt}*{w_fmt or fmt}", act), d,
@@ -885,6 +925,9 @@ def gemm_mx_call_plan(a_codes, a_scales, w_codes, w_scales, out, kernel=0, fmt="
     """What ``gemm_mx_call`` would run (``gemm_plan``'s dict): path "t128x128", "t256x256" (mxfp6 activations only) or "p256"
     (``kernel`` 1 or 2, "mxfp8" activations, "mxfp8" or "mxfp4" weights and "mxfp8" output; ``kernel`` 17 or 18: "mxfp6"
     activations and / or "mxfp6" output too); None where the q/k-norm epilogue declines the shape."""
+    if norm is not None and norm.get("stats") is not None:
+        return _mx_call_with_stats(gemm_mx_qkv_norm_rope_plan, a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, split,
+                                   norm, (res, gate0, gate1, act, out_scales, bias_rowscale), alpha)
     c, d, n, name = _mx_call(a_codes, a_scales, w_codes, w_scales, out, kernel, fmt, w_fmt, bias, res, gate0, gate1, split,
                              (gate_split, gate_batch_stride, act, bias_rowscale, alpha), out_scales, out_fmt, norm, True)
     return _plan(("bya_gemm_mx_call", (ctypes.byref(c), ctypes.byref(d))), name == "qkn")

@@ -132,6 +132,26 @@ typedef struct bya_qknorm_desc {
 } bya_qknorm_desc;
 int bya_gemm_qkv_norm_rope(const void* A, const void* W, const void* bias, void* C, const bya_gemm_desc* desc,
                            const bya_qknorm_desc* norm, hipStream_t stream);
+/* The fused q|k|v launches that ALSO record bya_qknorm_rope's score-bound statistics: bya_gemm_qkv_norm_rope_stats here,
+ * bya_gemm_fp8_qkv_norm_rope_stats and bya_gemm_mx_qkv_norm_rope_stats below -- their entry point's arguments plus `stats`,
+ * `stats_slots` in front of the stream.  (Entry points of their own and no new fields: bya_qknorm_desc and bya_mx_gemm_call keep
+ * their size and bytes, so every existing caller's descriptors stay valid as they are.)
+ * stats: bya_qknorm_rope's table, fp32 [stats_slots][2][batch * heads], zero-filled by the caller before the launch; NULL = the
+ * plain entry point's launch.  The kernel raises (atomic maximum on the bit pattern of a non-negative float) entry
+ * [workgroup index % stats_slots][0 = q, 1 = k][index] to the squared Euclidean norm of the finished, bf16-ROUNDED head rows as
+ * it stores them; 1 <= stats_slots <= 64 (BYA_ERR_SHAPE), the table 4-byte aligned (BYA_ERR_ALIGN), both checked before
+ * anything is launched.  `index` is what the two-launch path's bya_qknorm_rope writes: with n_split == width (dense)
+ * z * (width / 64) + head  of batch entry z; with n_split < width (the column blocks of the head-parallel sharded step:
+ * width % n_split == 0, n_split % 64 == 0, desc->batch == 1) the global head (column - tensor * width) / 64.  Column blocks
+ * with desc->batch > 1, or any other n_split: BYA_ERR_UNSUPPORTED.  The maximum over the slots equals bya_qknorm_rope's BIT FOR
+ * BIT (the squares of bf16 values are exact in fp32, their sum runs in the order of csrc/qknorm_math.h, a maximum does not depend
+ * on order); which slot holds it differs.  Rows past M, columns past N and v contribute nothing.  C is the plain entry point's,
+ * bit for bit.  A kernel path that does not record statistics answers BYA_ERR_UNSUPPORTED to a non-NULL table and launches
+ * nothing (the caller then issues the two launches): bya_gemm_qkv_norm_rope_stats records them on every plan path (the STATS
+ * instances of csrc/gemm_v4.hip and gemm_v5.hip); the fp8 and MX forms on path P256 alone.  Every other answer is the plain
+ * entry point's. */
+int bya_gemm_qkv_norm_rope_stats(const void* A, const void* W, const void* bias, void* C, const bya_gemm_desc* desc,
+                                 const bya_qknorm_desc* norm, float* stats, int32_t stats_slots, hipStream_t stream);
 
 /* The same product for SKINNY launches -- at most 64 rows, N <= 8192, N % 16 == 0, K % 32 == 0, K >= 256, no gates, no
  * bias_rowscale, no n_split (anything else: BYA_ERR_UNSUPPORTED) -- on a weight-streaming kernel: one workgroup per 16
@@ -193,6 +213,9 @@ int bya_gemm_bf16_plan(const void* A, const void* W, const void* bias, const voi
  * BYA_ERR_UNSUPPORTED where the entry point declines the shape */
 int bya_gemm_qkv_norm_rope_plan(const void* A, const void* W, const void* bias, const void* C, const bya_gemm_desc* desc,
                                 const bya_qknorm_desc* norm, bya_gemm_plan* plan);
+/* bya_gemm_qkv_norm_rope_stats: the same paths */
+int bya_gemm_qkv_norm_rope_stats_plan(const void* A, const void* W, const void* bias, const void* C, const bya_gemm_desc* desc,
+                                      const bya_qknorm_desc* norm, const float* stats, int32_t stats_slots, bya_gemm_plan* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * fp8 weights (BASELINE configs[4]; no reference counterpart: the reference runs bf16/fp16 only).
@@ -240,7 +263,9 @@ int bya_gemm_fp8_plan(const void* A8, const float* a_scale, const void* W8, cons
  *   restarts per batch entry).  q, k or v is decided per 64-column head, so width % 64 == 0 is enough (a tile may straddle
  *   q | k).  Always ONE launch, on the kernel bya_gemm_fp8 would choose for the same descriptor (option BYA_OPT_FP8_KERNEL, at
  *   least 200 tiles of 256 x 256, eligibility: bya_gemm_fp8_plan's rule) -- the two fp8 kernels differ in last bits, so the
- *   path is never swapped.  The norm statistics of bya_qknorm_rope are not offered.  BYA_ERR_UNSUPPORTED, nothing launched (the
+ *   path is never swapped.  bya_gemm_fp8_qkv_norm_rope_stats (bya_gemm_qkv_norm_rope_stats above) records the norm statistics on
+ *   path P256 (gemm256p_fp8_qkn_stats_kernel); where the launch would take T128X128 a non-NULL table is answered
+ *   BYA_ERR_UNSUPPORTED.  BYA_ERR_UNSUPPORTED, nothing launched (the
  *   caller keeps the two launches): an activation, bias_rowscale, alpha other than 0 / 1, n_split == 0, width % 64, N neither
  *   2 nor 3 widths, a descriptor that describes a residual (ldres or res_batch_stride != 0: there are no residual / gate
  *   arguments), rows or rotary rows beyond the 2 GiB reach of one launch's buffer descriptors.  n_split, c_split_stride, ldc,
@@ -254,6 +279,12 @@ int bya_gemm_fp8_qkv_norm_rope(const void* A8, const float* a_scale, const void*
 int bya_gemm_fp8_qkv_norm_rope_plan(const void* A8, const float* a_scale, const void* W8, const float* w_scale,
                                     const void* bias, const void* C, const bya_gemm_desc* desc, const bya_qknorm_desc* norm,
                                     bya_gemm_plan* plan);
+int bya_gemm_fp8_qkv_norm_rope_stats(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias,
+                                     void* C, const bya_gemm_desc* desc, const bya_qknorm_desc* norm, float* stats,
+                                     int32_t stats_slots, hipStream_t stream);
+int bya_gemm_fp8_qkv_norm_rope_stats_plan(const void* A8, const float* a_scale, const void* W8, const float* w_scale,
+                                          const void* bias, const void* C, const bya_gemm_desc* desc, const bya_qknorm_desc* norm,
+                                          const float* stats, int32_t stats_slots, bya_gemm_plan* plan);
 /* bya_layernorm_fp8: bya_layernorm (same arguments, same arithmetic) followed by bya_quantize_rows_fp8 of each output row,
  * in one pass: the normalised + modulated row is rounded to bf16 exactly as bya_layernorm would store it, then quantised --
  * byte for byte what the two launches produce, without the bf16 round trip.  q uint8 [batch][rows][D] (row stride ldq,
@@ -386,6 +417,17 @@ int bya_gemm_mx_qkv_norm_rope_on(const void* A, const void* a_scales, const void
 int bya_gemm_mx_qkv_norm_rope_on_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
                                       const void* bias, const void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* desc,
                                       const bya_qknorm_desc* norm, int32_t kernel, bya_gemm_plan* plan);
+/* bya_gemm_mx_qkv_norm_rope_on that also records the norm statistics (bya_gemm_qkv_norm_rope_stats above).  `kernel` is
+ * bya_gemm_mx_call's (0, 1, 2, or BYA_MX_KERNEL_FP6 + one of them; anything else BYA_ERR_SHAPE): e2m1 weights and, under the flag,
+ * e2m3 activations are admitted to path P256 as there.  The statistics are recorded on path P256 (every operand pair); where
+ * the launch would take a tiled kernel a non-NULL table is answered BYA_ERR_UNSUPPORTED. */
+int bya_gemm_mx_qkv_norm_rope_stats(const void* A, const void* a_scales, const void* W, const void* w_scales, const void* bias,
+                                    void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* desc, const bya_qknorm_desc* norm,
+                                    int32_t kernel, float* stats, int32_t stats_slots, hipStream_t stream);
+int bya_gemm_mx_qkv_norm_rope_stats_plan(const void* A, const void* a_scales, const void* W, const void* w_scales,
+                                         const void* bias, const void* C, int32_t fmt, int32_t w_fmt, const bya_gemm_desc* desc,
+                                         const bya_qknorm_desc* norm, int32_t kernel, const float* stats, int32_t stats_slots,
+                                         bya_gemm_plan* plan);
 /* Any of the MX GEMMs above as ONE call whose kernel is named by an ARGUMENT (no option is read; BYA_OPT_MX_KERNEL has no say),
  * and the one way e2m1 weights reach the persistent kernel.  The epilogue follows from the fields: `norm` set = the q/k-norm +
  * RoPE epilogue (bya_gemm_mx_qkv_norm_rope); `q_scales` set = the quantising epilogue (bya_gemm_mx_quant: C = the output codes,
