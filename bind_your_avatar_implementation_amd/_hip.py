@@ -66,6 +66,28 @@ class AttnMixSegments(_c.Structure):
     _fields_ = [("n", _i32), ("grp", _i32 * MIX_MAX_SEGMENTS), ("start", _i32 * MIX_MAX_SEGMENTS), ("len", _i32 * MIX_MAX_SEGMENTS)]
 
 
+class AttnMixSamples(_c.Structure):
+    """bya_attn_mix_samples: n and the distance from one sample to the next of every pointer of bya_attn_kv_mix_batch (elements)."""
+    _fields_ = [("n", _i32), ("reserved", _i32), ("q", _i64), ("k", _i64), ("v", _i64), ("r", _i64), ("af", _i64), ("z", _i64),
+                ("wsum", _i64)]
+
+
+class AttnMixMxSamples(_c.Structure):
+    """bya_attn_mix_mx_samples: the same for bya_attn_kv_mix_mx_batch (codes, scales: bytes)."""
+    _fields_ = [("n", _i32), ("reserved", _i32), ("q", _i64), ("k", _i64), ("v", _i64), ("r", _i64), ("af", _i64), ("codes", _i64),
+                ("scales", _i64), ("wsum", _i64)]
+
+
+class RouterScoresSamples(_c.Structure):
+    """bya_router_scores_samples (bya_router_scores_batch)."""
+    _fields_ = [("n", _i32), ("reserved", _i32), ("qr", _i64), ("kr", _i64), ("out", _i64)]
+
+
+class RouterHeadSamples(_c.Structure):
+    """bya_router_head_samples (bya_router_head_batch)."""
+    _fields_ = [("n", _i32), ("reserved", _i32), ("x", _i64), ("r", _i64)]
+
+
 class AttnPlan(_c.Structure):
     _fields_ = [("variant", _i32), ("grid", _i32), ("q_tile", _i32), ("stream_k", _i32), ("sk_rem", _i32), ("sk_cut", _i32),
                 ("o_wide", _i32), ("second_launch", _i32)]
@@ -189,11 +211,21 @@ SIGNATURES = {
                                _i64, _i64, _i64, _i64, _vp],
     "bya_attn_kv_mix_mx_seg_plan": [_vp, _vp, _vp, _c.POINTER(AttnMixDesc), _c.POINTER(AttnMixSegments), _i32, _i64, _i64, _i64,
                                     _i64, _c.POINTER(AttnMixPlan)],
+    "bya_attn_kv_mix_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(AttnMixDesc), AttnMixSamples, _vp],
+    "bya_attn_kv_mix_batch_plan": [_vp, _vp, _c.POINTER(AttnMixDesc), AttnMixSamples, _c.POINTER(AttnMixPlan)],
+    "bya_attn_kv_mix_mx_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(AttnMixDesc), _i32, _i64, _i64, _i64, _i64,
+                                 AttnMixMxSamples, _vp],
+    "bya_attn_kv_mix_mx_batch_plan": [_vp, _vp, _vp, _c.POINTER(AttnMixDesc), _i32, _i64, _i64, _i64, _i64, AttnMixMxSamples,
+                                      _c.POINTER(AttnMixPlan)],
     "bya_attn_tiny": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp],
     "bya_attn_tiny_plan": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _c.POINTER(AttnTinyPlan)],
     "bya_router_scores": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _vp],
     "bya_router_scores_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _c.POINTER(StepPlan)],
     "bya_router_head": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp],
+    "bya_router_scores_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, RouterScoresSamples, _vp],
+    "bya_router_scores_batch_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, RouterScoresSamples, _c.POINTER(StepPlan)],
+    "bya_router_head_batch": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, RouterHeadSamples, _vp],
+    "bya_router_head_batch_plan": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, RouterHeadSamples, _c.POINTER(StepPlan)],
     "bya_forcing_max_over_frames": [_vp, _vp, _i32, _i64, _i32, _vp],
     "bya_masked_combine": [_vp, _vp, _vp, _vp, _i32, _f32, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _vp],
     "bya_routed_mix": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp],

@@ -710,6 +710,65 @@ int mix_seg_plan_of(const bya_attn_mix_segments* s, const bya_attn_mix_desc* d, 
     return BYA_OK;
 }
 
+// bya_attn_kv_mix_batch / _mx_batch, behind the single-sample entry's own checks (p = its plan): the sample strides.  `out` /
+// `out_extent`: the strides of the outputs that are present (z; or codes, scales; wsum where given) and what ONE sample covers of
+// each, in the stride's unit -- samples must not overlap.  The batch exists on the <= 32-key form alone.  On success p->grid is
+// the whole launch's: the single-sample grid (returned in *grid1, blockIdx.x) times n (blockIdx.y).
+int mix_batch_plan_of(int32_t n, const int64_t (&in)[5], const int64_t* out, const long long* out_extent, int n_out,
+                      bya_attn_kv_mix_plan_info* p, int* grid1) {
+    if (n < 1 || n > 65535) return BYA_ERR_SHAPE;
+    if ((in[0] | in[1] | in[2] | in[3] | in[4]) < 0) return BYA_ERR_SHAPE;
+    if ((in[0] | in[1] | in[2]) % 8) return BYA_ERR_ALIGN;                       // q, k, v: 16-byte loads in every sample
+    for (int i = 0; i < n_out; ++i)
+        if (out[i] < 0 || out_extent[i] < 0 || (n > 1 && out[i] < out_extent[i])) return BYA_ERR_SHAPE;
+    if (p->form != BYA_KV_MIX_MIX32) return BYA_ERR_UNSUPPORTED;
+    if ((long long)p->grid * n > 0x7fffffffLL) return BYA_ERR_SHAPE;
+    *grid1 = p->grid;
+    p->grid *= n;
+    return BYA_OK;
+}
+
+// what one sample covers of an output whose row n of group g starts at g * grp + n * row and is `width` wide (-1: a negative
+// stride, which the batch entries refuse: nothing could be said about overlap)
+inline long long mix_extent(const bya_attn_mix_desc* d, long long grp, long long row, long long width) {
+    if (grp < 0 || row < 0) return -1;
+    return (d->n_grp - 1) * grp + (d->Sq - 1) * row + width;
+}
+
+// (every sample takes the form sample 0 takes: a z stride that is no multiple of 8 elements would send the odd samples to the
+// generic form, so it is declined like that form)
+int mix_batch_all_of(const void* z, const bya_attn_mix_desc* d, int has_af, uintptr_t qkv, int has_wsum, const bya_attn_mix_samples& b,
+                     bya_attn_kv_mix_plan_info* p, int* grid1, ByaMixSampleStrides& s) {
+    int rc = mix_plan_of(z, d, has_af, qkv, p);
+    if (rc != BYA_OK) return rc;
+    if (b.z % 4) return BYA_ERR_ALIGN;
+    const int64_t in[5] = {b.q, b.k, b.v, b.r, has_af ? b.af : 0};
+    const int64_t out[2] = {b.z, b.wsum};
+    const long long ext[2] = {mix_extent(d, d->z_grp, d->z_row, (long long)d->heads * d->head_dim), (long long)d->n_grp * d->Sq};
+    rc = mix_batch_plan_of(b.n, in, out, ext, has_wsum ? 2 : 1, p, grid1);
+    if (rc != BYA_OK) return rc;
+    if (b.z % 8) return BYA_ERR_UNSUPPORTED;
+    s = ByaMixSampleStrides{b.q, b.k, b.v, b.r, in[4], b.z, has_wsum ? b.wsum : 0, 0, 0, b.n};
+    return BYA_OK;
+}
+
+int mix_mx_batch_all_of(const void* codes, const void* scales, const bya_attn_mix_desc* d, int has_af, uintptr_t qkv, int has_wsum,
+                        int out_fmt, int64_t c_grp, int64_t c_row, int64_t sc_grp, int64_t sc_row, const bya_attn_mix_mx_samples& b,
+                        bya_attn_kv_mix_plan_info* p, int* grid1, ByaMixSampleStrides& s) {
+    int rc = mix_mx_plan_of(codes, scales, d, has_af, qkv, out_fmt, c_grp, c_row, sc_grp, sc_row, p);
+    if (rc != BYA_OK) return rc;
+    if (b.codes & 3) return BYA_ERR_ALIGN;
+    const long long blocks = (long long)d->heads * d->head_dim / 32;
+    const int64_t in[5] = {b.q, b.k, b.v, b.r, has_af ? b.af : 0};
+    const int64_t out[3] = {b.codes, b.scales, b.wsum};
+    const long long ext[3] = {mix_extent(d, c_grp, c_row, blocks * mx_block_bytes(out_fmt)), mix_extent(d, sc_grp, sc_row, blocks),
+                              (long long)d->n_grp * d->Sq};
+    rc = mix_batch_plan_of(b.n, in, out, ext, has_wsum ? 3 : 2, p, grid1);
+    if (rc != BYA_OK) return rc;
+    s = ByaMixSampleStrides{b.q, b.k, b.v, b.r, in[4], 0, has_wsum ? b.wsum : 0, b.codes, b.scales, b.n};
+    return BYA_OK;
+}
+
 }  // namespace
 
 // Which kernel a descriptor selects (reported to the host so tests and bench.py can say which softmax variant ran).
@@ -815,7 +874,7 @@ extern "C" int bya_attn_kv_mix_mx(const void* q, const void* k, const void* v, c
     ByaMixMxOut out;
     out.codes = static_cast<uint8_t*>(codes); out.scales = static_cast<uint8_t*>(scales);
     out.c_grp = c_grp; out.c_row = c_row; out.s_grp = sc_grp; out.s_row = sc_row; out.fmt = out_fmt;
-    return bya_launch_attn_kv_mix32_mx(q, k, v, r, af, wsum, *d, pl, out, nullptr, stream);
+    return bya_launch_attn_kv_mix32_mx(q, k, v, r, af, wsum, *d, pl, out, nullptr, nullptr, stream);
 }
 
 extern "C" int bya_attn_kv_mix_seg_plan(const void* z, const void* af, const bya_attn_mix_desc* d, const bya_attn_mix_segments* seg,
@@ -866,5 +925,59 @@ extern "C" int bya_attn_kv_mix_mx_seg(const void* q, const void* k, const void* 
     ByaMixMxOut out;
     out.codes = static_cast<uint8_t*>(codes); out.scales = static_cast<uint8_t*>(scales);
     out.c_grp = 0; out.c_row = c_row; out.s_grp = 0; out.s_row = sc_row; out.fmt = out_fmt;
-    return bya_launch_attn_kv_mix32_mx(q, k, v, r, af, wsum, *d, pl, out, seg, stream);
+    return bya_launch_attn_kv_mix32_mx(q, k, v, r, af, wsum, *d, pl, out, seg, nullptr, stream);
+}
+
+extern "C" int bya_attn_kv_mix_batch_plan(const void* z, const void* af, const bya_attn_mix_desc* d, bya_attn_mix_samples batch,
+                                         bya_attn_kv_mix_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_attn_kv_mix_plan_info p;
+    ByaMixSampleStrides s;
+    int grid1;
+    const int rc = mix_batch_all_of(z, d, af != nullptr, 0, batch.wsum != 0, batch, &p, &grid1, s);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_attn_kv_mix_batch(const void* q, const void* k, const void* v, const void* r, const void* af, void* z, float* wsum,
+                                     const bya_attn_mix_desc* d, bya_attn_mix_samples batch, hipStream_t stream) {
+    if (!q || !k || !v || !r || !z || !d) return BYA_ERR_SHAPE;
+    bya_attn_kv_mix_plan_info pl;
+    ByaMixSampleStrides s;
+    int grid1;
+    const int rc = mix_batch_all_of(z, d, af != nullptr, (uintptr_t)q | (uintptr_t)k | (uintptr_t)v, wsum != nullptr || batch.wsum != 0, batch, &pl, &grid1, s);
+    if (rc != BYA_OK) return rc;
+    pl.grid = grid1;
+    return bya_launch_attn_kv_mix32_batch(q, k, v, r, af, z, wsum, *d, pl, s, stream);
+}
+
+extern "C" int bya_attn_kv_mix_mx_batch_plan(const void* codes, const void* scales, const void* af, const bya_attn_mix_desc* d,
+                                            int32_t out_fmt, int64_t c_grp, int64_t c_row, int64_t sc_grp, int64_t sc_row,
+                                            bya_attn_mix_mx_samples batch, bya_attn_kv_mix_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_attn_kv_mix_plan_info p;
+    ByaMixSampleStrides s;
+    int grid1;
+    const int rc = mix_mx_batch_all_of(codes, scales, d, af != nullptr, 0, batch.wsum != 0, out_fmt, c_grp, c_row, sc_grp, sc_row, batch,
+                                       &p, &grid1, s);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_attn_kv_mix_mx_batch(const void* q, const void* k, const void* v, const void* r, const void* af, void* codes,
+                                        void* scales, float* wsum, const bya_attn_mix_desc* d, int32_t out_fmt, int64_t c_grp,
+                                        int64_t c_row, int64_t sc_grp, int64_t sc_row, bya_attn_mix_mx_samples batch,
+                                        hipStream_t stream) {
+    if (!q || !k || !v || !r) return BYA_ERR_SHAPE;
+    bya_attn_kv_mix_plan_info pl;
+    ByaMixSampleStrides s;
+    int grid1;
+    const int rc = mix_mx_batch_all_of(codes, scales, d, af != nullptr, (uintptr_t)q | (uintptr_t)k | (uintptr_t)v,
+                                       wsum != nullptr || batch.wsum != 0, out_fmt, c_grp, c_row, sc_grp, sc_row, batch, &pl, &grid1, s);
+    if (rc != BYA_OK) return rc;
+    pl.grid = grid1;
+    ByaMixMxOut out;
+    out.codes = static_cast<uint8_t*>(codes); out.scales = static_cast<uint8_t*>(scales);
+    out.c_grp = c_grp; out.c_row = c_row; out.s_grp = sc_grp; out.s_row = sc_row; out.fmt = out_fmt;
+    return bya_launch_attn_kv_mix32_mx(q, k, v, r, af, wsum, *d, pl, out, nullptr, &s, stream);
 }

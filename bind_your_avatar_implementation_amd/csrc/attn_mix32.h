@@ -1,7 +1,8 @@
 // The <= 32-key form of bya_attn_kv_mix (attn_mix32_body) and the fragment helpers it shares with the attention kernels of
-// attn.hip.  Three translation units instantiate it: attn.hip (the bf16 instances), attn_mix_seg.hip (the bf16 instance that
-// takes its rows from a segment table, bya_attn_kv_mix_seg) and attn_mix_mx.hip (the MX-output instances of both, built without
-// the SLP vectoriser like every translation unit that holds a quantiser: build.py, NO_SLP_SOURCES).
+// attn.hip.  Four translation units instantiate it: attn.hip (the bf16 instances), attn_mix_seg.hip (the bf16 instance that
+// takes its rows from a segment table, bya_attn_kv_mix_seg), attn_mix_batch.hip (the bf16 instances whose blockIdx.y is the sample
+// of a batch, bya_attn_kv_mix_batch) and attn_mix_mx.hip (the MX-output instances of all three, built without the SLP vectoriser
+// like every translation unit that holds a quantiser: build.py, NO_SLP_SOURCES).
 #pragma once
 #include "attn_common.h"
 #include "routing_weights.h"
@@ -9,6 +10,9 @@
 // Where the MX-output instances write (bya_attn_kv_mix_mx): strides in BYTES, fmt = MX_E4M3 / MX_E2M3.  A named type with
 // external linkage: it crosses from attn.hip to attn_mix_mx.hip in bya_launch_attn_kv_mix32_mx's signature.
 struct ByaMixMxOut { uint8_t* codes; uint8_t* scales; long long c_grp, c_row, s_grp, s_row; int fmt; };
+// What separates the samples of a batch launch (bya_attn_kv_mix_batch / _mx_batch): elements of each pointer's type, codes and
+// scales in BYTES; n samples.  External linkage for the same reason.
+struct ByaMixSampleStrides { long long q, k, v, r, af, z, wsum, codes, scales; int n; };
 
 namespace {
 
@@ -82,6 +86,28 @@ struct MixMxArgs { MixArgs a; ByaMixMxOut mx; };
 // captured graph holds it.  There MixArgs.n_grp / Sq bound the table (checked on the host) and the kernel reads neither.
 struct MixSegArgs { MixArgs a; bya_attn_mix_segments seg; };
 struct MixMxSegArgs { MixArgs a; ByaMixMxOut mx; bya_attn_mix_segments seg; };
+// The batch instances (bya_attn_kv_mix_batch / _mx_batch): sample blockIdx.y of a launch is the single-sample launch with every
+// pointer advanced by its stride (ByaMixSampleStrides).  By value like the segment table.
+struct MixBatchArgs { MixArgs a; ByaMixSampleStrides s; };
+struct MixMxBatchArgs { MixArgs a; ByaMixMxOut mx; ByaMixSampleStrides s; };
+
+// the arguments of sample blockIdx.y: what attn_mix32_body gets in a batch instance.  The body below it is the single-sample
+// launch's, blockIdx.x walks the (group, head, row chunk) of ONE sample as there: a row's arithmetic does not know the batch.
+__device__ __forceinline__ MixArgs mix_sample_args(const MixArgs& a, const ByaMixSampleStrides& s) {
+    const long long b = blockIdx.y;
+    MixArgs p = a;
+    p.q += b * s.q; p.k += b * s.k; p.v += b * s.v; p.r += b * s.r;
+    if (p.af) p.af += b * s.af;
+    if (p.z) p.z += b * s.z;
+    if (p.wsum) p.wsum += b * s.wsum;
+    return p;
+}
+__device__ __forceinline__ ByaMixMxOut mix_sample_out(const ByaMixMxOut& o, const ByaMixSampleStrides& s) {
+    const long long b = blockIdx.y;
+    ByaMixMxOut m = o;
+    m.codes += b * s.codes; m.scales += b * s.scales;
+    return m;
+}
 
 // bya_attn_kv_mix's descriptor -> kernel arguments (z and its strides: the bf16 entry's alone)
 inline void mix_args_of(const void* q, const void* k, const void* v, const void* r, const void* af, float* wsum,
@@ -322,11 +348,17 @@ __device__ __forceinline__ void attn_mix32_body(const MixArgs& p, char* smem, co
 
 // defined in attn_mix_mx.hip: the launch of the MX-output instances of the <= 32-key form for checked arguments (q .. wsum and
 // desc as for bya_attn_kv_mix, plan = its launch decisions, out = where the codes and scale bytes go, seg = NULL or the checked
-// table of the segment instance); called from bya_attn_kv_mix_mx and bya_attn_kv_mix_mx_seg
+// table of the segment instance, batch = NULL or the checked sample strides of the batch instance -- never both; plan.grid is
+// then the grid of ONE sample); called from bya_attn_kv_mix_mx, bya_attn_kv_mix_mx_seg and bya_attn_kv_mix_mx_batch
 int bya_launch_attn_kv_mix32_mx(const void* q, const void* k, const void* v, const void* r, const void* af, float* wsum,
                                 const bya_attn_mix_desc& desc, const bya_attn_kv_mix_plan_info& plan, const ByaMixMxOut& out,
-                                const bya_attn_mix_segments* seg, hipStream_t stream);
+                                const bya_attn_mix_segments* seg, const ByaMixSampleStrides* batch, hipStream_t stream);
 // defined in attn_mix_seg.hip: the launch of the bf16 segment instance for checked arguments; called from bya_attn_kv_mix_seg
 int bya_launch_attn_kv_mix32_seg(const void* q, const void* k, const void* v, const void* r, const void* af, void* z, float* wsum,
                                  const bya_attn_mix_desc& desc, const bya_attn_kv_mix_plan_info& plan,
                                  const bya_attn_mix_segments& seg, hipStream_t stream);
+// defined in attn_mix_batch.hip: the launch of the bf16 batch instances for checked arguments (plan.grid = the grid of ONE sample,
+// batch = the checked sample strides); called from bya_attn_kv_mix_batch
+int bya_launch_attn_kv_mix32_batch(const void* q, const void* k, const void* v, const void* r, const void* af, void* z, float* wsum,
+                                   const bya_attn_mix_desc& desc, const bya_attn_kv_mix_plan_info& plan,
+                                   const ByaMixSampleStrides& batch, hipStream_t stream);

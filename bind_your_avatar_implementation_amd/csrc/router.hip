@@ -14,14 +14,18 @@ namespace {
 
 constexpr int R_HEADS = 16, R_TOK = 32, R_HD = 128, R_QK = R_HEADS * R_HD, R_FEAT = R_HEADS * R_TOK;
 
+// What separates the samples of a batch launch (bya_router_scores_batch), in elements: blockIdx.y is the sample, blockIdx.x walks
+// one sample's tiles exactly as the single-sample launch does.
+struct ScoresSamples { long long qr, kr, out; };
+
 // One wave = 16 video tokens of one identity.  S^T tile (16 face tokens x 16 video tokens) per (head, half):
 // A = kr rows (face token), B = qr rows (video token), v_mfma_f32_16x16x32_bf16, K = 128 = 4 steps.
 // Lane (c = lane&15, g = lane>>4) ends up with score(video token c, face token 16j + 4g + e, head h) in
 // acc[h][j][e]; output feature index = face_token * 16 + h  (router.py:389-390 permute + reshape).
-__global__ __launch_bounds__(256) void router_scores_kernel(const bf16_t* __restrict__ qr, const bf16_t* __restrict__ kr,
-                                                            const bf16_t* __restrict__ ln_w, const bf16_t* __restrict__ ln_b,
-                                                            const bf16_t* __restrict__ pos, bf16_t* __restrict__ out,
-                                                            int n_id, long long N, float eps) {
+__device__ __forceinline__ void router_scores_body(const bf16_t* __restrict__ qr, const bf16_t* __restrict__ kr,
+                                                   const bf16_t* __restrict__ ln_w, const bf16_t* __restrict__ ln_b,
+                                                   const bf16_t* __restrict__ pos, bf16_t* __restrict__ out,
+                                                   int n_id, long long N, float eps) {
     const int lane = threadIdx.x & 63;
     const long long tiles = (N + 15) / 16;
     const long long wid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -101,10 +105,10 @@ __global__ __launch_bounds__(256) void router_scores_kernel(const bf16_t* __rest
 // sixteen rows of a fragment read hit sixteen different chunks), and the waves walk the identity's 16-token tiles on their
 // own: per tile 64 global loads (q only; nothing else competes for the vector-memory queue), 128 ds_read_b128, 128 MFMAs,
 // the same LayerNorm + positional epilogue.  Same MFMA order per accumulator -> bit-identical.
-__global__ __launch_bounds__(512) void router_scores_lds_kernel(const bf16_t* __restrict__ qr, const bf16_t* __restrict__ kr,
-                                                                const bf16_t* __restrict__ ln_w, const bf16_t* __restrict__ ln_b,
-                                                                const bf16_t* __restrict__ pos, bf16_t* __restrict__ out,
-                                                                int n_id, long long N, float eps) {
+__device__ __forceinline__ void router_scores_lds_body(const bf16_t* __restrict__ qr, const bf16_t* __restrict__ kr,
+                                                       const bf16_t* __restrict__ ln_w, const bf16_t* __restrict__ ln_b,
+                                                       const bf16_t* __restrict__ pos, bf16_t* __restrict__ out,
+                                                       int n_id, long long N, float eps) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -205,9 +209,9 @@ __global__ __launch_bounds__(512) void router_scores_lds_kernel(const bf16_t* __
 }
 
 // r[n, id] = sigmoid(x[id, n, :] . w + b); D = 512: one wave per row, 8 elements per lane.
-__global__ __launch_bounds__(256) void router_head_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
-                                                          const bf16_t* __restrict__ b, bf16_t* __restrict__ r, int n_id,
-                                                          long long N, int D) {
+__device__ __forceinline__ void router_head_body(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+                                                 const bf16_t* __restrict__ b, bf16_t* __restrict__ r, int n_id,
+                                                 long long N, int D) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= N * n_id) return;
@@ -226,6 +230,35 @@ __global__ __launch_bounds__(256) void router_head_kernel(const bf16_t* __restri
         const float z = bf2f(f2bf(acc + bf2f(b[0])));   // Linear output is bf16 before the sigmoid
         r[n * n_id + id] = f2bf(1.0f / (1.0f + __expf(-z)));
     }
+}
+
+// The kernels: the bodies above as they always were launched (one sample), and with blockIdx.y = the sample of a batch
+// (bya_router_scores_batch / bya_router_head_batch): the same body on that sample's pointers, blockIdx.x / gridDim.x walk one sample.
+#define SCORES_PARAMS const bf16_t* __restrict__ qr, const bf16_t* __restrict__ kr, const bf16_t* __restrict__ ln_w, \
+                      const bf16_t* __restrict__ ln_b, const bf16_t* __restrict__ pos, bf16_t* __restrict__ out, int n_id, \
+                      long long N, float eps
+__global__ __launch_bounds__(256) void router_scores_kernel(SCORES_PARAMS) {
+    router_scores_body(qr, kr, ln_w, ln_b, pos, out, n_id, N, eps);
+}
+__global__ __launch_bounds__(256) void router_scores_batch_kernel(SCORES_PARAMS, ScoresSamples bs) {
+    router_scores_body(qr + blockIdx.y * bs.qr, kr + blockIdx.y * bs.kr, ln_w, ln_b, pos, out + blockIdx.y * bs.out, n_id, N, eps);
+}
+__global__ __launch_bounds__(512) void router_scores_lds_kernel(SCORES_PARAMS) {
+    router_scores_lds_body(qr, kr, ln_w, ln_b, pos, out, n_id, N, eps);
+}
+__global__ __launch_bounds__(512) void router_scores_lds_batch_kernel(SCORES_PARAMS, ScoresSamples bs) {
+    router_scores_lds_body(qr + blockIdx.y * bs.qr, kr + blockIdx.y * bs.kr, ln_w, ln_b, pos, out + blockIdx.y * bs.out, n_id, N, eps);
+}
+#undef SCORES_PARAMS
+__global__ __launch_bounds__(256) void router_head_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+                                                          const bf16_t* __restrict__ b, bf16_t* __restrict__ r, int n_id,
+                                                          long long N, int D) {
+    router_head_body(x, w, b, r, n_id, N, D);
+}
+__global__ __launch_bounds__(256) void router_head_batch_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+                                                                const bf16_t* __restrict__ b, bf16_t* __restrict__ r, int n_id,
+                                                                long long N, int D, long long x_sample, long long r_sample) {
+    router_head_body(x + blockIdx.y * x_sample, w, b, r + blockIdx.y * r_sample, n_id, N, D);
 }
 
 // Tiny self-attention: one wave per (sequence, head); lane = head-dim index (64).
@@ -392,33 +425,130 @@ extern "C" int bya_router_scores_plan(const void* qr, const void* kr, const void
     return rc;
 }
 
+// the launch of bya_router_scores / _batch for checked arguments: pl = ONE sample's plan (its grid in x); n = 0: the single-sample
+// kernel, else the batch kernel with n samples in y
+static int launch_scores(const void* qr, const void* kr, const void* ln_w, const void* ln_b, const void* pos_emb, void* out,
+                         int32_t n_id, int64_t N, float eps, const bya_step_plan_info& pl, int n, const ScoresSamples& bs,
+                         hipStream_t stream) {
+    const dim3 grid((unsigned)pl.grid, (unsigned)(n > 0 ? n : 1));
+#define SCORES_ARGS (const bf16_t*)qr, (const bf16_t*)kr, (const bf16_t*)ln_w, (const bf16_t*)ln_b, (const bf16_t*)pos_emb, \
+                    (bf16_t*)out, n_id, (long long)N, eps
+    if (pl.kernel == BYA_ROUTER_SCORES_LDS) {
+        const size_t lds = (size_t)R_TOK * R_QK * 2;
+        static std::atomic<unsigned long long> big{0}, bbig{0};
+        const int rc = n ? bya_allow_big_lds(reinterpret_cast<const void*>(router_scores_lds_batch_kernel), 160 * 1024, bbig)
+                         : bya_allow_big_lds(reinterpret_cast<const void*>(router_scores_lds_kernel), 160 * 1024, big);
+        if (rc != BYA_OK) return BYA_ERR_LAUNCH;
+        if (n) BYA_LAUNCH(router_scores_lds_batch_kernel, grid, dim3(512), lds, stream, SCORES_ARGS, bs);
+        else BYA_LAUNCH(router_scores_lds_kernel, grid, dim3(512), lds, stream, SCORES_ARGS);
+        return ok();
+    }
+    if (n) BYA_LAUNCH(router_scores_batch_kernel, grid, dim3(256), 0, stream, SCORES_ARGS, bs);
+    else BYA_LAUNCH(router_scores_kernel, grid, dim3(256), 0, stream, SCORES_ARGS);
+#undef SCORES_ARGS
+    return ok();
+}
+
 extern "C" int bya_router_scores(const void* qr, const void* kr, const void* ln_w, const void* ln_b,
                                  const void* pos_emb, void* out, int32_t n_id, int64_t N, int32_t heads,
                                  int32_t face_tokens, float eps, hipStream_t stream) {
     bya_step_plan_info pl;
     const int rc = scores_plan_of(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, heads, face_tokens, &pl);
     if (rc != BYA_OK) return rc;
-    if (pl.kernel == BYA_ROUTER_SCORES_LDS) {
-        static std::atomic<unsigned long long> big{0};
-        if (bya_allow_big_lds(reinterpret_cast<const void*>(router_scores_lds_kernel), 160 * 1024, big) != BYA_OK) return BYA_ERR_LAUNCH;
-        BYA_LAUNCH(router_scores_lds_kernel, dim3((unsigned)pl.grid), dim3(512), (size_t)R_TOK * R_QK * 2, stream,
-                   (const bf16_t*)qr, (const bf16_t*)kr, (const bf16_t*)ln_w, (const bf16_t*)ln_b,
-                   (const bf16_t*)pos_emb, (bf16_t*)out, n_id, (long long)N, eps);
-        return ok();
-    }
-    BYA_LAUNCH(router_scores_kernel, dim3((unsigned)pl.grid), dim3(256), 0, stream,
-                       (const bf16_t*)qr, (const bf16_t*)kr, (const bf16_t*)ln_w, (const bf16_t*)ln_b,
-                       (const bf16_t*)pos_emb, (bf16_t*)out, n_id, (long long)N, eps);
-    return ok();
+    return launch_scores(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, eps, pl, 0, ScoresSamples{0, 0, 0}, stream);
+}
+
+// bya_router_scores_batch behind bya_router_scores' own checks (p = one sample's plan, whose grid comes back in *grid1): n and the
+// sample strides.  Every sample's pointers keep the 16-byte alignment of sample 0; the outputs of two samples do not overlap.
+static int scores_batch_plan_of(int32_t n_id, int64_t N, const bya_router_scores_samples& b, bya_step_plan_info* p, int* grid1) {
+    if (b.n < 1 || b.n > 65535 || (b.qr | b.kr | b.out) < 0) return BYA_ERR_SHAPE;
+    if ((b.qr | b.kr | b.out) % 8) return BYA_ERR_ALIGN;
+    if (b.n > 1 && b.out < (long long)n_id * N * R_FEAT) return BYA_ERR_SHAPE;
+    if ((long long)p->grid * b.n > 0x7fffffffLL) return BYA_ERR_SHAPE;
+    *grid1 = p->grid;
+    p->grid *= b.n;
+    return BYA_OK;
+}
+
+extern "C" int bya_router_scores_batch_plan(const void* qr, const void* kr, const void* ln_w, const void* ln_b, const void* pos_emb,
+                                            const void* out, int32_t n_id, int64_t N, int32_t heads, int32_t face_tokens,
+                                            bya_router_scores_samples batch, bya_step_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_step_plan_info p;
+    int grid1;
+    int rc = scores_plan_of(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, heads, face_tokens, &p);
+    if (rc == BYA_OK) rc = scores_batch_plan_of(n_id, N, batch, &p, &grid1);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_router_scores_batch(const void* qr, const void* kr, const void* ln_w, const void* ln_b, const void* pos_emb,
+                                       void* out, int32_t n_id, int64_t N, int32_t heads, int32_t face_tokens, float eps,
+                                       bya_router_scores_samples batch, hipStream_t stream) {
+    bya_step_plan_info pl;
+    int grid1;
+    int rc = scores_plan_of(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, heads, face_tokens, &pl);
+    if (rc == BYA_OK) rc = scores_batch_plan_of(n_id, N, batch, &pl, &grid1);
+    if (rc != BYA_OK) return rc;
+    pl.grid = grid1;
+    return launch_scores(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, eps, pl, batch.n, ScoresSamples{batch.qr, batch.kr, batch.out},
+                         stream);
+}
+
+// bya_router_head: argument checks and the grid of one sample (launcher and bya_router_head_batch_plan)
+static int head_plan_of(const void* x, const void* w, const void* b, const void* r, int32_t n_id, int64_t N, int32_t D,
+                        bya_step_plan_info* p) {
+    if (!x || !w || !b || !r || n_id <= 0 || N <= 0 || D <= 0 || D % 512) return BYA_ERR_SHAPE;
+    if (((uintptr_t)x | (uintptr_t)w) & 15) return BYA_ERR_ALIGN;
+    p->kernel = 0;
+    p->reserved = 0;
+    p->items = (long long)N * n_id;                                // one wave per (identity, row)
+    p->grid = (int32_t)((p->items + 3) / 4);
+    p->items_per_round = p->items;
+    p->rounds = 1;
+    return BYA_OK;
 }
 
 extern "C" int bya_router_head(const void* x, const void* w, const void* b, void* r, int32_t n_id, int64_t N,
                                int32_t D, hipStream_t stream) {
-    if (!x || !w || !b || !r || n_id <= 0 || N <= 0 || D <= 0 || D % 512) return BYA_ERR_SHAPE;
-    if (((uintptr_t)x | (uintptr_t)w) & 15) return BYA_ERR_ALIGN;
-    const long long rows = (long long)N * n_id;
-    BYA_LAUNCH(router_head_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, (const bf16_t*)x,
+    bya_step_plan_info pl;
+    const int rc = head_plan_of(x, w, b, r, n_id, N, D, &pl);
+    if (rc != BYA_OK) return rc;
+    BYA_LAUNCH(router_head_kernel, dim3((unsigned)pl.grid), dim3(256), 0, stream, (const bf16_t*)x,
                        (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)r, n_id, (long long)N, D);
+    return ok();
+}
+
+static int head_batch_plan_of(int32_t n_id, int64_t N, const bya_router_head_samples& b, bya_step_plan_info* p, int* grid1) {
+    if (b.n < 1 || b.n > 65535 || (b.x | b.r) < 0) return BYA_ERR_SHAPE;
+    if (b.x % 8) return BYA_ERR_ALIGN;
+    if (b.n > 1 && b.r < (long long)n_id * N) return BYA_ERR_SHAPE;
+    if ((long long)p->grid * b.n > 0x7fffffffLL) return BYA_ERR_SHAPE;
+    *grid1 = p->grid;
+    p->grid *= b.n;
+    return BYA_OK;
+}
+
+extern "C" int bya_router_head_batch_plan(const void* x, const void* w, const void* b, const void* r, int32_t n_id, int64_t N,
+                                          int32_t D, bya_router_head_samples batch, bya_step_plan_info* plan) {
+    if (!plan) return BYA_ERR_SHAPE;
+    bya_step_plan_info p;
+    int grid1;
+    int rc = head_plan_of(x, w, b, r, n_id, N, D, &p);
+    if (rc == BYA_OK) rc = head_batch_plan_of(n_id, N, batch, &p, &grid1);
+    if (rc == BYA_OK) *plan = p;
+    return rc;
+}
+
+extern "C" int bya_router_head_batch(const void* x, const void* w, const void* b, void* r, int32_t n_id, int64_t N, int32_t D,
+                                     bya_router_head_samples batch, hipStream_t stream) {
+    bya_step_plan_info pl;
+    int grid1;
+    int rc = head_plan_of(x, w, b, r, n_id, N, D, &pl);
+    if (rc == BYA_OK) rc = head_batch_plan_of(n_id, N, batch, &pl, &grid1);
+    if (rc != BYA_OK) return rc;
+    BYA_LAUNCH(router_head_batch_kernel, dim3((unsigned)grid1, (unsigned)batch.n), dim3(256), 0, stream, (const bf16_t*)x,
+                       (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)r, n_id, (long long)N, D, (long long)batch.x, (long long)batch.r);
     return ok();
 }
 

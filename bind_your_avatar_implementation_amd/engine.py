@@ -116,6 +116,7 @@ class DenoiseEngine:
         self.L = len(model.transformer_blocks)
         self.Tt_max = self.cfg.max_text_seq_length
         self.cache_invariants = False
+        self._cache_generation = 0               # bumped whenever the conditioning cache is rebuilt or dropped (cache_identity)
         # softmax scale * log2(e) of the joint attention is folded into k where k is finished in fp32 (q/k-norm + RoPE
         # kernel), so the attention kernel's scores are born in exp2 units (no per-score multiply)
         self.k_scale = (self.cfg.attention_head_dim ** -0.5) * 1.4426950408889634
@@ -191,6 +192,11 @@ class DenoiseEngine:
         # (tests/test_mx_cross_out_gpu.py) counts the launches per partial frame of the DEFAULT step, so the default moves
         # together with that test (tests/test_sp_segment_mix_gpu.py runs both settings against each other)
         self.sp_segment_mix = os.environ.get("BYA_SP_SEGMENT_MIX", "0") == "1"
+        # B >= 2 (the [uncond, cond] pair of a guided step), unsharded: the face / audio kv-mix and the router's scores and head
+        # take the batch as a grid dimension -- one launch per layer instead of one per sample, the same bytes
+        # (bya_attn_kv_mix_batch, bya_router_scores_batch, bya_router_head_batch).  Off by default: one GPU shows no gain beyond run-to-run spread (DESIGN.md
+        # section 5, "The guided step's [uncond, cond] pair").
+        self.batch_launches = bool(getattr(model, "batch_launches", False)) or os.environ.get("BYA_BATCH_LAUNCHES") == "1"
         if os.environ.get("BYA_SP_OVERLAP_V") == "all":
             self.SP_OVERLAP_V_MIN_ROWS = 0
         self.router_replicated = os.environ.get("BYA_ROUTER_REPLICATED", "0") == "1"
@@ -230,6 +236,7 @@ class DenoiseEngine:
             return False
         self._pack()
         self._inv_cache = {}
+        self._cache_generation += 1
         self.m._graphs = {}
         return True
 
@@ -708,6 +715,7 @@ class DenoiseEngine:
         launches produce them).  ``release()`` drops the cache and returns to the reference's recompute-every-step."""
         self.cache_invariants = True
         self._inv_cache = {}
+        self._new_cache_generation()
         n_id = self._count_ids(id_cond, audio_embeds)
         if self.m.is_train_face and id_cond is not None:
             B = id_cond[0].shape[0]
@@ -721,6 +729,37 @@ class DenoiseEngine:
     def release(self):
         self.cache_invariants = False
         self._inv_cache = {}
+        self._new_cache_generation()
+
+    def _new_cache_generation(self):
+        """The conditioning cache was rebuilt or dropped: graphs captured against the old one (they read its tensors in place,
+        transformer._graphed_step) can never be keyed again -- drop them, and with them their hold on those tensors."""
+        self._cache_generation += 1
+        graphs = getattr(self.m, "_graphs", None)
+        if graphs:
+            self.m._graphs = {k: e for k, e in graphs.items() if e.cache_hold is None}
+
+    def cache_identity(self, id_cond, id_vit_hidden, audio_embeds):
+        """-> (identity, holds) when the precomputed conditioning serves a step with exactly these tensors -- every part the step
+        would compute is cached under the ``_key`` of what is passed --, else None.  ``identity`` (hashable): the generation of the
+        cache and those keys; ``holds``: the cache entries (inputs and results), for whoever reads them in place to keep alive."""
+        if not self.cache_invariants:
+            return None
+        m = self.m
+        n_id = self._count_ids(id_cond, audio_embeds)
+        parts = []
+        if m.is_train_face and id_cond is not None:
+            parts.append(("face", list(id_cond[:n_id]) + [t for i in range(n_id) for t in id_vit_hidden[i]]))
+        if m.is_train_audio and audio_embeds is not None:
+            parts.append(("audio", [audio_embeds]))
+        keys, holds = [], []
+        for name, tensors in parts:
+            hit = self._inv_cache.get(name)
+            if hit is None or hit[0] != _key(tensors):
+                return None
+            keys.append((name, hit[0]))
+            holds.append(hit)
+        return ((self._cache_generation, tuple(keys)), holds) if parts else None
 
     # ------------------------------------------------------------------------------------------ the step
     @torch.no_grad()
@@ -1002,6 +1041,12 @@ class DenoiseEngine:
                     kvs_p = (ntok * 2 * inner_p, 0, 2 * inner_p)
 
                     def face_mix(z, mx):
+                        if self.batch_launches and B >= 2:          # one launch for the batch; declined: the loop below
+                            to = dict(z_strides=(0, inner_p)) if mx is None else dict(mx_out=(*mx, self.mx_fmt))
+                            if ops.attn_kv_mix_batch(qp, kv_l, kv_l[..., inner_p:], r_logits, None, z, head_dim=hd_p, heads=16,
+                                                     n_id=n_id, n_grp=1, Sq=N_loc, Skv=ntok, q_strides=(0, inner_p),
+                                                     k_strides=kvs_p, v_strides=kvs_p, scale=hd_p ** -0.5, **to) is not False:
+                                return None
                         for b in range(B):
                             rb = r_logits[b if r_logits.shape[0] > 1 else 0]
                             to = dict(z_strides=(0, inner_p)) if mx is None else dict(mx_out=(mx[0][b], mx[1][b], self.mx_fmt))
@@ -1047,6 +1092,12 @@ class DenoiseEngine:
 
                     def audio_mix(z, mx):
                         # the MX pair's rows are the rank's own, like z's: a segment writes at a byte offset of `start` rows
+                        if self.batch_launches and B >= 2 and not sh.active:      # one launch for the batch; declined: the loop
+                            to = dict(z_strides=(per_frame * D, D)) if mx is None else dict(mx_out=(*mx, self.mx_fmt))
+                            if ops.attn_kv_mix_batch(qa, ka, va, r_logits, af, z, wsum, head_dim=64, heads=H, n_id=n_id, n_grp=T,
+                                                     Sq=per_frame, Skv=ntok, q_strides=(per_frame * D, D), k_strides=kvs,
+                                                     v_strides=kvs, scale=64 ** -0.5, **to) is not False:
+                                return None
                         for b in range(B):
                             rb = r_logits[b if r_logits.shape[0] > 1 else 0]
                             if not sh.active:
@@ -1202,9 +1253,15 @@ class DenoiseEngine:
         qr = ops.gemm(qn, self.r_to_q[ca], buf("r_qr", B, N_loc, qk))
         rs = buf("r_s_loc", B, n_id, N_loc, F)
         pos = self.r_pos[sh.v0:sh.v1]
-        for b in range(B):
-            ops.router_scores(qr[b], kr[b].contiguous(), r.norm.weight, r.norm.bias, pos, rs[b], n_id, N_loc,
-                              eps=r.norm.eps)
+        # one launch for the batch; declined: the loop per sample.  (kr is _face_invariants' [B, n_id, 32, qk] view of one fresh
+        # buffer per layer, computed or cached: every sample's keys are contiguous, which both forms need -- the loop's
+        # .contiguous() is a no-op, ops.router_scores_batch asserts it)
+        batched = self.batch_launches and B >= 2
+        if not (batched and
+                ops.router_scores_batch(qr, kr, r.norm.weight, r.norm.bias, pos, rs, n_id, N_loc, eps=r.norm.eps) is not False):
+            for b in range(B):
+                ops.router_scores(qr[b], kr[b].contiguous(), r.norm.weight, r.norm.bias, pos, rs[b], n_id, N_loc,
+                                  eps=r.norm.eps)
         # exchange B: the spatial / temporal attentions mix tokens across the whole clip -> gather the 512-wide
         # router rows (36 MB) and run the four small blocks replicated
         if sh.active:
@@ -1233,8 +1290,9 @@ class DenoiseEngine:
         logits = buf("r_logits", B, N, n_id)
         fp = r.final_proj[0]
         rs4 = rs2.view(B, n_id, N, F)
-        for b in range(B):
-            ops.router_head(rs4[b], fp.weight, fp.bias, logits[b], n_id, N)
+        if not (batched and ops.router_head_batch(rs4, fp.weight, fp.bias, logits, n_id, N) is not False):
+            for b in range(B):
+                ops.router_head(rs4[b], fp.weight, fp.bias, logits[b], n_id, N)
         if taps is not None:
             for b in range(B):
                 taps[f"router{ca}_b{b}"] = logits[b:b + 1].clone()

@@ -1362,6 +1362,72 @@ def attn_kv_mix_segments_plan(z, af=None, *, segments, head_dim, heads, n_id, n_
     return plan
 
 
+def _sample_stride(t, n, name):
+    """Elements from one sample to the next of a tensor whose first dimension is the batch; one sample for the whole batch
+    (shape[0] == 1) is a stride of 0."""
+    if t.shape[0] not in (1, n):
+        raise ValueError(f"{name}: first dimension {t.shape[0]}, expected the {n} samples of the batch (or 1: shared)")
+    return t.stride(0) if t.shape[0] > 1 else 0
+
+
+def _mix_batch_call(qkvr, af, z, wsum, mx_out, plan, n, **kw):
+    """``_mix_call`` for sample 0 of tensors that carry the batch in front, with the bya_attn_mix_samples / _mx_samples of their
+    first-dimension strides behind the arguments: the call of ``attn_kv_mix_batch`` or its query."""
+    first = lambda t: None if t is None else t[0]
+    mx0 = None if mx_out is None else (mx_out[0][0], mx_out[1][0], mx_out[2])
+    mx, (entry, args) = _mix_call(tuple(first(t) for t in qkvr), first(af), first(z), first(wsum), mx0, plan, **kw)
+    s = _hip.AttnMixSamples() if mx is None else _hip.AttnMixMxSamples()
+    s.n = n
+    for name, t in zip("qkvr", qkvr):
+        setattr(s, name, _sample_stride(t, n, name))
+    s.af = 0 if af is None else _sample_stride(af, n, "af")
+    s.wsum = 0 if wsum is None else _sample_stride(wsum, n, "wsum")
+    if mx is None:
+        s.z = _sample_stride(z, n, "z")
+    else:
+        s.codes, s.scales = _sample_stride(mx_out[0], n, "mx_out codes"), _sample_stride(mx_out[1], n, "mx_out scales")
+    return mx, (entry + "_batch", (*args, s))
+
+
+def attn_kv_mix_batch(q, k, v, r, af, z, wsum=None, *, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides,
+                      z_strides=None, scale, mx_out=None):
+    """``attn_kv_mix`` for a batch of samples in ONE launch: every tensor carries the batch in front -- q [n, ..], k / v [n, ..],
+    r [n or 1, n_grp * Sq, n_id] (1: one forcing tensor for the whole batch), af None or [n, n_id, n_id], z [n, ..], wsum None or
+    [n, n_grp * Sq], ``mx_out`` = (codes [n, ..], scales [n, ..], fmt) -- and the strides given are those WITHIN a sample, as for
+    ``attn_kv_mix`` on ``q[b]``, ``k[b]`` ...  Byte for byte those n launches.  Returns z, or the MX pair, or False (nothing
+    launched, nothing counted) where the library has no batch form (more than 32 keys, the generic reference form, a z that is
+    not 16-byte aligned in every sample): the caller then issues the launches per sample."""
+    n = q.shape[0]
+    mx, call = _mix_batch_call((q, k, v, r), af, z, wsum, mx_out, False, n, head_dim=head_dim, heads=heads, n_id=n_id, n_grp=n_grp, Sq=Sq,
+                               Skv=Skv, q_strides=q_strides, k_strides=k_strides, v_strides=v_strides, z_strides=z_strides, scale=scale)
+    launched = _launch(None, None, 4.0 * n * n_id * n_grp * heads * Sq * Skv * head_dim, call, True)
+    return launched and (z if mx is None else (mx_out[0], mx_out[1]))
+
+
+def attn_kv_mix_batch_plan(z, af=None, *, n, head_dim, heads, n_id, n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides=None,
+                           scale=1.0, mx_out=None, sample_strides=None):
+    """What ``attn_kv_mix_batch`` would run (host-side; meta tensors may stand for device tensors): ``attn_kv_mix_plan``'s dict of
+    ONE sample with "grid" multiplied by ``n`` -- or None where the library declines the batch form.  z / af / the MX pair carry
+    the batch in front; ``sample_strides`` = {"q", "k", "v", "r", "wsum": elements from one sample to the next} for the operands
+    the query does not see (default: 0)."""
+    mx0 = None if mx_out is None else (mx_out[0][0], mx_out[1][0], mx_out[2])
+    mx, (entry, args) = _mix_call((), None if af is None else af[0], None if z is None else z[0], None, mx0, True, head_dim, heads, n_id,
+                                  n_grp, Sq, Skv, q_strides, k_strides, v_strides, z_strides, scale)
+    s = _hip.AttnMixSamples() if mx is None else _hip.AttnMixMxSamples()
+    s.n = n
+    for name, val in (sample_strides or {}).items():
+        setattr(s, name, val)
+    s.af = 0 if af is None else _sample_stride(af, n, "af")
+    if mx is None:
+        s.z = _sample_stride(z, n, "z")
+    else:
+        s.codes, s.scales = _sample_stride(mx_out[0], n, "mx_out codes"), _sample_stride(mx_out[1], n, "mx_out scales")
+    plan = _plan((entry + "_batch", (*args, s)), True, _hip.AttnMixPlan, _mix_plan_dict)
+    if plan is not None and mx is not None:
+        plan["mx_out"] = mx_out[2]
+    return plan
+
+
 def _tiny_call(q, k, v, out, L, heads, n_outer, n_inner, strides, ld_qkv, ld_o, scale, plan):
     ptr = _plan_p if plan else _p
     args = (ptr(q), ptr(k), ptr(v), ptr(out), L, heads, n_outer, n_inner)
@@ -1404,6 +1470,55 @@ def router_head(x, w, b, r, n_id, N):
     assert x.is_contiguous() and r.is_contiguous()
     _launch(None, None, 0.0, ("bya_router_head", (_p(x), _p(w), _p(b), _p(r), n_id, N, x.shape[-1])))
     return r
+
+
+def _scores_batch_call(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, eps, plan):
+    """``_scores_call`` for sample 0 of qr [n, N, 2048], kr [n, n_id, 32, 2048] and out [n, n_id, N, 512] with the
+    bya_router_scores_samples of their first-dimension strides behind the arguments."""
+    for t in (qr, kr, out):
+        assert t[0].is_contiguous()
+    entry, args = _scores_call(qr[0], kr[0], ln_w, ln_b, pos_emb, out[0], n_id, N, eps, plan)
+    s = _hip.RouterScoresSamples()
+    s.n = out.shape[0]
+    s.qr, s.kr, s.out = _sample_stride(qr, s.n, "qr"), _sample_stride(kr, s.n, "kr"), _sample_stride(out, s.n, "out")
+    return entry + "_batch", (*args, s)
+
+
+def router_scores_batch(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, eps=1e-5):
+    """``router_scores`` for the samples of a batch in ONE launch: qr [n, N, 2048], kr [n, n_id, 32, 2048], out [n, n_id, N, 512]
+    (each sample contiguous); byte for byte ``router_scores(qr[b], kr[b], ..., out[b])`` for every b.  Returns out, or False where
+    the library declines."""
+    n = out.shape[0]
+    return _launch(None, None, 2.0 * n * n_id * N * 32 * qr.shape[-1], _scores_batch_call(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, eps, False),
+                   True) and out
+
+
+def router_scores_batch_plan(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N):
+    """What ``router_scores_batch`` would launch (meta tensors will do): ``router_scores_plan``'s dict of one sample with "grid"
+    multiplied by the samples; None where the library declines."""
+    return _plan(_scores_batch_call(qr, kr, ln_w, ln_b, pos_emb, out, n_id, N, 0.0, True), True, _hip.StepPlan,
+                 lambda p: _step_plan(p, _hip.ROUTER_SCORES_KERNELS[p.kernel]))
+
+
+def _head_batch_call(x, w, b, r, n_id, N, plan):
+    ptr = _plan_p if plan else _p
+    assert x[0].is_contiguous() and r[0].is_contiguous()
+    s = _hip.RouterHeadSamples()
+    s.n = x.shape[0]
+    s.x, s.r = _sample_stride(x, s.n, "x"), _sample_stride(r, s.n, "r")
+    return "bya_router_head_batch", (ptr(x), ptr(w), ptr(b), ptr(r), n_id, N, x.shape[-1], s)
+
+
+def router_head_batch(x, w, b, r, n_id, N):
+    """``router_head`` for the samples of a batch in ONE launch: x [n, n_id, N, D], r [n, N, n_id] (each sample contiguous).
+    Returns r, or False where the library declines."""
+    return _launch(None, None, 0.0, _head_batch_call(x, w, b, r, n_id, N, False), True) and r
+
+
+def router_head_batch_plan(x, w, b, r, n_id, N):
+    """What ``router_head_batch`` would launch (meta tensors will do): {"kernel": "rows", "grid" = ceil(N * n_id / 4) * samples,
+    "rounds", "items" (= N * n_id, one wave each), "items_per_round"}; None where the library declines."""
+    return _plan(_head_batch_call(x, w, b, r, n_id, N, True), True, _hip.StepPlan, lambda p: _step_plan(p, "rows"))
 
 
 def forcing_max_over_frames(forcing, out, frames, per_frame, n_id):

@@ -162,6 +162,23 @@ class DPMScheduler(_SchedulerBase):
         return prev, x0
 
 
+def _self_healing_step(tr, dev, predict):
+    """``predict()`` with the hand-off counters of the split kernels read behind it (ops.heal_handoffs: one synchronisation).
+    A split-K / stream-K hand-off of the step timed out (the GPU is shared: the grids were not co-resident): the library is in
+    its unsplit mode now -- compute the step again instead of failing the clip at its end.  A captured graph (use_hip_graph)
+    still holds the very launches that timed out: drop them first, the re-run captures under the healed options.  The re-run is
+    checked like any step: time-outs behind it have no clean step to stand on, so the clip fails here."""
+    from . import ops
+    noise = predict()
+    if ops.heal_handoffs(dev):
+        tr._graphs = {}
+        noise = predict()
+        if ops.heal_handoffs(dev):
+            raise ops._hip.ByaError("a split-K / stream-K hand-off timed out again in the step that was re-run in the unsplit mode: "
+                                    "results of this run are not to be trusted")
+    return noise
+
+
 class BindyouravatarPipeline:
     """See module docstring.  ``transformer``: ``BindyouravatarTransformer3DModel`` of this package."""
 
@@ -271,8 +288,6 @@ class BindyouravatarPipeline:
         # Unsharded runs only -- ranks of a sharded step would have to agree to repeat it; they keep the end-of-clip check.
         heal = (torch.device(dev).type == "cuda" and getattr(tr, "_seq_world", 1) == 1 and getattr(tr, "_cfg", None) is None
                 and os.environ.get("BYA_SELF_HEAL", "1") != "0")
-        if heal:
-            from . import ops
         for i, t in enumerate(ts):
             if self._interrupt:
                 continue
@@ -290,11 +305,7 @@ class BindyouravatarPipeline:
                           audio_embeds=audio_embs, af_matrix=af_matrix, denoise_step=i,
                           routing_logits_zeros_flag=routing_logits_zeros_flag,
                           routing_logits_forcing=routing_logits_forcing)[0]
-            noise = predict()
-            if heal and ops.heal_handoffs(dev):
-                # a split-K / stream-K hand-off of this step timed out (the GPU is shared: the grids were not co-resident);
-                # the library is in its unsplit mode now -- compute the step again instead of failing the clip at its end
-                noise = predict()
+            noise = _self_healing_step(tr, dev, predict) if heal else predict()
             if use_dynamic_cfg:
                 self._guidance_scale = 1 + guidance_scale * (
                     (1 - math.cos(math.pi * ((num_inference_steps - t.item()) / num_inference_steps) ** 5.0)) / 2)

@@ -8,11 +8,24 @@ parameter CONTAINERS only: nothing here computes with torch ops -- ``forward`` h
 There is no CPU / eager fallback: calling ``forward`` without a GPU or without the built library raises.
 """
 from types import SimpleNamespace
-from typing import Any, Dict, Optional, Tuple, Union
+from typing import Any, Dict, NamedTuple, Optional, Tuple, Union
 
 import os
 import torch
 from torch import nn
+
+
+class GraphEntry(NamedTuple):
+    """One captured step of ``_graphed_step``: the graph, its static input buffers and output, and what it keeps alive -- the
+    workspace its launches point into, the engine, and (``cache_hold``: None for a graph that recomputes the conditioning) the
+    entries of the engine's conditioning cache it reads in place.  The engine drops entries with a ``cache_hold`` together with
+    the cache they were captured against."""
+    graph: Any
+    static: list
+    static_out: Any
+    ws: Any
+    engine: Any
+    cache_hold: Any
 
 
 # ------------------------------------------------------------------------------------------ containers
@@ -311,6 +324,9 @@ class BindyouravatarTransformer3DModel(nn.Module):
         # opt-in: replay the whole step (about 3000 kernel launches) from one captured hipGraph per input signature
         self.use_hip_graph = False
         self._graphs = {}
+        # opt-in, read when the engine is built (set it before the first call, or call invalidate_engine()): a batch of
+        # B >= 2 samples runs the face / audio kv-mix and the router's scores and head as ONE launch per layer (BYA_BATCH_LAUNCHES)
+        self.batch_launches = False
 
     # ---- API the reference pipeline touches -------------------------------------------------------
     @property
@@ -620,8 +636,15 @@ class BindyouravatarTransformer3DModel(nn.Module):
         graph and replay it: the launches are identical, only the host-side launch cost disappears.  Inputs are copied
         into the graph's static buffers before every replay; the returned tensor is a fresh copy of the static output."""
         self._engine.refresh_if_stale()                # in-place parameter edits drop the captured graphs too
-        flat = self._flatten(args, [])
-        key = tuple((tuple(t.shape), t.dtype) for t in flat) + tuple(a is None for a in args)
+        # A precomputed conditioning that serves exactly these identity / audio tensors (precompute_conditioning) is READ IN PLACE
+        # by the graph: the capture runs with the cache on and every lookup a hit, so it holds no conditioning launch and writes
+        # nothing into the cache.  The three conditioning arguments are then not graph inputs at all (positions 4, 5, 6 of `args`:
+        # the engine keys its cache by the caller's own tensors); the cache's identity -- generation and keys -- is part of the
+        # graph key, the entry keeps the cached tensors alive, and the engine drops such entries with the cache.
+        hit = self._engine.cache_identity(args[4], args[5], args[6])
+        live = args if hit is None else tuple(None if i in (4, 5, 6) else a for i, a in enumerate(args))
+        flat = self._flatten(live, [])
+        key = (tuple((tuple(t.shape), t.dtype) for t in flat) + tuple(a is None for a in args), None if hit is None else hit[0])
         entry = self._graphs.get(key)
         if entry is None:
             # a captured graph bakes in raw pointers of the engine's workspace: give every graph a workspace of its
@@ -629,9 +652,11 @@ class BindyouravatarTransformer3DModel(nn.Module):
             # or batch of an eager call changes)
             self._engine._ws_key, self._engine._ws = None, None
             static = [t.detach().clone().to(self.device) for t in flat]
-            static_args = self._rebuild(args, iter(static))
+            static_args = self._rebuild(live, iter(static))
+            if hit is not None:
+                static_args = tuple(args[i] if i in (4, 5, 6) else a for i, a in enumerate(static_args))
             cache = self._engine.cache_invariants
-            self._engine.cache_invariants = False          # the conditioning is recomputed inside the graph each replay
+            self._engine.cache_invariants = hit is not None   # no matching cache: recomputed inside the graph each replay
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):                   # warm-up outside capture (workspaces, function attributes)
@@ -641,9 +666,10 @@ class BindyouravatarTransformer3DModel(nn.Module):
             with torch.cuda.graph(graph):
                 static_out = self._engine.step(*static_args)
             self._engine.cache_invariants = cache
-            entry = self._graphs[key] = (graph, static, static_out, self._engine._ws, self._engine)
+            entry = self._graphs[key] = GraphEntry(graph, static, static_out, self._engine._ws, self._engine,
+                                                   None if hit is None else hit[1])
             self._engine._ws_key, self._engine._ws = None, None      # eager calls never write into a graph's buffers
-        graph, static, static_out = entry[:3]
+        graph, static, static_out = entry.graph, entry.static, entry.static_out
         for dst, src in zip(static, flat):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)

@@ -782,6 +782,46 @@ int bya_attn_kv_mix_mx_seg_plan(const void* codes, const void* scales, const voi
                                 const bya_attn_mix_segments* seg, int32_t out_fmt, int64_t c_grp, int64_t c_row, int64_t sc_grp,
                                 int64_t sc_row, bya_attn_kv_mix_plan_info* plan);
 
+/* bya_attn_kv_mix / bya_attn_kv_mix_mx over a BATCH of samples: one launch where the caller issued one per sample (the
+ * [uncond, cond] pair of a guided step).  The arguments are the single-sample entry's, for sample 0; `batch` (by value: no device
+ * memory, a captured graph carries it) holds the sample count n and, per pointer that differs between samples, the distance from
+ * one sample to the next: in ELEMENTS of the pointer's type for q, k, v, r, af, z (bf16) and wsum (fp32), in BYTES for codes and
+ * scales.  A stride of 0 shares the operand (one forcing tensor r for the whole batch); the af stride is ignored where af is
+ * NULL.  The wsum stride is checked (not negative, no overlap) whenever wsum is given OR the stride is not 0 -- the plan queries
+ * see no wsum pointer, and the entries follow the same rule; pass 0 without wsum.  The descriptor is common to the samples.
+ * The sample is a second grid dimension of the single-sample kernel body: a workgroup's (group, head, row chunk) within its sample
+ * is the single-sample launch's, so every row's arithmetic -- and with it wsum and the MX scale bytes -- does not depend on n.
+ * The output is byte for byte that of n single-sample launches with the pointers advanced by the strides; bytes those never write
+ * (rows >= Sq, bytes outside a head's code / scale bytes, anything between the samples) are never written.
+ * Refused before any launch: anything the single-sample entry refuses, with its code; n < 1 (or > 65535), a negative stride, an
+ * output (z, codes, scales, wsum by the rule above) stride smaller than what one sample covers of it when n > 1 -- samples would
+ * overlap --, a negative output row / group stride -> BYA_ERR_SHAPE; a q / k / v stride that is no multiple of 8 elements, a z
+ * stride that is no multiple of 4, a codes stride that is no multiple of 4 bytes -> BYA_ERR_ALIGN; the generic form (Skv > 32,
+ * BYA_REF_KV_MIX_GENERIC, a z that is not 16-byte aligned in every sample: z, z_grp, z_row or the z stride no multiple of 8) ->
+ * BYA_ERR_UNSUPPORTED, as the segment form: the caller then issues the launches per sample.
+ * The plan queries answer with bya_attn_kv_mix_plan's struct: the single-sample launch's form (BYA_KV_MIX_MIX32), row_chunks,
+ * lds_bytes and big_lds, and grid = the single-sample grid * n; untouched on rejection. */
+typedef struct bya_attn_mix_samples {
+    int32_t n;                                   /* samples, >= 1 */
+    int32_t reserved;
+    int64_t q, k, v, r, af, z, wsum;             /* elements from one sample to the next */
+} bya_attn_mix_samples;
+typedef struct bya_attn_mix_mx_samples {
+    int32_t n;
+    int32_t reserved;
+    int64_t q, k, v, r, af, codes, scales, wsum; /* codes, scales: bytes */
+} bya_attn_mix_mx_samples;
+int bya_attn_kv_mix_batch(const void* q, const void* k, const void* v, const void* r, const void* af, void* z, float* wsum,
+                          const bya_attn_mix_desc* desc, bya_attn_mix_samples batch, hipStream_t stream);
+int bya_attn_kv_mix_batch_plan(const void* z, const void* af, const bya_attn_mix_desc* desc, bya_attn_mix_samples batch,
+                               bya_attn_kv_mix_plan_info* plan);
+int bya_attn_kv_mix_mx_batch(const void* q, const void* k, const void* v, const void* r, const void* af, void* codes, void* scales,
+                             float* wsum, const bya_attn_mix_desc* desc, int32_t out_fmt, int64_t c_grp, int64_t c_row,
+                             int64_t sc_grp, int64_t sc_row, bya_attn_mix_mx_samples batch, hipStream_t stream);
+int bya_attn_kv_mix_mx_batch_plan(const void* codes, const void* scales, const void* af, const bya_attn_mix_desc* desc,
+                                  int32_t out_fmt, int64_t c_grp, int64_t c_row, int64_t sc_grp, int64_t sc_row,
+                                  bya_attn_mix_mx_samples batch, bya_attn_kv_mix_plan_info* plan);
+
 /* Tiny-sequence self-attention (sequence length L <= 16, head_dim 64) used by the router's temporal
  * (L = frames) and multi-ID (L = ids) attentions (models/router.py:482,488).  Element e of sequence
  * `g` lives at row  g_outer(g)*outer_stride + e*seq_stride + g_inner(g)  of the [rows, ld] matrices,
@@ -826,6 +866,37 @@ int bya_router_scores_plan(const void* qr, const void* kr, const void* ln_w, con
                            bya_step_plan_info* plan);           /* see bya_step_plan_info */
 int bya_router_head(const void* x, const void* w, const void* b, void* r, int32_t n_id, int64_t N, int32_t D,
                     hipStream_t stream);
+/* bya_router_scores / bya_router_head over a BATCH of samples, as bya_attn_kv_mix_batch: the single-sample entry's arguments for
+ * sample 0 plus, by value, n and the distance in bf16 ELEMENTS from one sample to the next of each pointer that differs per
+ * sample (qr, kr, out; x, r); 0 shares an input.  The sample is a second grid dimension of the same kernels (a single-sample
+ * launch is the batch of one): a sample's tiles are walked as there, the output is byte for byte that of n single-sample launches
+ * on the advanced pointers and nothing else is written.
+ * Refused before any launch: anything the single-sample entry refuses, with its code; n < 1 (or > 65535), a negative stride, an
+ * output stride (out: below n_id * N * 512; r: below N * n_id) that makes samples overlap when n > 1 -> BYA_ERR_SHAPE; a qr, kr,
+ * out or x stride that is no multiple of 8 elements -> BYA_ERR_ALIGN.
+ * Plan queries (bya_step_plan_info; untouched on rejection): bya_router_scores_batch_plan = bya_router_scores_plan's answer for one
+ * sample -- kernel, rounds, items, items_per_round -- with grid = its grid * n; bya_router_head_batch_plan: kernel = 0, items =
+ * items_per_round = N * n_id (one wave per identity and row), rounds = 1, grid = ceil(items / 4) * n. */
+typedef struct bya_router_scores_samples {
+    int32_t n;                                   /* samples, >= 1 */
+    int32_t reserved;
+    int64_t qr, kr, out;
+} bya_router_scores_samples;
+typedef struct bya_router_head_samples {
+    int32_t n;
+    int32_t reserved;
+    int64_t x, r;
+} bya_router_head_samples;
+int bya_router_scores_batch(const void* qr, const void* kr, const void* ln_w, const void* ln_b, const void* pos_emb, void* out,
+                            int32_t n_id, int64_t N, int32_t heads, int32_t face_tokens, float eps,
+                            bya_router_scores_samples batch, hipStream_t stream);
+int bya_router_scores_batch_plan(const void* qr, const void* kr, const void* ln_w, const void* ln_b, const void* pos_emb,
+                                 const void* out, int32_t n_id, int64_t N, int32_t heads, int32_t face_tokens,
+                                 bya_router_scores_samples batch, bya_step_plan_info* plan);
+int bya_router_head_batch(const void* x, const void* w, const void* b, void* r, int32_t n_id, int64_t N, int32_t D,
+                          bya_router_head_samples batch, hipStream_t stream);
+int bya_router_head_batch_plan(const void* x, const void* w, const void* b, const void* r, int32_t n_id, int64_t N, int32_t D,
+                               bya_router_head_samples batch, bya_step_plan_info* plan);
 
 /* Forcing override (models/transformer.py:813-819): out[t,r,id] = max_t' forcing[t',r,id]. Bit-exact. */
 int bya_forcing_max_over_frames(const void* forcing, void* out, int32_t frames, int64_t per_frame,
