@@ -359,6 +359,23 @@ int bya_layernorm_fp8(const void* x, void* q, float* q_scale, const void* w, con
  *   residual / gate arguments; those descriptor fields are ignored.  n_split, c_split_stride, ldc, c_batch_stride % 8 == 0 and
  *   C, the four norm vectors, cos and sin 16-byte aligned (BYA_ERR_ALIGN); otherwise the checks of bya_gemm_mx_mixed and of
  *   bya_gemm_qkv_norm_rope's norm descriptor (BYA_ERR_SHAPE).  Every check runs before any launch (and without a GPU).
+ *
+ * Domain of the GEMMs (what the definitions above promise, and what tests/test_gemm_cond_gpu.py holds every kernel instance to,
+ * element by element against fp64 on the very bytes; the bytes need not come from bya_quantize_mx):
+ *   codes        every finite code of the format -- e4m3 subnormals (0x01 .. 0x07) and +-448, all 64 e2m3 and all 16 e2m1 codes,
+ *                +-0 included.  The e4m3 NaN codes 0x7F / 0xFF are outside the domain (NaN / Inf propagation is not specified).
+ *   scale bytes  0 .. 254 (2^-127 .. 2^127).  The e8m0 NaN byte 255 is outside the domain.
+ *   along K      for every A block and the W block it meets, |E_a + E_w| <= 64 (E = byte - 127), so that every scaled product
+ *                is a normal fp32: the bytes may be individually extreme (A at 27, W at 227), their products may not.
+ *   result       res + gate * alpha * act(sum + rowscale * bias) with the sum within 2 K 2^-24 sum_k |a_k w_k| of the exact one
+ *                (fp32 accumulation in any order), then ONE rounding to bf16; where every partial sum is exact in fp32 the
+ *                result is the exact one rounded once, bit for bit.  e4m3 activations add the instruction's own block sum to
+ *                that bound: inside a 32-block it aligns the non-zero products by their exponent fields (a subnormal code
+ *                counts as 2^-6, a zero code takes no part) and drops, toward zero, the bits below 2^-13 of the largest
+ *                exponent sum (tests/test_gemm_cond_gpu.py asserts it on probes) -- at most
+ *                min(|p_k|, q) per product that has such bits.  e2m3 activations never have any.
+ *   bya_gemm_fp8 every finite e4m3 code; row scales any finite positive fp32, not only powers of two (the product of the two
+ *                scales is rounded to fp32 before it multiplies the sum).
  * --------------------------------------------------------------------------------------------- */
 enum { BYA_MX_E4M3 = 0, BYA_MX_E2M3 = 2, BYA_MX_E2M1 = 4 };
 int bya_quantize_mx(const void* x, void* codes, void* scales, int32_t M, int32_t K, int64_t ldx, int32_t fmt,

@@ -1,0 +1,649 @@
+"""Conditioning of the quantised GEMMs (a plain helper module: no tests, no fixtures; the sibling of ``cond_norm.py`` and
+``cond_attn.py``).  The exact-data suites draw MX and e4m3 elements from 11 values and block scales from 5 bytes; here the operands
+are built as BYTES over the whole domain of include/bya.h ("MX weights", "Domain of the GEMMs") -- every finite code, scale bytes
+0 .. 254 -- and every output element is held to the fp64 value of the definition on those very bytes.  Nothing passes through
+the quantiser, so the GEMM sees bytes no quantiser would emit.
+
+DATA.  An operand is a dict: ``codes`` (unpacked element codes, long [rows, K]), ``scales`` (uint8 [rows, K / 32]; fp8: fp32 row
+scales [rows]) and ``fam`` (index into ROW_FAMILIES per row).  ``packed`` turns the codes into the stored bytes (pack6 / pack4 of
+the CPU restatements), ``values`` dequantises THOSE bytes with dequant / dequant_mx.  The family changes every row (A: m mod 5,
+W: (n + 2) mod 5) and an output element (m, n) belongs to a family when its A row and its W row do, else to ``mixed``:
+    near       uniform over all finite codes, scale bytes 127 +- 3                                  the control
+    spread     the same codes, scale bytes 127 +- 10, 2 % of the blocks all-zero codes              sums ruled by a few blocks
+    cancel     pairs (2j, 2j + 1): A holds one code twice, W the code and its negative, one pair in eight nudged by one code
+               step: sum p is a few nudges while sum |p| is the whole row.  Scale bytes 127 +- 3     fp32 accumulation exposed
+    subnormal  only subnormal codes (e4m3 0x01 .. 0x07, e2m3 / e2m1 codes without exponent, both signs), scale bytes 127 +- 1
+    extreme    only +- the largest finite code, scale bytes 127 +- 1
+    far        (a launch of its own) all codes; A blocks at 27 +- 8 where the block index is even and at 227 +- 8 where it is
+               odd, W the other way round: individually extreme bytes, |E_a + E_w| <= 16.  A W block at 227 under a ``near`` A
+               row would leave the domain (|E_a + E_w| <= 64), so these rows cannot share a launch with the others.
+    one-hot    (a launch of its own, N >= K) W row n holds ONE non-zero code, at k = n mod K; A is dense, code (k + m) mod
+               (number of finite codes), so with M >= that number every code meets every position mod 128; A's scale byte is
+               span * b + m mod span (span = ceil(255 / blocks), capped at 254): 0 .. 254 all occur; W's bytes are
+               254 - span * b - span / 2 in every block, so E_a + E_w lies in [-span / 2, span / 2] ([-8, 8] at K = 512).
+EXACT FAMILIES (the result must EQUAL bf16(fp64) bit for bit; ``exact_units`` restates the proofs in integer arithmetic):
+    one-hot    every output is ONE product (the other 31 of the block and every other block contribute +-0): a 4-bit by 4-bit
+               significand has at most 8 bits, the exponent is far inside bf16's range, so it is exact in fp32 AND in bf16.
+    subnormal  an element is j * 2^-9 (e4m3), j / 8 (e2m3) or 1/2 (e2m1), |j| <= 7, so a scaled product is an integer of at most
+               49 times u 2^(d_a + d_w), u the product of the two element units and d in [-1, 1]: every partial sum of K of
+               them is at most K * 49 * 2^4 units of u 2^-2: below 2^24 up to K = 12288.
+    extreme    448 = 7 * 2^6, 7.5 = 15 * 2^-1, 6 = 3 * 2: at most 15 * 15 * 2^4 K units: below 2^24 up to K = 3072 in every
+               pair (at K = 12288 only where it is, ``exact_families``; elsewhere the family goes to the bars).
+Below 2^24 units every partial sum is exact in fp32 in any order; a flush of subnormals or a mis-decoded top code changes
+every element.  fp8 (``build_fp8``): the same code families (no block scales; near, spread with its all-zero blocks, cancel, subnormal, extreme) under per-row fp32
+scales log-uniform over [2^-20, 2^10], not powers of two, so every family is tolerance-checked there; one-hot as well.
+
+MEASURE (``check``).  y64 = the fp64 value of the definition in bya.h on the very bytes, epilogue included (``reference``);
+    e = |got - y64| / ulp,  ulp that of bf16(y64);     S = sum_k |a_k w_k| plus the epilogue's addends in absolute value.
+BAR (a), per element:  e <= 0.5 + eps,  eps = 2 (K + ops) u32 S / ulp (+ the block term below),  u32 = 2^-24:  one fp32 addition
+per product, in any order, each allowed to truncate rather than round, plus ``ops`` = the fp32 operations of the epilogue that
+the launch has (``epilogue_ops``: the fma with the bias, alpha, gate, residual; a plain launch has none and its bar is
+2 K u32 S; fp8: 2 more, the product of the two row scales and its product with the sum).  Derived, not measured.  With an
+activation the pre-activation term S is multiplied by min(|gelu'(x)| + (K + ops) u32 S, 1.13) (Taylor with |gelu''| < 1, and
+GELU's Lipschitz constant), the 0.5 becomes 1.5 (the exact suites'
+bound ACT_ULPS = 1 against bf16(exact) plus that rounding) and ulps below 2^-6 count as ulps of 2^-6, as in exact_gemm.bf16_ulps.
+THE INSTRUCTION'S BLOCK SUM.  The bar above was written for a block sum that is exact, and v_mfma_scale_f32_16x16x128_f8f6f4 does
+not give one for e4m3: on ``near`` rows, mxfp8 activations, T128X128 and P256 alike (kernels that the exact-data suites hold bit
+for bit), the first run measured a worst e of 1.85 against 0.5 + eps = 1.20 at K = 128 (one instruction per output), 1.21
+against 1.07 at K = 640, 12.9 against 10.5 under mxfp4 weights, and 2 - 3 % of the elements differing from bf16(fp64) at every
+K where the restatement differs in none; mxfp6 activations, ``subnormal``, ``extreme`` and ``one-hot`` were bit-exact.  MODEL of
+the instruction: inside a 32-block the non-zero products are aligned by their exponent FIELDS -- E = max_k (e_a + e_w), a
+subnormal code counting with its format's smallest normal exponent (e4m3: -6), a zero code taking no part -- and the bits of
+weight below q = 2^(E - 13) are dropped, toward zero; block sums, the other blocks and the accumulator then add in fp32.  The
+probes that fix the parameters are ``block_sum_probes``: one block holding +T, -T and one product s = +-225 * 2^-18 of 8
+significant bits; test_gemm_cond_gpu.py asserts the kernel returns the bits the model predicts, test_gemm_cond_cpu.py that
+``restate(model=True)`` predicts them:
+    the pair 1 x 2^2:          s comes back as its single bit 2^-11 = 2^(2 - 13), with either sign of s; from T = 2^3 on as 0;
+    the pair 1.75 x 1.75 x 2^2 = 12.25:  the same 2^-11, so E is the SUM of the field exponents, not the product's exponent;
+    the pair (subnormal code) x 2^8:  2^-11 for each of 2^-9, 2^-8, 1.5 * 2^-8, 2^-7: the field exponent -6, not the value's;
+    zero codes x 2^8 beside s: s whole (as the one-hot family, bit-exact on every instance, shows at every position);
+    the pair in ANOTHER block or another K-step: s exact at every T up to 2^47 s; 64 unit products beside such a pair sum to 64.
+A product loses |p_k| mod q <= min(|p_k|, q), and nothing when it has no bit below q, so
+    eps = (2 (K + ops) u32 S + T_blk) / ulp,   T_blk = sum over blocks, over the block's products with a bit below q, of
+    min(|p_k|, q)                                                                                       (``block_term``).
+e2m3 x e2m3 products are multiples of 2^-6 and E <= 4, so q <= 2^-9 and no bit is lost (e2m3 x e2m1 likewise): T_blk = 0,
+as for the three exact families and the old exact grid, whose bars do not move.  The term is always computed exactly (no
+cheaper bound); the model-shape cases of test_mx_gpu.py, where that costs M N K, take it on a fixed sample of rows.  The
+constant 13 and the field rule come from the probes, not from the errors the kernels show on this suite's data.
+(Through GELU: min(|gelu'| d + d^2 / 2, 1.13 d) with d the whole pre-activation bound.)
+BAR (b), per family:  the share of elements whose bits differ from bf16(y64) is at most p + 3 sqrt(p (1 - p) / n), p = 2
+mean(min(eps, 0.5)): a result within eps of the truth crosses a rounding boundary with probability at most 2 eps.
+BAR (c), per family:  the mean signed error in ulps, over the elements with eps <= 4, is within max(0.25, 3 sqrt(2 / n) sd) of the
+RESTATEMENT's over the same elements: n their number, sd the spread of the restatement's own signed errors there (with fewer
+than 30 elements: the bound 4.5 of any such error), sqrt 2 for a difference of two means.  Asserted at every shape that has
+such an element.  (Where an ulp is thousands of times smaller than S -- ``cancel`` at long K -- no element has eps <= 4 and
+a mean would say nothing.)  (b) and (c) are not asserted under an activation (the kernel's tanh is not the restatement's) nor
+on the exact families (they are held bit for bit).
+BAR (d):  every output finite, guard band intact (``exact_gemm.GuardedOut``).
+The restatement (``restate``): the sum of each 32-block exact (fp64 holds it: 32 products of 8 significant bits over 35
+binades), rounded to fp32 and added to an fp32 accumulator block by block; the epilogue in fp32 as csrc/gemm_common.h writes it.
+tests/test_gemm_cond_cpu.py holds it, a reversed K order and a 128-step grouping inside every bar, and plants the faults that
+must fail.
+
+FIGURES of the first runs on an MI355X (records, not bars; the full tables are in DESIGN.md, section 16).  T128X128 and P256 gave
+the same bits in every case.  worst e | 0.5 + eps | differing share | the restatement's share:
+    before the block term   mxfp8 x mxfp8 300x264x128  near 1.847 | 1.196 | 0.0176 | 0      spread 8.529 | 4.311 | 0.0247 | 0
+                            mxfp8 x mxfp8 300x264x640  near 1.207 | 1.065 | 0.0270 | 0.0003
+                            mxfp8 x mxfp4 300x264x128  near 12.93 | 10.53 | 0.0264 | 0
+    with it                 mxfp8 x mxfp8 300x264x512  near 0.496 | 0.582 | 0.0255 | 0      far 0.500 | 0.536 | 0.0232 | 0
+                            mxfp8 x mxfp8 130x128x12288 near 0.481 | 1.230 | 0.0323 | 0     cancel 0.048 | 20.79 | 0.1317 | 0
+                            mxfp8 x mxfp4 300x264x512  near 0.477 | 0.539 | 0.0252 | 0      far 0.500 | 0.520 | 0.0277 | 0
+                            mxfp6 x mxfp6 300x264x512  near 0.498 | 0.534 | 0      | 0      far 0.497 | 0.514 | 0      | 0
+                            mxfp6 x mxfp4 300x264x512  near 0.496 | 0.524 | 0      | 0      far 0.498 | 0.511 | 0      | 0
+                            t256x256 mxfp6 x mxfp6 3500x3700x256  near 0.500 | 0.507 | 0 | 0     far 0.499 | 0.505 | 0 | 0
+                            fp8 t128x128 300x264x512   near 0.495 | 0.613 | 0.0282 | 0      fp8 p256 3500x3704x512 near 0.492 | 0.570 | 0.0326 | 0.0001
+    subnormal, extreme and one-hot: bit-exact on every instance, before and after; every probe of ``block_sum_probes`` returned
+    the predicted bits.
+"""
+import functools
+import math
+
+import torch
+
+from exact_gemm import BF, bad_elements, describe
+from mx_ref import dequant, pack4, pack6
+
+U32 = 2.0 ** -24
+PAIRS = (("mxfp8", "mxfp8"), ("mxfp6", "mxfp6"), ("mxfp8", "mxfp4"), ("mxfp6", "mxfp4"))
+ROW_FAMILIES = ("near", "spread", "cancel", "subnormal", "extreme")
+FAMILIES = ROW_FAMILIES + ("mixed", "far", "one-hot")
+EXACT = ("subnormal", "extreme", "one-hot")
+MIXED, FAR, ONE_HOT = FAMILIES.index("mixed"), FAMILIES.index("far"), FAMILIES.index("one-hot")
+SCALE_HALF = {"near": 3, "spread": 10, "cancel": 3, "subnormal": 1, "extreme": 1}
+FAR_LOW, FAR_HIGH, FAR_HALF = 27, 227, 8
+GELU_SLOPE = 1.13
+ACT_FLOOR = 2.0 ** -6
+EPS_MEAN, MEAN_MARGIN = 4.0, 0.25
+SIGN = {"mxfp8": 0x80, "mxfp6": 0x20, "mxfp4": 0x8}
+TOP = {"mxfp8": 0x7E, "mxfp6": 0x1F, "mxfp4": 0x7}          # the largest finite magnitude's code
+# an element is (integer of at most INT_MAX) * 2^UNIT_LOG2: the subnormal codes and the largest code
+SUB_UNIT = {"mxfp8": -9, "mxfp6": -3, "mxfp4": -1}
+SUB_INT = {"mxfp8": 7, "mxfp6": 7, "mxfp4": 1}
+TOP_UNIT = {"mxfp8": 6, "mxfp6": -1, "mxfp4": 1}
+TOP_INT = {"mxfp8": 7, "mxfp6": 15, "mxfp4": 3}
+
+
+def seed_of(name):
+    return sum(ord(ch) * (i + 1) for i, ch in enumerate(name)) % (2 ** 31)
+
+
+def finite_codes(fmt):
+    """Every finite code of the format (e4m3: all but the NaN codes 0x7F / 0xFF)."""
+    n = 1 << {"mxfp8": 8, "mxfp6": 6, "mxfp4": 4}[fmt]
+    c = torch.arange(n)
+    return c[(c & 0x7F) != 0x7F] if fmt == "mxfp8" else c
+
+
+def subnormal_codes(fmt):
+    mags = torch.arange(1, SUB_INT[fmt] + 1)
+    return torch.cat([mags, mags | SIGN[fmt]])
+
+
+def extreme_codes(fmt):
+    return torch.tensor([TOP[fmt], TOP[fmt] | SIGN[fmt]])
+
+
+def packed(op, fmt):
+    """The stored bytes of an operand's codes."""
+    c = op["codes"]
+    return c.to(torch.uint8) if fmt in ("mxfp8", "fp8") else pack6(c) if fmt == "mxfp6" else pack4(c)
+
+
+def values(op, fmt):
+    """fp64 [rows, K] of the operand's BYTES (tests/test_mxfp4_cpu.py dequant; fp8: e4m3 times the fp32 row scale)."""
+    if fmt == "fp8":
+        return packed(op, fmt).view(torch.float8_e4m3fn).double() * op["scales"].double()[:, None]
+    return dequant(packed(op, fmt), op["scales"], fmt)
+
+
+def _codes_of(fam, fmt, side, rows, K, gen):
+    pick = lambda pool: pool[torch.randint(0, len(pool), (rows, K), generator=gen)]
+    if fam == "subnormal":
+        return pick(subnormal_codes(fmt))
+    if fam == "extreme":
+        return pick(extreme_codes(fmt))
+    c = pick(finite_codes(fmt))
+    if fam == "spread":
+        zero = torch.rand(rows, K // 32, generator=gen) < 0.02
+        c = torch.where(zero[..., None].expand(rows, K // 32, 32).reshape(rows, K), torch.zeros_like(c), c)
+    if fam == "cancel":
+        c = c.reshape(rows, K // 2, 2).clone()
+        c[..., 1] = c[..., 0]
+        if side == "w":
+            c[..., 1] ^= SIGN[fmt]
+            mag = c[..., 1] & ~SIGN[fmt]
+            up = torch.where(mag < TOP[fmt], mag + 1, mag - 1)                      # one code step, staying finite
+            nudge = torch.rand(rows, K // 2, generator=gen) < 0.125
+            c[..., 1] = torch.where(nudge, (c[..., 1] & SIGN[fmt]) | up, c[..., 1])
+        c = c.reshape(rows, K)
+    return c
+
+
+def build_operand(rows, K, fmt, side, seed, group="mid"):
+    """One MX operand (A: side "a", W: side "w") of the ``mid`` group (rows interleaved over ROW_FAMILIES) or the ``far`` one."""
+    gen = torch.Generator().manual_seed(seed)
+    nb = K // 32
+    if group == "far":
+        codes = _codes_of("near", fmt, side, rows, K, gen)
+        low = (torch.arange(nb) % 2 == 0) == (side == "a")
+        base = torch.where(low, FAR_LOW, FAR_HIGH)[None].expand(rows, nb)
+        scales = base + torch.randint(-FAR_HALF, FAR_HALF + 1, (rows, nb), generator=gen)
+        return dict(codes=codes, scales=scales.to(torch.uint8), fam=torch.full((rows,), FAR))
+    fam = (torch.arange(rows) + (0 if side == "a" else 2)) % len(ROW_FAMILIES)
+    codes = torch.zeros(rows, K, dtype=torch.long)
+    scales = torch.zeros(rows, nb, dtype=torch.long)
+    for i, name in enumerate(ROW_FAMILIES):
+        sel = fam == i
+        n = int(sel.sum())
+        if n:
+            codes[sel] = _codes_of(name, fmt, side, n, K, gen)
+            h = SCALE_HALF[name]
+            scales[sel] = 127 + torch.randint(-h, h + 1, (n, nb), generator=gen)
+    return dict(codes=codes, scales=scales.to(torch.uint8), fam=fam)
+
+
+def one_hot_span(K):
+    return -(-255 // (K // 32))
+
+
+def build_one_hot(M, N, K, fmt, w_fmt):
+    """-> (A, W) of the one-hot family (module docstring); needs N >= K, and M >= the number of finite codes of ``fmt`` for
+    every code to meet every position."""
+    assert N >= K
+    nb, span = K // 32, one_hot_span(K)
+    fin = finite_codes(fmt)
+    m, k, b = torch.arange(M)[:, None], torch.arange(K)[None], torch.arange(nb)[None]
+    a = dict(codes=fin[(k + m) % len(fin)], scales=(span * b + m % span).clamp(max=254).to(torch.uint8),
+             fam=torch.full((M,), ONE_HOT))
+    wfin = finite_codes(w_fmt)
+    nz = wfin[(wfin & ~SIGN[w_fmt]) != 0]
+    n = torch.arange(N)
+    wc = torch.zeros(N, K, dtype=torch.long)
+    wc[n, n % K] = nz[(3 * n + n // K) % len(nz)]
+    ws = (254 - span * b - span // 2).expand(N, nb)
+    assert int(ws.min()) >= 0 and int(ws.max()) <= 254
+    return a, dict(codes=wc, scales=ws.to(torch.uint8).contiguous(), fam=torch.full((N,), ONE_HOT))
+
+
+FP8_FAMILIES = ("near", "spread", "cancel", "subnormal", "extreme")
+
+
+def build_fp8(rows, K, side, seed, one_hot=False):
+    """e4m3 codes of the families of FP8_FAMILIES (rows interleaved) under fp32 row scales log-uniform over [2^-20, 2^10];
+    ``one_hot`` (W only): one non-zero code per row at k = n mod K."""
+    gen = torch.Generator().manual_seed(seed)
+    scales = torch.exp2(torch.rand(rows, generator=gen, dtype=torch.float64) * 30 - 20).float()
+    if one_hot:
+        fin = finite_codes("mxfp8")
+        nz = fin[(fin & 0x7F) != 0]
+        n = torch.arange(rows)
+        codes = torch.zeros(rows, K, dtype=torch.long)
+        codes[n, n % K] = nz[(3 * n + n // K) % len(nz)]
+        return dict(codes=codes, scales=scales, fam=torch.full((rows,), ONE_HOT))
+    idx = (torch.arange(rows) + (0 if side == "a" else 1)) % len(FP8_FAMILIES)
+    codes = torch.zeros(rows, K, dtype=torch.long)
+    for i, name in enumerate(FP8_FAMILIES):
+        sel = idx == i
+        if int(sel.sum()):
+            codes[sel] = _codes_of(name, "mxfp8", side, int(sel.sum()), K, gen)
+    fam = torch.tensor([FAMILIES.index(f) for f in FP8_FAMILIES])[idx]
+    return dict(codes=codes, scales=scales, fam=fam)
+
+
+def out_family(a, w):
+    """[M, N] index into FAMILIES: the rows' family where A's and W's agree, else ``mixed``."""
+    fa, fw = a["fam"][:, None], w["fam"][None, :]
+    return torch.where(fa == fw, fa, torch.full_like(fa, MIXED)).expand(len(a["fam"]), len(w["fam"]))
+
+
+def scale_exponent_sums(a, w):
+    """(min, max) of E_a + E_w over every (A row, W row, block) met along K."""
+    ea, ew = a["scales"].long() - 127, w["scales"].long() - 127
+    lo = (ea.amin(0) + ew.amin(0)).min()
+    hi = (ea.amax(0) + ew.amax(0)).max()
+    return int(lo), int(hi)
+
+
+def exact_families(fmt, w_fmt, K):
+    """The families whose result is exact at this K: one-hot always, subnormal / extreme while ``exact_units`` stays below 2^24."""
+    return ("one-hot",) + tuple(f for f in ("subnormal", "extreme") if exact_units(f, fmt, w_fmt, K) < 2 ** 24)
+
+
+def exact_units(fam, fmt, w_fmt, K):
+    """The integer-arithmetic bound of the exact families ``subnormal`` / ``extreme``: the largest partial sum of K scaled
+    products in units of the smallest product unit (must stay below 2^24)."""
+    ia, iw = (SUB_INT, SUB_INT) if fam == "subnormal" else (TOP_INT, TOP_INT)
+    return K * ia[fmt] * iw[w_fmt] * 2 ** (4 * SCALE_HALF[fam])
+
+
+def integer_products(a, w, fam, fmt, w_fmt):
+    """For rows of an exact family: the products as INTEGERS of the unit 2^(unit_a + unit_w - 2 SCALE_HALF) -> (long [Ma, Nw, K],
+    log2 of the unit); their sums are what the proof speaks of."""
+    unit = (SUB_UNIT if fam == "subnormal" else TOP_UNIT)
+    h = SCALE_HALF[fam]
+
+    def ints(op, f):
+        rows = op["fam"] == FAMILIES.index(fam)
+        v = values(dict(codes=op["codes"][rows], scales=op["scales"][rows]), f)
+        i = torch.ldexp(v, torch.tensor(float(-unit[f] + h)))
+        assert torch.equal(i, i.round()) and float(i.abs().max()) < 2 ** 20
+        return i.long()
+    ia, iw = ints(a, fmt), ints(w, w_fmt)
+    return ia[:, None, :] * iw[None, :, :], unit[fmt] + unit[w_fmt] - 2 * h
+
+
+# ------------------------------------------------------------------------------------------------ reference and restatement
+def make_epilogue(M, N, seed, bias=False, act=None, gates=False, res=False, alpha=1.0, rowscale=False, batch=1):
+    """Epilogue operands NOT on a grid: bias bf16 N(0, 1), gates bf16 in [0.5, 1.5] changing at row M / 3 + 1 (no tile
+    boundary), residual bf16 N(0, 1), bias_rowscale fp32 in [0.5, 2].  All on the CPU."""
+    g = torch.Generator().manual_seed(seed)
+    e = dict(bias=None, act=act, gate0=None, gate1=None, gate_split=0, res=None, alpha=alpha, rowscale=None)
+    if bias:
+        e["bias"] = torch.randn(N, generator=g).to(BF)
+    if gates:
+        e["gate0"], e["gate1"] = (0.5 + torch.rand(N, generator=g)).to(BF), (0.5 + torch.rand(N, generator=g)).to(BF)
+        e["gate_split"] = M // 3 + 1
+    if res:
+        e["res"] = torch.randn(batch * M, N, generator=g).to(BF)
+    if rowscale:
+        e["rowscale"] = (0.5 + 1.5 * torch.rand(batch * M, generator=g)).float()
+    return e
+
+
+NO_EPILOGUE = dict(bias=None, act=None, gate0=None, gate1=None, gate_split=0, res=None, alpha=1.0, rowscale=None)
+
+
+def epilogue_to(e, dev):
+    return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in e.items()}
+
+
+def _gate(e, rows, M, dtype):
+    if e["gate0"] is None:
+        return None
+    g1 = e["gate0"] if e["gate1"] is None else e["gate1"]
+    r = e.get("row_ids")                          # (a sample of a launch's rows: their indices within the batch entry)
+    r = ((torch.arange(rows, device=e["gate0"].device) % M) if r is None else r.to(e["gate0"].device))[:, None]
+    return torch.where(r < e["gate_split"], e["gate0"].to(dtype)[None], g1.to(dtype)[None])
+
+
+def epilogue_ops(e, base=0):
+    """The fp32 operations behind the sum: the fma with the bias, alpha, the gate, the residual (``base``: 2 for bya_gemm_fp8, the
+    product of the two row scales and its product with the sum).  A plain launch has none: the bar is the issue's 2 K u32 S."""
+    return base + (e["bias"] is not None) + (e["alpha"] != 1.0) + (e["gate0"] is not None) + (e["res"] is not None)
+
+
+def reference(a64, w64, e=NO_EPILOGUE, M=None, T=None, base_ops=0):
+    """-> (y64, S) fp64 [rows, N] (with ``T``, the block-sum term of the plain product: (y64, S, T through the epilogue)):
+    res + gate * alpha * act(a @ w.T + rowscale * bias) and the sum of the absolute values of every addend (through an
+    activation: times GELU's slope there, second-order term included).  a64 [rows = batch * M, K]; on a64's device."""
+    rows = a64.shape[0]
+    M = M or rows
+    y = a64 @ w64.T
+    S = a64.abs() @ w64.abs().T
+    if e["bias"] is not None:
+        rs = 1.0 if e["rowscale"] is None else e["rowscale"].double()[:, None]
+        add = rs * e["bias"].double()[None]
+        y, S = y + add, S + add.abs()
+    if e["act"] is not None:
+        assert e["act"] == "gelu_tanh"
+        gelu = lambda x: torch.nn.functional.gelu(x, approximate="tanh")
+        # Taylor: |gelu(x + d) - gelu(x)| <= |gelu'(x)| |d| + max |gelu''| d^2 / 2, |d| <= 2 (K + 4) u32 S and max |gelu''| < 1
+        slope = (gelu(y + 2.0 ** -20) - gelu(y - 2.0 ** -20)).abs() * 2.0 ** 19
+        slope = (slope + (a64.shape[1] + epilogue_ops(e, base_ops)) * U32 * S + (0.0 if T is None else 0.5 * T)).clamp(max=GELU_SLOPE)
+        y, S = gelu(y), S * slope
+        T = None if T is None else T * slope
+    f = abs(e["alpha"])
+    y = y * e["alpha"]
+    g = _gate(e, rows, M, torch.float64)
+    if g is not None:
+        y, f = y * g, f * g.abs()
+    S = S * f
+    T = None if T is None else T * f
+    if e["res"] is not None:
+        y, S = y + e["res"].double(), S + e["res"].double().abs()
+    return (y, S) if T is None else (y, S, T)
+
+
+BLOCK_BITS = 13
+
+
+EMIN = {"mxfp8": -6, "fp8": -6, "mxfp6": 0, "mxfp4": 0}      # the exponent a subnormal code carries in its exponent field
+
+
+def exp_floor(scales, fmt):
+    """[rows, K / 32] fp64: the smallest exponent an element of each block can carry in its FIELD, E_scale + emin."""
+    return scales.double() - 127 + EMIN[fmt]
+
+
+def field_exponents(x, floor=None):
+    """floor(log2 |x|) of x [rows, K / 32, 32]; a non-zero element below 2^floor[rows, K / 32] (a subnormal code; ``exp_floor``)
+    counts with that exponent, as its exponent FIELD says.  A zero takes no part: its product is no term of the sum."""
+    e = torch.frexp(x.abs())[1].double() - 1
+    if floor is not None:
+        e = torch.maximum(e, floor.to(x.device).reshape(x.shape[0], x.shape[1], 1).double())
+    return torch.where(x != 0, e, torch.full_like(e, -1000.0))
+
+
+def block_term(a64, w64, a_floor=None, w_floor=None, chunk=1 << 24):
+    """The block-sum term of bar (a) (module docstring, "THE INSTRUCTION'S BLOCK SUM"), fp64 [M, N]: for every 32-block, the sum
+    of min(|p_k|, q) over its products that have a bit below q = 2^(E - 13), E = max_k (e_a + e_w) over the non-zero products'
+    field exponents (``field_exponents``; ``a_floor`` / ``w_floor`` = ``exp_floor``).  Always the exact term, in chunks of
+    ``chunk`` products; e2m3 activations need none (``mx_block_term``)."""
+    M, K = a64.shape
+    N = w64.shape[0]
+    nb = K // 32
+    aa, wa = a64.abs().reshape(M, nb, 32), w64.abs().reshape(N, nb, 32)
+    ea, ew = field_exponents(aa, a_floor), field_exponents(wa, w_floor)
+    out = torch.zeros(M, N, dtype=torch.float64, device=a64.device)
+    rows = max(1, chunk // (N * 32))
+    for b in range(nb):
+        for r0 in range(0, M, rows):
+            p = aa[r0:r0 + rows, b, None, :] * wa[None, :, b, :]
+            q = torch.exp2((ea[r0:r0 + rows, b, None, :] + ew[None, :, b, :]).amax(-1, keepdim=True).clamp(min=-1000.0) - BLOCK_BITS)
+            out[r0:r0 + rows] += torch.where(torch.fmod(p, q) != 0, torch.minimum(p, q), torch.zeros_like(p)).sum(-1)
+    return out
+
+
+def mx_block_term(a64, w64, fmt, w_fmt, a_scales, w_scales):
+    """``block_term`` of an MX launch: zero without computing anything for e2m3 activations (products of e2m3 with e2m3 or e2m1
+    are multiples of 2^-6 and E <= 4, so q <= 2^-9 and no product has a bit below it: test_gemm_cond_cpu.py checks that)."""
+    if fmt == "mxfp6":
+        return torch.zeros(a64.shape[0], w64.shape[0], dtype=torch.float64, device=a64.device)
+    return block_term(a64, w64, exp_floor(a_scales, fmt), exp_floor(w_scales, w_fmt))
+
+
+def epilogue32(acc, e=NO_EPILOGUE, M=None):
+    """The epilogue of csrc/gemm_common.h on an fp32 accumulator, in fp32: v = alpha * act(fma(rowscale, bias, acc)); v *= gate;
+    v += res; bf16(v)."""
+    rows = acc.shape[0]
+    v = acc
+    if e["bias"] is not None:
+        rs = 1.0 if e["rowscale"] is None else e["rowscale"].double()[:, None]
+        v = (acc.double() + rs * e["bias"].double()[None]).float()                   # one rounding: the fma
+    if e["act"] is not None:
+        v = torch.nn.functional.gelu(v, approximate="tanh")
+    if e["alpha"] != 1.0:
+        v = v * e["alpha"]
+    g = _gate(e, rows, M or rows, torch.float32)
+    if g is not None:
+        v = v * g
+    if e["res"] is not None:
+        v = v + e["res"].float()
+    return v.to(BF)
+
+
+def truncated_block(a64, w64, k0, a_floor=None, w_floor=None):
+    """The MODEL of the instruction's block sum for the 32-block at k0: products truncated toward zero at q = 2^(E - 13)."""
+    blk = lambda x, f: field_exponents(x[:, None, k0:k0 + 32], None if f is None else f[:, k0 // 32:k0 // 32 + 1])
+    p = a64[:, None, k0:k0 + 32] * w64[None, :, k0:k0 + 32]
+    q = torch.exp2((blk(a64, a_floor)[:, :, None, :] + blk(w64, w_floor)[None, :, :, :]).amax(-1).clamp(min=-1000.0) - BLOCK_BITS)
+    return (torch.trunc(p / q) * q).sum(-1)
+
+
+def accumulate32(a64, w64, group=32, reverse=False, acc_bf16=False, skip=None, model=False, floors=(None, None)):
+    """The RESTATEMENT's sum (``model``: each block sum by ``truncated_block``, small shapes only): each ``group`` of K exact (fp64), rounded to fp32, added to an fp32 accumulator in K order
+    (``reverse``: from the last group).  Planted faults: ``acc_bf16`` rounds the accumulator to bf16 after every 128 of K;
+    ``skip`` = (rows, cols, k0): the 128-step at k0 is never added for that tile."""
+    K = a64.shape[1]
+    acc = torch.zeros(a64.shape[0], w64.shape[0], dtype=torch.float32, device=a64.device)
+    starts = list(range(0, K, group))
+    for k0 in (reversed(starts) if reverse else starts):
+        part = (truncated_block(a64, w64, k0, *floors) if model else a64[:, k0:k0 + group] @ w64[:, k0:k0 + group].T).float()
+        if skip is not None and skip[2] <= k0 < skip[2] + 128:
+            part[skip[0], skip[1]] = 0.0
+        acc = acc + part
+        if acc_bf16 and (k0 + group) % 128 == 0:
+            acc = acc.to(BF).float()
+    return acc
+
+
+def restate(a64, w64, e=NO_EPILOGUE, M=None, **kw):
+    return epilogue32(accumulate32(a64, w64, **kw), e, M)
+
+
+def fp8_block_term(a, w, dev="cpu"):
+    """``block_term`` of the code products (the instruction sees scale bytes of 127), times the product of the row scales."""
+    ca = packed(a, "fp8").view(torch.float8_e4m3fn).double().to(dev)
+    cw = packed(w, "fp8").view(torch.float8_e4m3fn).double().to(dev)
+    floor = lambda c: torch.full((c.shape[0], c.shape[1] // 32), float(EMIN["fp8"]), dtype=torch.float64, device=dev)
+    return block_term(ca, cw, floor(ca), floor(cw)) * (a["scales"].double().to(dev)[:, None] * w["scales"].double().to(dev)[None])
+
+
+def restate_fp8(a, w, e=NO_EPILOGUE, M=None, dev="cpu", a_scale=None, **kw):
+    """bya_gemm_fp8's definition in fp32: the code products summed as ``accumulate32`` does, then fp32(a_scale * w_scale) * sum."""
+    ca = packed(a, "fp8").view(torch.float8_e4m3fn).double().to(dev)
+    cw = packed(w, "fp8").view(torch.float8_e4m3fn).double().to(dev)
+    a_scale = a["scales"] if a_scale is None else a_scale
+    s = a_scale.to(dev)[:, None] * w["scales"].to(dev)[None]                          # fp32 product, one rounding
+    return epilogue32(s * accumulate32(ca, cw, **kw), e, M)
+
+
+def block_sum_probes():
+    """The probes that fix the MODEL's parameters, as e4m3 bytes: -> [(name, K, A codes [R, K], A scales [R, K / 32], W codes [K],
+    W scales [K / 32], expected results [R])].  One block holds a pair +T, -T that cancels and one product s of 8 significant
+    bits beside it; the exact result is s.  tests/test_gemm_cond_gpu.py asserts the kernel's bits, tests/test_gemm_cond_cpu.py
+    that ``restate(model=True)`` predicts exactly these."""
+    s8, q11 = 225 * 2.0 ** -18, 2.0 ** -11               # s = (1.875 * 2^-6)^2 = 2^-11 + 2^-12 + 2^-13 + 2^-18
+    S_CODE, W_HI = 0x0F, 0x78                            # 1.875 * 2^-6;  2^8
+    u8 = lambda rows: torch.tensor(rows, dtype=torch.uint8)
+
+    def one_block(name, a_pairs, w_pair, s_code, expected, K=128):
+        a = torch.zeros(len(a_pairs), K, dtype=torch.uint8)
+        w = torch.zeros(K, dtype=torch.uint8)
+        a[:, 0] = a[:, 1] = u8(a_pairs)
+        a[:, 2] = s_code
+        w[0], w[1], w[2] = w_pair, w_pair | 0x80, S_CODE
+        one = lambda t: torch.full((*t.shape[:-1], K // 32), 127, dtype=torch.uint8)
+        return name, K, a, one(a), w, one(w), torch.tensor(expected, dtype=torch.float64)
+
+    norm = [e << 3 for e in range(1, 16)]                # 2^-6 .. 2^8: T = 2^2 .. 2^16
+    probes = [
+        one_block("pair 1 x 2^e", norm, W_HI, S_CODE, [q11] + [0.0] * 14),
+        one_block("pair 1 x 2^e, s negative", norm, W_HI, S_CODE | 0x80, [-q11] + [0.0] * 14),
+        # 1.75 x 1.75 = 3.0625: the product's exponent is one above the sum of the fields; q follows the fields
+        one_block("pair 1.75 x 1.75 x 2^e", [c | 6 for c in norm], W_HI | 6, S_CODE, [q11] + [0.0] * 14),
+        # subnormal codes 2^-9, 2^-8, 1.5 * 2^-8, 2^-7: their FIELD says 2^-6, so q = 2^(-6 + 8 - 13) as under 2^-6 itself
+        one_block("pair subnormal x 2^8", [1, 2, 3, 4], W_HI, S_CODE, [q11] * 4),
+        # a zero code beside s takes no part, whatever it is multiplied with
+        one_block("zero codes x 2^8", [0, 0x80], W_HI, S_CODE, [s8, s8]),
+    ]
+    # the pair in ANOTHER block (its scale 2^d) or another K-step: s = 1.875^2 is exact at every T; 64 unit products sum to 64
+    ds = [0, 13, 14, 40, 47]
+    for name, K, pair_at, s_at, want in (("pair in another block", 128, (0, 1), (32,), 1.875 ** 2),
+                                         ("pair in another K-step", 256, (0, 128), (160,), 1.875 ** 2),
+                                         ("64 unit products beside a far pair", 128, (0, 1), tuple(range(64, 128)), 64.0)):
+        a = torch.zeros(len(ds), K, dtype=torch.uint8)
+        w = torch.zeros(K, dtype=torch.uint8)
+        asc = torch.full((len(ds), K // 32), 127, dtype=torch.uint8)
+        code = 0x38 if len(s_at) > 1 else 0x3F
+        a[:, list(pair_at)] = 0x38
+        w[pair_at[0]], w[pair_at[1]] = 0x38, 0xB8
+        a[:, list(s_at)], w[list(s_at)] = code, code
+        for blk in {k // 32 for k in pair_at}:
+            asc[:, blk] = u8([127 + d for d in ds])
+        probes.append((name, K, a, asc, w, torch.full((K // 32,), 127, dtype=torch.uint8), torch.full((len(ds),), want, dtype=torch.float64)))
+    return probes
+
+
+# ------------------------------------------------------------------------------------------------------ measure and bars
+def _ulp(y64, floor=0.0):
+    """The bf16 ulp of bf16(y64), fp64 (zero and subnormal results: that of the smallest normal)."""
+    mag = y64.to(BF).double().abs().clamp_min(max(floor, 2.0 ** -126))
+    return torch.exp2(torch.floor(torch.log2(mag)) - 7)
+
+
+def eps_of(S, ulp, K, ops=0, T=None):
+    return (2.0 * (K + ops) * U32 * S + (0.0 if T is None else T)) / ulp
+
+
+def figures(got, y64, S, K, fam, ops=0, act=None, T=None):
+    """Per family present -> dict(n, worst e, its eps, margin = max(e - 0.5 - eps), share of differing bits, the bar (b) of it,
+    mean signed error over eps <= EPS_MEAN and how many those are, finite)."""
+    g = got.double()
+    ulp = _ulp(y64, ACT_FLOOR if act else 0.0)
+    eps = eps_of(S, ulp, K, ops, T)
+    e = torch.nan_to_num((g - y64).abs() / ulp, nan=math.inf, posinf=math.inf)
+    over = e - ((1.5 if act else 0.5) + eps)
+    differ = bad_elements(got, y64.to(BF))
+    signed = (g - y64) / ulp
+    fam = fam.to(got.device)
+    out = {}
+    for i, name in enumerate(FAMILIES):
+        m = fam == i
+        n = int(m.sum())
+        if not n:
+            continue
+        em, epm = e[m], eps[m]
+        j = int(over[m].argmax())
+        p = min(1.0, 2.0 * float(epm.clamp(max=0.5).mean()))
+        narrow = epm <= EPS_MEAN
+        nn = int(narrow.sum())
+        sd = float(signed[m][narrow].std()) if nn >= 30 else 0.5 + EPS_MEAN
+        out[name] = dict(n=n, e=float(em[j]), eps=float(epm[j]), margin=float(over[m][j]), share=float(differ[m].double().mean()),
+                         share_bar=p + 3.0 * math.sqrt(p * (1.0 - p) / n), mean=float(signed[m][narrow].mean()) if nn else 0.0,
+                         mean_n=nn, mean_sd=sd, eps_median=float(epm.median()), finite=bool(torch.isfinite(g[m]).all()))
+    return out
+
+
+def check(name, got, y64, S, K, fam, restated=None, ops=0, act=None, plan=None, exact=EXACT, T=None, out=print):
+    """Print, per family, the worst e with its eps, the differing share beside the restatement's, and the mean signed errors; then
+    assert the bars of the module docstring.  got bf16 [rows, N]; y64, S fp64; fam [rows, N]; restated bf16 or None (then (c) is
+    not asserted).  The exact families are held to bf16(y64) bit for bit (``exact``: which families; fp8: none, they go to the bars like the others).  -> figures of ``got``."""
+    mine = figures(got, y64, S, K, fam, ops, act, T)
+    rest = figures(restated.to(got.device), y64, S, K, fam, ops, act, T) if restated is not None else {}
+    failed = []
+    for f, m in mine.items():
+        r = rest.get(f)
+        bar = (1.5 if act else 0.5)
+        out(f"{name} | {f:9s} | n {m['n']:8d} | worst e {m['e']:9.3f} (bar {bar} + eps {m['eps']:.3f}; median eps {m['eps_median']:.3f})"
+            f" | differing share {m['share']:.4f} (bar {m['share_bar']:.4f}"
+            + (f", restatement {r['share']:.4f}" if r else "") + f") | mean signed {m['mean']:+.4f} over {m['mean_n']}"
+            + (f" (restatement {r['mean']:+.4f}, worst e {r['e']:.3f})" if r else ""))
+        if not m["finite"]:
+            failed.append(f"{f}: a result is not finite")
+            continue
+        if not m["margin"] <= 0.0:
+            failed.append(f"{f}: e {m['e']:.3f} > {bar} + eps = {bar + m['eps']:.3f}")
+        if f in exact and act is None:
+            if m["share"] != 0.0:
+                failed.append(f"{f}: exact family, share {m['share']:.5f} of the elements differ from bf16(fp64)")
+            continue
+        if act is None:
+            if not m["share"] <= m["share_bar"]:
+                failed.append(f"{f}: differing share {m['share']:.4f} > {m['share_bar']:.4f}")
+            margin = max(MEAN_MARGIN, 3.0 * math.sqrt(2.0 / max(m["mean_n"], 1)) * r["mean_sd"]) if r else 0.0
+            if r and m["mean_n"] and not abs(m["mean"] - r["mean"]) <= margin:
+                failed.append(f"{f}: mean signed error {m['mean']:+.4f} against the restatement's {r['mean']:+.4f} +- {margin:.3f}")
+    if failed:
+        bad = bad_elements(got, y64.to(BF))
+        raise AssertionError(f"{name} [plan {plan}]: " + "; ".join(failed) + " | " + describe(bad, got, y64.to(BF)))
+    return mine
+
+
+# ------------------------------------------------------------------------------------------------------- the GPU matrix
+KERNEL_OF = {("t128x128", "mxfp8"): 0, ("t128x128", "mxfp6"): 0, ("t256x256", "mxfp6"): 0, ("p256", "mxfp8"): 2, ("p256", "mxfp6"): 18}
+T128_SHAPES = ((300, 264, 128), (300, 264, 512), (300, 264, 640), (130, 128, 3072), (130, 128, 12288))
+P256_SHAPES = ((300, 264, 512), (300, 264, 640), (1, 8, 1024), (130, 128, 12288))
+T256_SHAPE = (3500, 3700, 256)                 # 14 x 15 = 210 tiles of 256 x 256: the smallest launch class that reaches it
+ONE_HOT_SHAPE = (300, 512, 512)
+EPILOGUES = {
+    "bias": dict(bias=True), "gelu": dict(bias=True, act="gelu_tanh"), "gate_res": dict(bias=True, gates=True, res=True),
+    "split3": dict(bias=True), "alpha": dict(alpha=0.5), "rowscale": dict(bias=True, rowscale=True), "batch2": dict(bias=True),
+}
+EPI_SHAPE = {"t128x128": (300, 264, 512), "p256": (300, 264, 512), "t256x256": T256_SHAPE}
+
+
+def mx_cases():
+    """Every (path, fmt, w_fmt, M, N, K) of the plain-launch matrix."""
+    cases = []
+    for fmt, w_fmt in PAIRS:
+        cases += [("t128x128", fmt, w_fmt, *s) for s in T128_SHAPES]
+        cases += [("p256", fmt, w_fmt, *s) for s in P256_SHAPES]
+        if fmt == "mxfp6":
+            cases.append(("t256x256", fmt, w_fmt, *T256_SHAPE))
+    return cases
+
+
+def mx_instances():
+    """Every (path, fmt, w_fmt): the kernel instances."""
+    return sorted({c[:3] for c in mx_cases()})
+
+
+FP8_T128_SHAPES = ((300, 264, 128), (300, 264, 512), (300, 264, 640), (130, 128, 12288))
+FP8_P256_SHAPE = (3500, 3704, 512)             # 14 x 15 = 210 >= 200 tiles, K >= 512, N % 8 == 0: bya_gemm_fp8_plan's rule
+FP8_CASES = [("t128x128", *s) for s in FP8_T128_SHAPES] + [("p256", *FP8_P256_SHAPE)]
+
+
+@functools.lru_cache(maxsize=4)
+def mx_data(fmt, w_fmt, M, N, K, group, batch=1):
+    """(A, W) of a case on the CPU (cached: read-only).  ``group``: "mid", "far" or "one-hot"."""
+    if group == "one-hot":
+        return build_one_hot(M, N, K, fmt, w_fmt)
+    seed = seed_of(f"{fmt}-{w_fmt}-{M}x{N}x{K}-{group}")
+    return build_operand(batch * M, K, fmt, "a", seed, group), build_operand(N, K, w_fmt, "w", seed + 1, group)
+
+
+@functools.lru_cache(maxsize=4)
+def fp8_data(M, N, K, one_hot=False, batch=1):
+    seed = seed_of(f"fp8-{M}x{N}x{K}")
+    return build_fp8(batch * M, K, "a", seed), build_fp8(N, K, "w", seed + 1, one_hot)

@@ -8,85 +8,8 @@ import numpy as np
 import pytest
 import torch
 
-FMT_CODE = {"mxfp8": 0, "mxfp6": 2}
-EMAX = {"mxfp8": 8, "mxfp6": 2}
-BITS = {"mxfp8": 8, "mxfp6": 6}
-
-
-def e2m3_values():
-    """Magnitudes of the 32 non-negative e2m3 codes (code = exponent << 3 | mantissa, exponent bias 1, no inf / NaN)."""
-    c = torch.arange(32)
-    e, m = c >> 3, (c & 7).double()
-    return torch.where(e == 0, m / 8, (1 + m / 8) * torch.pow(2.0, (e - 1).double()))
-
-
-def e2m3_encode_nearest(v):
-    """The definition: RNE of float64 values to e2m3 codes, saturating at 7.5 -- the nearest of the 32 magnitudes, ties to
-    the even code."""
-    vals = e2m3_values()
-    a = v.abs().clamp(max=7.5)
-    d = (a[..., None] - vals).abs()
-    best = d.min(dim=-1, keepdim=True).values
-    cand = (d == best) & ((torch.arange(32) & 1) == 0)          # a tie sits between an odd and an even code
-    code = torch.where(cand.any(-1), cand.int().argmax(-1), (d == best).int().argmax(-1))
-    return code | (torch.signbit(v).long() << 5)
-
-
-def e2m3_encode(v):
-    """The same codes by counting steps of the value's binade (1/8 below 2, 1/4 in [2, 4), 1/2 from 4) and rounding the
-    count half-to-even (torch.round): the form that scales to whole activation matrices."""
-    a = v.abs().clamp(max=7.5)
-    c = torch.where(a < 2, torch.round(a * 8), torch.where(a < 4, torch.round(a * 4) + 8, torch.round(a * 2) + 16))
-    return c.long() | (torch.signbit(v).long() << 5)
-
-
-def e2m3_decode(c):
-    c = c.long()
-    mag = e2m3_values().to(c.device)[c & 31]
-    return torch.where((c & 32) != 0, -mag, mag)
-
-
-def pack6(codes):
-    """[.., K] e2m3 codes -> [.., K * 3 / 4] bytes: element i of a 32-block at bits 6i .. 6i+5, LSB first."""
-    c = codes.long().reshape(*codes.shape[:-1], -1, 4)
-    w = c[..., 0] | (c[..., 1] << 6) | (c[..., 2] << 12) | (c[..., 3] << 18)        # 24 bits = 3 bytes per 4 elements
-    return torch.stack([w & 255, (w >> 8) & 255, (w >> 16) & 255], -1).reshape(*codes.shape[:-1], -1).to(torch.uint8)
-
-
-def unpack6(b):
-    t = b.long().reshape(*b.shape[:-1], -1, 3)
-    w = t[..., 0] | (t[..., 1] << 8) | (t[..., 2] << 16)
-    return torch.stack([(w >> (6 * i)) & 63 for i in range(4)], -1).reshape(*b.shape[:-1], -1)
-
-
-def quant_mx_ref(x, fmt):
-    """include/bya.h, bya_quantize_mx, on the CPU: x bf16 [.., K] -> (codes uint8 [.., K * bits / 8], scales uint8 [.., K / 32])."""
-    xf = x.float().double()
-    blk = xf.reshape(*xf.shape[:-1], -1, 32)
-    amax = blk.abs().amax(-1, keepdim=True)
-    _, ex = torch.frexp(amax)                                        # amax = mant * 2^ex, mant in [0.5, 1)
-    E = (ex.long() - 1 - EMAX[fmt]).clamp(-127, 127)
-    zero = amax == 0
-    E = torch.where(zero, torch.zeros_like(E), E)
-    v = torch.ldexp(blk, -E.double())                                # exact: a power-of-two product
-    if fmt == "mxfp8":
-        q = v.clamp(-448.0, 448.0).float().to(torch.float8_e4m3fn).view(torch.uint8).long()
-    else:
-        q = e2m3_encode(v)
-    q = torch.where(zero, torch.zeros_like(q), q).reshape(*x.shape)
-    codes = q.to(torch.uint8) if fmt == "mxfp8" else pack6(q)
-    return codes, (E + 127).squeeze(-1).to(torch.uint8)
-
-
-def dequant_mx(codes, scales, fmt):
-    """MX bytes -> float64 [.., K]."""
-    if fmt == "mxfp8":
-        el = codes.view(torch.float8_e4m3fn).double()
-    else:
-        el = e2m3_decode(unpack6(codes))
-    el = el.reshape(*scales.shape, 32)
-    return torch.ldexp(el, (scales.long() - 127)[..., None].double()).reshape(*scales.shape[:-1], -1)
-
+from mx_ref import (BITS, EMAX, FMT_CODE, dequant_mx, e2m3_decode, e2m3_encode, e2m3_encode_nearest, e2m3_values,  # noqa: F401
+                    pack6, quant_mx_ref, unpack6)
 
 def test_e2m3_codes_are_fixed_points_and_ties_go_to_even():
     codes = torch.arange(64)

@@ -8,34 +8,42 @@ import torch.nn.functional as F
 
 from conftest import rel_fro
 from exact_gemm import SENTINEL, assert_exact
-from test_mx_cpu import BITS, dequant_mx, e2m3_encode, pack6, quant_mx_ref
+from mx_ref import BITS, dequant_mx, e2m3_encode, hard_inputs, pack6, quant_mx_ref, rnd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FORMATS = ("mxfp6", "mxfp8")
 
 
-def rnd(shape, seed, std=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(shape, generator=g) * std).to(torch.bfloat16)
+def sample_rows(M, gate_split, limit=288):
+    """Every row of a small launch; of a large one the first 8 (``hard_inputs`` plants its blocks in rows 0 .. 3), the 8 around the
+    gate boundary, the last 8 (the tail tile) and rows at a fixed odd stride."""
+    if M <= limit:
+        return torch.arange(M)
+    picks = set(range(8)) | set(range(M - 8, M)) | set(range(0, M, (M // (limit - 24)) | 1))
+    if gate_split:
+        picks |= set(range(max(0, gate_split - 4), min(M, gate_split + 4)))
+    return torch.tensor(sorted(picks))
 
 
-def hard_inputs(M, K, seed):
-    """Gaussian rows with per-channel outliers, all-zero and -0 blocks, saturating blocks and tiny (subnormal-range) blocks."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(M, K, generator=g) * 2.0
-    x[:, torch.randperm(K, generator=g)[:max(1, K // 64)]] *= 300.0                   # outlier channels
-    x = x.to(torch.bfloat16)
-    x[0, :64] = 0
-    x[1 % M, 32:64] = -0.0
-    if M > 2:
-        # a block whose maximum is just below the next power of two: x * 2^-E rounds past the largest finite value
-        x[2, :32] = torch.tensor([7.9, -7.95, 3.0] + [0.01] * 29).to(torch.bfloat16)
-        x[2, 32:64] = torch.tensor([511.0, -500.0, 470.0] + [1.0] * 29).to(torch.bfloat16)
-    if M > 3:
-        x[3, :32] = (torch.randn(32, generator=g) * 1e-39).to(torch.bfloat16)          # bf16 subnormals: E clamps at -127
-        x[3, 32:64] = (torch.randn(32, generator=g) * 1e30).to(torch.bfloat16)
-    return x
+def check_vs_fp64(name, got, ad, wd, K, bias, act, args, fmts, scales):
+    """cond_gemm.check of an output against the fp64 definition on the dequantised bytes ``ad``, ``wd``: the bar per element with
+    the EXACT block term, the differing share (without an activation) and, at K = 12288, where eps is wide, the signed mean
+    against the restatement.  e2m3 activations (block term zero): every element.  e4m3 activations: every element of
+    ``sample_rows``, since the exact term costs M N K operations."""
+    import cond_gemm as C
+    M = got.shape[0]
+    e = dict(C.NO_EPILOGUE, bias=bias, act=act, gate0=args.get("gate0"), gate1=args.get("gate1"), gate_split=args.get("gate_split", 0),
+             res=args.get("res"))
+    asc, wsc = scales
+    if fmts[0] != "mxfp6":
+        rows = sample_rows(M, e["gate_split"]).to(got.device)
+        got, ad, asc = got[rows], ad[rows], asc[rows]
+        e.update(row_ids=rows, res=None if e["res"] is None else e["res"][rows])
+    y64, S, T = C.reference(ad, wd, e, T=C.mx_block_term(ad, wd, *fmts, asc, wsc))
+    fam = torch.full(got.shape, C.MIXED, device=got.device)
+    C.check(name, got.contiguous(), y64, S, K, fam, restated=C.restate(ad, wd, e) if K == 12288 else None, ops=C.epilogue_ops(e),
+            act=act, exact=(), T=T)
 
 
 @pytest.mark.parametrize("fmt", FORMATS)
@@ -129,7 +137,8 @@ def test_gemm_mx_vs_exact_product_of_the_same_bytes(dev, fmt, M, N, K, kw):
     bias = rnd((N,), 4).to(dev) if kw.get("bias") else None
     ac, asc = ops.quantize_mx(a, fmt)
     wc, wsc = ops.quantize_mx(w, fmt)
-    ref = dequant_mx(ac, asc, fmt) @ dequant_mx(wc, wsc, fmt).T                          # fp64, on the device
+    ad, wd = dequant_mx(ac, asc, fmt), dequant_mx(wc, wsc, fmt)
+    ref = ad @ wd.T                                                                      # fp64, on the device
     if bias is not None:
         ref = ref + bias.double()
     if kw.get("act") == "gelu_tanh":
@@ -152,6 +161,8 @@ def test_gemm_mx_vs_exact_product_of_the_same_bytes(dev, fmt, M, N, K, kw):
     err = rel_fro(got.float(), ref.to(torch.bfloat16).float())
     print(f"{fmt} {M}x{N}x{K} {kw}: rel-Fro vs bf16(exact) = {err:.3e}")
     assert err <= 1e-3
+    # the Frobenius bar sees row 3 alone (its 1e30 block carries the whole norm: test_gemm_cond_cpu.py); every element:
+    check_vs_fp64(f"{fmt} {M}x{N}x{K} {kw}", got, ad, wd, K, bias, kw.get("act"), args, (fmt, fmt), (asc, wsc))
 
 
 def test_gemm_mx_batched_operands(dev):

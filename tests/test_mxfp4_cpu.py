@@ -9,77 +9,11 @@ import numpy as np
 import pytest
 import torch
 
-from test_mx_cpu import dequant_mx, quant_mx_ref
+from mx_ref import (dequant, dequant_mx, e2m1_decode, e2m1_encode, e2m1_encode_nearest, e2m1_values, pack4,  # noqa: F401
+                    quant_mx_ref, quant_ref, unpack4)
 
 E4M3, E2M3, E2M1 = 0, 2, 4
 T128X128, T256X256 = 1, 3
-
-
-def e2m1_values():
-    """Magnitudes of the 8 non-negative e2m1 codes (code = exponent << 1 | mantissa, exponent bias 1, no inf / NaN)."""
-    return torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], dtype=torch.float64)
-
-
-def e2m1_encode_nearest(v):
-    """The definition: RNE of float64 values to e2m1 codes, saturating at 6 -- the nearest of the 8 magnitudes, ties to the
-    even code."""
-    vals = e2m1_values()
-    a = v.abs().clamp(max=6.0)
-    d = (a[..., None] - vals).abs()
-    best = d.min(dim=-1, keepdim=True).values
-    cand = (d == best) & ((torch.arange(8) & 1) == 0)           # a tie sits between an odd and an even code
-    code = torch.where(cand.any(-1), cand.int().argmax(-1), (d == best).int().argmax(-1))
-    return code | (torch.signbit(v).long() << 3)
-
-
-def e2m1_encode(v):
-    """The same codes by counting steps of the value's binade (1/2 below 2, 1 in [2, 4), 2 from 4) and rounding the count
-    half-to-even: the form csrc/mx_common.h's f32_to_e2m1 uses."""
-    a = v.abs().clamp(max=6.0)
-    c = torch.where(a < 2, torch.round(a * 2), torch.where(a < 4, torch.round(a) + 2, torch.round(a / 2) + 4))
-    return c.long() | (torch.signbit(v).long() << 3)
-
-
-def e2m1_decode(c):
-    c = c.long()
-    mag = e2m1_values().to(c.device)[c & 7]
-    return torch.where((c & 8) != 0, -mag, mag)
-
-
-def pack4(codes):
-    """[.., K] e2m1 codes -> [.., K / 2] bytes: element i in bits 4 (i % 2) .. +3 of byte i / 2, low nibble first."""
-    c = codes.long().reshape(*codes.shape[:-1], -1, 2)
-    return (c[..., 0] | (c[..., 1] << 4)).to(torch.uint8)
-
-
-def unpack4(b):
-    b = b.long()
-    return torch.stack([b & 15, b >> 4], -1).reshape(*b.shape[:-1], -1)
-
-
-def quant_ref(x, fmt):
-    """include/bya.h, bya_quantize_mx, on the CPU for "mxfp4" (codes uint8 [.., K / 2], scales uint8 [.., K / 32]); the other
-    two formats go to tests/test_mx_cpu.py."""
-    if fmt != "mxfp4":
-        return quant_mx_ref(x, fmt)
-    xf = x.float().double()
-    blk = xf.reshape(*xf.shape[:-1], -1, 32)
-    amax = blk.abs().amax(-1, keepdim=True)
-    _, ex = torch.frexp(amax)                                        # amax = mant * 2^ex, mant in [0.5, 1)
-    E = (ex.long() - 1 - 2).clamp(-127, 127)                         # emax_elem = 2
-    zero = amax == 0
-    E = torch.where(zero, torch.zeros_like(E), E)
-    q = e2m1_encode(torch.ldexp(blk, -E.double()))                   # exact: a power-of-two product
-    q = torch.where(zero, torch.zeros_like(q), q).reshape(*x.shape)
-    return pack4(q), (E + 127).squeeze(-1).to(torch.uint8)
-
-
-def dequant(codes, scales, fmt):
-    """MX bytes -> float64 [.., K]."""
-    if fmt != "mxfp4":
-        return dequant_mx(codes, scales, fmt)
-    el = e2m1_decode(unpack4(codes)).reshape(*scales.shape, 32)
-    return torch.ldexp(el, (scales.long() - 127)[..., None].double()).reshape(*scales.shape[:-1], -1)
 
 
 def test_e2m1_codes_are_fixed_points_ties_go_to_even_and_nibbles_round_trip():

@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_fro
-from test_mx_gpu import exact_operand, hard_inputs, rnd
+from test_mx_gpu import check_vs_fp64, exact_operand, hard_inputs, rnd
 from test_mxfp4_cpu import dequant, e2m1_encode, pack4, quant_ref
 
 pytestmark = pytest.mark.gpu
@@ -81,7 +81,8 @@ def test_mixed_gemm_vs_exact_product_of_the_same_bytes(dev, fmt, M, N, K, kw):
     bias = rnd((N,), 4).to(dev)
     ac, asc = ops.quantize_mx(a, fmt)
     wc, wsc = ops.quantize_mx(w, "mxfp4")
-    ref = dequant(ac, asc, fmt) @ dequant(wc, wsc, "mxfp4").T + bias.double()            # fp64, on the device
+    ad, wd = dequant(ac, asc, fmt), dequant(wc, wsc, "mxfp4")
+    ref = ad @ wd.T + bias.double()                                                      # fp64, on the device
     if kw.get("act") == "gelu_tanh":
         ref = F.gelu(ref, approximate="tanh")
     args = {}
@@ -102,6 +103,7 @@ def test_mixed_gemm_vs_exact_product_of_the_same_bytes(dev, fmt, M, N, K, kw):
     err = rel_fro(got.float(), ref.to(torch.bfloat16).float())
     print(f"{fmt} x mxfp4 {M}x{N}x{K} {kw}: rel-Fro vs bf16(exact) = {err:.3e}")
     assert err <= 1e-3
+    check_vs_fp64(f"{fmt} x mxfp4 {M}x{N}x{K} {kw}", got, ad, wd, K, bias, kw.get("act"), args, (fmt, "mxfp4"), (asc, wsc))
 
 
 @pytest.mark.parametrize("fmt", ACT_FORMATS)
