@@ -112,6 +112,21 @@ typedef struct bya_gemm_desc {
 
 int bya_gemm_bf16(const void* A, const void* W, const void* bias, void* C, const void* res,
                   const void* gate0, const void* gate1, const bya_gemm_desc* desc, hipStream_t stream);
+/* Domain of the bf16 GEMMs (what the definition above promises for bya_gemm_bf16 on every plan path, with split-K and with a row
+ * split, for bya_gemm_skinny_bf16 and for bya_rowgemm512 without LayerNorm, and what tests/test_gemm_bf16_cond_gpu.py holds each
+ * of them to, element by element against fp64 on the very bits):
+ *   operands   every finite bf16 value, subnormals (j * 2^-133, |j| <= 127) and +-255 * 2^120 included: v_mfma_f32_16x16x32_bf16
+ *              keeps subnormal operands (measured: rows of nothing but subnormals times 2^120 come back bit-exact on every path,
+ *              and a one-hot W returns all 65280 finite bit patterns of A unchanged).  NaN / Inf propagation is not specified.
+ *   range      every partial sum, in any K order, and the result within fp32's finite range: sum_k |a_k w_k| below 2^126 is
+ *              enough.  Products and sums below 2^-126 underflow gradually (multiples of 2^-149), they are not flushed.
+ *   order      any K order: the sum is within 2 K 2^-24 sum_k |a_k w_k| of the exact one (one fp32 addition per product, each
+ *              allowed to truncate); where every partial sum is exact in fp32 the result is the exact one rounded once, bit for
+ *              bit, on every path.
+ *   epilogue   in fp32 with ONE rounding, at the end: v = alpha * act(fma(rowscale, bias, sum)); v *= gate; v += res; bf16(v),
+ *              round to nearest even.  No operand or intermediate is rounded to bf16 on the way -- not the gate, not
+ *              gate * alpha, not rowscale * bias, not the value the residual is added to.
+ * (DESIGN.md section 17 has the first run's figures.) */
 
 /* The packed q|k|v projection of a DiT block WITH the per-head q/k LayerNorm(64, eps, affine) + interleaved-pair RoPE of
  * bya_qknorm_rope in its epilogue (reference models/transformer.py:200-209,241-245 = diffusers Attention.to_q/k/v followed by

@@ -75,6 +75,12 @@ such an element.  (Where an ulp is thousands of times smaller than S -- ``cancel
 a mean would say nothing.)  (b) and (c) are not asserted under an activation (the kernel's tanh is not the restatement's) nor
 on the exact families (they are held bit for bit).
 BAR (d):  every output finite, guard band intact (``exact_gemm.GuardedOut``).
+BAR (e), where the caller passes ``rms_of`` (the bf16 GEMMs of ``cond_gemm_bf16.py`` at K >= 1024, where eps of (a) has grown to
+several ulps): per family of at least RMS_MIN_N = 1000 elements, the root mean square of (got - y64) / ulp is at most RMS_FACTOR =
+1.25 (the project's own factor: test_rowgemm512, "no further from the exact result than 1.25 x the reference chain") times the
+largest rms among the given correct summation orders.
+HOOKS for the sibling suites: ``figures`` / ``check`` take the family-name table ``fam`` indexes (``families``; an index outside
+it belongs to no family); ``reference`` / ``epilogue32`` take every activation of ACT64, each with its derived slope (below).
 The restatement (``restate``): the sum of each 32-block exact (fp64 holds it: 32 products of 8 significant bits over 35
 binades), rounded to fp32 and added to an fp32 accumulator block by block; the epilogue in fp32 as csrc/gemm_common.h writes it.
 tests/test_gemm_cond_cpu.py holds it, a reversed K order and a 128-step grouping inside every bar, and plants the faults that
@@ -112,6 +118,21 @@ MIXED, FAR, ONE_HOT = FAMILIES.index("mixed"), FAMILIES.index("far"), FAMILIES.i
 SCALE_HALF = {"near": 3, "spread": 10, "cancel": 3, "subnormal": 1, "extreme": 1}
 FAR_LOW, FAR_HIGH, FAR_HALF = 27, 227, 8
 GELU_SLOPE = 1.13
+# The activations of ``reference`` in fp64, and a Lipschitz bound of each smooth one (with x = the pre-activation,
+# phi / Phi the normal density / distribution, s the logistic function):
+#   gelu_erf   f = x Phi(x),  f' = Phi(x) + x phi(x),  f'' = phi(x) (2 - x^2).  f'' = 0 at x = sqrt 2, where f' is largest:
+#              Phi(1.41421) + 1.41421 phi(1.41421) = 0.92135 + 0.20755 = 1.1289 < 1.13;  |f''| <= f''(0) = 2 phi(0) = 0.798 < 1.
+#   silu       f = x s(x),  f' = s (1 + x (1 - s)),  f'' = s (1 - s) (2 + x (1 - 2 s)).  f'' = 0 at x = 2.3994, where
+#              f' = 0.91678 * (1 + 2.3994 * 0.08322) = 1.0998 < 1.10;  |f''| <= f''(0) = 0.5 < 1.
+#   gelu_tanh  1.13 and |f''| < 1 as before (its "ieee" twin in the kernels is the same function).
+#   relu, leaky_relu (negative slope 0.01): slope 1 for x > 0 and 0 / 0.01 for x < 0, no second-order term.
+ACT64 = {"gelu_tanh": lambda x: torch.nn.functional.gelu(x, approximate="tanh"),
+         "gelu_tanh_ieee": lambda x: torch.nn.functional.gelu(x, approximate="tanh"),
+         "gelu_erf": torch.nn.functional.gelu, "silu": torch.nn.functional.silu, "relu": torch.nn.functional.relu,
+         "leaky_relu": lambda x: torch.nn.functional.leaky_relu(x, 0.01)}
+ACT_SLOPE = {"gelu_tanh": GELU_SLOPE, "gelu_tanh_ieee": GELU_SLOPE, "gelu_erf": 1.13, "silu": 1.10}
+ACT_NEGATIVE_SLOPE = {"relu": 0.0, "leaky_relu": 0.01}
+RMS_FACTOR, RMS_MIN_N = 1.25, 1000             # bar (e)
 ACT_FLOOR = 2.0 ** -6
 EPS_MEAN, MEAN_MARGIN = 4.0, 0.25
 SIGN = {"mxfp8": 0x80, "mxfp6": 0x20, "mxfp4": 0x8}
@@ -345,12 +366,17 @@ def reference(a64, w64, e=NO_EPILOGUE, M=None, T=None, base_ops=0):
         add = rs * e["bias"].double()[None]
         y, S = y + add, S + add.abs()
     if e["act"] is not None:
-        assert e["act"] == "gelu_tanh"
-        gelu = lambda x: torch.nn.functional.gelu(x, approximate="tanh")
-        # Taylor: |gelu(x + d) - gelu(x)| <= |gelu'(x)| |d| + max |gelu''| d^2 / 2, |d| <= 2 (K + 4) u32 S and max |gelu''| < 1
-        slope = (gelu(y + 2.0 ** -20) - gelu(y - 2.0 ** -20)).abs() * 2.0 ** 19
-        slope = (slope + (a64.shape[1] + epilogue_ops(e, base_ops)) * U32 * S + (0.0 if T is None else 0.5 * T)).clamp(max=GELU_SLOPE)
-        y, S = gelu(y), S * slope
+        act = ACT64[e["act"]]
+        # d = 2 (K + ops) u32 S (+ T) bounds the pre-activation's error; ``half`` is d / 2
+        half = (a64.shape[1] + epilogue_ops(e, base_ops)) * U32 * S + (0.0 if T is None else 0.5 * T)
+        if e["act"] in ACT_SLOPE:
+            # Taylor: |act(x + d) - act(x)| <= |act'(x)| |d| + max |act''| d^2 / 2 with max |act''| < 1, capped by the Lipschitz constant
+            slope = (act(y + 2.0 ** -20) - act(y - 2.0 ** -20)).abs() * 2.0 ** 19
+            slope = (slope + half).clamp(max=ACT_SLOPE[e["act"]])
+        else:
+            # relu / leaky_relu: piecewise linear, no second-order term; within d of 0 the larger one-sided slope (1)
+            slope = torch.where(y > -2.0 * half, torch.ones_like(y), torch.full_like(y, ACT_NEGATIVE_SLOPE[e["act"]]))
+        y, S = act(y), S * slope
         T = None if T is None else T * slope
     f = abs(e["alpha"])
     y = y * e["alpha"]
@@ -421,7 +447,7 @@ def epilogue32(acc, e=NO_EPILOGUE, M=None):
         rs = 1.0 if e["rowscale"] is None else e["rowscale"].double()[:, None]
         v = (acc.double() + rs * e["bias"].double()[None]).float()                   # one rounding: the fma
     if e["act"] is not None:
-        v = torch.nn.functional.gelu(v, approximate="tanh")
+        v = ACT64[e["act"]](v)
     if e["alpha"] != 1.0:
         v = v * e["alpha"]
     g = _gate(e, rows, M or rows, torch.float32)
@@ -536,9 +562,11 @@ def eps_of(S, ulp, K, ops=0, T=None):
     return (2.0 * (K + ops) * U32 * S + (0.0 if T is None else T)) / ulp
 
 
-def figures(got, y64, S, K, fam, ops=0, act=None, T=None):
+def figures(got, y64, S, K, fam, ops=0, act=None, T=None, families=None):
     """Per family present -> dict(n, worst e, its eps, margin = max(e - 0.5 - eps), share of differing bits, the bar (b) of it,
-    mean signed error over eps <= EPS_MEAN and how many those are, finite)."""
+    mean signed error over eps <= EPS_MEAN and how many those are, rms of the signed error, finite).  ``families``: the table
+    ``fam`` indexes (default FAMILIES); an index outside it belongs to no family and is not looked at."""
+    families = FAMILIES if families is None else families
     g = got.double()
     ulp = _ulp(y64, ACT_FLOOR if act else 0.0)
     eps = eps_of(S, ulp, K, ops, T)
@@ -548,7 +576,7 @@ def figures(got, y64, S, K, fam, ops=0, act=None, T=None):
     signed = (g - y64) / ulp
     fam = fam.to(got.device)
     out = {}
-    for i, name in enumerate(FAMILIES):
+    for i, name in enumerate(families):
         m = fam == i
         n = int(m.sum())
         if not n:
@@ -561,16 +589,23 @@ def figures(got, y64, S, K, fam, ops=0, act=None, T=None):
         sd = float(signed[m][narrow].std()) if nn >= 30 else 0.5 + EPS_MEAN
         out[name] = dict(n=n, e=float(em[j]), eps=float(epm[j]), margin=float(over[m][j]), share=float(differ[m].double().mean()),
                          share_bar=p + 3.0 * math.sqrt(p * (1.0 - p) / n), mean=float(signed[m][narrow].mean()) if nn else 0.0,
-                         mean_n=nn, mean_sd=sd, eps_median=float(epm.median()), finite=bool(torch.isfinite(g[m]).all()))
+                         mean_n=nn, mean_sd=sd, eps_median=float(epm.median()),
+                         rms=float(torch.nan_to_num(signed[m], nan=math.inf).square().mean().sqrt()), finite=bool(torch.isfinite(g[m]).all()))
     return out
 
 
-def check(name, got, y64, S, K, fam, restated=None, ops=0, act=None, plan=None, exact=EXACT, T=None, out=print):
+def check(name, got, y64, S, K, fam, restated=None, ops=0, act=None, plan=None, exact=EXACT, T=None, out=print, families=None,
+          rms_of=None):
     """Print, per family, the worst e with its eps, the differing share beside the restatement's, and the mean signed errors; then
     assert the bars of the module docstring.  got bf16 [rows, N]; y64, S fp64; fam [rows, N]; restated bf16 or None (then (c) is
-    not asserted).  The exact families are held to bf16(y64) bit for bit (``exact``: which families; fp8: none, they go to the bars like the others).  -> figures of ``got``."""
-    mine = figures(got, y64, S, K, fam, ops, act, T)
-    rest = figures(restated.to(got.device), y64, S, K, fam, ops, act, T) if restated is not None else {}
+    not asserted).  The exact families are held to bf16(y64) bit for bit (``exact``: which families; fp8: none, they go to the bars like the others).
+    ``families``: the family-name table ``fam`` indexes (default FAMILIES).  ``rms_of``: bf16 results of correct summation orders
+    (a list); with it bar (e) is asserted: per family of at least RMS_MIN_N elements, the rms of (got - y64) / ulp is at most
+    RMS_FACTOR times the largest of theirs.  -> figures of ``got``."""
+    fig = lambda t: figures(t.to(got.device), y64, S, K, fam, ops, act, T, families)
+    mine = fig(got)
+    rest = fig(restated) if restated is not None else {}
+    orders = [fig(t) for t in rms_of] if rms_of else []
     failed = []
     for f, m in mine.items():
         r = rest.get(f)
@@ -578,12 +613,18 @@ def check(name, got, y64, S, K, fam, restated=None, ops=0, act=None, plan=None, 
         out(f"{name} | {f:9s} | n {m['n']:8d} | worst e {m['e']:9.3f} (bar {bar} + eps {m['eps']:.3f}; median eps {m['eps_median']:.3f})"
             f" | differing share {m['share']:.4f} (bar {m['share_bar']:.4f}"
             + (f", restatement {r['share']:.4f}" if r else "") + f") | mean signed {m['mean']:+.4f} over {m['mean_n']}"
-            + (f" (restatement {r['mean']:+.4f}, worst e {r['e']:.3f})" if r else ""))
+            + (f" (restatement {r['mean']:+.4f}, worst e {r['e']:.3f})" if r else "")
+            + f" | rms {m['rms']:.4f}" + (f" (restatement {r['rms']:.4f})" if r else "")
+            + (" (orders " + ", ".join("%.4f" % o[f]["rms"] for o in orders) + ")" if orders else ""))
         if not m["finite"]:
             failed.append(f"{f}: a result is not finite")
             continue
         if not m["margin"] <= 0.0:
             failed.append(f"{f}: e {m['e']:.3f} > {bar} + eps = {bar + m['eps']:.3f}")
+        if orders and act is None and f not in exact and m["n"] >= RMS_MIN_N:
+            top = max(o[f]["rms"] for o in orders)
+            if not m["rms"] <= RMS_FACTOR * top:
+                failed.append(f"{f}: rms error {m['rms']:.4f} ulp > {RMS_FACTOR} x {top:.4f}, the largest of the restatement orders")
         if f in exact and act is None:
             if m["share"] != 0.0:
                 failed.append(f"{f}: exact family, share {m['share']:.5f} of the elements differ from bf16(fp64)")
