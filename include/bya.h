@@ -1026,6 +1026,13 @@ int bya_rowgemm512_plan(const void* X, const void* W, const float* colsum, const
  * Statistics: one pass, as bya_rowgemm512 with ln = 1 -- the same domain (|mean| / spread <= 8) and, measured through a one-key
  * group (L = 1: O = v), the same drift beyond it: 0.78 bf16 ulp at 8 with colsum = 25.6, 5.9 at 64, 58 at 256, 429 on
  * near-constant rows.
+ * Score domain: the softmax subtracts each query's largest score over the keys of its group before exp2, so there is NO
+ * static bound on q . k * scale (unlike the static-bound attention kernels above).  The suite holds every output element to
+ * the fp64 softmax of the bf16 q, k, v on scores of up to +-162 exp2 units (q . k * scale * log2 e) within one group, a
+ * constant of +-60 under a row, one key 40 above the rest, and all-equal scores (tests/cond_rowattn.py: |error| <=
+ * (1 + eps) 2^-8 (sum_j p_j |v_j| / l + |O|), eps = 0.19 there).  The keys of the tile's other groups, its empty slots (which
+ * read as rows of zeros: k = cvec_k, v = cvec_v) and rows of no group have no weight in the result, whatever they hold.
+ * bya_router_group_attn_out inherits all of it.
  * --------------------------------------------------------------------------------------------- */
 int bya_router_group_attn(const void* X, const void* Wqkv, const float* colsum, const float* cvec, void* O,
                           int32_t M, int32_t ldx, int32_t ldo, int32_t L, int64_t n_outer, int64_t n_inner,
