@@ -15,11 +15,17 @@ One ``DenoiseEngine.step`` == one reference ``BindyouravatarTransformer3DModel.f
 * Step-invariant tensors (face tokens, per-layer face K/V, router keys, audio context, per-layer audio K/V) are
   produced by ``_face_invariants`` / ``_audio_invariants``; they are recomputed every step like the reference
   unless ``cache_invariants`` is switched on (explicit opt-in used by the pipeline).
+* ``_step`` is the step's table of contents: it makes one context (``_step_context``) and calls one short method per stage -- context,
+  conditioning, AdaLN vector, patch embed, then per block the AdaLN LayerNorm + joint attention (one of four ``_attn_*``
+  transports, chosen once per step), the MLP pair, face routing, audio injection, and the head.  The router half
+  (``_router``, ``_r_*``) has the same shape.  A stage reads and writes the context; none reads another's locals.
 
 Nothing here falls back to torch math: torch is used for device memory, views and copies only.
 """
 import contextlib
+import functools
 import os
+import types
 
 import torch
 
@@ -186,6 +192,9 @@ class DenoiseEngine:
         # (r6) sharded step, P2P transport: exchange A's v third on the side stream underneath the q | k projection
         # ("1" where a rank has at least SP_OVERLAP_V_MIN_ROWS rows, "0" never, "all" always)
         self.sp_overlap_v = os.environ.get("BYA_SP_OVERLAP_V", "1") != "0"
+        # below this many rows per rank the two smaller projection launches cost more than the hidden link time buys (2222 rows of
+        # an 8-rank step: 108 + 216 tiles of 256 x 256 on 256 CUs instead of 324)
+        self.SP_OVERLAP_V_MIN_ROWS = 0 if os.environ.get("BYA_SP_OVERLAP_V") == "all" else 4096
         self.sp_shard_mods = os.environ.get("BYA_SP_SHARD_MODS", "1") != "0"      # (r6) the AdaLN vector in column slices, one per rank
         # sharded step: the audio kv-mix of a rank's partial frames as ONE launch over a segment table (bya_attn_kv_mix_seg; the same
         # bits as the launch per partial frame).  "1" switches it on.  Off by default for now: the sharded MX test
@@ -197,8 +206,6 @@ class DenoiseEngine:
         # (bya_attn_kv_mix_batch, bya_router_scores_batch, bya_router_head_batch).  Off by default: one GPU shows no gain beyond run-to-run spread (DESIGN.md
         # section 5, "The guided step's [uncond, cond] pair").
         self.batch_launches = bool(getattr(model, "batch_launches", False)) or os.environ.get("BYA_BATCH_LAUNCHES") == "1"
-        if os.environ.get("BYA_SP_OVERLAP_V") == "all":
-            self.SP_OVERLAP_V_MIN_ROWS = 0
         self.router_replicated = os.environ.get("BYA_ROUTER_REPLICATED", "0") == "1"
         # q/k-norm + RoPE inside the q|k|v projection's epilogue (bya_gemm_qkv_norm_rope; bit-identical to the two launches)
         self.qkn_epilogue = os.environ.get("BYA_QKN_EPILOGUE", "1") != "0"
@@ -368,10 +375,10 @@ class DenoiseEngine:
             rp = self._parts[key] = RouterPartition(sh.rank, sh.world, pairs, per_frame, sh.group, sh.p2p)
         return rp
 
-    def _buf(self, name, *shape):
+    def _buf(self, name, *shape, dtype=torch.bfloat16):
         t = self._ws.get(name)
         if t is None or tuple(t.shape) != tuple(shape):
-            t = torch.empty(*shape, dtype=torch.bfloat16, device=self.dev)
+            t = torch.empty(*shape, dtype=dtype, device=self.dev)
             self._ws[name] = t
         return t
 
@@ -771,43 +778,76 @@ class DenoiseEngine:
 
     def _step(self, hidden_states, encoder_hidden_states, timestep, image_rotary_emb, id_cond, id_vit_hidden,
               audio_embeds, af_matrix, routing_logits_forcing, taps=None):
-        n_id = self.n_id = self._count_ids(id_cond, audio_embeds)
-        m, cfg, D, H = self.m, self.cfg, self.D, self.H
-        B, T, C, Hh, Ww = hidden_states.shape
+        """The step's table of contents: one context, the stages in order, the block loop, the head.  ``taps`` (a dict) is
+        filled with clones of the intermediate tensors (and keeps the cross-attentions on their unfused paths)."""
+        m = self.m
+        c = self._step_context(hidden_states, encoder_hidden_states, timestep, image_rotary_emb, id_cond, audio_embeds, taps)
+        self._conditioning(c, id_cond, id_vit_hidden, audio_embeds, af_matrix, routing_logits_forcing)
+        self._adaln_vector(c)
+        self._patch_embed(c)
+        attention = self._block_buffers(c)
+        for i, blk in enumerate(m.transformer_blocks):
+            # ---- D2..D4: CogVideoXBlock (models/transformer.py:223-262)
+            xq, gated = self._adaln(c, i, 0, blk.norm1)
+            attention(c, i, blk.attn1, xq, gated)
+            xq, gated = self._adaln(c, i, 1, blk.norm2)
+            self._mlp_pair(c, i, blk.ff, xq, gated)
+            if taps is not None:
+                taps[f"block{i}"] = c.x.clone()
+            if c.use_face and i % m.cross_attn_interval == 0:
+                self._face_routing(c, i, i // m.cross_attn_interval)
+            if c.use_audio and i % m.audio_attn_interval == 0:
+                self._audio_injection(c, i, i // m.audio_attn_interval)
+        return self._head(c)
+
+    def _step_context(self, hidden_states, encoder_hidden_states, timestep, image_rotary_emb, id_cond, audio_embeds, taps):
+        """-> the context the stages of this step share (a plain namespace): the geometry; the rank's shard ``sh`` with its row
+        counts; the inputs in the engine's types; later the AdaLN vector (``emb``, ``mods``, batch stride ``mbs``), the resident
+        buffers (``qkv`` = the views (q, k, v); sharded: ``heads`` or ``kv_full``), ``r_logits``, which a face layer leaves for the
+        audio layers behind it, and the conditioning: its results and the side stream ``side`` that produces them, with the
+        marks the layers wait for.  Also keys the workspace by geometry and shard (a new key drops the old workspace)."""
+        m = self.m
+        c = types.SimpleNamespace(taps=taps, side=None, face_marks={}, audio_mark=None, forced=None, af=None, r_logits=None,
+                                  face_kv=None, router_k=None, audio_k=None, audio_v=None)
+        n_id = c.n_id = self.n_id = self._count_ids(id_cond, audio_embeds)
+        B, T, C, Hh, Ww = c.B, c.T, c.C, c.Hh, c.Ww = hidden_states.shape
         ht, wt = Hh // 2, Ww // 2
-        per_frame, N = ht * wt, T * ht * wt
-        Tt = encoder_hidden_states.shape[1]
-        S = Tt + N
-        sh = self._shard(getattr(m, "_seq_rank", 0), getattr(m, "_seq_world", 1), S, Tt, getattr(m, "_seq_group", None))
+        c.per_frame, c.N = ht * wt, T * ht * wt
+        Tt = c.Tt = encoder_hidden_states.shape[1]
+        c.S = Tt + c.N
+        sh = c.sh = self._shard(getattr(m, "_seq_rank", 0), getattr(m, "_seq_world", 1), c.S, Tt, getattr(m, "_seq_group", None))
         if sh.active and B != 1:
             raise NotImplementedError("sequence-parallel execution shards ONE sample; split a CFG batch over rank groups")
-        S_loc, Tt_loc, N_loc, v0, v1 = sh.S_loc, sh.Tt_loc, sh.N_loc, sh.v0, sh.v1
+        c.S_loc, c.Tt_loc, c.N_loc, c.v0, c.v1 = sh.S_loc, sh.Tt_loc, sh.N_loc, sh.v0, sh.v1
         key = (B, T, C, Hh, Ww, Tt, sh.rank, sh.world, n_id)
         if self._ws_key != key:
             self._ws_key, self._ws = key, {}
             if sh.p2p is not None:
                 sh.p2p.drop_tables()       # the copy tables of the old workspace keep its tensors alive (a graph's are pinned)
         sh.begin_step()
-        buf = self._buf
-        hs = self._bf(hidden_states)
-        enc_in = self._bf(encoder_hidden_states)
+        c.hs = self._bf(hidden_states)
+        c.enc_in = self._bf(encoder_hidden_states)
         if not torch.is_tensor(timestep):
             timestep = torch.tensor([timestep] * B)
         ts = timestep.to(device=self.dev, dtype=torch.int64).reshape(-1)
         if ts.numel() == 1 and B > 1:
             ts = ts.expand(B)
-        ts = ts.contiguous()
-        use_face = m.is_train_face
-        use_audio = m.is_train_audio and audio_embeds is not None
-        if use_face and m.router.frames * m.router.height * m.router.width != N:
+        c.ts = ts.contiguous()
+        c.use_face = m.is_train_face
+        c.use_audio = m.is_train_audio and audio_embeds is not None
+        if c.use_face and m.router.frames * m.router.height * m.router.width != c.N:
             raise ValueError(f"router positional table is {m.router.frames}x{m.router.height}x{m.router.width} "
                              f"but the latents give {T}x{wt}x{ht} tokens")
-        cos = sin = None
+        c.cos = c.sin = None
         if image_rotary_emb is not None:
-            cos = image_rotary_emb[0].to(device=self.dev, dtype=torch.float32)[v0:v1].contiguous()
-            sin = image_rotary_emb[1].to(device=self.dev, dtype=torch.float32)[v0:v1].contiguous()
+            c.cos = image_rotary_emb[0].to(device=self.dev, dtype=torch.float32)[c.v0:c.v1].contiguous()
+            c.sin = image_rotary_emb[1].to(device=self.dev, dtype=torch.float32)[c.v0:c.v1].contiguous()
+        c.text_rows = c.Tt_loc if c.cos is not None else c.S_loc      # rows the q/k-norm launches do not rotate
+        return c
 
-        # ---- step-invariant conditioning (replicated on every rank: it is tiny)
+    def _conditioning(self, c, id_cond, id_vit_hidden, audio_embeds, af_matrix, routing_logits_forcing):
+        """The step-invariant conditioning (replicated on every rank: it is tiny), on its side stream, with the marks the
+        layers wait for; ``af`` and the forced routing logits."""
         # (recomputed every step like the reference unless cached.  Their ~250 small launches -- 5 ms when they run alone --
         # go to a side stream: nothing needs them before the first routing layer, ~8 ms into the step, so they fill the CUs
         # the big kernels of patch embed and block 0 leave idle; the main stream joins right before block 0's face branch.)
@@ -815,46 +855,45 @@ class DenoiseEngine:
         # for the side stream's mark behind face layer l's K/V and keys, the first audio layer for the mark behind the audio
         # K/V launch, which is enqueued right behind face layer 0: at 8 ranks the conditioning -- replicated on every rank -- is
         # 7 ms of launches against a 1.9 ms DiT layer, and nothing needs face layer 20's keys before layer 40.)
-        inv_side, face_marks, audio_mark = None, {}, [None]
-        if (use_face or use_audio) and ops._TIMERS is None and self.side_stream_conditioning:
+        if (c.use_face or c.use_audio) and ops._TIMERS is None and self.side_stream_conditioning:
             if self._side is None:
                 self._side = torch.cuda.Stream(self.dev)
-            inv_side = ops.on_stream(self._side)
-        with (inv_side if inv_side is not None else contextlib.nullcontext()):
-            audio_res = []
+            c.side = ops.on_stream(self._side)
 
-            def audio_now():
-                if use_audio and not audio_res:
-                    audio_res.append(self._cached("audio", [audio_embeds], lambda: self._audio_invariants(audio_embeds, T, B, n_id)))
-                    if inv_side is not None:
-                        audio_mark[0] = inv_side.mark()
+        def audio_now():                 # once per step; the mark behind it is what the first audio layer waits for
+            if c.use_audio and c.audio_k is None:
+                c.audio_k, c.audio_v = self._cached("audio", [audio_embeds],
+                                                    lambda: self._audio_invariants(audio_embeds, c.T, c.B, c.n_id))
+                if c.side is not None:
+                    c.audio_mark = c.side.mark()
 
-            def after_face_layer(l):
-                if inv_side is not None:
-                    face_marks[l] = inv_side.mark()
-                if l == 0:
-                    audio_now()
-            if use_face:
-                flat_face = list(id_cond[:n_id]) + [t for i in range(n_id) for t in id_vit_hidden[i]]
-                face_kv, router_k = self._cached("face", flat_face,
-                                                 lambda: self._face_invariants(id_cond, id_vit_hidden, B, n_id, after_face_layer))
+        def after_face_layer(l):         # behind face layer l's K/V and keys: the mark routing layer l waits for
+            if c.side is not None:
+                c.face_marks[l] = c.side.mark()
+            if l == 0:
+                audio_now()
+        with (c.side if c.side is not None else contextlib.nullcontext()):
+            if c.use_face:
+                flat_face = list(id_cond[:c.n_id]) + [t for i in range(c.n_id) for t in id_vit_hidden[i]]
+                c.face_kv, c.router_k = self._cached("face", flat_face, lambda: self._face_invariants(
+                    id_cond, id_vit_hidden, c.B, c.n_id, after_face_layer))
             audio_now()
-            if use_audio:
-                audio_k, audio_v = audio_res[0]
-        if use_audio:
-            af = self._bf(af_matrix)
-        forced = None
-        if routing_logits_forcing is not None and use_face:
+        if c.use_audio:
+            c.af = self._bf(af_matrix)
+        if routing_logits_forcing is not None and c.use_face:
+            T, per_frame, n_id = c.T, c.per_frame, c.n_id
             f_in = self._bf(routing_logits_forcing).reshape(T, per_frame, n_id)
-            forced = ops.forcing_max_over_frames(f_in, buf("forced", 1, N, n_id).view(T, per_frame, n_id), T, per_frame,
-                                                 n_id).view(1, N, n_id)[:, v0:v1].contiguous()
+            c.forced = ops.forcing_max_over_frames(f_in, self._buf("forced", 1, c.N, n_id).view(T, per_frame, n_id), T, per_frame,
+                                                   n_id).view(1, c.N, n_id)[:, c.v0:c.v1].contiguous()
 
-        # ---- D0: timestep embedding and every AdaLN modulation vector of the step
-        tfeat = ops.timestep_features(ts, buf("tfeat", B, D), cfg.flip_sin_to_cos, float(cfg.freq_shift))
+    def _adaln_vector(self, c):
+        """D0: timestep embedding and every AdaLN modulation vector of the step (``c.mods``, batch stride ``c.mbs``)."""
+        m, cfg, buf, B, sh = self.m, self.cfg, self._buf, c.B, c.sh
+        tfeat = ops.timestep_features(c.ts, buf("tfeat", B, self.D), cfg.flip_sin_to_cos, float(cfg.freq_shift))
         te = m.time_embedding
         e1 = ops.linear_small_m(tfeat, te.linear_1.weight, te.linear_1.bias, buf("e1", B, te.linear_1.weight.shape[0]),
                                 act_out="silu")
-        emb = ops.linear_small_m(e1, te.linear_2.weight, te.linear_2.bias, buf("emb", B, te.linear_2.weight.shape[0]))
+        emb = c.emb = ops.linear_small_m(e1, te.linear_2.weight, te.linear_2.bias, buf("emb", B, te.linear_2.weight.shape[0]))
         Nm = self.mod_w.shape[0]
         if sh.active and sh.p2p is not None and B == 1 and self.sp_shard_mods:
             # (r6) sharded step: the AdaLN vector -- 1.55 M outputs against a 1.6 GB weight, 0.6 ms of weight streaming that every
@@ -866,312 +905,321 @@ class DenoiseEngine:
             cut = [(Nm * j // W) // 8 * 8 for j in range(W)] + [Nm]
             part = buf("mods_part", 1, cut[r + 1] - cut[r])
             ops.linear_small_m(emb, self.mod_w[cut[r]:cut[r + 1]], self.mod_b[cut[r]:cut[r + 1]], part, silu_in=True)
-            mods = sh.p2p.symmetric(f"mods:{(1, Nm)}", (1, Nm), torch.bfloat16)
+            c.mods = sh.p2p.symmetric(f"mods:{(1, Nm)}", (1, Nm), torch.bfloat16)
             sh._exchange(("mods", Nm), [(part[0], j, f"mods:{(1, Nm)}", cut[r]) for j in range(W)])
         else:
-            mods = ops.linear_small_m(emb, self.mod_w, self.mod_b, buf("mods", B, Nm), silu_in=True)
-        mbs = mods.stride(0)
+            c.mods = ops.linear_small_m(emb, self.mod_w, self.mod_b, buf("mods", B, Nm), silu_in=True)
+        c.mbs = c.mods.stride(0)
 
-        # ---- D1: patch embed into the joint stream x = [text | video] (this rank's rows only)
-        x = buf("x", B, S_loc, D)
-        xv = x[:, Tt_loc:]
+    def _patch_embed(self, c):
+        """D1: patch embed into the joint stream x = [text | video] (this rank's rows only)."""
+        m, buf, sh, B, Tt, Tt_loc = self.m, self._buf, c.sh, c.B, c.Tt, c.Tt_loc
+        x = c.x = buf("x", B, c.S_loc, self.D)
+        c.xv = x[:, Tt_loc:]
         pe = self.pos_embedding
-        if pe is not None and pe.shape[0] != S:
+        if pe is not None and pe.shape[0] != c.S:
             raise ValueError("learned positional embeddings need the configured sample height/width/frames")
         if Tt_loc:
             tp = m.patch_embed.text_proj
-            ops.gemm(enc_in[:, sh.r0:sh.r0 + Tt_loc], tp.weight, x[:, :Tt_loc], bias=tp.bias,
+            ops.gemm(c.enc_in[:, sh.r0:sh.r0 + Tt_loc], tp.weight, x[:, :Tt_loc], bias=tp.bias,
                      res=None if pe is None else pe[sh.r0:sh.r0 + Tt_loc])
-        cols = ops.patchify(hs, buf("cols", B, N, C * 4))
-        ops.gemm(cols[:, v0:v1], self.patch_w, xv, bias=m.patch_embed.proj.bias,
-                 res=None if pe is None else pe[Tt + v0:Tt + v1])
-        if taps is not None:
-            taps["emb"], taps["embed"] = emb.clone(), x.clone()
+        cols = ops.patchify(c.hs, buf("cols", B, c.N, c.C * 4))
+        ops.gemm(cols[:, c.v0:c.v1], self.patch_w, c.xv, bias=m.patch_embed.proj.bias,
+                 res=None if pe is None else pe[Tt + c.v0:Tt + c.v1])
+        if c.taps is not None:
+            c.taps["emb"], c.taps["embed"] = c.emb.clone(), x.clone()
 
-        xn = buf("xn", B, S_loc, D)
+    def _block_buffers(self, c):
+        """The block loop's resident buffers and, chosen ONCE per step, the transport of the joint attention: -> the method
+        that runs block ``i``'s attention half, ``attention(c, i, attn1, xq, gated)``."""
+        buf, sh, B, S, S_loc, D = self._buf, c.sh, c.B, c.S, c.S_loc, self.D
+        c.xn = buf("xn", B, S_loc, D)
         qkv = buf("qkv", 3, B, S_loc, D)
-        q, k, v = qkv[0], qkv[1], qkv[2]
-        ff = buf("ff", B, S_loc, 4 * D)
-        head_parallel = sh.active and H % sh.world == 0 and not self.sp_allgather
-        if head_parallel:
+        c.qkv = (qkv[0], qkv[1], qkv[2])
+        c.ff = buf("ff", B, S_loc, 4 * D)
+        if not sh.active:
+            return self._attn_local
+        if self.H % sh.world == 0 and not self.sp_allgather:
             W = sh.world
             Dl = D // W
-            qkvb = buf("qkv_blocks", 3 * W, S_loc, Dl)         # column block t*W + j: tensor t (q,k,v), heads of rank j
-            qh, kh, vh = buf("q_heads", S, Dl), buf("k_heads", S, Dl), buf("v_heads", S, Dl)
-            oh = buf("o_heads", S, Dl)
-        elif sh.active:
-            k_full, v_full = buf("k_full", 1, S, D), buf("v_full", 1, S, D)
-        r_logits = None
-        for i, blk in enumerate(m.transformer_blocks):
-            # ---- D2..D4: CogVideoXBlock (models/transformer.py:223-262)
-            for half, nz in enumerate((blk.norm1, blk.norm2)):
-                mo = mods[:, (2 * i + half) * 6 * D:]
-                # chunk order: shift, scale, gate, enc_shift, enc_scale, enc_gate
-                ln_kw = dict(eps=nz.norm.eps, shift0=mo[:, 3 * D:], scale0=mo[:, 4 * D:], shift1=mo, scale1=mo[:, D:],
-                             split=Tt_loc, mod_batch_stride=mbs)
-                xq = None
-                if self._quantised(("qkv", "ff1")[half]) and self.fuse_ln_quant:
-                    # the AdaLN output feeds exactly one Linear (q|k|v, or the MLP's first): emit it in e4m3 / MX directly
-                    xq = self._layernorm_quant(("qkv", "ff1")[half], x, xn.shape, nz.norm.weight, nz.norm.bias, **ln_kw)
-                else:
-                    ops.layernorm(x, xn, nz.norm.weight, nz.norm.bias, **ln_kw)
-                if half == 0:
-                    at = blk.attn1
-                    if head_parallel:
-                        # exchange A, head-parallel: the projection writes per-destination column blocks, q/k-norm +
-                        # RoPE run on the local rows, then rows are traded for heads (every element moves once)
-                        if sh.p2p is None:
-                            self._dit_linear("qkv", i, xn[0], self.qkv_w[i], qkvb[0], bias=self.qkv_b[i], split=(Dl, S_loc * Dl),
-                                             quantised=None if xq is None else (xq[0][0], xq[1][0]))
-                        # v needs no norm: its exchange runs on the RCCL stream underneath q's norm + RoPE, q's exchange
-                        # underneath k's; only k's is exposed (every exchange is enqueued on the communicator's stream,
-                        # the compute stream waits by event right before the attention launch)
-                        qk_kw = dict(heads=H // W, text_rows=Tt_loc if cos is not None else S_loc, eps=at.norm_q.eps,
-                                     k_scale=self.k_scale)
-                        if sh.p2p is not None:
-                            # P2P transport: q/k-norm + RoPE on the local rows of both, then ONE push kernel carries all
-                            # 3 x W column blocks to their places in the peers' q / k / v buffers
-                            # (device bound: this rank's rows give its partial maxima for ALL heads; the tables travel with
-                            # the q|k|v exchange and the attention takes the maximum over the ranks' tables for its heads)
-                            sb, st = self._attn_bound(i, H, slots=max(1, 64 // W))
-                            if (self.sp_overlap_v and st is None and xq is None and not self._quantised("qkv")
-                                    and S_loc >= self.SP_OVERLAP_V_MIN_ROWS):
-                                # (r6) v FIRST: v needs no norm -- its projection is a launch of its own, its column blocks travel
-                                # on the side stream while the q | k projection (with the norm in its epilogue) runs; only the
-                                # q | k exchange is exposed.  Same bits: every output element is summed over K in the same order
-                                ops.gemm(xn[0], self.qkv_w[i][2 * D:], qkvb[2 * W], bias=self.qkv_b[i][2 * D:], split=(Dl, S_loc * Dl))
-                                sh.push_v_heads(qkvb[2 * W:])
-                                if not (self.qkn_epilogue and ops.gemm_qkv_norm_rope(
-                                        xn[0], self.qkv_w[i][:2 * D], qkvb[0], self.qkv_b[i][:2 * D], (Dl, S_loc * Dl), at.norm_q.weight,
-                                        at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, cos, sin, qk_kw["text_rows"], eps=at.norm_q.eps,
-                                        k_scale=self.k_scale, tensors=2)):
-                                    ops.gemm(xn[0], self.qkv_w[i][:2 * D], qkvb[0], bias=self.qkv_b[i][:2 * D], split=(Dl, S_loc * Dl))
-                                    ops.qknorm_rope(qkvb[:W], qkvb[W:2 * W], at.norm_q.weight, at.norm_q.bias, at.norm_k.weight,
-                                                    at.norm_k.bias, cos, sin, heads=H // W, text_rows=qk_kw["text_rows"],
-                                                    eps=at.norm_q.eps, k_scale=self.k_scale)
-                                qh_, kh_, vh_ = sh.rows_to_heads_qk(qkvb[:2 * W])
-                                st_all = None
-                            else:
-                                self._qkv_norm_rope(i, at, xn[0], qkvb[0], (Dl, S_loc * Dl), None if xq is None else (xq[0][0], xq[1][0]),
-                                                    cos, sin, qk_kw["text_rows"], H // W, qkvb[:W], qkvb[W:2 * W], st)
-                                qh_, kh_, vh_, st_all = sh.rows_to_heads_qkv(qkvb, st)
-                            ops.self_attention(qh_[None], kh_[None], vh_[None], oh[None], heads=H // W, tag="joint", prescaled=True,
-                                               score_bound=sb, bound=None if st is None else (st_all, sh.rank * (H // W), self._ws["qk_flags"]))
-                            xo = sh.heads_to_rows(oh)              # (the symmetric receive buffer, already in [rows, heads] order)
-                            self._dit_linear("out", i, xo[None], at.to_out[0].weight, x, bias=at.to_out[0].bias, res=x,
-                                             gate0=mo[:, 5 * D:], gate1=mo[:, 2 * D:], gate_split=Tt_loc, gate_batch_stride=mbs)
-                            continue
-                        pending = [sh.rows_to_heads(qkvb[2 * W:], vh, async_op=True)]
-                        ops.qknorm_rope(qkvb[:W], None, at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias,
-                                        cos, sin, **qk_kw)
-                        pending.append(sh.rows_to_heads(qkvb[:W], qh, async_op=True))
-                        ops.qknorm_rope(None, qkvb[W:2 * W], at.norm_q.weight, at.norm_q.bias, at.norm_k.weight,
-                                        at.norm_k.bias, cos, sin, **qk_kw)
-                        pending.append(sh.rows_to_heads(qkvb[W:2 * W], kh, async_op=True))
-                        for h in pending:
-                            if h is not None:
-                                h.wait()            # the compute stream waits (no host synchronisation)
-                        ops.self_attention(qh[None], kh[None], vh[None], oh[None], heads=H // W, tag="joint", prescaled=True,
-                                           score_bound=self.score_bound[i])
-                        sh.heads_to_rows(oh, xn[0])
-                        self._dit_linear("out", i, xn, at.to_out[0].weight, x, bias=at.to_out[0].bias, res=x, gate0=mo[:, 5 * D:],
-                                 gate1=mo[:, 2 * D:], gate_split=Tt_loc, gate_batch_stride=mbs)
-                        continue
-                    # (rows of K from other ranks are not in this rank's statistics: the all-gather form keeps the worst case)
-                    sb, st = self._attn_bound(i, B * H) if not sh.active else (self.score_bound[i], None)
-                    self._qkv_norm_rope(i, at, xn, q, (D, B * S_loc * D), xq, cos, sin, Tt_loc if cos is not None else S_loc,
-                                        H, q, k, st)
-                    if sh.active:      # exchange A (fallback when heads % world != 0): all-gather K and V
-                        if sh.p2p is not None:
-                            sh.gather_rows_many([k[0], v[0]], [k_full[0], v_full[0]])       # one exchange, double-buffered
-                        else:
-                            sh.gather_rows(k[0], k_full[0])
-                            sh.gather_rows(v[0], v_full[0])
-                        oq = self._joint_attention(q, k_full, v_full, xn, heads=H, tag="joint", prescaled=True,
-                                                   score_bound=self.score_bound[i])
-                    else:
-                        oq = self._joint_attention(q, k, v, xn, heads=H, tag="joint", prescaled=True, score_bound=sb,
-                                                   bound=None if st is None else (st, 0, self._ws["qk_flags"]))
-                    self._dit_linear("out", i, xn, at.to_out[0].weight, x, bias=at.to_out[0].bias, res=x, gate0=mo[:, 5 * D:],
-                             gate1=mo[:, 2 * D:], gate_split=Tt_loc, gate_batch_stride=mbs, quantised=oq)
-                else:
-                    fq = None
-                    if self._ff_pair_fused():
-                        # the MLP pair is row-local: FF1 emits FF2's MX operand, the bf16 `ff` is neither written nor read
-                        fq = self._ff1_mx_quant(i, xn, ff.shape, blk.ff.net[0].proj.bias, xq)
-                    else:
-                        self._dit_linear("ff1", i, xn, blk.ff.net[0].proj.weight, ff, bias=blk.ff.net[0].proj.bias,
-                                         act="gelu_tanh", quantised=xq)
-                    self._dit_linear("ff2", i, ff, blk.ff.net[2].weight, x, bias=blk.ff.net[2].bias, res=x, gate0=mo[:, 5 * D:],
-                             gate1=mo[:, 2 * D:], gate_split=Tt_loc, gate_batch_stride=mbs, quantised=fq)
+            # qkv_blocks: column block t*W + j = tensor t (q,k,v), heads of rank j
+            c.heads = (buf("qkv_blocks", 3 * W, S_loc, Dl), buf("q_heads", S, Dl), buf("k_heads", S, Dl), buf("v_heads", S, Dl),
+                       buf("o_heads", S, Dl))
+            return self._attn_heads_rccl if sh.p2p is None else self._attn_heads_p2p
+        c.kv_full = (buf("k_full", 1, S, D), buf("v_full", 1, S, D))
+        return self._attn_allgather
+
+    def _adaln(self, c, i, half, nz):
+        """The AdaLN LayerNorm in front of block ``i``'s attention (``half`` 0) or MLP (1), into ``c.xn`` -> (the quantised
+        operand where the LayerNorm emits it itself, else None; the gated-residual keywords of the half's closing Linear)."""
+        D, x = self.D, c.x
+        mo = c.mods[:, (2 * i + half) * 6 * D:]
+        # chunk order: shift, scale, gate, enc_shift, enc_scale, enc_gate
+        ln_kw = dict(eps=nz.norm.eps, shift0=mo[:, 3 * D:], scale0=mo[:, 4 * D:], shift1=mo, scale1=mo[:, D:],
+                     split=c.Tt_loc, mod_batch_stride=c.mbs)
+        gated = dict(res=x, gate0=mo[:, 5 * D:], gate1=mo[:, 2 * D:], gate_split=c.Tt_loc, gate_batch_stride=c.mbs)
+        which = ("qkv", "ff1")[half]
+        if self._quantised(which) and self.fuse_ln_quant:
+            # the AdaLN output feeds exactly one Linear (q|k|v, or the MLP's first): emit it in e4m3 / MX directly
+            return self._layernorm_quant(which, x, c.xn.shape, nz.norm.weight, nz.norm.bias, **ln_kw), gated
+        ops.layernorm(x, c.xn, nz.norm.weight, nz.norm.bias, **ln_kw)
+        return None, gated
+
+    def _attn_local(self, c, i, at, xq, gated):
+        """Joint attention of block ``i``, unsharded: q|k|v + norm + RoPE, attention, gated to_out."""
+        H, D, xn = self.H, self.D, c.xn
+        q, k, v = c.qkv
+        sb, st = self._attn_bound(i, c.B * H)
+        self._qkv_norm_rope(i, at, xn, q, (D, c.B * c.S_loc * D), xq, c.cos, c.sin, c.text_rows, H, q, k, st)
+        oq = self._joint_attention(q, k, v, xn, heads=H, tag="joint", prescaled=True, score_bound=sb,
+                                   bound=None if st is None else (st, 0, self._ws["qk_flags"]))
+        self._dit_linear("out", i, xn, at.to_out[0].weight, c.x, bias=at.to_out[0].bias, quantised=oq, **gated)
+
+    def _attn_allgather(self, c, i, at, xq, gated):
+        """Joint attention of block ``i``, exchange A as an all-gather of K and V (the fallback when heads % world != 0).
+        (rows of K from other ranks are not in this rank's statistics: the all-gather form keeps the worst case)"""
+        sh, H, D, xn = c.sh, self.H, self.D, c.xn
+        q, k, v = c.qkv
+        k_full, v_full = c.kv_full
+        self._qkv_norm_rope(i, at, xn, q, (D, c.B * c.S_loc * D), xq, c.cos, c.sin, c.text_rows, H, q, k, None)
+        if sh.p2p is not None:
+            sh.gather_rows_many([k[0], v[0]], [k_full[0], v_full[0]])       # one exchange, double-buffered
+        else:
+            sh.gather_rows(k[0], k_full[0])
+            sh.gather_rows(v[0], v_full[0])
+        oq = self._joint_attention(q, k_full, v_full, xn, heads=H, tag="joint", prescaled=True, score_bound=self.score_bound[i])
+        self._dit_linear("out", i, xn, at.to_out[0].weight, c.x, bias=at.to_out[0].bias, quantised=oq, **gated)
+
+    def _attn_heads_rccl(self, c, i, at, xq, gated):
+        """Joint attention of block ``i``, exchange A head-parallel over RCCL: the projection writes per-destination column
+        blocks, q/k-norm + RoPE run on the local rows, then rows are traded for heads (every element moves once)."""
+        sh, W, H, xn = c.sh, c.sh.world, self.H, c.xn
+        Dl = self.D // W
+        qkvb, qh, kh, vh, oh = c.heads
+        self._dit_linear("qkv", i, xn[0], self.qkv_w[i], qkvb[0], bias=self.qkv_b[i], split=(Dl, c.S_loc * Dl),
+                         quantised=None if xq is None else (xq[0][0], xq[1][0]))
+        # v needs no norm: its exchange runs on the RCCL stream underneath q's norm + RoPE, q's exchange
+        # underneath k's; only k's is exposed (every exchange is enqueued on the communicator's stream,
+        # the compute stream waits by event right before the attention launch)
+        qk = (at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, c.cos, c.sin)
+        qk_kw = dict(heads=H // W, text_rows=c.text_rows, eps=at.norm_q.eps, k_scale=self.k_scale)
+        pending = [sh.rows_to_heads(qkvb[2 * W:], vh, async_op=True)]
+        ops.qknorm_rope(qkvb[:W], None, *qk, **qk_kw)
+        pending.append(sh.rows_to_heads(qkvb[:W], qh, async_op=True))
+        ops.qknorm_rope(None, qkvb[W:2 * W], *qk, **qk_kw)
+        pending.append(sh.rows_to_heads(qkvb[W:2 * W], kh, async_op=True))
+        for h in pending:
+            if h is not None:
+                h.wait()            # the compute stream waits (no host synchronisation)
+        ops.self_attention(qh[None], kh[None], vh[None], oh[None], heads=H // W, tag="joint", prescaled=True,
+                           score_bound=self.score_bound[i])
+        sh.heads_to_rows(oh, xn[0])
+        self._dit_linear("out", i, xn, at.to_out[0].weight, c.x, bias=at.to_out[0].bias, **gated)
+
+    def _attn_heads_p2p(self, c, i, at, xq, gated):
+        """Joint attention of block ``i``, exchange A head-parallel over P2P: q/k-norm + RoPE on the local rows of both, then
+        ONE push kernel carries all 3 x W column blocks to their places in the peers' q / k / v buffers -- or, v first, two."""
+        sh, W, H, D, S_loc, xn = c.sh, c.sh.world, self.H, self.D, c.S_loc, c.xn[0]
+        Dl = D // W
+        qkvb, oh = c.heads[0], c.heads[4]
+        split, text_rows = (Dl, S_loc * Dl), c.text_rows
+        # (device bound: this rank's rows give its partial maxima for ALL heads; the tables travel with
+        # the q|k|v exchange and the attention takes the maximum over the ranks' tables for its heads)
+        sb, st = self._attn_bound(i, H, slots=max(1, 64 // W))
+        if self.sp_overlap_v and st is None and xq is None and not self._quantised("qkv") and S_loc >= self.SP_OVERLAP_V_MIN_ROWS:
+            # (r6) v FIRST: v needs no norm -- its projection is a launch of its own, its column blocks travel
+            # on the side stream while the q | k projection (with the norm in its epilogue) runs; only the
+            # q | k exchange is exposed.  Same bits: every output element is summed over K in the same order
+            qk = (at.norm_q.weight, at.norm_q.bias, at.norm_k.weight, at.norm_k.bias, c.cos, c.sin)
+            ek = dict(eps=at.norm_q.eps, k_scale=self.k_scale)
+            ops.gemm(xn, self.qkv_w[i][2 * D:], qkvb[2 * W], bias=self.qkv_b[i][2 * D:], split=split)
+            sh.push_v_heads(qkvb[2 * W:])
+            if not (self.qkn_epilogue and ops.gemm_qkv_norm_rope(xn, self.qkv_w[i][:2 * D], qkvb[0], self.qkv_b[i][:2 * D], split,
+                                                                 *qk, text_rows, tensors=2, **ek)):
+                ops.gemm(xn, self.qkv_w[i][:2 * D], qkvb[0], bias=self.qkv_b[i][:2 * D], split=split)
+                ops.qknorm_rope(qkvb[:W], qkvb[W:2 * W], *qk, heads=H // W, text_rows=text_rows, **ek)
+            qh_, kh_, vh_ = sh.rows_to_heads_qk(qkvb[:2 * W])
+            st_all = None
+        else:
+            self._qkv_norm_rope(i, at, xn, qkvb[0], split, None if xq is None else (xq[0][0], xq[1][0]), c.cos, c.sin, text_rows,
+                                H // W, qkvb[:W], qkvb[W:2 * W], st)
+            qh_, kh_, vh_, st_all = sh.rows_to_heads_qkv(qkvb, st)
+        ops.self_attention(qh_[None], kh_[None], vh_[None], oh[None], heads=H // W, tag="joint", prescaled=True,
+                           score_bound=sb, bound=None if st is None else (st_all, sh.rank * (H // W), self._ws["qk_flags"]))
+        xo = sh.heads_to_rows(oh)              # (the symmetric receive buffer, already in [rows, heads] order)
+        self._dit_linear("out", i, xo[None], at.to_out[0].weight, c.x, bias=at.to_out[0].bias, **gated)
+
+    def _mlp_pair(self, c, i, ff, xq, gated):
+        """The MLP pair of block ``i`` (models/transformer.py:255-260): ff.net.0 + GELU(tanh), gated ff.net.2."""
+        fq = None
+        if self._ff_pair_fused():
+            # the MLP pair is row-local: FF1 emits FF2's MX operand, the bf16 `ff` is neither written nor read
+            fq = self._ff1_mx_quant(i, c.xn, c.ff.shape, ff.net[0].proj.bias, xq)
+        else:
+            self._dit_linear("ff1", i, c.xn, ff.net[0].proj.weight, c.ff, bias=ff.net[0].proj.bias, act="gelu_tanh", quantised=xq)
+        self._dit_linear("ff2", i, c.ff, ff.net[2].weight, c.x, bias=ff.net[2].bias, quantised=fq, **gated)
+
+    def _kv_mix(self, c, q, k, v, af, wsum, kd, rows, sample, z, mx):
+        """The ``mix(z, mx)`` of ``_cross_out`` for one cross-attention layer, face (``af``, ``wsum`` None) or audio: ONE launch
+        for the batch where ``batch_launches`` asks and the library takes it, else one per sample -- ``sample(b, rb, zb, mxb)``
+        where the caller brings its own launcher (the sharded audio layer), else ops.attn_kv_mix on sample ``b``'s views.
+        ``kd`` is the layer's kv-mix descriptor, ``rows`` its ``Sq`` and ``q_strides`` (z has q's layout).  False as soon as a
+        launch declines the MX epilogue."""
+        r = c.r_logits
+        if self.batch_launches and c.B >= 2 and sample is None:          # one launch for the batch; declined: the loop below
+            to = dict(z_strides=rows["q_strides"]) if mx is None else dict(mx_out=(*mx, self.mx_fmt))
+            if ops.attn_kv_mix_batch(q, k, v, r, af, z, wsum, **kd, **rows, **to) is not False:
+                return None
+        for b in range(c.B):
+            rb = r[b if r.shape[0] > 1 else 0]
+            zb, mxb = None if z is None else z[b], None if mx is None else (mx[0][b], mx[1][b])
+            if sample is not None:
+                if sample(b, rb, zb, mxb) is False:
+                    return False
+                continue
+            to = dict(z_strides=rows["q_strides"]) if mx is None else dict(mx_out=(*mxb, self.mx_fmt))
+            if ops.attn_kv_mix(q[b], k[b], v[b], rb, None if af is None else af[b], zb, None if wsum is None else wsum[b],
+                               **kd, **rows, **to) is False:
+                return False
+
+    def _audio_mix_shard(self, c, qa, ka, va, wsum, kd, b, rb, zb, mxb):
+        """Sample ``b``'s audio kv-mix on a rank of the sharded step (``_kv_mix``'s per-sample launcher).  Shard boundaries cut
+        frames: the (partial) frames of this rank are the segments of one launch per run of ops.MIX_MAX_SEGMENTS, or -- switch
+        off, or declined for a run -- one launch per (partial) frame.  The MX pair's rows are the rank's own, like z's: a
+        segment writes at a byte offset of ``start`` rows."""
+        D, af, fmt = self.D, c.af[b], self.mx_fmt
+        kf = (kd["k_strides"][0], 0, D)
+        kd1 = dict(kd, n_grp=1, k_strides=kf, v_strides=kf)
+        segs = c.sh.frame_segments(c.per_frame)
+        for run in (segs[s0:s0 + ops.MIX_MAX_SEGMENTS] for s0 in range(0, len(segs), ops.MIX_MAX_SEGMENTS)):
+            to = dict(z_row=D) if mxb is None else dict(mx_out=(*mxb, fmt))
+            if self.sp_segment_mix and ops.attn_kv_mix_segments(qa[b], ka[b], va[b], rb, af, zb, wsum[b], segments=run, Sq=c.N_loc,
+                                                                q_row=D, **kd, **to) is not False:
+                continue
+            for f, start, length in run:
+                to = dict(z_strides=(0, D)) if mxb is None else dict(mx_out=(mxb[0][start:], mxb[1][start:], fmt))
+                if ops.attn_kv_mix(qa[b, start:], ka[b, :, f], va[b, :, f], rb[start:start + length], af,
+                                   None if zb is None else zb[start:], wsum[b, start:], Sq=length, q_strides=(0, D), **kd1,
+                                   **to) is False:
+                    return False
+
+    def _perceiver_attention(self, c, qp, kv_l, pout):
+        """The perceiver cross-attention of one face layer on its unfused path: every identity's output into ``pout``."""
+        n_id, N_loc, inner_p, ntok = c.n_id, c.N_loc, qp.shape[-1], kv_l.shape[2]
+        hd_p = inner_p // 16
+        ops.attention(qp, kv_l, kv_l[..., inner_p:], pout, head_dim=hd_p, heads=16, nb1=c.B, nb2=n_id, Sq=N_loc,
+                      Skv=ntok, q_strides=(N_loc * inner_p, 0, inner_p),
+                      k_strides=(n_id * ntok * 2 * inner_p, ntok * 2 * inner_p, 2 * inner_p),
+                      v_strides=(n_id * ntok * 2 * inner_p, ntok * 2 * inner_p, 2 * inner_p),
+                      o_strides=(n_id * N_loc * inner_p, N_loc * inner_p, inner_p), scale=hd_p ** -0.5)
+
+    def _face_routing(self, c, i, ca):
+        """P1 + R1..R4 + G1: face routing of layer ``ca``, behind block ``i`` (models/transformer.py:737-833).  Leaves the
+        routing logits in ``c.r_logits`` for the audio layers up to the next face layer."""
+        m, buf, B, N_loc, n_id, xv, taps = self.m, self._buf, c.B, c.N_loc, c.n_id, c.xv, c.taps
+        ops.on_stream.need(c.face_marks.pop(ca, None))     # the side stream has produced this layer's face K/V and keys
+        pc = m.perceiver_cross_attention[ca]
+        inner_p = pc.to_q.weight.shape[0]
+        lat = buf("lat", B, N_loc, self.D)
+        qp = self._ln_linear("pq", ca, xv, lat, pc.norm2, pc.to_q.weight, buf("qp", B, N_loc, inner_p))
+        kv_l = c.face_kv[ca]
+        fuse_face = self.fused_attn_mix and taps is None
+        pout = None if fuse_face else buf("pout", B, n_id, N_loc, inner_p)
+        # (fused: the attention runs behind the router, with the mix in its epilogue -- below)
+        attention = (lambda: None) if fuse_face else functools.partial(self._perceiver_attention, c, qp, kv_l, pout)
+        if c.forced is None:
+            # (sharded: the perceiver attention -- independent of the router -- is enqueued while the router's first
+            # repartition exchange is in flight on the RCCL stream)
+            c.r_logits = self._router(qp, c.router_k[ca], ca, B, c.T, c.per_frame, n_id, c.sh, taps, attention)
+        else:
+            attention()
+            c.r_logits = c.forced
+        if fuse_face:
+            # Perceiver attention with the masked combine in its epilogue: z = sum_id r[n, id] * attention_id
+            hd_p, ntok = inner_p // 16, kv_l.shape[2]
+            kvs_p = (ntok * 2 * inner_p, 0, 2 * inner_p)
+            kd = dict(head_dim=hd_p, heads=16, n_id=n_id, n_grp=1, Skv=ntok, k_strides=kvs_p, v_strides=kvs_p, scale=hd_p ** -0.5)
+            mix = functools.partial(self._kv_mix, c, qp, kv_l, kv_l[..., inner_p:], None, None, kd,
+                                    dict(Sq=N_loc, q_strides=(0, inner_p)), None)
+            self._cross_out("po", ca, "zmix_p", (B, N_loc, inner_p), mix, pc.to_out.weight, xv, res=xv, alpha=m.local_face_scale)
+        elif self.mix_before_projection:
+            # to_out is linear and bias-free: route first, project once (half the GEMM, no feat round trip)
+            z = ops.routed_mix(pout, c.r_logits, None, "face", buf("zmix_p", B, N_loc, inner_p))
+            self._dit_linear("po", ca, z, pc.to_out.weight, xv, res=xv, alpha=m.local_face_scale)
+        else:
+            feat = buf("feat", B, n_id, N_loc, self.D)
+            self._dit_linear("po", ca, pout.view(B * n_id, N_loc, inner_p), pc.to_out.weight, feat.view(B * n_id, N_loc, self.D))
             if taps is not None:
-                taps[f"block{i}"] = x.clone()
+                taps[f"id_feat{ca}"] = feat[0].clone()
+            ops.masked_combine(xv, feat, c.r_logits, None, "face", alpha=m.local_face_scale)
+        if taps is not None:
+            taps[f"face{i}"] = xv.clone()
 
-            # ---- P1 + R1..R4 + G1: face routing (models/transformer.py:737-833)
-            if use_face and i % m.cross_attn_interval == 0:
-                ca = i // m.cross_attn_interval
-                ops.on_stream.need(face_marks.pop(ca, None))     # the side stream has produced this layer's face K/V and keys
-                pc = m.perceiver_cross_attention[ca]
-                inner_p = pc.to_q.weight.shape[0]
-                hd_p = inner_p // 16
-                lat = buf("lat", B, N_loc, D)
-                qp = self._ln_linear("pq", ca, xv, lat, pc.norm2, pc.to_q.weight, buf("qp", B, N_loc, inner_p))
-                kv_l = face_kv[ca]
-                ntok = kv_l.shape[2]
-                fuse_face = self.fused_attn_mix and taps is None
-                pout = None if fuse_face else buf("pout", B, n_id, N_loc, inner_p)
+    def _audio_injection(self, c, i, ai):
+        """A1 + G2: audio injection of layer ``ai``, behind block ``i`` (models/transformer.py:858-936), routed by the logits
+        of the last face layer."""
+        buf, sh, B, N_loc, n_id, T, per_frame, xv = self._buf, c.sh, c.B, c.N_loc, c.n_id, c.T, c.per_frame, c.xv
+        D, H = self.D, self.H
+        ops.on_stream.need(c.audio_mark)
+        c.audio_mark = None
+        al = self.m.audio_model.layers[ai]
+        at = al["attn"]
+        an = buf("lat", B, N_loc, D)
+        qa = self._ln_linear("aq", ai, xv, an, al["norm_q"], at.to_q.weight, buf("qa", B, N_loc, D), bias=at.to_q.bias)
+        ka, va = c.audio_k[ai], c.audio_v[ai]
+        ntok = ka.shape[3]
+        kvs = (T * ntok * D, ntok * D, D)
+        if self.fused_attn_mix and c.taps is None:
+            # audio cross-attention with the masked combine in its epilogue (per sample: af differs per sample)
+            wsum = self._buf("wsum", B, N_loc, dtype=torch.float32)      # the mix's weight sums: to_out's bias scale
+            kd = dict(head_dim=64, heads=H, n_id=n_id, n_grp=T, Skv=ntok, k_strides=kvs, v_strides=kvs, scale=64 ** -0.5)
+            shard = functools.partial(self._audio_mix_shard, c, qa, ka, va, wsum, kd) if sh.active else None
+            mix = functools.partial(self._kv_mix, c, qa, ka, va, c.af, wsum, kd,
+                                    dict(Sq=per_frame, q_strides=(per_frame * D, D)), shard)
+            self._cross_out("ao", ai, "zmix_a", (B, N_loc, D), mix, at.to_out[0].weight, xv, bias=at.to_out[0].bias, res=xv,
+                            bias_rowscale=wsum)
+            return
+        ao = buf("ao", B, n_id, N_loc, D)
+        for b in range(B):      # (id, frame) batch of one sample; q rows shared by both ids
+            if not sh.active:
+                ops.attention(qa[b], ka[b], va[b], ao[b], head_dim=64, heads=H, nb1=n_id, nb2=T, Sq=per_frame,
+                              Skv=ntok, q_strides=(0, per_frame * D, D), k_strides=kvs, v_strides=kvs,
+                              o_strides=(N_loc * D, per_frame * D, D), scale=64 ** -0.5)
+            else:               # shard boundaries cut frames: one launch per (partial) frame of this rank
+                for f, start, length in sh.frame_segments(per_frame):
+                    ops.attention(qa[b, start:], ka[b, :, f], va[b, :, f], ao[b, :, start:], head_dim=64,
+                                  heads=H, nb1=n_id, nb2=1, Sq=length, Skv=ntok, q_strides=(0, 0, D),
+                                  k_strides=kvs, v_strides=kvs, o_strides=(N_loc * D, 0, D), scale=64 ** -0.5)
+        if self.mix_before_projection:
+            wsum = self._buf("wsum", B, N_loc, dtype=torch.float32)      # the mix's weight sums: to_out's bias scale
+            z = ops.routed_mix(ao, c.r_logits, c.af, "audio", buf("zmix_a", B, N_loc, D), wsum)
+            self._dit_linear("ao", ai, z, at.to_out[0].weight, xv, bias=at.to_out[0].bias, res=xv, bias_rowscale=wsum)
+        else:
+            feat = buf("feat", B, n_id, N_loc, D)
+            self._dit_linear("ao", ai, ao.view(B * n_id, N_loc, D), at.to_out[0].weight, feat.view(B * n_id, N_loc, D),
+                             bias=at.to_out[0].bias)
+            ops.masked_combine(xv, feat, c.r_logits, c.af, "audio")
+        if c.taps is not None:
+            c.taps[f"audio{i}"] = xv.clone()
 
-                def perceiver_attention():
-                    if fuse_face:
-                        return                       # runs behind the router, with the mix in its epilogue (below)
-                    ops.attention(qp, kv_l, kv_l[..., inner_p:], pout, head_dim=hd_p, heads=16, nb1=B, nb2=n_id, Sq=N_loc,
-                                  Skv=ntok, q_strides=(N_loc * inner_p, 0, inner_p),
-                                  k_strides=(n_id * ntok * 2 * inner_p, ntok * 2 * inner_p, 2 * inner_p),
-                                  v_strides=(n_id * ntok * 2 * inner_p, ntok * 2 * inner_p, 2 * inner_p),
-                                  o_strides=(n_id * N_loc * inner_p, N_loc * inner_p, inner_p), scale=hd_p ** -0.5)
-                if forced is None:
-                    # (sharded: the perceiver attention -- independent of the router -- is enqueued while the router's first
-                    # repartition exchange is in flight on the RCCL stream)
-                    r_logits = self._router(qp, router_k[ca], ca, B, T, per_frame, n_id, sh, taps, perceiver_attention)
-                else:
-                    perceiver_attention()
-                    r_logits = forced
-                if fuse_face:
-                    # Perceiver attention with the masked combine in its epilogue: z = sum_id r[n, id] * attention_id
-                    kvs_p = (ntok * 2 * inner_p, 0, 2 * inner_p)
-
-                    def face_mix(z, mx):
-                        if self.batch_launches and B >= 2:          # one launch for the batch; declined: the loop below
-                            to = dict(z_strides=(0, inner_p)) if mx is None else dict(mx_out=(*mx, self.mx_fmt))
-                            if ops.attn_kv_mix_batch(qp, kv_l, kv_l[..., inner_p:], r_logits, None, z, head_dim=hd_p, heads=16,
-                                                     n_id=n_id, n_grp=1, Sq=N_loc, Skv=ntok, q_strides=(0, inner_p),
-                                                     k_strides=kvs_p, v_strides=kvs_p, scale=hd_p ** -0.5, **to) is not False:
-                                return None
-                        for b in range(B):
-                            rb = r_logits[b if r_logits.shape[0] > 1 else 0]
-                            to = dict(z_strides=(0, inner_p)) if mx is None else dict(mx_out=(mx[0][b], mx[1][b], self.mx_fmt))
-                            if ops.attn_kv_mix(qp[b], kv_l[b], kv_l[b][..., inner_p:], rb, None, None if z is None else z[b],
-                                               head_dim=hd_p, heads=16, n_id=n_id, n_grp=1, Sq=N_loc, Skv=ntok,
-                                               q_strides=(0, inner_p), k_strides=kvs_p, v_strides=kvs_p, scale=hd_p ** -0.5,
-                                               **to) is False:
-                                return False
-                    self._cross_out("po", ca, "zmix_p", (B, N_loc, inner_p), face_mix, pc.to_out.weight, xv, res=xv,
-                                    alpha=m.local_face_scale)
-                elif self.mix_before_projection:
-                    # to_out is linear and bias-free: route first, project once (half the GEMM, no feat round trip)
-                    z = ops.routed_mix(pout, r_logits, None, "face", buf("zmix_p", B, N_loc, inner_p))
-                    self._dit_linear("po", ca, z, pc.to_out.weight, xv, res=xv, alpha=m.local_face_scale)
-                else:
-                    feat = buf("feat", B, n_id, N_loc, D)
-                    self._dit_linear("po", ca, pout.view(B * n_id, N_loc, inner_p), pc.to_out.weight, feat.view(B * n_id, N_loc, D))
-                    if taps is not None:
-                        taps[f"id_feat{ca}"] = feat[0].clone()
-                    ops.masked_combine(xv, feat, r_logits, None, "face", alpha=m.local_face_scale)
-                if taps is not None:
-                    taps[f"face{i}"] = xv.clone()
-
-            # ---- A1 + G2: audio injection (models/transformer.py:858-936)
-            if use_audio and i % m.audio_attn_interval == 0:
-                ops.on_stream.need(audio_mark[0])
-                audio_mark[0] = None
-                al = m.audio_model.layers[i // m.audio_attn_interval]
-                at = al["attn"]
-                an = buf("lat", B, N_loc, D)
-                qa = self._ln_linear("aq", i // m.audio_attn_interval, xv, an, al["norm_q"], at.to_q.weight,
-                                     buf("qa", B, N_loc, D), bias=at.to_q.bias)
-                ka, va = audio_k[i // m.audio_attn_interval], audio_v[i // m.audio_attn_interval]
-                ntok = ka.shape[3]
-                fuse_audio = self.fused_attn_mix and taps is None
-                kvs = (T * ntok * D, ntok * D, D)
-                if fuse_audio:
-                    # audio cross-attention with the masked combine in its epilogue (per sample: af differs per sample)
-                    wsum = self._ws.get("wsum")
-                    if wsum is None or wsum.numel() != B * N_loc:
-                        wsum = self._ws["wsum"] = torch.empty(B, N_loc, dtype=torch.float32, device=self.dev)
-                    ai = i // m.audio_attn_interval
-
-                    def audio_mix(z, mx):
-                        # the MX pair's rows are the rank's own, like z's: a segment writes at a byte offset of `start` rows
-                        if self.batch_launches and B >= 2 and not sh.active:      # one launch for the batch; declined: the loop
-                            to = dict(z_strides=(per_frame * D, D)) if mx is None else dict(mx_out=(*mx, self.mx_fmt))
-                            if ops.attn_kv_mix_batch(qa, ka, va, r_logits, af, z, wsum, head_dim=64, heads=H, n_id=n_id, n_grp=T,
-                                                     Sq=per_frame, Skv=ntok, q_strides=(per_frame * D, D), k_strides=kvs,
-                                                     v_strides=kvs, scale=64 ** -0.5, **to) is not False:
-                                return None
-                        for b in range(B):
-                            rb = r_logits[b if r_logits.shape[0] > 1 else 0]
-                            if not sh.active:
-                                to = dict(z_strides=(per_frame * D, D)) if mx is None else dict(mx_out=(mx[0][b], mx[1][b], self.mx_fmt))
-                                if ops.attn_kv_mix(qa[b], ka[b], va[b], rb, af[b], None if z is None else z[b], wsum[b],
-                                                   head_dim=64, heads=H, n_id=n_id, n_grp=T, Sq=per_frame, Skv=ntok,
-                                                   q_strides=(per_frame * D, D), k_strides=kvs, v_strides=kvs, scale=64 ** -0.5,
-                                                   **to) is False:
-                                    return False
-                                continue
-                            # shard boundaries cut frames: the (partial) frames of this rank are the segments of one launch per
-                            # run of ops.MIX_MAX_SEGMENTS, or -- switch off, or declined for a run -- one launch per (partial) frame
-                            segs = sh.frame_segments(per_frame)
-                            for run in (segs[s0:s0 + ops.MIX_MAX_SEGMENTS] for s0 in range(0, len(segs), ops.MIX_MAX_SEGMENTS)):
-                                to = dict(z_row=D) if mx is None else dict(mx_out=(mx[0][b], mx[1][b], self.mx_fmt))
-                                if self.sp_segment_mix and ops.attn_kv_mix_segments(
-                                        qa[b], ka[b], va[b], rb, af[b], None if z is None else z[b], wsum[b], segments=run,
-                                        head_dim=64, heads=H, n_id=n_id, n_grp=T, Sq=N_loc, Skv=ntok, q_row=D, k_strides=kvs,
-                                        v_strides=kvs, scale=64 ** -0.5, **to) is not False:
-                                    continue
-                                for f, start, length in run:
-                                    to = dict(z_strides=(0, D)) if mx is None else \
-                                        dict(mx_out=(mx[0][b, start:], mx[1][b, start:], self.mx_fmt))
-                                    if ops.attn_kv_mix(qa[b, start:], ka[b, :, f], va[b, :, f], rb[start:start + length], af[b],
-                                                       None if z is None else z[b, start:], wsum[b, start:], head_dim=64, heads=H,
-                                                       n_id=n_id, n_grp=1, Sq=length, Skv=ntok, q_strides=(0, D),
-                                                       k_strides=(kvs[0], 0, D), v_strides=(kvs[0], 0, D), scale=64 ** -0.5,
-                                                       **to) is False:
-                                        return False
-                    self._cross_out("ao", ai, "zmix_a", (B, N_loc, D), audio_mix, at.to_out[0].weight, xv,
-                                    bias=at.to_out[0].bias, res=xv, bias_rowscale=wsum)
-                    continue
-                ao = buf("ao", B, n_id, N_loc, D)
-                for b in range(B):      # (id, frame) batch of one sample; q rows shared by both ids
-                    if not sh.active:
-                        ops.attention(qa[b], ka[b], va[b], ao[b], head_dim=64, heads=H, nb1=n_id, nb2=T, Sq=per_frame,
-                                      Skv=ntok, q_strides=(0, per_frame * D, D), k_strides=kvs, v_strides=kvs,
-                                      o_strides=(N_loc * D, per_frame * D, D), scale=64 ** -0.5)
-                    else:               # shard boundaries cut frames: one launch per (partial) frame of this rank
-                        for f, start, length in sh.frame_segments(per_frame):
-                            ops.attention(qa[b, start:], ka[b, :, f], va[b, :, f], ao[b, :, start:], head_dim=64,
-                                          heads=H, nb1=n_id, nb2=1, Sq=length, Skv=ntok, q_strides=(0, 0, D),
-                                          k_strides=kvs, v_strides=kvs, o_strides=(N_loc * D, 0, D), scale=64 ** -0.5)
-                if self.mix_before_projection:
-                    wsum = self._ws.get("wsum")
-                    if wsum is None or wsum.numel() != B * N_loc:
-                        wsum = self._ws["wsum"] = torch.empty(B, N_loc, dtype=torch.float32, device=self.dev)
-                    z = ops.routed_mix(ao, r_logits, af, "audio", buf("zmix_a", B, N_loc, D), wsum)
-                    self._dit_linear("ao", i // m.audio_attn_interval, z, at.to_out[0].weight, xv, bias=at.to_out[0].bias, res=xv,
-                                     bias_rowscale=wsum)
-                else:
-                    feat = buf("feat", B, n_id, N_loc, D)
-                    self._dit_linear("ao", i // m.audio_attn_interval, ao.view(B * n_id, N_loc, D), at.to_out[0].weight,
-                                     feat.view(B * n_id, N_loc, D), bias=at.to_out[0].bias)
-                    ops.masked_combine(xv, feat, r_logits, af, "audio")
-                if taps is not None:
-                    taps[f"audio{i}"] = xv.clone()
-
-        if inv_side is not None:
-            inv_side.join()                  # (whatever of the conditioning no layer waited for: the step ends behind all of it)
-        # ---- F1: final norm, AdaLN head, projection, unpatchify (models/transformer.py:938-957)
+    def _head(self, c):
+        """F1: final norm, AdaLN head, projection, gather and verify, unpatchify (models/transformer.py:938-957)."""
+        m, buf, sh, B, N_loc, D, mods = self.m, self._buf, c.sh, c.B, c.N_loc, self.D, c.mods
+        if c.side is not None:
+            c.side.join()                    # (whatever of the conditioning no layer waited for: the step ends behind all of it)
         xf = buf("lat", B, N_loc, D)
-        ops.layernorm(xv, xf, m.norm_final.weight, m.norm_final.bias, eps=m.norm_final.eps)
+        ops.layernorm(c.xv, xf, m.norm_final.weight, m.norm_final.bias, eps=m.norm_final.eps)
         mo = mods[:, 2 * self.L * 6 * D:]                      # AdaLayerNorm chunk_dim=1: (shift, scale)
         xo = buf("qa", B, N_loc, D)
         ops.layernorm(xf, xo, m.norm_out.norm.weight, m.norm_out.norm.bias, eps=m.norm_out.norm.eps, shift0=mo,
-                      scale0=mo[:, D:], shift1=mo, scale1=mo[:, D:], split=0, mod_batch_stride=mbs)
+                      scale0=mo[:, D:], shift1=mo, scale1=mo[:, D:], split=0, mod_batch_stride=c.mbs)
         co = m.proj_out.weight.shape[0]
         y = ops.gemm(xo, m.proj_out.weight, buf("y", B, N_loc, co), bias=m.proj_out.bias)
         if sh.active:                                        # every rank returns the full latent prediction
-            y = sh.gather_video_rows(y, out=buf("y_full", B, N, co), in_place=True)
+            y = sh.gather_video_rows(y, out=buf("y_full", B, c.N, co), in_place=True)
             if self.verify_exchanges or (sh.p2p is not None and sh.p2p.verify):        # (verify mode implies the canary)
                 sh.verify_gathered(y)         # every rank holds the same gathered prediction -- or a receive buffer went stale
-        out = torch.empty(B, T, co // 4, Hh, Ww, dtype=torch.bfloat16, device=self.dev)
+        out = torch.empty(B, c.T, co // 4, c.Hh, c.Ww, dtype=torch.bfloat16, device=self.dev)
         ops.unpatchify(y, out)
         if sh.p2p is not None:
             sh.p2p.poison(out)             # NaN instead of numbers if any wait of this group ever gave up (sticky)
@@ -1202,10 +1250,6 @@ class DenoiseEngine:
     # row ranges in which a chain beats its two launches (profiles/r6_a_router_chain_probe.json, same box, us: MLP 50.5 -> 39.0 at
     # 17550 rows, 37.8 -> 28.9 at 8788, 69.2 -> 69.8 at 35100, 23.8 -> 26.8 at 4394; multi-ID 64.3 -> 60.2, 47.1 -> 43.2, 93.4 ->
     # 109, 28.6 -> 41.4; temporal level or slower everywhere)
-    # below this many rows per rank the two smaller projection launches cost more than the hidden link time buys (2222 rows of
-    # an 8-rank step: 108 + 216 tiles of 256 x 256 on 256 CUs instead of 324)
-    SP_OVERLAP_V_MIN_ROWS = 4096
-
     ROUTER_CHAIN_ROWS = {"mlp": (6000, 24000), "multi_id_attn": (6000, 24000), "temporal_attn": (1, 0)}
 
     def _chain_ok(self, rows, kind):
