@@ -128,6 +128,11 @@ class StepPlan(_c.Structure):
     _fields_ = [("kernel", _i32), ("grid", _i32), ("rounds", _i32), ("reserved", _i32), ("items", _i64), ("items_per_round", _i64)]
 
 
+class StepCachePlan(_c.Structure):
+    """bya_step_cache_plan_info: the grid the probe, the capture and the apply share, and the probe's partials."""
+    _fields_ = [("grid", _i32), ("vec", _i32), ("wg_pass_elems", _i32), ("passes", _i32), ("partials_bytes", _i64)]
+
+
 class SchedCoef(_c.Structure):
     _fields_ = [("guidance", _f32), ("sqrt_alpha", _f32), ("sqrt_beta", _f32), ("k_sample", _f32),
                 ("k_denoised", _f32), ("k_noise", _f32), ("k_cur", _f32), ("k_old", _f32)]
@@ -233,6 +238,10 @@ SIGNATURES = {
     "bya_unpatchify": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "bya_act_add": [_vp, _vp, _vp, _i64, _i32, _vp],
     "bya_act_add_plan": [_vp, _vp, _vp, _i64, _i32, _c.POINTER(StepPlan)],
+    "bya_step_cache_probe": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "bya_step_cache_probe_plan": [_vp, _vp, _vp, _vp, _i64, _c.POINTER(StepCachePlan)],
+    "bya_step_cache_capture": [_vp, _vp, _vp, _i64, _vp],
+    "bya_step_cache_apply": [_vp, _vp, _i64, _vp],
     "bya_rowgemm512": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp],
     "bya_rowgemm512_plan": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c.POINTER(RowGemmPlan)],
     "bya_router_group_attn_plan": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64,

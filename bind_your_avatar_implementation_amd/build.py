@@ -11,14 +11,14 @@ import sys
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libbya_hip.so")
-SOURCES = ["gemm.hip", "gemm_v4.hip", "gemm_v5.hip", "gemm_v6.hip", "gemm_fp8.hip", "gemm_fp8_v4.hip", "gemm_fp8_v4_qkn.hip", "gemm_fp8_v4_qkn_stats.hip", "gemm_mx.hip", "gemm_mx_v4.hip", "attn.hip", "attn_mix_mx.hip", "attn_mix_seg.hip", "attn_mix_batch.hip", "attn_w4.hip", "norm.hip", "misc.hip", "router.hip", "rowgemm.hip", "rowchain.hip", "comm.hip", "vae.hip", "calib.hip"]
+SOURCES = ["gemm.hip", "gemm_v4.hip", "gemm_v5.hip", "gemm_v6.hip", "gemm_fp8.hip", "gemm_fp8_v4.hip", "gemm_fp8_v4_qkn.hip", "gemm_fp8_v4_qkn_stats.hip", "gemm_mx.hip", "gemm_mx_v4.hip", "attn.hip", "attn_mix_mx.hip", "attn_mix_seg.hip", "attn_mix_batch.hip", "attn_w4.hip", "norm.hip", "misc.hip", "router.hip", "rowgemm.hip", "rowchain.hip", "comm.hip", "vae.hip", "calib.hip", "step_cache.hip"]
 # VALU-only kernels are built WITHOUT the SLP vectoriser, i.e. without packed-fp32 (v_pk_mul/fma/mov_f32) instructions:
 # with them the q/k-norm + RoPE kernel returned wrong values in lanes 48..63 of some waves whenever ANOTHER PROCESS kept
 # MFMA-heavy workgroups resident on the same CUs (19-20 of 20 runs; 0 of 20 for the same source built with
 # -fno-slp-vectorize; tools/timeslice/repro.py, profiles/history/r2_timeslice_repro_run*.json).  These
 # kernels are HBM-bound, the packed forms bought nothing.
 NO_SLP_SOURCES = {"norm.hip", "misc.hip", "router.hip", "gemm_fp8.hip", "gemm_mx.hip", "vae.hip", "rowgemm.hip", "rowchain.hip",
-                  "attn_mix_mx.hip"}     # (gemm_fp8 / gemm_mx / attn_mix_mx: their quantisers)
+                  "attn_mix_mx.hip", "step_cache.hip"}     # (gemm_fp8 / gemm_mx / attn_mix_mx: their quantisers)
 # translation units whose kernels keep their accumulators in AGPRs (one wave per SIMD, 512 registers)
 AGPR_SOURCES = {"gemm_v4.hip", "gemm_v5.hip", "gemm_v6.hip", "gemm_fp8_v4.hip", "gemm_fp8_v4_qkn.hip", "gemm_fp8_v4_qkn_stats.hip", "gemm_mx_v4.hip", "attn_w4.hip", "calib.hip"}
 

@@ -85,6 +85,80 @@ def mx_call_kernel(fmt, w_fmt, persistent_gemm, persistent_gemm_mxfp6=False):
     return 2 if persistent_gemm == "always" else 1
 
 
+def step_cache_distance(num, den):
+    """d = num / den of the probe's two sums; den == 0 gives inf, a NaN in either gives NaN."""
+    if den == 0.0:
+        return float("nan") if num != num else float("inf")
+    return num / den
+
+
+def step_cache_decide(num, den, has_ref, hits, threshold, max_hits):
+    """The policy of the first-block step cache (include/bya.h): re-use the block stack's residual if and only if a reference
+    exists, d = num / den < threshold and hits < max_hits (None: unbounded).  NaN compares false, threshold 0 never re-uses."""
+    if not has_ref or (max_hits is not None and hits >= max_hits):
+        return False
+    return step_cache_distance(num, den) < threshold
+
+
+def step_cache_refusal(model):
+    """Why the step cache cannot serve this model's step (None: it can): the ranks of a sequence-parallel step or of the CFG
+    rank split would have to agree on d, which is not built."""
+    if getattr(model, "_cfg", None) is not None:
+        return "the step cache is enabled under the CFG rank split: the two ranks would have to agree on the distance"
+    if getattr(model, "_seq_world", 1) != 1 or getattr(model, "_seq_group", None) is not None:
+        return "the step cache is enabled on a sequence-parallel step: the ranks would have to agree on the distance"
+    return None
+
+
+class StepCache:
+    """State of the first-block step cache (model.enable_step_cache; include/bya.h has the definition): the policy's two
+    numbers, the four stream-sized buffers (made by the engine on the first cached step of a workspace), whether ``r_ref``
+    holds the first-block residual of a fully computed step (``has_ref``), the run of re-used steps (``hits``), and the
+    counters ``step_cache_stats`` reports.  ``drop()`` forgets the reference -- the next step is full --, ``reset()`` the
+    counters too."""
+
+    def __init__(self, threshold, max_consecutive_hits=None, enabled=True):
+        self.threshold, self.max_hits, self.enabled = threshold, max_consecutive_hits, enabled
+        self.reset()
+
+    def drop(self):
+        self.has_ref, self.hits = False, 0
+        self.ws = self.E = self.r_ref = self.r_new = self.R = self.partials = self.sums = None
+        self.cond_key = self.cond_hold = None
+
+    def reset(self):
+        self.drop()
+        self.steps = self.full = self.reused = 0
+        self.distances = []
+        self._last = None
+
+    def uncount_last(self):
+        """Take the last counted step out of the counters (the pipeline re-runs it: nothing is counted twice)."""
+        if self._last is not None:
+            self.steps -= 1
+            setattr(self, self._last, getattr(self, self._last) - 1)
+            self.distances.pop()
+            self._last = None
+
+    def count(self, reused, d):
+        self._last = "reused" if reused else "full"
+        self.steps += 1
+        setattr(self, self._last, getattr(self, self._last) + 1)
+        self.distances.append(d)
+
+    def stats(self):
+        return {"steps": self.steps, "full": self.full, "reused": self.reused, "distances": list(self.distances)}
+
+
+def _flat_tensors(obj, out):
+    if torch.is_tensor(obj):
+        out.append(obj)
+    elif isinstance(obj, (list, tuple)):
+        for o in obj:
+            _flat_tensors(o, out)
+    return out
+
+
 class DenoiseEngine:
     # Identities / audio streams per sample.  The reference forward dereferences exactly id_cond[0], id_cond[1]
     # (models/transformer.py:638-639) and repeats the video twice (:784, :881); everything else in it (router, perceiver,
@@ -245,6 +319,8 @@ class DenoiseEngine:
         self._inv_cache = {}
         self._cache_generation += 1
         self.m._graphs = {}
+        if getattr(self.m, "_step_cache", None) is not None:
+            self.m._step_cache.drop()                  # its residuals came out of the old weights: the next step is full
         return True
 
     # ------------------------------------------------------------------------------------------ packing
@@ -779,13 +855,26 @@ class DenoiseEngine:
     def _step(self, hidden_states, encoder_hidden_states, timestep, image_rotary_emb, id_cond, id_vit_hidden,
               audio_embeds, af_matrix, routing_logits_forcing, taps=None):
         """The step's table of contents: one context, the stages in order, the block loop, the head.  ``taps`` (a dict) is
-        filled with clones of the intermediate tensors (and keeps the cross-attentions on their unfused paths)."""
+        filled with clones of the intermediate tensors (and keeps the cross-attentions on their unfused paths).  With the
+        first-block step cache on (model.enable_step_cache; a ``taps`` run bypasses it and leaves its state alone) the loop is
+        cut behind block 0: the probe there decides between blocks 1..L-1 and the cached residual of the block stack."""
         m = self.m
+        sc = getattr(m, "_step_cache", None) if taps is None else None
+        if sc is not None and not sc.enabled:
+            sc = None
+        if sc is not None and step_cache_refusal(m) is not None:
+            raise NotImplementedError(step_cache_refusal(m))
         c = self._step_context(hidden_states, encoder_hidden_states, timestep, image_rotary_emb, id_cond, audio_embeds, taps)
+        if sc is not None and c.sh.active:
+            raise NotImplementedError("the step cache is enabled on a sequence-parallel step: the ranks would have to agree on "
+                                      "the distance")
         self._conditioning(c, id_cond, id_vit_hidden, audio_embeds, af_matrix, routing_logits_forcing)
         self._adaln_vector(c)
         self._patch_embed(c)
         attention = self._block_buffers(c)
+        if sc is not None:
+            self._step_cache_begin(c, sc, (encoder_hidden_states, id_cond, id_vit_hidden, audio_embeds, af_matrix,
+                                           routing_logits_forcing))
         for i, blk in enumerate(m.transformer_blocks):
             # ---- D2..D4: CogVideoXBlock (models/transformer.py:223-262)
             xq, gated = self._adaln(c, i, 0, blk.norm1)
@@ -798,7 +887,46 @@ class DenoiseEngine:
                 self._face_routing(c, i, i // m.cross_attn_interval)
             if c.use_audio and i % m.audio_attn_interval == 0:
                 self._audio_injection(c, i, i // m.audio_attn_interval)
+            if sc is not None and i == 0 and self._step_cache_probe(c, sc):
+                break                                  # a re-used step: x already holds block 0's output + the cached residual
+        if sc is not None and sc._last == "full":
+            self._step_cache_capture(c, sc)
         return self._head(c)
+
+    def _step_cache_begin(self, c, sc, conditioning):
+        """Step cache, in front of block 0: drop the state where it cannot serve this step -- another workspace (geometry,
+        batch, identities), other conditioning inputs than the reference was taken under (their ``_key``; the inputs are kept
+        alive so that a pointer cannot come back as another tensor) --, make the buffers, and snapshot x into ``E``."""
+        cond = _flat_tensors(conditioning, [])
+        key = _key(cond)
+        if sc.ws is not self._ws or sc.cond_key != key:
+            sc.drop()
+            sc.ws, sc.cond_key, sc.cond_hold = self._ws, key, cond
+            new = lambda: torch.empty_like(c.x)
+            sc.E, sc.r_ref, sc.r_new, sc.R = new(), new(), new(), new()
+            plan = ops.step_cache_probe_plan(c.x, sc.E, None, sc.r_new)
+            sc.partials = torch.empty(plan["partials_bytes"] // 8, dtype=torch.float64, device=self.dev)
+            sc.sums = torch.empty(2, dtype=torch.float64, device=self.dev)
+        ops.step_cache_snapshot(c.x, sc.E)
+
+    def _step_cache_probe(self, c, sc):
+        """Step cache, behind block 0: the probe, the host's read of its two sums (the step's one synchronisation) and the
+        decision.  -> True for a re-used step: the cached residual is applied to x and blocks 1..L-1 do not run."""
+        ops.step_cache_probe(c.x, sc.E, sc.r_ref if sc.has_ref else None, sc.r_new, sc.partials, sc.sums)
+        num, den = sc.sums.tolist()
+        reuse = step_cache_decide(num, den, sc.has_ref, sc.hits, sc.threshold, sc.max_hits)
+        sc.count(reuse, step_cache_distance(num, den))
+        if reuse:
+            ops.step_cache_apply(c.x, sc.R)
+            sc.hits += 1
+        return reuse
+
+    def _step_cache_capture(self, c, sc):
+        """Step cache, behind the last block of a full step: R = x - (x after block 0); this step's first-block residual
+        becomes the reference."""
+        ops.step_cache_capture(c.x, sc.E, sc.R)
+        sc.r_ref, sc.r_new = sc.r_new, sc.r_ref
+        sc.has_ref, sc.hits = True, 0
 
     def _step_context(self, hidden_states, encoder_hidden_states, timestep, image_rotary_emb, id_cond, audio_embeds, taps):
         """-> the context the stages of this step share (a plain namespace): the geometry; the rank's shard ``sh`` with its row

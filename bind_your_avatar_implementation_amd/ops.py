@@ -1587,6 +1587,69 @@ def act_add_plan(x, out, act=None, res=None):
     return _plan(_act_call(x, out, act, res, True), False, _hip.StepPlan, lambda p: _step_plan(p, "act_add"))
 
 
+# ---- the first-block step cache (include/bya.h, "First-block step cache"): three streaming passes over the joint stream
+def _cache_tensors(plan, n, **tensors):
+    """The bf16 operands of a step-cache pass: contiguous, n elements each (None passes where the entry point allows it)."""
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if t.dtype != torch.bfloat16 or not t.is_contiguous() or t.numel() != n:
+            raise ValueError(f"{name}: expected a contiguous bf16 tensor of {n} elements")
+        if not (t.is_cuda or (plan and t.is_meta)):
+            raise ValueError(f"{name}: expected a device tensor (the engine has no CPU path)")
+
+
+def _probe_call(x, E, r_ref, r_new, partials, sums, plan):
+    ptr = _plan_p if plan else _p
+    n = x.numel()
+    _cache_tensors(plan, n, x=x, E=E, r_ref=r_ref, r_new=r_new)
+    head = (ptr(x), ptr(E), ptr(r_ref), ptr(r_new))
+    if plan:
+        return "bya_step_cache_probe", (*head, n)
+    for name, t, least in (("partials", partials, step_cache_probe_plan(x, E, r_ref, r_new)["partials_bytes"] // 8), ("sums", sums, 2)):
+        if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() < least:
+            raise ValueError(f"{name}: expected a contiguous fp64 device tensor of at least {least} elements")
+    return "bya_step_cache_probe", (*head, _p(partials), _p(sums), n)
+
+
+def step_cache_probe(x, E, r_ref, r_new, partials, sums):
+    """The probe of the first-block step cache: r_new = bf16(x - E), E <- x, sums[0] = sum |r_new - r_ref| and sums[1] =
+    sum |r_ref| in fp64 (both 0 where ``r_ref`` is None), through ``partials`` (fp64, ``step_cache_probe_plan``'s
+    "partials_bytes") and a one-workgroup finish launch: the same inputs give the same 16 bytes.  Returns ``sums``."""
+    _launch(None, None, 0.0, _probe_call(x, E, r_ref, r_new, partials, sums, False))
+    return sums
+
+
+def step_cache_probe_plan(x, E, r_ref, r_new):
+    """What ``step_cache_probe`` (and, on the same grid, ``step_cache_capture`` / ``step_cache_apply``) would launch (meta
+    tensors will do): {"grid", "vec" (bf16 per lane and pass), "wg_pass_elems", "passes" of workgroup 0, "partials_bytes"}."""
+    return _plan(_probe_call(x, E, r_ref, r_new, None, None, True), False, _hip.StepCachePlan,
+                 lambda p: {"grid": p.grid, "vec": p.vec, "wg_pass_elems": p.wg_pass_elems, "passes": p.passes,
+                            "partials_bytes": p.partials_bytes})
+
+
+def step_cache_capture(x, E, R):
+    """R = bf16(x - E): the residual of blocks 1..L-1 behind a full step (``E`` holds x after block 0).  Returns ``R``."""
+    _cache_tensors(False, x.numel(), x=x, E=E, R=R)
+    _launch(None, None, 0.0, ("bya_step_cache_capture", (_p(x), _p(E), _p(R), x.numel())))
+    return R
+
+
+def step_cache_apply(x, R):
+    """x = bf16(x + R) in place: a re-used step's stand-in for blocks 1..L-1.  Returns ``x``."""
+    _cache_tensors(False, x.numel(), x=x, R=R)
+    _launch(None, None, 0.0, ("bya_step_cache_apply", (_p(x), _p(R), x.numel())))
+    return x
+
+
+def step_cache_snapshot(x, E):
+    """E <- x, the device copy in front of block 0, under a kernel-timer label of its own like every launch of the step."""
+    tok = _begin("step_cache_snapshot")
+    E.copy_(x)
+    _end(tok)
+    return E
+
+
 def _sched_pred(pred, n):
     """-> (n_pred, pred_stride) of a prediction [1 or 2, ...]: the rows may be rows of a wider buffer (stride(0) >= n)."""
     n_pred = pred.shape[0] if pred.numel() != n else 1

@@ -167,11 +167,15 @@ def _self_healing_step(tr, dev, predict):
     A split-K / stream-K hand-off of the step timed out (the GPU is shared: the grids were not co-resident): the library is in
     its unsplit mode now -- compute the step again instead of failing the clip at its end.  A captured graph (use_hip_graph)
     still holds the very launches that timed out: drop them first, the re-run captures under the healed options.  The re-run is
-    checked like any step: time-outs behind it have no clean step to stand on, so the clip fails here."""
+    checked like any step: time-outs behind it have no clean step to stand on, so the clip fails here.  The step cache
+    (transformer.enable_step_cache) is reset first as well: the re-run is a full step, and the step is counted once."""
     from . import ops
     noise = predict()
     if ops.heal_handoffs(dev):
         tr._graphs = {}
+        reset = getattr(tr, "reset_step_cache", None)
+        if reset is not None:
+            reset(uncount_last=True)
         noise = predict()
         if ops.heal_handoffs(dev):
             raise ops._hip.ByaError("a split-K / stream-K hand-off timed out again in the step that was re-run in the unsplit mode: "
@@ -284,6 +288,8 @@ class BindyouravatarPipeline:
         old_x0 = None
         # the identities and the audio do not change between steps: face tokens, audio context and their K/V once
         tr.precompute_conditioning(id_cond, id_vit_hidden, audio_embs, lat_frames)
+        if hasattr(tr, "reset_step_cache"):
+            tr.reset_step_cache()                # a clip starts with a full step and its own step_cache_stats()
         # one synchronisation per step (~0.35 s of GPU work each): the hand-off counters of the split kernels (ops.heal_handoffs).
         # Unsharded runs only -- ranks of a sharded step would have to agree to repeat it; they keep the end-of-clip check.
         heal = (torch.device(dev).type == "cuda" and getattr(tr, "_seq_world", 1) == 1 and getattr(tr, "_cfg", None) is None

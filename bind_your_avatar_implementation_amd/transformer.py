@@ -327,6 +327,7 @@ class BindyouravatarTransformer3DModel(nn.Module):
         # opt-in, read when the engine is built (set it before the first call, or call invalidate_engine()): a batch of
         # B >= 2 samples runs the face / audio kv-mix and the router's scores and head as ONE launch per layer (BYA_BATCH_LAUNCHES)
         self.batch_launches = False
+        self._step_cache = None        # enable_step_cache: the first-block step cache's policy and state (engine.StepCache)
 
     # ---- API the reference pipeline touches -------------------------------------------------------
     @property
@@ -489,10 +490,61 @@ class BindyouravatarTransformer3DModel(nn.Module):
         self.invalidate_engine()
         return self
 
+    def enable_step_cache(self, threshold, *, max_consecutive_hits=None, enabled: bool = True):
+        """First-block step cache (include/bya.h "First-block step cache"; no reference counterpart, off
+        by default): every step runs block 0 and measures d = sum |r_new - r_ref| / sum |r_ref| of its first-block residual
+        against the last fully computed step's; a step with d < ``threshold`` -- and fewer than ``max_consecutive_hits`` re-used
+        steps in a row before it (None: unbounded) -- adds that step's residual of the whole block stack to the stream instead of
+        running blocks 1..L-1.  ``threshold`` has no default: none is defensible without a trained checkpoint (0 never re-uses,
+        inf always where a reference exists).  One host synchronisation per step; four stream-sized buffers.  The state is
+        dropped (the next step is full) when the geometry, batch or identity count changes, when the conditioning inputs are
+        other tensors than the reference was taken under, on ``invalidate_engine()`` / an in-place weight edit and on
+        ``reset_step_cache()``.  A sequence-parallel step and the CFG rank split refuse the mode (NotImplementedError).  With
+        ``use_hip_graph`` on, ``forward`` takes the eager path while the cache is enabled: the decision is the host's, a graph
+        cannot branch on it -- nothing about capture or replay changes.  ``enabled=False`` switches the mode off.  Returns self."""
+        from .engine import StepCache
+        if not isinstance(enabled, bool):
+            raise TypeError(f"enabled: expected a bool, got {type(enabled).__name__}")
+        if not enabled:
+            self._step_cache = None
+            return self
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+            raise TypeError(f"threshold: expected a number, got {type(threshold).__name__}")
+        if not threshold >= 0:                       # (NaN too)
+            raise ValueError(f"threshold: expected a number >= 0 (0 never re-uses, inf always), got {threshold}")
+        if max_consecutive_hits is not None:
+            if isinstance(max_consecutive_hits, bool) or not isinstance(max_consecutive_hits, int):
+                raise TypeError(f"max_consecutive_hits: expected an int or None, got {type(max_consecutive_hits).__name__}")
+            if max_consecutive_hits < 0:
+                raise ValueError(f"max_consecutive_hits: expected None or an int >= 0, got {max_consecutive_hits}")
+        self._step_cache = StepCache(float(threshold), max_consecutive_hits)
+        return self
+
+    def reset_step_cache(self, *, uncount_last: bool = False):
+        """Forget the step cache's reference and zero its counters: the next step is a full step (the pipeline calls this at the
+        start of a clip).  ``uncount_last``: keep the counters but take the last step out of them -- for a caller that runs that
+        step again (the pipeline's healed re-run), so that nothing is counted twice.  A no-op while the cache is off."""
+        sc = self._step_cache
+        if sc is not None:
+            if uncount_last:
+                sc.uncount_last()
+                sc.drop()
+            else:
+                sc.reset()
+        return self
+
+    def step_cache_stats(self):
+        """{"steps", "full", "reused", "distances"} since the last ``reset_step_cache()``: the cached steps run, how many ran
+        every block, how many re-used the residual, and each step's distance d (inf for a step without a reference).  None while
+        the cache is off."""
+        return None if self._step_cache is None else self._step_cache.stats()
+
     def invalidate_engine(self):
         """Drop packed weights / workspaces / captured graphs (call after changing parameters in place)."""
         self._engine = None
         self._graphs = {}
+        if getattr(self, "_step_cache", None) is not None:
+            self._step_cache.drop()            # (its residuals came out of the old weights; the counters stay)
 
     def load_state_dict(self, *a, **kw):
         out = super().load_state_dict(*a, **kw)
@@ -572,7 +624,8 @@ class BindyouravatarTransformer3DModel(nn.Module):
         if cfg is not None and hidden_states.shape[0] == 2:
             # CFG batch split: this rank computes one sample, the pair exchange restores the [uncond, cond] batch
             return (cfg.join(self._engine.step(*cfg.take(args))), None, None, None, None)
-        if self.use_hip_graph and torch.is_tensor(timestep) and self._graph_capturable():
+        cached = self._step_cache is not None and self._step_cache.enabled       # (the host decides mid-step: eager)
+        if self.use_hip_graph and not cached and torch.is_tensor(timestep) and self._graph_capturable():
             out = self._graphed_step(args)
         else:
             out = self._engine.step(*args)

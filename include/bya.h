@@ -971,6 +971,57 @@ int bya_act_add_plan(const void* x, const void* r, const void* y, int64_t n, int
                      bya_step_plan_info* plan);                  /* see bya_step_plan_info */
 
 /* ---------------------------------------------------------------------------------------------
+ * First-block step cache (an opt-in mode of this engine; the reference has none.  DESIGN.md section 19).
+ * Consecutive denoise steps change the token stream little: a step whose first block moved the stream by nearly what it moved
+ * it in the last fully computed step re-uses that step's residual of the WHOLE block stack instead of running blocks 1..L-1.
+ *
+ * x is the resident joint stream [B, S, D] bf16 (text rows first), n = B S D.  "Block 0" is iteration 0 of the step's block
+ * loop, its face routing and audio injection included.  Buffers of n bf16 each: the snapshot E, the first-block residuals
+ * r_ref (of the last FULLY COMPUTED step) and r_new (of this step), and the block-stack residual R.  Every step:
+ *   1. after the patch embed                E <- x                                  (a device copy)
+ *   2. block 0 runs
+ *   3. PROBE, one pass (bya_step_cache_probe):
+ *        r_new = bf16_rne(float(x) - float(E));   E <- x   (E now holds x after block 0)
+ *        (bf16_rne: round to nearest even; every NaN becomes the quiet NaN 0x7fc0, so that the written bits are a function of
+ *        the values alone -- converters disagree on a NaN's bits, torch's own scalar and vectorised ones among them)
+ *        num = sum |float(r_new) - float(r_ref)|,  den = sum |float(r_ref)|   over all n elements; r_new enters as stored
+ *        (rounded).  Terms in fp32, accumulation in fp64 in an order fixed by n alone: a lane adds its terms in pass order,
+ *        a workgroup its lanes in a fixed tree, the workgroups' partials land in fixed slots (partials[2 g], [2 g + 1]) and a
+ *        one-workgroup finish launch adds them in index order into sums[0] = num, sums[1] = den.  No floating-point atomics:
+ *        the same inputs give the same 16 bytes on every run.  r_ref == NULL (no reference yet): r_new and E are written,
+ *        both sums are 0.
+ *   4. the host reads the two doubles (one synchronisation), d = num / den (den == 0: inf), and RE-USES the residual if and
+ *      only if a reference exists, d < threshold and hits < max_consecutive_hits (none: unbounded).  NaN compares false: a
+ *      full step.  threshold = 0 never re-uses.
+ *   5. FULL step:    blocks 1..L-1 run; CAPTURE R = bf16_rne(float(x) - float(E)) (bya_step_cache_capture); r_ref and r_new
+ *                    swap; hits = 0.
+ *      RE-USED step: APPLY x = bf16_rne(float(x) + float(R)) in place (bya_step_cache_apply; x holds block 0's output);
+ *                    hits += 1; r_ref and R stay.
+ *   6. the head runs as always.
+ * The whole batch decides jointly (both halves of a guided step's [uncond, cond] pair skip together).
+ *
+ * The three entry points are HBM-bound streaming passes: 16-byte loads and stores, eight bf16 per lane, a grid-stride walk of
+ * grid = min(2048, ceil(n / 2048)) workgroups of 256 lanes -- a function of n alone.  Tensors are contiguous and 16-byte
+ * aligned (partials, sums: 8 bytes), n % 8 == 0: else BYA_ERR_SHAPE (a missing pointer, n <= 0, n % 8) or BYA_ERR_ALIGN with
+ * nothing launched.  They never allocate and never synchronise.  partials is the caller's: partials_bytes of the plan query
+ * (2 doubles per workgroup).  bya_step_cache_probe_plan answers for all three (they share the grid); the plan is untouched on
+ * rejection (plan == NULL: BYA_ERR_SHAPE).
+ * --------------------------------------------------------------------------------------------- */
+typedef struct bya_step_cache_plan_info {
+    int32_t grid;             /* workgroups of the probe, the capture and the apply */
+    int32_t vec;              /* bf16 per lane and pass: 8 (one 16-byte vector) */
+    int32_t wg_pass_elems;    /* elements a workgroup takes per pass of its walk: 2048 */
+    int32_t passes;           /* passes of workgroup 0: ceil(n / (grid wg_pass_elems)) */
+    int64_t partials_bytes;   /* what the probe needs behind `partials`: 16 grid */
+} bya_step_cache_plan_info;
+int bya_step_cache_probe(const void* x, void* E, const void* r_ref, void* r_new, double* partials, double* sums, int64_t n,
+                         hipStream_t stream);
+int bya_step_cache_probe_plan(const void* x, const void* E, const void* r_ref, const void* r_new, int64_t n,
+                              bya_step_cache_plan_info* plan);
+int bya_step_cache_capture(const void* x, const void* E, void* R, int64_t n, hipStream_t stream);
+int bya_step_cache_apply(void* x, const void* R, int64_t n, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Row-stationary GEMM for K = 512 with optional fused LayerNorm, GELU(erf) and residual:
  *     C[M,N] = res + act( LN?(X)[M,512] . W[N,512]^T + bias )
  * Replaces, inside every SpatialTemporalAttentionBlock of the Embedding Router (models/router.py:468-493), the
